@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """bench.py - HDR-merged Mpix/s and fraction of the HBM roofline on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 A step = one fused merge launch over one synthetic exposure stack that is already resident in HBM.
 Workload (BASELINE.json configs[1], the one the metric is quoted on): 7 x 4096 x 4096 x 3 uint8 frames
 + 256-entry ICRF, val-only merge -> float64 radiance. FOUR distinct stacks are resident and merged round-robin, so
-no launch re-reads the inputs of the one before it (cold inputs; the figure for re-merging ONE stack is reported beside
-it as roofline.same_stack_*). At N > 1 every rank merges its own stacks of the same size (independent units, no
-data-path collective; "weak" scaling); value = all ranks' pixels / max-over-ranks time. The roofline block prices the
-kernel hm_merge dispatches to (its name comes from the library: hm_merge_describe) from its average launch duration
-measured with HIP events on the launch stream inside the timed region; the cpu_baseline block times the NumPy oracle
-(a port of the reference's merge arithmetic) on a bounded row band of the same stack on the host, rank 0, N = 1 only,
-and checks the GPU output of the timed configuration against it.
+no launch re-reads the inputs of the one before it (cold inputs). At N > 1 every rank merges its own stacks of the same size
+(independent units, no data-path collective; "weak" scaling); value = all ranks' pixels / max-over-ranks time. The roofline
+block prices the kernel hm_merge dispatches to (its name comes from the library: hm_merge_describe) from its average launch
+duration measured with HIP events on the launch stream inside the timed region.
+A plain run does only that: set-up, pre-warm, warm-up, the K timed steps, the result line. --full adds what takes runs or
+work of its own: the cpu_baseline block (the NumPy oracle - a port of the reference's merge arithmetic - timed on a bounded
+row band of the same stack on the host, rank 0, N = 1 only, with a parity check of the GPU output of the timed configuration
+against it; --no-cpu-baseline leaves it out again) and, for the merges, roofline.same_stack_* (re-merging ONE stack),
+roofline.isolated_launch_us_min_median and roofline.copy_GBps / frac_of_copy; without --full these read null.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy before the line is printed
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared array for array (welford
+folds into one running state, which also counts the time-based pre-warm launches: compare its dumps with --prewarm-s 0).
 Other workloads (--workload): cfg3* = configs[2] and its parts, cfg4 / cfg4std = configs[3] (ONE 15 x 8192 x 8192 x 3 image
 in 8 row tiles dealt to the ranks, host-side assembly), cfg5 = configs[4], cfg2rand, cfg2smooth, cfg2f64 / cfg3f64std, welford, energy, linearity / linearitystd.
 """
@@ -113,6 +118,30 @@ def rank_report(dist, a, dev, elapsed, avg_us):
 
 
 DARK_THR = 0.05                 # pixel threshold of the dark maps (settings.DARK_THRESHOLD)
+DUMP_BYTES = 60_000_000         # --dump-outputs: bytes of array data written in all (the files stay under 64 MB)
+
+
+def cpu_leg_on(a, rank=0, world=1):
+    """The cpu_baseline leg (oracle timing + parity check) runs only under --full, on rank 0 of a one-rank run."""
+    return a.full and not a.no_cpu_baseline and rank == 0 and world == 1
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy, float64 (float32 stays float32). DUMP_BYTES are shared evenly by the
+    arrays; an array larger than its share is written as a fixed sample of its flattened elements: the sorted distinct indices of
+    a NumPy generator seeded with 0, the same for every run with the same shapes."""
+    out = pathlib.Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, x in arrays.items():
+        x = x.detach()
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.to(torch.float64)
+        cap = share // x.element_size()
+        if x.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, x.numel(), cap))
+            x = x.reshape(-1)[torch.as_tensor(idx, device=x.device)]
+        np.save(out / f"{name}.npy", x.cpu().numpy())
 
 
 # ---- counter records (tools/profile.sh -> tools/summarize_profile.py -> profiles/r04_pmc_counters.json) --------------------------------
@@ -277,6 +306,8 @@ def row_tile_workload(a, dev, rank, world, dist):
     barrier()
     elapsed = time.perf_counter() - t0
     avg_us = ev0.elapsed_time(ev1) * 1e3 / a.steps / max(n_launch, 1)
+    if a.dump_outputs and rank == 0:                    # this rank's tiles as the last step left them (before the assembly)
+        dump_outputs(a.dump_outputs, {f"tile{t_}_{k}": v for t_ in tiles.mine for k, v in tiles.plans[t_].outputs.items()})
     elapsed, ranks = rank_report(dist, a, dev, elapsed, avg_us)
     # host-side assembly of the image (once, untimed for `value`)
     # the CPU group of the assembly (segment name, shape agreement, barrier): a gloo group inside the nccl world - also at world
@@ -291,7 +322,7 @@ def row_tile_workload(a, dev, rank, world, dist):
     val, std = tiles.assemble(group=gloo, dst=0)        # steady state: D2H of every tile into its rows of the pinned image (+ the sends)
     assembly_ms = (time.perf_counter() - ta) * 1e3
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if cpu_leg_on(a, rank, world):
         from oracle import hdr_oracle as orc
         rows = a.cpu_rows if a.cpu_rows > 0 else (192 if with_std else 384)
         tile = n_tiles // 2 if n_tiles // 2 in tiles.mine else tiles.mine[0]           # an interior tile (row0 = 4096)
@@ -345,7 +376,7 @@ def producer_workload(a, dev, rank=0, world=1, dist=None):
     between two events) and a cpu_baseline leg = the oracle on a bounded sample (N = 1 only). At N > 1 every rank runs its own
     replica of the workload (no exchange step: "replicas only"). Rank 0 prints one JSON line."""
     from camera_linearity_amd import engine, _native as nat
-    steps, warmup = min(a.steps, 50), min(a.warmup, 5)
+    steps, warmup = a.steps, a.warmup
     if a.workload == "welford":
         H, W, K = 4096, 4096, 32
         g = torch.Generator(device=dev).manual_seed(1)
@@ -353,6 +384,7 @@ def producer_workload(a, dev, rank=0, world=1, dist=None):
         mean = torch.zeros((H, W, 3), dtype=torch.float64, device=dev)
         m2 = torch.zeros_like(mean)
         launch = lambda: engine.welford_update(clip, 5, mean, m2)                       # noqa: E731
+        outputs = lambda _: {"mean": mean, "m2": m2}       # noqa: E731  (the state the last fold left; it depends on how many folds ran)
         alg = int(nat.lib.hm_welford_algorithmic_bytes(K, 1, H * W * 3))
         units, unit, metric = H * W * K, "Mpix-frames/s", "Welford-folded Mpix-frames/s (mean + M2, 32 frames per launch)"
         cfg = {"workload": f"{K} uint8 4096x4096x3 frames folded into float64 mean / M2 per launch", "name": "welford"}
@@ -369,6 +401,7 @@ def producer_workload(a, dev, rank=0, world=1, dist=None):
         icrfs[:, -1] = 1.0
         icrfs_d = torch.as_tensor(icrfs, device=dev)
         launch = lambda: engine.linearity_energy(dn, None, t, icrfs_d, 5, 250)          # noqa: E731
+        outputs = lambda e: {"energy": e}                   # noqa: E731
         alg = X * Y * N * B                                                              # stack bytes x candidates
         units, unit, metric = B, "candidates/s", "ICRF-calibration energy evaluations/s (1024x1024x7 stack, 75 candidates per launch)"
         cfg = {"workload": "energy function of 75 candidate ICRFs on a 1024x1024x7 uint8 channel stack per launch", "name": "energy"}
@@ -391,18 +424,20 @@ def producer_workload(a, dev, rank=0, world=1, dist=None):
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(steps):
-        launch()
+        last = launch()
     ev1.record()
     barrier()
     elapsed = time.perf_counter() - t0
     avg_us = ev0.elapsed_time(ev1) * 1e3 / steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs(last))
     elapsed, ranks = rank_report(dist, a, dev, elapsed, avg_us)
     if dist is not None:
         dist.destroy_process_group()
     if rank != 0:
         return
     cpu = None
-    if not a.no_cpu_baseline and world == 1:
+    if cpu_leg_on(a, rank, world):
         from oracle import hdr_oracle as orc
         if a.workload == "welford":
             rows_c = 2048
@@ -495,7 +530,7 @@ def linearity_workload(a, dev, rank=0, world=1, dist=None):
     # the band the CPU leg compares, linearized BEFORE anything is thresholded in place
     cpu = None
     band_stats = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if cpu_leg_on(a, rank, world):
         bv, bs = linearized(slice(0, rows_cpu))
         band_host = ([v.cpu().numpy() for v in bv], None if bs is None else [x.cpu().numpy() for x in bs])
         band_stats = engine.pairs_statistics(bv, bs, pairs, to_host=True, thresholds=(lo, hi))
@@ -507,7 +542,7 @@ def linearity_workload(a, dev, rank=0, world=1, dist=None):
     torch.cuda.synchronize()
     E = H * W * 3
     alg = n * 8 * (2 if use_std else 1) * E             # every frame (and std) byte once
-    steps, warmup = min(a.steps, 100), min(a.warmup, 10)
+    steps, warmup = a.steps, a.warmup
     # untimed clock pre-warm: this kernel is FP64-VALU bound, so its time IS the shader clock - and after the seconds of host-side set-up
     # above the clock needs ~2 s of load to settle (0.5 s of pre-warm measured 2 790-3 575 us per launch, 3 s 2 457-2 460 us on the same
     # box in the same call: tools/lin_var.sh, profiles/r04_lin_prewarm.log). The HBM-bound merges settle within the default 0.5 s.
@@ -529,11 +564,14 @@ def linearity_workload(a, dev, rank=0, world=1, dist=None):
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(steps):
-        launch()
+        last = launch()
     ev1.record()
     barrier()
     elapsed = time.perf_counter() - t0
     avg_us = ev0.elapsed_time(ev1) * 1e3 / steps
+    if a.dump_outputs and rank == 0:                    # per statistic: (pairs, channels), pairs in the order of `pairs`
+        dump_outputs(a.dump_outputs, {f"{kind}_{key}": torch.stack([p_[i][key] for p_ in last]) for i, kind in enumerate(("abs", "rel"))
+                                      for key in ("mean", "std") + (("error",) if use_std else ())})
     elapsed, ranks = rank_report(dist, a, dev, elapsed, avg_us)
     if dist is not None:
         dist.destroy_process_group()
@@ -586,7 +624,11 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS) + ["cfg4", "cfg4std", "welford", "energy", "linearity", "linearitystd"])
     ap.add_argument("--stacks", type=int, default=0, help="distinct resident stacks merged round-robin (0 = 4 for cfg2 / cfg2rand, 2 for the cfg3 family, 1 otherwise)")
     ap.add_argument("--variant", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the measurements and checks beyond the headline: cpu_baseline (oracle timing + parity), "
+                                                           "same-stack, isolated-launch and copy-rate figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                                                                          "(float64, at most 64 MB in all: a fixed sample of larger arrays)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the default) or gloo (rehearsal of the N > 1 path on one GPU)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal only: initialise the process group even at world size 1")
@@ -715,12 +757,13 @@ def main():
         for _ in range(50):
             step()
         torch.cuda.synchronize()
+    counter[0] = 0                           # the round-robin restarts here, so the stack of every later step is fixed by the arguments
     for _ in range(a.warmup):
         step()
     # HIP events on the launch stream (torch's current stream is the one hm_merge is given), bracketing the
     # K back-to-back launches of the timed region: average launch duration = event span / K. (An event pair
     # around EVERY launch would put a barrier packet between consecutive kernels and measure a different,
-    # serialised pipeline.) A second pass after the timed region records per-launch events for min/max only.
+    # serialised pipeline.) Under --full a second pass after the timed region records per-launch events for min/max only.
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     barrier()
     t0 = time.perf_counter()
@@ -731,9 +774,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     avg_us = ev0.elapsed_time(ev1) * 1e3 / a.steps / launches_per_step      # per hm_merge call
-    # secondary figure: the same number of launches re-merging ONE stack (what round 1 reported as the headline)
+    if a.dump_outputs and rank == 0:         # the outputs of the stack(s) the last timed step merged
+        if launches_per_step > 1:
+            dump_outputs(a.dump_outputs, {f"stack{i}_{k}": v for i, p_ in enumerate(plans) for k, v in p_.outputs.items()})
+        else:
+            dump_outputs(a.dump_outputs, plans[(counter[0] - 1) % len(plans)].outputs)
+    # --full, secondary figure: the same number of launches re-merging ONE stack (what round 1 reported as the headline)
     same_us = None
-    if len(plans) > 1 and launches_per_step == 1:
+    if a.full and len(plans) > 1 and launches_per_step == 1:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(5):
             plan.launch()
@@ -743,14 +791,16 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         same_us = e0.elapsed_time(e1) * 1e3 / a.steps
-    per = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(a.steps, 20))]
-    for e0, e1 in per:
-        e0.record()
-        plan.launch()
-        e1.record()
-    torch.cuda.synchronize()
-    kernel_us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in per]
-    # the box's copy rate (the library's nontemporal 16-byte copy kernel between two output buffers, after the timed region): the merge's
+    kernel_us = None
+    if a.full:
+        per = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(a.steps, 20))]
+        for e0, e1 in per:
+            e0.record()
+            plan.launch()
+            e1.record()
+        torch.cuda.synchronize()
+        kernel_us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in per]
+    # --full: the device's copy rate (the library's nontemporal 16-byte copy kernel between two output buffers, after the timed region): the merge's
     # traffic is ~half reads, ~half writes, and a plain copy is what the memory system sustains for such a mix
     copy_gbps = None
     pair_ = None
@@ -758,7 +808,7 @@ def main():
         pair_ = (plans[0].outputs["val"], plans[1].outputs["val"])
     elif "val" in plans[0].outputs and "std" in plans[0].outputs:
         pair_ = (plans[0].outputs["val"], plans[0].outputs["std"])
-    if rank == 0 and pair_ is not None:
+    if a.full and rank == 0 and pair_ is not None:
         from camera_linearity_amd import _native as nat
         src, dst = pair_
         nbytes = src.numel() * 8
@@ -780,7 +830,7 @@ def main():
 
     # CPU leg + parity check of the timed configuration against the oracle on a row band (not timed on the GPU side)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if cpu_leg_on(a, rank, world):
         frames, stds, t = stack0["frames"], stack0["stds"], stack0["t"]
         rows = min(a.cpu_rows if a.cpu_rows > 0 else (4096 if not with_std and not corr else 512), H)
         if "f64" in a.workload:
@@ -812,7 +862,8 @@ def main():
                          "avg_launch_us": round(avg_us, 2),
                          "same_stack_avg_launch_us": None if same_us is None else round(same_us, 2),
                          "same_stack_frac": None if same_us is None else round(alg_bytes / same_us / 1e3 / HBM_PEAK_GBPS, 4),
-                         "isolated_launch_us_min_median": [round(float(np.min(kernel_us)), 2), round(float(np.median(kernel_us)), 2)],
+                         "isolated_launch_us_min_median": None if kernel_us is None else [round(float(np.min(kernel_us)), 2),
+                                                                                          round(float(np.median(kernel_us)), 2)],
                          "copy_GBps": None if copy_gbps is None else round(copy_gbps, 1),
                          "frac_of_copy": None if copy_gbps is None else round(achieved / copy_gbps, 4)},
             "ranks": ranks,

@@ -139,6 +139,46 @@ def test_bench_nccl_world_of_one(workload):
         assert line["assembly_ms"] > 0
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line reports exactly K timed steps and none of the
+    --full figures; DIR holds the seeded sample of the last step's radiance, which is the oracle's merge of the bench's own stack
+    (regenerated here), and a second run writes the same array."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import json
+    import bench
+    from camera_linearity_amd.synthetic import synthetic_icrf, synthetic_stack_device
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-s", "0.05", "--stacks", "1"]
+    runs = []
+    for d in ("a", "b"):
+        out = _bench(args + ["--dump-outputs", str(tmp_path / d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        runs.append(json.loads(lines[0]))
+    line = runs[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    assert line["metric"] == "HDR-merged Mpix/s (node)" and line["unit"] == "Mpix/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    r = line["roofline"]
+    assert r["same_stack_avg_launch_us"] is None and r["isolated_launch_us_min_median"] is None and r["copy_GBps"] is None
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["val.npy"]
+    assert (tmp_path / "a" / "val.npy").stat().st_size <= 64e6
+    v = np.load(tmp_path / "a" / "val.npy")
+    assert v.dtype == np.float64 and np.array_equal(v, np.load(tmp_path / "b" / "val.npy"))
+    n, H, W = 7, 4096, 4096
+    idx = np.unique(np.random.default_rng(0).integers(0, H * W * 3, bench.DUMP_BYTES // 8))
+    assert v.shape == idx.shape
+    pick = np.random.default_rng(5).choice(idx.size, 20000, replace=False)
+    pix, ch = idx[pick] // 3, idx[pick] % 3
+    frames, _, t = synthetic_stack_device(7, n, H, W, device="cuda")          # stack 0 of rank 0: seed 7
+    pix_d = torch.as_tensor(pix, device="cuda")
+    fh = [f.reshape(-1, 3)[pix_d].cpu().numpy().reshape(-1, 1, 3) for f in frames]
+    del frames
+    icrf, diff = synthetic_icrf()
+    ref = orc.merge(fh, t, icrf, None)["val"][np.arange(pix.size), 0, ch]
+    np.testing.assert_allclose(v[pick], ref, rtol=1e-12, atol=0)
+
+
 def test_bench_refuses_more_ranks_than_gpus():
     """--gpus N on a node with fewer GPUs and no --share-device: every rank prints ONE line and the run exits non-zero."""
     if not torch.cuda.is_available():

@@ -424,6 +424,39 @@ def test_bench_counter_records_go_stale_with_the_kernel_source(tmp_path, monkeyp
     assert bench.valu_roofline("welford", 100.0)["frac"] is None
 
 
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (float32 kept), whole while it fits its share of DUMP_BYTES, otherwise
+    the same seeded sample of its elements on every call; the files of one call stay within the budget."""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    bench.late_imports()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 8 * 1000)
+    big = torch.arange(50_000, dtype=torch.float64).reshape(100, 500)
+    arrays = {"val": big, "small": torch.linspace(0, 1, 10, dtype=torch.float32), "count": torch.arange(7, dtype=torch.int32)}
+    bench.dump_outputs(tmp_path / "a", arrays)
+    bench.dump_outputs(tmp_path / "b", arrays)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["count.npy", "small.npy", "val.npy"]
+    for name in ("val", "small", "count"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(x, y) and x.dtype == (np.float32 if name == "small" else np.float64)
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), arrays["small"].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "count.npy"), np.arange(7.0))
+    v = np.load(tmp_path / "a" / "val.npy")                     # element k of the flat array holds k: the sample is its own index
+    assert 900 < v.size <= 1000 and np.all(np.diff(v) > 0) and v.min() >= 0 and v.max() < 50_000 and np.array_equal(v, np.round(v))
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES + 3 * 256
+
+
+def test_bench_plain_run_options():
+    """--full (the extra measurements and checks) is off by default and --dump-outputs takes a directory."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout
+    assert re.search(r'add_argument\("--full", action="store_true"', (ROOT / "bench.py").read_text())
+
+
 def test_hm_merge_survives_random_argument_structs():
     """2 000 random hm_merge_args - wrong struct sizes, negative / huge / inconsistent geometry, NULL and misaligned pointers, too many or no
     frames, both frame kinds at once, bad median sizes, NaN / zero / negative exposures - through hm_merge, hm_merge_describe and

@@ -6,5 +6,5 @@ line() { python -c "import sys,json; l=json.loads(sys.stdin.read()); r=l['roofli
 for w in cfg4tile cfg2 cfg2rand; do
 for p in base probe1 probe2 probe3; do
   if [ $p = base ]; then unset HDRMERGE_LIB; else export HDRMERGE_LIB=$PWD/camera_linearity_amd/lib/alt_$p/libhdrmerge.so; fi
-  python bench.py --workload $w --no-cpu-baseline --steps 100 > $O/r04b_${w}_$p.log 2>&1; echo -n "$w $p rc=$? "; tail -1 $O/r04b_${w}_$p.log | line
+  python bench.py --full --workload $w --no-cpu-baseline --steps 100 > $O/r04b_${w}_$p.log 2>&1; echo -n "$w $p rc=$? "; tail -1 $O/r04b_${w}_$p.log | line
 done; done

@@ -7,6 +7,6 @@ for rep in 1 2; do
 for lib in ${LIBS:-default std_early0 std_fpf0 std_waves2 std_waves4 std_fb1 std_fb4}; do
   if [ $lib = default ]; then unset HDRMERGE_LIB; else export HDRMERGE_LIB=$PWD/camera_linearity_amd/lib/alt_$lib/libhdrmerge.so; fi
   for w in ${WLS:-cfg3flat cfg3std cfg4tilestd}; do
-    python bench.py --workload $w --steps 100 --no-cpu-baseline > $O/r04f_${w}_${lib}_$rep.log 2>&1; echo -n "$rep $lib $w rc=$? "; tail -1 $O/r04f_${w}_${lib}_$rep.log | line
+    python bench.py --full --workload $w --steps 100 --no-cpu-baseline > $O/r04f_${w}_${lib}_$rep.log 2>&1; echo -n "$rep $lib $w rc=$? "; tail -1 $O/r04f_${w}_${lib}_$rep.log | line
   done
 done; done

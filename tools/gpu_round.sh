@@ -7,9 +7,9 @@ timeout -k 10 900 python -m pytest tests -q -m gpu > $O/${TAG}_pytest_gpu.log 2>
 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1; echo "smoke rc=$?"
 python tools/bench_ops.py > $O/${TAG}_bench_ops.log 2>&1; cp $O/bench_ops.json $O/${TAG}_bench_ops.json; cut -c1-200 $O/${TAG}_bench_ops.log
 python tools/bench_linearity.py 2>&1 | tee $O/${TAG}_bench_linearity.log
-python bench.py > $O/${TAG}_bench_default.log 2>&1; tail -1 $O/${TAG}_bench_default.log | cut -c1-1000
+python bench.py --full > $O/${TAG}_bench_default.log 2>&1; tail -1 $O/${TAG}_bench_default.log | cut -c1-1000
 for W in ${WORKLOADS:-cfg3 cfg3std cfg3flat cfg3hot cfg4 cfg4std cfg5 cfg2rand cfg2f64 cfg3f64std}; do
-  timeout -k 10 600 python bench.py --workload $W --steps 50 --warmup 5 > $O/${TAG}_bench_$W.log 2>&1
+  timeout -k 10 600 python bench.py --full --workload $W --steps 50 --warmup 5 > $O/${TAG}_bench_$W.log 2>&1
   python - <<PY
 import json
 try:
