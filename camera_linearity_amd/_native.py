@@ -112,6 +112,12 @@ _SIGNATURES = {
                                     C.c_int64, C.c_int, C.c_void_p]),
     "hm_welford_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hm_welford_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "hm_noise_profile_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "hm_noise_profile_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int]),
+    "hm_noise_profile_update": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_void_p]),
+    "hm_noise_profile_std": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hm_noise_profile_clean_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "hm_tiff_lzw_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]),
     "hm_tiff_packbits_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]),
     "hm_linearity_energy_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

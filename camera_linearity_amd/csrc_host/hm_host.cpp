@@ -908,6 +908,93 @@ int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uin
 }
 int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) { return n_elems * (static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16)); }
 
+// compute_noise_profiles, modules/video_processing.py:77-106: profile[m, f, c] += 1 for every frame and element (np.add.at).
+// Per thread a private (256, 256, C) count over its elements, added into the profile at the end: exact, any thread count.
+size_t hm_noise_profile_workspace_bytes(int64_t, int) { return 0; }
+int64_t hm_noise_profile_algorithmic_bytes(int n_frames, int64_t n_elems, int C) {
+    return n_elems * (static_cast<int64_t>(n_frames) + 1) + int64_t{2} * 256 * 256 * C * 8;
+}
+int hm_noise_profile_update(const void* const* frames, int n_frames, const uint8_t* mean, int64_t n_elems, int C, int64_t* profiles,
+                            void*, int64_t workspace_bytes, void*) {
+    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || n_elems < 0 || C < 1 || workspace_bytes < 0) return HM_EINVAL;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    if (n_elems % C != 0) return HM_ESHAPE;
+    if (!frames || !mean || !profiles) return HM_EINVAL;
+    for (int k = 0; k < n_frames; ++k) if (!frames[k]) return HM_EINVAL;
+    if (n_frames == 0 || n_elems == 0) return HM_OK;
+#pragma omp parallel
+    {
+        std::vector<int64_t> loc(static_cast<size_t>(256) * 256 * C, 0);
+#pragma omp for schedule(static)
+        for (int64_t e = 0; e < n_elems; ++e) {
+            int64_t* row = loc.data() + (static_cast<int64_t>(mean[e]) * 256 * C + e % C);
+            for (int k = 0; k < n_frames; ++k) row[static_cast<int64_t>(static_cast<const uint8_t*>(frames[k])[e]) * C] += 1;
+        }
+#pragma omp critical
+        for (size_t i = 0; i < loc.size(); ++i) profiles[i] += loc[i];
+    }
+    return HM_OK;
+}
+
+// _calculate_STD, video_processing.py:109-133, per (level i, channel c): over the non-zero bins h of row i with edges
+// linspace(0, 1, 256) (the caller's table), mean = sum(h * edges) / sum(h), std = sqrt(sum((edges - mean)^2 h) / sum(h));
+// an empty row gives 0 / 0 = NaN (math.sqrt of NaN: the documented deviation of the Python layer)
+int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void*) {
+    if (!profiles || !edges || !out_std || C < 1) return HM_EINVAL;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+#pragma omp parallel for schedule(static)
+    for (int t = 0; t < 256 * C; ++t) {
+        const int i = t / C, c = t % C;
+        const int64_t* row = profiles + static_cast<int64_t>(i) * 256 * C + c;
+        double cnt = 0.0, s1 = 0.0;
+        for (int b = 0; b < 256; ++b) {
+            const double h = static_cast<double>(row[b * C]);
+            if (h != 0.0) { cnt += h; s1 += h * edges[b]; }
+        }
+        const double mean = s1 / cnt;
+        double s2 = 0.0;
+        for (int b = 0; b < 256; ++b) {
+            const double h = static_cast<double>(row[b * C]);
+            if (h != 0.0) { const double dv = edges[b] - mean; s2 += (dv * dv) * h; }
+        }
+        out_std[i * C + c] = std::sqrt(s2 / cnt);
+    }
+    return HM_OK;
+}
+
+// clean_data_edges, video_processing.py:12-74: per (row i, channel c) the four integer passes centred at i, in order, in place
+static inline int64_t floordiv2(int64_t x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
+int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
+    if (!profiles || C < 1) return HM_EINVAL;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+#pragma omp parallel for schedule(static)
+    for (int t = 0; t < 256 * C; ++t) {
+        const int i = t / C, c = t % C;
+        int64_t* row = profiles + static_cast<int64_t>(i) * 256 * C + c;
+        auto D = [&](int m) -> int64_t& { return row[static_cast<int64_t>(m) * C]; };
+        const int center = i, min_dn = 0, max_dn = 255;
+        for (int m = center - 1; m > min_dn; --m) {                                       // :31-38
+            if (D(m) == 0 && D(m - 1) == 0) { for (int q = 0; q < m; ++q) D(q) = 0; break; }
+            if (D(m - 1) >= D(m) || D(m + 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
+        }
+        for (int m = center + 1; m < max_dn; ++m) {                                       // :41-48
+            if (D(m) == 0 && D(m + 1) == 0) { for (int q = m; q < 256; ++q) D(q) = 0; break; }
+            if (D(m + 1) >= D(m) || D(m - 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
+        }
+        for (int m = min_dn + 1; m < center;) {                                           // :51-58
+            if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m - 1);
+            else if (D(m) == D(m + 1) && D(m) != 0) { D(m + 1) += 1; m -= 1; }
+            m += 1;
+        }
+        for (int m = max_dn - 1; m > center;) {                                           // :61-68
+            if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m + 1);
+            else if (D(m) == D(m - 1) && D(m) != 0) { D(m - 1) += 1; m += 1; }
+            m -= 1;
+        }
+    }
+    return HM_OK;
+}
+
 // _energy_function + analyze_linearity, modules/ICRF_calibration_exposure.py:66-145,148-201, for n_candidates ICRFs of one channel:
 // per candidate and exposure pair (i < j, np.triu_indices order) the (weighted) mean of |v_i - v_j t_i/t_j| (/ (v_j t_i/t_j) when
 // relative) over the pixels whose values lie inside [icrf[lower], icrf[upper]]; the energy is the nanmean over the pairs, +inf for NaN

@@ -953,6 +953,67 @@ def welford_finalize(mean: torch.Tensor, m2: Optional[torch.Tensor], count: int)
 
 
 # ------------------------------------------------------------------------------------------------
+# camera noise profiles and the per-DN STD table (modules/video_processing.py:12-133)
+# ------------------------------------------------------------------------------------------------
+_I64 = torch.int64
+
+
+def _check_profiles(profiles: torch.Tensor) -> int:
+    _require_cuda(profiles, "profiles")
+    if profiles.dtype != _I64 or not profiles.is_contiguous():
+        raise TypeError("profiles must be a contiguous int64 tensor")
+    if profiles.dim() != 3 or tuple(profiles.shape[:2]) != (BITS, BITS):
+        raise ValueError(f"profiles must be shaped ({BITS}, {BITS}, C)")
+    return profiles.shape[2]
+
+
+def noise_profile_update(frames: Sequence[torch.Tensor], mean_u8: torch.Tensor, profiles: torch.Tensor) -> None:
+    """Add every element of `frames` (uint8 (H, W, C) tensors) to profiles[mean DN, frame DN, c] in place (video_processing.py:
+    93-104). `profiles` ((256, 256, C) int64) is zeroed by the caller before the first update. HM_MAX_FRAMES frames per launch."""
+    Cc = _check_profiles(profiles)
+    _require_cuda(mean_u8, "mean_frame")
+    if mean_u8.dtype != _U8 or not mean_u8.is_contiguous():
+        raise TypeError("mean_frame must be a contiguous uint8 tensor")
+    if mean_u8.shape[-1] != Cc:
+        raise ValueError(f"mean_frame has {mean_u8.shape[-1]} channels, profiles {Cc}")
+    frames = list(frames)
+    for f in frames:
+        _require_cuda(f, "frame")
+        if f.dtype != _U8 or f.shape != mean_u8.shape:
+            raise ValueError("every frame must be a uint8 tensor shaped like mean_frame")
+    dev = profiles.device
+    n = mean_u8.numel()
+    wsb = nat.lib.hm_noise_profile_workspace_bytes(n, Cc)
+    ws = torch.empty(max(1, wsb), dtype=_U8, device=dev) if wsb else None
+    with _on(dev):
+        for k0 in range(0, len(frames), nat.HM_MAX_FRAMES):
+            batch = [f.contiguous() for f in frames[k0:k0 + nat.HM_MAX_FRAMES]]
+            nat.check(nat.lib.hm_noise_profile_update(_ptr_array(batch), len(batch), mean_u8.data_ptr(), n, Cc, profiles.data_ptr(),
+                                                      nat.ptr(ws), wsb, _stream(dev)), "hm_noise_profile_update")
+
+
+def noise_profile_std(profiles: torch.Tensor) -> torch.Tensor:
+    """-> (256, C) float64: _calculate_STD (video_processing.py:109-133) of every channel; NaN for a level without counts."""
+    Cc = _check_profiles(profiles)
+    dev = profiles.device
+    edges = torch.as_tensor(np.linspace(0, 1, num=BITS, dtype=float), device=dev)          # :120, bit-identical by construction
+    out = torch.empty((BITS, Cc), dtype=_F64, device=dev)
+    with _on(dev):
+        nat.check(nat.lib.hm_noise_profile_std(profiles.data_ptr(), Cc, edges.data_ptr(), out.data_ptr(), _stream(dev)),
+                  "hm_noise_profile_std")
+    return out
+
+
+def noise_profile_clean_edges(profiles: torch.Tensor) -> torch.Tensor:
+    """clean_data_edges (video_processing.py:12-74) of every channel's (256, 256) distributions, in place; returns `profiles`."""
+    Cc = _check_profiles(profiles)
+    dev = profiles.device
+    with _on(dev):
+        nat.check(nat.lib.hm_noise_profile_clean_edges(profiles.data_ptr(), Cc, _stream(dev)), "hm_noise_profile_clean_edges")
+    return profiles
+
+
+# ------------------------------------------------------------------------------------------------
 # ICRF-calibration energy function (modules/ICRF_calibration_exposure.py:66-201), batched over candidates
 # ------------------------------------------------------------------------------------------------
 def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], icrf_batch,

@@ -1,4 +1,5 @@
-"""Mean / STD frames of a video - mirror of modules/video_processing.py:161-262 on the HIP backend.
+"""Mean / STD frames of a video - mirror of modules/video_processing.py:161-262 on the HIP backend - and the camera
+noise profiles with the per-DN STD table computed from them (:12-133).
 
 The reference streams frames out of `cv.VideoCapture` one at a time and updates three whole-image NumPy
 arrays per frame (video_processing.py:199-208). Here the decoded frames are uploaded in batches and folded
@@ -10,6 +11,16 @@ takes any iterable of uint8 (H, W, C) frames - e.g. `frames_from_capture(cv.Vide
 of such iterables (the reference's "all videos of a directory" mode, :193-195).
 
 Deviation K (SURVEY.md 3.4 style): `if ICRF:` at :200 raises for an ndarray; the intended `ICRF is not None` is used.
+
+Noise profiles (`compute_noise_profiles`, :77-106) count, per channel, every (mean-frame DN, frame DN) pair of every frame
+into a (256, 256, C) int64 array (`hm_noise_profile_update`, a banded joint histogram in LDS); `_calculate_STD` (:109-133)
+and `noise_profiles_to_STD_data` turn it into the (256, C) float64 table of `ImageSet.calculate_numerical_STD`, and
+`clean_data_edges` (:12-74) runs the reference's integer cleaning passes. Sources are decoded frames as for
+`welford_algorithm`; as the reference reads every video twice (once for the mean), a source must be iterable twice (a
+list, or a zero-argument callable returning a fresh iterable) unless the caller passes `mean_frame=`.
+
+Deviation L (SURVEY.md 3.4 style): `_calculate_STD` calls `math.sqrt` at :130 without importing `math` and raises NameError;
+the intended `math.sqrt` is used, so a level without counts gives NaN (0 / 0 and sqrt(NaN)).
 """
 from __future__ import annotations
 
@@ -19,6 +30,7 @@ import numpy as np
 import torch
 
 from . import engine
+from .settings import BITS
 
 
 def _engine_for(device: torch.device):
@@ -140,3 +152,122 @@ def process_video(frame_source, video_path, ICRF: Optional[np.ndarray] = None, u
     ret = welford_algorithm(frame_source, ICRF, use_std)
     save_result(ret, video_path)
     return ret
+
+
+# ------------------------------------------------------------------------------------------------
+# noise profiles and the per-DN STD table (video_processing.py:12-133)
+# ------------------------------------------------------------------------------------------------
+def _source_list(frame_sources) -> list:
+    if callable(frame_sources):
+        return [frame_sources]
+    if isinstance(frame_sources, (list, tuple)) and frame_sources and not _looks_like_frame(frame_sources[0]):
+        return list(frame_sources)
+    return [frame_sources]
+
+
+def _fresh(source):
+    return source() if callable(source) else source
+
+
+def compute_noise_profiles(frame_sources, mean_frame=None, device=None, frames_per_launch: int = FRAMES_PER_LAUNCH,
+                           as_numpy: bool = True):
+    """Noise profiles of a camera from frames of a static scene (video_processing.py:77-106).
+
+    Args:
+        frame_sources: an iterable of uint8 (H, W, C) (or (H, W)) frames, a list of such iterables (several videos folded into
+            one result), or a zero-argument callable returning a fresh iterable (also as list items). A frame of None ends a source.
+            Without `mean_frame` every source is read twice, so a one-shot iterator is rejected.
+        mean_frame: uint8 (H, W, C) mean frame to count against; default: welford_algorithm's mean over all frames (:89).
+        device: the GPU to compute on (default: the current one), or "cpu" for the host build (libhdrmerge_host.so).
+    Returns:
+        (profiles int64 (256, 256, C), mean_frame uint8 (H, W, C)) - NumPy arrays (device tensors with as_numpy=False);
+        profiles[m, f, c] counts the elements of channel c with mean DN m and frame DN f.
+    """
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    eng = _engine_for(device)
+    if frames_per_launch < 1:
+        raise ValueError("frames_per_launch must be positive")
+    sources = _source_list(frame_sources)
+    if mean_frame is None:
+        for src in sources:
+            if not callable(src) and iter(src) is src:
+                raise ValueError("compute_noise_profiles reads every source twice (mean frame, then profiles): pass lists, "
+                                 "zero-argument callables returning fresh iterables, or mean_frame=")
+        mean = welford_algorithm([_fresh(s) for s in sources], None, False, device=device, frames_per_launch=frames_per_launch,
+                                 as_numpy=False)["mean"]                                     # :89
+    else:
+        mean = _as_device_frame(mean_frame, device).contiguous()
+    C = mean.shape[-1]
+    profiles = torch.zeros((BITS, BITS, C), dtype=torch.int64, device=device)              # :87
+    pending = []
+
+    def flush():
+        if pending:
+            eng.noise_profile_update(pending, mean, profiles)
+            pending.clear()
+
+    for src in sources:
+        for frame in _fresh(src):
+            if frame is None:
+                break
+            t = _as_device_frame(frame, device)
+            if t.shape != mean.shape:
+                raise ValueError(f"frame shape {tuple(t.shape)} differs from the mean frame's {tuple(mean.shape)}")
+            pending.append(t)
+            if len(pending) == frames_per_launch:
+                flush()
+    flush()
+    if as_numpy:
+        return profiles.cpu().numpy(), mean.cpu().numpy()
+    return profiles, mean
+
+
+def _profiles_tensor(arr, device, what: str):
+    """-> (device tensor (256, 256, C) int64, was a NumPy array, channel axis added). Device tensors keep their device."""
+    is_np = not isinstance(arr, torch.Tensor)
+    if is_np:
+        a = np.asarray(arr)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{what} must be an integer array, got {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    else:
+        if arr.dtype.is_floating_point or arr.dtype == torch.bool:
+            raise TypeError(f"{what} must be an integer tensor, got {arr.dtype}")
+        t = arr
+        dev = arr.device if device is None else torch.device(device)
+    squeeze = t.dim() == 2
+    if squeeze:
+        t = t[..., None]
+    if t.dim() != 3 or tuple(t.shape[:2]) != (BITS, BITS):
+        raise ValueError(f"{what} must be shaped ({BITS}, {BITS}) or ({BITS}, {BITS}, C), got {tuple(t.shape)}")
+    return t.to(device=dev, dtype=torch.int64).contiguous(), is_np, squeeze
+
+
+def noise_profiles_to_STD_data(profiles, device=None):
+    """(256, C) float64 STD table (`process_STD_data`'s STD_data, video_processing.py:136-158, without its text files): column c
+    is _calculate_STD(profiles[:, :, c]). The input of ImageSet.calculate_numerical_STD / load_std_image(STD_data)."""
+    t, is_np, squeeze = _profiles_tensor(profiles, device, "profiles")
+    out = _engine_for(t.device).noise_profile_std(t)
+    if squeeze:
+        out = out[:, 0]
+    return out.cpu().numpy() if is_np else out
+
+
+def _calculate_STD(mean_data_array, device=None):
+    """video_processing.py:109-133: the standard deviation of every signal level of ONE channel's (256, 256) profile,
+    shape (256,) float64 (deviation L: NaN for a level without counts)."""
+    if tuple(np.shape(mean_data_array) if not isinstance(mean_data_array, torch.Tensor) else mean_data_array.shape) != (BITS, BITS):
+        raise ValueError(f"_calculate_STD takes one channel's ({BITS}, {BITS}) array")
+    return noise_profiles_to_STD_data(mean_data_array, device)
+
+
+def clean_data_edges(base_data_arr, device=None):
+    """video_processing.py:12-74 on a (256, 256) or (256, 256, C) integer array (every channel), IN PLACE; returns it."""
+    t, is_np, _ = _profiles_tensor(base_data_arr, device, "base_data_arr")
+    _engine_for(t.device).noise_profile_clean_edges(t)
+    if is_np:
+        base_data_arr[...] = t.cpu().numpy().reshape(base_data_arr.shape)
+    elif t.data_ptr() != base_data_arr.data_ptr():
+        base_data_arr.copy_(t.reshape(base_data_arr.shape))
+    return base_data_arr

@@ -40,7 +40,8 @@ extern "C" {
 
 /* ABI history. 1: first release (hm_merge_args 264 bytes), later grown by hot_workspace / hot_workspace_bytes (280 bytes) without a bump.
  * 2: frames_workspace / frames_workspace_bytes (296 bytes), hm_merge_frames_workspace_bytes(), stacks of more than HM_MAX_FRAMES
- *    frames; hm_merge still accepts the 264- and 280-byte layouts (the missing tail reads as "no workspace").            */
+ *    frames; hm_merge still accepts the 264- and 280-byte layouts (the missing tail reads as "no workspace").
+ *    Later grown by the hm_noise_profile_* entry points without a bump (additions only).                                   */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -354,6 +355,31 @@ int hm_welford_update(const void* const* frames /*[host] n_frames device ptrs*/,
 int hm_welford_finalize(const double* mean, const double* m2 /*nullable*/, int64_t count,
                         uint8_t* out_mean /*nullable*/, uint8_t* out_std /*nullable*/, int64_t n_elems, void* stream);
 int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems);
+
+/* ------------------------------------------------------------------------------------------
+ * Camera noise profiles and the per-DN STD table: compute_noise_profiles, _calculate_STD and clean_data_edges,
+ * modules/video_processing.py:12-133 (the input of ImageSet.calculate_numerical_STD, modules/image_set.py).
+ *   profiles   (256, 256, C) int64: profiles[m, f, c] counts the elements of channel c whose mean-frame DN is m and
+ *              whose frame DN is f (:77-106, np.add.at); the caller zero-initialises it before the first update and
+ *              every update adds to it (the running-state convention of hm_welford_update)
+ *   hm_noise_profile_update   adds n_frames uint8 frames (each n_elems = H*W*C, HWC) against the uint8 mean frame
+ *              `mean` (n_elems). workspace: hm_noise_profile_workspace_bytes() bytes (0 at this version: NULL is fine).
+ *              C > HM_MAX_CHANNELS -> HM_EUNSUPPORTED.
+ *   hm_noise_profile_algorithmic_bytes   n_elems * (n_frames + 1) + 2 * 256 * 256 * C * 8: each frame byte and the mean
+ *              read once, the profile read and written once.
+ *   hm_noise_profile_std      out_std (256, C) float64 [level][c]: for each row, over its non-zero bins h with the edges
+ *              `edges` (256 float64, the caller's np.linspace(0, 1, 256)), mean = sum(h edges) / sum(h) and
+ *              std = sqrt(sum((edges - mean)^2 h) / sum(h)) (:109-133); NaN for a row without counts.
+ *   hm_noise_profile_clean_edges   the reference's four integer passes over every (row, channel) distribution, centred
+ *              at the row's level (:12-74), in place; bit-exact.
+ * ------------------------------------------------------------------------------------------ */
+size_t hm_noise_profile_workspace_bytes(int64_t n_elems, int C);
+int64_t hm_noise_profile_algorithmic_bytes(int n_frames, int64_t n_elems, int C);
+int hm_noise_profile_update(const void* const* frames /*[host] n_frames device ptrs*/, int n_frames, const uint8_t* mean,
+                            int64_t n_elems, int C, int64_t* profiles, void* workspace /*nullable when 0 bytes*/,
+                            int64_t workspace_bytes, void* stream);
+int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void* stream);
+int hm_noise_profile_clean_edges(int64_t* profiles, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * ICRF-calibration energy function: _energy_function + analyze_linearity,
