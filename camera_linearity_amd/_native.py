@@ -21,6 +21,7 @@ LIB_PATH = pathlib.Path(os.environ.get("HDRMERGE_LIB", _HERE / "lib" / "libhdrme
 HM_MAX_FRAMES = 32
 HM_MAX_CHANNELS = 4
 HM_MAX_DIMS = 6
+HM_KDE_MOMENTS = 11
 
 HM_OK, HM_EINVAL, HM_EUNSUPPORTED, HM_EALIGN, HM_ELAUNCH, HM_ENODEVICE, HM_ESHAPE = 0, -1, -2, -3, -4, -5, -6
 HM_OP_ADD, HM_OP_SUB, HM_OP_MUL, HM_OP_DIV, HM_OP_POW = range(5)
@@ -118,6 +119,10 @@ _SIGNATURES = {
                                           C.c_int64, C.c_void_p]),
     "hm_noise_profile_std": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_noise_profile_clean_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hm_kde_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "hm_kde_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hm_kde_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hm_tiff_lzw_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]),
     "hm_tiff_packbits_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]),
     "hm_linearity_energy_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

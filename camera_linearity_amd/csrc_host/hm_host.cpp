@@ -995,6 +995,94 @@ int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
     return HM_OK;
 }
 
+// compute_kernel_density_estimate, modules/measurand.py:716-761 (gaussian_kde(values, 'silverman', weights).evaluate), one channel.
+// The operation sequence of hm_kde.hip: counted = finite x (and std != 0), w = 1 / std or 1; moments over kKdeSlices fixed slices
+// added in order (the same bits for any thread count); evaluate sums w exp(-(d * d) * 0.5), d = x / h - y / h, per chunk of
+// kKdeChunk elements, the chunks in order, times `scale`.
+constexpr int kKdeSlices = 256;
+constexpr int64_t kKdeChunk = 4096;
+size_t hm_kde_workspace_bytes(int64_t, int, int) { return 0; }
+static inline bool kde_load(const double* val, const double* std_, int64_t e, double& x, double& w) {
+    x = val[e];
+    w = 1.0;
+    bool ok = std::isfinite(x);
+    if (std_) { const double s = std_[e]; ok = ok && s != 0.0; w = 1.0 / s; }
+    return ok;
+}
+int hm_kde_moments(const double* val, const double* std_, int64_t n_elems, int C, int channel, double* moments, void*, int64_t workspace_bytes, void*) {
+    if (!val || !moments || n_elems < 0 || C < 1 || channel < 0 || channel >= C || workspace_bytes < 0) return HM_EINVAL;
+    if (n_elems % C != 0) return HM_ESHAPE;
+    const int64_t n = n_elems / C;
+    std::vector<double> part(static_cast<size_t>(kKdeSlices) * 10);
+#pragma omp parallel for schedule(static)
+    for (int s = 0; s < kKdeSlices; ++s) {
+        double v[9] = {0.0, 0.0, 0.0, 0.0, kInf, -kInf, 0.0, 0.0, 0.0};
+        for (int64_t i = n * s / kKdeSlices; i < n * (s + 1) / kKdeSlices; ++i) {
+            double x, w;
+            if (!kde_load(val, std_, i * C + channel, x, w)) continue;
+            v[0] += 1.0; v[1] += w; v[2] += w * w; v[3] += w * x;
+            v[4] = std::fmin(v[4], x); v[5] = std::fmax(v[5], x);
+            v[6] += std::isfinite(w) ? 0.0 : 1.0; v[7] += w > 0.0 ? 1.0 : 0.0; v[8] += w < 0.0 ? 1.0 : 0.0;
+        }
+        std::copy(v, v + 9, part.begin() + s * 10);
+    }
+    double r[9] = {0.0, 0.0, 0.0, 0.0, kInf, -kInf, 0.0, 0.0, 0.0};
+    for (int s = 0; s < kKdeSlices; ++s)
+        for (int k = 0; k < 9; ++k) {
+            const double o = part[s * 10 + k];
+            r[k] = k == 4 ? std::fmin(r[k], o) : k == 5 ? std::fmax(r[k], o) : r[k] + o;
+        }
+    const double xbar = r[3] / r[1];
+#pragma omp parallel for schedule(static)
+    for (int s = 0; s < kKdeSlices; ++s) {
+        double a = 0.0;
+        for (int64_t i = n * s / kKdeSlices; i < n * (s + 1) / kKdeSlices; ++i) {
+            double x, w;
+            if (!kde_load(val, std_, i * C + channel, x, w)) continue;
+            const double d = x - xbar;
+            a += w * (d * d);
+        }
+        part[s * 10] = a;
+    }
+    double m2 = 0.0;
+    for (int s = 0; s < kKdeSlices; ++s) m2 += part[s * 10];
+    std::copy(r, r + 9, moments);
+    moments[9] = xbar;
+    moments[10] = m2;
+    return HM_OK;
+}
+int hm_kde_evaluate(const double* val, const double* std_, int64_t n_elems, int C, int channel, double h, double scale, const double* grid,
+                    int m, double* out, void*, int64_t workspace_bytes, void*) {
+    if (!val || n_elems < 0 || C < 1 || channel < 0 || channel >= C || workspace_bytes < 0) return HM_EINVAL;
+    if (n_elems % C != 0) return HM_ESHAPE;
+    if (m < 0 || !(h > 0.0) || !std::isfinite(h) || !std::isfinite(scale)) return HM_EINVAL;
+    if (m == 0) return HM_OK;
+    if (!grid || !out) return HM_EINVAL;
+    const int64_t n = n_elems / C;
+    std::vector<double> u, w;                                        // the counted elements, u = x / h
+    for (int64_t i = 0; i < n; ++i) {
+        double x, wi;
+        if (kde_load(val, std_, i * C + channel, x, wi)) { u.push_back(x / h); w.push_back(wi); }
+    }
+    const int64_t nc = static_cast<int64_t>(u.size());
+#pragma omp parallel for schedule(static)
+    for (int j = 0; j < m; ++j) {
+        const double v = grid[j] / h;
+        double total = 0.0;
+        for (int64_t k0 = 0; k0 < nc; k0 += kKdeChunk) {
+            double acc = 0.0;
+            const int64_t k1 = std::min(nc, k0 + kKdeChunk);
+            for (int64_t k = k0; k < k1; ++k) {
+                const double d = u[k] - v;
+                acc += w[k] * std::exp(-(d * d) * 0.5);
+            }
+            total += acc;
+        }
+        out[j] = total * scale;
+    }
+    return HM_OK;
+}
+
 // _energy_function + analyze_linearity, modules/ICRF_calibration_exposure.py:66-145,148-201, for n_candidates ICRFs of one channel:
 // per candidate and exposure pair (i < j, np.triu_indices order) the (weighted) mean of |v_i - v_j t_i/t_j| (/ (v_j t_i/t_j) when
 // relative) over the pixels whose values lie inside [icrf[lower], icrf[upper]]; the energy is the nanmean over the pairs, +inf for NaN

@@ -910,6 +910,82 @@ def channel_histogram(val: torch.Tensor, std: Optional[torch.Tensor], bins: int,
 
 
 # ------------------------------------------------------------------------------------------------
+# weighted Gaussian kernel density estimates (modules/measurand.py:716-761)
+# ------------------------------------------------------------------------------------------------
+def kde_bandwidth(mom: np.ndarray):
+    """(h, scale) of hm_kde_evaluate from one channel's hm_kde_moments, with the errors scipy.stats.gaussian_kde(values, 'silverman',
+    weights) raises there (scipy 1.15): p = w / sum w, neff = 1 / sum p^2, factor = (0.75 neff)^(-1/5), var = np.cov(bias=False,
+    aweights=p) = sum p (x - x_bar)^2 / (sum p - sum p^2 / sum p), h = sqrt(var) factor; scale = (2 pi)^(-1/2) / h / sum w.
+    Constant data always raise LinAlgError (deviation M: scipy's weighted covariance sometimes rounds to a tiny positive value)."""
+    count, sw, sw2, _, lo, hi, nonfinite, npos, nneg, _, m2 = (float(v) for v in mom[:nat.HM_KDE_MOMENTS])
+    if count <= 1:
+        raise ValueError("`dataset` input should have multiple elements.")
+    if nonfinite:
+        raise ValueError("array must not contain infs or NaNs")
+    if npos and nneg:
+        raise ValueError("weights of mixed sign")
+    if sw == 0.0:
+        raise ValueError("array must not contain infs or NaNs")
+    if lo == hi:
+        raise np.linalg.LinAlgError("1-th leading minor of the array is not positive definite")
+    neff = 1.0 / (sw2 / (sw * sw))
+    factor = np.power(neff * 3.0 / 4.0, -1.0 / 5)
+    var = (m2 / sw) / (1.0 - sw2 / (sw * sw))
+    if not (var > 0.0 and np.isfinite(var)):
+        raise np.linalg.LinAlgError("1-th leading minor of the array is not positive definite")
+    h = float(np.sqrt(var) * factor)
+    return h, float(np.power(2 * np.pi, -0.5) / h / sw), (lo, hi)
+
+
+def kernel_density_estimate(val: torch.Tensor, std: Optional[torch.Tensor], data_points: int, included_range, channels: Sequence[int]):
+    """modules/measurand.py:716-761 -> {c: (estimate ndarray (data_points,), x_range ndarray)}: hm_kde_moments per channel, one read-back,
+    the bandwidth and np.linspace grid on the host, hm_kde_evaluate per channel, one read-back."""
+    _require_cuda(val, "val")
+    val = val.contiguous()
+    if val.dtype != _F64:
+        raise TypeError("val must be float64")
+    if std is not None:
+        _require_cuda(std, "std")
+        std = std.to(_F64).contiguous()
+        if std.shape != val.shape:
+            raise ValueError("Value and std shapes must match.")
+    Cc = val.shape[-1] if val.dim() else 1
+    n = val.numel()
+    m = int(data_points)
+    if m < 0:
+        raise ValueError(f"Number of samples, {m}, must be non-negative.")
+    channels = list(channels)
+    for c in channels:
+        if not -Cc <= c < Cc:
+            raise IndexError(f"index {c} is out of bounds for axis with size {Cc}")
+    dev = val.device
+    wsb = nat.lib.hm_kde_workspace_bytes(n, Cc, m)
+    ws = torch.empty(wsb, dtype=_U8, device=dev) if wsb else None
+    wsp, wsn = nat.ptr(ws), int(wsb)
+    mom = torch.empty((len(channels), nat.HM_KDE_MOMENTS), dtype=_F64, device=dev)
+    with _on(dev):
+        for k, c in enumerate(channels):
+            nat.check(nat.lib.hm_kde_moments(val.data_ptr(), nat.ptr(std), n, Cc, c % Cc, mom[k].data_ptr(), wsp, wsn, _stream(dev)),
+                      "hm_kde_moments")
+        momh = mom.cpu().numpy()
+        grids, params = [], []
+        for k, c in enumerate(channels):
+            h, scale, (lo, hi) = kde_bandwidth(momh[k])
+            if included_range is not None:
+                lo, hi = included_range[0], included_range[1]
+            grids.append(np.linspace(lo, hi, num=m))
+            params.append((h, scale))
+        res = torch.zeros((len(channels), m), dtype=_F64, device=dev)
+        if m:
+            grid_d = torch.as_tensor(np.stack(grids), device=dev)
+            for k, c in enumerate(channels):
+                nat.check(nat.lib.hm_kde_evaluate(val.data_ptr(), nat.ptr(std), n, Cc, c % Cc, params[k][0], params[k][1], grid_d[k].data_ptr(),
+                                                  m, res[k].data_ptr(), wsp, wsn, _stream(dev)), "hm_kde_evaluate")
+        r = res.cpu().numpy()
+    return {c: (r[k].copy(), grids[k]) for k, c in enumerate(channels)}
+
+
+# ------------------------------------------------------------------------------------------------
 # upstream producer: Welford mean / M2 over video frames (modules/video_processing.py:161-219)
 # ------------------------------------------------------------------------------------------------
 def welford_update(frames: Sequence[torch.Tensor], count_before: int, mean: torch.Tensor, m2: Optional[torch.Tensor],

@@ -19,7 +19,8 @@ instead of 8) and materialises DN/255 (modules/image_set.py:223) only when `.val
 Rows "next" of SURVEY.md 8f-1: apply_thresholds, compute_difference, interpolate (equal shapes or broadcasting operands),
 compute_dimension_statistics (any axis or axis tuple), extract and compute_channel_histogram run as HIP kernels
 (csrc/hm_stats.hip, hm_ops.hip); what a kernel does not cover raises (more than 32 channels in apply_thresholds, more
-than 4 channels in the histogram, kernel density estimates) - nothing is computed with torch or NumPy arithmetic.
+than 4 channels in the histogram) - nothing is computed with torch or NumPy arithmetic. Kernel density estimates are
+HostMeasurand.compute_kernel_density_estimate (the reference's NumPy class) and kde.kernel_density_estimate on either backend.
 """
 from __future__ import annotations
 
@@ -394,10 +395,20 @@ class HipMeasurand(AbstractMeasurand):
         return {k_: self._export(v) for k_, v in st.items()}
 
     def compute_kernel_density_estimate(self, data_points: int, included_range=None, channels=None, use_std: bool = False):
-        """modules/measurand.py:716-761 is a NumPy-only plotting helper of the reference (scipy.stats.gaussian_kde on host arrays)
-        and is out of scope here: this package computes on the device only."""
-        raise NotImplementedError("kernel density estimates are host-side plotting support in the reference; "
-                                  "use to_numpy() and scipy.stats.gaussian_kde")
+        """modules/measurand.py:716-761 is a method of the reference's NumPy class; the device computes it through
+        camera_linearity_amd.kde.kernel_density_estimate, not as a method of the device Measurand."""
+        raise NotImplementedError("compute_kernel_density_estimate is a method of the host Measurand (use_cupy=False) only; "
+                                  "on the device use camera_linearity_amd.kde.kernel_density_estimate(measurand, ...)")
+
+    def _kernel_density_estimate(self, data_points: int, included_range=None, channels=None, use_std: bool = False):
+        """modules/measurand.py:716-761 on this measurand's library: hm_kde_moments + hm_kde_evaluate per channel."""
+        if channels is None:
+            channels = list(range(gs.NUM_OF_CHS))
+        if use_std and self._std is None:
+            raise TypeError("'NoneType' object is not subscriptable")          # self.std[..., c], measurand.py:742
+        vd = self._f64()
+        self._need_resident(vd, "compute_kernel_density_estimate")
+        return self._eng().kernel_density_estimate(vd, self._std if use_std else None, data_points, included_range, channels)
 
     def compute_channel_histogram(self, bins: int, included_range=None, channels=None, use_std: bool = False):
         """modules/measurand.py:430-469: np.histogram per channel - hm_channel_histogram on the device (per-workgroup
@@ -477,6 +488,11 @@ class HostMeasurand(HipMeasurand):
 
     def _eng(self):
         return _HOST_ENGINE
+
+    def compute_kernel_density_estimate(self, data_points: int, included_range=None, channels=None, use_std: bool = False):
+        """modules/measurand.py:716-761 (the reference defines it on this class): gaussian_kde(values, 'silverman', weights)
+        evaluated on np.linspace(lo, hi, data_points) per channel, computed in libhdrmerge_host.so (no SciPy)."""
+        return self._kernel_density_estimate(data_points, included_range, channels, use_std)
 
     def _need_resident(self, t: torch.Tensor, what: str) -> None:
         if t.is_cuda:

@@ -41,7 +41,7 @@ extern "C" {
 /* ABI history. 1: first release (hm_merge_args 264 bytes), later grown by hot_workspace / hot_workspace_bytes (280 bytes) without a bump.
  * 2: frames_workspace / frames_workspace_bytes (296 bytes), hm_merge_frames_workspace_bytes(), stacks of more than HM_MAX_FRAMES
  *    frames; hm_merge still accepts the 264- and 280-byte layouts (the missing tail reads as "no workspace").
- *    Later grown by the hm_noise_profile_* entry points without a bump (additions only).                                   */
+ *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only).                     */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -380,6 +380,28 @@ int hm_noise_profile_update(const void* const* frames /*[host] n_frames device p
                             int64_t workspace_bytes, void* stream);
 int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void* stream);
 int hm_noise_profile_clean_edges(int64_t* profiles, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Weighted Gaussian kernel density estimates: NumpyMeasurand.compute_kernel_density_estimate, modules/measurand.py:716-761
+ * (and CupyMeasurand's, modules/cupy_measurand.py:88-137): scipy.stats.gaussian_kde(values, 'silverman', weights).evaluate(x_range)
+ * for ONE channel `channel` of HWC float64 data `val` (n_elems = n * C, any C >= 1), `std` nullable (same layout).
+ *   counted    elements with a finite value and, with std, std != 0 (:741-749); weight w = 1 / std, or 1 without std
+ *   workspace  device memory of hm_kde_workspace_bytes(n_elems, C, m) bytes, owned by the caller, shared by both calls (the host
+ *              build needs none: 0 bytes, NULL is fine). No allocation, no host synchronisation, no float atomics: the
+ *              reductions run in a fixed order, so the same inputs give the same bits on every run and under graph replay.
+ *   hm_kde_moments   moments[0..10] (device, 11 float64): count, sum w, sum w^2, sum w x, min x, max x, #non-finite w, #w > 0,
+ *              #w < 0, x_bar = sum w x / sum w, sum w (x - x_bar)^2 - all over the counted elements. Two stream-ordered passes;
+ *              the second reads x_bar from moments[9] on the device.
+ *   hm_kde_evaluate  out[j] = scale * sum_i w_i exp(-(x_i / h - y_j / h)^2 / 2) for the m grid points y = grid (device);
+ *              the caller passes h = sqrt(cov) * silverman_factor and scale = (2 pi)^(-1/2) / h / sum w (scipy's norm and
+ *              weight normalisation). h must be > 0 and finite, scale finite.
+ * ------------------------------------------------------------------------------------------ */
+#define HM_KDE_MOMENTS 11
+size_t hm_kde_workspace_bytes(int64_t n_elems, int C, int m);
+int hm_kde_moments(const double* val, const double* std /*nullable*/, int64_t n_elems, int C, int channel, double* moments,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+int hm_kde_evaluate(const double* val, const double* std /*nullable*/, int64_t n_elems, int C, int channel, double h, double scale,
+                    const double* grid, int m, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * ICRF-calibration energy function: _energy_function + analyze_linearity,

@@ -549,8 +549,48 @@ def case_series(rng):
     return desc
 
 
+def case_kde(rng):
+    """kde.kernel_density_estimate on both backends: any C, odd sizes, included ranges inside / outside the data, weights with zeros and
+    infinities; both sides must return the same grid bit for bit and estimates within 1e-11, or raise the same exception type."""
+    from camera_linearity_amd import kde
+    c = int(rng.choice([1, 2, 3, 5]))
+    shape = (int(rng.integers(1, 60)), int(rng.integers(1, 60)), c)
+    x = rng.standard_normal(shape) * float(rng.choice([1e-3, 0.02, 1.0, 50.0])) + float(rng.uniform(-1, 1))
+    xs = rng.uniform(0.001, 0.05, shape) if rng.random() < 0.7 else None
+    sprinkle(rng, x, p=0.01)
+    if xs is not None and rng.random() < 0.3:
+        xs[rng.random(shape) < 0.02] = float(rng.choice([0.0, np.inf]))
+    m = int(rng.choice([1, 2, 17, 256, 1024, 1500]))
+    rngs = None if rng.random() < 0.5 else tuple(sorted(rng.uniform(-3, 3, 2).tolist()))
+    chans = [int(a) for a in rng.choice(c, size=int(rng.integers(1, c + 1)), replace=False)]
+    use_std = xs is not None and bool(rng.random() < 0.7)
+    desc = f"kde {shape} m={m} range={rngs} channels={chans} use_std={use_std}"
+    out = []
+    for A in (Measurand(D(x), D(xs), use_cupy=GPU), Measurand(x.copy(), None if xs is None else xs.copy(), use_cupy=False)):
+        try:
+            out.append(kde.kernel_density_estimate(A, m, rngs, chans, use_std))
+        except (ValueError, TypeError, np.linalg.LinAlgError) as e:
+            out.append(type(e))
+    ka, kb = out
+    if not isinstance(ka, dict) or not isinstance(kb, dict):
+        if ka is not kb:
+            raise Mismatch(f"{desc}: device {ka if not isinstance(ka, dict) else 'result'} vs host {kb if not isinstance(kb, dict) else 'result'}")
+        return desc
+    assert list(ka) == list(kb) == chans
+    for key in chans:
+        compare(f"kde[{key}].x_range", ka[key][1], kb[key][1], None)
+        ea, eb = ka[key][0], kb[key][0]                                   # |d| <= 1e-11 |host| + 1e-14 max |host| (exp amplifies the
+        if args.one:                                                      # last bit of u - v in far tails: judged against the peak)
+            say(f"  kde[{key}]: device {ea[:12]} host {eb[:12]}")
+        bad = ~(np.abs(ea - eb) <= 1e-11 * np.abs(eb) + 1e-14 * (np.abs(eb).max() if eb.size else 0.0))
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise Mismatch(f"kde[{key}].estimate: {int(bad.sum())} of {eb.size} outside 1e-11 rel + 1e-14 peak; {ea[i]!r} vs {eb[i]!r}")
+    return desc
+
+
 CASES = [(case_merge, 5), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2)]
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()
 counts = {fn.__name__: 0 for fn, _ in CASES}
