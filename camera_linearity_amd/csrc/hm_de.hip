@@ -1,0 +1,217 @@
+// hm_de.hip - one generation of the ICRF-calibration differential evolution on the device (gfx950): the solver loop of
+// calibration(), modules/ICRF_calibration_exposure.py:288-369 (SciPy's DifferentialEvolutionSolver, 'currenttobest1bin',
+// deferred updating), restated with counter-based random numbers - the algorithm is specified in include/hdrmerge.h.
+//
+//   k_de_trial    grid = S members, 256 lanes: lanes j < P form the trial component j (mutation, binomial crossover, out-of-range
+//                 redraw) and its physical parameter; then lane d forms DN d of the candidate ICRF (mean + PCA x, shift, ICRF[0] = 0)
+//                 and the range / monotonicity verdict is one ballot per wave, combined over the four waves in LDS
+//   hm_linearity_energy   the existing energy launcher (hm_energy.hip) on the S trial rows, unchanged
+//   k_de_select   ONE workgroup: deferred selection, then best index / mean / std by fixed-order LDS trees, the stop flag, and - as the
+//                 last store of the generation - the generation counter
+//
+// All state is the caller's: nothing is allocated, nothing synchronises the host, no float atomics. The generation counter and the
+// stop flag live in the status block on the device, so the same recorded launches can be replayed (hipGraph); after the stop flag is
+// set k_de_trial and k_de_select return before their first store (the energy kernels re-evaluate the unchanged trial rows to the same
+// bits), so the state no longer moves however many generations follow.
+#include "hm_common.h"
+
+namespace hm {
+
+struct DeK {
+    double* pop;              // (S, P) scaled to [0, 1]
+    double* energy;           // (S)
+    double* trial;            // (S, P)
+    double* trial_energy;     // (S)
+    double* icrf;             // (S, 256)
+    uint8_t* valid;           // (S)
+    int64_t* status;          // HM_DE_STATUS_WORDS
+    const double* mean_icrf;  // (256)
+    const double* pca;        // (256, P)
+    const double* lo;         // (P)
+    const double* hi;         // (P)
+    int32_t S, P;
+    uint64_t seed;
+    int64_t max_generations;
+    double m_lo, m_hi, cr, tol, energy_limit;
+};
+
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {          // the splitmix64 step
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ double de_uniform(uint64_t key, int i, int k) {
+    const uint64_t r = mix64(key + (static_cast<uint64_t>(i + 1) << 20) + static_cast<uint64_t>(k));
+    return static_cast<double>(r >> 11) * 0x1.0p-53;
+}
+
+__global__ __launch_bounds__(256) void k_de_trial(const DeK a) {
+    __shared__ double x[HM_DE_MAX_PARAMS];
+    __shared__ double last;
+    __shared__ int bad[4];
+    if (a.status[HM_DE_STOP] != 0) return;                                // uniform: the whole generation is a no-op
+    const int i = blockIdx.x, lane = threadIdx.x, P = a.P, S = a.S;
+    const int64_t g = a.status[HM_DE_GENERATION];
+
+    if (lane < P) {
+        const int j = lane;
+        const double ui = a.pop[static_cast<int64_t>(i) * P + j];
+        double tr = ui;                                                   // generation 0 evaluates the initial population: no draws
+        if (g > 0) {
+            const uint64_t key = mix64(a.seed ^ mix64(static_cast<uint64_t>(g)));
+            const double F = a.m_lo + (a.m_hi - a.m_lo) * de_uniform(key, S, 0);
+            // (the clamps never bind for U < 1 and a status block this library wrote: they keep a corrupted one inside the buffers)
+            const int b = min(max(static_cast<int>(a.status[HM_DE_BEST_INDEX]), 0), S - 1);
+            const int pick = min(static_cast<int>(floor(de_uniform(key, i, 0) * (S - 1))), S - 2);
+            const int r0 = pick + (pick >= i);
+            int c = min(static_cast<int>(floor(de_uniform(key, i, 1) * (S - 2))), S - 3);
+            const int lo2 = i < r0 ? i : r0, hi2 = i < r0 ? r0 : i;
+            c += (c >= lo2);
+            c += (c >= hi2);
+            const int r1 = c;
+            const int fill = static_cast<int>(floor(de_uniform(key, i, 2) * P));
+            if (de_uniform(key, i, 3 + j) < a.cr || j == fill) {
+                const double ub = a.pop[static_cast<int64_t>(b) * P + j];
+                const double u0 = a.pop[static_cast<int64_t>(r0) * P + j];
+                const double u1 = a.pop[static_cast<int64_t>(r1) * P + j];
+                tr = ui + F * (((ub - ui) + u0) - u1);
+                if (!(tr >= 0.0 && tr <= 1.0)) tr = de_uniform(key, i, 3 + P + j);   // SciPy's _ensure_constraint
+            }
+        }
+        a.trial[static_cast<int64_t>(i) * P + j] = tr;
+        x[j] = a.lo[j] + tr * (a.hi[j] - a.lo[j]);
+    }
+    __syncthreads();
+
+    double row = 0.0;
+    for (int j = 0; j < P; ++j) row += a.pca[lane * P + j] * x[j];        // PCA @ x, DN `lane`
+    row = a.mean_icrf[lane] + row;
+    if (lane == 255) last = row;
+    __syncthreads();
+    row += 1.0 - last;                                                    // :166
+    if (lane == 0) row = 0.0;                                             // :167
+    a.icrf[static_cast<int64_t>(i) * 256 + lane] = row;
+
+    // range (:173-175) and strict monotonicity (:177-179): the left neighbour from the wave, or from the previous wave through LDS
+    __shared__ double edge[4];
+    if ((lane & 63) == 63) edge[lane >> 6] = row;
+    __syncthreads();
+    double prev = __shfl_up(row, 1, 64);
+    if ((lane & 63) == 0 && lane > 0) prev = edge[(lane >> 6) - 1];
+    const bool wrong = row > 1.0 || row < 0.0 || (lane > 0 && !(row > prev));
+    const unsigned long long any = __ballot(wrong);
+    if ((lane & 63) == 0) bad[lane >> 6] = any != 0ull;
+    __syncthreads();
+    if (lane == 0) a.valid[i] = !(bad[0] | bad[1] | bad[2] | bad[3]);
+}
+
+// fixed-order tree over n (a power of two <= HM_DE_MAX_POP) LDS entries; the result is in v[0]
+__device__ __forceinline__ void tree_sum(double* v, int n) {
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        for (int t = threadIdx.x; t < s; t += blockDim.x) v[t] += v[t + s];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_de_select(const DeK a) {
+    __shared__ double e[HM_DE_MAX_POP];
+    __shared__ double v[HM_DE_MAX_POP];
+    __shared__ int idx[HM_DE_MAX_POP];
+    if (a.status[HM_DE_STOP] != 0) return;
+    const int S = a.S, P = a.P;
+    const int64_t g = a.status[HM_DE_GENERATION];
+    int n = 1;
+    while (n < S) n <<= 1;
+
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double ei = __builtin_inf();
+        if (i < S) {
+            const double et = a.trial_energy[i];
+            ei = a.energy[i];
+            if (g == 0 || et <= ei) {                                     // deferred updating: every trial saw the old population
+                ei = et;
+                a.energy[i] = et;
+                for (int j = 0; j < P; ++j) a.pop[static_cast<int64_t>(i) * P + j] = a.trial[static_cast<int64_t>(i) * P + j];
+            }
+        }
+        e[i] = ei;
+        v[i] = i < S ? ei : 0.0;
+        idx[i] = i;
+    }
+    __syncthreads();
+    tree_sum(v, n);
+    const double mean = v[0] / S;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double d = e[i] - mean;
+        v[i] = i < S ? d * d : 0.0;
+    }
+    __syncthreads();
+    tree_sum(v, n);
+    const double sd = sqrt(v[0] / S);
+    // lowest energy, ties to the lowest index (the padding is +inf with an index >= S, so it never wins a tie)
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        for (int t = threadIdx.x; t < s; t += blockDim.x) {
+            const double x0 = e[t], x1 = e[t + s];
+            const int i0 = idx[t], i1 = idx[t + s];
+            if (x1 < x0 || (x1 == x0 && i1 < i0)) { e[t] = x1; idx[t] = i1; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double best = e[0];
+        int64_t stop = 0;
+        if (g > 0 && (g & 1) == 0) {                                      // the reference loop advances two generations per pass (:351)
+            if (isfinite(mean) && sd == sd && sd <= a.tol * fabs(mean)) stop |= HM_DE_STOP_CONVERGED;   // mean finite <=> every E finite
+            if (best < a.energy_limit) stop |= HM_DE_STOP_ENERGY;
+        }
+        if (g >= a.max_generations) stop |= HM_DE_STOP_MAX;
+        a.status[HM_DE_BEST_INDEX] = idx[0];
+        a.status[HM_DE_BEST_ENERGY] = __double_as_longlong(best);
+        a.status[HM_DE_MEAN] = __double_as_longlong(mean);
+        a.status[HM_DE_STD] = __double_as_longlong(sd);
+        a.status[HM_DE_EVALUATIONS] += S;
+        a.status[HM_DE_STOP] = stop;
+        a.status[HM_DE_GENERATION] = g + 1;
+    }
+}
+
+}  // namespace hm
+
+using namespace hm;
+
+extern "C" size_t hm_de_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size) {
+    if (pop_size < 4 || pop_size > HM_DE_MAX_POP) return 0;
+    return hm_linearity_energy_workspace_bytes(n_pixels, n_frames, pop_size);
+}
+
+extern "C" int hm_de_generation(double* population, double* energies, double* trial, double* trial_energies, double* icrf,
+                                uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca,
+                                const double* lower_limits, const double* upper_limits, const uint8_t* dn, const double* std,
+                                const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size,
+                                int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
+                                double recombination, double tol, double energy_limit, void* workspace, void* stream) {
+    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
+    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
+    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;      // also rejects NaN
+    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
+    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
+    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !exposures || !workspace) return HM_EINVAL;
+    DeK k{};
+    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
+    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
+    k.S = pop_size; k.P = n_params; k.seed = static_cast<uint64_t>(seed); k.max_generations = max_generations;
+    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
+    hipLaunchKernelGGL(k_de_trial, dim3(pop_size), dim3(256), 0, as_stream(stream), k);
+    int rc = launch_status();
+    if (rc != HM_OK) return rc;
+    rc = hm_linearity_energy(dn, std, exposures, icrf, valid, pop_size, lower, upper, 1, n_pixels, n_frames, nullptr,
+                             trial_energies, workspace, stream);
+    if (rc != HM_OK) return rc;
+    hipLaunchKernelGGL(k_de_select, dim3(1), dim3(256), 0, as_stream(stream), k);
+    return launch_status();
+}

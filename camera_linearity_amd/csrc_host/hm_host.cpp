@@ -1150,4 +1150,115 @@ int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exp
     return HM_OK;
 }
 
+// One generation of the ICRF-calibration differential evolution (calibration(), modules/ICRF_calibration_exposure.py:288-369), as
+// specified in hdrmerge.h: trial (mutation, crossover, redraw), candidate ICRF + verdicts, energy (hm_linearity_energy above),
+// deferred selection, statistics and the stop flag - the HIP build's hm_de.hip with host pointers.
+static inline uint64_t de_mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static inline double de_uniform(uint64_t key, int i, int k) {
+    return static_cast<double>(de_mix64(key + (static_cast<uint64_t>(i + 1) << 20) + static_cast<uint64_t>(k)) >> 11) * 0x1.0p-53;
+}
+static inline double de_tree_sum(std::vector<double>& v) {                // the HIP build's fixed-order tree (size: a power of two)
+    for (size_t s = v.size() >> 1; s > 0; s >>= 1)
+        for (size_t t = 0; t < s; ++t) v[t] += v[t + s];
+    return v[0];
+}
+
+size_t hm_de_workspace_bytes(int64_t, int, int) { return 0; }
+int hm_de_generation(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
+                     int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits,
+                     const double* upper_limits, const uint8_t* dn, const double* std_, const double* exposures, int64_t n_pixels,
+                     int n_frames, int lower, int upper, int pop_size, int n_params, int64_t seed, int64_t max_generations,
+                     double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit, void*, void*) {
+    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
+    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
+    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;
+    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
+    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
+    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !exposures) return HM_EINVAL;
+    if (status[HM_DE_STOP] != 0) return HM_OK;                            // after the stop flag a generation is a no-op
+    const int S = pop_size, P = n_params;
+    const int64_t g = status[HM_DE_GENERATION];
+    const uint64_t key = de_mix64(static_cast<uint64_t>(seed) ^ de_mix64(static_cast<uint64_t>(g)));
+    const double F = mutation_lo + (mutation_hi - mutation_lo) * de_uniform(key, S, 0);
+    const int b = std::min(std::max(static_cast<int>(status[HM_DE_BEST_INDEX]), 0), S - 1);
+    for (int i = 0; i < S; ++i) {
+        double x[HM_DE_MAX_PARAMS];
+        const double* ui = population + static_cast<int64_t>(i) * P;
+        double* tr = trial + static_cast<int64_t>(i) * P;
+        const int pick = std::min(static_cast<int>(std::floor(de_uniform(key, i, 0) * (S - 1))), S - 2);
+        const int r0 = pick + (pick >= i);
+        int c = std::min(static_cast<int>(std::floor(de_uniform(key, i, 1) * (S - 2))), S - 3);
+        const int lo2 = std::min(i, r0), hi2 = std::max(i, r0);
+        c += (c >= lo2);
+        c += (c >= hi2);
+        const int r1 = c;
+        const int fill = static_cast<int>(std::floor(de_uniform(key, i, 2) * P));
+        for (int j = 0; j < P; ++j) {
+            double v = ui[j];
+            if (g > 0 && (de_uniform(key, i, 3 + j) < recombination || j == fill)) {
+                const double ub = population[static_cast<int64_t>(b) * P + j], u0 = population[static_cast<int64_t>(r0) * P + j],
+                             u1 = population[static_cast<int64_t>(r1) * P + j];
+                v = ui[j] + F * (((ub - ui[j]) + u0) - u1);
+                if (!(v >= 0.0 && v <= 1.0)) v = de_uniform(key, i, 3 + P + j);          // SciPy's _ensure_constraint
+            }
+            tr[j] = v;
+            x[j] = lower_limits[j] + v * (upper_limits[j] - lower_limits[j]);
+        }
+        double* row = icrf + static_cast<int64_t>(i) * 256;
+        for (int d = 0; d < 256; ++d) {
+            double acc = 0.0;
+            for (int j = 0; j < P; ++j) acc += pca[d * P + j] * x[j];
+            row[d] = mean_icrf[d] + acc;
+        }
+        const double shift = 1.0 - row[255];
+        for (int d = 0; d < 256; ++d) row[d] += shift;                                   // :166
+        row[0] = 0.0;                                                                    // :167
+        bool ok = true;
+        for (int d = 0; d < 256; ++d)
+            if (row[d] > 1.0 || row[d] < 0.0 || (d > 0 && !(row[d] > row[d - 1]))) ok = false;   // :173-179
+        valid[i] = ok;
+    }
+    const int rc = hm_linearity_energy(dn, std_, exposures, icrf, valid, S, lower, upper, 1, n_pixels, n_frames, nullptr,
+                                       trial_energies, nullptr, nullptr);
+    if (rc != HM_OK) return rc;
+    size_t n = 1;
+    while (n < static_cast<size_t>(S)) n <<= 1;
+    std::vector<double> v(n, 0.0);
+    for (int i = 0; i < S; ++i) {
+        if (g == 0 || trial_energies[i] <= energies[i]) {
+            energies[i] = trial_energies[i];
+            std::memcpy(population + static_cast<int64_t>(i) * P, trial + static_cast<int64_t>(i) * P, sizeof(double) * P);
+        }
+        v[i] = energies[i];
+    }
+    const double mean = de_tree_sum(v) / S;
+    std::fill(v.begin(), v.end(), 0.0);
+    for (int i = 0; i < S; ++i) { const double d = energies[i] - mean; v[i] = d * d; }
+    const double sd = std::sqrt(de_tree_sum(v) / S);
+    int best = 0;
+    for (int i = 1; i < S; ++i) if (energies[i] < energies[best]) best = i;              // ties: the lowest index
+    int64_t stop = 0;
+    if (g > 0 && (g & 1) == 0) {
+        if (std::isfinite(mean) && sd == sd && sd <= tol * std::fabs(mean)) stop |= HM_DE_STOP_CONVERGED;
+        if (energies[best] < energy_limit) stop |= HM_DE_STOP_ENERGY;
+    }
+    if (g >= max_generations) stop |= HM_DE_STOP_MAX;
+    auto bits = [](double d) { int64_t q; std::memcpy(&q, &d, 8); return q; };
+    status[HM_DE_BEST_INDEX] = best;
+    status[HM_DE_BEST_ENERGY] = bits(energies[best]);
+    status[HM_DE_MEAN] = bits(mean);
+    status[HM_DE_STD] = bits(sd);
+    status[HM_DE_EVALUATIONS] += S;
+    status[HM_DE_STOP] = stop;
+    status[HM_DE_GENERATION] = g + 1;
+    return HM_OK;
+}
+
 }  // extern "C"

@@ -1131,3 +1131,131 @@ def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], 
                                               nat.ptr(out_pairs), energy.data_ptr(), ws.data_ptr(), _stream(dev)),
                   "hm_linearity_energy")
     return (energy, out_pairs) if return_pairs else energy
+
+
+# ------------------------------------------------------------------------------------------------
+# ICRF-calibration differential evolution (modules/ICRF_calibration_exposure.py:288-369), one generation per hm_de_generation call
+# ------------------------------------------------------------------------------------------------
+class DEPlan:
+    """The state of one channel's differential-evolution solve (population, energies, trial rows, candidate ICRFs, verdicts, status block,
+    workspace - all on the stack's device) and the launches that advance it. `launch()` enqueues ONE generation (hm_de_generation: trial
+    kernel, the energy kernels, select kernel); the generation counter and the stop flag live in the status block on the device, so
+    `run()` records `check_every` generations once into a hipGraph - a linear chain, no parallel branches - and replays it, reading
+    the status block back once per replay. `graph=False` issues the same calls eagerly. After the stop flag is set a generation is a
+    no-op, so the result does not depend on `check_every`. Built inside nat.host_mode() on a host stack, it calls the host build in a
+    loop (no graph)."""
+
+    def __init__(self, dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], mean_icrf, pca,
+                 lower_limits, upper_limits, population, lower: int, upper: int, seed: int, max_generations: int,
+                 mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0):
+        _require_cuda(dn_stack, "image_value_stack")
+        if dn_stack.dtype != torch.uint8:
+            raise TypeError("image_value_stack must be uint8 digital numbers")
+        if dn_stack.dim() != 3:
+            raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")             # ICRF_calibration_exposure.py:82-83
+        dev = dn_stack.device
+        self.device = dev
+        self.host = dev.type != "cuda"
+        N = dn_stack.shape[2]
+        t = np.asarray(exposures, dtype=np.float64)
+        if t.ndim != 1 or t.size != N:
+            raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
+        self.dn = dn_stack.contiguous()
+        self.std = None
+        if std_stack is not None:
+            _require_cuda(std_stack, "image_std_stack")
+            if std_stack.shape != dn_stack.shape or std_stack.dtype != _F64:
+                raise ValueError("image_std_stack must be float64 and shaped like image_value_stack")
+            self.std = std_stack.contiguous()
+        pop = np.ascontiguousarray(np.asarray(population, dtype=np.float64))
+        if pop.ndim != 2:
+            raise ValueError("population must be (S, P) in scaled coordinates [0, 1]")
+        S, P = pop.shape
+        self.S, self.P, self.N = S, P, N
+        self.n_pixels = dn_stack.shape[0] * dn_stack.shape[1]
+        self.mean_icrf = _dev_f64(np.asarray(mean_icrf, dtype=np.float64).reshape(-1), dev)
+        self.pca = _dev_f64(np.asarray(pca, dtype=np.float64), dev)
+        if self.mean_icrf.numel() != BITS or tuple(self.pca.shape) != (BITS, P):
+            raise ValueError(f"mean ICRF must have {BITS} entries and the PCA basis must be ({BITS}, {P})")
+        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.population = torch.as_tensor(pop, device=dev).clone()
+        self.energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
+        self.trial = torch.zeros((S, P), dtype=_F64, device=dev)
+        self.trial_energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
+        self.icrf = torch.zeros((S, BITS), dtype=_F64, device=dev)
+        self.valid = torch.zeros(S, dtype=_U8, device=dev)
+        self.status = torch.zeros(nat.HM_DE_STATUS_WORDS, dtype=torch.int64, device=dev)
+        self._t = (C.c_double * N)(*t.tolist())
+        self._scalars = (int(lower), int(upper), int(S), int(P), C.c_int64(int(seed) & 0xFFFFFFFFFFFFFFFF).value,
+                         int(max_generations), float(mutation[0]), float(mutation[1]), float(recombination), float(tol),
+                         float(energy_limit))
+        with nat.host_mode() if self.host else _NoDevice():
+            ws_bytes = nat.lib.hm_de_workspace_bytes(self.n_pixels, N, S)
+        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+        self._graph = None
+        self._graph_len = 0
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        """Enqueue one generation on `stream` (default: the current stream of the plan's device)."""
+        lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
+
+        def call(st):
+            return nat.lib.hm_de_generation(self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
+                                            self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
+                                            self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(), self.lo.data_ptr(),
+                                            self.hi.data_ptr(), self.dn.data_ptr(), nat.ptr(self.std), self._t, self.n_pixels, self.N,
+                                            lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim, self.workspace.data_ptr(), st)
+        if self.host:
+            with nat.host_mode():
+                nat.check(call(None), "hm_de_generation")
+            return
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with _on(self.device):
+            rc = call(stream)
+        if rc:
+            nat.check(rc, "hm_de_generation")
+
+    def read_status(self) -> dict:
+        """The status block, copied to the host (this synchronises): generation = the number of generations after the initial
+        evaluation that have run."""
+        w = self.status.cpu().numpy()
+        f = w.view(np.float64)
+        return dict(generation=int(w[nat.HM_DE_GENERATION]) - 1, best_index=int(w[nat.HM_DE_BEST_INDEX]), stop=int(w[nat.HM_DE_STOP]),
+                    evaluations=int(w[nat.HM_DE_EVALUATIONS]), best_energy=float(f[nat.HM_DE_BEST_ENERGY]),
+                    mean=float(f[nat.HM_DE_MEAN]), std=float(f[nat.HM_DE_STD]))
+
+    def _record(self, n: int) -> None:
+        """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
+        dev = self.device
+        with torch.cuda.device(dev):
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                self.launch(side.cuda_stream)           # first launches load the kernels' code objects: outside the capture
+                self._graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._graph, stream=side):
+                    for _ in range(n):
+                        self.launch(side.cuda_stream)
+            torch.cuda.current_stream(dev).wait_stream(side)
+        self._graph_len = n
+
+    def run(self, check_every: int = 8, graph: bool = True) -> dict:
+        """Advance until the stop flag is set: `check_every` generations per status read. -> the final read_status()."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1")
+        use_graph = graph and not self.host
+        if use_graph and self._graph_len != check_every:
+            self._record(check_every)                   # (runs generation 0 as its warm-up launch)
+        while True:
+            if use_graph:
+                with _on(self.device):
+                    self._graph.replay()
+            else:
+                for _ in range(check_every):
+                    self.launch()
+            st = self.read_status()
+            if st["stop"]:
+                return st

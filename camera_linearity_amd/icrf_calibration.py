@@ -4,12 +4,14 @@ The reference minimises, per channel, an energy function with SciPy's differenti
 evaluation maps the (X, Y, N) channel stack through a candidate ICRF and reduces an (X, Y, N, N) array of
 pairwise relative differences on the host (ICRF_calibration_exposure.py:66-201), one candidate at a time.
 Here the stack stays on the device and `hm_linearity_energy` evaluates a whole POPULATION of candidates in one
-launch (grid = pixel chunks x frame pairs x candidates); the solver itself stays SciPy's, on the host, driven
-through its `vectorized=True` interface (one launch per generation) or, for the reference's exact update
-order, one candidate per call.
+launch (grid = pixel chunks x frame pairs x candidates). By default (`solver="scipy"`) the solver itself stays SciPy's,
+on the host, driven through its `vectorized=True` interface (one launch per generation) or, for the reference's exact
+update order, one candidate per call; the candidate ICRF (mean + PCA product, shift, range / monotonicity rejection:
+:22-45,:166-179) is then 256 numbers per candidate formed on the host with NumPy, like the reference.
 
-The candidate ICRF (mean + PCA product, shift, range / monotonicity rejection: :22-45,:166-179) is 256 numbers
-per candidate and is formed on the host with NumPy, like the reference.
+`solver="device"` runs the whole generation - mutation, crossover, candidate ICRFs and their verdicts, energy, selection,
+convergence statistics - where the stack lives (hm_de_generation, engine.DEPlan): the same strategy and settings, restated
+with counter-based random numbers (include/hdrmerge.h), started from SciPy's own Sobol population.
 """
 from __future__ import annotations
 
@@ -138,11 +140,21 @@ def initialize_channel_image_stacks(frames: Sequence, exposures: Sequence[float]
 def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values,
                   lower_PCA_limit: float, upper_PCA_limit: float, use_mean_ICRF: bool = True,
                   data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, seed=7,
-                  max_iterations: int = 1000, vectorized: bool = True, popsize: int = 15, channel: int = 0, verbose: bool = False):
+                  max_iterations: int = 1000, vectorized: bool = True, popsize: int = 15, channel: int = 0, verbose: bool = False,
+                  solver: str = "scipy", check_every: int = 8, graph: bool = True, tol: float = 0.01):
     """The per-channel solve of calibration() (:329-369): SciPy's DifferentialEvolutionSolver with the reference's
     settings. vectorized=True evaluates each generation's population in ONE launch (SciPy then uses deferred updating);
     vectorized=False keeps the reference's immediate updating and evaluates one candidate per launch.
+    solver="device": the generations run on the stack's backend (engine.DEPlan; deferred updating, SciPy's initial population, the
+    library's own random numbers), `check_every` generations per status read, recorded as a hipGraph unless graph=False; `vectorized`
+    does not apply. An iteration is two generations, as in the reference loop. `tol` is the solver's relative convergence tolerance
+    (the reference's 0.01) for either solver.
     -> (ICRF of the channel (256,), final energy, iterations)."""
+    if solver not in ("scipy", "device"):
+        raise ValueError(f"solver must be 'scipy' or 'device', got {solver!r}")
+    if solver == "device" and not use_mean_ICRF:
+        raise NotImplementedError('solver="device" forms candidates from a mean ICRF only; the power-law base (use_mean_ICRF=False) needs '
+                                  'solver="scipy"')
     PCA_array = np.asarray(PCA_array, dtype=np.float64)
     n_params = PCA_array.shape[1] + (0 if use_mean_ICRF else 1)
     limits, x0 = [], []
@@ -158,9 +170,24 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     extra = dict(vectorized=True, updating="deferred") if vectorized else {}
     # the reference passes seed= (SciPy 1.14, its Pipfile.lock); SciPy >= 1.15 renamed the argument to rng=
     extra["rng" if "rng" in inspect.signature(DifferentialEvolutionSolver.__init__).parameters else "seed"] = seed
+    if solver == "device":
+        # SciPy's own initial population (Sobol, same seed), read without iterating: both solvers start from the same S x P points
+        with DifferentialEvolutionSolver(_energy_function, limits, args=args, strategy="currenttobest1bin", tol=tol, x0=x0,
+                                         mutation=(0, 1.95), recombination=0.4, init="sobol", popsize=popsize, **extra) as start:
+            population = np.array(start.population, dtype=np.float64)
+        if not isinstance(seed, (int, np.integer)):
+            raise TypeError('solver="device" needs an integer seed')
+        lo, hi = np.asarray(limits, dtype=np.float64).T
+        plan = _engine_for(image_value_stack).DEPlan(image_value_stack, image_std_stack, _host(exposure_values), mean_ICRF_array, PCA_array,
+                                                     lo, hi, population, data_limits[0], data_limits[1], int(seed), 2 * int(max_iterations),
+                                                     (0.0, 1.95), 0.4, tol, energy_limit)
+        st = plan.run(check_every, graph)
+        u = plan.population[st["best_index"]].cpu().numpy()
+        icrf = _inverse_camera_response_function(mean_ICRF_array, PCA_array, lo + u * (hi - lo), use_mean_ICRF)
+        return icrf, st["best_energy"], st["generation"] // 2
     number_of_iterations = 0
     func_value = np.inf
-    with DifferentialEvolutionSolver(_energy_function, limits, args=args, strategy="currenttobest1bin", tol=0.01, x0=x0,
+    with DifferentialEvolutionSolver(_energy_function, limits, args=args, strategy="currenttobest1bin", tol=tol, x0=x0,
                                      mutation=(0, 1.95), recombination=0.4, init="sobol", popsize=popsize,
                                      **extra) as solver:                          # :344-347
         for step in solver:
@@ -182,7 +209,7 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
 def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_stacks, channel_image_std_stacks, exposure_values,
                 lower_PCA_limit: float, upper_PCA_limit: float, initial_function=None,
                 data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, rng_seed: int = 7,
-                vectorized: bool = True, max_iterations: int = 1000, popsize: int = 15):
+                vectorized: bool = True, max_iterations: int = 1000, popsize: int = 15, solver: str = "scipy"):
     """calibration() (:287-405) from arrays: per-channel mean ICRF (or `initial_function`) and PCA basis, the channel stacks
     of initialize_channel_image_stacks. The channels are solved one after another on this process's GPU (the reference
     forks one joblib worker per channel, :383; with one process per GPU, give each rank a channel instead).
@@ -194,7 +221,7 @@ def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_
         base = mean_ICRFs[c] if use_mean_ICRF else initial_function
         icrf_c, energies[c], _ = solve_channel(base, PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
                                                exposure_values, lower_PCA_limit, upper_PCA_limit, use_mean_ICRF, data_limits,
-                                               energy_limit, rng_seed + c, max_iterations, vectorized, popsize, c)
+                                               energy_limit, rng_seed + c, max_iterations, vectorized, popsize, c, solver=solver)
         results.append(icrf_c)
     ICRF = np.stack(results, axis=1)
     ICRF += (1 - ICRF[-1, :])[None, :]                                           # :390

@@ -425,6 +425,71 @@ int hm_linearity_energy(const uint8_t* dn, const double* std /*nullable*/, const
                         double* out_pairs /*nullable*/, double* out_energy, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ICRF-calibration differential evolution, one generation per call: the solver loop of calibration(),
+ * modules/ICRF_calibration_exposure.py:288-369 (SciPy's DifferentialEvolutionSolver with strategy 'currenttobest1bin',
+ * mutation (0, 1.95), recombination 0.4, tol 0.01, deferred updating), restated so that it needs no generator state:
+ * every random number is a pure function of (seed, generation, member, draw index).
+ *
+ *   mix64(z)   the splitmix64 step: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *              z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31                       (uint64, wrapping)
+ *   key_g      mix64(seed ^ mix64(g))
+ *   U(g, i, k) (mix64(key_g + ((i + 1) << 20) + k) >> 11) * 2^-53                               in [0, 1)
+ *
+ * Member i of the S members holds P parameters u in SciPy's scaled coordinates [0, 1]; x = lo + u (hi - lo).
+ * Generation 0 evaluates the population as it is (the trial IS the member, no draws) and accepts every energy.
+ * Generation g >= 1, with b the best member (lowest energy, ties to the lowest index) of the population before it:
+ *   dither     F = mutation_lo + (mutation_hi - mutation_lo) U(g, S, 0)
+ *   picks      a = floor(U(g,i,0) (S-1)), r0 = a + (a >= i);  c = floor(U(g,i,1) (S-2)), lo2 < hi2 the sorted {i, r0},
+ *              c += (c >= lo2), then c += (c >= hi2), r1 = c          (r0, r1 distinct, both different from i)
+ *   trial      v = u_i + F (u_b - u_i + u_r0 - u_r1);  fill = floor(U(g,i,2) P);  component j is v_j where
+ *              U(g,i,3+j) < recombination or j == fill, else u_i[j];  a component outside [0, 1] becomes U(g,i,3+P+j)
+ *   candidate  row = mean_icrf + pca @ x, row += 1 - row[255], row[0] = 0 (:166-167); valid unless an entry is > 1 or < 0
+ *              or the row is not strictly increasing (:173-179); the energy of an invalid row is +inf
+ *   energy     hm_linearity_energy on the S trial rows (use_relative = 1)
+ *   selection  the trial replaces member i where E_trial <= E_i (all members see the population of before: deferred)
+ *   statistics best index, mean(E), population std(E) (ddof 0) - fixed-order tree reductions
+ *   stop       after every EVEN generation g >= 2 (the reference loop advances two generations per pass, :351):
+ *              HM_DE_STOP_CONVERGED  all E finite and std(E) <= tol |mean(E)|        (solver.converged(), :356)
+ *              HM_DE_STOP_ENERGY     E_best < energy_limit                           (:356)
+ *              and after any generation g >= max_generations: HM_DE_STOP_MAX
+ *   Once status[HM_DE_STOP] != 0 a call changes nothing any more: calls may be issued (or replayed from a graph) in
+ *   batches of any size without the result depending on the batch size.
+ *
+ * State, all caller-owned device memory (host memory in the host build), nothing else is kept between calls:
+ *   population (S, P), energies (S), trial (S, P), trial_energies (S), icrf (S, 256) float64; valid (S) uint8;
+ *   status     HM_DE_STATUS_WORDS 64-bit words, zeroed by the caller before generation 0: int64 in GENERATION (the
+ *              generation the NEXT call runs; advanced by the last kernel of a call), BEST_INDEX, STOP, EVALUATIONS;
+ *              float64 bit patterns in BEST_ENERGY, MEAN, STD
+ *   mean_icrf (256), pca (256, P) row-major, lower_limits (P), upper_limits (P): float64 on the device
+ *   dn, std, exposures [host], n_pixels, n_frames, lower, upper: as for hm_linearity_energy
+ *   workspace  hm_de_workspace_bytes(n_pixels, n_frames, pop_size) bytes
+ * 4 <= pop_size <= HM_DE_MAX_POP, 1 <= n_params <= HM_DE_MAX_PARAMS, 0 <= mutation_lo <= mutation_hi < 2,
+ * 0 <= recombination <= 1, tol >= 0. No allocation, no host synchronisation, no float atomics: the same state gives
+ * the same bits on every run, launched eagerly or replayed from a graph.
+ * ------------------------------------------------------------------------------------------ */
+#define HM_DE_MAX_POP 1024
+#define HM_DE_MAX_PARAMS 32
+#define HM_DE_STATUS_WORDS 8
+#define HM_DE_GENERATION 0
+#define HM_DE_BEST_INDEX 1
+#define HM_DE_STOP 2
+#define HM_DE_EVALUATIONS 3
+#define HM_DE_BEST_ENERGY 4
+#define HM_DE_MEAN 5
+#define HM_DE_STD 6
+#define HM_DE_STOP_CONVERGED 1
+#define HM_DE_STOP_ENERGY 2
+#define HM_DE_STOP_MAX 4
+size_t hm_de_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size);
+int hm_de_generation(double* population, double* energies, double* trial, double* trial_energies, double* icrf,
+                     uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca,
+                     const double* lower_limits, const double* upper_limits, const uint8_t* dn,
+                     const double* std /*nullable*/, const double* exposures /*[host]*/, int64_t n_pixels, int n_frames,
+                     int lower, int upper, int pop_size, int n_params, int64_t seed, int64_t max_generations,
+                     double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit,
+                     void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-disk formats: host-side strip decoders for the TIFF files the reference exchanges with
  * OpenCV (modules/image_set.py:214-243 cv.imread, :264-363 cv.imwrite). HOST pointers, no device work, re-entrant.
  * Return the number of bytes written to dst, HM_EINVAL for a corrupt stream, HM_ESHAPE if dst_cap is too small.
