@@ -23,6 +23,7 @@ HM_MAX_CHANNELS = 4
 HM_MAX_DIMS = 6
 HM_KDE_MOMENTS = 11
 HM_DE_MAX_POP, HM_DE_MAX_PARAMS, HM_DE_STATUS_WORDS = 1024, 32, 8
+HM_DE_MAX_PROBLEMS = 64
 HM_DE_GENERATION, HM_DE_BEST_INDEX, HM_DE_STOP, HM_DE_EVALUATIONS, HM_DE_BEST_ENERGY, HM_DE_MEAN, HM_DE_STD = range(7)
 HM_DE_STOP_CONVERGED, HM_DE_STOP_ENERGY, HM_DE_STOP_MAX = 1, 2, 4
 
@@ -136,6 +137,10 @@ _SIGNATURES = {
     "hm_de_generation": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_void_p, C.c_void_p]),
+    "hm_de_batch_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "hm_de_generation_batch": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,9 +13,19 @@
 // stop flag live in the status block on the device, so the same recorded launches can be replayed (hipGraph); after the stop flag is
 // set k_de_trial and k_de_select return before their first store (the energy kernels re-evaluate the unchanged trial rows to the same
 // bits), so the state no longer moves however many generations follow.
+//
+// hm_de_generation_batch advances K problems of one shape by the same three stages: k_de_trial_batch, grid = (S, K);
+// energy_batch() (hm_energy.hip), candidates K x S, geometry from the per-problem S; k_de_select_batch, grid = K. The kernel
+// bodies are the single-problem ones (k_de_trial's shared, k_de_select's repeated as de_select_body) applied to problem k's slices of
+// the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
 #include "hm_common.h"
 
 namespace hm {
+
+// hm_energy.hip: the energy stage of hm_de_generation_batch (K problems x S candidates per launch; see there)
+int energy_batch(const uint8_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
+                 const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels,
+                 int n_frames, double* out_energy, void* workspace, hipStream_t st);
 
 struct DeK {
     double* pop;              // (S, P) scaled to [0, 1]
@@ -47,12 +57,29 @@ __device__ __forceinline__ double de_uniform(uint64_t key, int i, int k) {
     return static_cast<double>(r >> 11) * 0x1.0p-53;
 }
 
-__global__ __launch_bounds__(256) void k_de_trial(const DeK a) {
+// the seeds of a batch travel in the kernel arguments, like the stack pointers of its energy stage
+struct DeSeeds {
+    uint64_t seed[HM_DE_MAX_PROBLEMS];
+};
+
+// problem k of a batch: its slices of the (K, ...) state arrays and its seed; everything else is shared
+__device__ __forceinline__ DeK problem_of(const DeK& a, const DeSeeds& sd, const int k) {
+    DeK r = a;
+    const int64_t S = a.S, P = a.P;
+    r.pop += k * S * P; r.energy += k * S; r.trial += k * S * P; r.trial_energy += k * S; r.icrf += k * S * 256;
+    r.valid += k * S; r.status += static_cast<int64_t>(k) * HM_DE_STATUS_WORDS; r.mean_icrf += static_cast<int64_t>(k) * 256;
+    r.pca += k * 256 * P;
+    r.seed = sd.seed[k];
+    return r;
+}
+
+// (i: the member)
+__device__ __forceinline__ void de_trial_body(const DeK& a, const int i) {
     __shared__ double x[HM_DE_MAX_PARAMS];
     __shared__ double last;
     __shared__ int bad[4];
     if (a.status[HM_DE_STOP] != 0) return;                                // uniform: the whole generation is a no-op
-    const int i = blockIdx.x, lane = threadIdx.x, P = a.P, S = a.S;
+    const int lane = threadIdx.x, P = a.P, S = a.S;
     const int64_t g = a.status[HM_DE_GENERATION];
 
     if (lane < P) {
@@ -105,6 +132,12 @@ __global__ __launch_bounds__(256) void k_de_trial(const DeK a) {
     if ((lane & 63) == 0) bad[lane >> 6] = any != 0ull;
     __syncthreads();
     if (lane == 0) a.valid[i] = !(bad[0] | bad[1] | bad[2] | bad[3]);
+}
+
+__global__ __launch_bounds__(256) void k_de_trial(const DeK a) { de_trial_body(a, blockIdx.x); }
+
+__global__ __launch_bounds__(256) void k_de_trial_batch(const DeK a, const DeSeeds sd) {
+    de_trial_body(problem_of(a, sd, blockIdx.y), blockIdx.x);
 }
 
 // fixed-order tree over n (a power of two <= HM_DE_MAX_POP) LDS entries; the result is in v[0]
@@ -178,6 +211,74 @@ __global__ __launch_bounds__(256) void k_de_select(const DeK a) {
     }
 }
 
+// k_de_select's body once more, for k_de_select_batch: the single-problem kernel stays a kernel of its own text because routing it
+// through a shared device function moved its register allocation; the bytes-equal tests of the batch against single plans hold
+// the two copies to the same arithmetic
+__device__ __forceinline__ void de_select_body(const DeK& a) {
+    __shared__ double e[HM_DE_MAX_POP];
+    __shared__ double v[HM_DE_MAX_POP];
+    __shared__ int idx[HM_DE_MAX_POP];
+    if (a.status[HM_DE_STOP] != 0) return;
+    const int S = a.S, P = a.P;
+    const int64_t g = a.status[HM_DE_GENERATION];
+    int n = 1;
+    while (n < S) n <<= 1;
+
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double ei = __builtin_inf();
+        if (i < S) {
+            const double et = a.trial_energy[i];
+            ei = a.energy[i];
+            if (g == 0 || et <= ei) {                                     // deferred updating: every trial saw the old population
+                ei = et;
+                a.energy[i] = et;
+                for (int j = 0; j < P; ++j) a.pop[static_cast<int64_t>(i) * P + j] = a.trial[static_cast<int64_t>(i) * P + j];
+            }
+        }
+        e[i] = ei;
+        v[i] = i < S ? ei : 0.0;
+        idx[i] = i;
+    }
+    __syncthreads();
+    tree_sum(v, n);
+    const double mean = v[0] / S;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double d = e[i] - mean;
+        v[i] = i < S ? d * d : 0.0;
+    }
+    __syncthreads();
+    tree_sum(v, n);
+    const double sd = sqrt(v[0] / S);
+    // lowest energy, ties to the lowest index (the padding is +inf with an index >= S, so it never wins a tie)
+    for (int s = n >> 1; s > 0; s >>= 1) {
+        for (int t = threadIdx.x; t < s; t += blockDim.x) {
+            const double x0 = e[t], x1 = e[t + s];
+            const int i0 = idx[t], i1 = idx[t + s];
+            if (x1 < x0 || (x1 == x0 && i1 < i0)) { e[t] = x1; idx[t] = i1; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double best = e[0];
+        int64_t stop = 0;
+        if (g > 0 && (g & 1) == 0) {                                      // the reference loop advances two generations per pass (:351)
+            if (isfinite(mean) && sd == sd && sd <= a.tol * fabs(mean)) stop |= HM_DE_STOP_CONVERGED;   // mean finite <=> every E finite
+            if (best < a.energy_limit) stop |= HM_DE_STOP_ENERGY;
+        }
+        if (g >= a.max_generations) stop |= HM_DE_STOP_MAX;
+        a.status[HM_DE_BEST_INDEX] = idx[0];
+        a.status[HM_DE_BEST_ENERGY] = __double_as_longlong(best);
+        a.status[HM_DE_MEAN] = __double_as_longlong(mean);
+        a.status[HM_DE_STD] = __double_as_longlong(sd);
+        a.status[HM_DE_EVALUATIONS] += S;
+        a.status[HM_DE_STOP] = stop;
+        a.status[HM_DE_GENERATION] = g + 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_de_select_batch(const DeK a, const DeSeeds sd) { de_select_body(problem_of(a, sd, blockIdx.x)); }
+
 }  // namespace hm
 
 using namespace hm;
@@ -213,5 +314,52 @@ extern "C" int hm_de_generation(double* population, double* energies, double* tr
                              trial_energies, workspace, stream);
     if (rc != HM_OK) return rc;
     hipLaunchKernelGGL(k_de_select, dim3(1), dim3(256), 0, as_stream(stream), k);
+    return launch_status();
+}
+
+static bool de_batch_shape_ok(int pop_size, int n_problems) {
+    return pop_size >= 4 && pop_size <= HM_DE_MAX_POP && n_problems >= 1 && n_problems <= HM_DE_MAX_PROBLEMS &&
+           n_problems * pop_size <= 65535;
+}
+
+extern "C" size_t hm_de_batch_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size, int n_problems) {
+    if (!de_batch_shape_ok(pop_size, n_problems)) return 0;
+    return hm_linearity_energy_workspace_bytes(n_pixels, n_frames, pop_size) * static_cast<size_t>(n_problems);
+}
+
+extern "C" int hm_de_generation_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies,
+                                      double* icrf, uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca,
+                                      const double* lower_limits, const double* upper_limits, const uint8_t* const* dn,
+                                      const double* const* std, const int64_t* seeds, const double* exposures, int64_t n_pixels,
+                                      int n_frames, int lower, int upper, int pop_size, int n_params, int64_t max_generations,
+                                      double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit,
+                                      void* workspace, void* stream) {
+    if (n_problems < 1) return HM_EINVAL;
+    if (n_problems > HM_DE_MAX_PROBLEMS) return HM_ESHAPE;
+    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
+    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    if (n_problems * pop_size > 65535) return HM_EUNSUPPORTED;                // the energy grid's candidate dimension
+    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
+    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;      // also rejects NaN
+    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
+    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
+    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !seeds || !exposures || !workspace) return HM_EINVAL;
+    for (int i = 0; i < n_problems; ++i)                                      // host arrays: read within the validated K only
+        if (!dn[i] || (std && !std[i])) return HM_EINVAL;                     // stds for all problems or for none
+    DeK k{};
+    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
+    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
+    k.S = pop_size; k.P = n_params; k.max_generations = max_generations;
+    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
+    DeSeeds sd{};
+    for (int i = 0; i < n_problems; ++i) sd.seed[i] = static_cast<uint64_t>(seeds[i]);
+    hipLaunchKernelGGL(k_de_trial_batch, dim3(pop_size, n_problems), dim3(256), 0, as_stream(stream), k, sd);
+    int rc = launch_status();
+    if (rc != HM_OK) return rc;
+    rc = energy_batch(dn, std, status, n_problems, pop_size, exposures, icrf, valid, lower, upper, n_pixels, n_frames, trial_energies,
+                      workspace, as_stream(stream));
+    if (rc != HM_OK) return rc;
+    hipLaunchKernelGGL(k_de_select_batch, dim3(n_problems), dim3(256), 0, as_stream(stream), k, sd);
     return launch_status();
 }

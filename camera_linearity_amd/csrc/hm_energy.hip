@@ -21,6 +21,14 @@
 // from registers (see k_energy_pixel). The reference evaluates one candidate at a time on the host. The sums are
 // formed in a fixed order (lane-strided, shuffle tree, chunk order), so results are reproducible run to run;
 // they differ from NumPy's pairwise summation in the last bits (tests: 1e-12 relative).
+//
+// Batched forms (k_energy_pixel_batch, k_energy_partial_batch, k_energy_final_batch; energy_batch() below) serve
+// hm_de_generation_batch: the candidate dimension spans K problems x S candidates, candidate b belongs to problem b / S and
+// reads THAT problem's stack, and the workgroups of a problem whose stop flag is set return before their first store. The
+// kernel bodies repeat the single-stack kernels' operation for operation (energy_pixel_body, energy_partial_body; k_energy_final's
+// is shared) and the geometry and the chunk count come from the per-problem S and pixel count (energy_pixel_major,
+// energy_chunks), so a candidate's sums are formed in the same order - the same bits - whether its problem is evaluated alone
+// or in a batch.
 #include "hm_common.h"
 
 namespace hm {
@@ -43,6 +51,25 @@ struct EnergyPairs {
     double ratio[kEnergyRegPairs];
     double inv_ratio[kEnergyRegPairs];
 };
+
+// the problems of a batch: the stacks travel in the kernel arguments (a recorded graph holds them by value)
+struct EnergyBatch {
+    const uint8_t* dn[HM_DE_MAX_PROBLEMS];   // (P, N) each
+    const double* sd[HM_DE_MAX_PROBLEMS];    // (P, N) each; read only by the STD kernels
+    const int64_t* status;                   // (K, HM_DE_STATUS_WORDS): the stop flags
+    int32_t S;                               // candidates per problem
+};
+
+__device__ __forceinline__ bool batch_stopped(const EnergyBatch& q, int k) {
+    return q.status[static_cast<int64_t>(k) * HM_DE_STATUS_WORDS + HM_DE_STOP] != 0;
+}
+
+// the arguments of problem k's candidates: the shared ones, reading that problem's stack
+__device__ __forceinline__ EnergyK on_stack_of(const EnergyK& a, const EnergyBatch& q, int k) {
+    EnergyK r = a;
+    r.dn = q.dn[k]; r.sd = q.sd[k];
+    return r;
+}
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -112,6 +139,73 @@ __global__ __launch_bounds__(256) void k_energy_partial(const EnergyK a) {
         out[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
         out[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
     }
+}
+
+// k_energy_partial's body once more, for k_energy_partial_batch: the single-stack kernel stays a kernel of its own text because
+// routing it through a shared device function moved its register allocation; the bytes-equal tests
+// of the batch against single plans hold the two copies to the same arithmetic
+template <bool STD>
+__device__ __forceinline__ void energy_partial_body(const EnergyK a) {
+    __shared__ double lut[256];
+    __shared__ double red[4][2];
+    const int b = blockIdx.z;
+    double* out = a.partial + ((static_cast<int64_t>(b) * gridDim.y + blockIdx.y) * a.chunks + blockIdx.x) * 2;
+    if (a.valid && !a.valid[b]) {                     // uniform per workgroup
+        if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; }
+        return;
+    }
+    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
+    __syncthreads();
+    int i, j;
+    pair_of(blockIdx.y, a.N, i, j);
+    const double lo = lut[a.lower], hi = lut[a.upper];
+    const double ratio = a.t[i] / a.t[j];
+    const int N = a.N;
+
+    double num = 0.0, den = 0.0;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < a.P; p += stride) {
+        const uint8_t* px = a.dn + p * N;
+        double vi = lut[px[i]], vj = lut[px[j]];
+        if (vi < lo || vi > hi) vi = __builtin_nan("");
+        if (vj < lo || vj > hi) vj = __builtin_nan("");
+        const double scaled = vj * ratio;
+        double d = vi - scaled;
+        if (a.relative) d = d / scaled;
+        const double ad = fabs(d);
+        if (STD) {
+            const double si = a.sd[p * N + i], sj = a.sd[p * N + j];
+            double sigma;
+            if (a.relative) {
+                const double u = si / scaled;
+                const double v = (vi * sj) / (ratio * (vj * vj));
+                sigma = sqrt(u * u + v * v);
+            } else {
+                const double v = ratio * sj;
+                sigma = sqrt(si * si + v * v);
+            }
+            const bool finite = isfinite(ad) && sigma != 0.0;
+            const double w = 1.0 / sigma;
+            if (finite && w == w) { num += ad * w; den += w; }
+        } else {
+            if (ad == ad) { num += ad; den += 1.0; }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double s0 = wave_sum(num), s1 = wave_sum(den);
+    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        out[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+template <bool STD>
+__global__ __launch_bounds__(256) void k_energy_partial_batch(const EnergyK a, const EnergyBatch q) {
+    const int k = blockIdx.z / q.S;
+    if (batch_stopped(q, k)) return;                  // uniform per workgroup: a stopped problem costs no pixel work
+    energy_partial_body<STD>(on_stack_of(a, q, k));
 }
 
 // Pixel-major evaluation for N <= 8 frames: a thread owns pixels, reads their N samples (and stds) once, maps them
@@ -219,11 +313,94 @@ __global__ __launch_bounds__(256) void k_energy_pixel(const EnergyK a, const Ene
     }
 }
 
+// k_energy_pixel's body once more, for k_energy_pixel_batch (a copy for the same reason as energy_partial_body)
+template <int N, bool STD>
+__device__ __forceinline__ void energy_pixel_body(const EnergyK a, const EnergyPairs pr) {
+    constexpr int P = N * (N - 1) / 2;
+    __shared__ double lut[256];
+    __shared__ double red[4][2 * P];
+    const int b = blockIdx.y;
+    const int pairs = P;
+    auto out_of = [&](int p) { return a.partial + ((static_cast<int64_t>(b) * pairs + p) * a.chunks + blockIdx.x) * 2; };
+    if (a.valid && !a.valid[b]) {
+        if (threadIdx.x < P) { double* o = out_of(threadIdx.x); o[0] = 0.0; o[1] = 0.0; }
+        return;
+    }
+    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
+    __syncthreads();
+    const double lo = lut[a.lower], hi = lut[a.upper];
+    const bool rel = a.relative != 0;
+    double num[P], den[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) { num[p] = 0.0; den[p] = 0.0; }
+
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t px = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; px < a.P; px += stride) {
+        const uint8_t* q = a.dn + px * N;
+        double v[N], rv[N], s[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double x = lut[q[i]];
+            if (x < lo || x > hi) x = __builtin_nan("");                       // :96-97
+            v[i] = x;
+            rv[i] = HM_ENERGY_RCP ? rcp_second_order(x) : 1.0 / x;
+            s[i] = STD ? a.sd[px * N + i] : 0.0;
+        }
+        int p = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+#pragma unroll
+            for (int j = i + 1; j < N; ++j, ++p) {
+                const double ratio = pr.ratio[p];
+                const double scaled = v[j] * ratio;                             // :111
+                double d = v[i] - scaled;                                        // :114
+                double inv_s = 0.0;
+                if (rel) { inv_s = rv[j] * pr.inv_ratio[p]; d = d * inv_s; }     // :117  d / scaled
+                const double ad = fabs(d);                                       // :120
+                if (STD) {
+                    double qq;
+                    if (rel) {
+                        const double u = s[i] * inv_s;                           // s_i / scaled
+                        const double w2 = ((v[i] * s[j]) * inv_s) * rv[j];       // (v_i s_j) / (ratio v_j^2)        :127
+                        qq = u * u + w2 * w2;
+                    } else {
+                        const double w2 = ratio * s[j];
+                        qq = s[i] * s[i] + w2 * w2;                              // :129
+                    }
+                    const double w = rsqrt_third_order(qq);                      // 1 / sigma
+                    const bool ok = isfinite(ad) && qq != 0.0 && w == w;         // :133-134, general_functions.py:164
+                    if (ok) { num[p] += ad * w; den[p] += w; }
+                } else {
+                    if (ad == ad) { num[p] += ad; den[p] += 1.0; }               // :138
+                }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const double s0 = wave_sum(num[p]), s1 = wave_sum(den[p]);
+        if (lane == 0) { red[wave][2 * p] = s0; red[wave][2 * p + 1] = s1; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * P) {
+        const int p = threadIdx.x >> 1, k = threadIdx.x & 1;
+        out_of(p)[k] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+}
+
+template <int N, bool STD>
+__global__ __launch_bounds__(256) void k_energy_pixel_batch(const EnergyK a, const EnergyPairs pr, const EnergyBatch q) {
+    const int k = blockIdx.y / q.S;
+    if (batch_stopped(q, k)) return;
+    energy_pixel_body<N, STD>(on_stack_of(a, q, k), pr);
+}
+
 // one wave per candidate: pair results (chunks summed in order) and the NaN-ignoring mean over pairs
-__global__ __launch_bounds__(64) void k_energy_final(const double* __restrict__ partial, const uint8_t* __restrict__ valid,
-                                                     int pairs, int chunks, double* __restrict__ out_pairs,
-                                                     double* __restrict__ out_energy) {
-    const int b = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void energy_final_body(const double* __restrict__ partial, const uint8_t* __restrict__ valid,
+                                                  int pairs, int chunks, double* __restrict__ out_pairs,
+                                                  double* __restrict__ out_energy, const int b) {
+    const int lane = threadIdx.x;
     const bool ok = !valid || valid[b];
     double sum = 0.0, cnt = 0.0;
     for (int p = lane; p < pairs; p += 64) {
@@ -241,10 +418,75 @@ __global__ __launch_bounds__(64) void k_energy_final(const double* __restrict__ 
     }
 }
 
+__global__ __launch_bounds__(64) void k_energy_final(const double* __restrict__ partial, const uint8_t* __restrict__ valid,
+                                                     int pairs, int chunks, double* __restrict__ out_pairs,
+                                                     double* __restrict__ out_energy) {
+    energy_final_body(partial, valid, pairs, chunks, out_pairs, out_energy, blockIdx.x);
+}
+
+// the batch: one wave per candidate of every problem, none for a stopped problem (its partials were not rewritten)
+__global__ __launch_bounds__(64) void k_energy_final_batch(const double* __restrict__ partial, const uint8_t* __restrict__ valid,
+                                                           int pairs, int chunks, double* __restrict__ out_energy,
+                                                           const int64_t* __restrict__ status, int S) {
+    const int b = blockIdx.x;
+    if (status[static_cast<int64_t>(b / S) * HM_DE_STATUS_WORDS + HM_DE_STOP] != 0) return;
+    energy_final_body(partial, valid, pairs, chunks, nullptr, out_energy, b);
+}
+
 static int energy_chunks(int64_t P) {
     int64_t c = (P + 1023) / 1024;                  // >= 4 pixels per thread before splitting further
     if (c < 1) c = 1;
     return static_cast<int>(c > 64 ? 64 : c);
+}
+
+// pixel-major kernel when there are enough candidates (or few enough pixels) for chunks x candidates workgroups to
+// fill the chip; a lone candidate on a large stack keeps the pair-major kernel's pairs x chunks workgroups.
+// n_candidates is the count of ONE stack's candidates: a batch decides from its per-problem S, never from K x S.
+static bool energy_pixel_major(int n_frames, int n_candidates, int64_t n_pixels) {
+    return n_frames <= kEnergyRegFrames && (n_candidates >= 8 || n_pixels <= 16384);
+}
+
+static void energy_pair_ratios(EnergyPairs& pr, const double* exposures, int n_frames) {
+    int p = 0;
+    for (int i = 0; i < n_frames; ++i)
+        for (int j = i + 1; j < n_frames; ++j, ++p) {
+            pr.ratio[p] = exposures[i] / exposures[j];                       // :100
+            pr.inv_ratio[p] = 1.0 / pr.ratio[p];
+        }
+}
+
+// hm_de_generation_batch's energy stage (arguments validated there): the relative energies of the S candidates of each of
+// K problems, rows k S .. k S + S - 1 of icrf / valid / out_energy, on problem k's stack; workspace as K single launches.
+int energy_batch(const uint8_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
+                 const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels,
+                 int n_frames, double* out_energy, void* workspace, hipStream_t st) {
+    const int pairs = n_frames * (n_frames - 1) / 2, total = n_problems * pop_size;
+    EnergyK k{};
+    k.icrf = icrf; k.valid = valid; k.partial = static_cast<double*>(workspace);
+    k.P = n_pixels; k.N = n_frames; k.lower = lower; k.upper = upper; k.relative = 1;
+    k.chunks = energy_chunks(n_pixels);
+    for (int i = 0; i < n_frames; ++i) k.t[i] = exposures[i];
+    EnergyBatch q{};
+    for (int i = 0; i < n_problems; ++i) { q.dn[i] = dn[i]; q.sd[i] = std ? std[i] : nullptr; }
+    q.status = status; q.S = pop_size;
+    if (energy_pixel_major(n_frames, pop_size, n_pixels)) {
+        EnergyPairs pr{};
+        energy_pair_ratios(pr, exposures, n_frames);
+        const dim3 grid(k.chunks, total);
+#define HM_EPX(n) case n: if (std) hipLaunchKernelGGL((k_energy_pixel_batch<n, true>), grid, dim3(256), 0, st, k, pr, q); \
+                          else hipLaunchKernelGGL((k_energy_pixel_batch<n, false>), grid, dim3(256), 0, st, k, pr, q); break;
+        switch (n_frames) { HM_EPX(2) HM_EPX(3) HM_EPX(4) HM_EPX(5) HM_EPX(6) HM_EPX(7) HM_EPX(8) default: return HM_EUNSUPPORTED; }
+#undef HM_EPX
+    } else {
+        const dim3 grid(k.chunks, pairs, total);
+        if (std) hipLaunchKernelGGL(k_energy_partial_batch<true>, grid, dim3(256), 0, st, k, q);
+        else     hipLaunchKernelGGL(k_energy_partial_batch<false>, grid, dim3(256), 0, st, k, q);
+    }
+    int rc = launch_status();
+    if (rc != HM_OK) return rc;
+    hipLaunchKernelGGL(k_energy_final_batch, dim3(total), dim3(64), 0, st, static_cast<const double*>(workspace), valid, pairs,
+                       k.chunks, out_energy, status, pop_size);
+    return launch_status();
 }
 
 }  // namespace hm
@@ -273,16 +515,9 @@ extern "C" int hm_linearity_energy(const uint8_t* dn, const double* std, const d
     k.P = n_pixels; k.N = n_frames; k.lower = lower; k.upper = upper; k.relative = use_relative ? 1 : 0;
     k.chunks = energy_chunks(n_pixels);
     for (int i = 0; i < n_frames; ++i) k.t[i] = exposures[i];
-    // pixel-major kernel when there are enough candidates (or few enough pixels) for chunks x candidates workgroups to
-    // fill the chip; a lone candidate on a large stack keeps the pair-major kernel's pairs x chunks workgroups
-    if (n_frames <= kEnergyRegFrames && (n_candidates >= 8 || n_pixels <= 16384)) {
+    if (energy_pixel_major(n_frames, n_candidates, n_pixels)) {
         EnergyPairs pr{};
-        int p = 0;
-        for (int i = 0; i < n_frames; ++i)
-            for (int j = i + 1; j < n_frames; ++j, ++p) {
-                pr.ratio[p] = exposures[i] / exposures[j];                       // :100
-                pr.inv_ratio[p] = 1.0 / pr.ratio[p];
-            }
+        energy_pair_ratios(pr, exposures, n_frames);
         const dim3 grid(k.chunks, n_candidates);
 #define HM_EPX(n) case n: if (std) hipLaunchKernelGGL((k_energy_pixel<n, true>), grid, dim3(256), 0, as_stream(stream), k, pr); \
                           else hipLaunchKernelGGL((k_energy_pixel<n, false>), grid, dim3(256), 0, as_stream(stream), k, pr); break;

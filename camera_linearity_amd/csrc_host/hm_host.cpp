@@ -1261,4 +1261,38 @@ int hm_de_generation(double* population, double* energies, double* trial, double
     return HM_OK;
 }
 
+// n_problems problems of one shape per call (hdrmerge.h): on the host a batch IS its problems one after another, each through
+// hm_de_generation above on its slices of the (K, ...) state - which returns at once for a problem whose stop flag is set
+size_t hm_de_batch_workspace_bytes(int64_t, int, int, int) { return 0; }
+int hm_de_generation_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies, double* icrf,
+                           uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits,
+                           const double* upper_limits, const uint8_t* const* dn, const double* const* std_, const int64_t* seeds,
+                           const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size, int n_params,
+                           int64_t max_generations, double mutation_lo, double mutation_hi, double recombination, double tol,
+                           double energy_limit, void*, void*) {
+    if (n_problems < 1) return HM_EINVAL;
+    if (n_problems > HM_DE_MAX_PROBLEMS) return HM_ESHAPE;
+    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
+    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    if (n_problems * pop_size > 65535) return HM_EUNSUPPORTED;                // the HIP build's limit, kept so that both builds accept the same calls
+    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
+    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;
+    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
+    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
+    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !seeds || !exposures) return HM_EINVAL;
+    for (int k = 0; k < n_problems; ++k)
+        if (!dn[k] || (std_ && !std_[k])) return HM_EINVAL;                   // stds for all problems or for none
+    const int64_t S = pop_size, P = n_params;
+    for (int64_t k = 0; k < n_problems; ++k) {
+        const int rc = hm_de_generation(population + k * S * P, energies + k * S, trial + k * S * P, trial_energies + k * S,
+                                        icrf + k * S * 256, valid + k * S, status + k * HM_DE_STATUS_WORDS, mean_icrf + k * 256,
+                                        pca + k * 256 * P, lower_limits, upper_limits, dn[k], std_ ? std_[k] : nullptr, exposures,
+                                        n_pixels, n_frames, lower, upper, pop_size, n_params, seeds[k], max_generations, mutation_lo,
+                                        mutation_hi, recombination, tol, energy_limit, nullptr, nullptr);
+        if (rc != HM_OK) return rc;
+    }
+    return HM_OK;
+}
+
 }  // extern "C"

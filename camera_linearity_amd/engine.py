@@ -1136,6 +1136,13 @@ def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], 
 # ------------------------------------------------------------------------------------------------
 # ICRF-calibration differential evolution (modules/ICRF_calibration_exposure.py:288-369), one generation per hm_de_generation call
 # ------------------------------------------------------------------------------------------------
+def _status_dict(w: np.ndarray) -> dict:
+    f = w.view(np.float64)
+    return dict(generation=int(w[nat.HM_DE_GENERATION]) - 1, best_index=int(w[nat.HM_DE_BEST_INDEX]), stop=int(w[nat.HM_DE_STOP]),
+                evaluations=int(w[nat.HM_DE_EVALUATIONS]), best_energy=float(f[nat.HM_DE_BEST_ENERGY]),
+                mean=float(f[nat.HM_DE_MEAN]), std=float(f[nat.HM_DE_STD]))
+
+
 class DEPlan:
     """The state of one channel's differential-evolution solve (population, energies, trial rows, candidate ICRFs, verdicts, status block,
     workspace - all on the stack's device) and the launches that advance it. `launch()` enqueues ONE generation (hm_de_generation: trial
@@ -1220,11 +1227,7 @@ class DEPlan:
     def read_status(self) -> dict:
         """The status block, copied to the host (this synchronises): generation = the number of generations after the initial
         evaluation that have run."""
-        w = self.status.cpu().numpy()
-        f = w.view(np.float64)
-        return dict(generation=int(w[nat.HM_DE_GENERATION]) - 1, best_index=int(w[nat.HM_DE_BEST_INDEX]), stop=int(w[nat.HM_DE_STOP]),
-                    evaluations=int(w[nat.HM_DE_EVALUATIONS]), best_energy=float(f[nat.HM_DE_BEST_ENERGY]),
-                    mean=float(f[nat.HM_DE_MEAN]), std=float(f[nat.HM_DE_STD]))
+        return _status_dict(self.status.cpu().numpy())
 
     def _record(self, n: int) -> None:
         """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
@@ -1258,4 +1261,157 @@ class DEPlan:
                     self.launch()
             st = self.read_status()
             if st["stop"]:
+                return st
+
+
+class DEBatchPlan:
+    """K independent differential-evolution problems of one shape - the channels of a calibration, restarts of a channel with other seeds,
+    or both - advanced by ONE set of launches per generation (hm_de_generation_batch: trial kernel on (S, K) workgroups, the energy
+    kernels on K x S candidates, select kernel on K workgroups). Problem k reads stack `stack_of[k]` of `dn_stacks` (default: its own),
+    its own mean ICRF, PCA basis and seed, and owns slice k of every state tensor: `population[k]`, `energies[k]`, `trial[k]`,
+    `trial_energies[k]`, `icrf[k]`, `valid[k]`, `status[k]`. Every problem evolves bit for bit as a DEPlan with the same inputs would;
+    a problem whose stop flag is set costs no further work while the others run. `run()` records `check_every` generations as one
+    linear chain (hipGraph), replays it until ALL stop flags are set and reads the K status blocks back with one copy per replay.
+    Built inside nat.host_mode() on host stacks, it calls the host build in a loop (no graph)."""
+
+    def __init__(self, dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures: Sequence[float],
+                 mean_icrfs, pcas, lower_limits, upper_limits, populations, lower: int, upper: int, seeds: Sequence[int],
+                 max_generations: int, mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0,
+                 stack_of: Optional[Sequence[int]] = None):
+        dn_stacks = list(dn_stacks)
+        if not dn_stacks:
+            raise ValueError("dn_stacks must hold at least one stack")
+        for s in dn_stacks:
+            _require_cuda(s, "image_value_stack")
+            if s.dtype != torch.uint8:
+                raise TypeError("image_value_stack must be uint8 digital numbers")
+            if s.dim() != 3:
+                raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")         # ICRF_calibration_exposure.py:82-83
+            if s.shape != dn_stacks[0].shape:
+                raise ValueError(f"the stacks of a batch must have one shape: {tuple(s.shape)} != {tuple(dn_stacks[0].shape)}")
+            if s.device != dn_stacks[0].device:
+                raise ValueError(f"the stacks of a batch must live on one device: {s.device} != {dn_stacks[0].device}")
+        dev = dn_stacks[0].device
+        self.device = dev
+        self.host = dev.type != "cuda"
+        N = dn_stacks[0].shape[2]
+        t = np.asarray(exposures, dtype=np.float64)
+        if t.ndim != 1 or t.size != N:
+            raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
+        self.dn = [s.contiguous() for s in dn_stacks]
+        self.std = None
+        if std_stacks is not None and any(s is not None for s in std_stacks):
+            std_stacks = list(std_stacks)
+            if len(std_stacks) != len(dn_stacks) or any(s is None for s in std_stacks):
+                raise ValueError("image_std_stacks must be given for every stack of a batch or for none")
+            for s in std_stacks:
+                _require_cuda(s, "image_std_stack")
+                if s.shape != dn_stacks[0].shape or s.dtype != _F64 or s.device != dev:
+                    raise ValueError("image_std_stack must be float64, shaped like image_value_stack and on its device")
+            self.std = [s.contiguous() for s in std_stacks]
+        pop = np.ascontiguousarray(np.asarray(populations, dtype=np.float64))
+        if pop.ndim != 3:
+            raise ValueError("populations must be (K, S, P) in scaled coordinates [0, 1]")
+        K, S, P = pop.shape
+        if K < 1 or K > nat.HM_DE_MAX_PROBLEMS:
+            raise ValueError(f"a batch holds 1 to {nat.HM_DE_MAX_PROBLEMS} problems, got {K}")
+        if stack_of is None:
+            if len(dn_stacks) != K:
+                raise ValueError(f"{len(dn_stacks)} stacks for {K} problems: give stack_of, the stack index of every problem")
+            stack_of = range(K)
+        stack_of = [int(i) for i in stack_of]
+        if len(stack_of) != K or any(i < 0 or i >= len(dn_stacks) for i in stack_of):
+            raise ValueError(f"stack_of must hold {K} indices into the {len(dn_stacks)} stacks, got {stack_of}")
+        seeds = [int(s) for s in seeds]
+        if len(seeds) != K or len(mean_icrfs) != K or len(pcas) != K:
+            raise ValueError(f"seeds, mean_icrfs and pcas must hold one entry per problem ({K})")
+        self.K, self.S, self.P, self.N = K, S, P, N
+        self.stack_of = stack_of
+        self.n_pixels = dn_stacks[0].shape[0] * dn_stacks[0].shape[1]
+        means = [np.asarray(m, dtype=np.float64).reshape(-1) for m in mean_icrfs]
+        bases = [np.asarray(b, dtype=np.float64) for b in pcas]
+        if any(m.size != BITS for m in means) or any(b.shape != (BITS, P) for b in bases):
+            raise ValueError(f"every mean ICRF must have {BITS} entries and every PCA basis must be ({BITS}, {P})")
+        self.mean_icrf = _dev_f64(np.stack(means), dev)
+        self.pca = _dev_f64(np.stack(bases), dev)
+        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.population = torch.as_tensor(pop, device=dev).clone()
+        self.energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
+        self.trial = torch.zeros((K, S, P), dtype=_F64, device=dev)
+        self.trial_energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
+        self.icrf = torch.zeros((K, S, BITS), dtype=_F64, device=dev)
+        self.valid = torch.zeros((K, S), dtype=_U8, device=dev)
+        self.status = torch.zeros((K, nat.HM_DE_STATUS_WORDS), dtype=torch.int64, device=dev)
+        self._t = (C.c_double * N)(*t.tolist())
+        self._dn = _ptr_array([self.dn[i] for i in stack_of])
+        self._sd = None if self.std is None else _ptr_array([self.std[i] for i in stack_of])
+        self._seeds = (C.c_int64 * K)(*[C.c_int64(s & 0xFFFFFFFFFFFFFFFF).value for s in seeds])
+        self._scalars = (int(lower), int(upper), int(S), int(P), int(max_generations), float(mutation[0]), float(mutation[1]),
+                         float(recombination), float(tol), float(energy_limit))
+        with nat.host_mode() if self.host else _NoDevice():
+            ws_bytes = nat.lib.hm_de_batch_workspace_bytes(self.n_pixels, N, S, K)
+        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+        self._graph = None
+        self._graph_len = 0
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        """Enqueue one generation of every problem on `stream` (default: the current stream of the plan's device)."""
+        lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
+
+        def call(st):
+            return nat.lib.hm_de_generation_batch(self.K, self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
+                                                  self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
+                                                  self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(),
+                                                  self.lo.data_ptr(), self.hi.data_ptr(), self._dn, self._sd, self._seeds, self._t,
+                                                  self.n_pixels, self.N, lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim,
+                                                  self.workspace.data_ptr(), st)
+        if self.host:
+            with nat.host_mode():
+                nat.check(call(None), "hm_de_generation_batch")
+            return
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with _on(self.device):
+            rc = call(stream)
+        if rc:
+            nat.check(rc, "hm_de_generation_batch")
+
+    def read_status(self) -> list:
+        """The K status blocks from ONE copy to the host (this synchronises): a list of DEPlan.read_status() dicts."""
+        w = self.status.cpu().numpy()
+        return [_status_dict(w[k]) for k in range(self.K)]
+
+    def _record(self, n: int) -> None:
+        """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
+        dev = self.device
+        with torch.cuda.device(dev):
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                self.launch(side.cuda_stream)           # first launches load the kernels' code objects: outside the capture
+                self._graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._graph, stream=side):
+                    for _ in range(n):
+                        self.launch(side.cuda_stream)
+            torch.cuda.current_stream(dev).wait_stream(side)
+        self._graph_len = n
+
+    def run(self, check_every: int = 8, graph: bool = True) -> list:
+        """Advance until EVERY problem's stop flag is set: `check_every` generations per status read. -> the final read_status()."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1")
+        use_graph = graph and not self.host
+        if use_graph and self._graph_len != check_every:
+            self._record(check_every)                   # (runs generation 0 as its warm-up launch)
+        while True:
+            if use_graph:
+                with _on(self.device):
+                    self._graph.replay()
+            else:
+                for _ in range(check_every):
+                    self.launch()
+            st = self.read_status()
+            if all(s["stop"] for s in st):
                 return st

@@ -11,7 +11,10 @@ update order, one candidate per call; the candidate ICRF (mean + PCA product, sh
 
 `solver="device"` runs the whole generation - mutation, crossover, candidate ICRFs and their verdicts, energy, selection,
 convergence statistics - where the stack lives (hm_de_generation, engine.DEPlan): the same strategy and settings, restated
-with counter-based random numbers (include/hdrmerge.h), started from SciPy's own Sobol population.
+with counter-based random numbers (include/hdrmerge.h), started from SciPy's own Sobol population. Several such problems of one shape -
+the channels of a calibration (`calibration(..., batched=True)`), restarts of a channel with other seeds (`restarts=R`), or both - run
+in ONE plan (hm_de_generation_batch, engine.DEBatchPlan): one set of launches per generation for all of them, each problem evolving bit
+for bit as it would alone.
 """
 from __future__ import annotations
 
@@ -137,11 +140,81 @@ def initialize_channel_image_stacks(frames: Sequence, exposures: Sequence[float]
     return value_stacks, std_stacks, t
 
 
+RESTART_SEED_STRIDE = 1_000_003
+
+
+def restart_seed(seed: int, restart: int) -> int:
+    """The seed of restart r of a solve seeded with `seed`: seed + 1 000 003 r. Restart 0 is the solve itself; the stride keeps the
+    restarts of channel c (seeded rng_seed + c by calibration()) away from the seeds of the other channels."""
+    return int(seed) + RESTART_SEED_STRIDE * int(restart)
+
+
+def _seed_keyword(seed) -> dict:
+    # the reference passes seed= (SciPy 1.14, its Pipfile.lock); SciPy >= 1.15 renamed the argument to rng=
+    return {"rng" if "rng" in inspect.signature(DifferentialEvolutionSolver.__init__).parameters else "seed": seed}
+
+
+def _pca_limits(n_components: int, lower_PCA_limit: float, upper_PCA_limit: float):
+    """Search limits and start point of a mean-ICRF solve (:313-315)."""
+    return [[lower_PCA_limit, upper_PCA_limit] for _ in range(n_components)], [0] * n_components
+
+
+def _initial_population(limits, x0, args, tol, popsize, extra) -> np.ndarray:
+    """SciPy's own initial population (Sobol, the seed in `extra`), read without iterating: both solvers start from the same S x P points."""
+    with DifferentialEvolutionSolver(_energy_function, limits, args=args, strategy="currenttobest1bin", tol=tol, x0=x0,
+                                     mutation=(0, 1.95), recombination=0.4, init="sobol", popsize=popsize, **extra) as start:
+        return np.array(start.population, dtype=np.float64)
+
+
+def _solve_batch(means, pcas, stacks, std_stacks, stack_of, seeds, exposure_values, lower_PCA_limit, upper_PCA_limit, data_limits,
+                 energy_limit, max_iterations, popsize, check_every, graph, tol):
+    """K device solves of one shape in one engine.DEBatchPlan: problem k on stacks[stack_of[k]] with means[k], pcas[k], seeds[k] and
+    SciPy's Sobol population for seeds[k]. -> [(icrf, energy, iterations)] * K, each what solve_channel(solver="device") returns for it."""
+    K = len(seeds)
+    pcas = [np.asarray(b, dtype=np.float64) for b in pcas]
+    n_params = {b.shape[1] for b in pcas}
+    if len(n_params) != 1:
+        raise ValueError(f"a batched solve needs the same number of PCA components for every problem, got {[b.shape[1] for b in pcas]}")
+    shapes = {tuple(s.shape) for s in stacks}
+    if len(shapes) != 1:
+        raise ValueError(f"a batched solve needs channel stacks of one shape, got {[tuple(s.shape) for s in stacks]}")
+    limits, x0 = _pca_limits(n_params.pop(), lower_PCA_limit, upper_PCA_limit)
+    for sd in seeds:
+        if not isinstance(sd, (int, np.integer)):
+            raise TypeError('solver="device" needs an integer seed')
+    pops = []
+    for k in range(K):
+        c = stack_of[k]
+        args = (means[k], pcas[k], stacks[c], std_stacks[c], data_limits[0], data_limits[1], True, exposure_values)
+        pops.append(_initial_population(limits, x0, args, tol, popsize, dict(vectorized=True, updating="deferred", **_seed_keyword(seeds[k]))))
+    lo, hi = np.asarray(limits, dtype=np.float64).T
+    plan = _engine_for(stacks[0]).DEBatchPlan(stacks, std_stacks, _host(exposure_values), means, pcas, lo, hi, np.stack(pops), data_limits[0],
+                                              data_limits[1], [int(sd) for sd in seeds], 2 * int(max_iterations), (0.0, 1.95), 0.4, tol,
+                                              energy_limit, stack_of=stack_of)
+    sts = plan.run(check_every, graph)
+    best = plan.population[torch.arange(K), torch.as_tensor([st["best_index"] for st in sts])].cpu().numpy()      # one copy for the K members
+    return [(_inverse_camera_response_function(means[k], pcas[k], lo + best[k] * (hi - lo), True), sts[k]["best_energy"],
+             sts[k]["generation"] // 2) for k in range(K)]
+
+
+def _best_restart(results):
+    """The restart with the lowest final energy; ties go to the lowest restart index."""
+    return min(enumerate(results), key=lambda ir: (ir[1][1], ir[0]))[1]
+
+
+def _device_defaults():
+    """solve_channel's own defaults of check_every, graph and tol: what calibration()'s sequential path inherits by not passing them,
+    handed to the batched path from the same place, so the two stay array-equal if a default moves."""
+    import inspect
+    par = inspect.signature(solve_channel).parameters
+    return {name: par[name].default for name in ("check_every", "graph", "tol")}
+
+
 def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values,
                   lower_PCA_limit: float, upper_PCA_limit: float, use_mean_ICRF: bool = True,
                   data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, seed=7,
                   max_iterations: int = 1000, vectorized: bool = True, popsize: int = 15, channel: int = 0, verbose: bool = False,
-                  solver: str = "scipy", check_every: int = 8, graph: bool = True, tol: float = 0.01):
+                  solver: str = "scipy", check_every: int = 8, graph: bool = True, tol: float = 0.01, restarts: int = 1):
     """The per-channel solve of calibration() (:329-369): SciPy's DifferentialEvolutionSolver with the reference's
     settings. vectorized=True evaluates each generation's population in ONE launch (SciPy then uses deferred updating);
     vectorized=False keeps the reference's immediate updating and evaluates one candidate per launch.
@@ -149,9 +222,17 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     library's own random numbers), `check_every` generations per status read, recorded as a hipGraph unless graph=False; `vectorized`
     does not apply. An iteration is two generations, as in the reference loop. `tol` is the solver's relative convergence tolerance
     (the reference's 0.01) for either solver.
+    restarts=R > 1 (solver="device" only): R solves of the same channel from other seeds - restart r uses restart_seed(seed, r) =
+    seed + 1 000 003 r, so restart 0 is the restarts=1 solve, and starts from SciPy's Sobol population for that seed - advanced together
+    in one engine.DEBatchPlan; the triple of the restart with the lowest final energy is returned (ties: the lowest r).
     -> (ICRF of the channel (256,), final energy, iterations)."""
     if solver not in ("scipy", "device"):
         raise ValueError(f"solver must be 'scipy' or 'device', got {solver!r}")
+    restarts = int(restarts)
+    if restarts < 1:
+        raise ValueError(f"restarts must be >= 1, got {restarts}")
+    if restarts > 1 and solver != "device":
+        raise ValueError('restarts > 1 needs solver="device": the restarts run as one batch on the stack\'s backend')
     if solver == "device" and not use_mean_ICRF:
         raise NotImplementedError('solver="device" forms candidates from a mean ICRF only; the power-law base (use_mean_ICRF=False) needs '
                                   'solver="scipy"')
@@ -168,13 +249,16 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     args = (mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, data_limits[0], data_limits[1], use_mean_ICRF,
             exposure_values)
     extra = dict(vectorized=True, updating="deferred") if vectorized else {}
-    # the reference passes seed= (SciPy 1.14, its Pipfile.lock); SciPy >= 1.15 renamed the argument to rng=
-    extra["rng" if "rng" in inspect.signature(DifferentialEvolutionSolver.__init__).parameters else "seed"] = seed
+    extra.update(_seed_keyword(seed))
+    if solver == "device" and restarts > 1:
+        if not isinstance(seed, (int, np.integer)):
+            raise TypeError('solver="device" needs an integer seed')
+        return _best_restart(_solve_batch([mean_ICRF_array] * restarts, [PCA_array] * restarts, [image_value_stack], [image_std_stack],
+                                          [0] * restarts, [restart_seed(seed, r) for r in range(restarts)], exposure_values,
+                                          lower_PCA_limit, upper_PCA_limit, data_limits, energy_limit, max_iterations, popsize,
+                                          check_every, graph, tol))
     if solver == "device":
-        # SciPy's own initial population (Sobol, same seed), read without iterating: both solvers start from the same S x P points
-        with DifferentialEvolutionSolver(_energy_function, limits, args=args, strategy="currenttobest1bin", tol=tol, x0=x0,
-                                         mutation=(0, 1.95), recombination=0.4, init="sobol", popsize=popsize, **extra) as start:
-            population = np.array(start.population, dtype=np.float64)
+        population = _initial_population(limits, x0, args, tol, popsize, extra)
         if not isinstance(seed, (int, np.integer)):
             raise TypeError('solver="device" needs an integer seed')
         lo, hi = np.asarray(limits, dtype=np.float64).T
@@ -209,20 +293,45 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
 def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_stacks, channel_image_std_stacks, exposure_values,
                 lower_PCA_limit: float, upper_PCA_limit: float, initial_function=None,
                 data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, rng_seed: int = 7,
-                vectorized: bool = True, max_iterations: int = 1000, popsize: int = 15, solver: str = "scipy"):
+                vectorized: bool = True, max_iterations: int = 1000, popsize: int = 15, solver: str = "scipy", batched: bool = False,
+                restarts: int = 1):
     """calibration() (:287-405) from arrays: per-channel mean ICRF (or `initial_function`) and PCA basis, the channel stacks
-    of initialize_channel_image_stacks. The channels are solved one after another on this process's GPU (the reference
+    of initialize_channel_image_stacks. By default the channels are solved one after another on this process's GPU (the reference
     forks one joblib worker per channel, :383; with one process per GPU, give each rank a channel instead).
+    solver="device", batched=True solves them CONCURRENTLY, the reference's joblib.Parallel(n_jobs=NUM_OF_CHS) as one
+    engine.DEBatchPlan: all C x `restarts` problems in one set of launches per generation, channel c's restart r seeded
+    restart_seed(rng_seed + c, r), the best restart kept per channel. It needs channel stacks of one shape and the same number of PCA
+    components for every channel (ValueError otherwise, never a sequential fallback); with restarts=1 the result equals the sequential
+    solver="device" one bit for bit. `restarts` > 1 without `batched` runs each channel's restarts as a batch, channel after channel.
     -> (ICRF (BITS, C) interpolated, final energies (C,))."""
     C = len(channel_image_value_stacks)
     use_mean_ICRF = initial_function is None
     results, energies = [], np.zeros(C)
-    for c in range(C):
-        base = mean_ICRFs[c] if use_mean_ICRF else initial_function
-        icrf_c, energies[c], _ = solve_channel(base, PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
-                                               exposure_values, lower_PCA_limit, upper_PCA_limit, use_mean_ICRF, data_limits,
-                                               energy_limit, rng_seed + c, max_iterations, vectorized, popsize, c, solver=solver)
-        results.append(icrf_c)
+    if batched:
+        if solver != "device":
+            raise ValueError('batched=True needs solver="device": the channels run as one batch on the stacks\' backend')
+        if not use_mean_ICRF:
+            raise NotImplementedError('solver="device" forms candidates from a mean ICRF only; the power-law base (initial_function) needs '
+                                      'solver="scipy"')
+        restarts = int(restarts)
+        if restarts < 1:
+            raise ValueError(f"restarts must be >= 1, got {restarts}")
+        idx = [(c, r) for c in range(C) for r in range(restarts)]
+        solved = _solve_batch([mean_ICRFs[c] for c, _ in idx], [PCA_arrays[c] for c, _ in idx], list(channel_image_value_stacks),
+                              list(channel_image_std_stacks), [c for c, _ in idx], [restart_seed(rng_seed + c, r) for c, r in idx],
+                              exposure_values, lower_PCA_limit, upper_PCA_limit, data_limits, energy_limit, max_iterations, popsize,
+                              **_device_defaults())
+        for c in range(C):
+            icrf_c, energies[c], _ = _best_restart(solved[c * restarts:(c + 1) * restarts])
+            results.append(icrf_c)
+    else:
+        for c in range(C):
+            base = mean_ICRFs[c] if use_mean_ICRF else initial_function
+            icrf_c, energies[c], _ = solve_channel(base, PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
+                                                   exposure_values, lower_PCA_limit, upper_PCA_limit, use_mean_ICRF, data_limits,
+                                                   energy_limit, rng_seed + c, max_iterations, vectorized, popsize, c, solver=solver,
+                                                   restarts=restarts)
+            results.append(icrf_c)
     ICRF = np.stack(results, axis=1)
     ICRF += (1 - ICRF[-1, :])[None, :]                                           # :390
     ICRF[0, :] = 0                                                               # :391

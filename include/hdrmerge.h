@@ -490,6 +490,47 @@ int hm_de_generation(double* population, double* energies, double* trial, double
                      void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same generation for n_problems independent problems of identical shape - the channels of a calibration, or
+ * restarts of one channel with other seeds - advanced by ONE call: one linear chain of launches on one stream, no
+ * allocation, no host synchronisation, no float atomics (the contract of hm_de_generation).
+ *
+ * Specification: problem k of a batch evolves exactly as hm_de_generation would evolve it alone with the same inputs and
+ * seed - BIT FOR BIT, in every state array and every status word, after every call. In particular
+ *   - the random numbers of a problem depend on its own seed, the generation, the member and the draw index only
+ *     (U(g, i, k) above with seed = seeds[k]); never on the problem's position in the batch or on n_problems;
+ *   - the energy of a candidate is summed in the order hm_linearity_energy uses for pop_size candidates on n_pixels
+ *     pixels (the launch geometry is chosen from the per-problem pop_size, not from n_problems * pop_size);
+ *   - each problem has its own status block and stop flag. Once status[k][HM_DE_STOP] != 0 no kernel of a later call
+ *     stores anything for problem k (its energy workgroups return at once: a converged problem costs no pixel work
+ *     while the others run); the other problems go on. The caller stops issuing calls when every flag is set.
+ *
+ * Shared by all problems: pop_size S, n_params P, n_pixels, n_frames, exposures [host], lower, upper, lower_limits (P),
+ * upper_limits (P) on the device, max_generations, mutation range, recombination, tol, energy_limit.
+ * Per problem, as HOST arrays of n_problems entries read at call time (they travel in the kernel arguments, so a
+ * recorded graph holds them by value):
+ *   dn     device pointers to the uint8 (n_pixels, n_frames) stacks; problems may name the same stack
+ *   std    NULL (no problem has a std stack), or device pointers to float64 stacks for ALL problems
+ *   seeds  the problems' seeds
+ * Per-problem state, caller-owned device memory (host memory in the host build), contiguous with the problem outermost:
+ *   population (K, S, P), energies (K, S), trial (K, S, P), trial_energies (K, S), icrf (K, S, 256) float64;
+ *   valid (K, S) uint8; status (K, HM_DE_STATUS_WORDS) zeroed before generation 0; mean_icrf (K, 256), pca (K, 256, P)
+ *   workspace  hm_de_batch_workspace_bytes(n_pixels, n_frames, pop_size, n_problems) bytes (0 for arguments the call
+ *              would reject)
+ * Returns, before any launch and before any pointer is read: HM_EINVAL for n_problems < 1 or a NULL required pointer
+ * (array or entry), HM_ESHAPE for n_problems > HM_DE_MAX_PROBLEMS, HM_EUNSUPPORTED for n_problems * pop_size > 65535
+ * (the candidate limit of the energy grid); every other argument as hm_de_generation.
+ * ------------------------------------------------------------------------------------------ */
+#define HM_DE_MAX_PROBLEMS 64
+size_t hm_de_batch_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size, int n_problems);
+int hm_de_generation_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies,
+                           double* icrf, uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca,
+                           const double* lower_limits, const double* upper_limits, const uint8_t* const* dn /*[host]*/,
+                           const double* const* std /*[host], nullable*/, const int64_t* seeds /*[host]*/,
+                           const double* exposures /*[host]*/, int64_t n_pixels, int n_frames, int lower, int upper,
+                           int pop_size, int n_params, int64_t max_generations, double mutation_lo, double mutation_hi,
+                           double recombination, double tol, double energy_limit, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * On-disk formats: host-side strip decoders for the TIFF files the reference exchanges with
  * OpenCV (modules/image_set.py:214-243 cv.imread, :264-363 cv.imwrite). HOST pointers, no device work, re-entrant.
  * Return the number of bytes written to dst, HM_EINVAL for a corrupt stream, HM_ESHAPE if dst_cap is too small.

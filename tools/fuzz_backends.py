@@ -589,8 +589,45 @@ def case_kde(rng):
     return desc
 
 
+def case_de_batch(rng):
+    """hm_de_generation_batch against hm_de_generation: a random batch (K problems on 1..K stacks, with or without std stacks, any frame
+    count, populations on both sides of the energy launcher's geometry rule) and its K single plans, on BOTH builds - within a build every
+    state array and status word of problem k must equal its single plan's bit for bit after a few generations."""
+    K, S, P = int(rng.integers(1, 6)), int(rng.choice([4, 5, 8, 13, 32])), int(rng.integers(1, 6))
+    X, Y = (int(rng.integers(1, 40)), int(rng.integers(1, 40))) if rng.random() < 0.8 else (130, int(rng.integers(126, 140)))   # around 16 384 pixels
+    N = int(rng.choice([2, 3, 5, 7, 8, 9, 12]))
+    n_stacks = int(rng.integers(1, K + 1))
+    stack_of = [int(c) for c in rng.permutation(np.concatenate([np.arange(n_stacks), rng.integers(0, n_stacks, K - n_stacks)]))]
+    dns = [np.sort(rng.integers(0, 256, (X, Y, N)).astype(np.uint8), axis=2) for _ in range(n_stacks)]
+    sds = [0.004 * (1 + rng.random((X, Y, N))) for _ in range(n_stacks)] if rng.random() < 0.4 else None
+    t = np.sort(rng.uniform(1e-3, 1.0, size=N)) + np.arange(N) * 1e-4
+    xs = np.linspace(0, 1, 256)
+    means = [xs ** rng.uniform(0.7, 2.5) for _ in range(K)]
+    pcas = [np.stack([np.sin(np.pi * (m + 1) * xs) / (m + 1) for m in range(P)], axis=1) * rng.uniform(0.02, 0.15) for _ in range(K)]
+    pop = rng.random((K, S, P))
+    pop[:, ::2] = 0.5 + 0.3 * (pop[:, ::2] - 0.5)                                     # half of the members near the mean ICRF: valid rows
+    seeds = [int(x) for x in rng.integers(-2 ** 62, 2 ** 62, K)]
+    gens, max_gen = int(rng.integers(1, 7)), int(rng.choice([2, 3, 100]))
+    tol = float(rng.choice([0.0, 0.01, 10.0]))
+    lower, upper = int(rng.integers(0, 40)), int(rng.integers(200, 256))
+    desc = f"de_batch K={K} S={S} P={P} {X}x{Y}x{N} stacks={stack_of} std={sds is not None} gens={gens} max={max_gen} tol={tol}"
+    for name, eng, up in (("device", engine, D), ("host", heng, Hh)):
+        st, sd = [up(a) for a in dns], None if sds is None else [up(a) for a in sds]
+        batch = eng.DEBatchPlan(st, sd, t, means, pcas, -1.0, 1.0, pop, lower, upper, seeds, max_gen, tol=tol, stack_of=stack_of)
+        singles = [eng.DEPlan(st[c], None if sd is None else sd[c], t, means[k], pcas[k], -1.0, 1.0, pop[k], lower, upper, seeds[k], max_gen,
+                              tol=tol) for k, c in enumerate(stack_of)]
+        for _ in range(gens + 1):
+            batch.launch()
+            for pl in singles:
+                pl.launch()
+        for k, pl in enumerate(singles):
+            for what in ("population", "energies", "trial", "trial_energies", "icrf", "valid", "status"):
+                compare(f"{name} problem {k} {what}", getattr(batch, what)[k], getattr(pl, what), None)
+    return desc
+
+
 CASES = [(case_merge, 5), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2)]
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()
 counts = {fn.__name__: 0 for fn, _ in CASES}
