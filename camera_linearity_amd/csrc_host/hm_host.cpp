@@ -553,7 +553,7 @@ static int roi_mean(const T* img, int64_t H, int64_t W, int C, int64_t x0, int64
         for (int64_t q = y0; q < y1; ++q)
             for (int c = 0; c < C; ++c) acc[c] += static_cast<double>(img[(r * W + q) * C + c]);
     const double cnt = static_cast<double>((x1 - x0) * (y1 - y0));
-    for (int c = 0; c < C; ++c) out[c] = (acc[c] / cnt) / scale;                  // measurand.py:579 (uint8 images: DN / 255)
+    for (int c = 0; c < C; ++c) out[c] = (acc[c] / scale) / cnt;                  // measurand.py:579 (uint8 images: DN / 255); k_roi_final's order
     return HM_OK;
 }
 extern "C" {
@@ -837,6 +837,7 @@ int hm_channel_minmax(const double* val, const double* std_, int64_t n, int C, d
 int hm_channel_histogram(const double* val, const double* std_, int64_t n, int C, int channel_mask, const double* edges, int bins, double lo,
                          double hi, double* out, void*, void*) {
     if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || bins < 1 || !val || !edges || !out || !(hi > lo)) return HM_EINVAL;
+    if (static_cast<int64_t>(bins) * C > 8192) return HM_EUNSUPPORTED;         // (the device build's limit, 64 KB of LDS: one ABI, one answer)
     for (int i = 0; i < C * bins; ++i) out[i] = 0.0;
     const double norm = static_cast<double>(bins) / (hi - lo);
     for (int64_t e = 0; e < n; ++e) {                                                                     // np.histogram, measurand.py:430-469

@@ -893,6 +893,8 @@ def channel_histogram(val: torch.Tensor, std: Optional[torch.Tensor], bins: int,
         groups = {}
         for c in channels:
             lo, hi = (float(mmh[c, 0]), float(mmh[c, 1])) if included_range is None else (float(included_range[0]), float(included_range[1]))
+            if included_range is None and lo > hi:         # (+inf, -inf): nothing counted - np.histogram of an empty selection uses (0, 1)
+                lo, hi = 0.0, 1.0
             if lo == hi:                                   # np.histogram widens an empty range by +-0.5
                 lo, hi = lo - 0.5, hi + 0.5
             groups.setdefault((lo, hi), []).append(c)

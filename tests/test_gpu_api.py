@@ -143,7 +143,8 @@ def test_linearize_property(M, c, h, w, seed, with_std):
 @pytest.mark.parametrize("use_std", [False, True])
 @pytest.mark.parametrize("rng_", [None, (0.1, 0.9)])
 def test_channel_histogram_matches_numpy(M, use_std, rng_):
-    """compute_channel_histogram (measurand.py:430-469) = np.histogram per channel; counts exact, weighted sums 1e-12."""
+    """compute_channel_histogram (measurand.py:430-469) = np.histogram per channel; counts exact, weighted sums 1e-12
+    and within the derived bound of tests/test_stats_limits_host.py."""
     rng = np.random.default_rng(8)
     v = rng.random((64, 48, 3))
     v[3, 4, 0] = np.nan; v[5, 6, 1] = np.inf; v[0, 0, 2] = 0.9; v[1, 1, 2] = 0.1          # non-finite values and exact range edges
@@ -162,6 +163,9 @@ def test_channel_histogram_matches_numpy(M, use_std, rng_):
         np.testing.assert_allclose(got[c][1], ref_e, rtol=0, atol=0)
         if use_std:
             np.testing.assert_allclose(got[c][0], ref_h, rtol=1e-12)
+            # and the derived bound (k_b + 2) u sum|1/std| of tests/test_stats_limits_host.py: about 1e-14 here, the tighter of the two
+            import test_stats_limits_host as sl
+            sl.assert_hist("histogram hip", got[c][0], got[c][1], sl.hist_reference(cv.ravel(), s[..., c].ravel(), 32, rng_), True, f"channel {c}")
         else:
             assert np.array_equal(got[c][0], ref_h)
 
