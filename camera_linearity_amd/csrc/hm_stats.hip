@@ -364,6 +364,11 @@ __device__ __forceinline__ void acc_add(MomAcc& a, double v, double w, double s,
         w = 1.0;
     }
     if (weighted && use && !a.haveK) { weighted_first(a, v, w); return; }   // (rare: a lane's first two elements; v is finite here - v w is)
+    // An element that outweighs everything the lane has seen so far by 2^10 (rare; a std of 1e-200 beside ordinary ones is the extreme) must
+    // not sit in a block whose shift is somewhere else: its w (v - K)^2 would absorb the block's other terms in S2 to within u x the
+    // weight ratio, and S2 - S1 q then cancels down to nothing. The block so far is folded and the element becomes the shift of a new one
+    // (d = 0 exactly), as weighted_first() does for a lane's first two elements. Per lane; acc_fold() has no cross-lane step.
+    if (weighted && use && fabs(w) > 0x1p10 * fabs(a.S0 + a.m.W)) { acc_fold<false>(a); a.K = v; }
     a.K = (!a.haveK && use) ? v : a.K;
     a.haveK = a.haveK || use;
     const double we = use ? w : 0.0;
@@ -536,7 +541,10 @@ __device__ __forceinline__ void mom_finish(const Mom& m, bool weighted, double& 
         err = weighted ? m.ss / m.cs : nan;
         return;
     }
-    const double M2 = fmax(m.M2, 0.0);                      // a sum of squares: rounding in S2 - S1^2 / S0 may leave -1e-13 where the data have no spread
+    // sum w (v - mean)^2 has the sign of the weights: rounding in S2 - S1^2 / S0 may leave -1e-13 on the other side of 0 where the data have no
+    // spread. Stds that are all negative give w = 1 / std < 0 throughout: M2 and Wall are both negative and the reference's std is the
+    // ordinary positive one (measurand.py:342-346) - an unconditional max(M2, 0) made it 0.
+    const double M2 = m.W < 0.0 ? fmin(m.M2, 0.0) : fmax(m.M2, 0.0);
     if (m.Wall == m.W) { mean = m.W == 0.0 ? nan : m.mean; sd = sqrt(M2 / m.Wall); }
     else {                                                  // some weights belong to NaN values: the reference's denominators still count them
         mean = (m.W * m.mean) / m.Wall;
@@ -1281,9 +1289,12 @@ extern "C" size_t hm_channel_statistics_workspace_bytes(void) {
     return sizeof(double) * (kStatBlocks * HM_MAX_CHANNELS * kMomVals);
 }
 
+// n counts the elements of whole pixels (n % C == 0: HM_EINVAL otherwise, on both builds). The stds of a channel are expected to have one
+// sign: all negative gives the reference's statistics with error = nanmean(std) < 0; with mixed signs sum(1 / std) can cancel and
+// nothing is promised.
 extern "C" int hm_channel_statistics(const double* val, const double* std, int64_t n, int C,
                                      double* out /*3*C: mean, std, error*/, void* workspace, void* stream) {
-    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !val || !out || !workspace) return HM_EINVAL;
+    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !val || !out || !workspace || n % C != 0) return HM_EINVAL;
     if (!aligned(val, 8) || (std && !aligned(std, 8))) return HM_EALIGN;
     double* partial = static_cast<double*>(workspace);
     const int grid = stat_grid(n);
@@ -1300,7 +1311,8 @@ extern "C" size_t hm_pair_statistics_workspace_bytes(void) {
 
 extern "C" int hm_pair_statistics(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
                                   int64_t n, int C, double* out /*6*C*/, void* workspace, void* stream) {
-    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !x || !y || !out || !workspace) return HM_EINVAL;
+    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !x || !y || !out || !workspace || n % C != 0) return HM_EINVAL;
+    if (!aligned(x, 8) || !aligned(y, 8) || (sx && !aligned(sx, 8)) || (sy && !aligned(sy, 8))) return HM_EALIGN;
     double* partial = static_cast<double*>(workspace);
     const int grid = stat_grid(n);
     hipStream_t st = as_stream(stream);
@@ -1321,7 +1333,9 @@ extern "C" int hm_pairs_statistics(const double* const* vals, const double* cons
                                    const double* lower, const double* upper,
                                    double* out /*n_pairs * 6C*/, void* workspace, void* stream) {
     if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
-    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr))) return HM_EINVAL;
+    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i) if (!aligned(vals[i], 8) || (stds && !aligned(stds[i], 8))) return HM_EALIGN;
     const bool thr = lower != nullptr;
     PairsK k{};
     k.n = n; k.C = C; k.with_std = stds ? 1 : 0;
@@ -1331,9 +1345,8 @@ extern "C" int hm_pairs_statistics(const double* const* vals, const double* cons
         k.hi[c] = lim.hi[c] = (thr && c < C) ? upper[c] : __builtin_huge_val();
     }
     for (int i = 0; i < n_frames; ++i) {
-        if (!vals[i] || !aligned(vals[i], 8)) return HM_EINVAL;
         k.val[i] = vals[i];
-        if (stds) { if (!stds[i]) return HM_EINVAL; k.sd[i] = stds[i]; }
+        if (stds) k.sd[i] = stds[i];
     }
     for (int p = 0; p < n_pairs; ++p)
         if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;

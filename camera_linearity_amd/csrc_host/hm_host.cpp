@@ -29,6 +29,14 @@ constexpr double kInf = std::numeric_limits<double>::infinity();
 
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
+// the element count of a dense block of the given extents, or -1 when an extent is < 1 or the product is above 2^48 (as the HIP build)
+inline int64_t dense_elems(std::initializer_list<int64_t> dims) {
+    int64_t n = 1;
+    for (int64_t d : dims)
+        if (d < 1 || __builtin_mul_overflow(n, d, &n) || n > (int64_t{1} << 48)) return -1;
+    return n;
+}
+
 // measurand.py:615: w = e ** (-30 (v - 0.5)^2)
 inline double gauss_weight(double dv) { return std::exp(-30.0 * (dv * dv)); }
 
@@ -741,7 +749,8 @@ int hm_interpolate(const double* x0, const double* s0, const double* x1, const d
 size_t hm_axis_statistics_workspace_bytes(int64_t, int64_t, int64_t) { return 0; }
 int hm_axis_statistics(const double* val, const double* std_, int64_t outer, int64_t axis_len, int64_t inner, double* out_mean,
                        double* out_std, double* out_err, void*, void*) {
-    if (outer < 1 || axis_len < 1 || inner < 1 || !val || !out_mean || !out_std) return HM_EINVAL;
+    if (dense_elems({outer, axis_len, inner}) < 0 || !val || !out_mean || !out_std) return HM_EINVAL;
+    if (!aligned8(val) || !aligned8(std_)) return HM_EALIGN;
     const int64_t n_out = outer * inner;
 #pragma omp parallel for schedule(static)
     for (int64_t j = 0; j < n_out; ++j) {
@@ -759,7 +768,8 @@ int hm_axis_statistics(const double* val, const double* std_, int64_t outer, int
 size_t hm_axis_statistics2_workspace_bytes(int64_t, int64_t, int64_t, int64_t, int64_t) { return 0; }
 int hm_axis_statistics2(const double* val, const double* std_, int64_t outer, int64_t a1, int64_t mid, int64_t a2, int64_t inner,
                         double* out_mean, double* out_std, double* out_err, void*, void*) {
-    if (outer < 1 || a1 < 1 || mid < 1 || a2 < 1 || inner < 1 || !val || !out_mean || !out_std) return HM_EINVAL;
+    if (dense_elems({outer, a1, mid, a2, inner}) < 0 || !val || !out_mean || !out_std) return HM_EINVAL;
+    if (!aligned8(val) || !aligned8(std_)) return HM_EALIGN;
     const int64_t n_out = outer * mid * inner, line = a1 * a2;
 #pragma omp parallel for schedule(static)
     for (int64_t j = 0; j < n_out; ++j) {
@@ -775,15 +785,16 @@ int hm_axis_statistics2(const double* val, const double* std_, int64_t outer, in
 }
 
 size_t hm_channel_statistics_workspace_bytes(void) { return 64; }
-int hm_channel_statistics(const double* val, const double* std_, int64_t n, int C, double* out, void*, void*) {
-    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !val || !out || n % C != 0) return HM_EINVAL;
+int hm_channel_statistics(const double* val, const double* std_, int64_t n, int C, double* out, void* workspace, void*) {
+    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !val || !out || !workspace || n % C != 0) return HM_EINVAL;
     return hm_axis_statistics(val, std_, 1, n / C, C, out, out + C, out + 2 * C, nullptr, nullptr);
 }
 
 size_t hm_pair_statistics_workspace_bytes(void) { return 64; }
 int hm_pair_statistics(const double* x, const double* sx, const double* y, const double* sy, double multiplier, int64_t n, int C,
-                       double* out, void*, void*) {
-    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !x || !y || !out || n % C != 0) return HM_EINVAL;
+                       double* out, void* workspace, void*) {
+    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !x || !y || !out || !workspace || n % C != 0) return HM_EINVAL;
+    if (!aligned8(x) || !aligned8(y) || !aligned8(sx) || !aligned8(sy)) return HM_EALIGN;
     const bool with_std = sx || sy;
     const int64_t A = n / C;
     for (int h = 0; h < 2; ++h)
@@ -804,11 +815,11 @@ int hm_pair_statistics(const double* x, const double* sx, const double* y, const
 size_t hm_pairs_statistics_workspace_bytes(int) { return 64; }
 int hm_pairs_statistics(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
                         const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
-                        void*, void*) {
-    if (n_frames < 1 || n_pairs < 0 || n < 1 || C < 1 || C > HM_MAX_CHANNELS || !vals || !out || (n_pairs && (!pair_i || !pair_j || !multipliers)))
-        return HM_EINVAL;
-    if ((lower != nullptr) != (upper != nullptr)) return HM_EINVAL;
+                        void* workspace, void*) {
+    if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
+    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
     for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i) if (!aligned8(vals[i]) || (stds && !aligned8(stds[i]))) return HM_EALIGN;
     for (int p = 0; p < n_pairs; ++p)
         if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
     if (lower)                                                                                           // exposure_series.py:437-441, in place
@@ -817,7 +828,7 @@ int hm_pairs_statistics(const double* const* vals, const double* const* stds, in
 #pragma omp parallel for schedule(dynamic)
     for (int p = 0; p < n_pairs; ++p)
         hm_pair_statistics(vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, multipliers[p],
-                           n, C, out + static_cast<int64_t>(p) * 6 * C, nullptr, nullptr);
+                           n, C, out + static_cast<int64_t>(p) * 6 * C, workspace, nullptr);
     return HM_OK;
 }
 

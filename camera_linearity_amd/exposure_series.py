@@ -21,6 +21,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from . import _native as nat
 from . import settings as gs
 from .image_set import ImageSet
 
@@ -335,7 +336,7 @@ class ExposureSeries(object):
         pair it takes part in. Applies when the pairs are pairs of this series' own images, all images share one (H, W, C <= 4)
         shape on one device and either all or none of them carry a std; otherwise the per-pair path above runs."""
         sets = self.input_image_sets
-        if not self.exposure_pairs or not sets:
+        if not self.exposure_pairs or not sets or len(sets) > nat.HM_MAX_FRAMES:      # (hm_pairs_statistics takes no more on either build)
             return False
         index = {id(s): i for i, s in enumerate(sets)}
         if any(id(p.short_exposure) not in index or id(p.long_exposure) not in index for p in self.exposure_pairs):

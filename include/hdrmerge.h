@@ -280,6 +280,13 @@ int hm_interpolate(const double* x0, const double* s0, const double* x1, const d
  * (modules/exposure_series.py:33-54, the per-pair body of process_linearity :443-446): the statistics of
  * the absolute and relative difference of two frames without writing the difference images.
  * out is 6*C float64 on the device: [abs mean | abs std | abs error | rel mean | rel std | rel error]. */
+/* Status codes of the statistics entry points below, the same on both builds: n counts the elements of whole pixels, so n % C != 0 is
+ * HM_EINVAL, as are n < 1, C outside 1..HM_MAX_CHANNELS, an extent < 1 or a product of extents above 2^48, a NULL val / out / workspace
+ * (hm_axis_statistics: a NULL workspace only where hm_axis_statistics_workspace_bytes() is not 0), n_pairs < 1, n_frames outside
+ * 1..HM_MAX_FRAMES, a pair index outside the frames and `lower` without `upper`; a value or std buffer that is not 8-byte aligned is
+ * HM_EALIGN. Every one of them returns before anything is launched or written.
+ * The stds of one reduction line are expected to have one sign: all negative gives the reference's mean and (positive) std with
+ * error = nanmean(std) < 0; with mixed signs sum(1 / std) can cancel and nothing is promised. */
 size_t hm_pair_statistics_workspace_bytes(void);
 int hm_pair_statistics(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
                        int64_t n, int C, double* out, void* workspace, void* stream);

@@ -198,6 +198,33 @@ def test_host_process_linearity_matches_oracle():
     assert k == 6
 
 
+def test_host_process_linearity_above_hm_max_frames_goes_pair_by_pair():
+    """33 image sets: hm_pairs_statistics takes at most HM_MAX_FRAMES = 32 frames (HM_EINVAL on either build), so process_linearity
+    compares pair by pair (hm_pair_statistics) - and answers as it does for 32 sets, where the fused entry point runs."""
+    from camera_linearity_amd import _native as nat
+    from camera_linearity_amd.exposure_series import ExposureSeries
+    from camera_linearity_amd.image_set import ImageSet
+    n = nat.HM_MAX_FRAMES + 1
+    frames, stds, _ = orc.synthetic_stack(7, n, 8, 6, with_std=True)
+    t = [1.0 + 0.02 * i for i in range(n)]                               # every ratio above 0.1: all n (n - 1) / 2 pairs
+    icrf, _ = orc.synthetic_icrf((1.0, 1.0, 1.0))
+    calls, stats = nat.host_lib().calls, {}
+    for m in (n, n - 1):
+        sets = [ImageSet(value=orc.unit_from_u8(f), std=s.copy(), features=_features(ti)) for f, s, ti in zip(frames[:m], stds[:m], t)]
+        series = ExposureSeries(input_image_sets=sets)
+        series.initialize_exposure_pairs()
+        assert len(series.exposure_pairs) == m * (m - 1) // 2
+        before = calls["hm_pairs_statistics"], calls["hm_pair_statistics"]
+        series.process_linearity(icrf, linearity_limit=5, use_std=True)
+        fused, single = calls["hm_pairs_statistics"] - before[0], calls["hm_pair_statistics"] - before[1]
+        assert (fused, single) == ((0, m * (m - 1) // 2) if m > nat.HM_MAX_FRAMES else (1, 0)), (m, fused, single)
+        stats[m] = series.collect_exposure_pair_stats()
+    first = [k for k, (i, j) in enumerate((i, j) for i in range(n) for j in range(i + 1, n)) if j < n - 1]     # the pairs both series have
+    for a_, b_ in zip(stats[n], stats[n - 1]):
+        for key in ("means", "stds", "errors"):
+            np.testing.assert_allclose(a_[key][first], b_[key], rtol=1e-11, equal_nan=True)
+
+
 def test_host_merge_any_number_of_frames_and_tiles(heng):
     n, h, w = 40, 12, 10
     frames, stds, t = orc.synthetic_stack(3, n, h, w, with_std=True)
