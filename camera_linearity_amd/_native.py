@@ -21,6 +21,8 @@ LIB_PATH = pathlib.Path(os.environ.get("HDRMERGE_LIB", _HERE / "lib" / "libhdrme
 HM_MAX_FRAMES = 32
 HM_MAX_CHANNELS = 4
 HM_MAX_DIMS = 6
+HM_PAIRS_MAX = 16
+HM_PAIRS_HIST_MAX_BINS = 2048
 HM_KDE_MOMENTS = 11
 HM_DE_MAX_POP, HM_DE_MAX_PARAMS, HM_DE_STATUS_WORDS = 1024, 32, 8
 HM_DE_MAX_PROBLEMS = 64
@@ -103,6 +105,14 @@ _SIGNATURES = {
     "hm_channel_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_channel_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (lower / upper are HOST arrays of C doubles: typed, so that nothing but a host array or None is ever passed for them)
+    "hm_pairs_histogram_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hm_pairs_minmax": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hm_pairs_histogram": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_channel_statistics_workspace_bytes": (C.c_size_t, []),
     "hm_channel_statistics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_axis_statistics_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),

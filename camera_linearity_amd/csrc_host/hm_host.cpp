@@ -868,6 +868,102 @@ int hm_channel_histogram(const double* val, const double* std_, int64_t n, int C
     return HM_OK;
 }
 
+// ---- distributions of all exposure pairs (hm_pairs_minmax / hm_pairs_histogram): the difference terms of diff_terms() on the values as
+// read through the thresholds, hm_channel_minmax's / hm_channel_histogram's counting rule, weighted sums added in index order
+namespace {
+int pairs_dist_check(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
+                     const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, const void* out,
+                     const void* workspace) {
+    if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
+    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i) if (!aligned8(vals[i]) || (stds && !aligned8(stds[i]))) return HM_EALIGN;
+    for (int p = 0; p < n_pairs; ++p)
+        if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
+    return HM_OK;
+}
+
+// element e of pair (x, y): loaded, thresholded as read (a value outside its channel's limits is NaN with its std), differenced
+struct PairElems {
+    const double* x; const double* sx; const double* y; const double* sy;
+    const double* lower; const double* upper;
+    double mult; int C;
+    void at(int64_t e, double& a, double& as, double& r, double& rs) const {
+        double xv = x[e], yv = y[e], xs = sx ? sx[e] : 0.0, ys = sy ? sy[e] : 0.0;
+        if (lower) {
+            const int c = static_cast<int>(e % C);
+            if (xv < lower[c] || xv > upper[c]) { xv = kNaN; xs = sx ? kNaN : 0.0; }                      // measurand.py:418
+            if (yv < lower[c] || yv > upper[c]) { yv = kNaN; ys = sy ? kNaN : 0.0; }
+        }
+        diff_terms(xv, xs, yv, ys, mult, sx != nullptr, a, as, r, rs);
+    }
+};
+}  // namespace
+
+size_t hm_pairs_histogram_workspace_bytes(int, int, int) { return 64; }
+int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
+                    const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
+                    void* workspace, void*) {
+    const int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    if (rc != HM_OK) return rc;
+#pragma omp parallel for schedule(dynamic)
+    for (int p = 0; p < n_pairs; ++p) {
+        const PairElems pe{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
+                           multipliers[p], C};
+        double* o = out + static_cast<int64_t>(p) * 2 * C * 2;
+        for (int i = 0; i < 2 * C; ++i) { o[2 * i] = kInf; o[2 * i + 1] = -kInf; }
+        for (int64_t e = 0; e < n; ++e) {
+            double v[2], s[2];
+            pe.at(e, v[0], s[0], v[1], s[1]);
+            const int c = static_cast<int>(e % C);
+            for (int k = 0; k < 2; ++k) {
+                if (!(std::fabs(v[k]) <= std::numeric_limits<double>::max())) continue;
+                if (stds && s[k] == 0.0) continue;
+                double* m = o + (k * C + c) * 2;
+                m[0] = std::fmin(m[0], v[k]); m[1] = std::fmax(m[1], v[k]);
+            }
+        }
+    }
+    return HM_OK;
+}
+int hm_pairs_histogram(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
+                       const double* multipliers, int n_pairs, int64_t n, int C, int channel_mask, const double* lower, const double* upper,
+                       const double* edges, int bins, double* out, void* workspace, void*) {
+    int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    if (rc == HM_OK && (bins < 1 || bins > HM_PAIRS_HIST_MAX_BINS || !edges || channel_mask < 0 || (channel_mask >> C) != 0)) rc = HM_EINVAL;
+    if (rc != HM_OK) return rc;
+#pragma omp parallel for schedule(dynamic)
+    for (int p = 0; p < n_pairs; ++p) {
+        const PairElems pe{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
+                           multipliers[p], C};
+        double* o = out + static_cast<int64_t>(p) * 2 * C * bins;
+        const double* eg = edges + static_cast<int64_t>(p) * 2 * C * (bins + 1);
+        for (int64_t i = 0; i < int64_t{2} * C * bins; ++i) o[i] = 0.0;
+        for (int64_t e = 0; e < n; ++e) {
+            const int c = static_cast<int>(e % C);
+            if (!((channel_mask >> c) & 1)) continue;
+            double v[2], s[2];
+            pe.at(e, v[0], s[0], v[1], s[1]);
+            for (int k = 0; k < 2; ++k) {
+                const double x = v[k];
+                const double* ek = eg + static_cast<int64_t>(k * C + c) * (bins + 1);
+                const double lo = ek[0], hi = ek[bins];
+                if (!(hi > lo)) continue;                                                                 // (hm_channel_histogram: HM_EINVAL)
+                if (!(std::fabs(x) <= std::numeric_limits<double>::max())) continue;
+                double w = 1.0;
+                if (stds) { if (s[k] == 0.0) continue; w = 1.0 / s[k]; }                                  // :457,460
+                if (!(x >= lo && x <= hi)) continue;
+                const double t = (x - lo) * (static_cast<double>(bins) / (hi - lo));
+                int idx = t < static_cast<double>(bins) ? static_cast<int>(t) : bins - 1;                 // (the device build's form: never outside 0..bins-1)
+                if (x < ek[idx]) idx -= 1;
+                else if (x >= ek[idx + 1] && idx != bins - 1) idx += 1;
+                o[static_cast<int64_t>(k * C + c) * bins + idx] += w;
+            }
+        }
+    }
+    return HM_OK;
+}
+
 // ---- the producers ---------------------------------------------------------------------------------
 // welford_algorithm, modules/video_processing.py:161-219: per element, frames in order - delta = f - mean; mean += delta / n;
 // m2 += delta * (f - mean) (:205-208), f = icrf[dn, c] (:200-201) or dn / 255 (:203)

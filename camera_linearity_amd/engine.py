@@ -911,6 +911,72 @@ def channel_histogram(val: torch.Tensor, std: Optional[torch.Tensor], bins: int,
     return out
 
 
+def pairs_histogram(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch.Tensor]], pairs: Sequence[tuple], bins: int, included_range,
+                    channels: Sequence[int], thresholds: Optional[tuple] = None):
+    """ExposurePair.compute_difference + process_linearity_distribution of EVERY exposure pair of a stack without the difference images
+    (hm_pairs_histogram; `pairs` as in pairs_statistics). Returns one (abs_dict, rel_dict) per pair, each {c: (hist, bin_edges)} as
+    channel_histogram() builds them: int64 counts without stds, float64 sums of 1 / std with them, edges np.linspace(lo, hi, bins + 1).
+    included_range None: np.histogram's default range per (pair, kind, channel) from hm_pairs_minmax (one host copy), with channel_histogram's
+    two NumPy rules. thresholds = (lower, upper): apply_thresholds on the values as read; the frames are NOT modified."""
+    n, bins = len(vals), int(bins)
+    for i, v in enumerate(vals):
+        _require_cuda(v, f"vals[{i}]")
+        if v.shape != vals[0].shape or v.dtype != _F64:
+            raise ValueError("pairs_histogram needs float64 frames of one shape")
+    if not 1 <= bins <= nat.HM_PAIRS_HIST_MAX_BINS:
+        raise ValueError(f"pairs_histogram takes 1..{nat.HM_PAIRS_HIST_MAX_BINS} bins")
+    dev = vals[0].device
+    vals = [v.contiguous() for v in vals]
+    if stds is not None:
+        if len(stds) != n or any(s is None for s in stds):
+            raise ValueError("one std frame per value frame (or none at all)")
+        stds = [s.to(_F64).contiguous() for s in stds]
+    Cc = vals[0].shape[-1]
+    channels = [int(c) for c in channels]
+    if any(c < 0 or c >= Cc for c in channels):
+        raise ValueError("channel outside the frames' channels")
+    lo = hi = None
+    if thresholds is not None:
+        if len(thresholds[0]) != Cc or len(thresholds[1]) != Cc:
+            raise ValueError("The length of 'lower' and 'upper' must match the size of the independent axis.")
+        lo = (C.c_double * Cc)(*[float(x) for x in thresholds[0]])
+        hi = (C.c_double * Cc)(*[float(x) for x in thresholds[1]])
+    P = len(pairs)
+    vp = C.cast(_ptr_array(vals), C.POINTER(C.c_void_p))
+    sp = None if stds is None else C.cast(_ptr_array(stds), C.POINTER(C.c_void_p))
+    pi = (C.c_int32 * P)(*[int(p[0]) for p in pairs])
+    pj = (C.c_int32 * P)(*[int(p[1]) for p in pairs])
+    pm = (C.c_double * P)(*[float(p[2]) for p in pairs])
+    ws = torch.empty(max(1, nat.lib.hm_pairs_histogram_workspace_bytes(P, bins, Cc) // 8), dtype=_F64, device=dev)
+    with _on(dev):
+        if included_range is None:
+            mm = torch.empty(P * 2 * Cc * 2, dtype=_F64, device=dev)
+            nat.check(nat.lib.hm_pairs_minmax(vp, sp, n, pi, pj, pm, P, vals[0].numel(), Cc, lo, hi, mm.data_ptr(), ws.data_ptr(), _stream(dev)),
+                      "hm_pairs_minmax")
+            ranges = mm.cpu().numpy().reshape(P, 2, Cc, 2).copy()          # one device-to-host copy for all pairs
+            empty = ranges[..., 0] > ranges[..., 1]                        # (+inf, -inf): nothing counted - np.histogram of an empty selection uses (0, 1)
+            ranges[empty] = (0.0, 1.0)
+        else:
+            ranges = np.empty((P, 2, Cc, 2))
+            ranges[..., 0], ranges[..., 1] = float(included_range[0]), float(included_range[1])
+        same = ranges[..., 0] == ranges[..., 1]                            # np.histogram widens an empty range by +-0.5
+        ranges[same] += (-0.5, 0.5)
+        if not np.all(ranges[:, :, channels, 1] > ranges[:, :, channels, 0]):
+            raise ValueError("pairs_histogram: the upper end of the range must be above the lower end")
+        edges = np.zeros((P, 2, Cc, bins + 1))
+        for idx in np.ndindex(P, 2, Cc):
+            if idx[2] in channels:
+                edges[idx] = np.linspace(ranges[idx][0], ranges[idx][1], bins + 1)
+        edges_d = torch.as_tensor(edges, device=dev)
+        res = torch.empty(P * 2 * Cc * bins, dtype=_F64, device=dev)
+        nat.check(nat.lib.hm_pairs_histogram(vp, sp, n, pi, pj, pm, P, vals[0].numel(), Cc, sum(1 << c for c in set(channels)), lo, hi,
+                                             edges_d.data_ptr(), bins, res.data_ptr(), ws.data_ptr(), _stream(dev)), "hm_pairs_histogram")
+        r = res.cpu().numpy().reshape(P, 2, Cc, bins)
+    if stds is None:
+        r = r.astype(np.int64)
+    return [tuple({c: (r[p, k, c], edges[p, k, c]) for c in channels} for k in range(2)) for p in range(P)]
+
+
 # ------------------------------------------------------------------------------------------------
 # weighted Gaussian kernel density estimates (modules/measurand.py:716-761)
 # ------------------------------------------------------------------------------------------------

@@ -331,27 +331,38 @@ class ExposureSeries(object):
                 pair.compute_difference()
                 pair.compute_stats(axis=(0, 1), release_memory_after=True)
 
+    def _own_pairs_stack(self):
+        """(vals, stds or None, [(i, j, exposure ratio), ...]) when one all-pairs launch can serve this series: the pairs are pairs of the
+        series' own images, all images share one (H, W, C <= 4) shape on one device and one backend and either all or none of them carry a
+        std. None otherwise."""
+        sets = self.input_image_sets
+        if not self.exposure_pairs or not sets or len(sets) > nat.HM_MAX_FRAMES:      # (hm_pairs_statistics takes no more on either build)
+            return None
+        index = {id(s): i for i, s in enumerate(sets)}
+        if any(id(p.short_exposure) not in index or id(p.long_exposure) not in index for p in self.exposure_pairs):
+            return None
+        shapes = {s.measurand.shape for s in sets}
+        if len(shapes) != 1 or None in shapes or len(next(iter(shapes))) != 3 or next(iter(shapes))[-1] > 4:
+            return None
+        have_std = [s.measurand._std is not None for s in sets]
+        if any(have_std) != all(have_std):
+            return None
+        vals = [s.measurand._f64() for s in sets]
+        if not all(v.device == vals[0].device for v in vals) or len({s.measurand.backend for s in sets}) != 1:
+            return None
+        stds = [s.measurand._std for s in sets] if all(have_std) else None
+        pairs = [(index[id(p.short_exposure)], index[id(p.long_exposure)], p.exposure_ratio) for p in self.exposure_pairs]
+        return vals, stds, pairs
+
     def _all_pairs_fused(self, lower=None, upper=None) -> bool:
         """Every pair of the series in ONE launch (hm_pairs_statistics): each frame is read from HBM once instead of once per
         pair it takes part in. Applies when the pairs are pairs of this series' own images, all images share one (H, W, C <= 4)
         shape on one device and either all or none of them carry a std; otherwise the per-pair path above runs."""
+        stack = self._own_pairs_stack()
+        if stack is None:
+            return False
         sets = self.input_image_sets
-        if not self.exposure_pairs or not sets or len(sets) > nat.HM_MAX_FRAMES:      # (hm_pairs_statistics takes no more on either build)
-            return False
-        index = {id(s): i for i, s in enumerate(sets)}
-        if any(id(p.short_exposure) not in index or id(p.long_exposure) not in index for p in self.exposure_pairs):
-            return False
-        shapes = {s.measurand.shape for s in sets}
-        if len(shapes) != 1 or None in shapes or len(next(iter(shapes))) != 3 or next(iter(shapes))[-1] > 4:
-            return False
-        have_std = [s.measurand._std is not None for s in sets]
-        if any(have_std) != all(have_std):
-            return False
-        vals = [s.measurand._f64() for s in sets]
-        if not all(v.device == vals[0].device for v in vals) or len({s.measurand.backend for s in sets}) != 1:
-            return False
-        stds = [s.measurand._std for s in sets] if all(have_std) else None
-        pairs = [(index[id(p.short_exposure)], index[id(p.long_exposure)], p.exposure_ratio) for p in self.exposure_pairs]
+        vals, stds, pairs = stack
         thresholds = None
         if lower is not None or upper is not None:           # apply_thresholds (measurand.py:375-428) inside the launch, in place
             n_ch = vals[0].shape[-1]
@@ -374,6 +385,47 @@ class ExposureSeries(object):
             p.absolute_stats, p.relative_stats = {k: exp(v) for k, v in ab.items()}, {k: exp(v) for k, v in rel.items()}
             p.absolute_difference = p.relative_difference = None
         return True
+
+    def process_linearity_distribution(self, bins: int, included_range=None, channels=None, use_std: Optional[bool] = False,
+                                       lower: Optional[List] = None, upper: Optional[List] = None):
+        """The distributions of every exposure pair: a list in self.exposure_pairs order of what pair.compute_difference() followed by
+        pair.process_linearity_distribution(bins, included_range, channels, use_std) returns - (absolute, relative), each
+        {channel: (hist, bin_edges)}. lower / upper: per-channel limits as apply_thresholds takes them, applied to the values as they are
+        read: no image set is changed (process_linearity stays the call that thresholds in place).
+        Under the conditions of _all_pairs_fused (and use_std only with a std on every image, bins <= HM_PAIRS_HIST_MAX_BINS) all pairs
+        go through hm_pairs_histogram - no difference image is written, a frame is read once per launch; otherwise pair by pair through
+        the difference images, each pair's dropped after its histograms."""
+        if channels is None:
+            channels = list(range(gs.NUM_OF_CHS))
+        for image_set in self.input_image_sets:
+            if image_set.measurand.shape is None:
+                image_set.load_value_image()
+            if image_set.measurand._std is None and use_std:
+                image_set.load_std_image()
+        stack = self._own_pairs_stack() if int(bins) <= nat.HM_PAIRS_HIST_MAX_BINS else None
+        if stack is not None and (not use_std or stack[1] is not None):
+            vals, stds, pairs = stack
+            n_ch = vals[0].shape[-1]
+            thresholds = None
+            if lower is not None or upper is not None:
+                lower = [None] * n_ch if lower is None else lower
+                upper = [None] * n_ch if upper is None else upper
+                thresholds = ([-math.inf if l is None else l for l in lower], [math.inf if u is None else u for u in upper])
+            return self._eng().pairs_histogram(vals, stds if use_std else None, pairs, bins, included_range, channels, thresholds=thresholds)
+        import copy
+        out = []
+        for pair in self.exposure_pairs or []:
+            if lower is None and upper is None:
+                ab, rel = ImageSet.compute_difference(pair.short_exposure, pair.long_exposure)
+            else:                                            # thresholded copies: the series' images stay as they are
+                short, long_ = copy.copy(pair.short_exposure), copy.copy(pair.long_exposure)
+                short.measurand, long_.measurand = copy.deepcopy(short.measurand), copy.deepcopy(long_.measurand)
+                short.measurand.apply_thresholds(lower, upper)
+                long_.measurand.apply_thresholds(lower, upper)
+                ab, rel = ImageSet.compute_difference(short, long_)
+            out.append((ab.measurand.compute_channel_histogram(bins, included_range, channels, use_std),
+                        rel.measurand.compute_channel_histogram(bins, included_range, channels, use_std)))
+        return out
 
     def collect_exposure_pair_stats(self, return_cupy: Optional[bool] = False):
         rel = {"ratios": [], "means": [], "stds": [], "errors": []}

@@ -315,6 +315,32 @@ int hm_channel_minmax(const double* val, const double* std /*nullable*/, int64_t
                       void* workspace, void* stream);
 int hm_channel_histogram(const double* val, const double* std /*nullable*/, int64_t n, int C, int channel_mask,
                          const double* edges, int bins, double lo, double hi, double* out, void* workspace, void* stream);
+/* ExposurePair.process_linearity_distribution (modules/exposure_series.py: compute_difference, then compute_channel_histogram of the
+ * absolute and of the relative difference) for ALL pairs of a stack at once, without the difference images: arguments as
+ * hm_pairs_statistics. Kind 0 is the absolute, kind 1 the relative difference. For pair p, kind k and channel c the histogram equals
+ * hm_compute_difference(vals[pair_i[p]], ..., vals[pair_j[p]], ..., multipliers[p]) followed by hm_channel_histogram of that difference
+ * image (with stds: and of its std image) on edges[p][k][c][0 .. bins], lo the first and hi the last edge: the same difference
+ * expressions, the same counting rule. A (pair, kind, channel) whose last edge is not above its first counts nothing.
+ * edges: device, (n_pairs, 2, C, bins + 1) float64; out: device, (n_pairs, 2, C, bins) float64, channels outside channel_mask 0.0.
+ * lower / upper: [host] C limits each, or both NULL: apply_thresholds on the values AS READ - a value outside its channel's limits counts
+ * as NaN together with its std. The frames are NOT modified (hm_pairs_statistics stays the one entry point that thresholds in place).
+ * hm_pairs_minmax: np.histogram's default range, the min and max hm_channel_minmax would give on each difference image, out (n_pairs, 2,
+ * C, 2) = min, max; (+inf, -inf) where nothing counts.
+ * One launch per group of pairs whose histograms fit the 160 KiB of LDS of a CU (2 * C * bins * 8 bytes per pair; at most HM_PAIRS_MAX).
+ * Status codes: those of the statistics block above; in addition bins < 1, bins > HM_PAIRS_HIST_MAX_BINS, channel_mask with bits at or
+ * above C (or negative) and a NULL edges are HM_EINVAL. Every check returns before anything is launched, written or dereferenced.
+ * The workspace covers both calls. */
+#define HM_PAIRS_HIST_MAX_BINS 2048
+size_t hm_pairs_histogram_workspace_bytes(int n_pairs, int bins, int C);
+int hm_pairs_minmax(const double* const* vals, const double* const* stds /*nullable*/, int n_frames,
+                    const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                    int64_t n, int C, const double* lower /*nullable*/, const double* upper /*nullable*/,
+                    double* out /* device: (n_pairs, 2 kinds, C, 2) = min, max */, void* workspace, void* stream);
+int hm_pairs_histogram(const double* const* vals, const double* const* stds /*nullable*/, int n_frames,
+                       const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                       int64_t n, int C, int channel_mask, const double* lower /*nullable*/, const double* upper /*nullable*/,
+                       const double* edges /* device: (n_pairs, 2, C, bins + 1) */, int bins,
+                       double* out /* device: (n_pairs, 2, C, bins) */, void* workspace, void* stream);
 size_t hm_channel_statistics_workspace_bytes(void);
 int hm_channel_statistics(const double* val, const double* std /*nullable*/, int64_t n, int C,
                           double* out, void* workspace, void* stream);

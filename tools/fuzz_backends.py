@@ -626,8 +626,59 @@ def case_de_batch(rng):
     return desc
 
 
+def case_pairs_hist(rng):
+    """engine.pairs_histogram (hm_pairs_histogram / hm_pairs_minmax) on both builds: thresholds as read, channel subsets, given and default
+    ranges, bin counts on both sides of the pairs-per-launch splits. Unweighted counts and all edges must be equal; a weighted bin of k_b
+    elements may differ by 2 (k_b + 2) u sum|1 / std| - each build is within (k_b + 2) u sum|1 / std| of the exact sum whatever its
+    order of additions, and the stds drawn here are positive, so sum|1 / std| is the bin itself."""
+    c = int(rng.choice([1, 2, 3, 3, 4]))
+    n = int(rng.integers(2, 8))
+    h, w = int(rng.integers(1, 40 * args.scale)), int(rng.integers(1, 60 * args.scale))
+    rad = rng.random((h, w, c)) * 0.9 + 0.05
+    t = np.sort(rng.uniform(0.05, 1.0, size=n))
+    vals = [rad * ti * (1 + rng.normal(size=rad.shape) * 0.01) for ti in t]
+    stds = [0.004 * (1 + rng.random(rad.shape)) for _ in range(n)]
+    if rng.random() < args.specials:
+        for v in vals:
+            sprinkle(rng, v)
+        for sd in stds:
+            sprinkle(rng, sd, values=(0.0, np.inf), p=0.02)
+    pairs = [(i, j, float(t[i] / t[j])) for i in range(n) for j in range(i + 1, n)]
+    if rng.random() < 0.5:
+        pairs = [pairs[int(q)] for q in rng.choice(len(pairs), size=int(rng.integers(1, len(pairs) + 1)), replace=False)]
+    bins = int(rng.choice([1, 7, 64, 256, 700, 1138, 2048]))
+    rngs = None if rng.random() < 0.4 else (float(rng.uniform(-0.2, -0.01)), float(rng.uniform(0.01, 0.2)))
+    chans = sorted(int(a) for a in rng.choice(c, size=int(rng.integers(1, c + 1)), replace=False))
+    thr = None if rng.random() < 0.5 else ([float(rng.uniform(0.0, 0.1)) for _ in range(c)], [float(rng.uniform(0.5, 1.0)) for _ in range(c)])
+    with_std = bool(rng.random() < 0.5)
+    desc = f"pairs_hist n={n} {h}x{w}x{c} pairs={len(pairs)} bins={bins} range={rngs} channels={chans} std={with_std} thresholds={thr is not None}"
+    va, vb = [D(v) for v in vals], [Hh(v) for v in vals]
+    sa, sb = ([D(v) for v in stds], [Hh(v) for v in stds]) if with_std else (None, None)
+    ra = engine.pairs_histogram(va, sa, pairs, bins, rngs, chans, thresholds=thr)
+    rb = heng.pairs_histogram(vb, sb, pairs, bins, rngs, chans, thresholds=thr)
+    for i in range(n):                                                 # thresholds act on the values as read: the frames are untouched
+        compare(f"frame[{i}]", va[i], vals[i], None)
+    for q, (pa, pb) in enumerate(zip(ra, rb)):
+        for kind, (da, db) in enumerate(zip(pa, pb)):
+            assert da.keys() == db.keys()
+            for ch in db:
+                compare(f"pair{q}.kind{kind}.edges[{ch}]", da[ch][1], db[ch][1], None)
+                if not with_std:
+                    compare(f"pair{q}.kind{kind}.hist[{ch}]", da[ch][0], db[ch][0], None)
+                    continue
+                a_, b_ = as_np(da[ch][0]), as_np(db[ch][0])
+                if not (np.array_equal(np.isnan(a_), np.isnan(b_)) and np.array_equal(np.isinf(a_), np.isinf(b_))):
+                    raise Mismatch(f"pair{q}.kind{kind}.hist[{ch}]: NaN / inf patterns differ")
+                fin = np.isfinite(b_)
+                k_max = h * w                                          # k_b <= the pixels of the image
+                if np.any(np.abs(a_[fin] - b_[fin]) > 2 * (k_max + 2) * 2.0 ** -53 * np.abs(b_[fin])):
+                    i_ = int(np.argmax(np.abs(a_[fin] - b_[fin])))
+                    raise Mismatch(f"pair{q}.kind{kind}.hist[{ch}]: {a_[fin][i_]!r} vs {b_[fin][i_]!r} beyond 2 (k + 2) u sum|w|")
+    return desc
+
+
 CASES = [(case_merge, 5), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()
 counts = {fn.__name__: 0 for fn, _ in CASES}
