@@ -9,8 +9,10 @@
 // Arithmetic: the operation sequence of the device kernels, element by element (merge_one_element of hm_merge.hip, the operator
 // formulas of hm_ops.hip, ...), each citing the reference line it follows. Statistics use the reference's own two-pass form.
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
-// the TIFF strip decoders (host code already, in libhdrmerge.so) and the hm_debug_* probes.
+// the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
+// hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file.
 #include "hdrmerge.h"
+#include "../csrc/hm_tiff_lzw_body.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -1399,6 +1401,85 @@ int hm_de_generation_batch(int n_problems, double* population, double* energies,
                                         n_pixels, n_frames, lower, upper, pop_size, n_params, seeds[k], max_generations, mutation_lo,
                                         mutation_hi, recombination, tol, energy_limit, nullptr, nullptr);
         if (rc != HM_OK) return rc;
+    }
+    return HM_OK;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * hm_tiff_decode_strips on the host: the same argument checks, status words and frame as the device entry point of
+ * csrc/hm_tiff_device.hip, with HOST pointers - the decoder body both builds share (csrc/hm_tiff_lzw_body.h) with a serial emitter,
+ * one strip per OpenMP iteration. It exists so that the host build carries the whole ABI; tiff_io.imread does not go through it.
+ * ------------------------------------------------------------------------------------------ */
+struct TiffSerialEmit {
+    uint8_t* out;
+    void literal(int64_t op, uint8_t b) { out[op] = b; }
+    void copy(int64_t op, uint32_t from, uint32_t n, uint32_t period) {
+        for (uint32_t k = 0; k < n; ++k) out[op + k] = out[from + (k < period ? k : k - period)];
+    }
+};
+
+size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
+    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > (1ll << 31)) return 0;
+    return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
+}
+
+int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts, int n_strips,
+                          int compression, int predictor, int rows_per_strip, int height, int width, int samples, int bytes_per_sample,
+                          int color_mode, void* dst_, int64_t* strip_status, void* workspace, void* /*stream*/) {
+    static_assert(int(hm_lzw::kEinval) == int(HM_EINVAL) && int(hm_lzw::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_body.h repeats two codes of hdrmerge.h");
+    if (!file || !strip_offsets || !strip_counts || !dst_ || !strip_status || file_len < 0) return HM_EINVAL;
+    if (n_strips < 1 || rows_per_strip < 1 || height < 1 || width < 1) return HM_EINVAL;
+    if (predictor != 1 && predictor != 2) return HM_EINVAL;
+    if (color_mode != 0 && color_mode != 1) return HM_EINVAL;
+    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
+    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
+    if (bytes_per_sample != 1 && bytes_per_sample != 8) return HM_EUNSUPPORTED;
+    if (bytes_per_sample == 8 && (predictor == 2 || color_mode == 1)) return HM_EUNSUPPORTED;
+    const int rps = std::min(rows_per_strip, height);
+    if (n_strips != (height + rps - 1) / rps) return HM_ESHAPE;
+    const int64_t row_bytes = static_cast<int64_t>(width) * samples * bytes_per_sample;
+    if (row_bytes > (1ll << 31) / rps) return HM_ESHAPE;
+    if (compression == 5 && !workspace) return HM_EINVAL;
+    const int64_t strip_bytes = row_bytes * rps;
+    const int spp = samples, bps = bytes_per_sample, ospp = color_mode == 1 ? 3 : samples;
+    const int64_t out_row_bytes = static_cast<int64_t>(width) * ospp * bps;
+    uint8_t* dst = static_cast<uint8_t*>(dst_);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+#pragma omp parallel for schedule(dynamic)
+    for (int s = 0; s < n_strips; ++s) {
+        const int64_t o = strip_offsets[s], c = strip_counts[s];
+        const int rows = std::min(rps, height - s * rps);
+        const int64_t want = rows * row_bytes;
+        if (!(o >= 0 && c >= 0 && o <= file_len && c <= file_len - o)) { strip_status[s] = HM_EINVAL; continue; }
+        const uint8_t* in = file + o;
+        int64_t st = std::min(c, want);
+        if (compression == 5) {
+            std::vector<hm_lzw::Table> table(1);
+            TiffSerialEmit emit{ws + s * strip_bytes};
+            st = hm_lzw::decode(file + o, c, want, table[0], emit);
+            in = emit.out;
+        }
+        strip_status[s] = st;
+        if (st <= 0) continue;
+        for (int r = 0; r < rows; ++r) {
+            const int64_t avail = std::min(st, want) - r * row_bytes;
+            if (avail <= 0) break;
+            const int npx = avail >= row_bytes ? width : static_cast<int>(avail / (spp * bps));
+            const uint8_t* row_in = in + r * row_bytes;
+            uint8_t* out = dst + (static_cast<int64_t>(s) * rps + r) * out_row_bytes;
+            uint8_t run[4] = {0, 0, 0, 0};
+            for (int px = 0; px < npx; ++px)
+                for (int ch = 0; ch < ospp; ++ch) {
+                    const int sc = spp >= 3 ? (ch < 3 ? 2 - ch : ch) : 0;
+                    if (bps == 8) { memcpy(out + (static_cast<int64_t>(px) * ospp + ch) * 8, row_in + (static_cast<int64_t>(px) * spp + sc) * 8, 8); continue; }
+                    uint8_t v = row_in[static_cast<int64_t>(px) * spp + sc];
+                    if (predictor == 2) {
+                        if (spp == 1 && ch > 0) v = run[0];                      // grey replicated: the sum was advanced by channel 0
+                        else v = run[sc] = static_cast<uint8_t>(run[sc] + v);
+                    }
+                    out[static_cast<int64_t>(px) * ospp + ch] = v;
+                }
+        }
     }
     return HM_OK;
 }

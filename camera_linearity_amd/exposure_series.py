@@ -146,13 +146,14 @@ class ExposureSeries(object):
             out.append(cls(input_image_sets=sub))
         return out
 
-    def load_value_images(self, bit_64: Optional[bool] = False):
+    def load_value_images(self, bit_64: Optional[bool] = False, device_decode: Optional[bool] = False):
+        """`device_decode=True` (an addition): the TIFFs are decoded on the GPU, ImageSet.load_value_image."""
         for image_set in self.input_image_sets:
-            image_set.load_value_image(bit64=bit_64)
+            image_set.load_value_image(bit64=bit_64, device_decode=device_decode)
 
-    def load_std_images(self, bit_64: Optional[bool] = False):
+    def load_std_images(self, bit_64: Optional[bool] = False, device_decode: Optional[bool] = False):
         for image_set in self.input_image_sets:
-            image_set.load_std_image(bit64=bit_64)
+            image_set.load_std_image(bit64=bit_64, device_decode=device_decode)
 
     def linearize(self, ICRF, ICRF_diff=None, release_memory: Optional[bool] = False):
         """exposure_series.py:226-250."""

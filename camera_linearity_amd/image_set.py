@@ -9,6 +9,8 @@ IO: the reference reads/writes TIFF through OpenCV. Here `load_
 `load_std_image` / `save_64bit` / `save_8bit` go through `tiff_io` (cv.imread / cv.imwrite conventions
 without cv2: BGR arrays, RGB files, 8-bit and float64 samples) and also accept `.npy` arrays; images can
 always be supplied in memory (`value=`, `std=`, `measurand=`). 8-bit images are kept as uint8 DNs in HBM.
+`load_value_image(device_decode=True)` / `load_std_image(device_decode=True)` (device backend only, opt-in) decode the TIFF on the GPU
+(`tiff_io.imread_device`): the frame reaches the measurand without a host array in between.
 
 Deviations: G - bad_pixel_filter / flat_field_correction return the new ImageSet as
 the reference does, and the merge loop uses the result; I - scale_to_exposure scales by
@@ -34,6 +36,14 @@ def _read_image(path: Path, unchanged: bool = False) -> Optional[np.ndarray]:
     if path.suffix == ".npy":
         return np.load(path, allow_pickle=False) if path.exists() else None
     return tiff_io.imread(path, tiff_io.IMREAD_UNCHANGED if unchanged else tiff_io.IMREAD_COLOR)     # cv.imread's contract
+
+
+def _read_image_device(path: Path, unchanged: bool, device) -> Optional[torch.Tensor]:
+    """_read_image with the TIFF decoded on the GPU (tiff_io.imread_device): a device tensor, None for a missing file."""
+    path = Path(path)
+    if path.suffix == ".npy":
+        raise NotImplementedError("device_decode reads TIFF files; .npy arrays load through the default path (device_decode=False)")
+    return tiff_io.imread_device(path, tiff_io.IMREAD_UNCHANGED if unchanged else tiff_io.IMREAD_COLOR, device=device)
 
 
 def _std_path(path: Path) -> Path:
@@ -183,22 +193,43 @@ class ImageSet(object):
     def extract(self, channels=None):
         return ImageSet(file_path=self.path, features=self.features, measurand=self.measurand.extract(dims=channels, axis=-1))
 
-    def load_value_image(self, bit64: Optional[bool] = False):
-        """image_set.py:214-226. 8-bit images stay uint8 DNs on the device; `.measurand.val` is DN/255."""
+    def _require_device_decode(self):
+        if not self._use_cupy:
+            raise ValueError("device_decode=True needs the device backend (ImageSet(use_cupy=True)); a host-backend ImageSet reads "
+                             "its files with tiff_io.imread")
+        return HipMeasurand._device()
+
+    def load_value_image(self, bit64: Optional[bool] = False, device_decode: Optional[bool] = False):
+        """image_set.py:214-226. 8-bit images stay uint8 DNs on the device; `.measurand.val` is DN/255.
+        `device_decode=True` (an addition, device backend only) decodes the TIFF on the GPU: the frame goes from
+        tiff_io.imread_device straight into the measurand, with no host array in between. The default reads through tiff_io.imread."""
+        std = self.measurand._std
+        cls = self._measurand_class()
+        if device_decode:
+            img = _read_image_device(self.path, bool(bit64), self._require_device_decode())
+            if img is None:
+                raise FileNotFoundError(str(self.path))
+            if img.dtype == torch.uint8 and not bit64:
+                self._measurand = cls.from_dn(img, std)
+            else:
+                self._measurand = cls(img.to(torch.float64), std)
+            return
         img = _read_image(self.path, unchanged=bool(bit64))
         if img is None:
             raise FileNotFoundError(str(self.path))
-        std = self.measurand._std
-        cls = self._measurand_class()
         if img.dtype == np.uint8 and not bit64:
             self._measurand = cls.from_dn(img, std)
         else:
             self._measurand = cls(img.astype(np.float64), std)
 
-    def load_std_image(self, STD_data=None, bit64: Optional[bool] = False):
-        """image_set.py:228-243: '<name> STD.tif' as float64, else the per-DN table fallback."""
+    def load_std_image(self, STD_data=None, bit64: Optional[bool] = False, device_decode: Optional[bool] = False):
+        """image_set.py:228-243: '<name> STD.tif' as float64, else the per-DN table fallback. `device_decode`: as load_value_image."""
         std_array = None
-        if self.path is not None:
+        if device_decode:
+            device = self._require_device_decode()
+            if self.path is not None:
+                std_array = _read_image_device(_std_path(self.path), True, device)
+        elif self.path is not None:
             std_array = _read_image(_std_path(self.path), unchanged=True)
         if std_array is None:
             std_array = self.calculate_numerical_STD(STD_data)

@@ -21,17 +21,25 @@ Pillow/libtiff (tests/test_tiff_io.py) for the integer formats; the float64 thre
 BitsPerSample 64,64,64, RGB order in the file) follows the TIFF 6.0 specification and is parity-unpinned against cv2.
 
 The byte-serial LZW / PackBits loops run in libhdrmerge.so's host code (hm_tiff_lzw_decode); strips are decoded
-on a thread pool.
+on a thread pool. That is `imread`, the default path, and it reads the whole family above.
+
+`imread_device` is the opt-in device path for the files of the documented workflow (8-bit frames, float64 companions):
+the file's bytes are uploaded as they are and hm_tiff_decode_strips (csrc/hm_tiff_device.hip) decodes the LZW strips, undoes
+Predictor 2, swaps R and B and applies the imread flag on the GPU, so the frame is born in device memory. It reads
+little-endian samples of uint8 (1 / 3 / 4 samples, Predictor 1 / 2) and float64 (1 / 3 samples), Compression 1 and 5,
+strips, chunky; everything else it refuses with NotImplementedError - there is no fallback, `imread` is the host path.
+A `DeviceTiffReader` owns the staging and device buffers and is reused across the files of a series.
 """
 from __future__ import annotations
 
 import ctypes as C
+import mmap
 import os
 import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Optional
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -108,7 +116,29 @@ def read_tiff(path) -> np.ndarray:
         raise TiffError(f"malformed TIFF file {path}: {e}") from e
 
 
-def _read_tiff(buf: memoryview) -> np.ndarray:
+class TiffLayout(NamedTuple):
+    """What the first IFD says about the pixels: everything a decoder needs, nothing decoded yet."""
+    dtype: np.dtype            # of a sample, in the FILE's byte order
+    shape: Tuple[int, int, int]   # (H, W, samples per pixel)
+    rows_per_strip: int        # clamped to 1..H
+    offsets: Sequence[int]     # StripOffsets, at least n_strips of them
+    counts: Sequence[int]      # StripByteCounts (derived for uncompressed files that lack them)
+    compression: int
+    predictor: int
+    photometric: int
+
+    @property
+    def n_strips(self) -> int:
+        return (self.shape[0] + self.rows_per_strip - 1) // self.rows_per_strip
+
+    @property
+    def row_bytes(self) -> int:
+        return self.shape[1] * self.shape[2] * self.dtype.itemsize
+
+
+def _parse_layout(buf: memoryview) -> TiffLayout:
+    """Header and first IFD of a TIFF file -> TiffLayout. Raises what _read_tiff raises for a file it cannot lay out
+    (TiffError, NotImplementedError for tiles / mixed depths / planar samples / unknown sample formats)."""
     if len(buf) < 8:
         raise TiffError("not a TIFF file (too short)")
     bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
@@ -157,6 +187,13 @@ def _read_tiff(buf: memoryview) -> np.ndarray:
         if comp != 1:
             raise TiffError("compressed TIFF without StripByteCounts")
         counts = [row_bytes * min(rps, H - s * rps) for s in range(n_strips)]
+    return TiffLayout(dtype, (H, W, spp), rps, offsets, counts, comp, predictor, int(t.get(262, (1,))[0]))
+
+
+def _read_tiff(buf: memoryview) -> np.ndarray:
+    lay = _parse_layout(buf)
+    dtype, (H, W, spp), rps, offsets, counts, comp, predictor, photometric = lay
+    n_strips, row_bytes = lay.n_strips, lay.row_bytes
     out = np.empty((H, W * spp), dtype=dtype)
     out_bytes = out.view(np.uint8).reshape(H, row_bytes)
 
@@ -186,7 +223,6 @@ def _read_tiff(buf: memoryview) -> np.ndarray:
     elif predictor != 1:
         raise NotImplementedError(f"TIFF predictor {predictor}")
     img = np.ascontiguousarray(img.astype(dtype.newbyteorder("="), copy=False))
-    photometric = int(t.get(262, (1,))[0])
     if photometric == 0 and spp == 1 and dtype.kind == "u":               # WhiteIsZero
         img = np.iinfo(img.dtype).max - img
     return img[:, :, 0] if spp == 1 else img
@@ -299,3 +335,152 @@ def imwrite(path, img) -> bool:
         f.write(bytes(ifd))
         f.write(bytes(extra))
     return True
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The device path (opt-in): hm_tiff_decode_strips
+# ---------------------------------------------------------------------------------------------------------------------
+_HOST_PATH = "tiff_io.imread is the host path for such files"
+
+
+def _device_layout_check(lay: TiffLayout, flags: int) -> None:
+    """NotImplementedError for every kind of file the device decoder does not read (it never falls back)."""
+    spp = lay.shape[2]
+    if lay.compression in (8, 32946):
+        raise NotImplementedError(f"imread_device: Deflate-compressed strips are not decoded on the device; {_HOST_PATH}")
+    if lay.compression == 32773:
+        raise NotImplementedError(f"imread_device: PackBits-compressed strips are not decoded on the device; {_HOST_PATH}")
+    if lay.compression not in (1, 5):
+        raise NotImplementedError(f"imread_device: TIFF compression {lay.compression} is not supported; {_HOST_PATH}")
+    kind = lay.dtype.kind + str(lay.dtype.itemsize)
+    if kind not in ("u1", "f8"):
+        raise NotImplementedError(f"imread_device: {lay.dtype.name} samples are not decoded on the device (uint8 and float64 are); "
+                                  f"{_HOST_PATH}")
+    if lay.dtype.itemsize > 1 and lay.dtype.byteorder == ">":
+        raise NotImplementedError(f"imread_device: big-endian multi-byte samples are not decoded on the device; {_HOST_PATH}")
+    if spp not in ((1, 3, 4) if kind == "u1" else (1, 3)):
+        raise NotImplementedError(f"imread_device: {spp} {lay.dtype.name} samples per pixel are not decoded on the device; {_HOST_PATH}")
+    if lay.predictor not in (1, 2):
+        raise NotImplementedError(f"TIFF predictor {lay.predictor}")
+    if lay.predictor == 2 and kind != "u1":
+        raise NotImplementedError(f"imread_device: the horizontal predictor on floating-point samples is not supported; {_HOST_PATH}")
+    if lay.photometric == 0 and spp == 1 and kind == "u1":
+        raise NotImplementedError(f"imread_device: WhiteIsZero images are not inverted on the device; {_HOST_PATH}")
+    if kind == "f8" and flags != IMREAD_UNCHANGED:
+        raise NotImplementedError(f"imread_device: float64 samples are read with IMREAD_UNCHANGED only (no 8-bit conversion on the "
+                                  f"device); {_HOST_PATH}")
+
+
+class DeviceTiffReader:
+    """The buffers of the device path, kept and grown across the files of a series: a pinned host staging buffer that holds a file's
+    bytes followed by its strip tables (so ONE upload carries both), its device twin, the per-strip status and the decoder's workspace.
+    Per file: one read into pinned memory, one upload, one hm_tiff_decode_strips, one status read-back (the only synchronisation).
+    Not thread-safe: one reader per thread."""
+
+    def __init__(self, device=None):
+        self._device_arg = device
+        self.device = None                 # resolved by the first file that passes the layout checks (those need no GPU)
+        self._pinned = self._dev = self._status = self._ws = None
+
+    def _resolve_device(self):
+        import torch
+        if self.device is None:
+            dev = torch.device("cuda") if self._device_arg is None else torch.device(self._device_arg)
+            if dev.type != "cuda":
+                raise ValueError(f"DeviceTiffReader needs a GPU device, got {dev}")
+            self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        return self.device
+
+    def _grow(self, name: str, n: int, **kw):
+        import torch
+        t = getattr(self, name)
+        if t is None or t.numel() < n:
+            t = torch.empty(max(n, 1) + max(n, 1) // 4, **kw)          # head room: the files of a series differ a little in size
+            setattr(self, name, t)
+        return t
+
+    def read(self, path, flags: int = IMREAD_COLOR):
+        """The frame `imread(path, flags)` returns, as a tensor on the reader's device; None when the file does not exist."""
+        path = Path(path)
+        if not path.exists():
+            return None
+        if flags not in (IMREAD_COLOR, IMREAD_UNCHANGED):
+            raise ValueError(f"imread_device: flags must be IMREAD_COLOR or IMREAD_UNCHANGED, got {flags}")
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            if size < 8:
+                raise TiffError("not a TIFF file (too short)")
+            # the layout first, from a mapping (only the pages of the header and the IFD are touched): what the device does not read
+            # is refused before a byte is staged, and the staging buffer can be sized for the file AND its strip tables
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                view = memoryview(mm)
+                try:
+                    lay = _parse_layout(view)
+                except (struct.error, IndexError, OverflowError, MemoryError) as e:
+                    raise TiffError(f"malformed TIFF file {path}: {e}") from e
+                except NotImplementedError as e:
+                    raise NotImplementedError(f"imread_device: {e}; tiff_io.imread, the host path, refuses this layout too") from e
+                finally:
+                    view.release()
+            _device_layout_check(lay, flags)
+            H, W, spp = lay.shape
+            n = lay.n_strips
+            if len(lay.counts) < n:
+                raise TiffError("StripByteCounts shorter than the number of strips")
+            import torch
+            nat = _native()
+            device = self._resolve_device()
+            cap = (size + 7) // 8 * 8                   # the tables sit 8-byte aligned behind the file's bytes: ONE upload carries both
+            host = self._grow("_pinned", cap + 16 * n, dtype=torch.uint8, pin_memory=True).numpy()
+            if f.readinto(memoryview(host)[:size]) != size:
+                raise TiffError(f"short read of {path}")
+        tables = host[cap:cap + 16 * n].view(np.int64)
+        try:
+            tables[:n] = lay.offsets[:n]
+            tables[n:] = lay.counts[:n]
+        except OverflowError as e:
+            raise TiffError(f"malformed TIFF file {path}: {e}") from e
+        used = cap + 16 * n
+        dev = self._grow("_dev", used, dtype=torch.uint8, device=device)
+        status = self._grow("_status", n, dtype=torch.int64, device=device)
+        bps = lay.dtype.itemsize
+        strip_bytes = lay.rows_per_strip * lay.row_bytes
+        ws_bytes = int(nat.hip_lib.hm_tiff_decode_workspace_bytes(n, strip_bytes, lay.compression))
+        ws = self._grow("_ws", ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
+        color = flags == IMREAD_COLOR
+        out_spp = 3 if color else spp
+        out_shape = (H, W) if out_spp == 1 else (H, W, out_spp)
+        with torch.cuda.device(device):
+            dev[:used].copy_(self._pinned[:used], non_blocking=True)
+            dst = torch.empty(out_shape, dtype=torch.uint8 if bps == 1 else torch.float64, device=device)
+            base = dev.data_ptr()
+            nat.check(nat.hip_lib.hm_tiff_decode_strips(base, size, base + cap, base + cap + 8 * n, n, lay.compression, lay.predictor,
+                                                        lay.rows_per_strip, H, W, spp, bps, 1 if color else 0, dst.data_ptr(),
+                                                        status.data_ptr(), nat.ptr(ws), nat.current_stream_ptr(device)),
+                      "hm_tiff_decode_strips")
+            st = status[:n].cpu().numpy()              # waits for the upload and the kernels: the pinned buffer is free again after it
+        want = np.minimum(lay.rows_per_strip, H - np.arange(n, dtype=np.int64) * lay.rows_per_strip) * lay.row_bytes
+        bad = np.flatnonzero(st < want)
+        if bad.size:
+            s = int(bad[0])
+            if st[s] < 0:
+                what = "lies beyond the end of the file or holds a corrupt stream" if st[s] == nat.HM_EINVAL else \
+                    "decodes to more bytes than its rows hold"
+                raise TiffError(f"strip {s} {what} ({nat.strerror(int(st[s]))})")
+            raise TiffError(f"strip {s} decodes to {int(st[s])} bytes, expected {int(want[s])}")
+        return dst
+
+
+_readers = {}
+
+
+def imread_device(path, flags: int = IMREAD_COLOR, device=None, reader: Optional[DeviceTiffReader] = None):
+    """`imread` with the decode on the GPU: the same array (values, dtype, shape, BGR order) as a torch tensor in device memory, None
+    when the file does not exist. Opt-in; files outside the device decoder's family raise NotImplementedError (no fallback: call
+    `imread`), damaged strips raise TiffError naming the strip. `reader` (a DeviceTiffReader) carries the buffers from file to file;
+    without one, a reader per device is kept by the module."""
+    if reader is None:
+        reader = _readers.get(str(device))
+        if reader is None:
+            reader = _readers[str(device)] = DeviceTiffReader(device)
+    return reader.read(path, flags)

@@ -25,7 +25,8 @@
  * Two libraries export this ABI. libhdrmerge.so (the .hip files under csrc/) is the MI355X build described above. libhdrmerge_host.so
  * (csrc_host/hm_host.cpp, plain C++) is the HOST build behind Measurand(use_cupy=False) - the slot of the reference's NumpyMeasurand
  * (modules/measurand_factory.py:10-14): every pointer is then a HOST pointer, `stream` is ignored, calls are synchronous and workspaces
- * may be NULL; the hm_tiff_* decoders are not exported (they are host code of libhdrmerge.so already).
+ * may be NULL; the hm_tiff_* decoders are not exported (the two strip decoders are host code of libhdrmerge.so already;
+ * hm_tiff_decode_strips, the device path of the same files, is in both builds).
  * The device build never calls or falls back to the host build.
  */
 #ifndef HDRMERGE_H
@@ -572,6 +573,40 @@ int hm_de_generation_batch(int n_problems, double* population, double* energies,
  * ------------------------------------------------------------------------------------------ */
 int64_t hm_tiff_lzw_decode(const uint8_t* src, int64_t src_len, uint8_t* dst, int64_t dst_cap);
 int64_t hm_tiff_packbits_decode(const uint8_t* src, int64_t src_len, uint8_t* dst, int64_t dst_cap);
+
+/* ------------------------------------------------------------------------------------------
+ * The same strips decoded ON THE DEVICE (csrc/hm_tiff_device.hip; the host build carries the same entry point with host pointers and
+ * a serial loop, so that it exports the whole ABI - tiff_io.imread does not use it): the file's bytes go
+ * up as they are, and one call turns them into the frame cv.imread returns - LZW decode (one strip per wave, string table in LDS),
+ * Predictor 2 undone, R and B swapped at sample granularity, cv.imread's flag applied. Opt-in (tiff_io.imread_device); the host
+ * decoders above stay the default path.
+ *   file, file_len      the whole file in device memory
+ *   strip_offsets / strip_counts   (n_strips) int64 in device memory: StripOffsets / StripByteCounts. n_strips must be
+ *                       ceil(height / min(rows_per_strip, height)). Strip s holds min(rows_per_strip, height - s * rows_per_strip) rows of
+ *                       width * samples * bytes_per_sample bytes: its expected size. Strips, chunky layout, little-endian samples.
+ *   compression         1 (none: strips are read straight from `file`) or 5 (LZW, the stream rules of hm_tiff_lzw_decode)
+ *   predictor           1, or 2 (horizontal differencing) with 1-byte samples
+ *   samples             1, 3 or 4 per pixel; bytes_per_sample 1 (uint8) or 8 (float64)
+ *   color_mode          0 = cv.IMREAD_UNCHANGED: dst is (height, width, samples) in B,G,R(,A) order (samples == 1: (height, width));
+ *                       1 = cv.IMREAD_COLOR, 1-byte samples only: dst is (height, width, 3) B,G,R - grey replicated, alpha dropped
+ *   strip_status        (n_strips) int64 in device memory, written by the call: the number of bytes strip s produced (compression 1:
+ *                       min(count, expected size)), or the negative code hm_tiff_lzw_decode returns for that stream - HM_EINVAL for a
+ *                       corrupt one, HM_ESHAPE for one that runs past the expected size - and HM_EINVAL for a strip whose
+ *                       [offset, offset + count) does not lie inside [0, file_len): nothing of such a strip is read. A strip with a
+ *                       negative status leaves its rows of dst untouched and does not disturb the others; one that produced fewer
+ *                       bytes than expected fills the whole pixels it holds.
+ *   workspace           hm_tiff_decode_workspace_bytes(n_strips, strip_bytes, compression) bytes of device memory, with strip_bytes =
+ *                       min(rows_per_strip, height) * width * samples * bytes_per_sample; 0 (NULL is fine) for compression 1
+ * Returns, before any HIP call: HM_EINVAL for a NULL file / strip_offsets / strip_counts / dst / strip_status (or workspace with
+ * compression 5), file_len < 0, n_strips / rows_per_strip / height / width < 1, a predictor other than 1 or 2 and a color_mode other
+ * than 0 or 1; HM_EUNSUPPORTED for a compression other than 1 or 5, samples other than 1, 3 or 4, bytes_per_sample other than 1 or 8,
+ * and 8-byte samples with predictor 2 or color_mode 1; HM_ESHAPE for an n_strips that does not match the geometry and for strips of
+ * more than 2^31 bytes. The return value speaks of the call; the strips speak through strip_status, valid once `stream` has run.
+ * ------------------------------------------------------------------------------------------ */
+size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression);
+int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts, int n_strips,
+                          int compression, int predictor, int rows_per_strip, int height, int width, int samples, int bytes_per_sample,
+                          int color_mode, void* dst, int64_t* strip_status, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
