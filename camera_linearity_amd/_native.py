@@ -142,6 +142,10 @@ _SIGNATURES = {
     "hm_tiff_decode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_tiff_decode_strips": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 8
                               + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hm_tiff_encode_bound": (C.c_int64, [C.c_int64]),
+    "hm_tiff_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "hm_tiff_encode_payload_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "hm_tiff_encode_strips": (C.c_int, [C.c_void_p, C.c_int, C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "hm_linearity_energy_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hm_linearity_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

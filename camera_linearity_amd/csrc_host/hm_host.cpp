@@ -10,9 +10,11 @@
 // formulas of hm_ops.hip, ...), each citing the reference line it follows. Statistics use the reference's own two-pass form.
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
-// hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file.
+// hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twin of
+// hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
 #include "hdrmerge.h"
 #include "../csrc/hm_tiff_lzw_body.h"
+#include "../csrc/hm_tiff_lzw_enc_body.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -1480,6 +1482,111 @@ int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* 
                     out[static_cast<int64_t>(px) * ospp + ch] = v;
                 }
         }
+    }
+    return HM_OK;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * hm_tiff_encode_strips on the host: the same argument checks, payload layout and bytes as the device entry point of
+ * csrc/hm_tiff_encode.hip, with HOST pointers - the encoder body both builds share (csrc/hm_tiff_lzw_enc_body.h) with its serial ops,
+ * one strip per OpenMP iteration. tiff_io.imwrite(compression=5) writes through it, and the GPU tests compare the device call with it.
+ * ------------------------------------------------------------------------------------------ */
+static inline int64_t tiff_round16(int64_t x) { return (x + 15) & ~int64_t{15}; }
+
+int64_t hm_tiff_encode_bound(int64_t strip_bytes) {
+    if (strip_bytes < 1) return HM_EINVAL;
+    if (strip_bytes > hm_lzw_enc::kMaxInput) return HM_ESHAPE;
+    return hm_lzw_enc::bound(strip_bytes);
+}
+
+size_t hm_tiff_encode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
+    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > hm_lzw_enc::kMaxInput) return 0;
+    return static_cast<size_t>(n_strips) * static_cast<size_t>(tiff_round16(strip_bytes) + tiff_round16(hm_lzw_enc::bound(strip_bytes)));
+}
+
+size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes, int compression) {
+    if ((compression != 1 && compression != 5) || n_strips < 1 || strip_bytes < 1 || strip_bytes > hm_lzw_enc::kMaxInput) return 0;
+    if (compression == 1) return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
+    return static_cast<size_t>(n_strips) * static_cast<size_t>(tiff_round16(hm_lzw_enc::bound(strip_bytes)));
+}
+
+int hm_tiff_encode_strips(const void* src_, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
+                          int compression, int predictor, void* payload_, int64_t payload_cap, void* strip_offsets, void* strip_counts,
+                          void* workspace, void* /*stream*/) {
+    static_assert(int(hm_lzw_enc::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_enc_body.h repeats a code of hdrmerge.h");
+    if (!src_ || !payload_ || !strip_offsets || !strip_counts) return HM_EINVAL;
+    if (height < 1 || width < 1 || rows_per_strip < 1) return HM_EINVAL;
+    if (predictor != 1 && predictor != 2) return HM_EINVAL;
+    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
+    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
+    if (src_kind < 0 || src_kind > 2) return HM_EUNSUPPORTED;
+    if (src_kind == 2 && !(divisor > 0.0 && divisor <= std::numeric_limits<double>::max())) return HM_EINVAL;
+    const int bps = src_kind == 1 ? 8 : 1;
+    if (bps == 8 && predictor == 2) return HM_EUNSUPPORTED;
+    const int rps = std::min(rows_per_strip, height);
+    const int n_strips = (height + rps - 1) / rps;
+    const int64_t row_bytes = static_cast<int64_t>(width) * samples * bps;
+    if (row_bytes > hm_lzw_enc::kMaxInput / rps) return HM_ESHAPE;
+    const int64_t strip_bytes = row_bytes * rps;
+    if (compression == 5 && !workspace) return HM_EINVAL;
+    if (payload_cap < 0 || static_cast<uint64_t>(payload_cap) < hm_tiff_encode_payload_bytes(n_strips, strip_bytes, compression)) return HM_ESHAPE;
+    auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    if (!al(payload_, 16) || !al(strip_offsets, 8) || !al(strip_counts, 8) || !al(src_, src_kind == 0 ? 1 : 8) || (compression == 5 && !al(workspace, 16)))
+        return HM_EALIGN;
+    const uint8_t* src = static_cast<const uint8_t*>(src_);
+    uint8_t* payload = static_cast<uint8_t*>(payload_);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    int64_t* offsets = static_cast<int64_t*>(strip_offsets);
+    int64_t* counts = static_cast<int64_t*>(strip_counts);
+    const int spp = samples;
+    const int64_t bound = hm_lzw_enc::bound(strip_bytes), in_pitch = tiff_round16(strip_bytes), out_pitch = tiff_round16(bound);
+#pragma omp parallel for schedule(dynamic)
+    for (int s = 0; s < n_strips; ++s) {
+        const int rows = std::min(rps, height - s * rps);
+        const int64_t len = rows * row_bytes;
+        uint8_t* packed = compression == 1 ? payload + s * strip_bytes : ws + s * in_pitch;
+        for (int r = 0; r < rows; ++r) {
+            const int64_t in_row = (static_cast<int64_t>(s) * rps + r) * width * spp;          // in samples
+            uint8_t* out = packed + r * row_bytes;
+            for (int px = 0; px < width; ++px)
+                for (int ch = 0; ch < spp; ++ch) {
+                    const int64_t at = in_row + static_cast<int64_t>(px) * spp + (spp >= 3 ? (ch < 3 ? 2 - ch : ch) : 0);
+                    if (src_kind == 1) { memcpy(out + (static_cast<int64_t>(px) * spp + ch) * 8, src + at * 8, 8); continue; }
+                    auto sample = [&](int64_t k) {
+                        if (src_kind == 0) return src[k];
+                        double v;
+                        memcpy(&v, src + k * 8, 8);
+                        return hm_lzw_enc::quantize_u8(v, divisor);
+                    };
+                    const uint8_t v = sample(at), left = predictor == 2 && px > 0 ? sample(at - spp) : uint8_t{0};
+                    out[static_cast<int64_t>(px) * spp + ch] = static_cast<uint8_t>(v - left);
+                }
+        }
+        if (compression == 1) {
+            offsets[s] = s * strip_bytes;
+            counts[s] = len;
+        } else {
+            std::vector<hm_lzw_enc::Dict> dict(1);
+            hm_lzw_enc::SerialOps ops;
+            counts[s] = hm_lzw_enc::encode(packed, len, ws + n_strips * in_pitch + s * out_pitch, bound, dict[0], ops);
+        }
+    }
+    if (compression == 1) {
+        offsets[n_strips] = static_cast<int64_t>(height) * row_bytes;
+        return HM_OK;
+    }
+    int64_t total = 0;
+    for (int s = 0; s < n_strips; ++s) {
+        offsets[s] = total;
+        total += counts[s] > 0 ? tiff_round16(counts[s]) : 0;
+    }
+    offsets[n_strips] = total;
+#pragma omp parallel for schedule(dynamic)
+    for (int s = 0; s < n_strips; ++s) {
+        if (counts[s] <= 0) continue;
+        uint8_t* out = payload + offsets[s];
+        memcpy(out, ws + n_strips * in_pitch + s * out_pitch, static_cast<size_t>(counts[s]));
+        memset(out + counts[s], 0, static_cast<size_t>(tiff_round16(counts[s]) - counts[s]));       // the gap: zeros, never stale memory
     }
     return HM_OK;
 }

@@ -875,6 +875,20 @@ def pairs_statistics(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch
     return res
 
 
+def channel_minmax(val: torch.Tensor) -> np.ndarray:
+    """(C, 2) host array: min and max of the finite values of each channel of a (..., C) float64 tensor (hm_channel_minmax; a channel
+    without finite values gives (+inf, -inf)). One read-back of 2C doubles."""
+    _require_cuda(val, "val")
+    val = val.contiguous()
+    Cc = val.shape[-1]
+    ws = torch.empty(max(1, nat.lib.hm_histogram_workspace_bytes(1, Cc) // 8), dtype=_F64, device=val.device)
+    mm = torch.empty(2 * Cc, dtype=_F64, device=val.device)
+    with _on(val.device):
+        nat.check(nat.lib.hm_channel_minmax(val.data_ptr(), None, val.numel(), Cc, mm.data_ptr(), ws.data_ptr(), _stream(val.device)),
+                  "hm_channel_minmax")
+        return mm.cpu().numpy().reshape(Cc, 2)
+
+
 def channel_histogram(val: torch.Tensor, std: Optional[torch.Tensor], bins: int, included_range, channels: Sequence[int]):
     """modules/measurand.py:430-469 -> {c: (hist ndarray, bin_edges ndarray)} like np.histogram. A range of None is
     evaluated per channel from the counted values (np.histogram's default), with one extra reduction."""

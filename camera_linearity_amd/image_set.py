@@ -267,14 +267,53 @@ class ImageSet(object):
         new_measurand = self.measurand.normalize_by_map(flatSet.measurand)
         return ImageSet(file_path=self.path, features=self.features, measurand=new_measurand)
 
+    def _require_device_encode(self):
+        if not self._use_cupy:
+            raise ValueError("device_encode=True needs the device backend (ImageSet(use_cupy=True)); a host-backend ImageSet writes "
+                             "its files with tiff_io.imwrite")
+
+    @staticmethod
+    def _write_8bit_device(path, t: torch.Tensor, dn: Optional[torch.Tensor], compression: int):
+        """One uint8 file of save_8bit from device memory. `dn`: the uint8 DNs of a frame whose value image is DN / 255 (a from_dn
+        measurand), written as they are because around(dn / 255 * 255) is dn; None for every other image - a uint8 value image that is
+        not such a frame included, whose values ARE its DNs and are scaled like any other - which is scaled by its finite maximum if
+        that exceeds 1 and quantised by the encoder's pack kernel."""
+        if dn is not None:
+            tiff_io.imwrite_device(path, dn.contiguous(), compression=compression)
+            return
+        t = t.to(torch.float64).contiguous()
+        C = t.shape[-1] if t.dim() == 3 else 1
+        from . import engine
+        max_float = float(engine.channel_minmax(t.reshape(-1, C))[:, 1].max())      # one read-back of 2C doubles
+        tiff_io.imwrite_device(path, t, compression=compression, quantize_divisor=max_float if max_float > 1 else 1.0)
+
     def save_64bit(self, save_path: Optional[Path] = None, is_HDR: Optional[bool] = False,
-                   separate_channels: Optional[bool] = False):
+                   separate_channels: Optional[bool] = False, device_encode: Optional[bool] = False):
         """image_set.py:264-318: float64 TIFFs '<name>[ HDR].tif' and '<name>[ HDR] STD.tif' (or one file per channel,
-        '<name>[ HDR] <channel name>.tif')."""
+        '<name>[ HDR] <channel name>.tif').
+        `device_encode=True` (an addition, device backend only) writes the same files from the device tensors through
+        tiff_io.imwrite_device: the float64 images never become host arrays. The files are byte-identical to the default's."""
+        if device_encode:
+            self._require_device_encode()
         file_path = self.path.parent.joinpath("64bit", self.path.name) if save_path is None else Path(save_path)
         file_path.parent.mkdir(parents=True, exist_ok=True)
         base = str(file_path).removesuffix(".tif")
         acq_suffix, std_suffix = (" HDR.tif", " HDR STD.tif") if is_HDR else (".tif", " STD.tif")
+        if device_encode:
+            def f64(t):
+                return t.to(torch.float64).contiguous()
+            if not separate_channels:
+                tiff_io.imwrite_device(base + acq_suffix, f64(self.measurand.val))
+                if self.measurand.std is not None:
+                    tiff_io.imwrite_device(base + std_suffix, f64(self.measurand.std))
+            else:
+                for c in range(self.measurand.shape[-1]):
+                    name = gs.CH_STR.get(c, str(c))
+                    one = self.extract([c]).measurand
+                    tiff_io.imwrite_device(base + acq_suffix.replace(".tif", f" {name}.tif"), f64(one.val))
+                    if one.std is not None:
+                        tiff_io.imwrite_device(base + std_suffix.replace(".tif", f" {name}.tif"), f64(one.std))
+            return
         val, std = self.host_arrays()
         if not separate_channels:
             tiff_io.imwrite(base + acq_suffix, val.astype(np.float64))
@@ -287,17 +326,36 @@ class ImageSet(object):
                 if std is not None:
                     tiff_io.imwrite(base + std_suffix.replace(".tif", f" {name}.tif"), std[:, :, c])
 
-    def save_8bit(self, save_path: Optional[Path] = None, force_8_bit: Optional[bool] = False):
+    def save_8bit(self, save_path: Optional[Path] = None, force_8_bit: Optional[bool] = False,
+                  device_encode: Optional[bool] = False, compression: int = 1):
         """image_set.py:320-363: value image scaled to its maximum if that exceeds 1, rounded to uint8; the std image is
-        written as float64 unless force_8_bit."""
+        written as float64 unless force_8_bit.
+        `compression=5` (an addition) writes the uint8 files with LZW strips, as cv.imwrite does; a float64 std file stays
+        uncompressed (LZW enlarges float64 noise). `device_encode=True` (an addition, device backend only) takes the maximum on the
+        device and quantises, swaps, compresses and compacts there (tiff_io.imwrite_device): the float64 image never reaches the host.
+        For images whose samples are all finite and whose scaled values lie in [0, 255] the files decode to exactly the arrays the
+        default's files decode to. Outside that, the device path is defined - non-finite samples are ignored by the maximum and stored
+        as 0, scaled values outside [0, 255] wrap modulo 256 - where the default depends on NumPy's float-to-uint8 cast."""
+        if device_encode:
+            self._require_device_encode()
         file_path = self.path.parent.joinpath("8bit", self.path.name) if save_path is None else Path(save_path)
         file_path.parent.mkdir(parents=True, exist_ok=True)
+        std_path = str(file_path).removesuffix(".tif") + " STD.tif"
+        if device_encode:
+            m = self.measurand
+            self._write_8bit_device(file_path, m.val, m._dn, compression)      # _dn: set by from_dn only, where val is DN / 255
+            if m.std is not None:
+                if force_8_bit:
+                    self._write_8bit_device(std_path, m.std, None, compression)
+                else:
+                    tiff_io.imwrite_device(std_path, m.std.to(torch.float64).contiguous())
+            return
         val, std = self.host_arrays()
         val = val.astype(np.float64, copy=True)
         max_float = np.amax(val)
         if max_float > 1:
             val /= max_float
-        tiff_io.imwrite(file_path, np.around(val * gs.MAX_DN).astype(np.uint8))
+        tiff_io.imwrite(file_path, np.around(val * gs.MAX_DN).astype(np.uint8), compression=compression)
         if std is not None:
             std = std.astype(np.float64, copy=True)
             if force_8_bit:
@@ -305,7 +363,7 @@ class ImageSet(object):
                 if max_float > 1:
                     std /= max_float
                 std = np.around(std * gs.MAX_DN).astype(np.uint8)
-            tiff_io.imwrite(str(file_path).removesuffix(".tif") + " STD.tif", std)
+            tiff_io.imwrite(std_path, std, compression=compression if force_8_bit else 1)
 
     def save_npy(self, save_path: Path, is_HDR: bool = False):
         """Host-side dump of val (and std) as .npy next to each other ('<name> HDR.npy', '<name> HDR STD.npy' -

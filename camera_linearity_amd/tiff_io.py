@@ -9,7 +9,8 @@ that family of files:
          1/3/4 samples of uint8 / uint16 / float32 / float64, Compression none (1), LZW (5, with libtiff's early
          change), Deflate (8 / 32946), PackBits (32773), Predictor 1 / 2 (horizontal differencing)
   write  classic TIFF (BigTIFF when the file would pass 4 GiB), one strip per ~8 KiB of rows like OpenCV,
-         uncompressed, uint8 / uint16 / float32 / float64
+         uint8 / uint16 / float32 / float64 uncompressed (the default); on request LZW (5, what cv.imwrite's TIFF writer
+         uses) for uint8 / float64 and Predictor 2 for uint8, encoded by the host build's hm_tiff_encode_strips
 
 `imread` / `imwrite` follow OpenCV's channel convention: files hold RGB(A), arrays are BGR(A). OpenCV applies
 the swap on both sides for every depth, so a file written here and read by the reference (or the reverse) shows
@@ -29,6 +30,11 @@ Predictor 2, swaps R and B and applies the imread flag on the GPU, so the frame 
 little-endian samples of uint8 (1 / 3 / 4 samples, Predictor 1 / 2) and float64 (1 / 3 samples), Compression 1 and 5,
 strips, chunky; everything else it refuses with NotImplementedError - there is no fallback, `imread` is the host path.
 A `DeviceTiffReader` owns the staging and device buffers and is reused across the files of a series.
+
+`imwrite_device` is its writing twin: a uint8 or float64 tensor in device memory goes through hm_tiff_encode_strips
+(csrc/hm_tiff_encode.hip) - optional quantisation to uint8, R/B swap, Predictor 2, LZW, compaction - and comes down as one payload
+that is written between the header and the IFD. Compression 1 gives the very bytes `imwrite` writes. A `DeviceTiffWriter` owns
+the buffers. Not written on the device: uint16 / float32, tiles, Deflate, PackBits; there is no fallback, `imwrite` is the host path.
 """
 from __future__ import annotations
 
@@ -261,46 +267,38 @@ def imread(path, flags: int = IMREAD_COLOR) -> Optional[np.ndarray]:
     return np.ascontiguousarray(img)
 
 
-def imwrite(path, img) -> bool:
-    """cv.imwrite for TIFF files: (H, W) or (H, W, 3|4) arrays in BGR(A) order; uint8 / uint16 / float32 / float64.
-    Uncompressed strips, RGB(A) order in the file."""
-    a = np.asarray(img)
-    if a.dtype == np.bool_:
-        a = a.astype(np.uint8)
-    if a.dtype not in (np.uint8, np.uint16, np.float32, np.float64):
-        raise TypeError(f"imwrite: unsupported sample type {a.dtype}")
-    if a.ndim == 2:
-        a = a[:, :, None]
-    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
-        raise ValueError(f"imwrite: unsupported array shape {np.asarray(img).shape}")
-    H, W, S = a.shape
-    if H == 0 or W == 0:
-        raise ValueError("imwrite: empty image")
-    a = np.ascontiguousarray(_swap_rb(a)).astype(a.dtype.newbyteorder("<"), copy=False)
-    row_bytes = W * S * a.dtype.itemsize
-    rps = max(1, min(H, (1 << 13) // row_bytes))
-    n_strips = (H + rps - 1) // rps
-    data_bytes = H * row_bytes
-    big = data_bytes + 16 * n_strips + 4096 >= (1 << 32)
+def _strip_rows(H: int, row_bytes: int) -> int:
+    """OpenCV's strip rule: one strip per ~8 KiB of rows."""
+    return max(1, min(H, (1 << 13) // row_bytes))
+
+
+def _file_frame(H: int, W: int, S: int, dtype: np.dtype, rps: int, offsets, counts, payload_bytes: int, compression: int = 1,
+                predictor: int = 1) -> Tuple[bytes, bytes]:
+    """What surrounds the strips of a file, shared by imwrite and the device writer: (head, tail). The file is head + payload + tail:
+    head is the TIFF or BigTIFF header (the switch is decided from the real payload size), tail the padding to an even offset, the IFD
+    and its out-of-line values. `offsets` are relative to the payload's first byte; Compression (259) is always written, Predictor (317)
+    only when it is not 1."""
+    n_strips = len(counts)
+    big = payload_bytes + 16 * n_strips + 4096 >= (1 << 32)
     osz = 8 if big else 4
     otype = 16 if big else 4
     header = 16 if big else 8
-    counts = [row_bytes * min(rps, H - s * rps) for s in range(n_strips)]
-    offsets = [header + s * rps * row_bytes for s in range(n_strips)]
-    pos = header + data_bytes
+    pos = header + payload_bytes
     pos += pos & 1
     entries = []          # (tag, type, values)
-    fmt = 3 if a.dtype.kind == "f" else 1
+    fmt = 3 if dtype.kind == "f" else 1
     entries.append((256, 4, [W]))
     entries.append((257, 4, [H]))
-    entries.append((258, 3, [a.dtype.itemsize * 8] * S))
-    entries.append((259, 3, [1]))
+    entries.append((258, 3, [dtype.itemsize * 8] * S))
+    entries.append((259, 3, [compression]))
     entries.append((262, 3, [2 if S >= 3 else 1]))
-    entries.append((273, otype, offsets))
+    entries.append((273, otype, [header + int(o) for o in offsets[:n_strips]]))
     entries.append((277, 3, [S]))
     entries.append((278, 4, [rps]))
-    entries.append((279, otype, counts))
+    entries.append((279, otype, [int(c) for c in counts]))
     entries.append((284, 3, [1]))
+    if predictor != 1:
+        entries.append((317, 3, [predictor]))
     if S == 4:
         entries.append((338, 3, [2]))                   # unassociated alpha
     entries.append((339, 3, [fmt] * S))
@@ -323,17 +321,72 @@ def imwrite(path, img) -> bool:
             if len(extra) & 1:
                 extra += b"\0"
     ifd += struct.pack("<Q" if big else "<I", 0)
+    head = struct.pack("<2sHHHQ", b"II", 43, 8, 0, ifd_off) if big else struct.pack("<2sHI", b"II", 42, ifd_off)
+    pad = b"\0" if (header + payload_bytes) & 1 else b""
+    return head, pad + bytes(ifd) + bytes(extra)
+
+
+def _check_write_options(dtype, compression: int, predictor: int, who: str) -> None:
+    if compression not in (1, 5):
+        raise NotImplementedError(f"{who}: TIFF compression {compression} is not written (1 = none and 5 = LZW are)")
+    if predictor not in (1, 2):
+        raise ValueError(f"{who}: TIFF predictor {predictor} (1 = none and 2 = horizontal differencing exist)")
+    if predictor == 2 and np.dtype(dtype) != np.uint8:
+        raise NotImplementedError(f"{who}: the horizontal predictor is written for uint8 samples only, not {np.dtype(dtype).name}")
+    if (compression, predictor) != (1, 1) and np.dtype(dtype) not in (np.uint8, np.float64):
+        raise NotImplementedError(f"{who}: LZW strips and the predictor are written for uint8 and float64 samples, not {np.dtype(dtype).name}")
+
+
+def imwrite(path, img, compression: int = 1, predictor: int = 1) -> bool:
+    """cv.imwrite for TIFF files: (H, W) or (H, W, 3|4) arrays in BGR(A) order; uint8 / uint16 / float32 / float64.
+    RGB(A) order in the file. Default: uncompressed strips. `compression=5` writes LZW strips (uint8 and float64; what cv.imwrite's TIFF
+    writer does), `predictor=2` horizontal differencing (uint8 only); both go through the host build's hm_tiff_encode_strips. What is
+    not written raises ValueError / NotImplementedError before the file is created."""
+    a = np.asarray(img)
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if a.dtype not in (np.uint8, np.uint16, np.float32, np.float64):
+        raise TypeError(f"imwrite: unsupported sample type {a.dtype}")
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+        raise ValueError(f"imwrite: unsupported array shape {np.asarray(img).shape}")
+    H, W, S = a.shape
+    if H == 0 or W == 0:
+        raise ValueError("imwrite: empty image")
+    _check_write_options(a.dtype, compression, predictor, "imwrite")
+    row_bytes = W * S * a.dtype.itemsize
+    rps = _strip_rows(H, row_bytes)
+    n_strips = (H + rps - 1) // rps
+    if (compression, predictor) == (1, 1):
+        a = np.ascontiguousarray(_swap_rb(a)).astype(a.dtype.newbyteorder("<"), copy=False)
+        counts = [row_bytes * min(rps, H - s * rps) for s in range(n_strips)]
+        offsets = [s * rps * row_bytes for s in range(n_strips)]
+        payload = a.tobytes()
+    else:
+        nat = _native()
+        lib = nat.host_lib()
+        a = np.ascontiguousarray(a.astype(a.dtype.newbyteorder("="), copy=False))
+        strip_bytes = rps * row_bytes
+        cap = int(lib.hm_tiff_encode_payload_bytes(n_strips, strip_bytes, compression))
+        if cap == 0:
+            raise ValueError(f"imwrite: strips of {strip_bytes} bytes cannot be encoded")
+        buf = np.empty(cap, dtype=np.uint8)
+        ws = np.empty(max(1, int(lib.hm_tiff_encode_workspace_bytes(n_strips, strip_bytes, compression))), dtype=np.uint8)
+        tables = np.empty(2 * n_strips + 1, dtype=np.int64)
+        nat.check(lib.hm_tiff_encode_strips(a.ctypes.data, 0 if a.dtype == np.uint8 else 1, 1.0, H, W, S, rps, compression, predictor,
+                                            buf.ctypes.data, cap, tables.ctypes.data, tables.ctypes.data + 8 * (n_strips + 1),
+                                            ws.ctypes.data, None), "hm_tiff_encode_strips")
+        offsets, counts = tables[:n_strips + 1], tables[n_strips + 1:]
+        if (counts < 0).any():
+            raise TiffError(f"strip {int(np.flatnonzero(counts < 0)[0])} could not be encoded ({nat.strerror(int(counts[counts < 0][0]))})")
+        payload = memoryview(buf)[:int(offsets[n_strips])]
+    head, tail = _file_frame(H, W, S, a.dtype, rps, offsets, counts, len(payload), compression, predictor)
     path = Path(path)
     with open(path, "wb") as f:
-        if big:
-            f.write(struct.pack("<2sHHHQ", b"II", 43, 8, 0, ifd_off))
-        else:
-            f.write(struct.pack("<2sHI", b"II", 42, ifd_off))
-        f.write(a.tobytes())
-        if (header + data_bytes) & 1:
-            f.write(b"\0")
-        f.write(bytes(ifd))
-        f.write(bytes(extra))
+        f.write(head)
+        f.write(payload)
+        f.write(tail)
     return True
 
 
@@ -484,3 +537,107 @@ def imread_device(path, flags: int = IMREAD_COLOR, device=None, reader: Optional
         if reader is None:
             reader = _readers[str(device)] = DeviceTiffReader(device)
     return reader.read(path, flags)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The device path of writing (opt-in): hm_tiff_encode_strips
+# ---------------------------------------------------------------------------------------------------------------------
+class DeviceTiffWriter:
+    """The buffers of the device writer, kept and grown across files like DeviceTiffReader's: the device payload, the encoder's
+    workspace, the strip tables (offsets and counts in one tensor, so ONE read-back carries both) and a pinned host buffer.
+    Per file: one hm_tiff_encode_strips, one read-back of the tables (skipped for compression 1, whose tables follow from the geometry),
+    one copy of payload[:total] into pinned memory, one write of header, payload and IFD. Not thread-safe: one writer per thread."""
+
+    def __init__(self, device=None):
+        self._device_arg = device
+        self.device = None
+        self._payload = self._ws = self._tables = self._pinned = None
+
+    _grow = DeviceTiffReader._grow
+
+    def write(self, path, tensor, compression: int = 1, predictor: int = 1, quantize_divisor: Optional[float] = None) -> bool:
+        """`imwrite(path, array)` for a tensor in device memory: (H, W) or (H, W, 1|3|4), contiguous, uint8 or float64, BGR(A) order.
+        `quantize_divisor=d` (float64 tensors) stores uint8 samples around((v / d) * 255) - save_8bit's arithmetic; non-finite samples
+        give 0, results outside 0..255 wrap modulo 256. Nothing falls back: what the device does not write raises."""
+        import torch
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError(f"imwrite_device: a torch tensor in device memory is required, got {type(tensor).__name__}; "
+                            "tiff_io.imwrite is the host path")
+        if tensor.device.type != "cuda":
+            raise ValueError("imwrite_device: the tensor is in host memory; tiff_io.imwrite is the host path")
+        if tensor.dtype not in (torch.uint8, torch.float64):
+            raise TypeError(f"imwrite_device: uint8 and float64 tensors are written, not {tensor.dtype}; tiff_io.imwrite is the host path")
+        if tensor.dim() not in (2, 3) or (tensor.dim() == 3 and tensor.shape[2] not in (1, 3, 4)) or tensor.numel() == 0:
+            raise ValueError(f"imwrite_device: unsupported tensor shape {tuple(tensor.shape)}")
+        if not tensor.is_contiguous():
+            raise ValueError("imwrite_device: the tensor must be contiguous")
+        if quantize_divisor is not None:
+            if tensor.dtype != torch.float64:
+                raise ValueError("imwrite_device: quantize_divisor applies to float64 tensors")
+            quantize_divisor = float(quantize_divisor)
+            if not (0.0 < quantize_divisor < float("inf")):
+                raise ValueError(f"imwrite_device: quantize_divisor must be finite and positive, got {quantize_divisor}")
+        kind = 0 if tensor.dtype == torch.uint8 else (1 if quantize_divisor is None else 2)
+        out_dtype = np.dtype(np.float64 if kind == 1 else np.uint8)
+        _check_write_options(out_dtype, compression, predictor, "imwrite_device")
+        if self._device_arg is not None and torch.device(self._device_arg).index not in (None, tensor.device.index):
+            raise ValueError(f"imwrite_device: the writer belongs to {self._device_arg}, the tensor is on {tensor.device}")
+        device = self.device = tensor.device
+        H, W = int(tensor.shape[0]), int(tensor.shape[1])
+        S = int(tensor.shape[2]) if tensor.dim() == 3 else 1
+        row_bytes = W * S * out_dtype.itemsize
+        rps = _strip_rows(H, row_bytes)
+        n = (H + rps - 1) // rps
+        strip_bytes = rps * row_bytes
+        nat = _native()
+        lib = nat.hip_lib
+        cap = int(lib.hm_tiff_encode_payload_bytes(n, strip_bytes, compression))
+        if cap == 0:
+            raise ValueError(f"imwrite_device: strips of {strip_bytes} bytes cannot be encoded")
+        ws_bytes = int(lib.hm_tiff_encode_workspace_bytes(n, strip_bytes, compression))
+        payload = self._grow("_payload", cap, dtype=torch.uint8, device=device)
+        ws = self._grow("_ws", ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
+        tables = self._grow("_tables", 2 * n + 1, dtype=torch.int64, device=device)
+        with torch.cuda.device(device):
+            nat.check(lib.hm_tiff_encode_strips(tensor.data_ptr(), kind, 1.0 if quantize_divisor is None else quantize_divisor, H, W, S,
+                                                rps, compression, predictor, payload.data_ptr(), cap, tables.data_ptr(),
+                                                tables.data_ptr() + 8 * (n + 1), nat.ptr(ws), nat.current_stream_ptr(device)),
+                      "hm_tiff_encode_strips")
+            if compression == 1:
+                counts = [row_bytes * min(rps, H - s * rps) for s in range(n)]
+                offsets = [s * strip_bytes for s in range(n)]
+                total = H * row_bytes
+            else:
+                t = tables[:2 * n + 1].cpu().numpy()       # waits for the kernels
+                offsets, counts = t[:n + 1], t[n + 1:]
+                if (counts < 0).any():
+                    raise TiffError(f"strip {int(np.flatnonzero(counts < 0)[0])} could not be encoded "
+                                    f"({nat.strerror(int(counts[counts < 0][0]))})")
+                total = int(offsets[n])
+            pinned = self._grow("_pinned", total, dtype=torch.uint8, pin_memory=True)
+            pinned[:total].copy_(payload[:total], non_blocking=True)
+            head, tail = _file_frame(H, W, S, out_dtype, rps, offsets, counts, total, compression, predictor)
+            torch.cuda.current_stream(device).synchronize()
+        with open(Path(path), "wb") as f:
+            f.write(head)
+            f.write(memoryview(pinned.numpy())[:total])
+            f.write(tail)
+        return True
+
+
+_writers = {}
+
+
+def imwrite_device(path, tensor, compression: int = 1, predictor: int = 1, quantize_divisor: Optional[float] = None,
+                   writer: Optional[DeviceTiffWriter] = None) -> bool:
+    """`imwrite` with the encode on the GPU (hm_tiff_encode_strips): the tensor - contiguous, in device memory, uint8 or float64,
+    (H, W) or (H, W, 1|3|4) in BGR(A) order - becomes the strips of the file on the device and comes down as one payload. With
+    compression 1 the file is byte-identical to imwrite's. Opt-in; a host tensor, another dtype or a non-contiguous tensor raises (no
+    fallback: call `imwrite`). `writer` (a DeviceTiffWriter) carries the buffers from file to file; without one, a writer per device is
+    kept by the module."""
+    if writer is None:
+        key = str(getattr(tensor, "device", None))
+        writer = _writers.get(key)
+        if writer is None:
+            writer = _writers[key] = DeviceTiffWriter()
+    return writer.write(path, tensor, compression, predictor, quantize_divisor)

@@ -26,7 +26,7 @@
  * (csrc_host/hm_host.cpp, plain C++) is the HOST build behind Measurand(use_cupy=False) - the slot of the reference's NumpyMeasurand
  * (modules/measurand_factory.py:10-14): every pointer is then a HOST pointer, `stream` is ignored, calls are synchronous and workspaces
  * may be NULL; the hm_tiff_* decoders are not exported (the two strip decoders are host code of libhdrmerge.so already;
- * hm_tiff_decode_strips, the device path of the same files, is in both builds).
+ * hm_tiff_decode_strips, the device path of the same files, and hm_tiff_encode_strips, its writing twin, are in both builds).
  * The device build never calls or falls back to the host build.
  */
 #ifndef HDRMERGE_H
@@ -607,6 +607,45 @@ size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int com
 int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts, int n_strips,
                           int compression, int predictor, int rows_per_strip, int height, int width, int samples, int bytes_per_sample,
                           int color_mode, void* dst, int64_t* strip_status, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The writing twin (csrc/hm_tiff_encode.hip; the host build carries the same entry points with host pointers, one strip per OpenMP
+ * iteration, and tiff_io.imwrite writes its LZW files through that): one call turns an image in device memory into the strips of a
+ * TIFF file - float64 optionally quantised to uint8 with save_8bit's arithmetic, B,G,R(,A) turned into file order R,G,B(,A),
+ * Predictor 2 applied, every strip LZW-encoded by one wave with its dictionary in LDS, and the strips compacted into one payload that
+ * is copied down once. Opt-in (tiff_io.imwrite_device); tiff_io.imwrite stays the default path.
+ *   src                 (height, width, samples) in B,G,R(,A) order, dense, in device memory
+ *   src_kind            0 = uint8, stored as it is; 1 = float64, stored as it is (little-endian 8-byte words); 2 = float64 stored as
+ *                       uint8: q = rint((v / divisor) * 255.0) in exactly that order, round half to even, wrapped modulo 256 (the
+ *                       convention of hm_linearize_f64's index); non-finite samples give 0. A divisor of 1.0 is "no scaling"
+ *   divisor             read with src_kind 2 only
+ *   rows_per_strip      strip s holds min(rows_per_strip, height - s * rows_per_strip) rows of width * samples * (1 or 8) bytes;
+ *                       n_strips = ceil(height / min(rows_per_strip, height)), strip_bytes = min(rows_per_strip, height) * row bytes
+ *   compression         1 (none) or 5 (LZW: the stream rules of hm_tiff_lzw_decode, a Clear first and when the table is full, EOI last)
+ *   predictor           1, or 2 (horizontal differencing modulo 256 within a row) with 1-byte output
+ *   payload             payload_cap >= hm_tiff_encode_payload_bytes(n_strips, strip_bytes, compression) bytes, 16-byte aligned.
+ *                       Compression 1: strip s at s * strip_bytes, no gaps. Compression 5: strip s at strip_offsets[s], a multiple of
+ *                       16; the bytes between the end of a stream and the next strip are zeros. Every byte of
+ *                       payload[0, strip_offsets[n_strips]) is written by the call
+ *   strip_offsets       (n_strips + 1) int64, written by the call: offsets into payload; the last entry is the payload's size
+ *   strip_counts        (n_strips) int64, written by the call: StripByteCounts. Each is at most hm_tiff_encode_bound(strip_bytes) =
+ *                       (3 n + 1) / 2 + n / 2048 + 8, which no LZW stream of n bytes passes (derivation: csrc/hm_tiff_lzw_enc_body.h);
+ *                       every code is checked against it before it is emitted, and a strip that would pass it gets HM_ESHAPE here
+ *   workspace           hm_tiff_encode_workspace_bytes(n_strips, strip_bytes, compression) bytes, 16-byte aligned; 0 (NULL is fine)
+ *                       for compression 1
+ * Returns, before any HIP call: HM_EINVAL for a NULL src / payload / strip_offsets / strip_counts (or workspace with compression 5),
+ * height / width / rows_per_strip < 1, a predictor other than 1 or 2 and, with src_kind 2, a divisor that is not finite and positive;
+ * HM_EUNSUPPORTED for a compression other than 1 or 5, samples other than 1, 3 or 4, an unknown src_kind and predictor 2 with 8-byte
+ * output; HM_ESHAPE for strips of 2^31 bytes or more and a payload_cap below hm_tiff_encode_payload_bytes; HM_EALIGN for a payload or
+ * workspace that is not 16-byte aligned and tables or float64 sources that are not 8-byte aligned. The two size helpers return 0, and
+ * hm_tiff_encode_bound a negative code, for sizes below 1 and strips of 2^31 bytes or more.
+ * ------------------------------------------------------------------------------------------ */
+int64_t hm_tiff_encode_bound(int64_t strip_bytes);
+size_t hm_tiff_encode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression);
+size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes, int compression);
+int hm_tiff_encode_strips(const void* src, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
+                          int compression, int predictor, void* payload, int64_t payload_cap, void* strip_offsets /* n_strips + 1 int64 */,
+                          void* strip_counts /* n_strips int64 */, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,14 @@ installed) for a smooth, a photo-like (gradient + sensor noise) and a noise imag
 Without arguments: the host path (tiff_io.imread) only, no GPU needed. `--device`: the device path (tiff_io.imread_device) next to it, on
 the same files in the same run - timed from the open() of the file to the synchronised status read-back, so the upload of the file's
 bytes is inside - and the wall time of `ExposureSeries.from_dir_path -> load_value_images -> process_HDR_image` for a stack of
-7 x 4096 x 4096 x 3 LZW frames both ways (warm: the second run of each)."""
+7 x 4096 x 4096 x 3 LZW frames both ways (warm: the second run of each).
+
+`--write` (needs a GPU; nothing else runs): the way out of HBM. For a smooth, a photo-like and a noise image of 4096 x 4096 x 3 and
+2048 x 2048 x 3 held by a device-backend ImageSet as a float64 value image (values up to 4) with a std image, the wall time from the
+device-resident image to the closed files of `save_8bit` (compression 1 and 5) and `save_64bit` (val and std), host path against
+`device_encode=True`, warm (the median of three runs after a first, with the fastest and slowest in brackets), the size of the value file, and the device time of hm_tiff_encode_strips alone
+(HIP events around the call) with compression 1 - the pack kernel only - and 5, whose difference is the LZW kernel with its scan and
+compaction. The host path is the code of the commit before the device writer, unchanged, so one run gives both sides."""
 import argparse
 import pathlib
 import sys
@@ -19,7 +26,106 @@ from camera_linearity_amd import tiff_io as T  # noqa: E402
 
 ap = argparse.ArgumentParser(description=__doc__)
 ap.add_argument("--device", action="store_true", help="also time tiff_io.imread_device and the 7-frame load-and-merge both ways (needs a GPU)")
+ap.add_argument("--write", action="store_true", help="time ImageSet.save_8bit / save_64bit, host path against device_encode=True (needs a GPU)")
 args = ap.parse_args()
+
+
+def bench_write():
+    import shutil
+    import torch
+    from camera_linearity_amd import _native as nat
+    from camera_linearity_amd.image_set import ImageSet
+    d = pathlib.Path(tempfile.mkdtemp())
+    rng = np.random.default_rng(0)
+    dev = torch.device("cuda", 0)
+
+    class Ms(float):
+        """A median of three warm runs that prints with its spread."""
+        def __format__(self, spec):
+            return f"{float(self):{spec}} ({self.lo:.0f}-{self.hi:.0f})"
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        runs = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            runs.append((time.perf_counter() - t0) * 1e3)
+        runs.sort()
+        m = Ms(runs[1])
+        m.lo, m.hi = runs[0], runs[2]
+        return m
+
+    def encode_ms(t, kind, divisor, compression, predictor=1):
+        """Device time of one hm_tiff_encode_strips (HIP events), warm, best of 3."""
+        H, W, S = t.shape
+        row = W * S * (8 if kind == 1 else 1)
+        rps = max(1, min(H, 8192 // row))
+        n = -(-H // rps)
+        lib = nat.hip_lib
+        cap = lib.hm_tiff_encode_payload_bytes(n, rps * row, compression)
+        payload = torch.empty(cap, dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(16, lib.hm_tiff_encode_workspace_bytes(n, rps * row, compression)), dtype=torch.uint8, device=dev)
+        tables = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)
+        best = float("inf")
+        for _ in range(4):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            nat.check(lib.hm_tiff_encode_strips(t.data_ptr(), kind, divisor, H, W, S, rps, compression, predictor, payload.data_ptr(), cap,
+                                                tables.data_ptr(), tables.data_ptr() + 8 * (n + 1), ws.data_ptr(),
+                                                nat.current_stream_ptr(dev)), "hm_tiff_encode_strips")
+            e1.record()
+            e1.synchronize()
+            best = min(best, e0.elapsed_time(e1))
+        total = int(tables[n].item())
+        return best, total
+
+    for size in (4096, 2048):
+        ramp = np.add.outer(np.arange(size), np.arange(size))[:, :, None]
+        images = {"smooth": (ramp // 37 % 256 * np.ones(3)) / 255.0 * 4.0,
+                  "photo-like": np.clip(ramp / 40 + rng.normal(size=(size, size, 3)) * 2, 0, 255) / 255.0 * 4.0,
+                  "noise": rng.random((size, size, 3)) * 4.0}
+        for name, val in images.items():
+            std = np.ascontiguousarray(val[::-1]) * 0.01 + 1e-3
+            s_ = ImageSet(file_path=d / "10ms bf 5x scene.tif", value=val, std=std, use_cupy=True)
+            mb8, mb64 = val.size / 1e6, val.nbytes / 1e6
+            print(f"--- {size} x {size} x 3, {name}: uint8 image {mb8:.0f} MB, float64 image {mb64:.0f} MB", flush=True)
+            for compression in (1, 5):
+                th = timed(lambda: s_.save_8bit(d / "h8.tif", compression=compression))
+                td = timed(lambda: s_.save_8bit(d / "d8.tif", device_encode=True, compression=compression))
+                a, b = T.imread(d / "h8.tif", T.IMREAD_UNCHANGED), T.imread(d / "d8.tif", T.IMREAD_UNCHANGED)
+                assert np.array_equal(a, b)
+                print(f"save_8bit (uint8 val + float64 std) compression {compression}: host {th:.0f} ms, device_encode {td:.0f} ms "
+                      f"({float(th) / float(td):.1f} x), val file {(d / 'd8.tif').stat().st_size / 1e6:.1f} MB", flush=True)
+            th = timed(lambda: s_.save_64bit(d / "h64.tif"))
+            td = timed(lambda: s_.save_64bit(d / "d64.tif", device_encode=True))
+            assert (d / "h64.tif").read_bytes() == (d / "d64.tif").read_bytes()
+            print(f"save_64bit (val + std, uncompressed): host {th:.0f} ms, device_encode {td:.0f} ms ({float(th) / float(td):.1f} x)", flush=True)
+            tv = s_.measurand.val
+            hv = val
+            th = timed(lambda: T.imwrite(d / "h64z.tif", hv, compression=5))
+            td = timed(lambda: T.imwrite_device(d / "d64z.tif", tv, compression=5))
+            assert (d / "h64z.tif").read_bytes() == (d / "d64z.tif").read_bytes()
+            print(f"float64 val with LZW (array already on its side): imwrite {th:.0f} ms, imwrite_device {td:.0f} ms, "
+                  f"file {(d / 'd64z.tif').stat().st_size / 1e6:.0f} MB against {mb64:.0f} MB uncompressed", flush=True)
+            divisor = float(val.max())
+            p1, _ = encode_ms(tv, 2, divisor, 1)
+            p5, tot = encode_ms(tv, 2, divisor, 5)
+            q5, tot2 = encode_ms(tv, 2, divisor, 5, predictor=2)
+            f1, _ = encode_ms(tv, 1, 1.0, 1)
+            f5, totf = encode_ms(tv, 1, 1.0, 5)
+            print(f"hm_tiff_encode_strips alone: float64 -> uint8 pack {p1:.2f} ms, with LZW {p5:.2f} ms (LZW + scan + compaction "
+                  f"{p5 - p1:.2f} ms, payload {tot / 1e6:.1f} MB; predictor 2: {q5:.2f} ms, {tot2 / 1e6:.1f} MB); float64 pack {f1:.2f} ms, "
+                  f"with LZW {f5:.2f} ms (payload {totf / 1e6:.0f} MB)", flush=True)
+            del s_, tv
+    shutil.rmtree(d)
+
+
+if args.write:
+    bench_write()
+    sys.exit(0)
 
 d = pathlib.Path(tempfile.mkdtemp())
 rng = np.random.default_rng(0)
