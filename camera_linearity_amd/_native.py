@@ -32,6 +32,7 @@ HM_DE_STOP_CONVERGED, HM_DE_STOP_ENERGY, HM_DE_STOP_MAX = 1, 2, 4
 HM_OK, HM_EINVAL, HM_EUNSUPPORTED, HM_EALIGN, HM_ELAUNCH, HM_ENODEVICE, HM_ESHAPE = 0, -1, -2, -3, -4, -5, -6
 HM_OP_ADD, HM_OP_SUB, HM_OP_MUL, HM_OP_DIV, HM_OP_POW = range(5)
 HM_UOP_NEG, HM_UOP_LOG_E, HM_UOP_LOG_10 = range(3)
+HM_OUT_F64, HM_OUT_F32 = 0, 1          # hm_merge_args.out_kind: element type of out_val / out_std
 
 
 class HdrMergeError(RuntimeError):
@@ -48,7 +49,7 @@ class MergeArgs(C.Structure):
         ("stds", C.POINTER(C.c_void_p)), ("exposures", C.POINTER(C.c_double)),
         ("icrf", C.c_void_p), ("icrf_diff", C.c_void_p), ("w_lut", C.c_void_p), ("dw_lut", C.c_void_p),
         ("darks_u8", C.POINTER(C.c_void_p)), ("dark_min_dn", C.POINTER(C.c_int32)),
-        ("median_k", C.c_int32), ("_pad0", C.c_int32),
+        ("median_k", C.c_int32), ("out_kind", C.c_int32),
         ("flat_u8", C.c_void_p), ("flat_f64", C.c_void_p), ("flat_std", C.c_void_p),
         ("ff_mean", C.c_double * HM_MAX_CHANNELS), ("ff_std_mean", C.c_double * HM_MAX_CHANNELS),
         ("out_val", C.c_void_p), ("out_std", C.c_void_p), ("out_sum_w", C.c_void_p),

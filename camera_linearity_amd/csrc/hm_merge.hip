@@ -23,6 +23,8 @@
 //                     distinct map once (the d term of the algorithmic byte count) and queues the hot elements, a second kernel
 //                     recomputes one queued element per lane with the k x k medians substituted (needs the caller's workspace).
 //   merge_fixup_hot   the same pass without a workspace: one hot element per wave at a time (sparse maps only).
+// Every kernel that stores val / std has a template parameter OUT (hm_merge_args.out_kind): OUT_F64 stores the float64 result,
+// OUT_F32 rounds it once in registers (v_cvt_f32_f64, round to nearest even) and stores 4-byte elements. Nothing else differs.
 #include "hm_common.h"
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +40,7 @@
 namespace hm {
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------
@@ -77,6 +80,19 @@ __device__ __forceinline__ void reset_hot_counters(const MergeK& a) {
     if (a.hot_reset && blockIdx.x == 0 && threadIdx.x < 4) a.hot_reset[threadIdx.x] = 0u;
 }
 
+// Output element type (template parameter OUT). MergeK keeps out_val / out_std typed double*: with OUT_F32 they address float arrays.
+enum { OUT_F64 = HM_OUT_F64, OUT_F32 = HM_OUT_F32 };
+template <int OUT>
+__device__ __forceinline__ void store_out(double* base, int64_t e, double x) {         // element e of an output array
+    if constexpr (OUT == OUT_F64) base[e] = x;
+    else reinterpret_cast<float*>(base)[e] = static_cast<float>(x);
+}
+template <int OUT>
+__device__ __forceinline__ double* out_at(double* base, int64_t e) {                   // address of element e (scalar bases of the streaming kernels)
+    if constexpr (OUT == OUT_F64) return base + e;
+    else return reinterpret_cast<double*>(reinterpret_cast<float*>(base) + e);
+}
+
 __device__ __forceinline__ void elem_to_pixel(const MergeK& a, int64_t e, int64_t& row, int64_t& col, int& c) {
     const int64_t wc = a.W * a.C;
     row = a.row0 + e / wc;
@@ -104,7 +120,7 @@ __device__ __forceinline__ void flat_field_apply(const MergeK& a, int64_t e, int
 // Tables: t_w/t_dw [256], t_g/t_d [256*C] in LDS.
 // ------------------------------------------------------------------------------------------------
 enum { HOT_NONE = 0, HOT_WAVE = 1, HOT_LANE = 2 };
-template <bool F64IN, bool STD, int HOT>
+template <bool F64IN, bool STD, int HOT, int OUT = OUT_F64>
 __device__ __forceinline__ void merge_one_element(const MergeK& a, const double* t_w, const double* t_dw,
                                                   const double* t_g, const double* t_d, int64_t e, bool store) {
     const int C = a.C, N = a.n_frames;
@@ -179,8 +195,8 @@ __device__ __forceinline__ void merge_one_element(const MergeK& a, const double*
     double sd = STD ? sqrt(var) : 0.0;                                  // :394
     if (a.has_flat) flat_field_apply(a, e, c, STD, val, sd);
     if (store) {
-        a.out_val[e] = val;
-        if (STD) a.out_std[e] = sd;
+        store_out<OUT>(a.out_val, e, val);
+        if (STD) store_out<OUT>(a.out_std, e, sd);
     }
 }
 
@@ -199,7 +215,7 @@ __device__ __forceinline__ void fill_plain_tables(const MergeK& a, double* t_w, 
 // ------------------------------------------------------------------------------------------------
 // generic kernel: one element per thread, runtime N and C, uint8 or float64 frames.
 // ------------------------------------------------------------------------------------------------
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     reset_hot_counters(a);
@@ -207,7 +223,7 @@ __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
     __syncthreads();
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; q < a.n_elems; q += stride)
-        merge_one_element<F64IN, STD, HOT_NONE>(a, t_w, t_dw, t_g, t_d, a.elem0 + q, true);
+        merge_one_element<F64IN, STD, HOT_NONE, OUT>(a, t_w, t_dw, t_g, t_d, a.elem0 + q, true);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -220,7 +236,7 @@ __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
 // exactly the operation sequence of merge_one_element(), so the fix-up is bit-identical to what a
 // streaming kernel would have produced had it been given the filtered frames.
 // ------------------------------------------------------------------------------------------------
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w, const double* t_dw,
                                            const double* t_g, const double* t_d, int64_t e) {
     const int lane = threadIdx.x & 63;
@@ -340,8 +356,8 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
     double sd = STD ? sqrt(var) : 0.0;
     if (a.has_flat) flat_field_apply(a, e, c, STD, val, sd);
     if (lane == 0) {
-        a.out_val[e] = val;
-        if (STD) a.out_std[e] = sd;
+        store_out<OUT>(a.out_val, e, val);
+        if (STD) store_out<OUT>(a.out_std, e, sd);
     }
 }
 
@@ -383,7 +399,7 @@ __host__ __device__ inline uint32_t hot_piece_slots(int64_t n_elems) { return st
 // merge_fixup_hot: every lane scans 16 consecutive elements of every distinct dark map; elements with at least one hot
 // frame are recomputed, one at a time, by the wave. This is the path WITHOUT a workspace: one element per wave at a time
 // makes it collapse on dense maps (15 us of one wave per hot element) - callers that can pass a workspace should.
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) void merge_fixup_hot(const MergeK a) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     fill_plain_tables<F64IN, STD>(a, t_w, t_dw, t_g, t_d);
@@ -410,7 +426,7 @@ __global__ __launch_bounds__(256) void merge_fixup_hot(const MergeK a) {
             while (bits) {
                 const int b = __ffs(static_cast<int>(bits)) - 1;
                 bits &= bits - 1;
-                fixup_element<F64IN, STD>(a, t_w, t_dw, t_g, t_d, base + b);
+                fixup_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, base + b);
             }
         }
     }
@@ -585,7 +601,7 @@ __device__ __forceinline__ uint32_t lane_hotmask(const MergeK& a, int64_t ei) {
     return hotmask;
 }
 
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* t_w, const double* t_dw, const double* t_g, const double* t_d,
                                                  std::conditional_t<F64IN, double, uint8_t>* keep /* LDS, this thread's column, stride 256 */,
                                                  int64_t e, uint32_t hotmask) {
@@ -702,18 +718,18 @@ __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* 
     double val = acc / S;
     double sd = STD ? sqrt(var) : 0.0;                                                   // :394
     if (a.has_flat) flat_field_apply(a, e, c, STD, val, sd);
-    a.out_val[e] = val;
-    if (STD) a.out_std[e] = sd;
+    store_out<OUT>(a.out_val, e, val);
+    if (STD) store_out<OUT>(a.out_std, e, sd);
 }
 
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __device__ __forceinline__ void patch_element(const MergeK& a, const double* t_w, const double* t_dw, const double* t_g, const double* t_d,
                                               char* keep_lds, int64_t e, uint32_t hotmask) {
     using T = std::conditional_t<F64IN, double, uint8_t>;
     if (a.median_k == 3 && (!F64IN || a.n_frames <= kPatchF64Frames))                    // wave-uniform
-        patch_element_k3<F64IN, STD>(a, t_w, t_dw, t_g, t_d, reinterpret_cast<T*>(keep_lds) + threadIdx.x, e, hotmask);
+        patch_element_k3<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, reinterpret_cast<T*>(keep_lds) + threadIdx.x, e, hotmask);
     else
-        merge_one_element<F64IN, STD, HOT_LANE>(a, t_w, t_dw, t_g, t_d, e, true);
+        merge_one_element<F64IN, STD, HOT_LANE, OUT>(a, t_w, t_dw, t_g, t_d, e, true);
 }
 static int patch_keep_bytes(bool f64in, int n_frames, int median_k) {
     if (median_k != 3 || (f64in && n_frames > kPatchF64Frames)) return 16;
@@ -727,7 +743,7 @@ static int patch_keep_bytes(bool f64in, int n_frames, int median_k) {
 // neighbouring cache lines). Workgroups beyond the queue leave before they build their tables.
 // If the scan raised the overflow flag (more hot elements than the workspace holds: a quarter of the image with the recommended
 // size) the queue is ignored: every lane looks at its own elements' dark bytes and patches the hot ones.
-template <bool F64IN, bool STD>
+template <bool F64IN, bool STD, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uint32_t* ws, uint32_t bmax) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     extern __shared__ __attribute__((aligned(16))) char keep_lds[];
@@ -816,7 +832,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; q < a.n_elems; q += stride) {
             const int64_t e = a.elem0 + q;
             const uint32_t hotmask = lane_hotmask(a, a.in_off + e);
-            if (hotmask) patch_element<F64IN, STD>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
+            if (hotmask) patch_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
         return;
     }
@@ -829,7 +845,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
                 e = static_cast<int64_t>(queue[slot_of(q)]);
                 hotmask = lane_hotmask(a, a.in_off + e);
             }
-            patch_element<F64IN, STD>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
+            patch_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
     }
 }
@@ -855,6 +871,9 @@ constexpr int kStdTabBytes = 16 * 256 + 16 * 768;
 
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p));
+}
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
 }
 // the same load through an explicit global-address-space pointer: after an `asm volatile("+s")` pin the compiler no longer
 // knows that a kernarg pointer is global and would fall back to flat_load (which also counts against lgkmcnt)
@@ -883,6 +902,24 @@ __device__ __forceinline__ uint16_t ld_u16_buf(__amdgpu_buffer_rsrc_t r, uint32_
 __device__ __forceinline__ void store2(double* base, uint32_t byte_off, double x, double y) {
     f64x2 v; v.x = x; v.y = y;
     __builtin_nontemporal_store(v, reinterpret_cast<f64x2*>(reinterpret_cast<char*>(base) + byte_off));
+}
+
+// the lane's two elements of a 128-element sub-unit that starts at `base`: 16 bytes per lane as float64 (one contiguous 1 KB
+// global_store_dwordx4 per wave), 8 bytes per lane as float32 (one contiguous 512-byte global_store_dwordx2: four whole 128-byte lines)
+template <int OUT>
+__device__ __forceinline__ void store_pair(double* base, uint32_t lane16, double x, double y) {
+    if constexpr (OUT == OUT_F64) store2(base, lane16, x, y);
+    else {
+        f32x2 v; v.x = static_cast<float>(x); v.y = static_cast<float>(y);
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x2*>(reinterpret_cast<char*>(base) + (lane16 >> 1)));
+    }
+}
+
+// four consecutive float32 elements of one lane (merge_u8_val3's QUAD map): one contiguous 1 KB global_store_dwordx4 per wave
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_quad_f32(double* base, uint32_t lane16, float x0, float x1, float x2, float x3) {
+    f32x4 v; v.x = x0; v.y = x1; v.z = x2; v.w = x3;
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(reinterpret_cast<char*>(base) + lane16));
 }
 
 template <int TAB>
@@ -972,7 +1009,7 @@ constexpr uint32_t kSub = 128;     // elements per sub-unit (64 lanes x 2)
 #define HM_WAVES_ATTR
 #endif
 
-template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3>
+template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
 __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
@@ -1068,7 +1105,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
             const uint32_t c0 = C == 1 ? 0u : (2u * (g * U + s + lane)) % 3u;
             const uint32_t c1 = C == 1 ? 0u : (c0 + 1u) % 3u;
             const uint32_t coffs[2] = {STD ? c0 * 16u : chan_off<TAB>(c0), STD ? c1 * 16u : chan_off<TAB>(c1)};
-            double* ov = a.out_val + sbase;                                   // scalar bases
+            double* ov = out_at<OUT>(a.out_val, sbase);                       // scalar bases
             double* osw = SUMW ? a.out_sum_w + sbase : nullptr;
 
             // flat-field operands of the lane's two elements (one ushort / 16-byte loads)
@@ -1121,7 +1158,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                     flat_field_math(F[1], iF2[1], 0.0, a.ff_mean[c1], 0.0, false, val[1], dummy);
                 }
                 if constexpr (SUMW) store2(osw, lane16, S[0], S[1]);
-                store2(ov, lane16, val[0], val[1]);
+                store_pair<OUT>(ov, lane16, val[0], val[1]);
             } else {
                 const double2* t_wdw = reinterpret_cast<const double2*>(lds);
                 const char* t_gd = lds + 16 * 256;
@@ -1209,8 +1246,8 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                     flat_field_math(F[1], iF2[1], sF[1], a.ff_mean[c1], a.ff_std_mean[c1], true, val[1], so[1]);
                 }
                 if constexpr (SUMW) store2(osw, lane16, S[0], S[1]);
-                store2(ov, lane16, val[0], val[1]);
-                store2(a.out_std + sbase, lane16, so[0], so[1]);
+                store_pair<OUT>(ov, lane16, val[0], val[1]);
+                store_pair<OUT>(out_at<OUT>(a.out_std, sbase), lane16, so[0], so[1]);
             }
             __builtin_amdgcn_sched_barrier(0);   // keep one sub-unit's gathers from piling onto the next one's
         }
@@ -1228,15 +1265,15 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
 #ifndef HM_STD_WAVES_FLAT
 #define HM_STD_WAVES_FLAT 2
 #endif
-template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK>
+template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int OUT = OUT_F64>
 __global__ __launch_bounds__(BLOCK) HM_WAVES_ATTR void merge_u8_fast(const MergeK a) {
     static_assert(!STD, "std instantiations go through merge_u8_fast_std");
-    merge_u8_fast_body<NF, U, TAB, false, PREFETCH, FLAT, SUMW, BLOCK>(a);
+    merge_u8_fast_body<NF, U, TAB, false, PREFETCH, FLAT, SUMW, BLOCK, 3, OUT>(a);
 }
-template <int NF, int U, int TAB, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3>
+template <int NF, int U, int TAB, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES, FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES)))
 void merge_u8_fast_std(const MergeK a) {
-    merge_u8_fast_body<NF, U, TAB, true, PREFETCH, FLAT, SUMW, BLOCK, CH>(a);
+    merge_u8_fast_body<NF, U, TAB, true, PREFETCH, FLAT, SUMW, BLOCK, CH, OUT>(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1308,14 +1345,23 @@ __device__ __forceinline__ bool entry_inrange(double w, double wg) {
 #ifndef HM_VAL3_PROBE
 #define HM_VAL3_PROBE 0      // measurement builds only (wrong results): 1 = no LDS gathers (the ceiling of the HBM access pattern); 2 = every unit's
 #endif                       // frame bytes come from the first 64 units (L2 hits; the gathers and the stores are real); 3 = 2 without the stores
+// OUT / QUAD (float32 outputs): OUT_F32 stores float32 elements. With the pair map above that is 8 bytes per lane and store instruction,
+// half of what the float64 form moves per instruction. QUAD (OUT_F32, PF == 1, even U, MAP 0 or 3) keeps 16-byte stores by changing the
+// element map instead of exchanging values between lanes: lane l owns FOUR consecutive elements 4l .. 4l+3 of a 256-element span - one
+// global_load_dword per frame and span (half as many load instructions, half as many byte registers) and one contiguous 1 KB
+// global_store_dwordx4 per wave and span. "Slot" s of the pair map becomes half a span: s even = elements 4l, 4l+1, s odd = 4l+2, 4l+3 of span
+// s / 2, and the channel of element j of slot s is (4l + (s / 2) + 2 (s % 2) + j) % 3 - still a compile-time function of (s, j) on top of a lane
+// constant. The arithmetic per element is untouched. Needs the frames (and the flat field) 4-byte aligned at the call's first element and
+// the output 16-byte aligned; hm_merge sends other calls to the pair form (DESIGN.md 4.1.1 has the measured pair).
 #if HM_VAL3_PROBE >= 2
 #define HM_PROBE_UNIT(x) ((x) & 63u)
 #else
 #define HM_PROBE_UNIT(x) (x)
 #endif
-template <int NF, int U, int PF, int MAP, bool FLAT = false, int CH = 3>
+template <int NF, int U, int PF, int MAP, bool FLAT = false, int CH = 3, int OUT = OUT_F64, bool QUAD = false>
 __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
     static_assert(CH == 3 || CH == 1, "colour or monochrome");
+    static_assert(!QUAD || (OUT == OUT_F32 && PF == 1 && U % 2 == 0 && (MAP == 0 || MAP == 3)), "the four-elements-per-lane map: float32 outputs, prefetch form, whole spans");
     constexpr uint32_t TS = 16u * CH;                              // bytes of table per DN
     __shared__ __attribute__((aligned(16))) char lds[16 * 256 * CH];
     __shared__ uint32_t s_bad[4];
@@ -1332,7 +1378,9 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
     const uint32_t lane16 = lane * 16u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t wave_el = WGMAP ? wave * kSub : 0u;             // scalar: the wave's element offset inside a chunk
-    const uint32_t lane2 = lane * 2u + wave_el;                    // element (= byte) offset of the lane's first element inside the unit
+    const uint32_t lane2 = QUAD ? lane * 4u : lane * 2u + wave_el; // element (= byte) offset of the lane's first element inside the unit
+    constexpr int UR = QUAD ? U / 2 : U;                           // byte registers per frame and unit (QUAD: one dword per 256-element span)
+    constexpr uint32_t RSLOT = QUAD ? 2u * SLOT : SLOT;            // element distance between them
     const uint32_t n_units = static_cast<uint32_t>(a.n_elems / UNIT);
     const uint32_t ustride = WGMAP ? gridDim.x : gridDim.x * 4u;
     uint32_t u = WGMAP ? blockIdx.x : blockIdx.x * 4u + wave;      // wave-uniform
@@ -1342,12 +1390,20 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
     // (PF == 1 keeps 32-bit registers filled by zero-extending global loads: with two 16-bit register sets hipcc packs pairs
     // of them into one VGPR with v_perm_b32 at the loop back-edge, i.e. waits for the prefetch it has just issued)
     using reg_t = std::conditional_t<PF == 0, uint16_t, uint32_t>;
-    reg_t RA[NS][U], RB[PF ? NS : 1][PF ? U : 1];
+    reg_t RA[NS][UR], RB[PF ? NS : 1][PF ? UR : 1];
+    auto ld_reg = [](const uint8_t* q) { if constexpr (QUAD) return ld_u32(q); else return ld_u16(q); };
+    // the two DNs of frame i, slot s (QUAD: the low / high half of the span's dword)
+    auto dn_pair = [](const auto& regs, int i, int s_) {
+        if constexpr (QUAD) return (s_ & 1) ? (regs[i][s_ >> 1] >> 16) : (regs[i][s_ >> 1] & 0xffffu);
+        else return regs[i][s_];
+    };
+    // element j of slot s, counted from the lane's first element, modulo 3
+    auto el = [](int s_, int j) constexpr { return QUAD ? (s_ / 2) + 2 * (s_ % 2) + j : 2 * s_ + j; };
     auto load_unit = [&](uint32_t unit, auto& dst) {
         if constexpr (FLAT) {                                      // the flat field covers the OUTPUT rows: no in_off
             const uint8_t* p = a.flat_u8 + static_cast<int64_t>(unit) * UNIT;
 #pragma unroll
-            for (int s = 0; s < U; ++s) dst[NF][s] = ld_u16(p + SLOT * s + lane2);
+            for (int s = 0; s < UR; ++s) dst[NF][s] = ld_reg(p + RSLOT * s + lane2);
         }
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
@@ -1358,7 +1414,7 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
             } else {
                 const uint8_t* p = static_cast<const uint8_t*>(a.frame[i]) + a.in_off + static_cast<int64_t>(HM_PROBE_UNIT(unit)) * UNIT;
 #pragma unroll
-                for (int s = 0; s < U; ++s) dst[i][s] = ld_u16(p + SLOT * s + lane2);
+                for (int s = 0; s < UR; ++s) dst[i][s] = ld_reg(p + RSLOT * s + lane2);
             }
         }
     };
@@ -1393,10 +1449,10 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
         mm[1] = k == 0u ? m1 : k == 1u ? m2 : m0;
         mm[2] = k == 0u ? m2 : k == 1u ? m0 : m1;
     }
-    auto flat_epilogue = [&](int s_, reg_t r, double& v0, double& v1) {          // measurand.py:602, as flat_field_math() does it
+    auto flat_epilogue = [&](int s_, uint32_t r, double& v0, double& v1) {          // measurand.py:602, as flat_field_math() does it
         if constexpr (FLAT) {
-            v0 = (v0 / t_F[r & 255u]) * mm[ci(2 * s_)];
-            v1 = (v1 / t_F[r >> 8]) * mm[ci(2 * s_ + 1)];
+            v0 = (v0 / t_F[r & 255u]) * mm[ci(el(s_, 0))];
+            v1 = (v1 / t_F[r >> 8]) * mm[ci(el(s_, 1))];
         }
     };
 
@@ -1404,8 +1460,18 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
     auto process = [&](auto refill_tag, uint32_t unit, auto& cur) {
         constexpr bool REFILL = decltype(refill_tag)::value;
         const uint32_t next_off = HM_PROBE_UNIT(unit + ustride) * UNIT;                                   // scalar: byte offset of the next unit in every frame
-        double* og = a.out_val + static_cast<int64_t>(unit) * UNIT + wave_el;                // scalar base of the wave's output in this unit
+        double* og = out_at<OUT>(a.out_val, static_cast<int64_t>(unit) * UNIT + wave_el);    // scalar base of the wave's output in this unit
         double held[DEFER ? U : 1][2];
+        // the slot's two results: stored as a pair, or (QUAD) the even slot's kept as two floats until the odd slot completes the lane's four
+        float q0 = 0.0f, q1 = 0.0f;
+        auto emit = [&](int s_, double v0, double v1) {
+            if constexpr (QUAD) {
+                if (s_ % 2 == 0) { q0 = static_cast<float>(v0); q1 = static_cast<float>(v1); }
+                else store_quad_f32(out_at<OUT>(og, RSLOT * (s_ / 2)), lane16, q0, q1, static_cast<float>(v0), static_cast<float>(v1));
+            } else {
+                store_pair<OUT>(out_at<OUT>(og, SLOT * s_), lane16, v0, v1);
+            }
+        };
         if constexpr (PIPE) {
             // software-pipelined gathers ("software-pipelined LDS gathers"): two sets of gathered {w, w g} pairs; the ds_read_b128 of the next
             // bundle of HM_FB frames (of this or the next sub-unit) are in flight while the current bundle's add / fma chain runs
@@ -1415,9 +1481,9 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
 #pragma unroll
                 for (int f = 0; f < HM_FB; ++f) {
                     if (b_ * HM_FB + f < NF) {
-                        const reg_t r = cur[b_ * HM_FB + f][s_];
-                        dst[f][0] = *reinterpret_cast<const double2*>(lds + (__umul24(static_cast<uint32_t>(r & 255u), TS) + off[ci(2 * s_)]));
-                        dst[f][1] = *reinterpret_cast<const double2*>(lds + (__umul24(static_cast<uint32_t>(r >> 8), TS) + off[ci(2 * s_ + 1)]));
+                        const auto r = dn_pair(cur, b_ * HM_FB + f, s_);
+                        dst[f][0] = *reinterpret_cast<const double2*>(lds + (__umul24(static_cast<uint32_t>(r & 255u), TS) + off[ci(el(s_, 0))]));
+                        dst[f][1] = *reinterpret_cast<const double2*>(lds + (__umul24(static_cast<uint32_t>(r >> 8), TS) + off[ci(el(s_, 1))]));
                     }
                 }
                 if constexpr (REFILL) {                     // PF == 0: the bytes just turned into addresses make room for the next unit's
@@ -1459,8 +1525,8 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
                 double v0, v1;
                 if (fastdiv) { v0 = div_inrange(acc[0], S[0]); v1 = div_inrange(acc[1], S[1]); }
                 else { v0 = acc[0] / S[0]; v1 = acc[1] / S[1]; }
-                flat_epilogue(s, cur[NS - 1][s], v0, v1);
-                store2(og + SLOT * s, lane16, v0, v1);
+                flat_epilogue(s, dn_pair(cur, NS - 1, s), v0, v1);
+                emit(s, v0, v1);
                 __builtin_amdgcn_sched_barrier(0);
             }
             return;
@@ -1474,9 +1540,9 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
 #pragma unroll
                 for (int f = 0; f < HM_FB; ++f) {
                     if (i0 + f < NF) {
-                        const reg_t r = cur[i0 + f][s];
-                        addr[f][0] = __umul24(static_cast<uint32_t>(r & 255u), TS) + off[ci(2 * s)];
-                        addr[f][1] = __umul24(static_cast<uint32_t>(r >> 8), TS) + off[ci(2 * s + 1)];
+                        const auto r = dn_pair(cur, i0 + f, s);
+                        addr[f][0] = __umul24(static_cast<uint32_t>(r & 255u), TS) + off[ci(el(s, 0))];
+                        addr[f][1] = __umul24(static_cast<uint32_t>(r >> 8), TS) + off[ci(el(s, 1))];
                     }
                 }
                 if constexpr (REFILL) {
@@ -1512,18 +1578,18 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
             double v0, v1;
             if (fastdiv) { v0 = div_inrange(acc[0], S[0]); v1 = div_inrange(acc[1], S[1]); }
             else { v0 = acc[0] / S[0]; v1 = acc[1] / S[1]; }
-            flat_epilogue(s, cur[NS - 1][s], v0, v1);
+            flat_epilogue(s, dn_pair(cur, NS - 1, s), v0, v1);
             if constexpr (DEFER) { held[s][0] = v0; held[s][1] = v1; }
 #if HM_VAL3_PROBE == 3
-            else { if (v0 != v0 && v1 == 12345.0) store2(og + SLOT * s, lane16, v0, v1); }
+            else { if (v0 != v0 && v1 == 12345.0) store_pair<OUT>(out_at<OUT>(og, SLOT * s), lane16, v0, v1); }
 #else
-            else store2(og + SLOT * s, lane16, v0, v1);
+            else emit(s, v0, v1);
 #endif
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (DEFER) {                      // U KB of contiguous output in U back-to-back store instructions
 #pragma unroll
-            for (int s = 0; s < U; ++s) store2(og + SLOT * s, lane16, held[s][0], held[s][1]);
+            for (int s = 0; s < U; ++s) store_pair<OUT>(out_at<OUT>(og, SLOT * s), lane16, held[s][0], held[s][1]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1562,7 +1628,7 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
 constexpr int kLoopChunk = 8;
 constexpr int kTemplatedN = 20;                    // frame counts with their own instantiation of the templated kernels (see hm_merge's dispatch)
 
-template <int C, bool STD, bool FLAT, bool SUMW>
+template <int C, bool STD, bool FLAT, bool SUMW, int OUT>
 __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
@@ -1649,7 +1715,7 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                 flat_field_math(F[1], iF2[1], 0.0, a.ff_mean[c1], 0.0, false, val[1], dummy);
             }
             if constexpr (SUMW) store2(a.out_sum_w + sbase, lane16, S[0], S[1]);
-            store2(a.out_val + sbase, lane16, val[0], val[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_val, sbase), lane16, val[0], val[1]);
         } else {
             const double2* t_wdw = reinterpret_cast<const double2*>(lds);
             const char* t_gd = lds + 16 * 256;
@@ -1721,8 +1787,8 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                 flat_field_math(F[1], iF2[1], sF[1], a.ff_mean[c1], a.ff_std_mean[c1], true, val[1], so[1]);
             }
             if constexpr (SUMW) store2(a.out_sum_w + sbase, lane16, S[0], S[1]);
-            store2(a.out_val + sbase, lane16, val[0], val[1]);
-            store2(a.out_std + sbase, lane16, so[0], so[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_val, sbase), lane16, val[0], val[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_std, sbase), lane16, so[0], so[1]);
         }
     }
 }
@@ -1737,10 +1803,10 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
 #else
 #define HM_LOOP_STD_ATTR
 #endif
-template <int C, bool FLAT, bool SUMW>
-__global__ __launch_bounds__(256) HM_LOOP_VAL_ATTR void merge_u8_loop(const MergeK a) { merge_u8_loop_body<C, false, FLAT, SUMW>(a); }
-template <int C, bool FLAT, bool SUMW>
-__global__ __launch_bounds__(256) HM_LOOP_STD_ATTR void merge_u8_loop_std(const MergeK a) { merge_u8_loop_body<C, true, FLAT, SUMW>(a); }
+template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
+__global__ __launch_bounds__(256) HM_LOOP_VAL_ATTR void merge_u8_loop(const MergeK a) { merge_u8_loop_body<C, false, FLAT, SUMW, OUT>(a); }
+template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
+__global__ __launch_bounds__(256) HM_LOOP_STD_ATTR void merge_u8_loop_std(const MergeK a) { merge_u8_loop_body<C, true, FLAT, SUMW, OUT>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // merge_f64_val / merge_f64_std (body: merge_f64_body): float64 frames (the reference's 64-bit mode, image_set.py:225 / frames saved by save_64bit) with the
@@ -1760,7 +1826,7 @@ __device__ __forceinline__ uint32_t lut_index_f64(double v) {
     return static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;          // measurand.py:503
 }
 
-template <int C, bool STD, bool FLAT, bool SUMW>
+template <int C, bool STD, bool FLAT, bool SUMW, int OUT>
 __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
@@ -1857,7 +1923,7 @@ __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
                 flat_field_math(F[1], iF2[1], 0.0, a.ff_mean[c1], 0.0, false, val[1], dummy);
             }
             if constexpr (SUMW) store2(a.out_sum_w + sbase, lane16, S[0], S[1]);
-            store2(a.out_val + sbase, lane16, val[0], val[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_val, sbase), lane16, val[0], val[1]);
         } else {
             double invS[2], invS2[2];
             // one frame of pass 2 (measurand.py:512,616; exposure_series.py:388-389) given its weight
@@ -1973,8 +2039,8 @@ __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
                 flat_field_math(F[1], iF2[1], sF[1], a.ff_mean[c1], a.ff_std_mean[c1], true, val[1], so[1]);
             }
             if constexpr (SUMW) store2(a.out_sum_w + sbase, lane16, S[0], S[1]);
-            store2(a.out_val + sbase, lane16, val[0], val[1]);
-            store2(a.out_std + sbase, lane16, so[0], so[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_val, sbase), lane16, val[0], val[1]);
+            store_pair<OUT>(out_at<OUT>(a.out_std, sbase), lane16, so[0], so[1]);
         }
     }
 }
@@ -1989,13 +2055,13 @@ __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
 #ifndef HM_F64_STD_WAVES
 #define HM_F64_STD_WAVES 3
 #endif
-template <int C, bool FLAT, bool SUMW>
+template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HM_F64_VAL_WAVES, HM_F64_VAL_WAVES))) void merge_f64_val(const MergeK a) {
-    merge_f64_body<C, false, FLAT, SUMW>(a);
+    merge_f64_body<C, false, FLAT, SUMW, OUT>(a);
 }
-template <int C, bool FLAT, bool SUMW>
+template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HM_F64_STD_WAVES, HM_F64_STD_WAVES))) void merge_f64_std(const MergeK a) {
-    merge_f64_body<C, true, FLAT, SUMW>(a);
+    merge_f64_body<C, true, FLAT, SUMW, OUT>(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2004,12 +2070,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HM_F64_STD_
 // hm_merge_describe(): the dispatch below runs with this pointer set and every launch site records its kernel's name
 // instead of launching - so the description cannot drift from what hm_merge really dispatches to.
 static thread_local std::string* g_describe = nullptr;
+static thread_local bool g_describe_f32 = false;      // the call being described has out_kind = HM_OUT_F32
+static thread_local bool g_describe_quad = false;     // ... and the kernel being named stores four float32 elements per lane (merge_u8_val3's QUAD map)
 static bool describe_only(const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
     if (!g_describe) return false;
     char buf[160];
     snprintf(buf, sizeof buf, fmt, a, b, c, d);
+    std::string name = buf;
+    // float32 calls: every kernel that stores val / std (all of them have a template argument list) says so inside it;
+    // the strings of float64 calls stay as they were
+    const size_t close = name.find('>');
+    if (g_describe_f32 && close != std::string::npos) name.insert(close, g_describe_quad ? ",out=f32x4" : ",out=f32");
     if (!g_describe->empty()) *g_describe += " + ";
-    *g_describe += buf;
+    *g_describe += name;
     return true;
 }
 
@@ -2071,12 +2144,12 @@ static bool decode_variant(int variant, bool with_std, FastCfg& c) {
     return true;
 }
 
-template <int NF, int U, int TAB, bool STD, bool PF, bool FLAT, bool SUMW, int BLOCK, int CH = 3>
+template <int NF, int U, int TAB, bool STD, bool PF, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
 static int launch_one(const MergeK& k, hipStream_t st) {
     constexpr int lds = (STD ? kStdTabBytes : TabInfo<TAB>::bytes) + (FLAT ? 16 * 256 : 0);
     void (*kernel)(const MergeK);
-    if constexpr (STD) kernel = merge_u8_fast_std<NF, U, TAB, PF, FLAT, SUMW, BLOCK, CH>;
-    else kernel = merge_u8_fast<NF, U, TAB, false, PF, FLAT, SUMW, BLOCK>;
+    if constexpr (STD) kernel = merge_u8_fast_std<NF, U, TAB, PF, FLAT, SUMW, BLOCK, CH, OUT>;
+    else kernel = merge_u8_fast<NF, U, TAB, false, PF, FLAT, SUMW, BLOCK, OUT>;
     if (describe_only(CH == 1 ? "merge_u8_fast_std<N=%d,U=%d,flat=%d,sum_w=%d,C=1>"
                               : (STD ? "merge_u8_fast_std<N=%d,U=%d,flat=%d,sum_w=%d>" : "merge_u8_fast<N=%d,U=%d,flat=%d,sum_w=%d>"), NF, U, FLAT, SUMW)) return HM_OK;
     int per_cu = 2048 / BLOCK;                       // 32 waves per CU
@@ -2144,7 +2217,7 @@ static bool use_val3_flat(const MergeK& k, bool with_std) {
 }
 static int val3_unit_elems(const Val3Cfg& c) { return c.u * (c.map == 1 ? 4 : 1) * static_cast<int>(kSub); }
 
-template <int NF, int U, int PF, int MAP, bool FLAT = false, int CH = 3>
+template <int NF, int U, int PF, int MAP, bool FLAT = false, int CH = 3, int OUT = OUT_F64, bool QUAD = false>
 static int launch_val3_cfg(const MergeK& k, hipStream_t st) {
     const int64_t units = k.n_elems / (U * (MAP == 1 ? 4 : 1) * static_cast<int>(kSub));
     // workgroups per CU (8 are resident). U = 2 (N <= 8): 12 - a grid of 3072 is a multiple of 3 as it stands (2048 had to become 2046) and
@@ -2159,9 +2232,12 @@ static int launch_val3_cfg(const MergeK& k, hipStream_t st) {
     unsigned grid = MAP == 1 ? static_cast<unsigned>(units < cu_count() * 8 ? units : cu_count() * 8) : stream_grid(units, 4, wg_per_cu);   // 8 workgroups of 4 waves per CU
     if (U % 3 != 0 && grid >= 3) grid -= grid % 3;          // the unit index must advance by a multiple of 3 per iteration (see the kernel)
     if (grid == 0) grid = 1;
-    if (describe_only(CH == 1 ? (FLAT ? "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,flat=1,C=1>" : "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,C=1>")
-                              : (FLAT ? "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,flat=1>" : "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d>"), NF, U, PF, MAP)) return HM_OK;
-    hipLaunchKernelGGL((merge_u8_val3<NF, U, PF, MAP, FLAT, CH>), dim3(grid), dim3(256), 0, st, k);
+    g_describe_quad = QUAD;
+    const bool dry = describe_only(CH == 1 ? (FLAT ? "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,flat=1,C=1>" : "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,C=1>")
+                                           : (FLAT ? "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d,flat=1>" : "merge_u8_val3<N=%d,U=%d,PF=%d,MAP=%d>"), NF, U, PF, MAP);
+    g_describe_quad = false;
+    if (dry) return HM_OK;
+    hipLaunchKernelGGL((merge_u8_val3<NF, U, PF, MAP, FLAT, CH, OUT, QUAD>), dim3(grid), dim3(256), 0, st, k);
     return launch_status();
 }
 template <int NF>
@@ -2220,12 +2296,12 @@ static int launch_val_tab(const MergeK& k, const FastCfg& c, hipStream_t st) {
     }
 }
 
-template <int NF, bool STD, int U, int TAB>
+template <int NF, bool STD, int U, int TAB, int OUT = OUT_F64>
 static int launch_extras(const MergeK& k, hipStream_t st) {
     const bool flat = k.has_flat != 0, sumw = k.out_sum_w != nullptr;
-    if (flat && sumw) return launch_one<NF, U, TAB, STD, true, true, true, 256>(k, st);
-    if (flat) return launch_one<NF, U, TAB, STD, true, true, false, 256>(k, st);
-    return launch_one<NF, U, TAB, STD, true, false, true, 256>(k, st);
+    if (flat && sumw) return launch_one<NF, U, TAB, STD, true, true, true, 256, 3, OUT>(k, st);
+    if (flat) return launch_one<NF, U, TAB, STD, true, true, false, 256, 3, OUT>(k, st);
+    return launch_one<NF, U, TAB, STD, true, false, true, 256, 3, OUT>(k, st);
 }
 
 template <int NF>
@@ -2277,6 +2353,45 @@ static int launch_fast_nf(const MergeK& k, const FastCfg& c, bool with_std, hipS
     }
 }
 
+// float32 outputs: what launch_fast_nf() above chooses in a build without the tuning matrix, with OUT_F32 stores (a tuning build refuses
+// variant > 0 for float32 calls). Instantiated for the frame counts of kF32Templated() only; the others stream through the run-time-N kernels.
+constexpr bool kF32Templated(int n_frames) { return n_frames == 7 || n_frames == 15; }
+// merge_u8_val3 with float32 outputs: the four-elements-per-lane map (16-byte stores) where the configuration has whole 256-element spans
+// and the call's alignment allows dword loads, else the pair map (8-byte stores)
+constexpr bool val3_quad_cfg(Val3Cfg c) { return c.pf == 1 && c.u % 2 == 0 && (c.map == 0 || c.map == 3); }
+constexpr int kVariantF32Pairs = 32;     // args->variant of a float32 call: the library default with the pair map forced (A/B of the store shape, tools/bench_merge_f32.py)
+template <int NF, bool FLAT, int CH>
+static int launch_val3_f32(const MergeK& k, bool quad_ok, hipStream_t st) {
+    constexpr Val3Cfg c = FLAT ? val3_flat_default(NF) : val3_default(NF);
+    if constexpr (val3_quad_cfg(c)) {
+        if (quad_ok) return launch_val3_cfg<NF, c.u, c.pf, c.map, FLAT, CH, OUT_F32, true>(k, st);
+    }
+    return launch_val3_cfg<NF, c.u, c.pf, c.map, FLAT, CH, OUT_F32, false>(k, st);
+}
+template <int NF>
+static int launch_fast_nf_f32(const MergeK& k, bool with_std, bool allow_quad, hipStream_t st) {
+    constexpr int O = OUT_F32;
+    bool quad_ok = allow_quad && aligned(k.out_val, 16) && (!k.has_flat || !k.flat_u8 || aligned(k.flat_u8, 4));
+    for (int i = 0; i < NF && quad_ok; ++i) quad_ok = aligned(static_cast<const uint8_t*>(k.frame[i]) + k.in_off, 4);
+    const bool extras = k.has_flat || k.out_sum_w;
+    if (with_std) {
+        if (use_fast_std_mono(k, true, false)) {
+            if (k.has_flat) return launch_one<NF, kUStd, TAB_PLAIN, true, true, true, false, 256, 1, O>(k, st);
+            return launch_one<NF, kUStd, TAB_PLAIN, true, true, false, false, 256, 1, O>(k, st);
+        }
+        if (extras) return launch_extras<NF, true, kUStd, TAB_PLAIN, O>(k, st);
+        return launch_one<NF, kUStd, TAB_PLAIN, true, true, false, false, 256, 3, O>(k, st);
+    }
+    if (use_val3_mono(k, false, false)) {
+        if (k.has_flat) return launch_val3_f32<NF, true, 1>(k, quad_ok, st);
+        return launch_val3_f32<NF, false, 1>(k, quad_ok, st);
+    }
+    if (use_val3_flat(k, false)) return launch_val3_f32<NF, true, 3>(k, quad_ok, st);
+    if (extras) return launch_extras<NF, false, kUVal, TAB_FUSED, O>(k, st);
+    if (!use_val3(k.variant, NF, false, false)) return launch_one<NF, kUVal, TAB_FUSED, false, true, false, false, 256, 3, O>(k, st);   // variant > 0
+    return launch_val3_f32<NF, false, 3>(k, quad_ok, st);
+}
+
 // elements per group of the configuration launch_fast_nf() will really use
 static int fast_group_elems(int n_frames, int variant, const FastCfg& c, bool with_std, bool extras, bool val3_flat) {
     if (val3_flat) return val3_unit_elems(val3_flat_default(n_frames));
@@ -2287,13 +2402,13 @@ static int fast_group_elems(int n_frames, int variant, const FastCfg& c, bool wi
     return c.u * static_cast<int>(kSub);
 }
 
-template <int C>
+template <int C, int OUT>
 static int launch_loop_c(const MergeK& k, bool with_std, hipStream_t st) {
     const bool flat = k.has_flat != 0, sumw = k.out_sum_w != nullptr;
     const int lds = (with_std ? 16 * 256 + 16 * 256 * C : 16 * 256 * C) + (flat ? 16 * 256 : 0);
     const unsigned grid = stream_grid(k.n_elems / static_cast<int>(kSub), 4, 8);
     if (describe_only(with_std ? "merge_u8_loop_std<C=%d,flat=%d,sum_w=%d>(N=%d)" : "merge_u8_loop<C=%d,flat=%d,sum_w=%d>(N=%d)", C, flat, sumw, k.n_frames)) return HM_OK;
-#define HM_LOOP(K, F, W) hipLaunchKernelGGL((K<C, F, W>), dim3(grid), dim3(256), lds, st, k)
+#define HM_LOOP(K, F, W) hipLaunchKernelGGL((K<C, F, W, OUT>), dim3(grid), dim3(256), lds, st, k)
     if (with_std) {
         if (flat && sumw) HM_LOOP(merge_u8_loop_std, true, true); else if (flat) HM_LOOP(merge_u8_loop_std, true, false);
         else if (sumw) HM_LOOP(merge_u8_loop_std, false, true); else HM_LOOP(merge_u8_loop_std, false, false);
@@ -2305,13 +2420,13 @@ static int launch_loop_c(const MergeK& k, bool with_std, hipStream_t st) {
     return launch_status();
 }
 
-template <int C>
+template <int C, int OUT>
 static int launch_f64_c(const MergeK& k, bool with_std, hipStream_t st) {
     const bool flat = k.has_flat != 0, sumw = k.out_sum_w != nullptr;
     const int lds = 16 * 256 * C + (flat ? 16 * 256 : 0);
     const unsigned grid = stream_grid(k.n_elems / static_cast<int>(kSub), 4, 8);
     if (describe_only(with_std ? "merge_f64_std<C=%d,flat=%d,sum_w=%d>(N=%d)" : "merge_f64_val<C=%d,flat=%d,sum_w=%d>(N=%d)", C, flat, sumw, k.n_frames)) return HM_OK;
-#define HM_F64(K, F, W) hipLaunchKernelGGL((K<C, F, W>), dim3(grid), dim3(256), lds, st, k)
+#define HM_F64(K, F, W) hipLaunchKernelGGL((K<C, F, W, OUT>), dim3(grid), dim3(256), lds, st, k)
     if (with_std) {
         if (flat && sumw) HM_F64(merge_f64_std, true, true); else if (flat) HM_F64(merge_f64_std, true, false);
         else if (sumw) HM_F64(merge_f64_std, false, true); else HM_F64(merge_f64_std, false, false);
@@ -2323,39 +2438,43 @@ static int launch_f64_c(const MergeK& k, bool with_std, hipStream_t st) {
     return launch_status();
 }
 
+template <int OUT>
 static int launch_f64(const MergeK& k, bool with_std, hipStream_t st) {
     switch (k.C) {
-        case 1: return launch_f64_c<1>(k, with_std, st);
-        case 2: return launch_f64_c<2>(k, with_std, st);
-        case 3: return launch_f64_c<3>(k, with_std, st);
-        default: return launch_f64_c<4>(k, with_std, st);
+        case 1: return launch_f64_c<1, OUT>(k, with_std, st);
+        case 2: return launch_f64_c<2, OUT>(k, with_std, st);
+        case 3: return launch_f64_c<3, OUT>(k, with_std, st);
+        default: return launch_f64_c<4, OUT>(k, with_std, st);
     }
 }
 
+template <int OUT>
 static int launch_loop(const MergeK& k, bool with_std, hipStream_t st) {
     switch (k.C) {
-        case 1: return launch_loop_c<1>(k, with_std, st);
-        case 2: return launch_loop_c<2>(k, with_std, st);
-        case 3: return launch_loop_c<3>(k, with_std, st);
-        default: return launch_loop_c<4>(k, with_std, st);
+        case 1: return launch_loop_c<1, OUT>(k, with_std, st);
+        case 2: return launch_loop_c<2, OUT>(k, with_std, st);
+        case 3: return launch_loop_c<3, OUT>(k, with_std, st);
+        default: return launch_loop_c<4, OUT>(k, with_std, st);
     }
 }
 
+template <int OUT>
 static int launch_generic(const MergeK& k, bool f64in, bool with_std, hipStream_t st) {
     const unsigned grid = stream_grid(k.n_elems, 256, 8);
     if (describe_only("merge_generic<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
-#define HM_GEN(F, S) hipLaunchKernelGGL((merge_generic<F, S>), dim3(grid), dim3(256), 0, st, k)
+#define HM_GEN(F, S) hipLaunchKernelGGL((merge_generic<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
     if (f64in) { if (with_std) HM_GEN(true, true); else HM_GEN(true, false); }
     else       { if (with_std) HM_GEN(false, true); else HM_GEN(false, false); }
 #undef HM_GEN
     return launch_status();
 }
 
+template <int OUT>
 static int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t st) {
     const int64_t chunks = (k.n_elems + 15) / 16;
     const unsigned grid = stream_grid(chunks, 256, 8);
     if (describe_only("merge_fixup_hot<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
-#define HM_FIX(F, S) hipLaunchKernelGGL((merge_fixup_hot<F, S>), dim3(grid), dim3(256), 0, st, k)
+#define HM_FIX(F, S) hipLaunchKernelGGL((merge_fixup_hot<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
     if (f64in) { if (with_std) HM_FIX(true, true); else HM_FIX(true, false); }
     else       { if (with_std) HM_FIX(false, true); else HM_FIX(false, false); }
 #undef HM_FIX
@@ -2364,6 +2483,7 @@ static int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t 
 
 // the queue path of the hot-pixel pass: zero the counters, scan the dark maps into the queue, patch the queued elements;
 // on overflow merge_patch_hot goes over the whole tile instead of the queue (a queue that was too small costs time, never correctness)
+template <int OUT>
 static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t* ws, size_t ws_bytes, hipStream_t st) {
     const size_t head = static_cast<size_t>(kHotQueueHeader) + 2u * hot_piece_slots(k.n_elems);     // counters + piece table, in words
     const size_t words = ws_bytes / 4 - head;
@@ -2382,8 +2502,8 @@ static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t
     // rounds at 3 resident per CU - 57-65 us for 35 000 queued elements, each round the same dependent chain of memory round trips.
     const int keep = patch_keep_bytes(f64in, k.n_frames, k.median_k);
     const void* fn;
-    if (f64in) fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<true, true>) : reinterpret_cast<const void*>(merge_patch_hot<true, false>);
-    else       fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<false, true>) : reinterpret_cast<const void*>(merge_patch_hot<false, false>);
+    if (f64in) fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<true, false, OUT>);
+    else       fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<false, false, OUT>);
     // (the query costs a few microseconds of host time: remembered per kernel, LDS size and device, under a mutex - hm_merge may be called
     // from several host threads)
     static struct { const void* fn; int keep, dev, per_cu; } seen[16];
@@ -2405,12 +2525,12 @@ static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t
         std::lock_guard<std::mutex> hold(seen_lock);
         if (n_seen < 16) { seen[n_seen].fn = fn; seen[n_seen].keep = keep; seen[n_seen].dev = dev; seen[n_seen].per_cu = per_cu; ++n_seen; }
     }
-    if (per_cu < 0) return launch_fixup(k, f64in, with_std, st);
+    if (per_cu < 0) return launch_fixup<OUT>(k, f64in, with_std, st);
     if (const int e = tune_env("HM_TUNE_PATCH_WG_PER_CU", 1, 16)) per_cu = e;
     const unsigned grid = stream_grid(k.n_elems, 256, per_cu);
     uint32_t bmax = 64;
     if (const int e = tune_env("HM_TUNE_PATCH_BMAX", 1, 64)) bmax = static_cast<uint32_t>(e);
-#define HM_PATCH(K, F, S) hipLaunchKernelGGL((K<F, S>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax)
+#define HM_PATCH(K, F, S) hipLaunchKernelGGL((K<F, S, OUT>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax)
 #define HM_PATCH4(K) { if (f64in) { if (with_std) HM_PATCH(K, true, true); else HM_PATCH(K, true, false); } \
                        else       { if (with_std) HM_PATCH(K, false, true); else HM_PATCH(K, false, false); } }
     HM_PATCH4(merge_patch_hot)
@@ -2428,7 +2548,8 @@ extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
     const bool s = g->stds != nullptr;
     const int64_t in_b = g->frames_f64 ? 8 : 1;
     int64_t per = N * (in_b + (s ? 8 : 0));
-    if (g->out_val) per += 8 * (1 + (s ? 1 : 0));
+    const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
+    if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
     if (g->flat_u8 || g->flat_f64) per += (g->flat_u8 ? 1 : 8) + ((s && g->flat_std) ? 8 : 0);
     if (g->darks_u8)                                       // every DISTINCT (map, threshold) is read once (scan_chunk_hotbits)
@@ -2461,6 +2582,7 @@ extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len)
     if (!buf || buf_len < 1) return HM_EINVAL;
     std::string names;
     hm::g_describe = &names;
+    hm::g_describe_f32 = false;                            // set by hm_merge once it has accepted a float32 call
     const int rc = hm_merge(g, nullptr);
     hm::g_describe = nullptr;
     snprintf(buf, static_cast<size_t>(buf_len), "%s", names.c_str());
@@ -2468,16 +2590,21 @@ extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len)
 }
 
 // struct_size values hm_merge accepts: the current layout and the two older ones of ABI version 1 (without the hot-pixel queue
-// workspace: 264 bytes; with it: 280 bytes) - the missing tail reads as zero (no workspace).
+// workspace: 264 bytes; with it: 280 bytes) - the missing tail reads as zero (no workspace). out_kind took the place of a pad word those
+// callers never promised to zero: for them it is cleared (float64 outputs).
 static bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
     if (!g) return false;
     const uint32_t sz = g->struct_size;
     if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return false;
     full = hm_merge_args{};
     memcpy(&full, g, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
+    if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;
     full.struct_size = sizeof(hm_merge_args);
     return true;
 }
+
+template <int OUT>
+static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, bool flat, bool hot, void* stream);
 
 extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
     using namespace hm;
@@ -2486,6 +2613,8 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
     const hm_merge_args* g = &full;
     const int N = g->n_frames, C = g->channels;
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
+    if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
+    const bool f32out = g->out_kind == HM_OUT_F32;
     if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
     if (g->rows == 0) return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;   // empty tile: nothing to do
     const bool f64in = g->frames_f64 != nullptr;
@@ -2529,8 +2658,14 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
         }
         if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
     }
-    if ((g->out_val && !aligned(g->out_val, 8)) || (g->out_std && !aligned(g->out_std, 8)) ||
+    const int out_align = f32out ? 4 : 8;
+    if ((g->out_val && !aligned(g->out_val, out_align)) || (g->out_std && !aligned(g->out_std, out_align)) ||
         (g->out_sum_w && !aligned(g->out_sum_w, 8))) return HM_EALIGN;
+    // float32 outputs exist for the one-launch kernels only: the chunked path keeps float64 running sums in out_val / out_std, the row-band
+    // loop below advances output pointers by float64 elements, and the variant matrix of a tuning build is float64 instantiations
+    if (f32out && (N > HM_MAX_FRAMES || g->variant <= -2 || (HM_TUNE_NF != 0 && g->variant > 0) ||
+                   g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
+    if (f32out) g_describe_f32 = true;
     // More frames than one launch takes (modules/exposure_series.py:334,372 have no limit): HM_MAX_FRAMES per launch with the running
     // sums in memory (hm_merge_chunk.hip). variant <= -2 forces that path with -variant frames per chunk (tests: any chunking gives the
     // bits of the one-launch kernels).
@@ -2565,6 +2700,17 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
             return HM_OK;
         }
     }
+    return f32out ? merge_one_launch<OUT_F32>(g, f64in, with_std, flat, hot, stream)
+                  : merge_one_launch<OUT_F64>(g, f64in, with_std, flat, hot, stream);
+}
+
+// One streaming launch (+ generic tail + hot-pixel pass) for validated arguments; OUT = element type of out_val / out_std.
+template <int OUT>
+static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
+    using namespace hm;
+    const int N = g->n_frames, C = g->channels;
+    const bool f32_pairs = OUT == OUT_F32 && g->variant == kVariantF32Pairs;      // float32 A/B: the default dispatch without the QUAD map
+    const int variant = f32_pairs ? 0 : g->variant;
     MergeK k{};
     for (int i = 0; i < N; ++i) {
         k.frame[i] = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
@@ -2582,7 +2728,7 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
     k.in_off = (g->row0 - g->buf_row0) * g->width * C;
     k.H = g->height; k.W = g->width; k.row0 = g->row0; k.buf_row0 = g->buf_row0; k.buf_rows = g->buf_rows;
     k.n_frames = N; k.C = C; k.median_k = hot ? g->median_k : 3; k.has_flat = flat ? 1 : 0;
-    k.variant = g->variant;
+    k.variant = variant;
     k.inv_t_inrange = 1;
     for (int i = 0; i < N; ++i) k.inv_t_inrange = k.inv_t_inrange && k.inv_t[i] >= 0x1p-300 && k.inv_t[i] <= 0x1p300;
     hipStream_t st = as_stream(stream);
@@ -2592,42 +2738,53 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
 
     // ---- streaming pass: fast kernel where eligible, generic kernel otherwise (dark maps are not read here)
     FastCfg cfg;
-    const int tune_variant = (HM_TUNE_NF != 0 && g->variant >= 10000) ? g->variant % 10000 : g->variant;   // W * 10000 + 7UPM (tuning builds)
+    const int tune_variant = (HM_TUNE_NF != 0 && variant >= 10000) ? variant % 10000 : variant;   // W * 10000 + 7UPM (tuning builds)
     if (tune_variant >= 7000 && tune_variant < 9000) {        // merge_u8_val3 / merge_u8_priv A/B variants (tuning builds)
         Val3Cfg vc;
         int pu = 0;
-        const bool ok = tune_variant < 8000 ? val3_variant(g->variant, N, vc) : priv_variant(g->variant, N, pu);
+        const bool ok = tune_variant < 8000 ? val3_variant(variant, N, vc) : priv_variant(variant, N, pu);
         if (!ok || with_std || flat || g->out_sum_w || f64in || C != 3) return HM_EINVAL;
         cfg = default_cfg(with_std);
-    } else if (!decode_variant(g->variant, with_std, cfg)) return HM_EINVAL;
-    bool fast = g->out_val && E < (int64_t{1} << 32) && g->variant >= 0;
-    const bool mono_val3 = use_val3_mono(k, with_std, f64in);
-    const bool mono_std = use_fast_std_mono(k, with_std, f64in);
+    } else if (!decode_variant(variant, with_std, cfg)) return HM_EINVAL;
+    bool fast = g->out_val && E < (int64_t{1} << 32) && variant >= 0;
+    // (float32 outputs: templated kernels for the frame counts of kF32Templated() only - build time; the others take the run-time-N kernels)
+    const bool templated = OUT == OUT_F64 || kF32Templated(N);
+    const bool mono_val3 = templated && use_val3_mono(k, with_std, f64in);
+    const bool mono_std = templated && use_fast_std_mono(k, with_std, f64in);
     // Templates up to kTemplatedN = 20 frames (round 4, late: 16 before). On 2048 x 4096 x 3 stacks the templated kernels beat the run-time-N
     // kernel at N = 17 (val-only 115 against 130 us, with std 790 against 880 us) and N = 20 (132 against 150, 985 against 1 025 us) and lose from
     // N = 24 (with std) / 32 (val-only) on, where their per-frame register arrays no longer fit (profiles/r04z_n32_templates_ab.log).
-    const bool loop_kernel = (f64in || N > kTemplatedN || C != 3) && !mono_val3 && !mono_std;   // run-time-N / any-C streaming kernel instead of the templates
+    const bool loop_kernel = (f64in || N > kTemplatedN || C != 3 || !templated) && !mono_val3 && !mono_std;   // run-time-N / any-C streaming kernel instead of the templates
     if (fast) {
         for (int i = 0; i < N && fast; ++i) {
             fast = f64in ? aligned(static_cast<const double*>(k.frame[i]) + k.in_off, 16)
                          : aligned(static_cast<const uint8_t*>(k.frame[i]) + k.in_off, 2);
             if (fast && with_std) fast = aligned(k.sd[i] + k.in_off, 16);
         }
-        fast = fast && aligned(k.out_val, 16) && (!k.out_std || aligned(k.out_std, 16)) &&
+        constexpr int pair_bytes = OUT == OUT_F32 ? 8 : 16;                  // one lane's two output elements
+        fast = fast && aligned(k.out_val, pair_bytes) && (!k.out_std || aligned(k.out_std, pair_bytes)) &&
                (!k.out_sum_w || aligned(k.out_sum_w, 16));
         if (fast && flat)
             fast = (k.flat_u8 ? aligned(k.flat_u8, 2) : aligned(k.flat_f64, 16)) && (!with_std || aligned(k.flat_std, 16));
     }
     int rc = HM_OK;
     if (!fast) {
-        rc = launch_generic(k, f64in, with_std, st);
+        rc = launch_generic<OUT>(k, f64in, with_std, st);
     } else {
         const int64_t grp = loop_kernel ? static_cast<int64_t>(kSub) : (mono_val3 ? val3_unit_elems(flat ? val3_flat_default(N) : val3_default(N))
-                                                                                                 : fast_group_elems(N, g->variant, cfg, with_std, flat || g->out_sum_w, use_val3_flat(k, with_std)));
+                                                                                                 : fast_group_elems(N, variant, cfg, with_std, flat || g->out_sum_w, use_val3_flat(k, with_std)));
         const int64_t body = (E / grp) * grp;
         if (body > 0) {
             MergeK kb = k;
             kb.n_elems = body;
+            if constexpr (OUT == OUT_F32) {
+                switch (loop_kernel ? 0 : N) {
+                    case 7: rc = launch_fast_nf_f32<7>(kb, with_std, !f32_pairs, st); break;
+                    case 15: rc = launch_fast_nf_f32<15>(kb, with_std, !f32_pairs, st); break;
+                    static_assert(kF32Templated(7) && kF32Templated(15) && !kF32Templated(8), "one case per float32-templated frame count");
+                    default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : launch_loop<OUT>(kb, with_std, st); break;
+                }
+            } else {
             switch (loop_kernel ? 0 : N) {
 #define HM_CASE(n) case n: rc = launch_fast_nf<n>(kb, cfg, with_std, st); break;
                 HM_CASE(1) HM_CASE(2) HM_CASE(3) HM_CASE(4) HM_CASE(5) HM_CASE(6) HM_CASE(7) HM_CASE(8)
@@ -2635,21 +2792,22 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
                 HM_CASE(17) HM_CASE(18) HM_CASE(19) HM_CASE(20)
                 static_assert(kTemplatedN == 20, "one HM_CASE per templated frame count");
 #undef HM_CASE
-                default: rc = f64in ? launch_f64(kb, with_std, st) : launch_loop(kb, with_std, st); break;   // run-time frame count
+                default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : launch_loop<OUT>(kb, with_std, st); break;   // run-time frame count
+            }
             }
             if (rc != HM_OK) return rc;
         }
         if (body < E) {                                    // tail: less than one group
             MergeK kt = k;
             kt.elem0 = body; kt.n_elems = E - body;
-            rc = launch_generic(kt, f64in, with_std, st);
+            rc = launch_generic<OUT>(kt, f64in, with_std, st);
         }
     }
     if (rc != HM_OK) return rc;
     // ---- hot-pixel fix-up pass (stream-ordered after the streaming pass: it overwrites the affected elements)
     if (hot) {
-        rc = hot_queue ? launch_hot_queue(k, f64in, with_std, static_cast<uint32_t*>(g->hot_workspace), g->hot_workspace_bytes, st)
-                   : launch_fixup(k, f64in, with_std, st);
+        rc = hot_queue ? launch_hot_queue<OUT>(k, f64in, with_std, static_cast<uint32_t*>(g->hot_workspace), g->hot_workspace_bytes, st)
+                   : launch_fixup<OUT>(k, f64in, with_std, st);
     }
     return rc;
 }

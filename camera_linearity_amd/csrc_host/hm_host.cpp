@@ -269,7 +269,8 @@ int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
     const int64_t E = g->rows * g->width * g->channels;
     const bool s = g->stds != nullptr;
     int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + (s ? 8 : 0));
-    if (g->out_val) per += 8 * (1 + (s ? 1 : 0));
+    const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;
+    if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
     if (g->flat_u8 || g->flat_f64) per += (g->flat_u8 ? 1 : 8) + ((s && g->flat_std) ? 8 : 0);
     if (g->darks_u8)
@@ -289,10 +290,14 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
     if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return HM_EINVAL;
     full = hm_merge_args{};
     std::memcpy(&full, g_in, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
+    if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;                  // the older layouts carried an unspecified pad word there
     const hm_merge_args* g = &full;
     const int N = g->n_frames, C = g->channels;
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
+    if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
+    const bool f32out = g->out_kind == HM_OUT_F32;
     if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    if (g->rows == 0) return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;   // empty tile: nothing to do (as the device build)
     const bool f64in = g->frames_f64 != nullptr;
     if (f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;
     if (!g->exposures || !g->icrf) return HM_EINVAL;
@@ -332,8 +337,12 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
         }
         if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
     }
-    if ((g->out_val && !aligned8(g->out_val)) || (g->out_std && !aligned8(g->out_std)) || (g->out_sum_w && !aligned8(g->out_sum_w)))
+    const auto out_aligned = [&](const void* q) { return f32out ? (reinterpret_cast<uintptr_t>(q) & 3u) == 0 : aligned8(q); };
+    if ((g->out_val && !out_aligned(g->out_val)) || (g->out_std && !out_aligned(g->out_std)) || (g->out_sum_w && !aligned8(g->out_sum_w)))
         return HM_EALIGN;
+    // the refusals of the device build (its chunked path and row-band loop are float64 only), so that a call means the same on both
+    if (f32out && g->rows > 0 && (N > HM_MAX_FRAMES || g->variant <= -2 ||
+                                  g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     return HM_OK;
 }
 
@@ -342,7 +351,8 @@ int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) {
     hm_merge_args full; bool hot = false;
     const int rc = merge_check(g, full, hot);
     if (rc == HM_OK && full.rows > 0)
-        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr, hot, full.n_frames);
+        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr, hot,
+                      full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
     else buf[0] = 0;
     return rc;
 }
@@ -365,6 +375,11 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
         for (int q = 0; q < 256 * C; ++q) wg_store[static_cast<size_t>(q)] = g->w_lut[q / C] * g->icrf[q];
     }
     const double* const wg_tab = wg_store.data();
+    // out_kind: the float64 result rounded once (to nearest even) at the store - static_cast<float> - into 4-byte elements
+    const bool f32out = g->out_kind == HM_OUT_F32;
+    const auto put = [f32out](double* base, int64_t e, double x) {
+        if (f32out) reinterpret_cast<float*>(base)[e] = static_cast<float>(x); else base[e] = x;
+    };
 #pragma omp parallel
     {
         std::vector<double> vv(static_cast<size_t>(N)), ss(static_cast<size_t>(N));
@@ -408,7 +423,7 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
                             const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
                             flat_field_math(F, 0.0, g->ff_mean[cb[j]], g->ff_std_mean[cb[j]], false, val, none);
                         }
-                        g->out_val[e] = val;
+                        put(g->out_val, e, val);
                     }
                 }
             }
@@ -452,7 +467,7 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
                     const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
                     flat_field_math(F, 0.0, g->ff_mean[c], g->ff_std_mean[c], false, val1, none);
                 }
-                g->out_val[e] = val1;
+                put(g->out_val, e, val1);
                 continue;
             }
             for (int i = 0; i < N; ++i) {
@@ -493,8 +508,8 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
                 const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
                 flat_field_math(F, STD ? g->flat_std[e] : 0.0, g->ff_mean[c], g->ff_std_mean[c], STD, val, sd);
             }
-            g->out_val[e] = val;
-            if constexpr (STD) g->out_std[e] = sd;
+            put(g->out_val, e, val);
+            if constexpr (STD) put(g->out_std, e, sd);
         }
     }
 }

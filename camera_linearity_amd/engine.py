@@ -303,7 +303,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
                flat: Optional[torch.Tensor] = None, flat_std: Optional[torch.Tensor] = None,
                ff_mean=None, ff_std_mean=None, want_sum_w: bool = False, want_val: bool = True,
                height: Optional[int] = None, row0: int = 0, rows: Optional[int] = None, buf_row0: int = 0,
-               variant: int = 0, hot_queue: bool = True) -> MergePlan:
+               variant: int = 0, hot_queue: bool = True, out_dtype: torch.dtype = torch.float64) -> MergePlan:
     """Build the launch descriptor for one fused merge (modules/exposure_series.py:317-419).
 
     frames : N tensors (buf_rows, W, C), all uint8 DNs or all float64 values, ascending exposure.
@@ -315,7 +315,13 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
              False = the workspace-free path (one hot element per wave at a time; sparse maps only).
     flat, flat_std : flat-field value (uint8 DN or float64) and float64 uncertainty covering the
              OUTPUT rows; ff_mean / ff_std_mean are the C ROI means (host floats).
+    out_dtype : torch.float64 (default) or torch.float32 - the element type of the `val` / `std` outputs (hm_merge_args.out_kind).
+             All arithmetic is float64 either way; float32 rounds the float64 result once, to nearest even, at the kernel's store, so
+             the outputs equal the float64 outputs cast to float32 - with half the output bytes. `sum_w` stays float64. More than
+             HM_MAX_FRAMES frames (and a forced chunking, variant <= -2) exist for float64 only: NotImplementedError.
     """
+    if out_dtype not in (_F64, torch.float32):
+        raise TypeError(f"out_dtype must be torch.float64 or torch.float32, got {out_dtype}")
     n = len(frames)
     if n == 0:
         raise ValueError("merge needs at least one frame")
@@ -368,6 +374,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     a = nat.MergeArgs()
     a.struct_size = C.sizeof(nat.MergeArgs)
     a.n_frames, a.channels, a.variant = n, Cc, int(variant)
+    a.out_kind = nat.HM_OUT_F32 if out_dtype == torch.float32 else nat.HM_OUT_F64
     a.height, a.width, a.row0, a.rows, a.buf_row0, a.buf_rows = height, W, int(row0), rows, int(buf_row0), buf_rows
     fptrs = _ptr_array(fr)
     if dt == _U8:
@@ -437,10 +444,10 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
             keep.append(flat_std)
     outputs = {}
     if want_val:
-        outputs["val"] = torch.empty(out_shape, dtype=_F64, device=dev)
+        outputs["val"] = torch.empty(out_shape, dtype=out_dtype, device=dev)
         a.out_val = outputs["val"].data_ptr()
         if with_std:
-            outputs["std"] = torch.empty(out_shape, dtype=_F64, device=dev)
+            outputs["std"] = torch.empty(out_shape, dtype=out_dtype, device=dev)
             a.out_std = outputs["std"].data_ptr()
     if want_sum_w:
         outputs["sum_w"] = torch.empty(out_shape, dtype=_F64, device=dev)
@@ -452,7 +459,10 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         ws = torch.empty(fw, dtype=_U8, device=dev)
         a.frames_workspace, a.frames_workspace_bytes = ws.data_ptr(), fw
         keep.append(ws)
-    return MergePlan(a, keep, dev, outputs)
+    plan = MergePlan(a, keep, dev, outputs)
+    if out_dtype == torch.float32:
+        plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs raises here, not at the first launch
+    return plan
 
 
 def merge(frames, exposures, icrf, icrf_diff=None, stds=None, **kw) -> dict:

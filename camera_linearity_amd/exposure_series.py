@@ -239,9 +239,10 @@ class ExposureSeries(object):
 
     def _compute_HDR_image_set(self, list_of_dark_fields, sum_of_weights, square_sum_of_weights, ICRF, ICRF_diff,
                                flat_set: Optional[ImageSet] = None, dark_threshold: Optional[float] = None,
-                               use_std: Optional[bool] = None):
+                               use_std: Optional[bool] = None, out_dtype=None):
         """exposure_series.py:347-397. The fused kernel recomputes the sum of weights in registers, so the
-        two precalculated arrays are accepted for signature compatibility and not read."""
+        two precalculated arrays are accepted for signature compatibility and not read.
+        out_dtype: None / torch.float64, or torch.float32 - the merged measurand then holds float32 arrays (engine.plan_merge)."""
         from . import engine
         eng = self._eng()
         sets = self.input_image_sets
@@ -277,7 +278,7 @@ class ExposureSeries(object):
                 kw.update(flat_std=fstd, ff_std_mean=_roi_means(flat_set, eng, fstd, (x0, x1, y0, y1), "std"))
         exposures = [s.features["exposure"] for s in sets]
         out = eng.merge(frames, exposures, ICRF, ICRF_diff if use_std else None, stds, darks=darks, dark_min=mins,
-                        median_k=gs.MEDIAN_FILTER_KERNEL_SIZE, **kw)
+                        median_k=gs.MEDIAN_FILTER_KERNEL_SIZE, out_dtype=torch.float64 if out_dtype is None else out_dtype, **kw)
         hdr = type(sets[0].measurand)(out["val"], out.get("std"))
         hdr_set = ImageSet(file_path=sets[0].get_file_path_without_exposure(), features=dict(sets[0].features) if sets[0].features else None,
                            measurand=hdr)
@@ -285,8 +286,10 @@ class ExposureSeries(object):
         return hdr_set
 
     def process_HDR_image(self, ICRF=None, ICRF_diff=None, dark_list: Optional[List[ImageSet]] = None,
-                          flat_list: Optional[List[ImageSet]] = None, use_std: Optional[bool] = None):
+                          flat_list: Optional[List[ImageSet]] = None, use_std: Optional[bool] = None, out_dtype=None):
         """exposure_series.py:399-419: merge the input images into self.merged_image_set.
+        `out_dtype=torch.float32` (an addition; None = float64) stores the merged value / std images as float32: the same float64
+        arithmetic, rounded once at the kernel's store - what ImageSet.save_32bit then writes.
 
         Defaults mirror the reference: `ICRF=None` reads settings.ICRF_CALIBRATED_FILE (:406-407; deviation E - the table is
         read as ONE (BITS, C) array and the derivative is formed with the reference's gradient convention), `dark_list=None`
@@ -307,7 +310,7 @@ class ExposureSeries(object):
             flat_list = ImageSet.multiple_from_path(Path(gs.DEFAULT_FLAT_PATH), use_cupy=self.use_cupy)
         flat_set = self.input_image_sets[0].get_flat_field(flat_list) if flat_list else None
         self.merged_image_set = self._compute_HDR_image_set(dark_list, None, None, ICRF, ICRF_diff, flat_set=flat_set,
-                                                            use_std=use_std)
+                                                            use_std=use_std, out_dtype=out_dtype)
 
     # ---- linearity statistics (exposure_series.py:421-476; "next" row f-1)
     def process_linearity(self, ICRF, linearity_limit: Optional[int] = None, use_std: Optional[bool] = False):

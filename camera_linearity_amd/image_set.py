@@ -322,9 +322,29 @@ class ImageSet(object):
         else:
             for c in range(val.shape[-1]):
                 name = gs.CH_STR.get(c, str(c))
-                tiff_io.imwrite(base + acq_suffix.replace(".tif", f" {name}.tif"), val[:, :, c])
+                tiff_io.imwrite(base + acq_suffix.replace(".tif", f" {name}.tif"), val[:, :, c].astype(np.float64, copy=False))
                 if std is not None:
-                    tiff_io.imwrite(base + std_suffix.replace(".tif", f" {name}.tif"), std[:, :, c])
+                    tiff_io.imwrite(base + std_suffix.replace(".tif", f" {name}.tif"), std[:, :, c].astype(np.float64, copy=False))
+
+    def save_32bit(self, save_path: Optional[Path] = None, is_HDR: Optional[bool] = False, separate_channels: Optional[bool] = False):
+        """float32 TIFFs (an addition: what a merge with out_dtype=torch.float32 produces, and what HDR tools exchange): save_64bit's
+        naming and suffixes under '32bit/', written uncompressed by the host tiff_io.imwrite (a float32 image is stored bit for bit;
+        a float64 one is rounded to float32 here). There is no device-encode form: tiff_io.imwrite_device does not take float32."""
+        file_path = self.path.parent.joinpath("32bit", self.path.name) if save_path is None else Path(save_path)
+        file_path.parent.mkdir(parents=True, exist_ok=True)
+        base = str(file_path).removesuffix(".tif")
+        acq_suffix, std_suffix = (" HDR.tif", " HDR STD.tif") if is_HDR else (".tif", " STD.tif")
+        val, std = self.host_arrays()
+        if not separate_channels:
+            tiff_io.imwrite(base + acq_suffix, val.astype(np.float32, copy=False))
+            if std is not None:
+                tiff_io.imwrite(base + std_suffix, std.astype(np.float32, copy=False))
+        else:
+            for c in range(val.shape[-1]):
+                name = gs.CH_STR.get(c, str(c))
+                tiff_io.imwrite(base + acq_suffix.replace(".tif", f" {name}.tif"), val[:, :, c].astype(np.float32, copy=False))
+                if std is not None:
+                    tiff_io.imwrite(base + std_suffix.replace(".tif", f" {name}.tif"), std[:, :, c].astype(np.float32, copy=False))
 
     def save_8bit(self, save_path: Optional[Path] = None, force_8_bit: Optional[bool] = False,
                   device_encode: Optional[bool] = False, compression: int = 1):

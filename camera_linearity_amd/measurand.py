@@ -236,14 +236,20 @@ class HipMeasurand(AbstractMeasurand):
         v = self._tv()
         return v if v.dtype == _F64 else v.to(_F64)
 
+    def _s64(self):
+        """The std tensor as float64, or None. A float32 Measurand (a merge with out_dtype=torch.float32) is storage: wherever a
+        method upcasts `val` for a float64 kernel (_f64), `std` is upcast the same way."""
+        s = self._std
+        return s if s is None or s.dtype == _F64 else s.to(_F64)
+
     def _binary(self, other, op):
         from ._native import HM_OP_ADD  # noqa: F401  (fail early and loudly without the library)
         normalized_other, use_std = self._normalize_input(other)
         x1, x2 = self._f64(), normalized_other._f64()
         if not is_broadcastable(x1.shape, x2.shape):
             raise ValueError("Measurands are not broadcastable.")
-        s1 = self._std if use_std else None
-        s2 = normalized_other._std if use_std else None
+        s1 = self._s64() if use_std else None
+        s2 = normalized_other._s64() if use_std else None
         if x2.device != x1.device:
             x2 = x2.to(x1.device)
             s2 = None if s2 is None else s2.to(x1.device)
@@ -275,12 +281,12 @@ class HipMeasurand(AbstractMeasurand):
         if isinstance(other, (int, float)) and not isinstance(other, bool):
             # plain scalar exponent (S ** 2, ** (1/2) of the merge loop): the propagation formula of measurand.py:236-239 with
             # s2 = 0, value and derivative without pow() where the exponent allows (hm_pow_scalar)
-            val, std = self._eng().pow_scalar(self._f64(), self._std, float(other))
+            val, std = self._eng().pow_scalar(self._f64(), self._s64(), float(other))
             return self.__class__(val, std)
         return self._binary(other, HM_OP_POW)
 
     def _unary(self, op):
-        val, std = self._eng().elementwise_unary(op, self._f64(), self._std)
+        val, std = self._eng().elementwise_unary(op, self._f64(), self._s64())
         return self.__class__(val, std)
 
     def __neg__(self):
@@ -347,7 +353,7 @@ class HipMeasurand(AbstractMeasurand):
             if map._std is None:
                 raise ValueError("flat field needs a std image to propagate uncertainty")
             std_means = eng.roi_mean(map._std, x0, x1, y0, y1).cpu().numpy()
-        val, std = eng.normalize_by_map(self._f64(), self._std, fval, map._std, means, std_means)
+        val, std = eng.normalize_by_map(self._f64(), self._s64(), fval, map._s64(), means, std_means)
         return self.__class__(val, std)
 
     # ---------------------------------------------------------------- "next" rows: every branch below is one HIP kernel of
@@ -357,7 +363,7 @@ class HipMeasurand(AbstractMeasurand):
         if dims is None:
             raise TypeError("extract() needs the indices to take (dims); the reference's lib.take(val, None, axis) raises too")
         target = [dims] if type(dims) is int else list(dims)
-        value, std = self._eng().take_axis(self._f64(), self._std, target, axis)
+        value, std = self._eng().take_axis(self._f64(), self._s64(), target, axis)
         return self.__class__(value, std)
 
     def apply_thresholds(self, lower: Optional[List] = None, upper: Optional[List] = None):
@@ -374,8 +380,8 @@ class HipMeasurand(AbstractMeasurand):
         if n > 32:
             raise NotImplementedError("hm_apply_thresholds supports up to 32 channels on the last axis")
         value = value.contiguous()
-        if self._std is not None and not self._std.is_contiguous():
-            self._std = self._std.contiguous()
+        if self._std is not None and (self._std.dtype != _F64 or not self._std.is_contiguous()):
+            self._std = self._s64().contiguous()
         self._eng().apply_thresholds_(value, self._std, lo_l, hi_l)          # hm_apply_thresholds, in place
         self.val = value
 
@@ -384,14 +390,14 @@ class HipMeasurand(AbstractMeasurand):
         values = self._f64()
         self._need_resident(values, "compute_dimension_statistics")
         if axis is None:                                                         # statistics over every element: one "channel"
-            st = self._eng().channel_statistics(values.reshape(-1, 1), None if self._std is None else self._std.reshape(-1, 1))
+            st = self._eng().channel_statistics(values.reshape(-1, 1), None if self._std is None else self._s64().reshape(-1, 1))
             return {k_: (None if v is None else self._export(v.reshape(()))) for k_, v in st.items()}
         all_but_last = values.dim() >= 2 and \
             sorted(a % values.dim() for a in ((axis,) if isinstance(axis, int) else tuple(axis))) == list(range(values.dim() - 1))
         if all_but_last and values.shape[-1] <= 4:
-            st = self._eng().channel_statistics(values, self._std)                  # hm_channel_statistics
+            st = self._eng().channel_statistics(values, self._s64())                # hm_channel_statistics
         else:
-            st = self._eng().axis_statistics(values, self._std, axis)               # hm_axis_statistics: any other axis / axis tuple
+            st = self._eng().axis_statistics(values, self._s64(), axis)             # hm_axis_statistics: any other axis / axis tuple
         return {k_: self._export(v) for k_, v in st.items()}
 
     def compute_kernel_density_estimate(self, data_points: int, included_range=None, channels=None, use_std: bool = False):
@@ -408,7 +414,7 @@ class HipMeasurand(AbstractMeasurand):
             raise TypeError("'NoneType' object is not subscriptable")          # self.std[..., c], measurand.py:742
         vd = self._f64()
         self._need_resident(vd, "compute_kernel_density_estimate")
-        return self._eng().kernel_density_estimate(vd, self._std if use_std else None, data_points, included_range, channels)
+        return self._eng().kernel_density_estimate(vd, self._s64() if use_std else None, data_points, included_range, channels)
 
     def compute_channel_histogram(self, bins: int, included_range=None, channels=None, use_std: bool = False):
         """modules/measurand.py:430-469: np.histogram per channel - hm_channel_histogram on the device (per-workgroup
@@ -419,7 +425,7 @@ class HipMeasurand(AbstractMeasurand):
         self._need_resident(vd, "compute_channel_histogram")
         if vd.shape[-1] > 4 or bins * vd.shape[-1] > 8192:
             raise NotImplementedError("hm_channel_histogram supports up to 4 channels and bins * channels <= 8192")
-        return self._eng().channel_histogram(vd, self._std if use_std else None, bins, included_range, channels)
+        return self._eng().channel_histogram(vd, self._s64() if use_std else None, bins, included_range, channels)
 
     @staticmethod
     def compute_difference(x: "HipMeasurand", y: "HipMeasurand", multiplier: float):
@@ -429,7 +435,7 @@ class HipMeasurand(AbstractMeasurand):
         x._need_resident(xv, "compute_difference")
         if not is_broadcastable(xv.shape, yv.shape):
             raise ValueError("Measurands are not broadcastable.")
-        ad, ads, rd, rds = x._eng().compute_difference(xv, x._std, yv, y._std, multiplier)   # hm_compute_difference(_bcast)
+        ad, ads, rd, rds = x._eng().compute_difference(xv, x._s64(), yv, y._s64(), multiplier)   # hm_compute_difference(_bcast)
         return cls(ad, ads), cls(rd, rds)
 
     @staticmethod
@@ -439,7 +445,7 @@ class HipMeasurand(AbstractMeasurand):
         x0._need_resident(x0._f64(), "interpolate")
         if not is_broadcastable(x0.shape, x1.shape):
             raise ValueError("Measurands are not broadcastable.")
-        res, res_std = x0._eng().interpolate(x0._f64(), x0._std, x1._f64(), x1._std, y0, y1, y)   # hm_interpolate(_bcast)
+        res, res_std = x0._eng().interpolate(x0._f64(), x0._s64(), x1._f64(), x1._s64(), y0, y1, y)   # hm_interpolate(_bcast)
         return cls(res, res_std)
 
 

@@ -72,7 +72,8 @@ def merge_row_tile(frames_host: Sequence[np.ndarray], exposures, icrf, icrf_diff
     they are staged in pinned buffers and copied with asynchronous H2D copies on the current stream, the fused kernel is
     launched behind them, and the result comes back through pinned buffers with asynchronous D2H copies (one
     synchronisation at the end). Returns (row0, row1, val, std) with host arrays. `tile` overrides the (row0, row1) that
-    row_tile_bounds() gives this rank (a rank that owns several tiles calls once per tile)."""
+    row_tile_bounds() gives this rank (a rank that owns several tiles calls once per tile).
+    The result is float64: the float32 outputs of engine.plan_merge(out_dtype=...) are not offered on this path."""
     from . import engine
     H = frames_host[0].shape[0]
     row_elems = int(np.prod(frames_host[0].shape[1:], dtype=np.int64))           # W * C: odd -> even tile starts and halo (halo_bounds)
@@ -119,7 +120,7 @@ class SharedHostImage:
     group): the name travels by broadcast_object_list and a MIN-reduce agrees that every rank mapped it - if any rank could not
     (no /dev/shm, not enough room in it), open() returns None on ALL ranks and the caller falls back to gather_tiles. The
     creator unlinks the name as soon as everyone is attached, so nothing is left in /dev/shm if a rank dies later (the pages
-    live until the last mapping goes)."""
+    live until the last mapping goes). The image is float64 only (a merge with float32 outputs has no shared-memory form)."""
 
     DIR = "/dev/shm"
 
@@ -219,7 +220,8 @@ class RowTileSet:
     stack cut into 8 tiles of 1024 rows). `launch()` enqueues one fused merge per tile; `download()` brings the results
     back through pinned buffers with asynchronous D2H copies on a side stream (tile k's copy overlaps tile k+1's);
     `assemble()` puts the tiles of all ranks into ONE host image on `dst`: a shared-memory image every rank copies its own rows
-    into (SharedHostImage), or - fallback - tensor sends over the CPU (gloo) group. There is no GPU<->GPU traffic on this path."""
+    into (SharedHostImage), or - fallback - tensor sends over the CPU (gloo) group. There is no GPU<->GPU traffic on this path.
+    The tiles, their staging and the assembled image are float64: add_tile refuses out_dtype=torch.float32."""
 
     def __init__(self, height: int, n_tiles: int, rank: int = 0, world_size: int = 1, median_k: int = 0, row_elems: Optional[int] = None):
         """row_elems = W * C (optional): lets input_rows() keep a tile's first element at an even offset for odd W * C (halo_bounds)."""
@@ -240,6 +242,8 @@ class RowTileSet:
     def add_tile(self, tile: int, frames, exposures, icrf, icrf_diff=None, stds=None, **kw):
         """frames / stds / darks: device tensors covering input_rows(tile); flat / flat_std cover the tile's own rows."""
         from . import engine
+        if kw.get("out_dtype", torch.float64) != torch.float64:
+            raise TypeError("RowTileSet assembles float64 images: out_dtype=torch.float32 is not supported here")
         r0, r1 = self.bounds[tile]
         b0, _ = self.input_rows(tile)
         self.plans[tile] = engine.plan_merge(frames, exposures, icrf, icrf_diff, stds, height=self.height, row0=r0, rows=r1 - r0,

@@ -29,7 +29,9 @@ class _Slot:
 
 class MergePipeline:
     def __init__(self, n_frames: int, height: int, width: int, exposures: Sequence[float], icrf, icrf_diff=None,
-                 channels: int = 3, with_std: bool = False, device=None, depth: int = 2):
+                 channels: int = 3, with_std: bool = False, device=None, depth: int = 2, out_dtype: torch.dtype = torch.float64):
+        """out_dtype: torch.float64 or torch.float32 - the plans' output type (engine.plan_merge) and that of the pinned result staging:
+        float32 halves the device-to-host copy, which is what bounds a stream of val-only merges."""
         if depth < 2:
             raise ValueError("depth must be at least 2 (one slot in flight while the next is filled)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -46,9 +48,9 @@ class MergePipeline:
             s.h_stds = [torch.empty(self.shape, dtype=torch.float64, pin_memory=True) for _ in range(n_frames)] if with_std else None
             s.d_frames = [torch.empty(self.shape, dtype=torch.uint8, device=self.device) for _ in range(n_frames)]
             s.d_stds = [torch.empty(self.shape, dtype=torch.float64, device=self.device) for _ in range(n_frames)] if with_std else None
-            s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if with_std else None, s.d_stds)
-            s.h_val = torch.empty(self.shape, dtype=torch.float64, pin_memory=True)
-            s.h_std = torch.empty(self.shape, dtype=torch.float64, pin_memory=True) if with_std else None
+            s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if with_std else None, s.d_stds, out_dtype=out_dtype)
+            s.h_val = torch.empty(self.shape, dtype=out_dtype, pin_memory=True)
+            s.h_std = torch.empty(self.shape, dtype=out_dtype, pin_memory=True) if with_std else None
             s.ev_h2d = torch.cuda.Event()
             s.ev_run = torch.cuda.Event()
             s.ev_d2h = torch.cuda.Event()

@@ -52,7 +52,7 @@ enum {
     HM_OK = 0,
     HM_EINVAL = -1,        /* bad argument (null pointer, non-positive size, bad enum)        */
     HM_EUNSUPPORTED = -2,  /* valid request this build cannot serve (C > 4; N > HM_MAX_FRAMES without frames_workspace / out_sum_w) */
-    HM_EALIGN = -3,        /* a float64 buffer is not 8-byte aligned                           */
+    HM_EALIGN = -3,        /* a float64 buffer is not 8-byte aligned (a float32 output: not 4-byte aligned) */
     HM_ELAUNCH = -4,       /* the HIP runtime rejected the launch (hipGetLastError != success) */
     HM_ENODEVICE = -5,     /* no usable gfx950 device                                          */
     HM_ESHAPE = -6         /* geometry inconsistent (tile outside image, halo too small, ...)  */
@@ -124,7 +124,9 @@ typedef struct hm_merge_args {
     int32_t  n_frames;            /* N >= 1, ascending exposure (N > HM_MAX_FRAMES: see frames_workspace) */
     int32_t  channels;            /* C, 1..HM_MAX_CHANNELS                                          */
     int32_t  variant;             /* 0 = library default; >0 selects a tuning variant (tools/tune_merge.py), -1 forces the generic kernel,
-                                     <= -2 forces the chunked path with -variant frames per launch (tests) */
+                                     <= -2 forces the chunked path with -variant frames per launch (tests);
+                                     32 with out_kind = HM_OUT_F32: the default dispatch with merge_u8_val3's pair stores forced (A/B
+                                     of the float32 store shape, tools/bench_merge_f32.py) */
     int64_t  height;              /* H of the full image                                            */
     int64_t  width;               /* W                                                              */
     int64_t  row0, rows;          /* output rows of this call                                       */
@@ -133,7 +135,13 @@ typedef struct hm_merge_args {
                                      (row0 - buf_row0) * W * C elements into every frame buffer, at an EVEN offset - and float64
                                      frames / stds / outputs / flat buffers 16-byte aligned there; otherwise the call runs in the
                                      one-element-per-thread generic kernel: same bits, 3-4 x slower. Only an odd W * C with an odd
-                                     number of halo rows above the tile breaks this: give such a tile one more row above.)          */
+                                     number of halo rows above the tile breaks this: give such a tile one more row above.
+                                     With out_kind = HM_OUT_F32 the same rule holds with float32 out_val / out_std 8-byte aligned
+                                     there - the streaming kernels store element pairs, 8 bytes per lane; float32 outputs that are
+                                     only 4-byte aligned run in the generic kernel. out_sum_w is float64 and keeps its 16 bytes.
+                                     The val-only kernel merge_u8_val3 stores FOUR float32 elements per lane where it can: uint8
+                                     frames / flat field 4-byte aligned and out_val 16-byte aligned at the first element; calls that
+                                     only meet the pair rule run the same kernel with pair stores.)                                 */
 
     const uint8_t* const* frames_u8;   /* [host] N device pointers to uint8 DN frames, or NULL       */
     const double*  const* frames_f64;  /* [host] N device pointers to float64 value frames, or NULL  */
@@ -149,7 +157,13 @@ typedef struct hm_merge_args {
     const uint8_t* const* darks_u8;    /* [host] N device pointers (NULL entries = no filter), or NULL */
     const int32_t* dark_min_dn;        /* [host] N thresholds in DN (1..256)                         */
     int32_t  median_k;            /* odd kernel size (gs.MEDIAN_FILTER_KERNEL_SIZE), 3..7           */
-    int32_t  _pad0;
+    int32_t  out_kind;            /* HM_OUT_F64 (0) or HM_OUT_F32: element type of out_val / out_std. Read only when struct_size ==
+                                     sizeof(hm_merge_args): the 264- and 280-byte layouts always mean float64. Other values: HM_EINVAL.
+                                     All arithmetic is float64 either way; HM_OUT_F32 rounds the float64 result once, to nearest even,
+                                     at the store ((float)x) and writes 4-byte elements: out_val / out_std are then `float` arrays, 4-byte
+                                     aligned. HM_EUNSUPPORTED with HM_OUT_F32, before any launch: n_frames > HM_MAX_FRAMES or variant <= -2
+                                     (the chunked path keeps float64 running sums in out_val / out_std) and a tile of 2^32 elements
+                                     or more.                                                                                       */
 
     /* flat-field epilogue (all NULL = off)                                                          */
     const uint8_t* flat_u8;       /* flat value as DN (value = DN/255), or                          */
@@ -158,9 +172,9 @@ typedef struct hm_merge_args {
     double ff_mean[HM_MAX_CHANNELS];     /* per-channel ROI mean of flat value  (measurand.py:582)  */
     double ff_std_mean[HM_MAX_CHANNELS]; /* per-channel ROI mean of flat std    (measurand.py:583)  */
 
-    double* out_val;              /* rows x W x C float64, or NULL (sum-of-weights only)            */
-    double* out_std;              /* rows x W x C float64; required iff stds != NULL                */
-    double* out_sum_w;            /* optional S (rows x W x C), NULL to skip                        */
+    double* out_val;              /* rows x W x C float64 (float with HM_OUT_F32), or NULL (sum-of-weights only) */
+    double* out_std;              /* rows x W x C float64 (float with HM_OUT_F32); required iff stds != NULL */
+    double* out_sum_w;            /* optional S (rows x W x C), float64 in both kinds, NULL to skip */
 
     /* hot-pixel queue (optional; used when darks_u8 is set). With a workspace the dark maps are scanned into a queue of hot
      * element indices and a balanced second kernel patches one queued element per lane - its cost follows the number of
@@ -180,6 +194,7 @@ typedef struct hm_merge_args {
     size_t   frames_workspace_bytes;
 } hm_merge_args;
 
+enum { HM_OUT_F64 = 0, HM_OUT_F32 = 1 };   /* hm_merge_args.out_kind */
 int hm_merge(const hm_merge_args* args /*[host]*/, void* stream);
 /* Recommended / smallest accepted size of hm_merge_args.hot_workspace for a call with n_elems = rows * W * C output elements
  * (counters + a table of 8 bytes per 65 536 elements + the queue: a quarter of the elements / one entry). */
@@ -190,10 +205,11 @@ size_t hm_merge_hot_workspace_min_bytes(int64_t n_elems);
 size_t hm_merge_frames_workspace_bytes(int n_frames, int64_t n_elems, int has_out_sum_w);
 
 /* Algorithmic HBM bytes one hm_merge call moves: every input byte once, every output
- * byte once, LUTs excluded. Used by bench.py for roofline.achieved. */
+ * byte once (4 bytes per out_val / out_std element with HM_OUT_F32), LUTs excluded. Used by bench.py for roofline.achieved. */
 int64_t hm_merge_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
 /* The kernels hm_merge() would launch for these arguments, in launch order, as text ("merge_u8_val3<N=7,...> +
- * merge_fixup_hot<...>"): the same dispatch code runs with launching switched off. Same status codes as hm_merge. */
+ * merge_fixup_hot<...>"): the same dispatch code runs with launching switched off. Same status codes as hm_merge.
+ * With HM_OUT_F32 every listed kernel that stores val / std carries "out=f32" in its name. */
 int hm_merge_describe(const hm_merge_args* args, char* buf, int buf_len);
 
 /* ------------------------------------------------------------------------------------------
