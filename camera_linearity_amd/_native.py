@@ -77,6 +77,10 @@ _SIGNATURES = {
     "hm_merge_frames_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_merge_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
     "hm_merge_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_char_p, C.c_int]),
+    # the merge with its stds from a (256, C) per-DN table in device memory (buf: a ctypes string buffer, passed as its address)
+    "hm_merge_std_table": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p]),
+    "hm_merge_std_table_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int]),
+    "hm_merge_std_table_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
     "hm_hot_pixel_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,

@@ -92,16 +92,18 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
     return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
 }
 
-template <typename T>
-__device__ __noinline__ T wave_median(const T* __restrict__ buf, int64_t H, int64_t W, int C,
-                                      int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
+// wave_median_of(): the same over any element accessor `at(index) -> double` (held by value: the function is not inlined), index =
+// (buffer row * W + column) * C + c; the merge's per-DN std table maps the neighbourhood through it before the median is taken.
+template <typename At>
+__device__ __noinline__ double wave_median_of(At at, int64_t H, int64_t W, int C,
+                                              int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
     const int lane = threadIdx.x & 63;
     const int n = k * k, r = k / 2, m = n / 2;
     const bool valid = lane < n;
     const int p = valid ? lane : 0;
     const int64_t yy = reflect_index(row + (p / k - r), H) - buf_row0;
     const int64_t xx = reflect_index(col + (p % k - r), W);
-    const double v = static_cast<double>(buf[(yy * W + xx) * C + c]);   // uint8 -> double: exact, order-preserving
+    const double v = at((yy * W + xx) * C + c);
     int less = 0, leq = 0;
     for (int q = 0; q < n; ++q) {
         const double u = readlane_f64(v, q);
@@ -110,7 +112,17 @@ __device__ __noinline__ T wave_median(const T* __restrict__ buf, int64_t H, int6
     }
     const unsigned long long is_med = __ballot(valid && less <= m && m < leq);
     const int src = __ffsll(static_cast<long long>(is_med)) - 1;        // non-empty for totally ordered input
-    return static_cast<T>(readlane_f64(v, src < 0 ? 0 : src));
+    return readlane_f64(v, src < 0 ? 0 : src);
+}
+template <typename T>
+struct PlainAt {
+    const T* buf;
+    __device__ __forceinline__ double operator()(int64_t i) const { return static_cast<double>(buf[i]); }   // uint8 -> double: exact, order-preserving
+};
+template <typename T>
+__device__ __forceinline__ T wave_median(const T* __restrict__ buf, int64_t H, int64_t W, int C,
+                                         int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
+    return static_cast<T>(wave_median_of(PlainAt<T>{buf}, H, W, C, buf_row0, row, col, c, k));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -144,9 +156,10 @@ __device__ __forceinline__ typename MedianKey<T>::type median9(typename MedianKe
     return p[4];
 }
 
-template <typename T>
-__device__ __forceinline__ T lane_median(const T* __restrict__ buf, int64_t H, int64_t W, int C,
-                                         int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
+// lane_median_of<T>(): over an element accessor `at(index) -> MedianKey<T>::type`, index = (buffer row * W + column) * C + c.
+template <typename T, typename At>
+__device__ __forceinline__ typename MedianKey<T>::type lane_median_of(At at, int64_t H, int64_t W, int C,
+                                                                      int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
     using K = MedianKey<T>;
     using V = typename K::type;
     if (k == 3) {
@@ -154,27 +167,33 @@ __device__ __forceinline__ T lane_median(const T* __restrict__ buf, int64_t H, i
         const int64_t x[3] = {reflect_index(col - 1, W), col, reflect_index(col + 1, W)};
         V p[9];
 #pragma unroll
-        for (int q = 0; q < 9; ++q) p[q] = static_cast<V>(buf[(y[q / 3] + x[q % 3]) * C + c]);
-        return static_cast<T>(median9<T>(p));
+        for (int q = 0; q < 9; ++q) p[q] = at((y[q / 3] + x[q % 3]) * C + c);
+        return median9<T>(p);
     }
     const int n = k * k, r = k / 2, m = n / 2;
-    auto at = [&](int q) -> V {
+    auto nb = [&](int q) -> V {
         const int64_t yy = reflect_index(row + (q / k - r), H) - buf_row0;
         const int64_t xx = reflect_index(col + (q % k - r), W);
-        return static_cast<V>(buf[(yy * W + xx) * C + c]);
+        return at((yy * W + xx) * C + c);
     };
-    V med = at(m);
+    V med = nb(m);
     for (int q = 0; q < n; ++q) {
-        const V v = at(q);
+        const V v = nb(q);
         int less = 0, leq = 0;
         for (int s = 0; s < n; ++s) {
-            const V u = at(s);
+            const V u = nb(s);
             less += (u < v);
             leq += (u <= v);
         }
         if (less <= m && m < leq) { med = v; break; }
     }
-    return static_cast<T>(med);
+    return med;
+}
+template <typename T>
+__device__ __forceinline__ T lane_median(const T* __restrict__ buf, int64_t H, int64_t W, int C,
+                                         int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
+    using V = typename MedianKey<T>::type;
+    return static_cast<T>(lane_median_of<T>([buf](int64_t i) { return static_cast<V>(buf[i]); }, H, W, C, buf_row0, row, col, c, k));
 }
 
 }  // namespace hm

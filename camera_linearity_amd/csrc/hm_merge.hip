@@ -72,6 +72,7 @@ struct MergeK {
     int32_t inv_t_inrange;                 // every 1/exposure in [2^-300, 2^300] (host check; see div_inrange)
     int32_t variant;
     uint32_t* hot_reset;                   // the hot-pixel queue's four counter words, zeroed by the streaming kernel that runs before the scan
+    const double* std_lut;                 // hm_merge_std_table: (256, C) per-DN std table read by the LUT instantiations instead of sd[] (else null)
 };
 
 // The queue's counters must be zero when merge_scan_hot starts. A hipMemsetAsync costs two fill kernels (~10 us per call, 1 % of
@@ -107,6 +108,22 @@ __device__ __forceinline__ void flat_field_apply(const MergeK& a, int64_t e, int
     flat_field_math(F, with_std ? 1.0 / (F * F) : 1.0, with_std ? a.flat_std[e] : 0.0, a.ff_mean[c], a.ff_std_mean[c], with_std, val, sd);
 }
 
+// index linearize forms from a frame value (measurand.py:503): the DN itself, or the rounded, wrapped float64 value
+__device__ __forceinline__ uint32_t lut_index_f64(double v) {
+    return static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;
+}
+__device__ __forceinline__ uint32_t lut_index_of(uint8_t v) { return v; }
+__device__ __forceinline__ uint32_t lut_index_of(double v) { return lut_index_f64(v); }
+
+// std of element `i` of frame `f` through the per-DN table (hm_merge_std_table): what linearize(frame, icrf = std_table).val holds there.
+// Handed to the k x k medians as their element accessor: a hot frame's std is the median of the MAPPED neighbourhood (the reference
+// filters the std image on its own, measurand.py:553-555), which differs from std_table[median DN] for a table that is not monotone.
+template <typename T>
+struct StdLutAt {
+    const T* f; const double* lut; int C, c;
+    __device__ __forceinline__ double operator()(int64_t i) const { return lut[lut_index_of(f[i]) * C + c]; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // One output element: the reference arithmetic (exposure_series.py:340-394) in the operation sequence
 // shared by every kernel of this file, so a result does not depend on which kernel (or tiling) produced
@@ -120,7 +137,8 @@ __device__ __forceinline__ void flat_field_apply(const MergeK& a, int64_t e, int
 // Tables: t_w/t_dw [256], t_g/t_d [256*C] in LDS.
 // ------------------------------------------------------------------------------------------------
 enum { HOT_NONE = 0, HOT_WAVE = 1, HOT_LANE = 2 };
-template <bool F64IN, bool STD, int HOT, int OUT = OUT_F64>
+// LUT (hm_merge_std_table): the frames' stds come from a.std_lut (global memory: these are the cold paths) instead of a.sd[].
+template <bool F64IN, bool STD, int HOT, int OUT = OUT_F64, bool LUT = false>
 __device__ __forceinline__ void merge_one_element(const MergeK& a, const double* t_w, const double* t_dw,
                                                   const double* t_g, const double* t_d, int64_t e, bool store) {
     const int C = a.C, N = a.n_frames;
@@ -183,7 +201,14 @@ __device__ __forceinline__ void merge_one_element(const MergeK& a, const double*
         acc = (i == 0) ? wg * it : fma(wg, it, acc);                    // :388 numerator
         if (STD) {
             double s;
-            if (HOT != HOT_NONE && hot) s = median_of(a.sd[i]);
+            if constexpr (LUT) {
+                using T = std::conditional_t<F64IN, double, uint8_t>;
+                const StdLutAt<T> at{static_cast<const T*>(a.frame[i]), a.std_lut, C, c};
+                if (HOT != HOT_NONE && hot) {
+                    if constexpr (HOT == HOT_WAVE) s = wave_median_of(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
+                    else s = lane_median_of<double>(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
+                } else s = a.std_lut[idx * C + c];
+            } else if (HOT != HOT_NONE && hot) s = median_of(a.sd[i]);
             else s = a.sd[i][ei];
             const double dg = t_d[idx * C + c] * s;                     // measurand.py:512
             const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;   // :389
@@ -215,7 +240,7 @@ __device__ __forceinline__ void fill_plain_tables(const MergeK& a, double* t_w, 
 // ------------------------------------------------------------------------------------------------
 // generic kernel: one element per thread, runtime N and C, uint8 or float64 frames.
 // ------------------------------------------------------------------------------------------------
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     reset_hot_counters(a);
@@ -223,7 +248,7 @@ __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
     __syncthreads();
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; q < a.n_elems; q += stride)
-        merge_one_element<F64IN, STD, HOT_NONE, OUT>(a, t_w, t_dw, t_g, t_d, a.elem0 + q, true);
+        merge_one_element<F64IN, STD, HOT_NONE, OUT, LUT>(a, t_w, t_dw, t_g, t_d, a.elem0 + q, true);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -236,7 +261,8 @@ __global__ __launch_bounds__(256) void merge_generic(const MergeK a) {
 // exactly the operation sequence of merge_one_element(), so the fix-up is bit-identical to what a
 // streaming kernel would have produced had it been given the filtered frames.
 // ------------------------------------------------------------------------------------------------
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+// LUT (hm_merge_std_table): a frame's std, and every neighbour's, is the per-DN table entry of the value loaded beside it.
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w, const double* t_dw,
                                            const double* t_g, const double* t_d, int64_t e) {
     const int lane = threadIdx.x & 63;
@@ -265,7 +291,8 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
     // --- parallel loads of the lane's own frame
     const bool hot = owner && dk && static_cast<int>(dk[ei]) >= dmin;
     double v = F64IN ? static_cast<const double*>(fr)[ei] : static_cast<double>(static_cast<const uint8_t*>(fr)[ei]);
-    double sdv = STD ? sp[ei] : 0.0;
+    double sdv = 0.0;
+    if constexpr (STD) sdv = LUT ? a.std_lut[(F64IN ? lut_index_f64(v) : static_cast<uint32_t>(v)) * C + c] : sp[ei];
     // --- medians of the hot frames, floor(64 / k^2) frames per batch
     const unsigned long long hotmask = __ballot(hot);
     const int k = a.median_k, kk = k * k, r = k / 2, m = kk / 2;
@@ -287,7 +314,7 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
         double nv = 0.0, ns = 0.0;
         if (part) {
             nv = F64IN ? static_cast<const double*>(pf)[ni] : static_cast<double>(static_cast<const uint8_t*>(pf)[ni]);
-            if (STD) ns = ps[ni];
+            if constexpr (STD) ns = LUT ? a.std_lut[(F64IN ? lut_index_f64(nv) : static_cast<uint32_t>(nv)) * C + cc] : ps[ni];
         }
         int lv = 0, qv = 0, ls = 0, qs = 0;
         for (int q = 0; q < kk; ++q) {
@@ -399,7 +426,7 @@ __host__ __device__ inline uint32_t hot_piece_slots(int64_t n_elems) { return st
 // merge_fixup_hot: every lane scans 16 consecutive elements of every distinct dark map; elements with at least one hot
 // frame are recomputed, one at a time, by the wave. This is the path WITHOUT a workspace: one element per wave at a time
 // makes it collapse on dense maps (15 us of one wave per hot element) - callers that can pass a workspace should.
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __global__ __launch_bounds__(256) void merge_fixup_hot(const MergeK a) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     fill_plain_tables<F64IN, STD>(a, t_w, t_dw, t_g, t_d);
@@ -426,7 +453,7 @@ __global__ __launch_bounds__(256) void merge_fixup_hot(const MergeK a) {
             while (bits) {
                 const int b = __ffs(static_cast<int>(bits)) - 1;
                 bits &= bits - 1;
-                fixup_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, base + b);
+                fixup_element<F64IN, STD, OUT, LUT>(a, t_w, t_dw, t_g, t_d, base + b);
             }
         }
     }
@@ -601,7 +628,7 @@ __device__ __forceinline__ uint32_t lane_hotmask(const MergeK& a, int64_t ei) {
     return hotmask;
 }
 
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* t_w, const double* t_dw, const double* t_g, const double* t_d,
                                                  std::conditional_t<F64IN, double, uint8_t>* keep /* LDS, this thread's column, stride 256 */,
                                                  int64_t e, uint32_t hotmask) {
@@ -666,20 +693,24 @@ __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* 
 #pragma unroll
             for (int f = 0; f < kPatchFB; ++f) {
                 if (i0 + f < N) {
-                    const double* sr = a.sd[i0 + f] + ei;
+                    // the std of element ei + off: the frame's std image, or (LUT) the per-DN table entry of the frame's value there - the
+                    // UNFILTERED value: the median is taken over the mapped neighbourhood
+                    const double* sr = LUT ? nullptr : a.sd[i0 + f] + ei;
+                    const StdLutAt<T> lut_at{static_cast<const T*>(a.frame[i0 + f]) + ei, a.std_lut, C, c};
+                    auto std_at = [&](int64_t off) -> double { if constexpr (LUT) return lut_at(off); else return sr[off]; };
                     const bool hot = (hotmask >> (i0 + f)) & 1u;
 #if HM_PATCH_HOT_ONLY
-                    const double centre = sr[0];
+                    const double centre = std_at(0);
 #pragma unroll
                     for (int q = 0; q < 9; ++q) sp[f][q] = centre;
                     if (hot) {
 #pragma unroll
                         for (int q = 0; q < 9; ++q)
-                            if (q != 4) sp[f][q] = sr[dy[q / 3] + dx[q % 3]];
+                            if (q != 4) sp[f][q] = std_at(dy[q / 3] + dx[q % 3]);
                     }
 #else
 #pragma unroll
-                    for (int q = 0; q < 9; ++q) sp[f][q] = sr[hot ? dy[q / 3] + dx[q % 3] : int64_t{0}];
+                    for (int q = 0; q < 9; ++q) sp[f][q] = std_at(hot ? dy[q / 3] + dx[q % 3] : int64_t{0});
 #endif
                 }
             }
@@ -722,14 +753,14 @@ __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* 
     if (STD) store_out<OUT>(a.out_std, e, sd);
 }
 
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __device__ __forceinline__ void patch_element(const MergeK& a, const double* t_w, const double* t_dw, const double* t_g, const double* t_d,
                                               char* keep_lds, int64_t e, uint32_t hotmask) {
     using T = std::conditional_t<F64IN, double, uint8_t>;
     if (a.median_k == 3 && (!F64IN || a.n_frames <= kPatchF64Frames))                    // wave-uniform
-        patch_element_k3<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, reinterpret_cast<T*>(keep_lds) + threadIdx.x, e, hotmask);
+        patch_element_k3<F64IN, STD, OUT, LUT>(a, t_w, t_dw, t_g, t_d, reinterpret_cast<T*>(keep_lds) + threadIdx.x, e, hotmask);
     else
-        merge_one_element<F64IN, STD, HOT_LANE, OUT>(a, t_w, t_dw, t_g, t_d, e, true);
+        merge_one_element<F64IN, STD, HOT_LANE, OUT, LUT>(a, t_w, t_dw, t_g, t_d, e, true);
 }
 static int patch_keep_bytes(bool f64in, int n_frames, int median_k) {
     if (median_k != 3 || (f64in && n_frames > kPatchF64Frames)) return 16;
@@ -743,7 +774,7 @@ static int patch_keep_bytes(bool f64in, int n_frames, int median_k) {
 // neighbouring cache lines). Workgroups beyond the queue leave before they build their tables.
 // If the scan raised the overflow flag (more hot elements than the workspace holds: a quarter of the image with the recommended
 // size) the queue is ignored: every lane looks at its own elements' dark bytes and patches the hot ones.
-template <bool F64IN, bool STD, int OUT = OUT_F64>
+template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false>
 __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uint32_t* ws, uint32_t bmax) {
     __shared__ double t_w[256], t_dw[256], t_g[256 * HM_MAX_CHANNELS], t_d[256 * HM_MAX_CHANNELS];
     extern __shared__ __attribute__((aligned(16))) char keep_lds[];
@@ -832,7 +863,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; q < a.n_elems; q += stride) {
             const int64_t e = a.elem0 + q;
             const uint32_t hotmask = lane_hotmask(a, a.in_off + e);
-            if (hotmask) patch_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
+            if (hotmask) patch_element<F64IN, STD, OUT, LUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
         return;
     }
@@ -845,7 +876,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
                 e = static_cast<int64_t>(queue[slot_of(q)]);
                 hotmask = lane_hotmask(a, a.in_off + e);
             }
-            patch_element<F64IN, STD, OUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
+            patch_element<F64IN, STD, OUT, LUT>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
     }
 }
@@ -1003,17 +1034,32 @@ constexpr uint32_t kSub = 128;     // elements per sub-unit (64 lanes x 2)
 #define HM_PIN_NF 8      // std kernel: above this N, pass 2 re-derives its per-frame addresses (registers)
 #endif
 
+// merge_u8_fast_std with the per-DN std table (merge_u8_fast_std_lut): sub-units per group, frames per pass-2 scheduling bundle and
+// the occupancy target, chosen for THIS instantiation from the compiler's resource report
+#ifndef HM_LUT_U
+#define HM_LUT_U 1
+#endif
+#ifndef HM_LUT_FB
+#define HM_LUT_FB 2
+#endif
+#ifdef HM_LUT_WAVES
+#define HM_LUT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(HM_LUT_WAVES, HM_LUT_WAVES)))
+#else
+#define HM_LUT_WAVES_ATTR
+#endif
+
 #ifdef HM_WAVES          /* experiment knob (tools/build_alt.sh): ask the register allocator for this many waves per SIMD */
 #define HM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(HM_WAVES, HM_WAVES)))
 #else
 #define HM_WAVES_ATTR
 #endif
 
-template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
+template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64, bool LUT = false>
 __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
     static_assert(CH == 3 || (CH == 1 && STD && !SUMW), "monochrome: the std instantiations (with or without the flat field) only");
+    static_assert(!LUT || STD, "the per-DN std table belongs to the std kernel");
     constexpr int C = CH;
     // frames up to which pass 2 keeps its per-frame state pinned / its std loads issued early (flat-field instantiations). With the
     // sum-of-weights output on top, N = 8 needed 168 VGPRs + 20 bytes of scratch per lane: that one shape takes the N > 8 form (152 VGPRs)
@@ -1064,7 +1110,9 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
         double2* t_wdw = reinterpret_cast<double2*>(lds);
         double2* t_gd = reinterpret_cast<double2*>(lds + 16 * 256);
         for (int i = threadIdx.x; i < 256; i += BLOCK) t_wdw[i] = double2{a.w_lut[i], a.dw_lut[i]};
-        for (int i = threadIdx.x; i < 256 * C; i += BLOCK) t_gd[i] = double2{a.icrf[i], a.icrf_diff[i]};
+        // LUT (hm_merge_std_table): the entry's second half is dg itself, icrf_diff * std (measurand.py:512) - the product the std-stream
+        // form makes per element-frame from the same two operands, made once per (DN, c); the kernel then has no std loads at all
+        for (int i = threadIdx.x; i < 256 * C; i += BLOCK) t_gd[i] = double2{a.icrf[i], LUT ? a.icrf_diff[i] * a.std_lut[i] : a.icrf_diff[i]};
     }
     // uint8 flat fields take only 256 values: {F = DN/255, 1/F**2} per DN in LDS saves two float64 divisions per element
     double2* t_flat = reinterpret_cast<double2*>(lds + (STD ? kStdTabBytes : TabInfo<TAB>::bytes));
@@ -1164,7 +1212,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                 const char* t_gd = lds + 16 * 256;
                 // HM_STD_EARLY (flat-field instantiations): all NF float64 std loads of the sub-unit are issued here, ahead of pass 1's
                 // gathers (4 VGPRs per frame: stacks of up to HM_PIN_NF frames only), instead of HM_STD_FB frames at a time inside pass 2
-                constexpr bool EARLY = HM_STD_EARLY && FLAT && NF <= PIN_NF;
+                constexpr bool EARLY = !LUT && HM_STD_EARLY && FLAT && NF <= PIN_NF;
                 f64x2 sd_early[EARLY ? NF : 1];
                 if constexpr (EARLY) {
 #pragma unroll
@@ -1201,14 +1249,15 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                 for (int i = 0; i < NF; ++i) {
                     const double it = a.inv_t[i];
                     f64x2 sdv;
-                    if constexpr (EARLY) sdv = sd_early[i];
+                    if constexpr (LUT) sdv = f64x2{1.0, 1.0};                  // unused: the table entry is dg
+                    else if constexpr (EARLY) sdv = sd_early[i];
                     else {
                         const double* sp = a.sd[i] + a.in_off + sbase;                           // scalar base
                         if (NF > PIN_NF || !FLAT) asm volatile("" : "+s"(sp));     // keep base + 32-bit lane offset addressing (no per-frame VGPR address pairs)
                         sdv = ld_f64x2_global(sp, lane16);
                     }
                     uint32_t packed = cur[i][s];
-                    if (NF > PIN_NF || !FLAT) HM_PIN(packed);                  // re-extract the DNs here instead of keeping pass 1's indices alive
+                    if (LUT || NF > PIN_NF || !FLAT) HM_PIN(packed);           // re-extract the DNs here instead of keeping pass 1's indices alive
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         const uint32_t dn = j == 0 ? (packed & 255u) : (packed >> 8);
@@ -1220,7 +1269,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                         const double2 gd = *reinterpret_cast<const double2*>(t_gd + dn * (16u * C) + coffs[j]);
 #endif
                         const double w = wdw.x, dw = wdw.y, gg = gd.x;
-                        const double dg = gd.y * (j == 0 ? sdv.x : sdv.y);                       // measurand.py:512
+                        const double dg = LUT ? gd.y : gd.y * (j == 0 ? sdv.x : sdv.y);          // measurand.py:512
                         const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
                         const double term = (A * dg) * it;
                         if (i == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }
@@ -1229,10 +1278,11 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                             var[j] = fma(term, term, var[j]);
                         }
                     }
-                    if ((i % HM_STD_FB) == HM_STD_FB - 1 || i == NF - 1) {
+                    constexpr int FB = LUT ? HM_LUT_FB : HM_STD_FB;
+                    if ((i % FB) == FB - 1 || i == NF - 1) {
 #pragma unroll
                         for (int j = 0; j < 2; ++j) { HM_PIN(acc[j]); HM_PIN(var[j]); }
-                        __builtin_amdgcn_sched_barrier(0);   // HM_STD_FB frames' std loads + gathers at a time
+                        __builtin_amdgcn_sched_barrier(0);   // FB frames' std loads + gathers at a time
                     }
                 }
                 double val[2], so[2];
@@ -1274,6 +1324,12 @@ template <int NF, int U, int TAB, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES, FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES)))
 void merge_u8_fast_std(const MergeK a) {
     merge_u8_fast_body<NF, U, TAB, true, PREFETCH, FLAT, SUMW, BLOCK, CH, OUT>(a);
+}
+// The same kernel with the per-DN std table (hm_merge_std_table): no std loads, the {g, dg} entries carry the table. Its register
+// budget is its own (HM_LUT_U / HM_LUT_FB / HM_LUT_WAVES below), not the std-stream kernel's.
+template <int NF, int U, bool FLAT, int OUT = OUT_F64>
+__global__ __launch_bounds__(256) HM_LUT_WAVES_ATTR void merge_u8_fast_std_lut(const MergeK a) {
+    merge_u8_fast_body<NF, U, TAB_PLAIN, true, true, FLAT, false, 256, 3, OUT, true>(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1628,7 +1684,7 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
 constexpr int kLoopChunk = 8;
 constexpr int kTemplatedN = 20;                    // frame counts with their own instantiation of the templated kernels (see hm_merge's dispatch)
 
-template <int C, bool STD, bool FLAT, bool SUMW, int OUT>
+template <int C, bool STD, bool FLAT, bool SUMW, int OUT, bool LUT = false>
 __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
@@ -1649,7 +1705,8 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
         double2* t_wdw = reinterpret_cast<double2*>(lds);
         double2* t_gd = reinterpret_cast<double2*>(lds + 16 * 256);
         for (int i = threadIdx.x; i < 256; i += 256) t_wdw[i] = double2{a.w_lut[i], a.dw_lut[i]};
-        for (int i = threadIdx.x; i < 256 * C; i += 256) t_gd[i] = double2{a.icrf[i], a.icrf_diff[i]};
+        // LUT (hm_merge_std_table): {g, dg = icrf_diff * std} per (DN, c), as in merge_u8_fast_body
+        for (int i = threadIdx.x; i < 256 * C; i += 256) t_gd[i] = double2{a.icrf[i], LUT ? a.icrf_diff[i] * a.std_lut[i] : a.icrf_diff[i]};
     }
     double2* t_flat = reinterpret_cast<double2*>(lds + (STD ? 16 * 256 + 16 * 256 * C : 16 * 256 * C));
     if constexpr (FLAT) {
@@ -1742,20 +1799,24 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                 invS[j] = 1.0 / S[j];
                 invS2[j] = 1.0 / (S[j] * S[j]);                          // 1 / S**2, exposure_series.py:343
             }
-            // pass 2: the frame bytes again (cache hits) + the float64 std streams, two frames per step
-            for (int i0 = 0; i0 < N; i0 += 2) {
-                uint32_t r[2];
-                f64x2 sdv[2];
+            // pass 2: the frame bytes again (cache hits) + the float64 std streams, two frames per step (LUT: no std streams, P2 = 4 frames)
+            constexpr int P2 = LUT ? 4 : 2;
+            for (int i0 = 0; i0 < N; i0 += P2) {
+                uint32_t r[P2];
+                f64x2 sdv[P2];
 #pragma unroll
-                for (int k = 0; k < 2; ++k) {
+                for (int k = 0; k < P2; ++k) {
                     if (i0 + k < N) {
                         r[k] = ld_u16(static_cast<const uint8_t*>(a.frame[i0 + k]) + ibase + lane2);
-                        const double* sp = a.sd[i0 + k] + ibase;
-                        sdv[k] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(reinterpret_cast<const char*>(sp) + lane16));
+                        if constexpr (LUT) sdv[k] = f64x2{1.0, 1.0};      // unused: the table entry is dg
+                        else {
+                            const double* sp = a.sd[i0 + k] + ibase;
+                            sdv[k] = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(reinterpret_cast<const char*>(sp) + lane16));
+                        }
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < 2; ++k) {
+                for (int k = 0; k < P2; ++k) {
                     if (i0 + k < N) {
                         const double it = a.inv_t[i0 + k];
 #pragma unroll
@@ -1764,7 +1825,7 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                             const double2 wdw = t_wdw[dn];
                             const double2 gd = *reinterpret_cast<const double2*>(t_gd + dn * (16u * C) + coffs[j]);
                             const double w = wdw.x, dw = wdw.y, gg = gd.x;
-                            const double dg = gd.y * (j == 0 ? sdv[k].x : sdv[k].y);                       // measurand.py:512
+                            const double dg = LUT ? gd.y : gd.y * (j == 0 ? sdv[k].x : sdv[k].y);          // measurand.py:512
                             const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
                             const double term = (A * dg) * it;
                             if (i0 + k == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }
@@ -1786,7 +1847,8 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                 flat_field_math(F[0], iF2[0], sF[0], a.ff_mean[c0], a.ff_std_mean[c0], true, val[0], so[0]);
                 flat_field_math(F[1], iF2[1], sF[1], a.ff_mean[c1], a.ff_std_mean[c1], true, val[1], so[1]);
             }
-            if constexpr (SUMW) store2(a.out_sum_w + sbase, lane16, S[0], S[1]);
+            // (the table instantiations exist with SUMW only and test the pointer - a scalar branch - instead of doubling their number: build time)
+            if constexpr (SUMW) { if (!LUT || a.out_sum_w) store2(a.out_sum_w + sbase, lane16, S[0], S[1]); }
             store_pair<OUT>(out_at<OUT>(a.out_val, sbase), lane16, val[0], val[1]);
             store_pair<OUT>(out_at<OUT>(a.out_std, sbase), lane16, so[0], so[1]);
         }
@@ -1805,8 +1867,8 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
 #endif
 template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
 __global__ __launch_bounds__(256) HM_LOOP_VAL_ATTR void merge_u8_loop(const MergeK a) { merge_u8_loop_body<C, false, FLAT, SUMW, OUT>(a); }
-template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64>
-__global__ __launch_bounds__(256) HM_LOOP_STD_ATTR void merge_u8_loop_std(const MergeK a) { merge_u8_loop_body<C, true, FLAT, SUMW, OUT>(a); }
+template <int C, bool FLAT, bool SUMW, int OUT = OUT_F64, bool LUT = false>
+__global__ __launch_bounds__(256) HM_LOOP_STD_ATTR void merge_u8_loop_std(const MergeK a) { merge_u8_loop_body<C, true, FLAT, SUMW, OUT, LUT>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // merge_f64_val / merge_f64_std (body: merge_f64_body): float64 frames (the reference's 64-bit mode, image_set.py:225 / frames saved by save_64bit) with the
@@ -1821,10 +1883,6 @@ __global__ __launch_bounds__(256) HM_LOOP_STD_ATTR void merge_u8_loop_std(const 
 // ------------------------------------------------------------------------------------------------
 constexpr int kF64Chunk = 4;
 constexpr int kF64Keep = 8;        // std mode: stacks up to this size keep their frame values in registers between the passes
-
-__device__ __forceinline__ uint32_t lut_index_f64(double v) {
-    return static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;          // measurand.py:503
-}
 
 template <int C, bool STD, bool FLAT, bool SUMW, int OUT>
 __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
@@ -2072,6 +2130,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HM_F64_STD_
 static thread_local std::string* g_describe = nullptr;
 static thread_local bool g_describe_f32 = false;      // the call being described has out_kind = HM_OUT_F32
 static thread_local bool g_describe_quad = false;     // ... and the kernel being named stores four float32 elements per lane (merge_u8_val3's QUAD map)
+static thread_local bool g_describe_lut = false;      // the call being described takes its stds from the per-DN table (hm_merge_std_table)
 static bool describe_only(const char* fmt, int a = 0, int b = 0, int c = 0, int d = 0) {
     if (!g_describe) return false;
     char buf[160];
@@ -2079,7 +2138,9 @@ static bool describe_only(const char* fmt, int a = 0, int b = 0, int c = 0, int 
     std::string name = buf;
     // float32 calls: every kernel that stores val / std (all of them have a template argument list) says so inside it;
     // the strings of float64 calls stay as they were
-    const size_t close = name.find('>');
+    // table calls: likewise every kernel that forms a std (in such a call: every kernel with a template argument list) carries "std=lut"
+    size_t close = name.find('>');
+    if (g_describe_lut && close != std::string::npos) { name.insert(close, ",std=lut"); close = name.find('>'); }
     if (g_describe_f32 && close != std::string::npos) name.insert(close, g_describe_quad ? ",out=f32x4" : ",out=f32");
     if (!g_describe->empty()) *g_describe += " + ";
     *g_describe += name;
@@ -2304,8 +2365,31 @@ static int launch_extras(const MergeK& k, hipStream_t st) {
     return launch_one<NF, U, TAB, STD, true, false, true, 256, 3, OUT>(k, st);
 }
 
+// hm_merge_std_table on colour stacks of up to kLutTemplatedN frames with float64 outputs, with or without a flat field:
+// merge_u8_fast_std_lut. The rarer shapes (sum-of-weights output, C != 3, more frames, float32 outputs) take merge_u8_loop_std's table
+// instantiations - build time.
+constexpr int kLutTemplatedN = 16;
+template <int NF>
+static int launch_fast_lut(const MergeK& k, hipStream_t st) {
+    constexpr int U = HM_LUT_U;
+    constexpr int OUT = OUT_F64;
+    const bool flat = k.has_flat != 0;
+    if (describe_only("merge_u8_fast_std<N=%d,U=%d,flat=%d,sum_w=%d>", NF, U, flat, 0)) return HM_OK;
+    const int lds = kStdTabBytes + (flat ? 16 * 256 : 0);
+    const unsigned grid = stream_grid(k.n_elems / (U * static_cast<int>(kSub)), 4, 8);
+    if (flat) hipLaunchKernelGGL((merge_u8_fast_std_lut<NF, U, true, OUT>), dim3(grid), dim3(256), lds, st, k);
+    else hipLaunchKernelGGL((merge_u8_fast_std_lut<NF, U, false, OUT>), dim3(grid), dim3(256), lds, st, k);
+    return launch_status();
+}
+static bool use_fast_lut(const MergeK& k, bool f64in) {
+    return k.std_lut && !f64in && k.C == 3 && k.n_frames <= kLutTemplatedN && !k.out_sum_w && k.variant == 0;
+}
+
 template <int NF>
 static int launch_fast_nf(const MergeK& k, const FastCfg& c, bool with_std, hipStream_t st) {
+    if constexpr (NF <= kLutTemplatedN) {
+        if (k.std_lut) return launch_fast_lut<NF>(k, st);
+    }
     const bool extras = k.has_flat || k.out_sum_w;
     if (with_std) {
         if (use_fast_std_mono(k, true, false)) {
@@ -2409,13 +2493,17 @@ static int launch_loop_c(const MergeK& k, bool with_std, hipStream_t st) {
     const unsigned grid = stream_grid(k.n_elems / static_cast<int>(kSub), 4, 8);
     if (describe_only(with_std ? "merge_u8_loop_std<C=%d,flat=%d,sum_w=%d>(N=%d)" : "merge_u8_loop<C=%d,flat=%d,sum_w=%d>(N=%d)", C, flat, sumw, k.n_frames)) return HM_OK;
 #define HM_LOOP(K, F, W) hipLaunchKernelGGL((K<C, F, W, OUT>), dim3(grid), dim3(256), lds, st, k)
-    if (with_std) {
+#define HM_LOOP_LUT(F) hipLaunchKernelGGL((merge_u8_loop_std<C, F, true, OUT, true>), dim3(grid), dim3(256), lds, st, k)
+    if (with_std && k.std_lut) {                  // (one instantiation serves calls with and without out_sum_w)
+        if (flat) HM_LOOP_LUT(true); else HM_LOOP_LUT(false);
+    } else if (with_std) {
         if (flat && sumw) HM_LOOP(merge_u8_loop_std, true, true); else if (flat) HM_LOOP(merge_u8_loop_std, true, false);
         else if (sumw) HM_LOOP(merge_u8_loop_std, false, true); else HM_LOOP(merge_u8_loop_std, false, false);
     } else {
         if (flat && sumw) HM_LOOP(merge_u8_loop, true, true); else if (flat) HM_LOOP(merge_u8_loop, true, false);
         else if (sumw) HM_LOOP(merge_u8_loop, false, true); else HM_LOOP(merge_u8_loop, false, false);
     }
+#undef HM_LOOP_LUT
 #undef HM_LOOP
     return launch_status();
 }
@@ -2463,7 +2551,11 @@ static int launch_generic(const MergeK& k, bool f64in, bool with_std, hipStream_
     const unsigned grid = stream_grid(k.n_elems, 256, 8);
     if (describe_only("merge_generic<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
 #define HM_GEN(F, S) hipLaunchKernelGGL((merge_generic<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
-    if (f64in) { if (with_std) HM_GEN(true, true); else HM_GEN(true, false); }
+    if (with_std && k.std_lut) {
+        if (f64in) hipLaunchKernelGGL((merge_generic<true, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
+        else hipLaunchKernelGGL((merge_generic<false, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
+    }
+    else if (f64in) { if (with_std) HM_GEN(true, true); else HM_GEN(true, false); }
     else       { if (with_std) HM_GEN(false, true); else HM_GEN(false, false); }
 #undef HM_GEN
     return launch_status();
@@ -2475,7 +2567,11 @@ static int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t 
     const unsigned grid = stream_grid(chunks, 256, 8);
     if (describe_only("merge_fixup_hot<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
 #define HM_FIX(F, S) hipLaunchKernelGGL((merge_fixup_hot<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
-    if (f64in) { if (with_std) HM_FIX(true, true); else HM_FIX(true, false); }
+    if (with_std && k.std_lut) {
+        if (f64in) hipLaunchKernelGGL((merge_fixup_hot<true, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
+        else hipLaunchKernelGGL((merge_fixup_hot<false, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
+    }
+    else if (f64in) { if (with_std) HM_FIX(true, true); else HM_FIX(true, false); }
     else       { if (with_std) HM_FIX(false, true); else HM_FIX(false, false); }
 #undef HM_FIX
     return launch_status();
@@ -2501,8 +2597,10 @@ static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t
     // resident from the start and a sparse queue costs the latency of one element. A grid of 8 per CU ran its workgroups in three
     // rounds at 3 resident per CU - 57-65 us for 35 000 queued elements, each round the same dependent chain of memory round trips.
     const int keep = patch_keep_bytes(f64in, k.n_frames, k.median_k);
+    const bool lut = with_std && k.std_lut;
     const void* fn;
-    if (f64in) fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<true, false, OUT>);
+    if (lut) fn = f64in ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT, true>) : reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT, true>);
+    else if (f64in) fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<true, false, OUT>);
     else       fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<false, false, OUT>);
     // (the query costs a few microseconds of host time: remembered per kernel, LDS size and device, under a mutex - hm_merge may be called
     // from several host threads)
@@ -2533,7 +2631,10 @@ static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t
 #define HM_PATCH(K, F, S) hipLaunchKernelGGL((K<F, S, OUT>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax)
 #define HM_PATCH4(K) { if (f64in) { if (with_std) HM_PATCH(K, true, true); else HM_PATCH(K, true, false); } \
                        else       { if (with_std) HM_PATCH(K, false, true); else HM_PATCH(K, false, false); } }
-    HM_PATCH4(merge_patch_hot)
+    if (lut) {
+        if (f64in) hipLaunchKernelGGL((merge_patch_hot<true, true, OUT, true>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
+        else hipLaunchKernelGGL((merge_patch_hot<false, true, OUT, true>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
+    } else HM_PATCH4(merge_patch_hot)
 #undef HM_PATCH4
 #undef HM_PATCH
     return launch_status();
@@ -2541,13 +2642,14 @@ static int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t
 
 }  // namespace hm
 
-extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
+// lut: the call is hm_merge_std_table - std outputs (and the flat field's std) without the N float64 std streams
+static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
     const int N = g->n_frames;
-    const bool s = g->stds != nullptr;
+    const bool s = lut || g->stds != nullptr;
     const int64_t in_b = g->frames_f64 ? 8 : 1;
-    int64_t per = N * (in_b + (s ? 8 : 0));
+    int64_t per = N * (in_b + ((s && !lut) ? 8 : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
@@ -2562,6 +2664,8 @@ extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
         }
     return per * E;
 }
+extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
+extern "C" int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
 
 // Workspace of the hot-pixel queue for a call that produces n_elems = rows * W * C output elements: 16 bytes of counters, the piece
 // table (8 bytes per 65 536 elements + 8 KB) and one uint32 per queued element. The recommended size holds a quarter of the elements
@@ -2578,15 +2682,23 @@ extern "C" size_t hm_merge_hot_workspace_bytes(int64_t n_elems) {
     return hm_merge_hot_workspace_min_bytes(n_elems) + static_cast<size_t>(entries - 1) * 4;
 }
 
-extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) {
+static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream);
+
+static int merge_describe(const hm_merge_args* g, const double* std_table, bool table_call, char* buf, int buf_len) {
     if (!buf || buf_len < 1) return HM_EINVAL;
     std::string names;
     hm::g_describe = &names;
-    hm::g_describe_f32 = false;                            // set by hm_merge once it has accepted a float32 call
-    const int rc = hm_merge(g, nullptr);
+    hm::g_describe_f32 = false;                            // set by merge_entry once it has accepted a float32 call
+    hm::g_describe_lut = false;                            // ... or a call that forms its stds from the table
+    const int rc = table_call ? hm_merge_std_table(g, std_table, nullptr) : merge_entry(g, nullptr, nullptr);
     hm::g_describe = nullptr;
     snprintf(buf, static_cast<size_t>(buf_len), "%s", names.c_str());
     return rc;
+}
+extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, nullptr, false, buf, buf_len); }
+extern "C" int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table, char* buf, int buf_len) {
+    if (!g) return HM_EINVAL;                              // before anything else is read - or written
+    return merge_describe(g, std_table, true, buf, buf_len);
 }
 
 // struct_size values hm_merge accepts: the current layout and the two older ones of ABI version 1 (without the hot-pixel queue
@@ -2604,9 +2716,25 @@ static bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
 }
 
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, bool flat, bool hot, void* stream);
+static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool f64in, bool with_std, bool flat, bool hot, void* stream);
 
-extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
+extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) { return merge_entry(g_in, nullptr, stream); }
+
+// hm_merge_std_table: the table call's own argument rules, then hm_merge's path with the table in place of the std frames
+extern "C" int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void* stream) {
+    if (!g_in) return HM_EINVAL;
+    hm_merge_args full;
+    if (!widen_args(g_in, full)) return HM_EINVAL;
+    if (full.stds || !std_table || !full.icrf_diff) return HM_EINVAL;
+    if (full.frames_u8 && !full.dw_lut) return HM_EINVAL;
+    if (full.out_val && !full.out_std) return HM_EINVAL;
+    if (!hm::aligned(std_table, 8)) return HM_EALIGN;
+    // a call without out_val forms no std: it is hm_merge's sum-of-weights call
+    return merge_entry(&full, full.out_val ? std_table : nullptr, stream);
+}
+
+// std_table != NULL (from hm_merge_std_table only; g->stds is NULL then): the stds come from the per-DN table
+static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream) {
     using namespace hm;
     hm_merge_args full;
     if (!widen_args(g_in, full)) return HM_EINVAL;
@@ -2620,7 +2748,7 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
     const bool f64in = g->frames_f64 != nullptr;
     if (f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;          // exactly one input kind
     if (!g->exposures || !g->icrf) return HM_EINVAL;
-    const bool with_std = g->stds != nullptr;
+    const bool with_std = g->stds != nullptr || std_table != nullptr;
     if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
     if (g->out_val) {
         if (with_std != (g->out_std != nullptr)) return HM_EINVAL;
@@ -2652,7 +2780,7 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
         const void* f = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
         if (!f) return HM_EINVAL;
         if (f64in && !aligned(f, 8)) return HM_EALIGN;
-        if (with_std) {
+        if (g->stds) {
             if (!g->stds[i]) return HM_EINVAL;
             if (!aligned(g->stds[i], 8)) return HM_EALIGN;
         }
@@ -2665,7 +2793,10 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
     // loop below advances output pointers by float64 elements, and the variant matrix of a tuning build is float64 instantiations
     if (f32out && (N > HM_MAX_FRAMES || g->variant <= -2 || (HM_TUNE_NF != 0 && g->variant > 0) ||
                    g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
+    // the per-DN std table exists in the one-launch kernels only (hm_merge_chunk.hip reads std frames)
+    if (std_table && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
     if (f32out) g_describe_f32 = true;
+    if (std_table) g_describe_lut = true;
     // More frames than one launch takes (modules/exposure_series.py:334,372 have no limit): HM_MAX_FRAMES per launch with the running
     // sums in memory (hm_merge_chunk.hip). variant <= -2 forces that path with -variant frames per chunk (tests: any chunking gives the
     // bits of the one-launch kernels).
@@ -2694,19 +2825,19 @@ extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) {
                 if (g->flat_u8) b.flat_u8 = g->flat_u8 + adv;
                 if (g->flat_f64) b.flat_f64 = g->flat_f64 + adv;
                 if (g->flat_std) b.flat_std = g->flat_std + adv;
-                const int rc_b = hm_merge(&b, stream);
+                const int rc_b = merge_entry(&b, std_table, stream);
                 if (rc_b != HM_OK) return rc_b;
             }
             return HM_OK;
         }
     }
-    return f32out ? merge_one_launch<OUT_F32>(g, f64in, with_std, flat, hot, stream)
-                  : merge_one_launch<OUT_F64>(g, f64in, with_std, flat, hot, stream);
+    return f32out ? merge_one_launch<OUT_F32>(g, std_table, f64in, with_std, flat, hot, stream)
+                  : merge_one_launch<OUT_F64>(g, std_table, f64in, with_std, flat, hot, stream);
 }
 
 // One streaming launch (+ generic tail + hot-pixel pass) for validated arguments; OUT = element type of out_val / out_std.
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
+static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
     using namespace hm;
     const int N = g->n_frames, C = g->channels;
     const bool f32_pairs = OUT == OUT_F32 && g->variant == kVariantF32Pairs;      // float32 A/B: the default dispatch without the QUAD map
@@ -2714,12 +2845,12 @@ static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, b
     MergeK k{};
     for (int i = 0; i < N; ++i) {
         k.frame[i] = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
-        if (with_std) k.sd[i] = g->stds[i];
+        if (g->stds) k.sd[i] = g->stds[i];
         k.inv_t[i] = 1.0 / g->exposures[i];
         k.dark[i] = hot ? g->darks_u8[i] : nullptr;
         k.dark_min[i] = hot && g->dark_min_dn ? g->dark_min_dn[i] : 256;
     }
-    k.icrf = g->icrf; k.icrf_diff = g->icrf_diff; k.w_lut = g->w_lut; k.dw_lut = g->dw_lut;
+    k.icrf = g->icrf; k.icrf_diff = g->icrf_diff; k.w_lut = g->w_lut; k.dw_lut = g->dw_lut; k.std_lut = std_table;
     k.flat_u8 = g->flat_u8; k.flat_f64 = g->flat_f64; k.flat_std = g->flat_std;
     for (int c = 0; c < HM_MAX_CHANNELS; ++c) { k.ff_mean[c] = g->ff_mean[c]; k.ff_std_mean[c] = g->ff_std_mean[c]; }
     k.out_val = g->out_val; k.out_std = g->out_std; k.out_sum_w = g->out_sum_w;
@@ -2746,20 +2877,24 @@ static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, b
         if (!ok || with_std || flat || g->out_sum_w || f64in || C != 3) return HM_EINVAL;
         cfg = default_cfg(with_std);
     } else if (!decode_variant(variant, with_std, cfg)) return HM_EINVAL;
-    bool fast = g->out_val && E < (int64_t{1} << 32) && variant >= 0;
+    // (the per-DN std table: uint8 frames stream through the kernels that hold it in LDS; float64 frames go to merge_generic - merge_f64_std reads std frames)
+    const bool lut = std_table != nullptr;
+    bool fast = g->out_val && E < (int64_t{1} << 32) && variant >= 0 && !(lut && f64in);
     // (float32 outputs: templated kernels for the frame counts of kF32Templated() only - build time; the others take the run-time-N kernels)
     const bool templated = OUT == OUT_F64 || kF32Templated(N);
     const bool mono_val3 = templated && use_val3_mono(k, with_std, f64in);
-    const bool mono_std = templated && use_fast_std_mono(k, with_std, f64in);
+    const bool mono_std = templated && !lut && use_fast_std_mono(k, with_std, f64in);
+    const bool lut_templated = OUT == OUT_F64 && use_fast_lut(k, f64in);
     // Templates up to kTemplatedN = 20 frames (round 4, late: 16 before). On 2048 x 4096 x 3 stacks the templated kernels beat the run-time-N
     // kernel at N = 17 (val-only 115 against 130 us, with std 790 against 880 us) and N = 20 (132 against 150, 985 against 1 025 us) and lose from
     // N = 24 (with std) / 32 (val-only) on, where their per-frame register arrays no longer fit (profiles/r04z_n32_templates_ab.log).
-    const bool loop_kernel = (f64in || N > kTemplatedN || C != 3 || !templated) && !mono_val3 && !mono_std;   // run-time-N / any-C streaming kernel instead of the templates
+    const bool loop_kernel = lut ? !lut_templated
+                                 : (f64in || N > kTemplatedN || C != 3 || !templated) && !mono_val3 && !mono_std;   // run-time-N / any-C streaming kernel instead of the templates
     if (fast) {
         for (int i = 0; i < N && fast; ++i) {
             fast = f64in ? aligned(static_cast<const double*>(k.frame[i]) + k.in_off, 16)
                          : aligned(static_cast<const uint8_t*>(k.frame[i]) + k.in_off, 2);
-            if (fast && with_std) fast = aligned(k.sd[i] + k.in_off, 16);
+            if (fast && with_std && !lut) fast = aligned(k.sd[i] + k.in_off, 16);
         }
         constexpr int pair_bytes = OUT == OUT_F32 ? 8 : 16;                  // one lane's two output elements
         fast = fast && aligned(k.out_val, pair_bytes) && (!k.out_std || aligned(k.out_std, pair_bytes)) &&
@@ -2771,7 +2906,7 @@ static int merge_one_launch(const hm_merge_args* g, bool f64in, bool with_std, b
     if (!fast) {
         rc = launch_generic<OUT>(k, f64in, with_std, st);
     } else {
-        const int64_t grp = loop_kernel ? static_cast<int64_t>(kSub) : (mono_val3 ? val3_unit_elems(flat ? val3_flat_default(N) : val3_default(N))
+        const int64_t grp = loop_kernel ? static_cast<int64_t>(kSub) : lut_templated ? static_cast<int64_t>(HM_LUT_U) * kSub : (mono_val3 ? val3_unit_elems(flat ? val3_flat_default(N) : val3_default(N))
                                                                                                  : fast_group_elems(N, variant, cfg, with_std, flat || g->out_sum_w, use_val3_flat(k, with_std)));
         const int64_t body = (E / grp) * grp;
         if (body > 0) {

@@ -77,6 +77,24 @@ inline T median_at(const T* buf, int64_t H, int64_t W, int C, int64_t buf_row0, 
     return v[n / 2];
 }
 
+// the same median over the neighbourhood mapped through `at(value)` (hm_merge_std_table: the per-DN std of every neighbour; the reference
+// filters the std image on its own, measurand.py:553-555)
+template <typename T, typename At>
+inline double median_mapped_at(const T* buf, At at, int64_t H, int64_t W, int C, int64_t buf_row0, int64_t row, int64_t col, int c, int k) {
+    double v[49];
+    const int r = k / 2;
+    int n = 0;
+    for (int dy = -r; dy <= r; ++dy) {
+        const int64_t yy = reflect_index(row + dy, H) - buf_row0;
+        for (int dx = -r; dx <= r; ++dx) {
+            const int64_t xx = reflect_index(col + dx, W);
+            v[n++] = at(buf[(yy * W + xx) * C + c]);
+        }
+    }
+    std::nth_element(v, v + n / 2, v + n);
+    return v[n / 2];
+}
+
 // measurand.py:585-602 (1 / F**2 formed once, as the device kernels do; <= 2 ulp on the std)
 inline void flat_field_math(double F, double sF, double m, double s, bool with_std, double& val, double& sd) {
     if (with_std) {
@@ -264,11 +282,12 @@ size_t hm_merge_hot_workspace_bytes(int64_t) { return 16; }
 size_t hm_merge_hot_workspace_min_bytes(int64_t) { return 16; }
 size_t hm_merge_frames_workspace_bytes(int, int64_t, int) { return 0; }           // any number of frames in one pass on the host
 
-int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
+// lut: hm_merge_std_table - std outputs without the N float64 std streams
+static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
-    const bool s = g->stds != nullptr;
-    int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + (s ? 8 : 0));
+    const bool s = lut || g->stds != nullptr;
+    int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + ((s && !lut) ? 8 : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
@@ -283,8 +302,11 @@ int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) {
         }
     return per * E;
 }
+int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
+int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
 
-static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot) {
+// std_table: NULL for hm_merge; hm_merge_std_table's table (its own argument rules, then hm_merge's with the table in place of the std frames)
+static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot, const double* std_table = nullptr, bool table_call = false) {
     if (!g_in) return HM_EINVAL;
     const uint32_t sz = g_in->struct_size;
     if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return HM_EINVAL;
@@ -292,6 +314,13 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
     std::memcpy(&full, g_in, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
     if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;                  // the older layouts carried an unspecified pad word there
     const hm_merge_args* g = &full;
+    if (table_call) {
+        if (g->stds || !std_table || !g->icrf_diff) return HM_EINVAL;
+        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
+        if (g->out_val && !g->out_std) return HM_EINVAL;
+        if (!aligned8(std_table)) return HM_EALIGN;
+        if (!g->out_val) std_table = nullptr;                                       // no std is formed: hm_merge's sum-of-weights call
+    }
     const int N = g->n_frames, C = g->channels;
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
     if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
@@ -301,7 +330,7 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
     const bool f64in = g->frames_f64 != nullptr;
     if (f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;
     if (!g->exposures || !g->icrf) return HM_EINVAL;
-    const bool with_std = g->stds != nullptr;
+    const bool with_std = g->stds != nullptr || std_table != nullptr;
     if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
     if (g->out_val) {
         if (with_std != (g->out_std != nullptr)) return HM_EINVAL;
@@ -331,7 +360,7 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
         const void* f = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
         if (!f) return HM_EINVAL;
         if (f64in && !aligned8(f)) return HM_EALIGN;
-        if (with_std) {
+        if (g->stds) {
             if (!g->stds[i]) return HM_EINVAL;
             if (!aligned8(g->stds[i])) return HM_EALIGN;
         }
@@ -346,15 +375,21 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
     return HM_OK;
 }
 
-int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) {
+static int merge_describe(const hm_merge_args* g, const double* std_table, bool table_call, char* buf, int buf_len) {
     if (!buf || buf_len < 1) return HM_EINVAL;
     hm_merge_args full; bool hot = false;
-    const int rc = merge_check(g, full, hot);
+    const int rc = merge_check(g, full, hot, std_table, table_call);
+    const bool lut = table_call && full.out_val;
     if (rc == HM_OK && full.rows > 0)
-        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr, hot,
-                      full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
+        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr || lut, hot,
+                      lut ? ",std=lut" : "", full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
     else buf[0] = 0;
     return rc;
+}
+int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, nullptr, false, buf, buf_len); }
+int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table, char* buf, int buf_len) {
+    if (!g) return HM_EINVAL;                                                     // before anything else is read - or written
+    return merge_describe(g, std_table, true, buf, buf_len);
 }
 
 // exposure_series.py:340-394 per output element, the operation sequence of merge_one_element() (hm_merge.hip): S in frame order;
@@ -363,8 +398,10 @@ int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) {
 
 // One instantiation per (float64 frames, dark maps, std) combination: the per-element loop carries no run-time mode tests, and the row / column
 // of an element are only worked out where a median needs them. Same operations in the same order in every instantiation.
+// std_table (hm_merge_std_table; g->stds is NULL then): a frame's std is std_table[idx * C + c], idx the index linearize forms from the
+// frame's own value; for a hot frame the median of the neighbourhood's mapped values.
 template <bool F64IN, bool HOT, bool STD>
-static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
+static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, const double* std_table) {
     const int N = g->n_frames, C = g->channels;
     const bool flat = g->flat_u8 || g->flat_f64;
     const int64_t W = g->width, wc = W * C, E = g->rows * wc;
@@ -439,12 +476,23 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
                     const bool h = g->darks_u8[i] && static_cast<int>(g->darks_u8[i][ei]) >= g->dark_min_dn[i];   // measurand.py:545
                     if constexpr (F64IN) v[i] = h ? median_at(g->frames_f64[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->frames_f64[i][ei];
                     else dn[i] = h ? median_at(g->frames_u8[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->frames_u8[i][ei];
-                    if constexpr (STD) sdv[i] = h ? median_at(g->stds[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->stds[i][ei];
+                    if constexpr (STD) {
+                        if (std_table) {
+                            const auto at_u8 = [=](uint8_t x) { return std_table[static_cast<uint32_t>(x) * C + c]; };
+                            const auto at_f64 = [=](double x) { return std_table[lut_index(x) * C + c]; };
+                            if constexpr (F64IN) sdv[i] = h ? median_mapped_at(g->frames_f64[i], at_f64, g->height, W, C, g->buf_row0, row, col, c, k) : at_f64(g->frames_f64[i][ei]);
+                            else sdv[i] = h ? median_mapped_at(g->frames_u8[i], at_u8, g->height, W, C, g->buf_row0, row, col, c, k) : at_u8(g->frames_u8[i][ei]);
+                        } else sdv[i] = h ? median_at(g->stds[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->stds[i][ei];
+                    }
                 }
             } else {
                 for (int i = 0; i < N; ++i) {
                     if constexpr (F64IN) v[i] = g->frames_f64[i][ei]; else dn[i] = g->frames_u8[i][ei];
-                    if constexpr (STD) sdv[i] = g->stds[i][ei];
+                    if constexpr (STD) {
+                        if (!std_table) sdv[i] = g->stds[i][ei];
+                        else if constexpr (F64IN) sdv[i] = std_table[lut_index(v[i]) * C + c];
+                        else sdv[i] = std_table[dn[i] * C + c];
+                    }
                 }
             }
             double S = 0.0;
@@ -516,30 +564,34 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k) {
 
 extern "C" {
 
-int hm_merge(const hm_merge_args* g_in, void*) {
+static int merge_run(const hm_merge_args* g_in, const double* std_table, bool table_call) {
     hm_merge_args full; bool hot = false;
-    const int rc = merge_check(g_in, full, hot);
+    const int rc = merge_check(g_in, full, hot, std_table, table_call);
     if (rc != HM_OK) return rc;
     const hm_merge_args* g = &full;
     if (g->rows == 0) return HM_OK;
     const int N = g->n_frames;
-    const bool f64in = g->frames_f64 != nullptr, with_std = g->stds != nullptr && g->out_val != nullptr;
+    if (!g->out_val) std_table = nullptr;
+    const bool f64in = g->frames_f64 != nullptr, with_std = (g->stds != nullptr || std_table != nullptr) && g->out_val != nullptr;
     std::vector<double> inv_t(static_cast<size_t>(N));
     for (int i = 0; i < N; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
     const int k = hot ? g->median_k : 3;
     const int mode = (f64in ? 4 : 0) | (hot ? 2 : 0) | (with_std ? 1 : 0);
     switch (mode) {
-        case 0: merge_elements<false, false, false>(g, inv_t.data(), k); break;
-        case 1: merge_elements<false, false, true>(g, inv_t.data(), k); break;
-        case 2: merge_elements<false, true, false>(g, inv_t.data(), k); break;
-        case 3: merge_elements<false, true, true>(g, inv_t.data(), k); break;
-        case 4: merge_elements<true, false, false>(g, inv_t.data(), k); break;
-        case 5: merge_elements<true, false, true>(g, inv_t.data(), k); break;
-        case 6: merge_elements<true, true, false>(g, inv_t.data(), k); break;
-        default: merge_elements<true, true, true>(g, inv_t.data(), k); break;
+        case 0: merge_elements<false, false, false>(g, inv_t.data(), k, std_table); break;
+        case 1: merge_elements<false, false, true>(g, inv_t.data(), k, std_table); break;
+        case 2: merge_elements<false, true, false>(g, inv_t.data(), k, std_table); break;
+        case 3: merge_elements<false, true, true>(g, inv_t.data(), k, std_table); break;
+        case 4: merge_elements<true, false, false>(g, inv_t.data(), k, std_table); break;
+        case 5: merge_elements<true, false, true>(g, inv_t.data(), k, std_table); break;
+        case 6: merge_elements<true, true, false>(g, inv_t.data(), k, std_table); break;
+        default: merge_elements<true, true, true>(g, inv_t.data(), k, std_table); break;
     }
     return HM_OK;
 }
+
+int hm_merge(const hm_merge_args* g_in, void*) { return merge_run(g_in, nullptr, false); }
+int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void*) { return merge_run(g_in, std_table, true); }
 
 }  // extern "C"
 

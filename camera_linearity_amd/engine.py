@@ -260,39 +260,53 @@ class MergePlan:
     `launch()` enqueues the fused kernel on the current stream of the plan's device; it can be called
     repeatedly (bench, hipGraph capture)."""
 
-    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict):
+    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None):
         self.args = args
         self._keep = keep
         self.device = torch.device(device)
         self.outputs = outputs
         self._ref = C.byref(args)
         self.host = self.device.type != "cuda"             # a plan of the host backend (built inside nat.host_mode())
+        self.std_table = std_table                         # (256, C) float64 per-DN std table: the plan goes through hm_merge_std_table
+        self._table = None if std_table is None else std_table.data_ptr()
+
+    def _call(self, lib, stream):
+        if self._table is None:
+            return lib.hm_merge(self._ref, stream)
+        return lib.hm_merge_std_table(self._ref, self._table, stream)
 
     def launch(self, stream: Optional[int] = None) -> None:
+        what = "hm_merge" if self._table is None else "hm_merge_std_table"
         if self.host:
             with nat.host_mode():
-                nat.check(nat.lib.hm_merge(self._ref, None), "hm_merge")
+                nat.check(self._call(nat.lib, None), what)
             return
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if torch.cuda.current_device() == self.device.index:
-            rc = nat.lib.hm_merge(self._ref, stream)
+            rc = self._call(nat.lib, stream)
         else:
             with _on(self.device):
-                rc = nat.lib.hm_merge(self._ref, stream)
+                rc = self._call(nat.lib, stream)
         if rc:
-            nat.check(rc, "hm_merge")
+            nat.check(rc, what)
 
     @property
     def algorithmic_bytes(self) -> int:
+        if self._table is not None:
+            return int(nat.hip_lib.hm_merge_std_table_algorithmic_bytes(C.byref(self.args)))
         return int(nat.hip_lib.hm_merge_algorithmic_bytes(C.byref(self.args)))
 
     @property
     def kernels(self) -> str:
-        """Names of the kernels launch() dispatches to, in launch order (hm_merge_describe: the library's own dispatch, dry)."""
+        """Names of the kernels launch() dispatches to, in launch order (hm_merge_describe / hm_merge_std_table_describe: the library's
+        own dispatch, dry)."""
         buf = C.create_string_buffer(512)
         lib = nat.host_lib() if self.host else nat.hip_lib
-        nat.check(lib.hm_merge_describe(self._ref, buf, 512), "hm_merge_describe")
+        if self._table is not None:
+            nat.check(lib.hm_merge_std_table_describe(self._ref, self._table, C.addressof(buf), 512), "hm_merge_std_table_describe")
+        else:
+            nat.check(lib.hm_merge_describe(self._ref, buf, 512), "hm_merge_describe")
         return buf.value.decode()
 
 
@@ -303,7 +317,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
                flat: Optional[torch.Tensor] = None, flat_std: Optional[torch.Tensor] = None,
                ff_mean=None, ff_std_mean=None, want_sum_w: bool = False, want_val: bool = True,
                height: Optional[int] = None, row0: int = 0, rows: Optional[int] = None, buf_row0: int = 0,
-               variant: int = 0, hot_queue: bool = True, out_dtype: torch.dtype = torch.float64) -> MergePlan:
+               variant: int = 0, hot_queue: bool = True, out_dtype: torch.dtype = torch.float64, std_table=None) -> MergePlan:
     """Build the launch descriptor for one fused merge (modules/exposure_series.py:317-419).
 
     frames : N tensors (buf_rows, W, C), all uint8 DNs or all float64 values, ascending exposure.
@@ -319,6 +333,11 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
              All arithmetic is float64 either way; float32 rounds the float64 result once, to nearest even, at the kernel's store, so
              the outputs equal the float64 outputs cast to float32 - with half the output bytes. `sum_w` stays float64. More than
              HM_MAX_FRAMES frames (and a forced chunking, variant <= -2) exist for float64 only: NotImplementedError.
+    std_table : (256, C) array or tensor - the per-DN STD table of ImageSet.calculate_numerical_STD (video_processing.
+             noise_profiles_to_STD_data) instead of `stds`: frame i's std is std_table[idx_i, c], formed inside the kernel from the table in LDS
+             (hm_merge_std_table), so no std frame exists in device memory. The outputs equal those of `stds=[linearize(f, None,
+             std_table)[0] for f in frames]`, bit for bit. Needs icrf_diff; excludes `stds` (ValueError). At most HM_MAX_FRAMES frames
+             and no forced chunking: NotImplementedError.
     """
     if out_dtype not in (_F64, torch.float32):
         raise TypeError(f"out_dtype must be torch.float64 or torch.float32, got {out_dtype}")
@@ -347,9 +366,16 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     rows = (buf_row0 + buf_rows - row0) if rows is None else int(rows)
     if len(exposures) != n:
         raise ValueError("one exposure per frame is required")
-    with_std = stds is not None
+    if std_table is not None:
+        if stds is not None:
+            raise ValueError("std_table and stds are mutually exclusive: the table takes the place of the std frames")
+        if icrf_diff is None:
+            raise ValueError("ICRF_diff is required to propagate uncertainty")
+        if n > nat.HM_MAX_FRAMES or variant <= -2:
+            raise NotImplementedError(f"std_table merges take at most {nat.HM_MAX_FRAMES} frames in one launch (the chunked path reads std frames)")
+    with_std = stds is not None or std_table is not None
     sd = []
-    if with_std:
+    if stds is not None:
         if len(stds) != n:
             raise ValueError("one std frame per value frame is required")
         if icrf_diff is None:
@@ -370,6 +396,11 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
             raise ValueError(f"ICRF_diff must have shape ({BITS}, {Cc})")
     w_lut, dw_lut = weight_luts(dev)
     keep += [icrf_t, diff_t, w_lut, dw_lut]
+    table_t = None
+    if std_table is not None:
+        table_t = _dev_f64(std_table, dev)
+        if tuple(table_t.shape) != (BITS, Cc):
+            raise ValueError(f"std_table must have shape ({BITS}, {Cc}), got {tuple(table_t.shape)}")
 
     a = nat.MergeArgs()
     a.struct_size = C.sizeof(nat.MergeArgs)
@@ -382,7 +413,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     else:
         a.frames_f64 = C.cast(fptrs, C.POINTER(C.c_void_p))
     keep.append(fptrs)
-    if with_std:
+    if stds is not None:
         sptrs = _ptr_array(sd)
         a.stds = C.cast(sptrs, C.POINTER(C.c_void_p))
         keep.append(sptrs)
@@ -459,14 +490,14 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         ws = torch.empty(fw, dtype=_U8, device=dev)
         a.frames_workspace, a.frames_workspace_bytes = ws.data_ptr(), fw
         keep.append(ws)
-    plan = MergePlan(a, keep, dev, outputs)
-    if out_dtype == torch.float32:
-        plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs raises here, not at the first launch
+    plan = MergePlan(a, keep, dev, outputs, std_table=table_t)
+    if out_dtype == torch.float32 or table_t is not None:
+        plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs / table calls raises here, not at the first launch
     return plan
 
 
 def merge(frames, exposures, icrf, icrf_diff=None, stds=None, **kw) -> dict:
-    """plan_merge(...).launch(); returns {'val', 'std'?, 'sum_w'?} device tensors."""
+    """plan_merge(...).launch(); returns {'val', 'std'?, 'sum_w'?} device tensors (`std_table=`: see plan_merge)."""
     plan = plan_merge(frames, exposures, icrf, icrf_diff, stds, **kw)
     plan.launch()
     return plan.outputs

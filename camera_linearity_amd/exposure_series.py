@@ -23,7 +23,7 @@ import torch
 
 from . import _native as nat
 from . import settings as gs
-from .image_set import ImageSet
+from .image_set import ImageSet, _std_path, read_STD_file
 
 
 def icrf_derivative(ICRF, bits: int = None):
@@ -239,13 +239,36 @@ class ExposureSeries(object):
 
     def _compute_HDR_image_set(self, list_of_dark_fields, sum_of_weights, square_sum_of_weights, ICRF, ICRF_diff,
                                flat_set: Optional[ImageSet] = None, dark_threshold: Optional[float] = None,
-                               use_std: Optional[bool] = None, out_dtype=None):
+                               use_std: Optional[bool] = None, out_dtype=None, STD_data=None):
         """exposure_series.py:347-397. The fused kernel recomputes the sum of weights in registers, so the
         two precalculated arrays are accepted for signature compatibility and not read.
-        out_dtype: None / torch.float64, or torch.float32 - the merged measurand then holds float32 arrays (engine.plan_merge)."""
+        out_dtype: None / torch.float64, or torch.float32 - the merged measurand then holds float32 arrays (engine.plan_merge).
+        STD_data: the (BITS, C) per-DN STD table of ImageSet.calculate_numerical_STD (None: settings.STD_FILE_NAME, when set). The
+        reference's rule per frame (image_set.py:228-243): '<name> STD.tif', else the table. When NO frame has a std - in memory or on
+        disk - the table goes into the fused kernel as it is (engine.plan_merge(std_table=...)) and no std image is materialised; when
+        some frames have one, the others' are made from the table and the merge reads std frames. Without a table nothing changes."""
         from . import engine
         eng = self._eng()
         sets = self.input_image_sets
+        std_table = None
+        if use_std is None or use_std:
+            if STD_data is None:
+                STD_data = read_STD_file()
+            if STD_data is not None:
+                for s in sets:
+                    if s.measurand.shape is None:
+                        s.load_value_image()
+                have = [s.measurand._std is not None or (s.path is not None and _std_path(s.path).exists()) for s in sets]
+                table = np.asarray(STD_data.cpu() if isinstance(STD_data, torch.Tensor) else STD_data, dtype=np.float64)
+                n_ch = sets[0].measurand.shape[-1]
+                fusable = table.shape == (gs.BITS, n_ch) and len(sets) <= nat.HM_MAX_FRAMES and len(sets[0].measurand.shape) == 3
+                if not any(have) and fusable:
+                    std_table, use_std = table, False       # (no std FRAMES: _stack_inputs collects values only)
+                else:
+                    for s in sets:
+                        if s.measurand._std is None:
+                            s.load_std_image(STD_data)      # the file, else the table: image_set.py:228-243
+                    use_std = True
         if use_std is None:
             for s in sets:                                  # the reference loads every frame's std image (:377),
                 if s.measurand._std is None and s.path is not None:     # whether or not its value image is in memory yet
@@ -256,6 +279,7 @@ class ExposureSeries(object):
                                  "(pass use_std=False to merge values only)")
             use_std = all(have)
         frames, stds, darks, mins = self._stack_inputs(list_of_dark_fields, dark_threshold, with_std=use_std)
+        use_std = use_std or std_table is not None          # from here on: the merge produces a std image
         dev = frames[0].device
         if ICRF_diff is None and use_std:
             ICRF_diff = icrf_derivative(ICRF)
@@ -278,7 +302,8 @@ class ExposureSeries(object):
                 kw.update(flat_std=fstd, ff_std_mean=_roi_means(flat_set, eng, fstd, (x0, x1, y0, y1), "std"))
         exposures = [s.features["exposure"] for s in sets]
         out = eng.merge(frames, exposures, ICRF, ICRF_diff if use_std else None, stds, darks=darks, dark_min=mins,
-                        median_k=gs.MEDIAN_FILTER_KERNEL_SIZE, out_dtype=torch.float64 if out_dtype is None else out_dtype, **kw)
+                        median_k=gs.MEDIAN_FILTER_KERNEL_SIZE, out_dtype=torch.float64 if out_dtype is None else out_dtype,
+                        std_table=std_table, **kw)
         hdr = type(sets[0].measurand)(out["val"], out.get("std"))
         hdr_set = ImageSet(file_path=sets[0].get_file_path_without_exposure(), features=dict(sets[0].features) if sets[0].features else None,
                            measurand=hdr)
@@ -286,7 +311,7 @@ class ExposureSeries(object):
         return hdr_set
 
     def process_HDR_image(self, ICRF=None, ICRF_diff=None, dark_list: Optional[List[ImageSet]] = None,
-                          flat_list: Optional[List[ImageSet]] = None, use_std: Optional[bool] = None, out_dtype=None):
+                          flat_list: Optional[List[ImageSet]] = None, use_std: Optional[bool] = None, out_dtype=None, STD_data=None):
         """exposure_series.py:399-419: merge the input images into self.merged_image_set.
         `out_dtype=torch.float32` (an addition; None = float64) stores the merged value / std images as float32: the same float64
         arithmetic, rounded once at the kernel's store - what ImageSet.save_32bit then writes.
@@ -294,7 +319,9 @@ class ExposureSeries(object):
         Defaults mirror the reference: `ICRF=None` reads settings.ICRF_CALIBRATED_FILE (:406-407; deviation E - the table is
         read as ONE (BITS, C) array and the derivative is formed with the reference's gradient convention), `dark_list=None`
         globs settings.DEFAULT_DARK_PATH (:409) and `flat_list=None` settings.DEFAULT_FLAT_PATH (image_set.py:146-155). A
-        path that is not configured means "none": no dark frames / no flat field - but a missing ICRF raises."""
+        path that is not configured means "none": no dark frames / no flat field - but a missing ICRF raises.
+        `STD_data` (None: the table of settings.STD_FILE_NAME, when set): the per-DN STD table behind frames without a std image; a series
+        with no std image at all is merged with the table inside the fused kernel (_compute_HDR_image_set)."""
         if ICRF is None:
             if gs.ICRF_CALIBRATED_FILE is None:
                 raise ValueError("process_HDR_image(ICRF=None) needs settings.ICRF_CALIBRATED_FILE (settings.configure(...)) "
@@ -310,7 +337,7 @@ class ExposureSeries(object):
             flat_list = ImageSet.multiple_from_path(Path(gs.DEFAULT_FLAT_PATH), use_cupy=self.use_cupy)
         flat_set = self.input_image_sets[0].get_flat_field(flat_list) if flat_list else None
         self.merged_image_set = self._compute_HDR_image_set(dark_list, None, None, ICRF, ICRF_diff, flat_set=flat_set,
-                                                            use_std=use_std, out_dtype=out_dtype)
+                                                            use_std=use_std, out_dtype=out_dtype, STD_data=STD_data)
 
     # ---- linearity statistics (exposure_series.py:421-476; "next" row f-1)
     def process_linearity(self, ICRF, linearity_limit: Optional[int] = None, use_std: Optional[bool] = False):

@@ -52,6 +52,20 @@ def _std_path(path: Path) -> Path:
     return Path(s.removesuffix(suffix) + " STD" + suffix)     # image_set.py:235
 
 
+def read_STD_file() -> Optional[np.ndarray]:
+    """The per-DN STD table of settings.STD_FILE_NAME (image_set.py:376-381) as a float64 array - read like settings.ICRF_CALIBRATED_FILE,
+    a relative name below settings.DATA_PATH when that is configured. None when the setting is unset or the file does not exist."""
+    if gs.STD_FILE_NAME is None:
+        return None
+    path = Path(gs.STD_FILE_NAME)
+    if not path.is_absolute() and gs.DATA_PATH is not None:
+        path = Path(gs.DATA_PATH) / path
+    try:
+        return np.loadtxt(path, dtype=float)
+    except FileNotFoundError:
+        return None
+
+
 class ImageSet(object):
 
     def __init__(self, file_path=None, value=None, std=None, features: Optional[Dict] = None,
@@ -238,7 +252,10 @@ class ImageSet(object):
         self.measurand.std = std_array
 
     def calculate_numerical_STD(self, STD_data=None):
-        """image_set.py:365-385: map DN -> std through a (BITS, C) or (BITS,) table with the linearize kernel."""
+        """image_set.py:365-385: map DN -> std through a (BITS, C) or (BITS,) table with the linearize kernel. `STD_data=None` reads
+        the table from settings.STD_FILE_NAME (:376-381); not configured or not found means no estimate."""
+        if STD_data is None:
+            STD_data = read_STD_file()
         if STD_data is None:
             print("Could not load STD data for numerical estimation.")
             return None

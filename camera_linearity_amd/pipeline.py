@@ -29,14 +29,20 @@ class _Slot:
 
 class MergePipeline:
     def __init__(self, n_frames: int, height: int, width: int, exposures: Sequence[float], icrf, icrf_diff=None,
-                 channels: int = 3, with_std: bool = False, device=None, depth: int = 2, out_dtype: torch.dtype = torch.float64):
+                 channels: int = 3, with_std: bool = False, device=None, depth: int = 2, out_dtype: torch.dtype = torch.float64,
+                 std_table=None):
         """out_dtype: torch.float64 or torch.float32 - the plans' output type (engine.plan_merge) and that of the pinned result staging:
-        float32 halves the device-to-host copy, which is what bounds a stream of val-only merges."""
+        float32 halves the device-to-host copy, which is what bounds a stream of val-only merges.
+        std_table: (256, C) per-DN STD table (engine.plan_merge) - a std output without std inputs: the slots hold no std staging buffers
+        and no std frame is copied to the device (8 bytes per element and frame with `with_std`). Excludes with_std."""
         if depth < 2:
             raise ValueError("depth must be at least 2 (one slot in flight while the next is filled)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if std_table is not None and with_std:
+            raise ValueError("std_table takes the place of the std inputs: with_std must be False")
         self.n, self.shape, self.with_std, self.depth = n_frames, (height, width, channels), with_std, depth
-        if with_std and icrf_diff is None:
+        self.std_out = with_std or std_table is not None             # the plans produce a std image
+        if self.std_out and icrf_diff is None:
             raise ValueError("uncertainty propagation needs ICRF_diff")
         self.s_h2d = torch.cuda.Stream(self.device)
         self.s_run = torch.cuda.Stream(self.device)
@@ -48,9 +54,10 @@ class MergePipeline:
             s.h_stds = [torch.empty(self.shape, dtype=torch.float64, pin_memory=True) for _ in range(n_frames)] if with_std else None
             s.d_frames = [torch.empty(self.shape, dtype=torch.uint8, device=self.device) for _ in range(n_frames)]
             s.d_stds = [torch.empty(self.shape, dtype=torch.float64, device=self.device) for _ in range(n_frames)] if with_std else None
-            s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if with_std else None, s.d_stds, out_dtype=out_dtype)
+            s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if self.std_out else None, s.d_stds, out_dtype=out_dtype,
+                                       std_table=std_table)
             s.h_val = torch.empty(self.shape, dtype=out_dtype, pin_memory=True)
-            s.h_std = torch.empty(self.shape, dtype=out_dtype, pin_memory=True) if with_std else None
+            s.h_std = torch.empty(self.shape, dtype=out_dtype, pin_memory=True) if self.std_out else None
             s.ev_h2d = torch.cuda.Event()
             s.ev_run = torch.cuda.Event()
             s.ev_d2h = torch.cuda.Event()
@@ -78,7 +85,7 @@ class MergePipeline:
         self.s_d2h.wait_event(s.ev_run)
         with torch.cuda.stream(self.s_d2h):
             s.h_val.copy_(s.plan.outputs["val"], non_blocking=True)
-            if self.with_std:
+            if self.std_out:
                 s.h_std.copy_(s.plan.outputs["std"], non_blocking=True)
             s.ev_d2h.record(self.s_d2h)
         s.busy = True

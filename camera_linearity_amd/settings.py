@@ -20,6 +20,7 @@ UPPER_LIN_LIM = 250            # :69
 
 # Paths behind the reference's default arguments (global_settings.py:40-60). None = not configured: nothing is looked up.
 ICRF_CALIBRATED_FILE = None    # text table (BITS, C) read by process_HDR_image(ICRF=None), exposure_series.py:406-407
+STD_FILE_NAME = None           # text table (BITS, C) or (BITS,) of per-DN stds read by calculate_numerical_STD(None) / process_HDR_image(STD_data=None), image_set.py:376-381
 DEFAULT_DARK_PATH = None       # directory of dark frames, exposure_series.py:409 / image_set.py:170
 DEFAULT_FLAT_PATH = None       # directory of flat fields, image_set.py:146-155
 DATA_PATH = None               # directory of the text tables read_txt_to_array loads by name (global_settings.py: the data directory)

@@ -151,7 +151,37 @@ int main(void) {
         free(val2); free(sd2);
     }
 #endif
-    const int ok = worst_val < 1e-12 && worst_std < 1e-9 && graph_ok;
+    /* The same merge with the per-frame stds taken from a per-DN table inside the kernel (ImageSet.calculate_numerical_STD's table): no std
+     * frames at all. With std frames filled from that table, stds[i][e] = table[frames[i][e] * C + c], hm_merge gives the same bits. */
+    int table_ok = 1;
+    {
+        static double table[256 * C];
+        for (int k = 0; k < 256 * C; ++k) table[k] = 0.004 + 1e-5 * ((k * 37) % 101);
+        double* d_table;
+        CHECK_HIP(hipMalloc((void**)&d_table, sizeof table));
+        CHECK_HIP(hipMemcpy(d_table, table, sizeof table, hipMemcpyHostToDevice));
+        for (int i = 0; i < N; ++i) {
+            for (int64_t e = 0; e < E; ++e) stds[i][e] = table[frames[i][e] * C + (int)(e % C)];
+            CHECK_HIP(hipMemcpy(d_stds[i], stds[i], E * 8, hipMemcpyHostToDevice));
+        }
+        CHECK_HM(hm_merge(&a, stream));
+        CHECK_HIP(hipStreamSynchronize(stream));
+        double* sd_stream = (double*)malloc(E * 8);
+        double* sd_table = (double*)malloc(E * 8);
+        CHECK_HIP(hipMemcpy(sd_stream, d_std, E * 8, hipMemcpyDeviceToHost));
+        hm_merge_args b = a;
+        b.stds = NULL;
+        memset(sd_table, 0xff, E * 8);
+        CHECK_HIP(hipMemcpy(d_std, sd_table, E * 8, hipMemcpyHostToDevice));      /* poison: the call must write every element */
+        CHECK_HM(hm_merge_std_table(&b, d_table, stream));
+        CHECK_HIP(hipStreamSynchronize(stream));
+        CHECK_HIP(hipMemcpy(sd_table, d_std, E * 8, hipMemcpyDeviceToHost));
+        table_ok = memcmp(sd_stream, sd_table, E * 8) == 0;
+        printf("hm_merge_std_table against hm_merge with std frames made from the table: %s (%lld against %lld algorithmic bytes)\n",
+               table_ok ? "identical bits" : "DIFFERENT", (long long)hm_merge_std_table_algorithmic_bytes(&b), (long long)hm_merge_algorithmic_bytes(&a));
+        free(sd_stream); free(sd_table);
+    }
+    const int ok = worst_val < 1e-12 && worst_std < 1e-9 && graph_ok && table_ok;
     puts(ok ? "C ABI merge OK" : "C ABI merge MISMATCH");
     return ok ? 0 : 1;
 }

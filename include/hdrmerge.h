@@ -212,6 +212,26 @@ int64_t hm_merge_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
  * With HM_OUT_F32 every listed kernel that stores val / std carries "out=f32" in its name. */
 int hm_merge_describe(const hm_merge_args* args, char* buf, int buf_len);
 
+/* hm_merge with the per-frame uncertainty taken from a per-DN table instead of N float64 std frames (the reference's default for
+ * captures without "<name> STD.tif" files: ImageSet.calculate_numerical_STD, modules/image_set.py:365-385):
+ *     std_i[h, w, c] = std_table[idx_i * C + c],
+ * idx_i the index linearize forms (the DN of a uint8 frame, rint(v * 255) & 255 of a float64 frame). The result equals hm_merge on the
+ * same arguments plus stds[i] = hm_linearize_u8 / hm_linearize_f64(frame_i, icrf = std_table).val, bit for bit, without those frames ever
+ * existing: the table sits in LDS next to the ICRF tables. For a frame that is hot at an element (dark maps) the std is the k x k median
+ * of the MAPPED neighbourhood, median_j(std_table[idx_j * C + c]), as the reference filters the std image on its own
+ * (modules/measurand.py:553-555) - not std_table[median DN].
+ * std_table: (256, C) float64, [device] (host memory on the host build), 8-byte aligned (else HM_EALIGN). args->stds must be NULL.
+ * HM_EINVAL: NULL args (returned before anything else is read), args->stds set, NULL std_table, no icrf_diff, no dw_lut (uint8 frames),
+ * out_val without out_std. A call without out_val (sum of weights only) behaves as hm_merge. Everything else - out_kind, flat field,
+ * out_sum_w, row tiles, the older struct_size values - as hm_merge, except: more than HM_MAX_FRAMES frames and variant <= -2 (the chunked
+ * path) are HM_EUNSUPPORTED, before any launch. float64 frames with a table stream through merge_generic only (merge_f64_std reads std frames).
+ * hm_merge_std_table_describe: as hm_merge_describe; every listed kernel that forms a std carries "std=lut".
+ * hm_merge_std_table_algorithmic_bytes: hm_merge_algorithmic_bytes for the same call with std frames, minus their 8 N bytes per element
+ * (both outputs counted, the table excluded like the other LUTs). */
+int hm_merge_std_table(const hm_merge_args* args /*[host]*/, const double* std_table, void* stream);
+int hm_merge_std_table_describe(const hm_merge_args* args, const double* std_table, char* buf, int buf_len);
+int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
+
 /* ------------------------------------------------------------------------------------------
  * Row 8 standalone - AbstractMeasurand.filter_larger_than_by_map (modules/measurand.py:543-557):
  * out = where(map >= min / map > thr, median_kxk(x, axes=(0,1), mode='reflect'), x), one call per array
