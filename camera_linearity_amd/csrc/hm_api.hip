@@ -44,6 +44,21 @@ extern "C" int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) {
     return HM_OK;
 }
 
+// number of CUs of the current device (hm_common.h; every unit sizes its grids with it)
+namespace hm {
+static int g_cu_count = 0;
+int cu_count() {
+    if (g_cu_count == 0) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
+            g_cu_count = p.multiProcessorCount;
+        else
+            g_cu_count = kCUs;
+    }
+    return g_cu_count;
+}
+}  // namespace hm
 
 // Shader-clock probe (diagnostic; docs/DESIGN_history_r01_r02.md 4.4): ONE wave on a side stream samples s_memtime (shader cycles) and s_memrealtime (100 MHz)
 // at its start and after `spins` sleep periods, while the caller's kernels run on another stream: out[0] = shader cycles, out[1] = 100 MHz

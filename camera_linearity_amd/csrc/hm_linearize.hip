@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_linearize(const void* __restrict__ in, 
 
 
 // ---------------- linearize, streaming form ----------------
-// The shape of the merge kernels (hm_merge.hip, merge_u8_val3) for one frame: a wave owns groups of 3 x 128 = 384 consecutive
+// The shape of the merge kernels (hm_merge_nf.h, merge_u8_val3) for one frame: a wave owns groups of 3 x 128 = 384 consecutive
 // elements (128 whole pixels for C = 3, so the channel of element j of sub-unit s is a compile-time function of (s, j) on top of a
 // lane constant), lane l handles elements 2l, 2l + 1 of a sub-unit - one ushort (uint8 input) or one 16-byte (float64 input) load
 // per sub-unit and 16-byte stores that make every store instruction a contiguous 1 KB; the NEXT group's loads are issued before

@@ -1,7 +1,7 @@
 // hm_merge_chunk.hip - HDR merge of stacks of MORE than HM_MAX_FRAMES frames (gfx950).
 //
 // The reference's merge loop has no frame limit (modules/exposure_series.py:334,372 iterate over the whole series). The
-// streaming kernels of hm_merge.hip take their frame pointers from the kernarg segment and therefore serve at most
+// streaming kernels of hm_merge*.hip take their frame pointers from the kernarg segment and therefore serve at most
 // HM_MAX_FRAMES per launch; a longer stack is merged here, HM_MAX_FRAMES frames per launch, with the running sums kept in
 // memory between the launches:
 //
@@ -11,7 +11,7 @@
 //              acc and var of exposure_series.py:388-389 with the final 1/S and 1/S**2 (acc in out_val, var in out_std);
 //              the last one finishes val = acc / S, std = sqrt(var) (+ flat field).
 //
-// The operation sequence per output element is merge_one_element()'s of hm_merge.hip - S in frame order, the numerator and
+// The operation sequence per output element is merge_one_element()'s of hm_merge_dev.h - S in frame order, the numerator and
 // the variance accumulated with fma in frame order, acc / S last; a float64 stored and re-loaded between two launches is the
 // same float64 - so a stack merged in chunks of ANY size gives the bits of the one-launch kernels (tests force chunks of 2-5
 // frames on short stacks and compare with merge_generic). Hot pixels (dark maps) are handled inline: a lane whose frame is

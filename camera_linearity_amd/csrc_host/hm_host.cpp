@@ -6,7 +6,7 @@
 // synchronous, workspaces may be NULL - written from scratch in plain C++ (g++ -O2 -fopenmp, no HIP, no NumPy, nothing from
 // oracle/). It is selected EXPLICITLY (Measurand(use_cupy=False) / HostMeasurand); the HIP backend never falls back to it.
 //
-// Arithmetic: the operation sequence of the device kernels, element by element (merge_one_element of hm_merge.hip, the operator
+// Arithmetic: the operation sequence of the device kernels, element by element (merge_one_element of hm_merge_dev.h, the operator
 // formulas of hm_ops.hip, ...), each citing the reference line it follows. Statistics use the reference's own two-pass form.
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
@@ -392,7 +392,7 @@ int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table,
     return merge_describe(g, std_table, true, buf, buf_len);
 }
 
-// exposure_series.py:340-394 per output element, the operation sequence of merge_one_element() (hm_merge.hip): S in frame order;
+// exposure_series.py:340-394 per output element, the operation sequence of merge_one_element() (hm_merge_dev.h): S in frame order;
 // 1/S and 1/S**2 once; numerator and variance accumulated with fma in frame order; acc / S last; flat field last.
 }  // extern "C" (templates below)
 

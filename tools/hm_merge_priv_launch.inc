@@ -1,4 +1,4 @@
-// hm_merge_priv_launch.inc - host-side launchers of merge_u8_priv; included by hm_merge.hip inside namespace hm, tuning builds only.
+// hm_merge_priv_launch.inc - host-side launchers of merge_u8_priv; included by hm_merge_nf.h inside namespace hm, tuning builds only.
 template <int NF, int U, int MODE, int BLOCK>
 static int launch_priv_cfg(const MergeK& k, hipStream_t st) {
     static bool attr_set = false;
@@ -16,13 +16,7 @@ static int launch_priv_cfg(const MergeK& k, hipStream_t st) {
     hipLaunchKernelGGL((merge_u8_priv<NF, U, MODE, BLOCK>), dim3(static_cast<unsigned>(grid)), dim3(BLOCK), lds, st, k);
     return launch_status();
 }
-// 8UMB: merge_u8_priv<N, U, MODE M, BLOCK = 256 | 768 | 1024 for B = 0 | 1 | 2> (tuning builds, N == HM_TUNE_NF)
-static bool priv_variant(int variant, int n_frames, int& u) {
-    if (variant < 8000 || variant >= 9000 || n_frames != HM_TUNE_NF || HM_TUNE_NF == 0) return false;
-    u = (variant / 100) % 10;
-    const int m = (variant / 10) % 10, bcode = variant % 10;
-    return (u == 2 || u == 4) && m <= 1 && bcode <= 2;
-}
+// (the 8UMB variant code is decoded by priv_variant(), camera_linearity_amd/csrc/hm_merge_host.h: the dispatcher needs it too)
 template <int NF>
 static int launch_priv(const MergeK& k, hipStream_t st) {
     const int u = (k.variant / 100) % 10, m = (k.variant / 10) % 10, bcode = k.variant % 10;
