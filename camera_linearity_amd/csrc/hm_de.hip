@@ -16,8 +16,8 @@
 //
 // hm_de_generation_batch advances K problems of one shape by the same three stages: k_de_trial_batch, grid = (S, K);
 // energy_batch() (hm_energy.hip), candidates K x S, geometry from the per-problem S; k_de_select_batch, grid = K. The kernel
-// bodies are the single-problem ones (k_de_trial's shared, k_de_select's repeated as de_select_body) applied to problem k's slices of
-// the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
+// bodies are the single-problem ones (k_de_trial's a shared function, k_de_select's the same text included a second time,
+// hm_de_select_body.h) applied to problem k's slices of the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
 #include "hm_common.h"
 
 namespace hm {
@@ -149,132 +149,11 @@ __device__ __forceinline__ void tree_sum(double* v, int n) {
 }
 
 __global__ __launch_bounds__(256) void k_de_select(const DeK a) {
-    __shared__ double e[HM_DE_MAX_POP];
-    __shared__ double v[HM_DE_MAX_POP];
-    __shared__ int idx[HM_DE_MAX_POP];
-    if (a.status[HM_DE_STOP] != 0) return;
-    const int S = a.S, P = a.P;
-    const int64_t g = a.status[HM_DE_GENERATION];
-    int n = 1;
-    while (n < S) n <<= 1;
-
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        double ei = __builtin_inf();
-        if (i < S) {
-            const double et = a.trial_energy[i];
-            ei = a.energy[i];
-            if (g == 0 || et <= ei) {                                     // deferred updating: every trial saw the old population
-                ei = et;
-                a.energy[i] = et;
-                for (int j = 0; j < P; ++j) a.pop[static_cast<int64_t>(i) * P + j] = a.trial[static_cast<int64_t>(i) * P + j];
-            }
-        }
-        e[i] = ei;
-        v[i] = i < S ? ei : 0.0;
-        idx[i] = i;
-    }
-    __syncthreads();
-    tree_sum(v, n);
-    const double mean = v[0] / S;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double d = e[i] - mean;
-        v[i] = i < S ? d * d : 0.0;
-    }
-    __syncthreads();
-    tree_sum(v, n);
-    const double sd = sqrt(v[0] / S);
-    // lowest energy, ties to the lowest index (the padding is +inf with an index >= S, so it never wins a tie)
-    for (int s = n >> 1; s > 0; s >>= 1) {
-        for (int t = threadIdx.x; t < s; t += blockDim.x) {
-            const double x0 = e[t], x1 = e[t + s];
-            const int i0 = idx[t], i1 = idx[t + s];
-            if (x1 < x0 || (x1 == x0 && i1 < i0)) { e[t] = x1; idx[t] = i1; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double best = e[0];
-        int64_t stop = 0;
-        if (g > 0 && (g & 1) == 0) {                                      // the reference loop advances two generations per pass (:351)
-            if (isfinite(mean) && sd == sd && sd <= a.tol * fabs(mean)) stop |= HM_DE_STOP_CONVERGED;   // mean finite <=> every E finite
-            if (best < a.energy_limit) stop |= HM_DE_STOP_ENERGY;
-        }
-        if (g >= a.max_generations) stop |= HM_DE_STOP_MAX;
-        a.status[HM_DE_BEST_INDEX] = idx[0];
-        a.status[HM_DE_BEST_ENERGY] = __double_as_longlong(best);
-        a.status[HM_DE_MEAN] = __double_as_longlong(mean);
-        a.status[HM_DE_STD] = __double_as_longlong(sd);
-        a.status[HM_DE_EVALUATIONS] += S;
-        a.status[HM_DE_STOP] = stop;
-        a.status[HM_DE_GENERATION] = g + 1;
-    }
+#include "hm_de_select_body.h"
 }
 
-// k_de_select's body once more, for k_de_select_batch: the single-problem kernel stays a kernel of its own text because routing it
-// through a shared device function moved its register allocation; the bytes-equal tests of the batch against single plans hold
-// the two copies to the same arithmetic
 __device__ __forceinline__ void de_select_body(const DeK& a) {
-    __shared__ double e[HM_DE_MAX_POP];
-    __shared__ double v[HM_DE_MAX_POP];
-    __shared__ int idx[HM_DE_MAX_POP];
-    if (a.status[HM_DE_STOP] != 0) return;
-    const int S = a.S, P = a.P;
-    const int64_t g = a.status[HM_DE_GENERATION];
-    int n = 1;
-    while (n < S) n <<= 1;
-
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        double ei = __builtin_inf();
-        if (i < S) {
-            const double et = a.trial_energy[i];
-            ei = a.energy[i];
-            if (g == 0 || et <= ei) {                                     // deferred updating: every trial saw the old population
-                ei = et;
-                a.energy[i] = et;
-                for (int j = 0; j < P; ++j) a.pop[static_cast<int64_t>(i) * P + j] = a.trial[static_cast<int64_t>(i) * P + j];
-            }
-        }
-        e[i] = ei;
-        v[i] = i < S ? ei : 0.0;
-        idx[i] = i;
-    }
-    __syncthreads();
-    tree_sum(v, n);
-    const double mean = v[0] / S;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double d = e[i] - mean;
-        v[i] = i < S ? d * d : 0.0;
-    }
-    __syncthreads();
-    tree_sum(v, n);
-    const double sd = sqrt(v[0] / S);
-    // lowest energy, ties to the lowest index (the padding is +inf with an index >= S, so it never wins a tie)
-    for (int s = n >> 1; s > 0; s >>= 1) {
-        for (int t = threadIdx.x; t < s; t += blockDim.x) {
-            const double x0 = e[t], x1 = e[t + s];
-            const int i0 = idx[t], i1 = idx[t + s];
-            if (x1 < x0 || (x1 == x0 && i1 < i0)) { e[t] = x1; idx[t] = i1; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double best = e[0];
-        int64_t stop = 0;
-        if (g > 0 && (g & 1) == 0) {                                      // the reference loop advances two generations per pass (:351)
-            if (isfinite(mean) && sd == sd && sd <= a.tol * fabs(mean)) stop |= HM_DE_STOP_CONVERGED;   // mean finite <=> every E finite
-            if (best < a.energy_limit) stop |= HM_DE_STOP_ENERGY;
-        }
-        if (g >= a.max_generations) stop |= HM_DE_STOP_MAX;
-        a.status[HM_DE_BEST_INDEX] = idx[0];
-        a.status[HM_DE_BEST_ENERGY] = __double_as_longlong(best);
-        a.status[HM_DE_MEAN] = __double_as_longlong(mean);
-        a.status[HM_DE_STD] = __double_as_longlong(sd);
-        a.status[HM_DE_EVALUATIONS] += S;
-        a.status[HM_DE_STOP] = stop;
-        a.status[HM_DE_GENERATION] = g + 1;
-    }
+#include "hm_de_select_body.h"
 }
 
 __global__ __launch_bounds__(256) void k_de_select_batch(const DeK a, const DeSeeds sd) { de_select_body(problem_of(a, sd, blockIdx.x)); }
@@ -282,6 +161,35 @@ __global__ __launch_bounds__(256) void k_de_select_batch(const DeK a, const DeSe
 }  // namespace hm
 
 using namespace hm;
+
+// the kernel arguments of a generation, as given (de_check judges them); a batch passes no seed here: its seeds travel in DeSeeds
+static DeK de_args(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
+                   int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits, const double* upper_limits,
+                   int pop_size, int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
+                   double recombination, double tol, double energy_limit) {
+    DeK k{};
+    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
+    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
+    k.S = pop_size; k.P = n_params; k.seed = static_cast<uint64_t>(seed); k.max_generations = max_generations;
+    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
+    return k;
+}
+
+// the argument checks of hm_de_generation (n_problems = 1) and of hm_de_generation_batch (its n_problems already within 1 ..
+// HM_DE_MAX_PROBLEMS), in the order both document: the first violation decides the code. `stacks` is dn, whichever its type.
+static int de_check(const DeK& k, int n_problems, const void* stacks, const double* exposures, const void* workspace, int64_t n_pixels,
+                    int n_frames, int lower, int upper) {
+    if (k.S < 4 || k.P < 1 || n_pixels < 0 || k.max_generations < 0) return HM_EINVAL;
+    if (k.S > HM_DE_MAX_POP || k.P > HM_DE_MAX_PARAMS) return HM_ESHAPE;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    if (n_problems * k.S > 65535) return HM_EUNSUPPORTED;                     // the energy grid's candidate dimension (a batch only: S <= HM_DE_MAX_POP)
+    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
+    if (!(k.m_lo >= 0.0 && k.m_lo <= k.m_hi && k.m_hi < 2.0)) return HM_EINVAL;                          // also rejects NaN
+    if (!(k.cr >= 0.0 && k.cr <= 1.0) || !(k.tol >= 0.0) || k.energy_limit != k.energy_limit) return HM_EINVAL;
+    if (!k.pop || !k.energy || !k.trial || !k.trial_energy || !k.icrf || !k.valid || !k.status) return HM_EINVAL;
+    if (!k.mean_icrf || !k.pca || !k.lo || !k.hi || !stacks || !exposures || !workspace) return HM_EINVAL;
+    return HM_OK;
+}
 
 extern "C" size_t hm_de_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size) {
     if (pop_size < 4 || pop_size > HM_DE_MAX_POP) return 0;
@@ -294,21 +202,12 @@ extern "C" int hm_de_generation(double* population, double* energies, double* tr
                                 const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size,
                                 int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
                                 double recombination, double tol, double energy_limit, void* workspace, void* stream) {
-    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
-    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;      // also rejects NaN
-    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
-    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
-    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !exposures || !workspace) return HM_EINVAL;
-    DeK k{};
-    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
-    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
-    k.S = pop_size; k.P = n_params; k.seed = static_cast<uint64_t>(seed); k.max_generations = max_generations;
-    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
+    const DeK k = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
+                          pop_size, n_params, seed, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    int rc = de_check(k, 1, dn, exposures, workspace, n_pixels, n_frames, lower, upper);
+    if (rc != HM_OK) return rc;
     hipLaunchKernelGGL(k_de_trial, dim3(pop_size), dim3(256), 0, as_stream(stream), k);
-    int rc = launch_status();
+    rc = launch_status();
     if (rc != HM_OK) return rc;
     rc = hm_linearity_energy(dn, std, exposures, icrf, valid, pop_size, lower, upper, 1, n_pixels, n_frames, nullptr,
                              trial_energies, workspace, stream);
@@ -336,26 +235,17 @@ extern "C" int hm_de_generation_batch(int n_problems, double* population, double
                                       void* workspace, void* stream) {
     if (n_problems < 1) return HM_EINVAL;
     if (n_problems > HM_DE_MAX_PROBLEMS) return HM_ESHAPE;
-    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
-    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (n_problems * pop_size > 65535) return HM_EUNSUPPORTED;                // the energy grid's candidate dimension
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;      // also rejects NaN
-    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
-    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
-    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !seeds || !exposures || !workspace) return HM_EINVAL;
+    const DeK k = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
+                          pop_size, n_params, 0, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    int rc = de_check(k, n_problems, dn, exposures, workspace, n_pixels, n_frames, lower, upper);
+    if (rc != HM_OK) return rc;
+    if (!seeds) return HM_EINVAL;
     for (int i = 0; i < n_problems; ++i)                                      // host arrays: read within the validated K only
         if (!dn[i] || (std && !std[i])) return HM_EINVAL;                     // stds for all problems or for none
-    DeK k{};
-    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
-    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
-    k.S = pop_size; k.P = n_params; k.max_generations = max_generations;
-    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
     DeSeeds sd{};
     for (int i = 0; i < n_problems; ++i) sd.seed[i] = static_cast<uint64_t>(seeds[i]);
     hipLaunchKernelGGL(k_de_trial_batch, dim3(pop_size, n_problems), dim3(256), 0, as_stream(stream), k, sd);
-    int rc = launch_status();
+    rc = launch_status();
     if (rc != HM_OK) return rc;
     rc = energy_batch(dn, std, status, n_problems, pop_size, exposures, icrf, valid, lower, upper, n_pixels, n_frames, trial_energies,
                       workspace, as_stream(stream));

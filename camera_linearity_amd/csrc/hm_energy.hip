@@ -25,10 +25,10 @@
 // Batched forms (k_energy_pixel_batch, k_energy_partial_batch, k_energy_final_batch; energy_batch() below) serve
 // hm_de_generation_batch: the candidate dimension spans K problems x S candidates, candidate b belongs to problem b / S and
 // reads THAT problem's stack, and the workgroups of a problem whose stop flag is set return before their first store. The
-// kernel bodies repeat the single-stack kernels' operation for operation (energy_pixel_body, energy_partial_body; k_energy_final's
-// is shared) and the geometry and the chunk count come from the per-problem S and pixel count (energy_pixel_major,
-// energy_chunks), so a candidate's sums are formed in the same order - the same bits - whether its problem is evaluated alone
-// or in a batch.
+// kernel bodies are the single-stack kernels' own text, included a second time (hm_energy_pixel_body.h, hm_energy_partial_body.h;
+// k_energy_final's is a shared function) and the geometry and the chunk count come from the per-problem S and pixel count
+// (energy_pixel_major, energy_chunks), so a candidate's sums are formed in the same order - the same bits - whether its problem is
+// evaluated alone or in a batch.
 #include "hm_common.h"
 
 namespace hm {
@@ -86,119 +86,12 @@ __device__ __forceinline__ void pair_of(int p, int N, int& i, int& j) {
 
 template <bool STD>
 __global__ __launch_bounds__(256) void k_energy_partial(const EnergyK a) {
-    __shared__ double lut[256];
-    __shared__ double red[4][2];
-    const int b = blockIdx.z;
-    double* out = a.partial + ((static_cast<int64_t>(b) * gridDim.y + blockIdx.y) * a.chunks + blockIdx.x) * 2;
-    if (a.valid && !a.valid[b]) {                     // uniform per workgroup
-        if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; }
-        return;
-    }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
-    int i, j;
-    pair_of(blockIdx.y, a.N, i, j);
-    const double lo = lut[a.lower], hi = lut[a.upper];
-    const double ratio = a.t[i] / a.t[j];
-    const int N = a.N;
-
-    double num = 0.0, den = 0.0;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < a.P; p += stride) {
-        const uint8_t* px = a.dn + p * N;
-        double vi = lut[px[i]], vj = lut[px[j]];
-        if (vi < lo || vi > hi) vi = __builtin_nan("");
-        if (vj < lo || vj > hi) vj = __builtin_nan("");
-        const double scaled = vj * ratio;
-        double d = vi - scaled;
-        if (a.relative) d = d / scaled;
-        const double ad = fabs(d);
-        if (STD) {
-            const double si = a.sd[p * N + i], sj = a.sd[p * N + j];
-            double sigma;
-            if (a.relative) {
-                const double u = si / scaled;
-                const double v = (vi * sj) / (ratio * (vj * vj));
-                sigma = sqrt(u * u + v * v);
-            } else {
-                const double v = ratio * sj;
-                sigma = sqrt(si * si + v * v);
-            }
-            const bool finite = isfinite(ad) && sigma != 0.0;
-            const double w = 1.0 / sigma;
-            if (finite && w == w) { num += ad * w; den += w; }
-        } else {
-            if (ad == ad) { num += ad; den += 1.0; }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double s0 = wave_sum(num), s1 = wave_sum(den);
-    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        out[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-    }
+#include "hm_energy_partial_body.h"
 }
 
-// k_energy_partial's body once more, for k_energy_partial_batch: the single-stack kernel stays a kernel of its own text because
-// routing it through a shared device function moved its register allocation; the bytes-equal tests
-// of the batch against single plans hold the two copies to the same arithmetic
 template <bool STD>
 __device__ __forceinline__ void energy_partial_body(const EnergyK a) {
-    __shared__ double lut[256];
-    __shared__ double red[4][2];
-    const int b = blockIdx.z;
-    double* out = a.partial + ((static_cast<int64_t>(b) * gridDim.y + blockIdx.y) * a.chunks + blockIdx.x) * 2;
-    if (a.valid && !a.valid[b]) {                     // uniform per workgroup
-        if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; }
-        return;
-    }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
-    int i, j;
-    pair_of(blockIdx.y, a.N, i, j);
-    const double lo = lut[a.lower], hi = lut[a.upper];
-    const double ratio = a.t[i] / a.t[j];
-    const int N = a.N;
-
-    double num = 0.0, den = 0.0;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < a.P; p += stride) {
-        const uint8_t* px = a.dn + p * N;
-        double vi = lut[px[i]], vj = lut[px[j]];
-        if (vi < lo || vi > hi) vi = __builtin_nan("");
-        if (vj < lo || vj > hi) vj = __builtin_nan("");
-        const double scaled = vj * ratio;
-        double d = vi - scaled;
-        if (a.relative) d = d / scaled;
-        const double ad = fabs(d);
-        if (STD) {
-            const double si = a.sd[p * N + i], sj = a.sd[p * N + j];
-            double sigma;
-            if (a.relative) {
-                const double u = si / scaled;
-                const double v = (vi * sj) / (ratio * (vj * vj));
-                sigma = sqrt(u * u + v * v);
-            } else {
-                const double v = ratio * sj;
-                sigma = sqrt(si * si + v * v);
-            }
-            const bool finite = isfinite(ad) && sigma != 0.0;
-            const double w = 1.0 / sigma;
-            if (finite && w == w) { num += ad * w; den += w; }
-        } else {
-            if (ad == ad) { num += ad; den += 1.0; }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double s0 = wave_sum(num), s1 = wave_sum(den);
-    if (lane == 0) { red[wave][0] = s0; red[wave][1] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        out[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-    }
+#include "hm_energy_partial_body.h"
 }
 
 template <bool STD>
@@ -240,153 +133,12 @@ __device__ __forceinline__ double rcp_second_order(double x) {
 
 template <int N, bool STD>
 __global__ __launch_bounds__(256) void k_energy_pixel(const EnergyK a, const EnergyPairs pr) {
-    constexpr int P = N * (N - 1) / 2;
-    __shared__ double lut[256];
-    __shared__ double red[4][2 * P];
-    const int b = blockIdx.y;
-    const int pairs = P;
-    auto out_of = [&](int p) { return a.partial + ((static_cast<int64_t>(b) * pairs + p) * a.chunks + blockIdx.x) * 2; };
-    if (a.valid && !a.valid[b]) {
-        if (threadIdx.x < P) { double* o = out_of(threadIdx.x); o[0] = 0.0; o[1] = 0.0; }
-        return;
-    }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
-    const double lo = lut[a.lower], hi = lut[a.upper];
-    const bool rel = a.relative != 0;
-    double num[P], den[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) { num[p] = 0.0; den[p] = 0.0; }
-
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t px = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; px < a.P; px += stride) {
-        const uint8_t* q = a.dn + px * N;
-        double v[N], rv[N], s[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double x = lut[q[i]];
-            if (x < lo || x > hi) x = __builtin_nan("");                       // :96-97
-            v[i] = x;
-            rv[i] = HM_ENERGY_RCP ? rcp_second_order(x) : 1.0 / x;
-            s[i] = STD ? a.sd[px * N + i] : 0.0;
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-#pragma unroll
-            for (int j = i + 1; j < N; ++j, ++p) {
-                const double ratio = pr.ratio[p];
-                const double scaled = v[j] * ratio;                             // :111
-                double d = v[i] - scaled;                                        // :114
-                double inv_s = 0.0;
-                if (rel) { inv_s = rv[j] * pr.inv_ratio[p]; d = d * inv_s; }     // :117  d / scaled
-                const double ad = fabs(d);                                       // :120
-                if (STD) {
-                    double qq;
-                    if (rel) {
-                        const double u = s[i] * inv_s;                           // s_i / scaled
-                        const double w2 = ((v[i] * s[j]) * inv_s) * rv[j];       // (v_i s_j) / (ratio v_j^2)        :127
-                        qq = u * u + w2 * w2;
-                    } else {
-                        const double w2 = ratio * s[j];
-                        qq = s[i] * s[i] + w2 * w2;                              // :129
-                    }
-                    const double w = rsqrt_third_order(qq);                      // 1 / sigma
-                    const bool ok = isfinite(ad) && qq != 0.0 && w == w;         // :133-134, general_functions.py:164
-                    if (ok) { num[p] += ad * w; den[p] += w; }
-                } else {
-                    if (ad == ad) { num[p] += ad; den[p] += 1.0; }               // :138
-                }
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const double s0 = wave_sum(num[p]), s1 = wave_sum(den[p]);
-        if (lane == 0) { red[wave][2 * p] = s0; red[wave][2 * p + 1] = s1; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * P) {
-        const int p = threadIdx.x >> 1, k = threadIdx.x & 1;
-        out_of(p)[k] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    }
+#include "hm_energy_pixel_body.h"
 }
 
-// k_energy_pixel's body once more, for k_energy_pixel_batch (a copy for the same reason as energy_partial_body)
 template <int N, bool STD>
 __device__ __forceinline__ void energy_pixel_body(const EnergyK a, const EnergyPairs pr) {
-    constexpr int P = N * (N - 1) / 2;
-    __shared__ double lut[256];
-    __shared__ double red[4][2 * P];
-    const int b = blockIdx.y;
-    const int pairs = P;
-    auto out_of = [&](int p) { return a.partial + ((static_cast<int64_t>(b) * pairs + p) * a.chunks + blockIdx.x) * 2; };
-    if (a.valid && !a.valid[b]) {
-        if (threadIdx.x < P) { double* o = out_of(threadIdx.x); o[0] = 0.0; o[1] = 0.0; }
-        return;
-    }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
-    const double lo = lut[a.lower], hi = lut[a.upper];
-    const bool rel = a.relative != 0;
-    double num[P], den[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) { num[p] = 0.0; den[p] = 0.0; }
-
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    for (int64_t px = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; px < a.P; px += stride) {
-        const uint8_t* q = a.dn + px * N;
-        double v[N], rv[N], s[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double x = lut[q[i]];
-            if (x < lo || x > hi) x = __builtin_nan("");                       // :96-97
-            v[i] = x;
-            rv[i] = HM_ENERGY_RCP ? rcp_second_order(x) : 1.0 / x;
-            s[i] = STD ? a.sd[px * N + i] : 0.0;
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-#pragma unroll
-            for (int j = i + 1; j < N; ++j, ++p) {
-                const double ratio = pr.ratio[p];
-                const double scaled = v[j] * ratio;                             // :111
-                double d = v[i] - scaled;                                        // :114
-                double inv_s = 0.0;
-                if (rel) { inv_s = rv[j] * pr.inv_ratio[p]; d = d * inv_s; }     // :117  d / scaled
-                const double ad = fabs(d);                                       // :120
-                if (STD) {
-                    double qq;
-                    if (rel) {
-                        const double u = s[i] * inv_s;                           // s_i / scaled
-                        const double w2 = ((v[i] * s[j]) * inv_s) * rv[j];       // (v_i s_j) / (ratio v_j^2)        :127
-                        qq = u * u + w2 * w2;
-                    } else {
-                        const double w2 = ratio * s[j];
-                        qq = s[i] * s[i] + w2 * w2;                              // :129
-                    }
-                    const double w = rsqrt_third_order(qq);                      // 1 / sigma
-                    const bool ok = isfinite(ad) && qq != 0.0 && w == w;         // :133-134, general_functions.py:164
-                    if (ok) { num[p] += ad * w; den[p] += w; }
-                } else {
-                    if (ad == ad) { num[p] += ad; den[p] += 1.0; }               // :138
-                }
-            }
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const double s0 = wave_sum(num[p]), s1 = wave_sum(den[p]);
-        if (lane == 0) { red[wave][2 * p] = s0; red[wave][2 * p + 1] = s1; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * P) {
-        const int p = threadIdx.x >> 1, k = threadIdx.x & 1;
-        out_of(p)[k] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    }
+#include "hm_energy_pixel_body.h"
 }
 
 template <int N, bool STD>
@@ -455,17 +207,24 @@ static void energy_pair_ratios(EnergyPairs& pr, const double* exposures, int n_f
         }
 }
 
+// the kernel arguments of one launch (validated by the caller); a batch passes no stack here: on_stack_of() gives each problem its own
+static EnergyK energy_args(const uint8_t* dn, const double* std, const double* exposures, const double* icrf, const uint8_t* valid,
+                           int lower, int upper, int relative, int64_t n_pixels, int n_frames, void* workspace) {
+    EnergyK k{};
+    k.dn = dn; k.sd = std; k.icrf = icrf; k.valid = valid; k.partial = static_cast<double*>(workspace);
+    k.P = n_pixels; k.N = n_frames; k.lower = lower; k.upper = upper; k.relative = relative;
+    k.chunks = energy_chunks(n_pixels);
+    for (int i = 0; i < n_frames; ++i) k.t[i] = exposures[i];
+    return k;
+}
+
 // hm_de_generation_batch's energy stage (arguments validated there): the relative energies of the S candidates of each of
 // K problems, rows k S .. k S + S - 1 of icrf / valid / out_energy, on problem k's stack; workspace as K single launches.
 int energy_batch(const uint8_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
                  const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels,
                  int n_frames, double* out_energy, void* workspace, hipStream_t st) {
     const int pairs = n_frames * (n_frames - 1) / 2, total = n_problems * pop_size;
-    EnergyK k{};
-    k.icrf = icrf; k.valid = valid; k.partial = static_cast<double*>(workspace);
-    k.P = n_pixels; k.N = n_frames; k.lower = lower; k.upper = upper; k.relative = 1;
-    k.chunks = energy_chunks(n_pixels);
-    for (int i = 0; i < n_frames; ++i) k.t[i] = exposures[i];
+    const EnergyK k = energy_args(nullptr, nullptr, exposures, icrf, valid, lower, upper, 1, n_pixels, n_frames, workspace);
     EnergyBatch q{};
     for (int i = 0; i < n_problems; ++i) { q.dn[i] = dn[i]; q.sd[i] = std ? std[i] : nullptr; }
     q.status = status; q.S = pop_size;
@@ -510,11 +269,7 @@ extern "C" int hm_linearity_energy(const uint8_t* dn, const double* std, const d
     if (n_candidates > 65535) return HM_EUNSUPPORTED;
     if (!dn || !exposures || !icrf || !out_energy || !workspace) return HM_EINVAL;
     const int pairs = n_frames * (n_frames - 1) / 2;
-    EnergyK k{};
-    k.dn = dn; k.sd = std; k.icrf = icrf; k.valid = valid; k.partial = static_cast<double*>(workspace);
-    k.P = n_pixels; k.N = n_frames; k.lower = lower; k.upper = upper; k.relative = use_relative ? 1 : 0;
-    k.chunks = energy_chunks(n_pixels);
-    for (int i = 0; i < n_frames; ++i) k.t[i] = exposures[i];
+    const EnergyK k = energy_args(dn, std, exposures, icrf, valid, lower, upper, use_relative ? 1 : 0, n_pixels, n_frames, workspace);
     if (energy_pixel_major(n_frames, n_candidates, n_pixels)) {
         EnergyPairs pr{};
         energy_pair_ratios(pr, exposures, n_frames);

@@ -1215,26 +1215,46 @@ def noise_profile_clean_edges(profiles: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # ICRF-calibration energy function (modules/ICRF_calibration_exposure.py:66-201), batched over candidates
 # ------------------------------------------------------------------------------------------------
+def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures, batch: bool = False):
+    """The uint8 (X, Y, N) stacks of a calibration - one, or those of a batch: one shape, one device -, their float64 std stacks (None,
+    or a sequence whose entries are all None: no stds) and the N exposures, checked in this order
+    -> (contiguous stacks, contiguous std stacks | None, exposures as a float64 array). `batch` words the std messages for a batch, whose
+    std stacks must also live on the stacks' device."""
+    first = dn_stacks[0]
+    for s in dn_stacks:
+        _require_cuda(s, "image_value_stack")
+        if s.dtype != torch.uint8:
+            raise TypeError("image_value_stack must be uint8 digital numbers")
+        if s.dim() != 3:
+            raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")             # ICRF_calibration_exposure.py:82-83
+        if s.shape != first.shape:
+            raise ValueError(f"the stacks of a batch must have one shape: {tuple(s.shape)} != {tuple(first.shape)}")
+        if s.device != first.device:
+            raise ValueError(f"the stacks of a batch must live on one device: {s.device} != {first.device}")
+    t = np.asarray(exposures, dtype=np.float64)
+    if t.ndim != 1 or t.size != first.shape[2]:
+        raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
+    if std_stacks is None or all(s is None for s in std_stacks):
+        return [s.contiguous() for s in dn_stacks], None, t
+    std_stacks = list(std_stacks)
+    if len(std_stacks) != len(dn_stacks) or any(s is None for s in std_stacks):
+        raise ValueError("image_std_stacks must be given for every stack of a batch or for none")
+    for s in std_stacks:
+        _require_cuda(s, "image_std_stack")
+        if s.shape != first.shape or s.dtype != _F64 or (batch and s.device != first.device):
+            raise ValueError("image_std_stack must be float64, shaped like image_value_stack and on its device" if batch else
+                             "image_std_stack must be float64 and shaped like image_value_stack")
+    return [s.contiguous() for s in dn_stacks], [s.contiguous() for s in std_stacks], t
+
+
 def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], icrf_batch,
                      lower: int, upper: int, valid=None, use_relative: bool = True, return_pairs: bool = False):
     """Energy of every candidate ICRF row of `icrf_batch` ((B, 256) float64) on one channel's (X, Y, N) uint8 stack.
     -> energies (B,) float64 device tensor [, pair results (B, N(N-1)/2)]."""
-    _require_cuda(dn_stack, "image_value_stack")
-    if dn_stack.dtype != torch.uint8:
-        raise TypeError("image_value_stack must be uint8 digital numbers")
-    if dn_stack.dim() != 3:
-        raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")             # ICRF_calibration_exposure.py:82-83
+    (dn_stack,), sd, t = _check_stacks([dn_stack], [std_stack], exposures)
+    std_stack = None if sd is None else sd[0]
     dev = dn_stack.device
     N = dn_stack.shape[2]
-    t = np.asarray(exposures, dtype=np.float64)
-    if t.ndim != 1 or t.size != N:
-        raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
-    dn_stack = dn_stack.contiguous()
-    if std_stack is not None:
-        _require_cuda(std_stack, "image_std_stack")
-        if std_stack.shape != dn_stack.shape or std_stack.dtype != _F64:
-            raise ValueError("image_std_stack must be float64 and shaped like image_value_stack")
-        std_stack = std_stack.contiguous()
     lut = _dev_f64(icrf_batch, dev)
     if lut.dim() == 1:
         lut = lut[None]
@@ -1266,7 +1286,64 @@ def _status_dict(w: np.ndarray) -> dict:
                 mean=float(f[nat.HM_DE_MEAN]), std=float(f[nat.HM_DE_STD]))
 
 
-class DEPlan:
+class _DEPlanBase:
+    """What DEPlan and DEBatchPlan share: one native call per generation, `check_every` of them recorded as one linear chain and
+    replayed until the plan has stopped. A subclass sets `device` and `host`, names its entry point (`_entry`) and supplies
+    `_call(stream)` (the native call -> status code), `read_status()` and `_stopped(status)`."""
+    _entry = ""
+    _graph = None
+    _graph_len = 0
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        """Enqueue one generation - of every problem, for a batch - on `stream` (default: the current stream of the plan's device)."""
+        if self.host:
+            with nat.host_mode():
+                nat.check(self._call(None), self._entry)
+            return
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with _on(self.device):
+            rc = self._call(stream)
+        if rc:
+            nat.check(rc, self._entry)
+
+    def _record(self, n: int) -> None:
+        """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
+        dev = self.device
+        with torch.cuda.device(dev):
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                self.launch(side.cuda_stream)           # first launches load the kernels' code objects: outside the capture
+                self._graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self._graph, stream=side):
+                    for _ in range(n):
+                        self.launch(side.cuda_stream)
+            torch.cuda.current_stream(dev).wait_stream(side)
+        self._graph_len = n
+
+    def run(self, check_every: int = 8, graph: bool = True):
+        """Advance until the stop flag is set - EVERY problem's, for a batch: `check_every` generations per status read.
+        -> the final read_status()."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise ValueError("check_every must be >= 1")
+        use_graph = graph and not self.host
+        if use_graph and self._graph_len != check_every:
+            self._record(check_every)                   # (runs generation 0 as its warm-up launch)
+        while True:
+            if use_graph:
+                with _on(self.device):
+                    self._graph.replay()
+            else:
+                for _ in range(check_every):
+                    self.launch()
+            st = self.read_status()
+            if self._stopped(st):
+                return st
+
+
+class DEPlan(_DEPlanBase):
     """The state of one channel's differential-evolution solve (population, energies, trial rows, candidate ICRFs, verdicts, status block,
     workspace - all on the stack's device) and the launches that advance it. `launch()` enqueues ONE generation (hm_de_generation: trial
     kernel, the energy kernels, select kernel); the generation counter and the stop flag live in the status block on the device, so
@@ -1274,29 +1351,17 @@ class DEPlan:
     the status block back once per replay. `graph=False` issues the same calls eagerly. After the stop flag is set a generation is a
     no-op, so the result does not depend on `check_every`. Built inside nat.host_mode() on a host stack, it calls the host build in a
     loop (no graph)."""
+    _entry = "hm_de_generation"
 
     def __init__(self, dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], mean_icrf, pca,
                  lower_limits, upper_limits, population, lower: int, upper: int, seed: int, max_generations: int,
                  mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0):
-        _require_cuda(dn_stack, "image_value_stack")
-        if dn_stack.dtype != torch.uint8:
-            raise TypeError("image_value_stack must be uint8 digital numbers")
-        if dn_stack.dim() != 3:
-            raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")             # ICRF_calibration_exposure.py:82-83
+        (self.dn,), sd, t = _check_stacks([dn_stack], [std_stack], exposures)
+        self.std = None if sd is None else sd[0]
         dev = dn_stack.device
         self.device = dev
         self.host = dev.type != "cuda"
         N = dn_stack.shape[2]
-        t = np.asarray(exposures, dtype=np.float64)
-        if t.ndim != 1 or t.size != N:
-            raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
-        self.dn = dn_stack.contiguous()
-        self.std = None
-        if std_stack is not None:
-            _require_cuda(std_stack, "image_std_stack")
-            if std_stack.shape != dn_stack.shape or std_stack.dtype != _F64:
-                raise ValueError("image_std_stack must be float64 and shaped like image_value_stack")
-            self.std = std_stack.contiguous()
         pop = np.ascontiguousarray(np.asarray(population, dtype=np.float64))
         if pop.ndim != 2:
             raise ValueError("population must be (S, P) in scaled coordinates [0, 1]")
@@ -1323,71 +1388,25 @@ class DEPlan:
         with nat.host_mode() if self.host else _NoDevice():
             ws_bytes = nat.lib.hm_de_workspace_bytes(self.n_pixels, N, S)
         self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
-        self._graph = None
-        self._graph_len = 0
 
-    def launch(self, stream: Optional[int] = None) -> None:
-        """Enqueue one generation on `stream` (default: the current stream of the plan's device)."""
+    def _call(self, stream):
         lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
-
-        def call(st):
-            return nat.lib.hm_de_generation(self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
-                                            self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
-                                            self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(), self.lo.data_ptr(),
-                                            self.hi.data_ptr(), self.dn.data_ptr(), nat.ptr(self.std), self._t, self.n_pixels, self.N,
-                                            lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim, self.workspace.data_ptr(), st)
-        if self.host:
-            with nat.host_mode():
-                nat.check(call(None), "hm_de_generation")
-            return
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        with _on(self.device):
-            rc = call(stream)
-        if rc:
-            nat.check(rc, "hm_de_generation")
+        return nat.lib.hm_de_generation(self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
+                                        self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
+                                        self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(), self.lo.data_ptr(),
+                                        self.hi.data_ptr(), self.dn.data_ptr(), nat.ptr(self.std), self._t, self.n_pixels, self.N,
+                                        lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim, self.workspace.data_ptr(), stream)
 
     def read_status(self) -> dict:
         """The status block, copied to the host (this synchronises): generation = the number of generations after the initial
         evaluation that have run."""
         return _status_dict(self.status.cpu().numpy())
 
-    def _record(self, n: int) -> None:
-        """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
-        dev = self.device
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self.launch(side.cuda_stream)           # first launches load the kernels' code objects: outside the capture
-                self._graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph, stream=side):
-                    for _ in range(n):
-                        self.launch(side.cuda_stream)
-            torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph_len = n
-
-    def run(self, check_every: int = 8, graph: bool = True) -> dict:
-        """Advance until the stop flag is set: `check_every` generations per status read. -> the final read_status()."""
-        check_every = int(check_every)
-        if check_every < 1:
-            raise ValueError("check_every must be >= 1")
-        use_graph = graph and not self.host
-        if use_graph and self._graph_len != check_every:
-            self._record(check_every)                   # (runs generation 0 as its warm-up launch)
-        while True:
-            if use_graph:
-                with _on(self.device):
-                    self._graph.replay()
-            else:
-                for _ in range(check_every):
-                    self.launch()
-            st = self.read_status()
-            if st["stop"]:
-                return st
+    def _stopped(self, status: dict) -> bool:
+        return bool(status["stop"])
 
 
-class DEBatchPlan:
+class DEBatchPlan(_DEPlanBase):
     """K independent differential-evolution problems of one shape - the channels of a calibration, restarts of a channel with other seeds,
     or both - advanced by ONE set of launches per generation (hm_de_generation_batch: trial kernel on (S, K) workgroups, the energy
     kernels on K x S candidates, select kernel on K workgroups). Problem k reads stack `stack_of[k]` of `dn_stacks` (default: its own),
@@ -1396,6 +1415,7 @@ class DEBatchPlan:
     a problem whose stop flag is set costs no further work while the others run. `run()` records `check_every` generations as one
     linear chain (hipGraph), replays it until ALL stop flags are set and reads the K status blocks back with one copy per replay.
     Built inside nat.host_mode() on host stacks, it calls the host build in a loop (no graph)."""
+    _entry = "hm_de_generation_batch"
 
     def __init__(self, dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures: Sequence[float],
                  mean_icrfs, pcas, lower_limits, upper_limits, populations, lower: int, upper: int, seeds: Sequence[int],
@@ -1404,34 +1424,11 @@ class DEBatchPlan:
         dn_stacks = list(dn_stacks)
         if not dn_stacks:
             raise ValueError("dn_stacks must hold at least one stack")
-        for s in dn_stacks:
-            _require_cuda(s, "image_value_stack")
-            if s.dtype != torch.uint8:
-                raise TypeError("image_value_stack must be uint8 digital numbers")
-            if s.dim() != 3:
-                raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")         # ICRF_calibration_exposure.py:82-83
-            if s.shape != dn_stacks[0].shape:
-                raise ValueError(f"the stacks of a batch must have one shape: {tuple(s.shape)} != {tuple(dn_stacks[0].shape)}")
-            if s.device != dn_stacks[0].device:
-                raise ValueError(f"the stacks of a batch must live on one device: {s.device} != {dn_stacks[0].device}")
+        self.dn, self.std, t = _check_stacks(dn_stacks, std_stacks, exposures, batch=True)
         dev = dn_stacks[0].device
         self.device = dev
         self.host = dev.type != "cuda"
         N = dn_stacks[0].shape[2]
-        t = np.asarray(exposures, dtype=np.float64)
-        if t.ndim != 1 or t.size != N:
-            raise ValueError("exposure_values must be a 1D array matching the third dimension of image_stack.")   # :85-86
-        self.dn = [s.contiguous() for s in dn_stacks]
-        self.std = None
-        if std_stacks is not None and any(s is not None for s in std_stacks):
-            std_stacks = list(std_stacks)
-            if len(std_stacks) != len(dn_stacks) or any(s is None for s in std_stacks):
-                raise ValueError("image_std_stacks must be given for every stack of a batch or for none")
-            for s in std_stacks:
-                _require_cuda(s, "image_std_stack")
-                if s.shape != dn_stacks[0].shape or s.dtype != _F64 or s.device != dev:
-                    raise ValueError("image_std_stack must be float64, shaped like image_value_stack and on its device")
-            self.std = [s.contiguous() for s in std_stacks]
         pop = np.ascontiguousarray(np.asarray(populations, dtype=np.float64))
         if pop.ndim != 3:
             raise ValueError("populations must be (K, S, P) in scaled coordinates [0, 1]")
@@ -1475,66 +1472,20 @@ class DEBatchPlan:
         with nat.host_mode() if self.host else _NoDevice():
             ws_bytes = nat.lib.hm_de_batch_workspace_bytes(self.n_pixels, N, S, K)
         self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
-        self._graph = None
-        self._graph_len = 0
 
-    def launch(self, stream: Optional[int] = None) -> None:
-        """Enqueue one generation of every problem on `stream` (default: the current stream of the plan's device)."""
+    def _call(self, stream):
         lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
-
-        def call(st):
-            return nat.lib.hm_de_generation_batch(self.K, self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
-                                                  self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
-                                                  self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(),
-                                                  self.lo.data_ptr(), self.hi.data_ptr(), self._dn, self._sd, self._seeds, self._t,
-                                                  self.n_pixels, self.N, lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim,
-                                                  self.workspace.data_ptr(), st)
-        if self.host:
-            with nat.host_mode():
-                nat.check(call(None), "hm_de_generation_batch")
-            return
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        with _on(self.device):
-            rc = call(stream)
-        if rc:
-            nat.check(rc, "hm_de_generation_batch")
+        return nat.lib.hm_de_generation_batch(self.K, self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
+                                              self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
+                                              self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(),
+                                              self.lo.data_ptr(), self.hi.data_ptr(), self._dn, self._sd, self._seeds, self._t,
+                                              self.n_pixels, self.N, lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim,
+                                              self.workspace.data_ptr(), stream)
 
     def read_status(self) -> list:
         """The K status blocks from ONE copy to the host (this synchronises): a list of DEPlan.read_status() dicts."""
         w = self.status.cpu().numpy()
         return [_status_dict(w[k]) for k in range(self.K)]
 
-    def _record(self, n: int) -> None:
-        """Record n generations as one linear chain (warm-up launch outside the capture: it is a real generation, the first of the run)."""
-        dev = self.device
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self.launch(side.cuda_stream)           # first launches load the kernels' code objects: outside the capture
-                self._graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph, stream=side):
-                    for _ in range(n):
-                        self.launch(side.cuda_stream)
-            torch.cuda.current_stream(dev).wait_stream(side)
-        self._graph_len = n
-
-    def run(self, check_every: int = 8, graph: bool = True) -> list:
-        """Advance until EVERY problem's stop flag is set: `check_every` generations per status read. -> the final read_status()."""
-        check_every = int(check_every)
-        if check_every < 1:
-            raise ValueError("check_every must be >= 1")
-        use_graph = graph and not self.host
-        if use_graph and self._graph_len != check_every:
-            self._record(check_every)                   # (runs generation 0 as its warm-up launch)
-        while True:
-            if use_graph:
-                with _on(self.device):
-                    self._graph.replay()
-            else:
-                for _ in range(check_every):
-                    self.launch()
-            st = self.read_status()
-            if all(s["stop"] for s in st):
-                return st
+    def _stopped(self, status: list) -> bool:
+        return all(s["stop"] for s in status)

@@ -334,6 +334,38 @@ def test_solver_argument_errors():
         ic.calibration([None], [pr["pca"]], pr["stacks"], [None], pr["t"], -1.0, 1.0, initial_function=np.linspace(0, 1, 256), solver="device")
     with pytest.raises(ValueError):
         make_plan(pr, np.full((16, 3), 0.5)).run(0)
+    # the stack / std stack / exposure checks that DEPlan and linearity_energy share, and DEPlan's own model checks
+    eng, pop, icrfs = ic._engine_for(pr["stack"]), np.full((16, 3), 0.5), np.linspace(0, 1, 256)[None]
+
+    def plan(stack=pr["stack"], std=None, t=pr["t"], mean=pr["mean"], pca=pr["pca"], pop=pop):
+        return eng.DEPlan(stack, std, t, mean, pca, -1.0, 1.0, pop, 5, 250, 11, 10)
+
+    def energy(stack=pr["stack"], std=None, t=pr["t"]):
+        return eng.linearity_energy(stack, std, t, icrfs, 5, 250)
+    assert plan().S == 16 and energy().shape == (1,)
+    sd = torch.full(tuple(pr["stack"].shape), 0.01, dtype=torch.float64)
+    assert plan(std=sd).std is not None and energy(std=sd).shape == (1,)
+    for build in (plan, energy):
+        with pytest.raises(TypeError, match="must be uint8 digital numbers"):
+            build(stack=pr["stack"].to(torch.float64))
+        with pytest.raises(ValueError, match=r"3D array with shape \(X, Y, N\)"):
+            build(stack=pr["stack"][0])
+        with pytest.raises(ValueError, match="exposure_values must be a 1D array matching the third dimension"):
+            build(t=pr["t"][:4])
+        with pytest.raises(ValueError, match="image_std_stack must be float64 and shaped like image_value_stack"):
+            build(std=sd.to(torch.float32))
+        with pytest.raises(ValueError, match="image_std_stack must be float64 and shaped like image_value_stack"):
+            build(std=sd[:, :-1])
+        with pytest.raises(TypeError, match="image_value_stack must be a torch.Tensor"):
+            build(stack=pr["stack"].numpy())
+    with pytest.raises(ValueError, match=r"population must be \(S, P\)"):
+        plan(pop=pop[0])
+    with pytest.raises(ValueError, match=r"mean ICRF must have 256 entries and the PCA basis must be \(256, 3\)"):
+        plan(mean=pr["mean"][:255])
+    with pytest.raises(ValueError, match=r"mean ICRF must have 256 entries and the PCA basis must be \(256, 3\)"):
+        plan(pca=pr["pca"][:, :2])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):                           # host tensors outside host_mode(): the HIP backend refuses
+        ic.engine.DEPlan(pr["stack"], None, pr["t"], pr["mean"], pr["pca"], -1.0, 1.0, pop, 5, 250, 11, 10)
 
 
 def test_host_stack_never_reaches_the_hip_library():
