@@ -81,6 +81,9 @@ _SIGNATURES = {
     "hm_merge_std_table": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p]),
     "hm_merge_std_table_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int]),
     "hm_merge_std_table_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
+    "hm_merge_std_f32": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p]),
+    "hm_merge_std_f32_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int]),
+    "hm_merge_std_f32_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
     "hm_hot_pixel_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,

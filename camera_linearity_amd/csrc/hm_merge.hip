@@ -18,17 +18,20 @@
 //                     hm_merge_nf.h (with merge_u8_fast_std_lut, the per-DN std table's form), instantiated per range of frame
 //                     counts by hm_merge_nf_*.hip.
 //   merge_u8_loop / merge_u8_loop_std   uint8 frames, run-time N (17..32) and C (1..4): same decomposition, frames in chunks.
-//                     hm_merge_loop.hip
+//                     hm_merge_loop.h, instantiated by hm_merge_loop.hip (and hm_merge_loop_sd32.hip)
 //   merge_f64_val / merge_f64_std       float64 frames (64-bit mode): analytic weight, computed LUT index.
 //                     hm_merge_f64.hip
 //   merge_generic     anything else (tails shorter than a group, unaligned tiles, forced by variant < 0):
-//                     one element per thread. hm_merge_hot.hip, with the hot-pixel kernels:
+//                     one element per thread. hm_merge_hot.h (instantiated by hm_merge_hot.hip and hm_merge_hot_sd32.hip), with the hot-pixel kernels:
 //   merge_scan_hot + merge_patch_hot    dark-frame hot pixels: the streaming kernels never look at the dark maps; a scan reads every
 //                     distinct map once (the d term of the algorithmic byte count) and queues the hot elements, a second kernel
 //                     recomputes one queued element per lane with the k x k medians substituted (needs the caller's workspace).
 //   merge_fixup_hot   the same pass without a workspace: one hot element per wave at a time (sparse maps only).
 // Every kernel that stores val / std has a template parameter OUT (hm_merge_args.out_kind): OUT_F64 stores the float64 result,
 // OUT_F32 rounds it once in registers (v_cvt_f32_f64, round to nearest even) and stores 4-byte elements. Nothing else differs.
+// Every kernel that reads std frames has a template parameter SD (hm_merge_std_f32): SD = float reads 4-byte std elements and widens each
+// once in registers (exact), so the result equals that of the widened frames bit for bit. Its instantiations live in units of their own
+// (hm_merge_nf_sd32.hip, hm_merge_loop_sd32.hip, hm_merge_hot_sd32.hip).
 //
 // This file is the host side of the call: argument validation, the dispatch (merge_entry, merge_one_launch) and the C entry points.
 // It holds no kernel and instantiates none: hm_merge_dev.h has what the families share on the device, hm_merge_host.h the describe
@@ -48,7 +51,9 @@ bool describe_only(const char* fmt, int a, int b, int c, int d, bool quad) {
     // the strings of float64 calls stay as they were
     // table calls: likewise every kernel that forms a std (in such a call: every kernel with a template argument list) carries "std=lut"
     size_t close = name.find('>');
+    // float32-std calls (hm_merge_std_f32): likewise "std=f32" - merge_scan_hot, which reads no std, has no argument list
     if (g_describe->lut && close != std::string::npos) { name.insert(close, ",std=lut"); close = name.find('>'); }
+    if (g_describe->sd32 && close != std::string::npos) { name.insert(close, ",std=f32"); close = name.find('>'); }
     if (g_describe->f32 && close != std::string::npos) name.insert(close, quad ? ",out=f32x4" : ",out=f32");
     if (!g_describe->names.empty()) g_describe->names += " + ";
     g_describe->names += name;
@@ -85,13 +90,14 @@ static int fast_group_elems(int n_frames, int variant, const FastCfg& c, bool wi
 }  // namespace hm
 
 // lut: the call is hm_merge_std_table - std outputs (and the flat field's std) without the N float64 std streams
-static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
+// sd32: the call is hm_merge_std_f32 - N float32 std streams (g->stds is NULL in both)
+static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut, bool sd32 = false) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
     const int N = g->n_frames;
-    const bool s = lut || g->stds != nullptr;
+    const bool s = lut || sd32 || g->stds != nullptr;
     const int64_t in_b = g->frames_f64 ? 8 : 1;
-    int64_t per = N * (in_b + ((s && !lut) ? 8 : 0));
+    int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
@@ -108,6 +114,7 @@ static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
 }
 extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
 extern "C" int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
+extern "C" int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false, true); }
 
 // Workspace of the hot-pixel queue for a call that produces n_elems = rows * W * C output elements: 16 bytes of counters, the piece
 // table (8 bytes per 65 536 elements + 8 KB) and one uint32 per queued element. The recommended size holds a quarter of the elements
@@ -124,7 +131,7 @@ extern "C" size_t hm_merge_hot_workspace_bytes(int64_t n_elems) {
     return hm_merge_hot_workspace_min_bytes(n_elems) + static_cast<size_t>(entries - 1) * 4;
 }
 
-static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream);
+static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream, bool sd32 = false);
 
 static int merge_describe(const hm_merge_args* g, const double* std_table, bool table_call, char* buf, int buf_len) {
     if (!buf || buf_len < 1) return HM_EINVAL;
@@ -139,6 +146,16 @@ extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len)
 extern "C" int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table, char* buf, int buf_len) {
     if (!g) return HM_EINVAL;                              // before anything else is read - or written
     return merge_describe(g, std_table, true, buf, buf_len);
+}
+extern "C" int hm_merge_std_f32_describe(const hm_merge_args* g, const float* const* stds_f32, char* buf, int buf_len) {
+    if (!g) return HM_EINVAL;                              // before anything else is read - or written
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    hm::DescribeCtx ctx;                                   // f32 / sd32: set by merge_entry once it has accepted such a call
+    hm::g_describe = &ctx;
+    const int rc = hm_merge_std_f32(g, stds_f32, nullptr);
+    hm::g_describe = nullptr;
+    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
+    return rc;
 }
 
 // struct_size values hm_merge accepts: the current layout and the two older ones of ABI version 1 (without the hot-pixel queue
@@ -156,7 +173,7 @@ static bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
 }
 
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool f64in, bool with_std, bool flat, bool hot, void* stream);
+static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool sd32, bool f64in, bool with_std, bool flat, bool hot, void* stream);
 
 extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) { return merge_entry(g_in, nullptr, stream); }
 
@@ -173,8 +190,28 @@ extern "C" int hm_merge_std_table(const hm_merge_args* g_in, const double* std_t
     return merge_entry(&full, full.out_val ? std_table : nullptr, stream);
 }
 
+// hm_merge_std_f32: the call's own argument rules, then hm_merge's path with the float32 frames in the place of args->stds
+extern "C" int hm_merge_std_f32(const hm_merge_args* g_in, const float* const* stds_f32, void* stream) {
+    if (!g_in) return HM_EINVAL;
+    hm_merge_args full;
+    if (!widen_args(g_in, full)) return HM_EINVAL;
+    if (full.stds || !stds_f32) return HM_EINVAL;
+    for (int i = 0; i < full.n_frames; ++i)
+        if (!stds_f32[i]) return HM_EINVAL;
+    if (!full.icrf_diff) return HM_EINVAL;
+    if (full.frames_u8 && !full.dw_lut) return HM_EINVAL;
+    if (full.out_val && !full.out_std) return HM_EINVAL;
+    for (int i = 0; i < full.n_frames; ++i)
+        if (!hm::aligned(stds_f32[i], 4)) return HM_EALIGN;
+    // a call without out_val forms no std: it is hm_merge's sum-of-weights call
+    if (!full.out_val) return merge_entry(&full, nullptr, stream);
+    full.stds = reinterpret_cast<const double* const*>(stds_f32);
+    return merge_entry(&full, nullptr, stream, true);
+}
+
 // std_table != NULL (from hm_merge_std_table only; g->stds is NULL then): the stds come from the per-DN table
-static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream) {
+// sd32 (from hm_merge_std_f32 only): g->stds addresses float32 frames, 4-byte aligned
+static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream, bool sd32) {
     using namespace hm;
     hm_merge_args full;
     if (!widen_args(g_in, full)) return HM_EINVAL;
@@ -222,7 +259,7 @@ static int merge_entry(const hm_merge_args* g_in, const double* std_table, void*
         if (f64in && !aligned(f, 8)) return HM_EALIGN;
         if (g->stds) {
             if (!g->stds[i]) return HM_EINVAL;
-            if (!aligned(g->stds[i], 8)) return HM_EALIGN;
+            if (!aligned(g->stds[i], sd32 ? 4 : 8)) return HM_EALIGN;
         }
         if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
     }
@@ -235,7 +272,9 @@ static int merge_entry(const hm_merge_args* g_in, const double* std_table, void*
                    g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     // the per-DN std table exists in the one-launch kernels only (hm_merge_chunk.hip reads std frames)
     if (std_table && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
-    if (g_describe) { g_describe->f32 = f32out; g_describe->lut = std_table != nullptr; }
+    // ... and so do float32 std frames
+    if (sd32 && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
+    if (g_describe) { g_describe->f32 = f32out; g_describe->lut = std_table != nullptr; g_describe->sd32 = sd32; }
     // More frames than one launch takes (modules/exposure_series.py:334,372 have no limit): HM_MAX_FRAMES per launch with the running
     // sums in memory (hm_merge_chunk.hip). variant <= -2 forces that path with -variant frames per chunk (tests: any chunking gives the
     // bits of the one-launch kernels).
@@ -264,19 +303,19 @@ static int merge_entry(const hm_merge_args* g_in, const double* std_table, void*
                 if (g->flat_u8) b.flat_u8 = g->flat_u8 + adv;
                 if (g->flat_f64) b.flat_f64 = g->flat_f64 + adv;
                 if (g->flat_std) b.flat_std = g->flat_std + adv;
-                const int rc_b = merge_entry(&b, std_table, stream);
+                const int rc_b = merge_entry(&b, std_table, stream, sd32);
                 if (rc_b != HM_OK) return rc_b;
             }
             return HM_OK;
         }
     }
-    return f32out ? merge_one_launch<OUT_F32>(g, std_table, f64in, with_std, flat, hot, stream)
-                  : merge_one_launch<OUT_F64>(g, std_table, f64in, with_std, flat, hot, stream);
+    return f32out ? merge_one_launch<OUT_F32>(g, std_table, sd32, f64in, with_std, flat, hot, stream)
+                  : merge_one_launch<OUT_F64>(g, std_table, sd32, f64in, with_std, flat, hot, stream);
 }
 
 // One streaming launch (+ generic tail + hot-pixel pass) for validated arguments; OUT = element type of out_val / out_std.
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
+static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool sd32, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
     using namespace hm;
     const int N = g->n_frames, C = g->channels;
     const bool f32_pairs = OUT == OUT_F32 && g->variant == kVariantF32Pairs;      // float32 A/B: the default dispatch without the QUAD map
@@ -318,7 +357,8 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
     } else if (!decode_variant(variant, with_std, cfg)) return HM_EINVAL;
     // (the per-DN std table: uint8 frames stream through the kernels that hold it in LDS; float64 frames go to merge_generic - merge_f64_std reads std frames)
     const bool lut = std_table != nullptr;
-    bool fast = g->out_val && E < (int64_t{1} << 32) && variant >= 0 && !(lut && f64in);
+    // (float32 std frames likewise: uint8 frames stream, float64 frames go to merge_generic)
+    bool fast = g->out_val && E < (int64_t{1} << 32) && variant >= 0 && !((lut || sd32) && f64in);
     // (float32 outputs: templated kernels for the frame counts of kF32Templated() only - build time; the others take the run-time-N kernels)
     const bool templated = OUT == OUT_F64 || kF32Templated(N);
     const bool mono_val3 = templated && use_val3_mono(k, with_std, f64in);
@@ -327,13 +367,15 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
     // Templates up to kTemplatedN = 20 frames (round 4, late: 16 before). On 2048 x 4096 x 3 stacks the templated kernels beat the run-time-N
     // kernel at N = 17 (val-only 115 against 130 us, with std 790 against 880 us) and N = 20 (132 against 150, 985 against 1 025 us) and lose from
     // N = 24 (with std) / 32 (val-only) on, where their per-frame register arrays no longer fit (profiles/r04z_n32_templates_ab.log).
-    const bool loop_kernel = lut ? !lut_templated
+    const bool sd32_templated = use_fast_sd32(k, sd32, f64in);
+    const bool loop_kernel = lut ? !lut_templated : sd32 ? !sd32_templated
                                  : (f64in || N > kTemplatedN || C != 3 || !templated) && !mono_val3 && !mono_std;   // run-time-N / any-C streaming kernel instead of the templates
     if (fast) {
         for (int i = 0; i < N && fast; ++i) {
             fast = f64in ? aligned(static_cast<const double*>(k.frame[i]) + k.in_off, 16)
                          : aligned(static_cast<const uint8_t*>(k.frame[i]) + k.in_off, 2);
-            if (fast && with_std && !lut) fast = aligned(k.sd[i] + k.in_off, 16);
+            // (float32 stds: the lane's pair is one 8-byte load - the first element at an even offset, every std buffer 8-byte aligned there)
+            if (fast && with_std && !lut) fast = sd32 ? (k.in_off % 2 == 0 && aligned(k.sd_as<float>(i) + k.in_off, 8)) : aligned(k.sd[i] + k.in_off, 16);
         }
         constexpr int pair_bytes = OUT == OUT_F32 ? 8 : 16;                  // one lane's two output elements
         fast = fast && aligned(k.out_val, pair_bytes) && (!k.out_std || aligned(k.out_std, pair_bytes)) &&
@@ -341,9 +383,12 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
         if (fast && flat)
             fast = (k.flat_u8 ? aligned(k.flat_u8, 2) : aligned(k.flat_f64, 16)) && (!with_std || aligned(k.flat_std, 16));
     }
+    // the families with a std element type: SD = float for hm_merge_std_f32
+    const auto generic = [&](const MergeK& kk) { return sd32 ? launch_generic<OUT, float>(kk, f64in, with_std, st) : launch_generic<OUT>(kk, f64in, with_std, st); };
+    const auto loop = [&](const MergeK& kk) { return sd32 ? launch_loop<OUT, float>(kk, with_std, st) : launch_loop<OUT>(kk, with_std, st); };
     int rc = HM_OK;
     if (!fast) {
-        rc = launch_generic<OUT>(k, f64in, with_std, st);
+        rc = generic(k);
     } else {
         const int64_t grp = loop_kernel ? static_cast<int64_t>(kSub) : lut_templated ? static_cast<int64_t>(HM_LUT_U) * kSub : (mono_val3 ? val3_unit_elems(flat ? val3_flat_default(N) : val3_default(N))
                                                                                                  : fast_group_elems(N, variant, cfg, with_std, flat || g->out_sum_w, use_val3_flat(k, with_std)));
@@ -351,12 +396,19 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
         if (body > 0) {
             MergeK kb = k;
             kb.n_elems = body;
-            if constexpr (OUT == OUT_F32) {
+            if (sd32_templated) {
+                switch (N) {
+                    case 7: rc = launch_fast_nf_sd32<7, OUT>(kb, st); break;
+                    case 15: rc = launch_fast_nf_sd32<15, OUT>(kb, st); break;
+                    static_assert(kSd32Templated(7) && kSd32Templated(15) && !kSd32Templated(8), "one case per float32-std-templated frame count");
+                    default: rc = HM_EINVAL; break;
+                }
+            } else if constexpr (OUT == OUT_F32) {
                 switch (loop_kernel ? 0 : N) {
                     case 7: rc = launch_fast_nf<7, OUT_F32>(kb, cfg, with_std, !f32_pairs, st); break;
                     case 15: rc = launch_fast_nf<15, OUT_F32>(kb, cfg, with_std, !f32_pairs, st); break;
                     static_assert(kF32Templated(7) && kF32Templated(15) && !kF32Templated(8), "one case per float32-templated frame count");
-                    default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : launch_loop<OUT>(kb, with_std, st); break;
+                    default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : loop(kb); break;
                 }
             } else {
             switch (loop_kernel ? 0 : N) {
@@ -366,7 +418,7 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
                 HM_CASE(17) HM_CASE(18) HM_CASE(19) HM_CASE(20)
                 static_assert(kTemplatedN == 20, "one HM_CASE per templated frame count");
 #undef HM_CASE
-                default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : launch_loop<OUT>(kb, with_std, st); break;   // run-time frame count
+                default: rc = f64in ? launch_f64<OUT>(kb, with_std, st) : loop(kb); break;   // run-time frame count
             }
             }
             if (rc != HM_OK) return rc;
@@ -374,13 +426,15 @@ static int merge_one_launch(const hm_merge_args* g, const double* std_table, boo
         if (body < E) {                                    // tail: less than one group
             MergeK kt = k;
             kt.elem0 = body; kt.n_elems = E - body;
-            rc = launch_generic<OUT>(kt, f64in, with_std, st);
+            rc = generic(kt);
         }
     }
     if (rc != HM_OK) return rc;
     // ---- hot-pixel fix-up pass (stream-ordered after the streaming pass: it overwrites the affected elements)
     if (hot) {
-        rc = hot_queue ? launch_hot_queue<OUT>(k, f64in, with_std, static_cast<uint32_t*>(g->hot_workspace), g->hot_workspace_bytes, st)
+        if (sd32) rc = hot_queue ? launch_hot_queue<OUT, float>(k, f64in, with_std, static_cast<uint32_t*>(g->hot_workspace), g->hot_workspace_bytes, st)
+                             : launch_fixup<OUT, float>(k, f64in, with_std, st);
+        else rc = hot_queue ? launch_hot_queue<OUT>(k, f64in, with_std, static_cast<uint32_t*>(g->hot_workspace), g->hot_workspace_bytes, st)
                    : launch_fixup<OUT>(k, f64in, with_std, st);
     }
     return rc;

@@ -16,7 +16,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------------
 struct MergeK {
     const void*    frame[HM_MAX_FRAMES];   // uint8 or float64 frames, at image row buf_row0
-    const double*  sd[HM_MAX_FRAMES];      // float64 std frames (or null)
+    const double*  sd[HM_MAX_FRAMES];      // float64 std frames (or null); in a hm_merge_std_f32 call float32 frames, read through sd_as<float>()
     const uint8_t* dark[HM_MAX_FRAMES];    // per-frame dark DN map (or null)
     double  inv_t[HM_MAX_FRAMES];          // 1 / exposure
     int32_t dark_min[HM_MAX_FRAMES];       // hot iff dark >= dark_min
@@ -41,6 +41,10 @@ struct MergeK {
     int32_t variant;
     uint32_t* hot_reset;                   // the hot-pixel queue's four counter words, zeroed by the streaming kernel that runs before the scan
     const double* std_lut;                 // hm_merge_std_table: (256, C) per-DN std table read by the LUT instantiations instead of sd[] (else null)
+    // std frame i with the element type of the instantiation (template parameter SD: double, or float for hm_merge_std_f32; the struct
+    // itself carries no flag for it - the dispatcher picks the SD = float launchers - and keeps its layout)
+    template <typename SD>
+    __host__ __device__ __forceinline__ const SD* sd_as(int i) const { return reinterpret_cast<const SD*>(sd[i]); }
 };
 
 // The queue's counters must be zero when merge_scan_hot starts. A hipMemsetAsync costs two fill kernels (~10 us per call, 1 % of
@@ -92,6 +96,14 @@ struct StdLutAt {
     __device__ __forceinline__ double operator()(int64_t i) const { return lut[lut_index_of(f[i]) * C + c]; }
 };
 
+// std of element `i` of a std frame of element type SD, widened to float64 (exact for float: hm_merge_std_f32). The k x k medians take it
+// as their element accessor: widening is monotone, so the median of the widened neighbourhood is the widened median.
+template <typename SD>
+struct StdAt {
+    const SD* s;
+    __device__ __forceinline__ double operator()(int64_t i) const { return static_cast<double>(s[i]); }
+};
+
 // Hot-element queue in the caller's workspace (hm_merge_args.hot_workspace), uint32 words:
 //   ws[0] = number of queued elements, ws[1] = overflow flag (the queue was too small: merge_patch_hot goes over the whole tile),
 //   ws[2] = number of pieces the scan wrote (its workgroups x rounds), ws[3] unused;
@@ -117,7 +129,8 @@ __host__ __device__ inline uint32_t hot_piece_slots(int64_t n_elems) { return st
 // ------------------------------------------------------------------------------------------------
 enum { HOT_NONE = 0, HOT_WAVE = 1, HOT_LANE = 2 };
 // LUT (hm_merge_std_table): the frames' stds come from a.std_lut (global memory: these are the cold paths) instead of a.sd[].
-template <bool F64IN, bool STD, int HOT, int OUT = OUT_F64, bool LUT = false>
+// SD (hm_merge_std_f32): element type of the std frames; a float std is widened once, on its way into a register.
+template <bool F64IN, bool STD, int HOT, int OUT = OUT_F64, bool LUT = false, typename SD = double>
 __device__ __forceinline__ void merge_one_element(const MergeK& a, const double* t_w, const double* t_dw,
                                                   const double* t_g, const double* t_d, int64_t e, bool store) {
     const int C = a.C, N = a.n_frames;
@@ -187,8 +200,16 @@ __device__ __forceinline__ void merge_one_element(const MergeK& a, const double*
                     if constexpr (HOT == HOT_WAVE) s = wave_median_of(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
                     else s = lane_median_of<double>(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
                 } else s = a.std_lut[idx * C + c];
-            } else if (HOT != HOT_NONE && hot) s = median_of(a.sd[i]);
-            else s = a.sd[i][ei];
+            } else if constexpr (std::is_same_v<SD, double>) {
+                if (HOT != HOT_NONE && hot) s = median_of(a.sd[i]);
+                else s = a.sd[i][ei];
+            } else {
+                const StdAt<SD> at{a.template sd_as<SD>(i)};
+                if (HOT != HOT_NONE && hot) {
+                    if constexpr (HOT == HOT_WAVE) s = wave_median_of(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
+                    else s = lane_median_of<double>(at, a.H, a.W, C, a.buf_row0, row, col, cc, a.median_k);
+                } else s = at(ei);
+            }
             const double dg = t_d[idx * C + c] * s;                     // measurand.py:512
             const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;   // :389
             const double term = (A * dg) * it;
@@ -260,6 +281,26 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const void* p) {
 constexpr int kAuxNT = 2;                                             // cache-policy bits of the raw-buffer builtins on gfx94x/gfx950: nt
 __device__ __forceinline__ uint16_t ld_u16_buf(__amdgpu_buffer_rsrc_t r, uint32_t lane_off, uint32_t group_off) {
     return __builtin_amdgcn_raw_buffer_load_b16(r, static_cast<int>(lane_off), static_cast<int>(group_off), kAuxNT);
+}
+// The lane's two stds of a 128-element sub-unit of a std frame (SD = double: the 16-byte load above; SD = float, hm_merge_std_f32: one
+// 8-byte load, half the bytes and half the registers per frame) at (scalar base) + lane16 (float: lane16 / 2). sd_pair_x / _y widen.
+typedef const __attribute__((address_space(1))) f32x2* global_f32x2_ptr;
+template <typename SD> struct SdPair { typedef f64x2 type; };
+template <> struct SdPair<float> { typedef f32x2 type; };
+template <typename SD>
+__device__ __forceinline__ typename SdPair<SD>::type ld_sd_pair_global(const SD* scalar_base, uint32_t lane16) {
+    if constexpr (std::is_same_v<SD, double>) return ld_f64x2_global(scalar_base, lane16);
+    else {
+        global_char_ptr g = (global_char_ptr)(scalar_base);
+        return __builtin_nontemporal_load((global_f32x2_ptr)(g + (lane16 >> 1)));
+    }
+}
+// the same load through a generic pointer (merge_u8_loop_std)
+template <typename SD>
+__device__ __forceinline__ typename SdPair<SD>::type ld_sd_pair(const SD* base, uint32_t lane16) {
+    if constexpr (std::is_same_v<SD, double>)
+        return __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(reinterpret_cast<const char*>(base) + lane16));
+    else return __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(reinterpret_cast<const char*>(base) + (lane16 >> 1)));
 }
 // store two float64 at (scalar base) + (32-bit byte offset in a VGPR)
 __device__ __forceinline__ void store2(double* base, uint32_t byte_off, double x, double y) {

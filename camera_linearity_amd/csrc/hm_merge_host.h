@@ -21,6 +21,7 @@ struct DescribeCtx {
     std::string names;
     bool f32 = false;     // the call being described has out_kind = HM_OUT_F32
     bool lut = false;     // the call being described takes its stds from the per-DN table (hm_merge_std_table)
+    bool sd32 = false;    // the call being described reads float32 std frames (hm_merge_std_f32)
 };
 extern thread_local DescribeCtx* g_describe;          // hm_merge.hip: set by merge_describe(), read by describe_only()
 // quad: the kernel being named stores four float32 elements per lane (merge_u8_val3's QUAD map)
@@ -140,18 +141,30 @@ constexpr bool kF32Templated(int n_frames) { return n_frames == 7 || n_frames ==
 constexpr bool val3_quad_cfg(Val3Cfg c) { return c.pf == 1 && c.u % 2 == 0 && (c.map == 0 || c.map == 3); }
 constexpr int kVariantF32Pairs = 32;     // args->variant of a float32 call: the library default with the pair map forced (A/B of the store shape, tools/bench_merge_f32.py)
 
+// hm_merge_std_f32 (float32 std frames): compile-time-N kernels for colour stacks of these frame counts (BASELINE configs 3 and 4), with or
+// without a flat field, both output types; every other uint8 shape (other N, C != 3, a sum-of-weights output) streams through
+// merge_u8_loop_std at run-time N - build time. float64 frames with float32 stds run in merge_generic (merge_f64_std reads float64 stds).
+constexpr bool kSd32Templated(int n_frames) { return n_frames == 7 || n_frames == 15; }
+inline bool use_fast_sd32(const MergeK& k, bool sd32, bool f64in) {
+    return sd32 && !f64in && k.C == 3 && kSd32Templated(k.n_frames) && !k.out_sum_w && k.variant == 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // family launchers (k.n_elems whole groups of the family's unit size, or any count for the generic and hot-pixel kernels)
 // ------------------------------------------------------------------------------------------------
 // hm_merge_nf.h, instantiated by hm_merge_nf_*.hip: the compile-time-N kernels. allow_quad: float32 calls may take merge_u8_val3's QUAD map.
 template <int NF, int OUT> int launch_fast_nf(const MergeK& k, const FastCfg& c, bool with_std, bool allow_quad, hipStream_t st);
-// hm_merge_loop.hip / hm_merge_f64.hip: run-time N, uint8 / float64 frames
-template <int OUT> int launch_loop(const MergeK& k, bool with_std, hipStream_t st);
+// ... and merge_u8_fast_std reading float32 std frames (use_fast_sd32), instantiated by hm_merge_nf_sd32.hip
+template <int NF, int OUT> int launch_fast_nf_sd32(const MergeK& k, hipStream_t st);
+// SD: element type of the std frames - double, or float for hm_merge_std_f32 (std calls without the per-DN table only), instantiated by
+// units of their own (hm_merge_loop_sd32.hip, hm_merge_hot_sd32.hip)
+// hm_merge_loop.h / hm_merge_f64.hip: run-time N, uint8 / float64 frames
+template <int OUT, typename SD = double> int launch_loop(const MergeK& k, bool with_std, hipStream_t st);
 template <int OUT> int launch_f64(const MergeK& k, bool with_std, hipStream_t st);
-// hm_merge_hot.hip: one element per thread, and the hot-pixel pass without / with the queue workspace
-template <int OUT> int launch_generic(const MergeK& k, bool f64in, bool with_std, hipStream_t st);
-template <int OUT> int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t st);
-template <int OUT> int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t* ws, size_t ws_bytes, hipStream_t st);
+// hm_merge_hot.h: one element per thread, and the hot-pixel pass without / with the queue workspace
+template <int OUT, typename SD = double> int launch_generic(const MergeK& k, bool f64in, bool with_std, hipStream_t st);
+template <int OUT, typename SD = double> int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t st);
+template <int OUT, typename SD = double> int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t* ws, size_t ws_bytes, hipStream_t st);
 
 #define HM_NF_ARGS const MergeK&, const FastCfg&, bool, bool, hipStream_t
 #define HM_EXTERN_NF(n) extern template int launch_fast_nf<n, OUT_F64>(HM_NF_ARGS);
@@ -163,14 +176,26 @@ static_assert(kTemplatedN == 20, "one HM_EXTERN_NF per templated frame count");
 extern template int launch_fast_nf<7, OUT_F32>(HM_NF_ARGS);
 extern template int launch_fast_nf<15, OUT_F32>(HM_NF_ARGS);
 static_assert(kF32Templated(7) && kF32Templated(15) && !kF32Templated(8), "one declaration per float32-templated frame count");
+#define HM_EXTERN_SD32(n) \
+    extern template int launch_fast_nf_sd32<n, OUT_F64>(const MergeK&, hipStream_t); \
+    extern template int launch_fast_nf_sd32<n, OUT_F32>(const MergeK&, hipStream_t);
+HM_EXTERN_SD32(7) HM_EXTERN_SD32(15)
+static_assert(kSd32Templated(7) && kSd32Templated(15) && !kSd32Templated(8), "one declaration per float32-std-templated frame count");
+#undef HM_EXTERN_SD32
 #define HM_EXTERN_OUT(OUT) \
-    extern template int launch_loop<OUT>(const MergeK&, bool, hipStream_t); \
-    extern template int launch_f64<OUT>(const MergeK&, bool, hipStream_t); \
-    extern template int launch_generic<OUT>(const MergeK&, bool, bool, hipStream_t); \
-    extern template int launch_fixup<OUT>(const MergeK&, bool, bool, hipStream_t); \
-    extern template int launch_hot_queue<OUT>(const MergeK&, bool, bool, uint32_t*, size_t, hipStream_t);
+    extern template int launch_f64<OUT>(const MergeK&, bool, hipStream_t);
 HM_EXTERN_OUT(OUT_F64)
 HM_EXTERN_OUT(OUT_F32)
 #undef HM_EXTERN_OUT
+#define HM_EXTERN_OUT_SD(OUT, SD) \
+    extern template int launch_loop<OUT, SD>(const MergeK&, bool, hipStream_t); \
+    extern template int launch_generic<OUT, SD>(const MergeK&, bool, bool, hipStream_t); \
+    extern template int launch_fixup<OUT, SD>(const MergeK&, bool, bool, hipStream_t); \
+    extern template int launch_hot_queue<OUT, SD>(const MergeK&, bool, bool, uint32_t*, size_t, hipStream_t);
+HM_EXTERN_OUT_SD(OUT_F64, double)
+HM_EXTERN_OUT_SD(OUT_F32, double)
+HM_EXTERN_OUT_SD(OUT_F64, float)
+HM_EXTERN_OUT_SD(OUT_F32, float)
+#undef HM_EXTERN_OUT_SD
 
 }  // namespace hm

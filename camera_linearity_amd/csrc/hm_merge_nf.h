@@ -64,7 +64,8 @@ namespace hm {
 #define HM_WAVES_ATTR
 #endif
 
-template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64, bool LUT = false>
+// SD (hm_merge_std_f32): element type of the std frames - float: the lane's two stds are one 8-byte load, widened once in registers.
+template <int NF, int U, int TAB, bool STD, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64, bool LUT = false, typename SD = double>
 __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     reset_hot_counters(a);
@@ -223,10 +224,10 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                 // HM_STD_EARLY (flat-field instantiations): all NF float64 std loads of the sub-unit are issued here, ahead of pass 1's
                 // gathers (4 VGPRs per frame: stacks of up to HM_PIN_NF frames only), instead of HM_STD_FB frames at a time inside pass 2
                 constexpr bool EARLY = !LUT && HM_STD_EARLY && FLAT && NF <= PIN_NF;
-                f64x2 sd_early[EARLY ? NF : 1];
+                typename SdPair<SD>::type sd_early[EARLY ? NF : 1];
                 if constexpr (EARLY) {
 #pragma unroll
-                    for (int i = 0; i < NF; ++i) sd_early[i] = ld_f64x2_global(a.sd[i] + a.in_off + sbase, lane16);
+                    for (int i = 0; i < NF; ++i) sd_early[i] = ld_sd_pair_global<SD>(a.template sd_as<SD>(i) + a.in_off + sbase, lane16);
                 }
                 // pass 1: S = sum_i w_i
                 double S[2];
@@ -258,13 +259,13 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
 #pragma unroll
                 for (int i = 0; i < NF; ++i) {
                     const double it = a.inv_t[i];
-                    f64x2 sdv;
-                    if constexpr (LUT) sdv = f64x2{1.0, 1.0};                  // unused: the table entry is dg
+                    typename SdPair<SD>::type sdv;
+                    if constexpr (LUT) sdv = typename SdPair<SD>::type{1.0, 1.0};   // unused: the table entry is dg
                     else if constexpr (EARLY) sdv = sd_early[i];
                     else {
-                        const double* sp = a.sd[i] + a.in_off + sbase;                           // scalar base
+                        const SD* sp = a.template sd_as<SD>(i) + a.in_off + sbase;               // scalar base
                         if (NF > PIN_NF || !FLAT) asm volatile("" : "+s"(sp));     // keep base + 32-bit lane offset addressing (no per-frame VGPR address pairs)
-                        sdv = ld_f64x2_global(sp, lane16);
+                        sdv = ld_sd_pair_global<SD>(sp, lane16);
                     }
                     uint32_t packed = cur[i][s];
                     if (LUT || NF > PIN_NF || !FLAT) HM_PIN(packed);           // re-extract the DNs here instead of keeping pass 1's indices alive
@@ -279,7 +280,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
                         const double2 gd = *reinterpret_cast<const double2*>(t_gd + dn * (16u * C) + coffs[j]);
 #endif
                         const double w = wdw.x, dw = wdw.y, gg = gd.x;
-                        const double dg = LUT ? gd.y : gd.y * (j == 0 ? sdv.x : sdv.y);          // measurand.py:512
+                        const double dg = LUT ? gd.y : gd.y * static_cast<double>(j == 0 ? sdv.x : sdv.y);   // measurand.py:512
                         const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
                         const double term = (A * dg) * it;
                         if (i == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }
@@ -330,10 +331,10 @@ __global__ __launch_bounds__(BLOCK) HM_WAVES_ATTR void merge_u8_fast(const Merge
     static_assert(!STD, "std instantiations go through merge_u8_fast_std");
     merge_u8_fast_body<NF, U, TAB, false, PREFETCH, FLAT, SUMW, BLOCK, 3, OUT>(a);
 }
-template <int NF, int U, int TAB, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
+template <int NF, int U, int TAB, bool PREFETCH, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64, typename SD = double>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES, FLAT ? HM_STD_WAVES_FLAT : HM_STD_WAVES)))
 void merge_u8_fast_std(const MergeK a) {
-    merge_u8_fast_body<NF, U, TAB, true, PREFETCH, FLAT, SUMW, BLOCK, CH, OUT>(a);
+    merge_u8_fast_body<NF, U, TAB, true, PREFETCH, FLAT, SUMW, BLOCK, CH, OUT, false, SD>(a);
 }
 // The same kernel with the per-DN std table (hm_merge_std_table): no std loads, the {g, dg} entries carry the table. Its register
 // budget is its own (HM_LUT_U / HM_LUT_FB / HM_LUT_WAVES below), not the std-stream kernel's.
@@ -685,11 +686,11 @@ __global__ __launch_bounds__(256) void merge_u8_val3(const MergeK a) {
 // ------------------------------------------------------------------------------------------------
 // host side: the launchers of the kernels above
 // ------------------------------------------------------------------------------------------------
-template <int NF, int U, int TAB, bool STD, bool PF, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64>
+template <int NF, int U, int TAB, bool STD, bool PF, bool FLAT, bool SUMW, int BLOCK, int CH = 3, int OUT = OUT_F64, typename SD = double>
 static int launch_one(const MergeK& k, hipStream_t st) {
     constexpr int lds = (STD ? kStdTabBytes : TabInfo<TAB>::bytes) + (FLAT ? 16 * 256 : 0);
     void (*kernel)(const MergeK);
-    if constexpr (STD) kernel = merge_u8_fast_std<NF, U, TAB, PF, FLAT, SUMW, BLOCK, CH, OUT>;
+    if constexpr (STD) kernel = merge_u8_fast_std<NF, U, TAB, PF, FLAT, SUMW, BLOCK, CH, OUT, SD>;
     else kernel = merge_u8_fast<NF, U, TAB, false, PF, FLAT, SUMW, BLOCK, OUT>;
     if (describe_only(CH == 1 ? "merge_u8_fast_std<N=%d,U=%d,flat=%d,sum_w=%d,C=1>"
                               : (STD ? "merge_u8_fast_std<N=%d,U=%d,flat=%d,sum_w=%d>" : "merge_u8_fast<N=%d,U=%d,flat=%d,sum_w=%d>"), NF, U, FLAT, SUMW)) return HM_OK;
@@ -870,7 +871,16 @@ int launch_fast_nf(const MergeK& k, const FastCfg& c, bool with_std, bool allow_
     }
 }
 
+// hm_merge_std_f32 on colour stacks of the frame counts of kSd32Templated(), without a sum-of-weights output: merge_u8_fast_std reading
+// float32 std frames, with the scheduling of the float64-std instantiation it stands beside (hm_merge_nf_sd32.hip instantiates these)
+template <int NF, int OUT>
+int launch_fast_nf_sd32(const MergeK& k, hipStream_t st) {
+    if (k.has_flat) return launch_one<NF, kUStd, TAB_PLAIN, true, true, true, false, 256, 3, OUT, float>(k, st);
+    return launch_one<NF, kUStd, TAB_PLAIN, true, true, false, false, 256, 3, OUT, float>(k, st);
+}
+
 // one line per frame count in a hm_merge_nf_*.hip unit
 #define HM_INSTANTIATE_NF(n, OUT) template int launch_fast_nf<n, OUT>(HM_NF_ARGS);
+#define HM_INSTANTIATE_NF_SD32(n, OUT) template int launch_fast_nf_sd32<n, OUT>(const MergeK&, hipStream_t);
 
 }  // namespace hm

@@ -282,12 +282,12 @@ size_t hm_merge_hot_workspace_bytes(int64_t) { return 16; }
 size_t hm_merge_hot_workspace_min_bytes(int64_t) { return 16; }
 size_t hm_merge_frames_workspace_bytes(int, int64_t, int) { return 0; }           // any number of frames in one pass on the host
 
-// lut: hm_merge_std_table - std outputs without the N float64 std streams
-static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
+// lut: hm_merge_std_table - std outputs without the N float64 std streams; sd32: hm_merge_std_f32 - N float32 std streams
+static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut, bool sd32 = false) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
-    const bool s = lut || g->stds != nullptr;
-    int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + ((s && !lut) ? 8 : 0));
+    const bool s = lut || sd32 || g->stds != nullptr;
+    int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
     if (g->out_sum_w) per += 8;
@@ -304,9 +304,13 @@ static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut) {
 }
 int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
 int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
+int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false, true); }
 
 // std_table: NULL for hm_merge; hm_merge_std_table's table (its own argument rules, then hm_merge's with the table in place of the std frames)
-static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot, const double* std_table = nullptr, bool table_call = false) {
+// stds_f32 / f32_call: hm_merge_std_f32 (its own argument rules, then hm_merge's with the float32 frames in the place of args->stds: on return
+// full.stds addresses them, and sd32 says so, unless the call has no out_val and forms no std)
+static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot, const double* std_table = nullptr, bool table_call = false,
+                       const float* const* stds_f32 = nullptr, bool f32_call = false, bool* sd32_out = nullptr) {
     if (!g_in) return HM_EINVAL;
     const uint32_t sz = g_in->struct_size;
     if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return HM_EINVAL;
@@ -321,6 +325,22 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
         if (!aligned8(std_table)) return HM_EALIGN;
         if (!g->out_val) std_table = nullptr;                                       // no std is formed: hm_merge's sum-of-weights call
     }
+    bool sd32 = false;
+    if (f32_call) {
+        if (g->stds || !stds_f32) return HM_EINVAL;
+        for (int i = 0; i < g->n_frames; ++i)
+            if (!stds_f32[i]) return HM_EINVAL;
+        if (!g->icrf_diff) return HM_EINVAL;
+        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
+        if (g->out_val && !g->out_std) return HM_EINVAL;
+        for (int i = 0; i < g->n_frames; ++i)
+            if ((reinterpret_cast<uintptr_t>(stds_f32[i]) & 3u) != 0) return HM_EALIGN;
+        if (g->out_val) {                                                           // (without out_val no std is formed: hm_merge's sum-of-weights call)
+            full.stds = reinterpret_cast<const double* const*>(stds_f32);
+            sd32 = true;
+        }
+    }
+    if (sd32_out) *sd32_out = sd32;
     const int N = g->n_frames, C = g->channels;
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
     if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
@@ -362,7 +382,7 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
         if (f64in && !aligned8(f)) return HM_EALIGN;
         if (g->stds) {
             if (!g->stds[i]) return HM_EINVAL;
-            if (!aligned8(g->stds[i])) return HM_EALIGN;
+            if (!sd32 && !aligned8(g->stds[i])) return HM_EALIGN;
         }
         if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
     }
@@ -372,6 +392,8 @@ static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot
     // the refusals of the device build (its chunked path and row-band loop are float64 only), so that a call means the same on both
     if (f32out && g->rows > 0 && (N > HM_MAX_FRAMES || g->variant <= -2 ||
                                   g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
+    // (float32 std frames exist in the device build's one-launch kernels only: one ABI, one answer)
+    if (sd32 && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
     return HM_OK;
 }
 
@@ -391,6 +413,17 @@ int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table,
     if (!g) return HM_EINVAL;                                                     // before anything else is read - or written
     return merge_describe(g, std_table, true, buf, buf_len);
 }
+int hm_merge_std_f32_describe(const hm_merge_args* g, const float* const* stds_f32, char* buf, int buf_len) {
+    if (!g) return HM_EINVAL;                                                     // before anything else is read - or written
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    hm_merge_args full; bool hot = false, sd32 = false;
+    const int rc = merge_check(g, full, hot, nullptr, false, stds_f32, true, &sd32);
+    if (rc == HM_OK && full.rows > 0)
+        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr, hot,
+                      sd32 ? ",std=f32" : "", full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
+    else buf[0] = 0;
+    return rc;
+}
 
 // exposure_series.py:340-394 per output element, the operation sequence of merge_one_element() (hm_merge_dev.h): S in frame order;
 // 1/S and 1/S**2 once; numerator and variance accumulated with fma in frame order; acc / S last; flat field last.
@@ -400,9 +433,12 @@ int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table,
 // of an element are only worked out where a median needs them. Same operations in the same order in every instantiation.
 // std_table (hm_merge_std_table; g->stds is NULL then): a frame's std is std_table[idx * C + c], idx the index linearize forms from the
 // frame's own value; for a hot frame the median of the neighbourhood's mapped values.
+// sd32 (hm_merge_std_f32): g->stds addresses float32 frames; each std is widened (exactly) as it is read, a hot frame's after its median
+// (widening is monotone: the same element either way).
 template <bool F64IN, bool HOT, bool STD>
-static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, const double* std_table) {
+static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, const double* std_table, bool sd32) {
     const int N = g->n_frames, C = g->channels;
+    const auto std32 = [g](int i) { return reinterpret_cast<const float*>(g->stds[i]); };
     const bool flat = g->flat_u8 || g->flat_f64;
     const int64_t W = g->width, wc = W * C, E = g->rows * wc;
     const int64_t in_off = (g->row0 - g->buf_row0) * wc;
@@ -482,14 +518,15 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
                             const auto at_f64 = [=](double x) { return std_table[lut_index(x) * C + c]; };
                             if constexpr (F64IN) sdv[i] = h ? median_mapped_at(g->frames_f64[i], at_f64, g->height, W, C, g->buf_row0, row, col, c, k) : at_f64(g->frames_f64[i][ei]);
                             else sdv[i] = h ? median_mapped_at(g->frames_u8[i], at_u8, g->height, W, C, g->buf_row0, row, col, c, k) : at_u8(g->frames_u8[i][ei]);
-                        } else sdv[i] = h ? median_at(g->stds[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->stds[i][ei];
+                        } else if (sd32) sdv[i] = static_cast<double>(h ? median_at(std32(i), g->height, W, C, g->buf_row0, row, col, c, k) : std32(i)[ei]);
+                        else sdv[i] = h ? median_at(g->stds[i], g->height, W, C, g->buf_row0, row, col, c, k) : g->stds[i][ei];
                     }
                 }
             } else {
                 for (int i = 0; i < N; ++i) {
                     if constexpr (F64IN) v[i] = g->frames_f64[i][ei]; else dn[i] = g->frames_u8[i][ei];
                     if constexpr (STD) {
-                        if (!std_table) sdv[i] = g->stds[i][ei];
+                        if (!std_table) sdv[i] = sd32 ? static_cast<double>(std32(i)[ei]) : g->stds[i][ei];
                         else if constexpr (F64IN) sdv[i] = std_table[lut_index(v[i]) * C + c];
                         else sdv[i] = std_table[dn[i] * C + c];
                     }
@@ -564,9 +601,9 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
 
 extern "C" {
 
-static int merge_run(const hm_merge_args* g_in, const double* std_table, bool table_call) {
-    hm_merge_args full; bool hot = false;
-    const int rc = merge_check(g_in, full, hot, std_table, table_call);
+static int merge_run(const hm_merge_args* g_in, const double* std_table, bool table_call, const float* const* stds_f32 = nullptr, bool f32_call = false) {
+    hm_merge_args full; bool hot = false, sd32 = false;
+    const int rc = merge_check(g_in, full, hot, std_table, table_call, stds_f32, f32_call, &sd32);
     if (rc != HM_OK) return rc;
     const hm_merge_args* g = &full;
     if (g->rows == 0) return HM_OK;
@@ -578,20 +615,21 @@ static int merge_run(const hm_merge_args* g_in, const double* std_table, bool ta
     const int k = hot ? g->median_k : 3;
     const int mode = (f64in ? 4 : 0) | (hot ? 2 : 0) | (with_std ? 1 : 0);
     switch (mode) {
-        case 0: merge_elements<false, false, false>(g, inv_t.data(), k, std_table); break;
-        case 1: merge_elements<false, false, true>(g, inv_t.data(), k, std_table); break;
-        case 2: merge_elements<false, true, false>(g, inv_t.data(), k, std_table); break;
-        case 3: merge_elements<false, true, true>(g, inv_t.data(), k, std_table); break;
-        case 4: merge_elements<true, false, false>(g, inv_t.data(), k, std_table); break;
-        case 5: merge_elements<true, false, true>(g, inv_t.data(), k, std_table); break;
-        case 6: merge_elements<true, true, false>(g, inv_t.data(), k, std_table); break;
-        default: merge_elements<true, true, true>(g, inv_t.data(), k, std_table); break;
+        case 0: merge_elements<false, false, false>(g, inv_t.data(), k, std_table, sd32); break;
+        case 1: merge_elements<false, false, true>(g, inv_t.data(), k, std_table, sd32); break;
+        case 2: merge_elements<false, true, false>(g, inv_t.data(), k, std_table, sd32); break;
+        case 3: merge_elements<false, true, true>(g, inv_t.data(), k, std_table, sd32); break;
+        case 4: merge_elements<true, false, false>(g, inv_t.data(), k, std_table, sd32); break;
+        case 5: merge_elements<true, false, true>(g, inv_t.data(), k, std_table, sd32); break;
+        case 6: merge_elements<true, true, false>(g, inv_t.data(), k, std_table, sd32); break;
+        default: merge_elements<true, true, true>(g, inv_t.data(), k, std_table, sd32); break;
     }
     return HM_OK;
 }
 
 int hm_merge(const hm_merge_args* g_in, void*) { return merge_run(g_in, nullptr, false); }
 int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void*) { return merge_run(g_in, std_table, true); }
+int hm_merge_std_f32(const hm_merge_args* g_in, const float* const* stds_f32, void*) { return merge_run(g_in, nullptr, false, stds_f32, true); }
 
 }  // extern "C"
 

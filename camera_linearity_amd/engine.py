@@ -260,7 +260,7 @@ class MergePlan:
     `launch()` enqueues the fused kernel on the current stream of the plan's device; it can be called
     repeatedly (bench, hipGraph capture)."""
 
-    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None):
+    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None, stds_f32=None):
         self.args = args
         self._keep = keep
         self.device = torch.device(device)
@@ -269,14 +269,17 @@ class MergePlan:
         self.host = self.device.type != "cuda"             # a plan of the host backend (built inside nat.host_mode())
         self.std_table = std_table                         # (256, C) float64 per-DN std table: the plan goes through hm_merge_std_table
         self._table = None if std_table is None else std_table.data_ptr()
+        self._stds_f32 = stds_f32                          # ctypes array of N pointers to float32 std frames: the plan goes through hm_merge_std_f32
 
     def _call(self, lib, stream):
+        if self._stds_f32 is not None:
+            return lib.hm_merge_std_f32(self._ref, self._stds_f32, stream)
         if self._table is None:
             return lib.hm_merge(self._ref, stream)
         return lib.hm_merge_std_table(self._ref, self._table, stream)
 
     def launch(self, stream: Optional[int] = None) -> None:
-        what = "hm_merge" if self._table is None else "hm_merge_std_table"
+        what = "hm_merge_std_f32" if self._stds_f32 is not None else "hm_merge" if self._table is None else "hm_merge_std_table"
         if self.host:
             with nat.host_mode():
                 nat.check(self._call(nat.lib, None), what)
@@ -293,17 +296,21 @@ class MergePlan:
 
     @property
     def algorithmic_bytes(self) -> int:
+        if self._stds_f32 is not None:
+            return int(nat.hip_lib.hm_merge_std_f32_algorithmic_bytes(C.byref(self.args)))
         if self._table is not None:
             return int(nat.hip_lib.hm_merge_std_table_algorithmic_bytes(C.byref(self.args)))
         return int(nat.hip_lib.hm_merge_algorithmic_bytes(C.byref(self.args)))
 
     @property
     def kernels(self) -> str:
-        """Names of the kernels launch() dispatches to, in launch order (hm_merge_describe / hm_merge_std_table_describe: the library's
-        own dispatch, dry)."""
+        """Names of the kernels launch() dispatches to, in launch order (hm_merge_describe / hm_merge_std_table_describe /
+        hm_merge_std_f32_describe: the library's own dispatch, dry)."""
         buf = C.create_string_buffer(512)
         lib = nat.host_lib() if self.host else nat.hip_lib
-        if self._table is not None:
+        if self._stds_f32 is not None:
+            nat.check(lib.hm_merge_std_f32_describe(self._ref, self._stds_f32, C.addressof(buf), 512), "hm_merge_std_f32_describe")
+        elif self._table is not None:
             nat.check(lib.hm_merge_std_table_describe(self._ref, self._table, C.addressof(buf), 512), "hm_merge_std_table_describe")
         else:
             nat.check(lib.hm_merge_describe(self._ref, buf, 512), "hm_merge_describe")
@@ -323,6 +330,11 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     frames : N tensors (buf_rows, W, C), all uint8 DNs or all float64 values, ascending exposure.
              They cover image rows [buf_row0, buf_row0 + buf_rows) of an image `height` rows tall;
              the call produces rows [row0, row0 + rows). Defaults: the buffers are the whole image.
+    stds   : N std tensors with the frames' shape. Tensors that are ALL torch.float32 (what ImageSet.save_32bit writes and a float32
+             Measurand keeps) are read by the kernels as they are (hm_merge_std_f32: made contiguous, never copied into float64) when there
+             are at most HM_MAX_FRAMES frames and no forced chunking (variant > -2). Anything else - float64, mixed dtypes, float16 /
+             bfloat16, float32 with more frames or forced chunking - is widened to float64 first. The outputs are the same bits either way:
+             widening float32 loses nothing and each std is widened once inside the kernel.
     darks  : per frame a uint8 dark DN map covering the same rows as the frames, or None;
              dark_min[i] = smallest hot DN (see dark_min_dn()). hot_queue: give the hot-pixel pass its queue workspace
              (hm_merge_hot_workspace_bytes: 1 byte per output element) so that it stays balanced on dense maps;
@@ -374,7 +386,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         if n > nat.HM_MAX_FRAMES or variant <= -2:
             raise NotImplementedError(f"std_table merges take at most {nat.HM_MAX_FRAMES} frames in one launch (the chunked path reads std frames)")
     with_std = stds is not None or std_table is not None
-    sd = []
+    sd, sd_f32 = [], False
     if stds is not None:
         if len(stds) != n:
             raise ValueError("one std frame per value frame is required")
@@ -384,7 +396,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
             _require_cuda(s, f"stds[{i}]")
             if tuple(s.shape) != shape:
                 raise ValueError("Value and std shapes must match.")
-            sd.append(s.to(_F64).contiguous())
+        # float32 std frames as they are (hm_merge_std_f32) where one launch takes the stack; everything else widened, as ever
+        sd_f32 = all(s.dtype == torch.float32 for s in stds) and n <= nat.HM_MAX_FRAMES and variant > -2
+        sd = [s.contiguous() if sd_f32 else s.to(_F64).contiguous() for s in stds]
         keep.extend(sd)
     icrf_t = _dev_f64(icrf, dev)
     if tuple(icrf_t.shape) != (BITS, Cc):
@@ -407,7 +421,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     a.n_frames, a.channels, a.variant = n, Cc, int(variant)
     a.out_kind = nat.HM_OUT_F32 if out_dtype == torch.float32 else nat.HM_OUT_F64
     a.height, a.width, a.row0, a.rows, a.buf_row0, a.buf_rows = height, W, int(row0), rows, int(buf_row0), buf_rows
-    fptrs = _ptr_array(fr)
+    fptrs, sptrs = _ptr_array(fr), None
     if dt == _U8:
         a.frames_u8 = C.cast(fptrs, C.POINTER(C.c_void_p))
     else:
@@ -415,7 +429,8 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     keep.append(fptrs)
     if stds is not None:
         sptrs = _ptr_array(sd)
-        a.stds = C.cast(sptrs, C.POINTER(C.c_void_p))
+        if not sd_f32:
+            a.stds = C.cast(sptrs, C.POINTER(C.c_void_p))
         keep.append(sptrs)
     exp = (C.c_double * n)(*[float(t) for t in exposures])
     a.exposures = C.cast(exp, C.POINTER(C.c_double))
@@ -490,8 +505,8 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         ws = torch.empty(fw, dtype=_U8, device=dev)
         a.frames_workspace, a.frames_workspace_bytes = ws.data_ptr(), fw
         keep.append(ws)
-    plan = MergePlan(a, keep, dev, outputs, std_table=table_t)
-    if out_dtype == torch.float32 or table_t is not None:
+    plan = MergePlan(a, keep, dev, outputs, std_table=table_t, stds_f32=sptrs if sd_f32 else None)
+    if out_dtype == torch.float32 or table_t is not None or sd_f32:
         plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs / table calls raises here, not at the first launch
     return plan
 

@@ -321,7 +321,10 @@ class ExposureSeries(object):
         globs settings.DEFAULT_DARK_PATH (:409) and `flat_list=None` settings.DEFAULT_FLAT_PATH (image_set.py:146-155). A
         path that is not configured means "none": no dark frames / no flat field - but a missing ICRF raises.
         `STD_data` (None: the table of settings.STD_FILE_NAME, when set): the per-DN STD table behind frames without a std image; a series
-        with no std image at all is merged with the table inside the fused kernel (_compute_HDR_image_set)."""
+        with no std image at all is merged with the table inside the fused kernel (_compute_HDR_image_set).
+        A series whose images all hold float32 std images - set in memory, or loaded by load_std_image from the float32 '<name> STD.tif'
+        files ImageSet.save_32bit writes - is merged from them as they are (engine.plan_merge: hm_merge_std_f32, no float64 copies), up to
+        HM_MAX_FRAMES frames; the result is that of the widened stds, bit for bit."""
         if ICRF is None:
             if gs.ICRF_CALIBRATED_FILE is None:
                 raise ValueError("process_HDR_image(ICRF=None) needs settings.ICRF_CALIBRATED_FILE (settings.configure(...)) "

@@ -346,7 +346,9 @@ class ImageSet(object):
     def save_32bit(self, save_path: Optional[Path] = None, is_HDR: Optional[bool] = False, separate_channels: Optional[bool] = False):
         """float32 TIFFs (an addition: what a merge with out_dtype=torch.float32 produces, and what HDR tools exchange): save_64bit's
         naming and suffixes under '32bit/', written uncompressed by the host tiff_io.imwrite (a float32 image is stored bit for bit;
-        a float64 one is rounded to float32 here). There is no device-encode form: tiff_io.imwrite_device does not take float32."""
+        a float64 one is rounded to float32 here). There is no device-encode form: tiff_io.imwrite_device does not take float32.
+        A float32 '<name> STD.tif' written here comes back from load_std_image as float32, and ExposureSeries.process_HDR_image merges
+        such std images as they are (hm_merge_std_f32), without widening them to float64 first."""
         file_path = self.path.parent.joinpath("32bit", self.path.name) if save_path is None else Path(save_path)
         file_path.parent.mkdir(parents=True, exist_ok=True)
         base = str(file_path).removesuffix(".tif")

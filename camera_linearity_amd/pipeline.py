@@ -30,17 +30,25 @@ class _Slot:
 class MergePipeline:
     def __init__(self, n_frames: int, height: int, width: int, exposures: Sequence[float], icrf, icrf_diff=None,
                  channels: int = 3, with_std: bool = False, device=None, depth: int = 2, out_dtype: torch.dtype = torch.float64,
-                 std_table=None):
+                 std_table=None, std_dtype: torch.dtype = torch.float64):
         """out_dtype: torch.float64 or torch.float32 - the plans' output type (engine.plan_merge) and that of the pinned result staging:
         float32 halves the device-to-host copy, which is what bounds a stream of val-only merges.
         std_table: (256, C) per-DN STD table (engine.plan_merge) - a std output without std inputs: the slots hold no std staging buffers
-        and no std frame is copied to the device (8 bytes per element and frame with `with_std`). Excludes with_std."""
+        and no std frame is copied to the device (8 bytes per element and frame with `with_std`). Excludes with_std.
+        std_dtype: torch.float64 (default) or torch.float32, with `with_std` - the element type of the std inputs on both sides of the bus:
+        float32 pinned and device staging, read by the merge as they are (engine.plan_merge / hm_merge_std_f32), half the std bytes to
+        copy and to hold, the same output bits as the widened stds. ValueError for other dtypes, or with std_table."""
         if depth < 2:
             raise ValueError("depth must be at least 2 (one slot in flight while the next is filled)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if std_table is not None and with_std:
             raise ValueError("std_table takes the place of the std inputs: with_std must be False")
+        if std_dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"std_dtype must be torch.float64 or torch.float32, got {std_dtype}")
+        if std_dtype != torch.float64 and std_table is not None:
+            raise ValueError("std_table takes the place of the std inputs: std_dtype does not apply")
         self.n, self.shape, self.with_std, self.depth = n_frames, (height, width, channels), with_std, depth
+        self.std_dtype = std_dtype
         self.std_out = with_std or std_table is not None             # the plans produce a std image
         if self.std_out and icrf_diff is None:
             raise ValueError("uncertainty propagation needs ICRF_diff")
@@ -51,9 +59,9 @@ class MergePipeline:
         for _ in range(depth):
             s = _Slot()
             s.h_frames = [torch.empty(self.shape, dtype=torch.uint8, pin_memory=True) for _ in range(n_frames)]
-            s.h_stds = [torch.empty(self.shape, dtype=torch.float64, pin_memory=True) for _ in range(n_frames)] if with_std else None
+            s.h_stds = [torch.empty(self.shape, dtype=std_dtype, pin_memory=True) for _ in range(n_frames)] if with_std else None
             s.d_frames = [torch.empty(self.shape, dtype=torch.uint8, device=self.device) for _ in range(n_frames)]
-            s.d_stds = [torch.empty(self.shape, dtype=torch.float64, device=self.device) for _ in range(n_frames)] if with_std else None
+            s.d_stds = [torch.empty(self.shape, dtype=std_dtype, device=self.device) for _ in range(n_frames)] if with_std else None
             s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if self.std_out else None, s.d_stds, out_dtype=out_dtype,
                                        std_table=std_table)
             s.h_val = torch.empty(self.shape, dtype=out_dtype, pin_memory=True)
@@ -66,7 +74,7 @@ class MergePipeline:
 
     # ---- producer side
     def input_views(self, slot: int):
-        """NumPy views of slot `slot`'s pinned staging: (frames [N x (H, W, C) uint8], stds [N x float64] or None)."""
+        """NumPy views of slot `slot`'s pinned staging: (frames [N x (H, W, C) uint8], stds [N x std_dtype] or None)."""
         s = self.slots[slot]
         return [t.numpy() for t in s.h_frames], (None if s.h_stds is None else [t.numpy() for t in s.h_stds])
 
@@ -130,7 +138,7 @@ class MergePipeline:
                 np.copyto(dst, src)
             if sv is not None:
                 for dst, src in zip(sv, stds[k]):
-                    np.copyto(dst, src)
+                    np.copyto(dst, src)                     # (casts into the staging's std_dtype)
             return True
         out = []
         for _, val, std in self.run(fill):

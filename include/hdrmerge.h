@@ -42,7 +42,8 @@ extern "C" {
 /* ABI history. 1: first release (hm_merge_args 264 bytes), later grown by hot_workspace / hot_workspace_bytes (280 bytes) without a bump.
  * 2: frames_workspace / frames_workspace_bytes (296 bytes), hm_merge_frames_workspace_bytes(), stacks of more than HM_MAX_FRAMES
  *    frames; hm_merge still accepts the 264- and 280-byte layouts (the missing tail reads as "no workspace").
- *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only).                     */
+ *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only), and likewise by
+ *    hm_merge_std_table* and hm_merge_std_f32* (new entry points beside hm_merge; hm_merge_args keeps its 296 bytes).     */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -141,7 +142,10 @@ typedef struct hm_merge_args {
                                      only 4-byte aligned run in the generic kernel. out_sum_w is float64 and keeps its 16 bytes.
                                      The val-only kernel merge_u8_val3 stores FOUR float32 elements per lane where it can: uint8
                                      frames / flat field 4-byte aligned and out_val 16-byte aligned at the first element; calls that
-                                     only meet the pair rule run the same kernel with pair stores.)                                 */
+                                     only meet the pair rule run the same kernel with pair stores.
+                                     With float32 std frames (hm_merge_std_f32) the lane's two stds are one 8-byte load: the call's
+                                     first input element must sit at an even element offset and every std buffer must be 8-byte
+                                     aligned at that element; otherwise the call runs in the generic kernel, same bits.)            */
 
     const uint8_t* const* frames_u8;   /* [host] N device pointers to uint8 DN frames, or NULL       */
     const double*  const* frames_f64;  /* [host] N device pointers to float64 value frames, or NULL  */
@@ -231,6 +235,29 @@ int hm_merge_describe(const hm_merge_args* args, char* buf, int buf_len);
 int hm_merge_std_table(const hm_merge_args* args /*[host]*/, const double* std_table, void* stream);
 int hm_merge_std_table_describe(const hm_merge_args* args, const double* std_table, char* buf, int buf_len);
 int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
+
+/* hm_merge with the per-frame uncertainty read from N FLOAT32 std frames as they are (what ImageSet.save_32bit writes and a float32
+ * Measurand keeps), instead of widening each into a float64 copy first: 4 N bytes per element less to read, and no second copy to hold.
+ *   - The result equals hm_merge on the same arguments with stds[i] set to the float64 widening of stds_f32[i], bit for bit in out_val,
+ *     out_std and out_sum_w: for both out_kind values, with or without flat field, dark maps (with or without hot_workspace), out_sum_w
+ *     and row tiles (row0 / rows / buf_row0 / buf_rows), for uint8 and float64 frames, C = 1..4, and the 264- / 280-byte layouts.
+ *   - Each float32 std is converted to float64 once, in registers (exact); all arithmetic stays float64 in the operation sequence every
+ *     kernel of the merge shares, so the result does not depend on which kernel or tiling produced it.
+ *   - For a frame that is hot at an element (dark maps) the std is the k x k median of the std neighbourhood, as in hm_merge: widening is
+ *     monotone and exact, so the median may be taken on either side of the conversion.
+ * stds_f32: [host] N device pointers (host memory on the host build) to float32 frames with the frames' geometry, each 4-byte aligned
+ * (else HM_EALIGN). args->stds must be NULL; flat_std stays float64.
+ * HM_EINVAL, in this order: NULL args (returned before anything else is read), args->stds set, NULL stds_f32 or a NULL entry, no icrf_diff,
+ * no dw_lut (uint8 frames), out_val without out_std. Then HM_EALIGN: a std pointer that is not 4-byte aligned. A call without out_val (sum
+ * of weights only) behaves as hm_merge. Everything else as hm_merge, except: more than HM_MAX_FRAMES frames and variant <= -2 (the chunked
+ * path) are HM_EUNSUPPORTED, before any launch. uint8 frames stream (compile-time-N kernels for colour stacks of 7 and 15 frames,
+ * merge_u8_loop_std at run-time N for every other shape); float64 frames with float32 stds run in merge_generic only.
+ * The streaming kernels' pair rule for float32 stds is stated at hm_merge_args.buf_row0.
+ * hm_merge_std_f32_describe: as hm_merge_describe; every listed kernel that reads stds carries "std=f32" (merge_scan_hot reads none).
+ * hm_merge_std_f32_algorithmic_bytes: hm_merge_algorithmic_bytes of the same call with float64 std frames, minus 4 N bytes per element. */
+int hm_merge_std_f32(const hm_merge_args* args /*[host]*/, const float* const* stds_f32 /*[host] N device pointers*/, void* stream);
+int hm_merge_std_f32_describe(const hm_merge_args* args, const float* const* stds_f32, char* buf, int buf_len);
+int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------
  * Row 8 standalone - AbstractMeasurand.filter_larger_than_by_map (modules/measurand.py:543-557):

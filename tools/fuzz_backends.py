@@ -251,6 +251,78 @@ def case_merge_std_table(rng):
     return desc
 
 
+def case_merge_std_f32(rng):
+    """the merge reading float32 std frames as they are (engine.plan_merge with torch.float32 stds, hm_merge_std_f32): HIP against the host
+    build, and on the device against the float64-std merge of the widened frames (bit for bit)"""
+    c = int(rng.choice([1, 2, 3, 3, 3, 4]))
+    n = int(rng.choice([1, 2, 3, 5, 7, 7, 8, 15, 15, 16, 20, 21, 32]))
+    h, w = int(rng.integers(1, 48 * args.scale)), int(rng.integers(1, 130 * args.scale))
+    if rng.random() < 0.4:
+        h, w = int(rng.integers(8, 40 * args.scale)), 128 * int(rng.integers(1, 4 * args.scale))
+    f64 = rng.random() < 0.2
+    use_dark, use_flat, sum_w = rng.random() < 0.4, rng.random() < 0.4, rng.random() < 0.3
+    k = int(rng.choice([3, 5, 7]))
+    f32 = rng.random() < 0.3
+    variant = int(rng.choice([0, 0, 0, -1]))
+    offset = rng.random() < 0.2                                   # std views that are 4- but not 8-byte aligned: the generic kernel
+    desc = f"merge_std_f32 n={n} h={h} w={w} c={c} f64={f64} dark={use_dark} flat={use_flat} sum_w={sum_w} k={k} f32={f32} variant={variant} offset={offset}"
+    t = np.sort(rng.uniform(1e-4, 2.0, size=n))
+    if f64:
+        frames = [rng.integers(0, 256, (h, w, c)) / 255.0 + rng.choice([0.0, 0.5 / 255, 1e-3, 1.0], size=(h, w, c)) for _ in range(n)]
+    else:
+        frames = [rng.integers(0, 256, (h, w, c)).astype(np.uint8) for _ in range(n)]
+    g, d = icrf_tables(rng, c)
+    stds = []
+    for _ in range(n):
+        sd = rng.random((h, w, c), dtype=np.float32) * np.float32(0.02)
+        sd[rng.random(sd.shape) < 0.05] = 0.0
+        if rng.random() < 0.3:
+            sd.reshape(-1)[int(rng.integers(0, sd.size))] = rng.choice(np.array([1e-45, 3e38], dtype=np.float32))
+        if not use_dark and rng.random() < 0.2:                   # (a median of NaNs has no defined answer)
+            sd.reshape(-1)[int(rng.integers(0, sd.size))] = rng.choice(np.array([np.inf, np.nan], dtype=np.float32))
+        stds.append(sd)
+    kw = dict(want_sum_w=bool(sum_w))
+    if use_dark:
+        dm = rng.integers(0, 20, (h, w, c)).astype(np.uint8)
+        dm[rng.random(dm.shape) < rng.choice([0.001, 0.02, 0.2])] = 220
+        kw.update(darks=[dm if i % 3 else None for i in range(n)] if n > 1 else [dm], dark_min=[100] * n, median_k=k, hot_queue=bool(rng.random() < 0.7))
+    if use_flat:
+        kw.update(flat=rng.integers(120, 250, (h, w, c)).astype(np.uint8), ff_mean=list(rng.uniform(0.6, 0.9, size=c)),
+                  flat_std=0.002 * (1 + rng.random((h, w, c))), ff_std_mean=list(rng.uniform(0.001, 0.003, size=c)))
+    if f32:
+        kw.update(out_dtype=torch.float32)
+
+    def shifted(x):                                               # the same values one float32 into a larger allocation
+        base = torch.empty(x.numel() + 1, dtype=x.dtype, device=x.device)
+        base[1:] = x.reshape(-1)
+        return base[1:].view(x.shape)
+
+    def run(eng, conv, variant, widen):
+        k2 = dict(kw)
+        for name in ("flat", "flat_std"):
+            if name in k2:
+                k2[name] = conv(k2[name])
+        if "darks" in k2:
+            k2["darks"] = [None if x is None else conv(x) for x in k2["darks"]]
+        sd = [conv(x) for x in stds]
+        assert all(x.dtype == torch.float32 for x in sd)
+        if widen:
+            sd = [x.to(torch.float64) for x in sd]
+        elif offset:
+            sd = [shifted(x) for x in sd]
+        plan = eng.plan_merge([conv(f) for f in frames], list(t), g, d, sd, variant=variant, **k2)
+        if ("std=f32" in plan.kernels) == widen:
+            raise Mismatch(f"float32 stds {'widened' if not widen else 'not widened'}: {plan.kernels}")
+        plan.launch()
+        return plan.outputs
+
+    a, b, s = run(engine, D, variant, False), run(heng, Hh, 0, False), run(engine, D, 0, True)
+    for key in b:
+        compare(f"{key} (float32 stds, device vs widened)", a[key], s[key], None)
+        compare(f"{key}", a[key], b[key], None if not f64 else (1e-8 if key == "std" else 1e-12))
+    return desc
+
+
 def rand_operand(rng, shape, positive=False):
     v = rng.normal(size=shape) * 10 ** rng.uniform(-2, 2)
     if positive:
@@ -729,7 +801,7 @@ def case_pairs_hist(rng):
     return desc
 
 
-CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
+CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
          (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()
