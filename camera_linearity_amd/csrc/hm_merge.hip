@@ -33,11 +33,14 @@
 // once in registers (exact), so the result equals that of the widened frames bit for bit. Its instantiations live in units of their own
 // (hm_merge_nf_sd32.hip, hm_merge_loop_sd32.hip, hm_merge_hot_sd32.hip).
 //
-// This file is the host side of the call: argument validation, the dispatch (merge_entry, merge_one_launch) and the C entry points.
+// This file is the host side of the call: the dispatch (merge_entry, merge_one_launch) and the C entry points.
 // It holds no kernel and instantiates none: hm_merge_dev.h has what the families share on the device, hm_merge_host.h the describe
 // context, the launch geometry and the family launchers' declarations. Stacks of more than HM_MAX_FRAMES frames: hm_merge_chunk.hip.
+// The argument rules of the three entry points (accepted layouts, the order of the checks, the algorithmic byte count) are not here:
+// hm_merge_rules.h has the one copy that this build and the host build (csrc_host/hm_host.cpp) both compile; merge_entry adds the two
+// refusals that are this build's own.
 #include "hm_merge_host.h"
-#include <cstring>
+#include "hm_merge_rules.h"
 
 namespace hm {
 
@@ -89,32 +92,12 @@ static int fast_group_elems(int n_frames, int variant, const FastCfg& c, bool wi
 
 }  // namespace hm
 
-// lut: the call is hm_merge_std_table - std outputs (and the flat field's std) without the N float64 std streams
-// sd32: the call is hm_merge_std_f32 - N float32 std streams (g->stds is NULL in both)
-static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut, bool sd32 = false) {
-    if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
-    const int64_t E = g->rows * g->width * g->channels;
-    const int N = g->n_frames;
-    const bool s = lut || sd32 || g->stds != nullptr;
-    const int64_t in_b = g->frames_f64 ? 8 : 1;
-    int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
-    const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
-    if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
-    if (g->out_sum_w) per += 8;
-    if (g->flat_u8 || g->flat_f64) per += (g->flat_u8 ? 1 : 8) + ((s && g->flat_std) ? 8 : 0);
-    if (g->darks_u8)                                       // every DISTINCT (map, threshold) is read once (scan_chunk_hotbits)
-        for (int i = 0; i < N; ++i) {
-            if (!g->darks_u8[i]) continue;
-            bool seen = false;
-            for (int k = 0; k < i; ++k)
-                seen = seen || (g->darks_u8[k] == g->darks_u8[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
-            per += seen ? 0 : 1;
-        }
-    return per * E;
-}
-extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
-extern "C" int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
-extern "C" int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false, true); }
+using hm_rules::MergeCall;
+using hm_rules::MergeEntry;
+
+extern "C" int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_MERGE); }
+extern "C" int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_STD_TABLE); }
+extern "C" int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_STD_F32); }
 
 // Workspace of the hot-pixel queue for a call that produces n_elems = rows * W * C output elements: 16 bytes of counters, the piece
 // table (8 bytes per 65 536 elements + 8 KB) and one uint32 per queued element. The recommended size holds a quarter of the elements
@@ -131,150 +114,50 @@ extern "C" size_t hm_merge_hot_workspace_bytes(int64_t n_elems) {
     return hm_merge_hot_workspace_min_bytes(n_elems) + static_cast<size_t>(entries - 1) * 4;
 }
 
-static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream, bool sd32 = false);
+static int merge_entry(const hm_merge_args* g_in, MergeEntry entry, const void* extra, void* stream);
 
-static int merge_describe(const hm_merge_args* g, const double* std_table, bool table_call, char* buf, int buf_len) {
-    if (!buf || buf_len < 1) return HM_EINVAL;
-    hm::DescribeCtx ctx;                                   // f32 / lut: set by merge_entry once it has accepted such a call
+// extra: the entry's own pointer (hm_merge_rules.h). The std entries return for NULL args before anything else is read - or written.
+static int merge_describe(const hm_merge_args* g, MergeEntry entry, const void* extra, char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || (!g && entry != hm_rules::ENTRY_MERGE)) return HM_EINVAL;
+    hm::DescribeCtx ctx;                                   // f32 / lut / sd32: set by merge_entry once it has accepted such a call
     hm::g_describe = &ctx;
-    const int rc = table_call ? hm_merge_std_table(g, std_table, nullptr) : merge_entry(g, nullptr, nullptr);
+    const int rc = merge_entry(g, entry, extra, nullptr);
     hm::g_describe = nullptr;
     snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
     return rc;
 }
-extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, nullptr, false, buf, buf_len); }
+extern "C" int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, hm_rules::ENTRY_MERGE, nullptr, buf, buf_len); }
 extern "C" int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table, char* buf, int buf_len) {
-    if (!g) return HM_EINVAL;                              // before anything else is read - or written
-    return merge_describe(g, std_table, true, buf, buf_len);
+    return merge_describe(g, hm_rules::ENTRY_STD_TABLE, std_table, buf, buf_len);
 }
 extern "C" int hm_merge_std_f32_describe(const hm_merge_args* g, const float* const* stds_f32, char* buf, int buf_len) {
-    if (!g) return HM_EINVAL;                              // before anything else is read - or written
-    if (!buf || buf_len < 1) return HM_EINVAL;
-    hm::DescribeCtx ctx;                                   // f32 / sd32: set by merge_entry once it has accepted such a call
-    hm::g_describe = &ctx;
-    const int rc = hm_merge_std_f32(g, stds_f32, nullptr);
-    hm::g_describe = nullptr;
-    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
-    return rc;
+    return merge_describe(g, hm_rules::ENTRY_STD_F32, stds_f32, buf, buf_len);
 }
 
-// struct_size values hm_merge accepts: the current layout and the two older ones of ABI version 1 (without the hot-pixel queue
-// workspace: 264 bytes; with it: 280 bytes) - the missing tail reads as zero (no workspace). out_kind took the place of a pad word those
-// callers never promised to zero: for them it is cleared (float64 outputs).
-static bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
-    if (!g) return false;
-    const uint32_t sz = g->struct_size;
-    if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return false;
-    full = hm_merge_args{};
-    memcpy(&full, g, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
-    if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;
-    full.struct_size = sizeof(hm_merge_args);
-    return true;
-}
+extern "C" int hm_merge(const hm_merge_args* g, void* stream) { return merge_entry(g, hm_rules::ENTRY_MERGE, nullptr, stream); }
+// hm_merge's path with the table / the float32 frames in the place of the std frames
+extern "C" int hm_merge_std_table(const hm_merge_args* g, const double* std_table, void* stream) { return merge_entry(g, hm_rules::ENTRY_STD_TABLE, std_table, stream); }
+extern "C" int hm_merge_std_f32(const hm_merge_args* g, const float* const* stds_f32, void* stream) { return merge_entry(g, hm_rules::ENTRY_STD_F32, stds_f32, stream); }
 
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool sd32, bool f64in, bool with_std, bool flat, bool hot, void* stream);
-
-extern "C" int hm_merge(const hm_merge_args* g_in, void* stream) { return merge_entry(g_in, nullptr, stream); }
-
-// hm_merge_std_table: the table call's own argument rules, then hm_merge's path with the table in place of the std frames
-extern "C" int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void* stream) {
-    if (!g_in) return HM_EINVAL;
-    hm_merge_args full;
-    if (!widen_args(g_in, full)) return HM_EINVAL;
-    if (full.stds || !std_table || !full.icrf_diff) return HM_EINVAL;
-    if (full.frames_u8 && !full.dw_lut) return HM_EINVAL;
-    if (full.out_val && !full.out_std) return HM_EINVAL;
-    if (!hm::aligned(std_table, 8)) return HM_EALIGN;
-    // a call without out_val forms no std: it is hm_merge's sum-of-weights call
-    return merge_entry(&full, full.out_val ? std_table : nullptr, stream);
+static int merge_one_launch(const MergeCall& call, void* stream);
+static int merge_launch(const MergeCall& call, void* stream) {
+    return call.f32out ? merge_one_launch<hm::OUT_F32>(call, stream) : merge_one_launch<hm::OUT_F64>(call, stream);
 }
 
-// hm_merge_std_f32: the call's own argument rules, then hm_merge's path with the float32 frames in the place of args->stds
-extern "C" int hm_merge_std_f32(const hm_merge_args* g_in, const float* const* stds_f32, void* stream) {
-    if (!g_in) return HM_EINVAL;
-    hm_merge_args full;
-    if (!widen_args(g_in, full)) return HM_EINVAL;
-    if (full.stds || !stds_f32) return HM_EINVAL;
-    for (int i = 0; i < full.n_frames; ++i)
-        if (!stds_f32[i]) return HM_EINVAL;
-    if (!full.icrf_diff) return HM_EINVAL;
-    if (full.frames_u8 && !full.dw_lut) return HM_EINVAL;
-    if (full.out_val && !full.out_std) return HM_EINVAL;
-    for (int i = 0; i < full.n_frames; ++i)
-        if (!hm::aligned(stds_f32[i], 4)) return HM_EALIGN;
-    // a call without out_val forms no std: it is hm_merge's sum-of-weights call
-    if (!full.out_val) return merge_entry(&full, nullptr, stream);
-    full.stds = reinterpret_cast<const double* const*>(stds_f32);
-    return merge_entry(&full, nullptr, stream, true);
-}
-
-// std_table != NULL (from hm_merge_std_table only; g->stds is NULL then): the stds come from the per-DN table
-// sd32 (from hm_merge_std_f32 only): g->stds addresses float32 frames, 4-byte aligned
-static int merge_entry(const hm_merge_args* g_in, const double* std_table, void* stream, bool sd32) {
+// The argument rules of all three entries are hm_merge_rules.h's (shared with the host build); this build adds two refusals of its own.
+static int merge_entry(const hm_merge_args* g_in, MergeEntry entry, const void* extra, void* stream) {
     using namespace hm;
-    hm_merge_args full;
-    if (!widen_args(g_in, full)) return HM_EINVAL;
-    const hm_merge_args* g = &full;
+    MergeCall call;
+    const int rc_args = hm_rules::check_merge_call(g_in, entry, extra, call);
+    if (rc_args != HM_OK || call.empty) return rc_args;
+    const hm_merge_args* g = &call.a;
     const int N = g->n_frames, C = g->channels;
-    if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
-    if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
-    const bool f32out = g->out_kind == HM_OUT_F32;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (g->rows == 0) return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;   // empty tile: nothing to do
-    const bool f64in = g->frames_f64 != nullptr;
-    if (f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;          // exactly one input kind
-    if (!g->exposures || !g->icrf) return HM_EINVAL;
-    const bool with_std = g->stds != nullptr || std_table != nullptr;
-    if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
-    if (g->out_val) {
-        if (with_std != (g->out_std != nullptr)) return HM_EINVAL;
-        if (with_std && !g->icrf_diff) return HM_EINVAL;
-    }
-    if (!f64in && (!g->w_lut || (with_std && !g->dw_lut))) return HM_EINVAL;
-    const bool flat = g->flat_u8 || g->flat_f64;
-    if (g->flat_u8 && g->flat_f64) return HM_EINVAL;
-    if (flat && with_std && !g->flat_std) return HM_EINVAL;
-    // geometry
-    if (g->row0 < 0 || g->row0 + g->rows > g->height) return HM_ESHAPE;
-    if (g->buf_row0 < 0 || g->buf_row0 > g->row0 || g->buf_row0 + g->buf_rows > g->height ||
-        g->buf_row0 + g->buf_rows < g->row0 + g->rows) return HM_ESHAPE;
-    bool hot = false;
-    if (g->darks_u8) {
-        if (!g->dark_min_dn) return HM_EINVAL;
-        for (int i = 0; i < N; ++i) hot = hot || (g->darks_u8[i] != nullptr);
-    }
-    if (hot) {
-        const int k = g->median_k;
-        if (k < 3 || k > 7 || (k % 2) == 0) return HM_EINVAL;
-        const int64_t r = k / 2;
-        const int64_t need_lo = g->row0 - r < 0 ? 0 : g->row0 - r;
-        const int64_t need_hi = g->row0 + g->rows + r > g->height ? g->height : g->row0 + g->rows + r;
-        if (g->buf_row0 > need_lo || g->buf_row0 + g->buf_rows < need_hi) return HM_ESHAPE;   // halo too small
-    }
-    // per-frame pointers and exposures (any N: the chunked path below has no frame limit)
-    for (int i = 0; i < N; ++i) {
-        const void* f = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
-        if (!f) return HM_EINVAL;
-        if (f64in && !aligned(f, 8)) return HM_EALIGN;
-        if (g->stds) {
-            if (!g->stds[i]) return HM_EINVAL;
-            if (!aligned(g->stds[i], sd32 ? 4 : 8)) return HM_EALIGN;
-        }
-        if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
-    }
-    const int out_align = f32out ? 4 : 8;
-    if ((g->out_val && !aligned(g->out_val, out_align)) || (g->out_std && !aligned(g->out_std, out_align)) ||
-        (g->out_sum_w && !aligned(g->out_sum_w, 8))) return HM_EALIGN;
-    // float32 outputs exist for the one-launch kernels only: the chunked path keeps float64 running sums in out_val / out_std, the row-band
-    // loop below advances output pointers by float64 elements, and the variant matrix of a tuning build is float64 instantiations
-    if (f32out && (N > HM_MAX_FRAMES || g->variant <= -2 || (HM_TUNE_NF != 0 && g->variant > 0) ||
-                   g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     // the per-DN std table exists in the one-launch kernels only (hm_merge_chunk.hip reads std frames)
-    if (std_table && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
-    // ... and so do float32 std frames
-    if (sd32 && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
-    if (g_describe) { g_describe->f32 = f32out; g_describe->lut = std_table != nullptr; g_describe->sd32 = sd32; }
+    if (call.std_src == hm_rules::STD_TABLE && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
+    // the variant matrix of a tuning build is float64 instantiations
+    if (call.f32out && HM_TUNE_NF != 0 && g->variant > 0) return HM_EUNSUPPORTED;
+    if (g_describe) { g_describe->f32 = call.f32out; g_describe->lut = call.std_src == hm_rules::STD_TABLE; g_describe->sd32 = call.std_src == hm_rules::STD_F32; }
     // More frames than one launch takes (modules/exposure_series.py:334,372 have no limit): HM_MAX_FRAMES per launch with the running
     // sums in memory (hm_merge_chunk.hip). variant <= -2 forces that path with -variant frames per chunk (tests: any chunking gives the
     // bits of the one-launch kernels).
@@ -293,7 +176,8 @@ static int merge_entry(const hm_merge_args* g_in, const double* std_table, void*
             int64_t band_rows = limit / per_row;
             if (band_rows > 1) band_rows &= ~int64_t{1};
             for (int64_t r = 0; r < g->rows; r += band_rows) {
-                hm_merge_args b = *g;
+                MergeCall band = call;                                 // (a band of a valid tile is valid: the rules are not asked again)
+                hm_merge_args& b = band.a;
                 b.row0 = g->row0 + r;
                 b.rows = g->rows - r < band_rows ? g->rows - r : band_rows;
                 const int64_t adv = r * per_row;                       // outputs and the flat field cover the OUTPUT rows
@@ -303,20 +187,22 @@ static int merge_entry(const hm_merge_args* g_in, const double* std_table, void*
                 if (g->flat_u8) b.flat_u8 = g->flat_u8 + adv;
                 if (g->flat_f64) b.flat_f64 = g->flat_f64 + adv;
                 if (g->flat_std) b.flat_std = g->flat_std + adv;
-                const int rc_b = merge_entry(&b, std_table, stream, sd32);
+                const int rc_b = merge_launch(band, stream);
                 if (rc_b != HM_OK) return rc_b;
             }
             return HM_OK;
         }
     }
-    return f32out ? merge_one_launch<OUT_F32>(g, std_table, sd32, f64in, with_std, flat, hot, stream)
-                  : merge_one_launch<OUT_F64>(g, std_table, sd32, f64in, with_std, flat, hot, stream);
+    return merge_launch(call, stream);
 }
 
 // One streaming launch (+ generic tail + hot-pixel pass) for validated arguments; OUT = element type of out_val / out_std.
 template <int OUT>
-static int merge_one_launch(const hm_merge_args* g, const double* std_table, bool sd32, bool f64in, bool with_std, bool flat, bool hot, void* stream) {
+static int merge_one_launch(const MergeCall& call, void* stream) {
     using namespace hm;
+    const hm_merge_args* g = &call.a;
+    const double* const std_table = call.std_table;
+    const bool sd32 = call.std_src == hm_rules::STD_F32, f64in = call.f64in, with_std = call.with_std, flat = call.flat, hot = call.hot;
     const int N = g->n_frames, C = g->channels;
     const bool f32_pairs = OUT == OUT_F32 && g->variant == kVariantF32Pairs;      // float32 A/B: the default dispatch without the QUAD map
     const int variant = f32_pairs ? 0 : g->variant;

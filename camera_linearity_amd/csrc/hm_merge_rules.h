@@ -1,0 +1,172 @@
+// hm_merge_rules.h - the argument rules of the fused merge's three C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32), written
+// once for both builds of the ABI: the device build's dispatcher (hm_merge.hip) and the host build (csrc_host/hm_host.cpp) include this file
+// and hold no argument test of their own - one ABI, one answer. Plain C++17 on hdrmerge.h and the standard headers: no HIP type, no OpenMP.
+//
+// What lives here: the struct_size values accepted and their widening, where a call's stds come from, every status a call can be refused
+// with - in the order the specification gives them: an earlier rule wins over a later one broken in the same call - and the algorithmic byte
+// count. What a build does with a validated call (MergeCall) is its own business.
+//
+// The one difference between the builds: a table call (hm_merge_std_table) with more than HM_MAX_FRAMES frames or variant <= -2 is
+// HM_EUNSUPPORTED on the device build, whose chunked path reads std frames (hm_merge.hip adds that refusal after check_merge_call), and runs
+// on the host build, which takes any number of frames in one pass. The device build's only other addition refuses what a tuning build
+// (-DHM_TUNE_NF) has no float32-output instantiations for.
+#pragma once
+#include "hdrmerge.h"
+#include <cstdint>
+#include <cstring>
+
+namespace hm_rules {
+
+enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32 };   // the C entry point called
+
+// where the call's per-frame stds come from
+enum StdSource {
+    STD_NONE,     // no std is formed (a std-entry call without out_val too: it is hm_merge's sum-of-weights call)
+    STD_F64,      // args->stds: N float64 frames
+    STD_TABLE,    // hm_merge_std_table: the (256, C) per-DN table; args->stds is NULL
+    STD_F32       // hm_merge_std_f32: N float32 frames, 4-byte aligned; MergeCall::a.stds addresses them
+};
+
+// A call that passed check_merge_call().
+struct MergeCall {
+    hm_merge_args a;                   // the caller's arguments in the current layout
+    StdSource std_src;
+    const double* std_table;           // STD_TABLE: the table, else NULL
+    bool f64in;                        // float64 frames (else uint8)
+    bool with_std;                     // std_src != STD_NONE
+    bool flat;                         // a flat field of either kind
+    bool hot;                          // at least one frame has a dark map
+    bool f32out;                       // out_kind == HM_OUT_F32
+    bool empty;                        // rows == 0: nothing to do; none of the rules after the shape of the tile has been looked at
+};
+
+inline bool ptr_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// struct_size values hm_merge accepts: the current layout and the two older ones of ABI version 1 (without the hot-pixel queue
+// workspace: 264 bytes; with it: 280 bytes) - the missing tail reads as zero (no workspace). out_kind took the place of a pad word those
+// callers never promised to zero: for them it is cleared (float64 outputs).
+inline bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
+    if (!g) return false;
+    const uint32_t sz = g->struct_size;
+    if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return false;
+    full = hm_merge_args{};
+    std::memcpy(&full, g, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
+    if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;
+    full.struct_size = sizeof(hm_merge_args);
+    return true;
+}
+
+// extra: the entry point's own pointer - NULL for hm_merge, std_table for hm_merge_std_table, stds_f32 for hm_merge_std_f32.
+// Returns the call's status; `call` is complete when that is HM_OK (with call.empty set there is nothing to run).
+inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const void* extra, MergeCall& call) {
+    call = MergeCall{};
+    if (!widen_args(g_in, call.a)) return HM_EINVAL;
+    hm_merge_args* const g = &call.a;
+    const int N = g->n_frames, C = g->channels;
+    // the std entries' own rules; without out_val they form no std and the call is hm_merge's
+    if (entry == ENTRY_STD_TABLE) {
+        const double* std_table = static_cast<const double*>(extra);
+        if (g->stds || !std_table || !g->icrf_diff) return HM_EINVAL;
+        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
+        if (g->out_val && !g->out_std) return HM_EINVAL;
+        if (!ptr_aligned(std_table, 8)) return HM_EALIGN;
+        if (g->out_val) { call.std_src = STD_TABLE; call.std_table = std_table; }
+    } else if (entry == ENTRY_STD_F32) {
+        const float* const* stds_f32 = static_cast<const float* const*>(extra);
+        if (g->stds || !stds_f32) return HM_EINVAL;
+        for (int i = 0; i < N; ++i)
+            if (!stds_f32[i]) return HM_EINVAL;
+        if (!g->icrf_diff) return HM_EINVAL;
+        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
+        if (g->out_val && !g->out_std) return HM_EINVAL;
+        for (int i = 0; i < N; ++i)
+            if (!ptr_aligned(stds_f32[i], 4)) return HM_EALIGN;
+        if (g->out_val) { call.std_src = STD_F32; g->stds = reinterpret_cast<const double* const*>(stds_f32); }
+    } else if (g->stds) call.std_src = STD_F64;
+    // hm_merge's rules
+    if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
+    if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
+    call.f32out = g->out_kind == HM_OUT_F32;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    if (g->rows == 0) {                                                  // empty tile: nothing to do
+        call.empty = true;
+        return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;
+    }
+    call.f64in = g->frames_f64 != nullptr;
+    if (call.f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;       // exactly one input kind
+    if (!g->exposures || !g->icrf) return HM_EINVAL;
+    const bool with_std = call.with_std = call.std_src != STD_NONE;
+    if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
+    if (g->out_val) {
+        if (with_std != (g->out_std != nullptr)) return HM_EINVAL;
+        if (with_std && !g->icrf_diff) return HM_EINVAL;
+    }
+    if (!call.f64in && (!g->w_lut || (with_std && !g->dw_lut))) return HM_EINVAL;
+    call.flat = g->flat_u8 || g->flat_f64;
+    if (g->flat_u8 && g->flat_f64) return HM_EINVAL;
+    if (call.flat && with_std && !g->flat_std) return HM_EINVAL;
+    // geometry
+    if (g->row0 < 0 || g->row0 + g->rows > g->height) return HM_ESHAPE;
+    if (g->buf_row0 < 0 || g->buf_row0 > g->row0 || g->buf_row0 + g->buf_rows > g->height ||
+        g->buf_row0 + g->buf_rows < g->row0 + g->rows) return HM_ESHAPE;
+    if (g->darks_u8) {
+        if (!g->dark_min_dn) return HM_EINVAL;
+        for (int i = 0; i < N; ++i) call.hot = call.hot || (g->darks_u8[i] != nullptr);
+    }
+    if (call.hot) {
+        const int k = g->median_k;
+        if (k < 3 || k > 7 || (k % 2) == 0) return HM_EINVAL;
+        const int64_t r = k / 2;
+        const int64_t need_lo = g->row0 - r < 0 ? 0 : g->row0 - r;
+        const int64_t need_hi = g->row0 + g->rows + r > g->height ? g->height : g->row0 + g->rows + r;
+        if (g->buf_row0 > need_lo || g->buf_row0 + g->buf_rows < need_hi) return HM_ESHAPE;   // halo too small
+    }
+    // per-frame pointers and exposures (any N: neither build's hm_merge has a frame limit)
+    for (int i = 0; i < N; ++i) {
+        const void* f = call.f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
+        if (!f) return HM_EINVAL;
+        if (call.f64in && !ptr_aligned(f, 8)) return HM_EALIGN;
+        if (g->stds) {
+            if (!g->stds[i]) return HM_EINVAL;
+            if (!ptr_aligned(g->stds[i], call.std_src == STD_F32 ? 4 : 8)) return HM_EALIGN;
+        }
+        if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
+    }
+    const int out_align = call.f32out ? 4 : 8;
+    if ((g->out_val && !ptr_aligned(g->out_val, out_align)) || (g->out_std && !ptr_aligned(g->out_std, out_align)) ||
+        (g->out_sum_w && !ptr_aligned(g->out_sum_w, 8))) return HM_EALIGN;
+    // What only the device build's one-launch kernels have, refused by both builds so that a call means the same on both: float32 outputs
+    // (the chunked path keeps float64 running sums in out_val / out_std and the row-band loop advances output pointers by float64 elements)
+    // and float32 std frames (the chunked path reads float64 ones).
+    const bool chunked = N > HM_MAX_FRAMES || g->variant <= -2;
+    if (call.f32out && (chunked || g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
+    if (call.std_src == STD_F32 && chunked) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+// Algorithmic bytes of a call through `entry` (hdrmerge.h: hm_merge_algorithmic_bytes): STD_TABLE calls read no std stream, STD_F32 calls
+// 4-byte ones (args->stds is NULL in both). Takes the caller's arguments as they are: a refused call has a count too.
+inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry) {
+    if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
+    const int64_t E = g->rows * g->width * g->channels;
+    const int N = g->n_frames;
+    const bool lut = entry == ENTRY_STD_TABLE, sd32 = entry == ENTRY_STD_F32;
+    const bool s = lut || sd32 || g->stds != nullptr;
+    const int64_t in_b = g->frames_f64 ? 8 : 1;
+    int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
+    const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
+    if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
+    if (g->out_sum_w) per += 8;
+    if (g->flat_u8 || g->flat_f64) per += (g->flat_u8 ? 1 : 8) + ((s && g->flat_std) ? 8 : 0);
+    if (g->darks_u8)                                       // every DISTINCT (map, threshold) is read once (the device build's scan)
+        for (int i = 0; i < N; ++i) {
+            if (!g->darks_u8[i]) continue;
+            bool seen = false;
+            for (int k = 0; k < i; ++k)
+                seen = seen || (g->darks_u8[k] == g->darks_u8[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
+            per += seen ? 0 : 1;
+        }
+    return per * E;
+}
+
+}  // namespace hm_rules

@@ -13,6 +13,7 @@
 // hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twin of
 // hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
 #include "hdrmerge.h"
+#include "../csrc/hm_merge_rules.h"
 #include "../csrc/hm_tiff_lzw_body.h"
 #include "../csrc/hm_tiff_lzw_enc_body.h"
 
@@ -282,147 +283,33 @@ size_t hm_merge_hot_workspace_bytes(int64_t) { return 16; }
 size_t hm_merge_hot_workspace_min_bytes(int64_t) { return 16; }
 size_t hm_merge_frames_workspace_bytes(int, int64_t, int) { return 0; }           // any number of frames in one pass on the host
 
-// lut: hm_merge_std_table - std outputs without the N float64 std streams; sd32: hm_merge_std_f32 - N float32 std streams
-static int64_t merge_algorithmic_bytes(const hm_merge_args* g, bool lut, bool sd32 = false) {
-    if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
-    const int64_t E = g->rows * g->width * g->channels;
-    const bool s = lut || sd32 || g->stds != nullptr;
-    int64_t per = g->n_frames * ((g->frames_f64 ? 8 : 1) + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
-    const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;
-    if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
-    if (g->out_sum_w) per += 8;
-    if (g->flat_u8 || g->flat_f64) per += (g->flat_u8 ? 1 : 8) + ((s && g->flat_std) ? 8 : 0);
-    if (g->darks_u8)
-        for (int i = 0; i < g->n_frames; ++i) {
-            if (!g->darks_u8[i]) continue;
-            bool seen = false;
-            for (int k = 0; k < i; ++k)
-                seen = seen || (g->darks_u8[k] == g->darks_u8[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
-            per += seen ? 0 : 1;
-        }
-    return per * E;
-}
-int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false); }
-int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, true); }
-int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return merge_algorithmic_bytes(g, false, true); }
+// The argument rules of the three entries and the byte count: ../csrc/hm_merge_rules.h, the copy the device build compiles too. This build
+// adds no refusal of its own.
+using hm_rules::MergeCall;
+using hm_rules::MergeEntry;
 
-// std_table: NULL for hm_merge; hm_merge_std_table's table (its own argument rules, then hm_merge's with the table in place of the std frames)
-// stds_f32 / f32_call: hm_merge_std_f32 (its own argument rules, then hm_merge's with the float32 frames in the place of args->stds: on return
-// full.stds addresses them, and sd32 says so, unless the call has no out_val and forms no std)
-static int merge_check(const hm_merge_args* g_in, hm_merge_args& full, bool& hot, const double* std_table = nullptr, bool table_call = false,
-                       const float* const* stds_f32 = nullptr, bool f32_call = false, bool* sd32_out = nullptr) {
-    if (!g_in) return HM_EINVAL;
-    const uint32_t sz = g_in->struct_size;
-    if (sz != sizeof(hm_merge_args) && sz != 264u && sz != 280u) return HM_EINVAL;
-    full = hm_merge_args{};
-    std::memcpy(&full, g_in, sz < sizeof(hm_merge_args) ? sz : sizeof(hm_merge_args));
-    if (sz != sizeof(hm_merge_args)) full.out_kind = HM_OUT_F64;                  // the older layouts carried an unspecified pad word there
-    const hm_merge_args* g = &full;
-    if (table_call) {
-        if (g->stds || !std_table || !g->icrf_diff) return HM_EINVAL;
-        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
-        if (g->out_val && !g->out_std) return HM_EINVAL;
-        if (!aligned8(std_table)) return HM_EALIGN;
-        if (!g->out_val) std_table = nullptr;                                       // no std is formed: hm_merge's sum-of-weights call
-    }
-    bool sd32 = false;
-    if (f32_call) {
-        if (g->stds || !stds_f32) return HM_EINVAL;
-        for (int i = 0; i < g->n_frames; ++i)
-            if (!stds_f32[i]) return HM_EINVAL;
-        if (!g->icrf_diff) return HM_EINVAL;
-        if (g->frames_u8 && !g->dw_lut) return HM_EINVAL;
-        if (g->out_val && !g->out_std) return HM_EINVAL;
-        for (int i = 0; i < g->n_frames; ++i)
-            if ((reinterpret_cast<uintptr_t>(stds_f32[i]) & 3u) != 0) return HM_EALIGN;
-        if (g->out_val) {                                                           // (without out_val no std is formed: hm_merge's sum-of-weights call)
-            full.stds = reinterpret_cast<const double* const*>(stds_f32);
-            sd32 = true;
-        }
-    }
-    if (sd32_out) *sd32_out = sd32;
-    const int N = g->n_frames, C = g->channels;
-    if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
-    if (g->out_kind != HM_OUT_F64 && g->out_kind != HM_OUT_F32) return HM_EINVAL;
-    const bool f32out = g->out_kind == HM_OUT_F32;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (g->rows == 0) return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;   // empty tile: nothing to do (as the device build)
-    const bool f64in = g->frames_f64 != nullptr;
-    if (f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;
-    if (!g->exposures || !g->icrf) return HM_EINVAL;
-    const bool with_std = g->stds != nullptr || std_table != nullptr;
-    if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
-    if (g->out_val) {
-        if (with_std != (g->out_std != nullptr)) return HM_EINVAL;
-        if (with_std && !g->icrf_diff) return HM_EINVAL;
-    }
-    if (!f64in && (!g->w_lut || (with_std && !g->dw_lut))) return HM_EINVAL;
-    const bool flat = g->flat_u8 || g->flat_f64;
-    if (g->flat_u8 && g->flat_f64) return HM_EINVAL;
-    if (flat && with_std && !g->flat_std) return HM_EINVAL;
-    if (g->row0 < 0 || g->row0 + g->rows > g->height) return HM_ESHAPE;
-    if (g->buf_row0 < 0 || g->buf_row0 > g->row0 || g->buf_row0 + g->buf_rows > g->height ||
-        g->buf_row0 + g->buf_rows < g->row0 + g->rows) return HM_ESHAPE;
-    hot = false;
-    if (g->darks_u8) {
-        if (!g->dark_min_dn) return HM_EINVAL;
-        for (int i = 0; i < N; ++i) hot = hot || (g->darks_u8[i] != nullptr);
-    }
-    if (hot) {
-        const int k = g->median_k;
-        if (k < 3 || k > 7 || (k % 2) == 0) return HM_EINVAL;
-        const int64_t r = k / 2;
-        const int64_t need_lo = g->row0 - r < 0 ? 0 : g->row0 - r;
-        const int64_t need_hi = g->row0 + g->rows + r > g->height ? g->height : g->row0 + g->rows + r;
-        if (g->buf_row0 > need_lo || g->buf_row0 + g->buf_rows < need_hi) return HM_ESHAPE;
-    }
-    for (int i = 0; i < N; ++i) {
-        const void* f = f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
-        if (!f) return HM_EINVAL;
-        if (f64in && !aligned8(f)) return HM_EALIGN;
-        if (g->stds) {
-            if (!g->stds[i]) return HM_EINVAL;
-            if (!sd32 && !aligned8(g->stds[i])) return HM_EALIGN;
-        }
-        if (!(g->exposures[i] > 0.0)) return HM_EINVAL;
-    }
-    const auto out_aligned = [&](const void* q) { return f32out ? (reinterpret_cast<uintptr_t>(q) & 3u) == 0 : aligned8(q); };
-    if ((g->out_val && !out_aligned(g->out_val)) || (g->out_std && !out_aligned(g->out_std)) || (g->out_sum_w && !aligned8(g->out_sum_w)))
-        return HM_EALIGN;
-    // the refusals of the device build (its chunked path and row-band loop are float64 only), so that a call means the same on both
-    if (f32out && g->rows > 0 && (N > HM_MAX_FRAMES || g->variant <= -2 ||
-                                  g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
-    // (float32 std frames exist in the device build's one-launch kernels only: one ABI, one answer)
-    if (sd32 && (N > HM_MAX_FRAMES || g->variant <= -2)) return HM_EUNSUPPORTED;
-    return HM_OK;
-}
+int64_t hm_merge_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_MERGE); }
+int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_STD_TABLE); }
+int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_STD_F32); }
 
-static int merge_describe(const hm_merge_args* g, const double* std_table, bool table_call, char* buf, int buf_len) {
-    if (!buf || buf_len < 1) return HM_EINVAL;
-    hm_merge_args full; bool hot = false;
-    const int rc = merge_check(g, full, hot, std_table, table_call);
-    const bool lut = table_call && full.out_val;
-    if (rc == HM_OK && full.rows > 0)
-        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr || lut, hot,
-                      lut ? ",std=lut" : "", full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
+// extra: the entry's own pointer (hm_merge_rules.h). The std entries return for NULL args before anything else is read - or written.
+static int merge_describe(const hm_merge_args* g, MergeEntry entry, const void* extra, char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || (!g && entry != hm_rules::ENTRY_MERGE)) return HM_EINVAL;
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g, entry, extra, call);
+    if (rc == HM_OK && !call.empty)
+        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s%s>(N=%d)", call.f64in, call.with_std, call.hot,
+                      call.std_src == hm_rules::STD_TABLE ? ",std=lut" : call.std_src == hm_rules::STD_F32 ? ",std=f32" : "",
+                      call.f32out ? ",out=f32" : "", call.a.n_frames);
     else buf[0] = 0;
     return rc;
 }
-int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, nullptr, false, buf, buf_len); }
+int hm_merge_describe(const hm_merge_args* g, char* buf, int buf_len) { return merge_describe(g, hm_rules::ENTRY_MERGE, nullptr, buf, buf_len); }
 int hm_merge_std_table_describe(const hm_merge_args* g, const double* std_table, char* buf, int buf_len) {
-    if (!g) return HM_EINVAL;                                                     // before anything else is read - or written
-    return merge_describe(g, std_table, true, buf, buf_len);
+    return merge_describe(g, hm_rules::ENTRY_STD_TABLE, std_table, buf, buf_len);
 }
 int hm_merge_std_f32_describe(const hm_merge_args* g, const float* const* stds_f32, char* buf, int buf_len) {
-    if (!g) return HM_EINVAL;                                                     // before anything else is read - or written
-    if (!buf || buf_len < 1) return HM_EINVAL;
-    hm_merge_args full; bool hot = false, sd32 = false;
-    const int rc = merge_check(g, full, hot, nullptr, false, stds_f32, true, &sd32);
-    if (rc == HM_OK && full.rows > 0)
-        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_host<f64in=%d,std=%d,hot=%d%s%s>(N=%d)", full.frames_f64 != nullptr, full.stds != nullptr, hot,
-                      sd32 ? ",std=f32" : "", full.out_kind == HM_OUT_F32 ? ",out=f32" : "", full.n_frames);
-    else buf[0] = 0;
-    return rc;
+    return merge_describe(g, hm_rules::ENTRY_STD_F32, stds_f32, buf, buf_len);
 }
 
 // exposure_series.py:340-394 per output element, the operation sequence of merge_one_element() (hm_merge_dev.h): S in frame order;
@@ -601,15 +488,15 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
 
 extern "C" {
 
-static int merge_run(const hm_merge_args* g_in, const double* std_table, bool table_call, const float* const* stds_f32 = nullptr, bool f32_call = false) {
-    hm_merge_args full; bool hot = false, sd32 = false;
-    const int rc = merge_check(g_in, full, hot, std_table, table_call, stds_f32, f32_call, &sd32);
-    if (rc != HM_OK) return rc;
-    const hm_merge_args* g = &full;
-    if (g->rows == 0) return HM_OK;
+static int merge_run(const hm_merge_args* g_in, MergeEntry entry, const void* extra) {
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g_in, entry, extra, call);
+    if (rc != HM_OK || call.empty) return rc;
+    const hm_merge_args* g = &call.a;
     const int N = g->n_frames;
-    if (!g->out_val) std_table = nullptr;
-    const bool f64in = g->frames_f64 != nullptr, with_std = (g->stds != nullptr || std_table != nullptr) && g->out_val != nullptr;
+    const double* const std_table = call.std_table;
+    const bool sd32 = call.std_src == hm_rules::STD_F32, f64in = call.f64in, hot = call.hot;
+    const bool with_std = call.with_std && g->out_val != nullptr;                 // (float64 std frames without out_val: no std is formed)
     std::vector<double> inv_t(static_cast<size_t>(N));
     for (int i = 0; i < N; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
     const int k = hot ? g->median_k : 3;
@@ -627,9 +514,9 @@ static int merge_run(const hm_merge_args* g_in, const double* std_table, bool ta
     return HM_OK;
 }
 
-int hm_merge(const hm_merge_args* g_in, void*) { return merge_run(g_in, nullptr, false); }
-int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void*) { return merge_run(g_in, std_table, true); }
-int hm_merge_std_f32(const hm_merge_args* g_in, const float* const* stds_f32, void*) { return merge_run(g_in, nullptr, false, stds_f32, true); }
+int hm_merge(const hm_merge_args* g_in, void*) { return merge_run(g_in, hm_rules::ENTRY_MERGE, nullptr); }
+int hm_merge_std_table(const hm_merge_args* g_in, const double* std_table, void*) { return merge_run(g_in, hm_rules::ENTRY_STD_TABLE, std_table); }
+int hm_merge_std_f32(const hm_merge_args* g_in, const float* const* stds_f32, void*) { return merge_run(g_in, hm_rules::ENTRY_STD_F32, stds_f32); }
 
 }  // extern "C"
 

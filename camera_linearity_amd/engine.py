@@ -268,52 +268,43 @@ class MergePlan:
         self._ref = C.byref(args)
         self.host = self.device.type != "cuda"             # a plan of the host backend (built inside nat.host_mode())
         self.std_table = std_table                         # (256, C) float64 per-DN std table: the plan goes through hm_merge_std_table
-        self._table = None if std_table is None else std_table.data_ptr()
-        self._stds_f32 = stds_f32                          # ctypes array of N pointers to float32 std frames: the plan goes through hm_merge_std_f32
-
-    def _call(self, lib, stream):
-        if self._stds_f32 is not None:
-            return lib.hm_merge_std_f32(self._ref, self._stds_f32, stream)
-        if self._table is None:
-            return lib.hm_merge(self._ref, stream)
-        return lib.hm_merge_std_table(self._ref, self._table, stream)
+        # the C entry point the plan goes through and the entry's own argument after the struct: the ctypes array of N pointers to float32
+        # std frames (hm_merge_std_f32), the table, or none
+        if stds_f32 is not None:
+            self._entry, self._extra = "hm_merge_std_f32", (stds_f32,)
+        elif std_table is not None:
+            self._entry, self._extra = "hm_merge_std_table", (std_table.data_ptr(),)
+        else:
+            self._entry, self._extra = "hm_merge", ()
+        lib = nat.host_lib() if self.host else nat.hip_lib
+        self._run = getattr(lib, self._entry)
+        self._describe = getattr(lib, self._entry + "_describe")
+        self._bytes = getattr(nat.hip_lib, self._entry + "_algorithmic_bytes")
 
     def launch(self, stream: Optional[int] = None) -> None:
-        what = "hm_merge_std_f32" if self._stds_f32 is not None else "hm_merge" if self._table is None else "hm_merge_std_table"
         if self.host:
             with nat.host_mode():
-                nat.check(self._call(nat.lib, None), what)
+                nat.check(self._run(self._ref, *self._extra, None), self._entry)
             return
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if torch.cuda.current_device() == self.device.index:
-            rc = self._call(nat.lib, stream)
+            rc = self._run(self._ref, *self._extra, stream)
         else:
             with _on(self.device):
-                rc = self._call(nat.lib, stream)
+                rc = self._run(self._ref, *self._extra, stream)
         if rc:
-            nat.check(rc, what)
+            nat.check(rc, self._entry)
 
     @property
     def algorithmic_bytes(self) -> int:
-        if self._stds_f32 is not None:
-            return int(nat.hip_lib.hm_merge_std_f32_algorithmic_bytes(C.byref(self.args)))
-        if self._table is not None:
-            return int(nat.hip_lib.hm_merge_std_table_algorithmic_bytes(C.byref(self.args)))
-        return int(nat.hip_lib.hm_merge_algorithmic_bytes(C.byref(self.args)))
+        return int(self._bytes(self._ref))
 
     @property
     def kernels(self) -> str:
-        """Names of the kernels launch() dispatches to, in launch order (hm_merge_describe / hm_merge_std_table_describe /
-        hm_merge_std_f32_describe: the library's own dispatch, dry)."""
+        """Names of the kernels launch() dispatches to, in launch order (the entry's _describe form: the library's own dispatch, dry)."""
         buf = C.create_string_buffer(512)
-        lib = nat.host_lib() if self.host else nat.hip_lib
-        if self._stds_f32 is not None:
-            nat.check(lib.hm_merge_std_f32_describe(self._ref, self._stds_f32, C.addressof(buf), 512), "hm_merge_std_f32_describe")
-        elif self._table is not None:
-            nat.check(lib.hm_merge_std_table_describe(self._ref, self._table, C.addressof(buf), 512), "hm_merge_std_table_describe")
-        else:
-            nat.check(lib.hm_merge_describe(self._ref, buf, 512), "hm_merge_describe")
+        nat.check(self._describe(self._ref, *self._extra, buf, 512), self._entry + "_describe")
         return buf.value.decode()
 
 
