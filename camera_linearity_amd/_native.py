@@ -84,6 +84,11 @@ _SIGNATURES = {
     "hm_merge_std_f32": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p]),
     "hm_merge_std_f32_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int]),
     "hm_merge_std_f32_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
+    # the merge on uint16 DN frames with an explicit bit depth (frames: a ctypes array of N pointers, passed as its address)
+    "hm_merge_u16": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_int, C.c_void_p]),
+    "hm_merge_u16_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "hm_merge_u16_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
+    "hm_linearize_u16": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
@@ -168,7 +173,13 @@ _SIGNATURES = {
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# Entry points that fill HOST arrays whose length follows from a scalar argument (2**bit_depth doubles each): bound like the others, kept
+# apart from _SIGNATURES because a caller must size the arrays from that argument first (weight_luts_host does).
+_HOST_TABLE_SIGNATURES = {
+    "hm_gaussian_weight_lut_bits_host": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_HOST_TABLE_SIGNATURES)
 
 
 class _Lib:
@@ -199,7 +210,7 @@ def _load():
             f"libhdrmerge.so not found at {LIB_PATH}: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C camera_linearity_amd/csrc` (hipcc, --offload-arch=gfx950). There is no CPU fallback.")
     lib = _Lib(C.CDLL(str(LIB_PATH)))
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_HOST_TABLE_SIGNATURES}.items():
         lib._bind(name, res, args)
     return lib
 
@@ -223,7 +234,7 @@ def host_lib():
         if not HOST_LIB_PATH.exists():
             raise ImportError(f"libhdrmerge_host.so not found at {HOST_LIB_PATH}: build it with `make -C camera_linearity_amd/csrc host` (g++)")
         h = _Lib(C.CDLL(str(HOST_LIB_PATH)))
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_HOST_TABLE_SIGNATURES}.items():
             if name not in HOST_ONLY_MISSING:
                 h._bind(name, res, args)
         if h.hm_version() != HM_ABI_VERSION:

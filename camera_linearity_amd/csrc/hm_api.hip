@@ -44,6 +44,20 @@ extern "C" int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) {
     return HM_OK;
 }
 
+// the same formula on the grid v = k / (2^bit_depth - 1): the tables of hm_merge_u16 (bit_depth = 8: the tables above)
+extern "C" int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut, double* dw_lut) {
+    if ((!w_lut && !dw_lut) || bit_depth < 8 || bit_depth > 16) return HM_EINVAL;
+    const int n = 1 << bit_depth;
+    const double max_dn = static_cast<double>(n - 1);
+    for (int k = 0; k < n; ++k) {
+        const double v = static_cast<double>(k) / max_dn;
+        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
+        if (w_lut) w_lut[k] = y;
+        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
+    }
+    return HM_OK;
+}
+
 // number of CUs of the current device (hm_common.h; every unit sizes its grids with it)
 namespace hm {
 static int g_cu_count = 0;

@@ -265,9 +265,42 @@ __global__ __launch_bounds__(256) void k_linearize_stream(const void* __restrict
     }
 }
 
+// ---------------- linearize, uint16 DNs ----------------
+// hm_linearize_u16: tables of 2^bit_depth rows stay in global memory (up to 2 MiB at 16 bits), one element per thread, every gather at
+// the masked index DN & (2^bit_depth - 1).
+template <bool STD>
+__global__ __launch_bounds__(256) void k_linearize_u16(const uint16_t* __restrict__ dn, const double* __restrict__ sd,
+                                                       const double* __restrict__ icrf, const double* __restrict__ icrf_diff,
+                                                       double* __restrict__ out_val, double* __restrict__ out_std,
+                                                       uint16_t* __restrict__ out_idx, int64_t n, int C, int lut_stride, uint32_t mask) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
+        const uint32_t k = static_cast<uint32_t>(dn[e]) & mask;
+        const int64_t at = lut_stride == 1 ? static_cast<int64_t>(k) : static_cast<int64_t>(k) * C + (e % C);
+        out_val[e] = icrf[at];
+        if (STD) out_std[e] = icrf_diff[at] * sd[e];                                     // measurand.py:512
+        if (out_idx) out_idx[e] = static_cast<uint16_t>(k);
+    }
+}
+
 }  // namespace hm
 
 using namespace hm;
+
+extern "C" int hm_linearize_u16(const uint16_t* dn, const double* std, const double* icrf, const double* icrf_diff,
+                                double* out_val, double* out_std, uint16_t* out_idx, int64_t n, int C, int lut_stride, int bit_depth, void* stream) {
+    if (n < 0 || C < 1 || !icrf || (n > 0 && (!dn || !out_val))) return HM_EINVAL;
+    if ((lut_stride != 1 && lut_stride != C) || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
+    if (n == 0) return HM_OK;
+    if (!aligned(dn, 2) || (out_idx && !aligned(out_idx, 2)) || !aligned(out_val, 8) || (out_std && !aligned(out_std, 8)) || (std && !aligned(std, 8)))
+        return HM_EALIGN;
+    const bool with_std = std && icrf_diff && out_std;                       // measurand.py:498-500
+    const unsigned grid = stream_grid(n, 256, 8);
+    const uint32_t mask = (1u << bit_depth) - 1u;
+    if (with_std) hipLaunchKernelGGL((k_linearize_u16<true>), dim3(grid), dim3(256), 0, as_stream(stream), dn, std, icrf, icrf_diff, out_val, out_std, out_idx, n, C, lut_stride, mask);
+    else hipLaunchKernelGGL((k_linearize_u16<false>), dim3(grid), dim3(256), 0, as_stream(stream), dn, std, icrf, icrf_diff, out_val, out_std, out_idx, n, C, lut_stride, mask);
+    return launch_status();
+}
 
 extern "C" int hm_u8_to_unit_f64(const uint8_t* dn, double* out, int64_t n, void* stream) {
     if (n < 0 || (n > 0 && (!dn || !out))) return HM_EINVAL;

@@ -1,4 +1,4 @@
-// hm_merge_rules.h - the argument rules of the fused merge's three C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32), written
+// hm_merge_rules.h - the argument rules of the fused merge's four C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32, hm_merge_u16), written
 // once for both builds of the ABI: the device build's dispatcher (hm_merge.hip) and the host build (csrc_host/hm_host.cpp) include this file
 // and hold no argument test of their own - one ABI, one answer. Plain C++17 on hdrmerge.h and the standard headers: no HIP type, no OpenMP.
 //
@@ -17,7 +17,34 @@
 
 namespace hm_rules {
 
-enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32 };   // the C entry point called
+enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32, ENTRY_U16 };   // the C entry point called
+
+// hm_merge_u16's own arguments (check_merge_call's `extra` for ENTRY_U16)
+struct U16Extra { const uint16_t* const* frames; int bit_depth; };
+
+// hm_merge_u16: which of a call's tables a streaming kernel holds in LDS, the bytes that takes, and the fit rule - at most a gfx950
+// workgroup's 160 KiB (hdrmerge.h states all of it for callers). n = 2^bit_depth rows:
+//   U16_TAB_ALL     value-only w[n] | (w g)[n C]: 8 (1 + C) n bytes; with std {w, dw}[n] | {g, d}[n C]: 16 (1 + C) n bytes
+//   U16_TAB_WDW_G   (std calls) {w, dw}[n] | g[n C]: 8 (2 + C) n bytes; icrf_diff is gathered from global memory
+//   U16_TAB_PER_DN  the per-DN tables only - w[n]: 8 n bytes, with std {w, dw}[n]: 16 n bytes; the per-(DN, channel) ones from global memory
+//   U16_TAB_GLOBAL  nothing in LDS
+enum U16Tables { U16_TAB_GLOBAL = 0, U16_TAB_PER_DN = 1, U16_TAB_WDW_G = 2, U16_TAB_ALL = 3 };
+constexpr int64_t kU16MaxLds = 160 * 1024;
+inline int64_t u16_table_bytes(int bit_depth, int C, bool with_std, int place = U16_TAB_ALL) {
+    const int64_t n = int64_t{1} << bit_depth;
+    switch (place) {
+        case U16_TAB_ALL: return (with_std ? 16 : 8) * int64_t{1 + C} * n;
+        case U16_TAB_WDW_G: return 8 * int64_t{2 + C} * n;
+        case U16_TAB_PER_DN: return (with_std ? 16 : 8) * n;
+        default: return 0;
+    }
+}
+inline bool u16_tables_fit_lds(int bit_depth, int C, bool with_std) { return u16_table_bytes(bit_depth, C, with_std) <= kU16MaxLds; }
+// the largest PARTIAL placement that fits (variant 3; the library's choice where not everything fits), U16_TAB_GLOBAL when none does
+inline int u16_mixed_tables(int bit_depth, int C, bool with_std) {
+    if (with_std && u16_table_bytes(bit_depth, C, true, U16_TAB_WDW_G) <= kU16MaxLds) return U16_TAB_WDW_G;
+    return u16_table_bytes(bit_depth, C, with_std, U16_TAB_PER_DN) <= kU16MaxLds ? U16_TAB_PER_DN : U16_TAB_GLOBAL;
+}
 
 // where the call's per-frame stds come from
 enum StdSource {
@@ -32,7 +59,9 @@ struct MergeCall {
     hm_merge_args a;                   // the caller's arguments in the current layout
     StdSource std_src;
     const double* std_table;           // STD_TABLE: the table, else NULL
-    bool f64in;                        // float64 frames (else uint8)
+    bool f64in;                        // float64 frames (else uint8, or uint16 in a hm_merge_u16 call)
+    const uint16_t* const* frames_u16; // hm_merge_u16: the N frames (a.frames_u8 and a.frames_f64 are NULL), else NULL
+    int bit_depth;                     // hm_merge_u16: 9..16, else 0
     bool with_std;                     // std_src != STD_NONE
     bool flat;                         // a flat field of either kind
     bool hot;                          // at least one frame has a dark map
@@ -56,7 +85,8 @@ inline bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
     return true;
 }
 
-// extra: the entry point's own pointer - NULL for hm_merge, std_table for hm_merge_std_table, stds_f32 for hm_merge_std_f32.
+// extra: the entry point's own pointer - NULL for hm_merge, std_table for hm_merge_std_table, stds_f32 for hm_merge_std_f32, a U16Extra
+// for hm_merge_u16.
 // Returns the call's status; `call` is complete when that is HM_OK (with call.empty set there is nothing to run).
 inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const void* extra, MergeCall& call) {
     call = MergeCall{};
@@ -82,6 +112,17 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         for (int i = 0; i < N; ++i)
             if (!ptr_aligned(stds_f32[i], 4)) return HM_EALIGN;
         if (g->out_val) { call.std_src = STD_F32; g->stds = reinterpret_cast<const double* const*>(stds_f32); }
+    } else if (entry == ENTRY_U16) {
+        const U16Extra* x = static_cast<const U16Extra*>(extra);
+        if (g->frames_u8 || g->frames_f64 || !x || !x->frames) return HM_EINVAL;
+        for (int i = 0; i < N; ++i)
+            if (!x->frames[i]) return HM_EINVAL;
+        if (x->bit_depth < 9 || x->bit_depth > 16 || !g->w_lut) return HM_EINVAL;
+        if (g->stds && (!g->icrf_diff || !g->dw_lut)) return HM_EINVAL;
+        for (int i = 0; i < N; ++i)
+            if (!ptr_aligned(x->frames[i], 2)) return HM_EALIGN;
+        call.frames_u16 = x->frames; call.bit_depth = x->bit_depth;
+        if (g->stds) call.std_src = STD_F64;
     } else if (g->stds) call.std_src = STD_F64;
     // hm_merge's rules
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
@@ -93,7 +134,7 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         return g->row0 >= 0 && g->row0 <= g->height ? HM_OK : HM_ESHAPE;
     }
     call.f64in = g->frames_f64 != nullptr;
-    if (call.f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;       // exactly one input kind
+    if (!call.frames_u16 && call.f64in == (g->frames_u8 != nullptr)) return HM_EINVAL;       // exactly one input kind
     if (!g->exposures || !g->icrf) return HM_EINVAL;
     const bool with_std = call.with_std = call.std_src != STD_NONE;
     if (!g->out_val && !g->out_sum_w) return HM_EINVAL;
@@ -123,7 +164,8 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
     }
     // per-frame pointers and exposures (any N: neither build's hm_merge has a frame limit)
     for (int i = 0; i < N; ++i) {
-        const void* f = call.f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
+        const void* f = call.frames_u16 ? static_cast<const void*>(call.frames_u16[i])
+                        : call.f64in ? static_cast<const void*>(g->frames_f64[i]) : static_cast<const void*>(g->frames_u8[i]);
         if (!f) return HM_EINVAL;
         if (call.f64in && !ptr_aligned(f, 8)) return HM_EALIGN;
         if (g->stds) {
@@ -141,6 +183,15 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
     const bool chunked = N > HM_MAX_FRAMES || g->variant <= -2;
     if (call.f32out && (chunked || g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     if (call.std_src == STD_F32 && chunked) return HM_EUNSUPPORTED;
+    if (entry == ENTRY_U16) {
+        // variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
+        // memory / split between the two (the largest partial placement)
+        if (g->variant > 3) return HM_EINVAL;
+        // what hm_merge_u16 leaves out: dark maps and uint8 flat fields (8-bit data), the chunked path
+        if (g->darks_u8 || g->flat_u8 || chunked) return HM_EUNSUPPORTED;
+        if (g->variant == 1 && !u16_tables_fit_lds(call.bit_depth, C, with_std && g->out_val)) return HM_EUNSUPPORTED;
+        if (g->variant == 3 && u16_mixed_tables(call.bit_depth, C, with_std && g->out_val) == U16_TAB_GLOBAL) return HM_EUNSUPPORTED;
+    }
     return HM_OK;
 }
 
@@ -152,7 +203,7 @@ inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry)
     const int N = g->n_frames;
     const bool lut = entry == ENTRY_STD_TABLE, sd32 = entry == ENTRY_STD_F32;
     const bool s = lut || sd32 || g->stds != nullptr;
-    const int64_t in_b = g->frames_f64 ? 8 : 1;
+    const int64_t in_b = entry == ENTRY_U16 ? 2 : g->frames_f64 ? 8 : 1;
     int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));

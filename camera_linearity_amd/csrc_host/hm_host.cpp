@@ -246,6 +246,19 @@ int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) {
     return HM_OK;
 }
 
+int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut, double* dw_lut) {
+    if ((!w_lut && !dw_lut) || bit_depth < 8 || bit_depth > 16) return HM_EINVAL;
+    const int n = 1 << bit_depth;
+    const double max_dn = static_cast<double>(n - 1);
+    for (int k = 0; k < n; ++k) {
+        const double v = static_cast<double>(k) / max_dn;
+        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
+        if (w_lut) w_lut[k] = y;
+        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
+    }
+    return HM_OK;
+}
+
 int hm_u8_to_unit_f64(const uint8_t* dn, double* out, int64_t n, void*) {
     if (n < 0 || (n > 0 && (!dn || !out))) return HM_EINVAL;
 #pragma omp parallel for schedule(static)
@@ -276,6 +289,26 @@ int hm_linearize_u8(const uint8_t* dn, const double* std_, const double* icrf, c
 int hm_linearize_f64(const double* v, const double* std_, const double* icrf, const double* icrf_diff, double* out_val, double* out_std,
                      uint8_t* out_idx, int64_t n, int C, int lut_stride, void*) {
     return linearize_any(nullptr, v, std_, icrf, icrf_diff, out_val, out_std, out_idx, n, C, lut_stride);
+}
+// uint16 DNs: idx = dn & (2^bit_depth - 1), tables of 2^bit_depth rows
+int hm_linearize_u16(const uint16_t* dn, const double* std_, const double* icrf, const double* icrf_diff, double* out_val, double* out_std,
+                     uint16_t* out_idx, int64_t n, int C, int lut_stride, int bit_depth, void*) {
+    if (n < 0 || C < 1 || !icrf || (n > 0 && (!dn || !out_val))) return HM_EINVAL;
+    if ((lut_stride != 1 && lut_stride != C) || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
+    if (n == 0) return HM_OK;
+    if ((reinterpret_cast<uintptr_t>(dn) & 1u) || (reinterpret_cast<uintptr_t>(out_idx) & 1u) || !aligned8(out_val) || (out_std && !aligned8(out_std)) ||
+        (std_ && !aligned8(std_))) return HM_EALIGN;
+    const bool use_std = std_ && icrf_diff && out_std;                            // measurand.py:498-500
+    const uint32_t mask = (1u << bit_depth) - 1u;
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < n; ++e) {
+        const uint32_t k = static_cast<uint32_t>(dn[e]) & mask;
+        const int64_t at = lut_stride == 1 ? k : static_cast<int64_t>(k) * C + (e % C);
+        out_val[e] = icrf[at];
+        if (use_std) out_std[e] = icrf_diff[at] * std_[e];                        // :512
+        if (out_idx) out_idx[e] = static_cast<uint16_t>(k);
+    }
+    return HM_OK;
 }
 
 // ---- rows 5-9: the merge ------------------------------------------------------------------------------------------
@@ -486,7 +519,83 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
     }
 }
 
+// hm_merge_u16: uint16 DN frames, tables of 2^bit_depth rows read at idx = DN & mask. One pass over the elements with the operation
+// sequence of merge_elements' general loop (no dark maps, no per-DN std table, float64 std frames, the float64 flat field).
+template <bool STD>
+static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* frames, uint32_t mask, const double* inv_t) {
+    const int N = g->n_frames, C = g->channels;
+    const bool flat = g->flat_f64 != nullptr;
+    const int64_t wc = g->width * C, E = g->rows * wc;
+    const int64_t in_off = (g->row0 - g->buf_row0) * wc;
+    const bool f32out = g->out_kind == HM_OUT_F32;
+    const auto put = [f32out](double* base, int64_t e, double x) {
+        if (f32out) reinterpret_cast<float*>(base)[e] = static_cast<float>(x); else base[e] = x;
+    };
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < E; ++e) {
+        const int64_t ei = in_off + e;
+        const int c = static_cast<int>(e % C);
+        double S = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const double w = g->w_lut[frames[i][ei] & mask];
+            S = i == 0 ? w : S + w;                                              // exposure_series.py:340
+        }
+        if (g->out_sum_w) g->out_sum_w[e] = S;
+        if (!g->out_val) continue;
+        const double invS = 1.0 / S, invS2 = 1.0 / (S * S);                     // :343
+        double acc = 0.0, var = 0.0;
+        for (int i = 0; i < N; ++i) {
+            const uint32_t idx = frames[i][ei] & mask;
+            const double w = g->w_lut[idx];
+            const double gg = g->icrf[idx * C + c];
+            const double it = inv_t[i];
+            const double wg = w * gg;
+            acc = i == 0 ? wg * it : std::fma(wg, it, acc);                     // :388 numerator
+            if constexpr (STD) {
+                const double dw = g->dw_lut[idx];
+                const double dg = g->icrf_diff[idx * C + c] * g->stds[i][ei];                        // measurand.py:512
+                const double A = (dw * gg + w * dg) * invS - ((dw * w) * gg) * invS2;                // :389
+                const double term = (A * dg) * it;
+                var = i == 0 ? term * term : std::fma(term, term, var);
+            }
+        }
+        double val = acc / S;
+        double sd = STD ? std::sqrt(var) : 0.0;                                 // :394
+        if (flat) flat_field_math(g->flat_f64[e], STD ? g->flat_std[e] : 0.0, g->ff_mean[c], g->ff_std_mean[c], STD, val, sd);
+        put(g->out_val, e, val);
+        if constexpr (STD) put(g->out_std, e, sd);
+    }
+}
+
 extern "C" {
+
+int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16); }
+
+int hm_merge_u16_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
+    const hm_rules::U16Extra x{frames_u16, bit_depth};
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g, hm_rules::ENTRY_U16, &x, call);
+    if (rc == HM_OK && !call.empty)
+        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d%s>(N=%d)", call.bit_depth, call.a.channels,
+                      call.with_std && call.a.out_val, call.f32out ? ",out=f32" : "", call.a.n_frames);
+    else buf[0] = 0;
+    return rc;
+}
+
+int hm_merge_u16(const hm_merge_args* g_in, const uint16_t* const* frames_u16, int bit_depth, void*) {
+    const hm_rules::U16Extra x{frames_u16, bit_depth};
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g_in, hm_rules::ENTRY_U16, &x, call);
+    if (rc != HM_OK || call.empty) return rc;
+    const hm_merge_args* g = &call.a;
+    std::vector<double> inv_t(static_cast<size_t>(g->n_frames));
+    for (int i = 0; i < g->n_frames; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
+    const uint32_t mask = (1u << call.bit_depth) - 1u;
+    if (call.with_std && g->out_val) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data());
+    else merge_elements_u16<false>(g, call.frames_u16, mask, inv_t.data());
+    return HM_OK;
+}
 
 static int merge_run(const hm_merge_args* g_in, MergeEntry entry, const void* extra) {
     MergeCall call;

@@ -4,7 +4,7 @@ Everything here is plumbing - argument checking, pointer tables, output allocati
 hand-written HIP kernels in csrc/. No arithmetic of the hot path happens in Python or in torch ops.
 The only host-side numbers are the 256-entry Gaussian weight tables (modules/measurand.py:615-616
 evaluated on the DN grid with NumPy, so that they are bit-identical to what the reference computes
-for 8-bit frames) and per-frame scalars (1/exposure, DN thresholds).
+for 8-bit frames; 2**bit_depth entries for uint16 frames) and per-frame scalars (1/exposure, DN thresholds).
 """
 from __future__ import annotations
 
@@ -19,6 +19,7 @@ from .settings import BITS, MAX_DN
 
 _F64 = torch.float64
 _U8 = torch.uint8
+_U16 = torch.uint16
 
 
 # ---------------------------------------------------------------------------------------------
@@ -68,18 +69,29 @@ def _ptr_array(tensors: Sequence[Optional[torch.Tensor]]):
 _weight_cache: Dict[str, tuple] = {}
 
 
-def weight_luts_host():
-    """w, dw on the DN grid v = k/255: modules/measurand.py:615-616 with NumPy (`np.e ** x`)."""
-    v = np.arange(BITS, dtype=np.uint8).astype(np.float64) / MAX_DN       # modules/image_set.py:223
+def _check_bit_depth(bit_depth) -> int:
+    """The bit depth of uint16 DN frames (hm_merge_u16, hm_linearize_u16): an integer in 9..16."""
+    if isinstance(bit_depth, bool) or not isinstance(bit_depth, (int, np.integer)) or not 9 <= int(bit_depth) <= 16:
+        raise ValueError(f"bit_depth must be an integer in 9..16 for uint16 frames, got {bit_depth!r}")
+    return int(bit_depth)
+
+
+def weight_luts_host(bit_depth: int = 8):
+    """w, dw on the DN grid v = k / (2**bit_depth - 1) (8 bits: k/255): modules/measurand.py:615-616 with NumPy (`np.e ** x`)."""
+    if bit_depth == 8:
+        v = np.arange(BITS, dtype=np.uint8).astype(np.float64) / MAX_DN   # modules/image_set.py:223
+    else:
+        bit_depth = _check_bit_depth(bit_depth)
+        v = np.arange(2 ** bit_depth, dtype=np.uint32).astype(np.float64) / (2 ** bit_depth - 1)
     w = np.e ** (-30 * (v - 0.5) ** 2)
     dw = -2 * 30 * (v - 0.5) * w
     return w, dw
 
 
-def weight_luts(device) -> tuple:
-    key = str(torch.device(device))
+def weight_luts(device, bit_depth: int = 8) -> tuple:
+    key = str(torch.device(device)) if bit_depth == 8 else f"{torch.device(device)}/{int(bit_depth)}"
     if key not in _weight_cache:
-        w, dw = weight_luts_host()
+        w, dw = weight_luts_host(bit_depth)
         _weight_cache[key] = (torch.as_tensor(w, device=device), torch.as_tensor(dw, device=device))
     return _weight_cache[key]
 
@@ -132,9 +144,15 @@ def gaussian_weight(val: torch.Tensor):
     return w, dw
 
 
-def linearize(val: torch.Tensor, std: Optional[torch.Tensor], icrf, icrf_diff=None, return_index: bool = False):
-    """modules/measurand.py:471-541. `icrf` is (256, C) or 1-D (256,). Returns (val, std|None[, idx])."""
+def linearize(val: torch.Tensor, std: Optional[torch.Tensor], icrf, icrf_diff=None, return_index: bool = False, bit_depth: Optional[int] = None):
+    """modules/measurand.py:471-541. `icrf` is (256, C) or 1-D (256,). Returns (val, std|None[, idx]).
+    torch.uint16 DNs need `bit_depth` in 9..16 (hm_linearize_u16): tables of 2**bit_depth rows, idx = DN & (2**bit_depth - 1) as uint16."""
     _require_cuda(val, "val")
+    if val.dtype == _U16:
+        bit_depth = _check_bit_depth(bit_depth)
+    elif bit_depth is not None:
+        raise ValueError(f"bit_depth is for torch.uint16 DNs, got {val.dtype} values")
+    n_rows = BITS if bit_depth is None else 2 ** bit_depth
     dev = val.device
     val = val.contiguous()
     icrf_t = _dev_f64(icrf, dev)
@@ -146,8 +164,10 @@ def linearize(val: torch.Tensor, std: Optional[torch.Tensor], icrf, icrf_diff=No
         if icrf_t.shape[-1] != C_:
             raise ValueError(f"ICRF has {icrf_t.shape[-1]} channels, value has {C_}")
         lut_stride = C_
-    if icrf_t.shape[0] != BITS:
-        raise ValueError(f"ICRF must have {BITS} rows, got {icrf_t.shape[0]}")
+    if icrf_t.shape[0] != n_rows:
+        raise ValueError(f"ICRF must have {n_rows} rows, got {icrf_t.shape[0]}")
+    if bit_depth is not None and diff_t is not None and diff_t.shape != icrf_t.shape:
+        raise ValueError(f"ICRF_diff must have the ICRF's shape {tuple(icrf_t.shape)}, got {tuple(diff_t.shape)}")
     use_std = std is not None and diff_t is not None                      # measurand.py:498-500
     if use_std:
         _require_cuda(std, "std")
@@ -163,6 +183,12 @@ def linearize(val: torch.Tensor, std: Optional[torch.Tensor], icrf, icrf_diff=No
                                          out_val.data_ptr(), nat.ptr(out_std), val.numel(), C_, lut_stride, _stream(dev))
             if return_index:
                 idx = val.clone()                                          # measurand.py:505
+        elif val.dtype == _U16:
+            if return_index:
+                idx = torch.empty(val.shape, dtype=_U16, device=dev)
+            rc = nat.lib.hm_linearize_u16(val.data_ptr(), nat.ptr(std) if use_std else None, icrf_t.data_ptr(), nat.ptr(diff_t),
+                                          out_val.data_ptr(), nat.ptr(out_std), nat.ptr(idx), val.numel(), C_, lut_stride, bit_depth,
+                                          _stream(dev))
         elif val.dtype == _F64:
             if return_index:
                 idx = torch.empty(val.shape, dtype=_U8, device=dev)
@@ -260,7 +286,8 @@ class MergePlan:
     `launch()` enqueues the fused kernel on the current stream of the plan's device; it can be called
     repeatedly (bench, hipGraph capture)."""
 
-    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None, stds_f32=None):
+    def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None, stds_f32=None,
+                 frames_u16=None, bit_depth: Optional[int] = None):
         self.args = args
         self._keep = keep
         self.device = torch.device(device)
@@ -270,7 +297,10 @@ class MergePlan:
         self.std_table = std_table                         # (256, C) float64 per-DN std table: the plan goes through hm_merge_std_table
         # the C entry point the plan goes through and the entry's own argument after the struct: the ctypes array of N pointers to float32
         # std frames (hm_merge_std_f32), the table, or none
-        if stds_f32 is not None:
+        self.bit_depth = bit_depth                         # uint16 DN frames: the plan goes through hm_merge_u16 (ctypes array of N frame pointers, depth)
+        if frames_u16 is not None:
+            self._entry, self._extra = "hm_merge_u16", (frames_u16, int(bit_depth))
+        elif stds_f32 is not None:
             self._entry, self._extra = "hm_merge_std_f32", (stds_f32,)
         elif std_table is not None:
             self._entry, self._extra = "hm_merge_std_table", (std_table.data_ptr(),)
@@ -315,7 +345,8 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
                flat: Optional[torch.Tensor] = None, flat_std: Optional[torch.Tensor] = None,
                ff_mean=None, ff_std_mean=None, want_sum_w: bool = False, want_val: bool = True,
                height: Optional[int] = None, row0: int = 0, rows: Optional[int] = None, buf_row0: int = 0,
-               variant: int = 0, hot_queue: bool = True, out_dtype: torch.dtype = torch.float64, std_table=None) -> MergePlan:
+               variant: int = 0, hot_queue: bool = True, out_dtype: torch.dtype = torch.float64, std_table=None,
+               bit_depth: Optional[int] = None) -> MergePlan:
     """Build the launch descriptor for one fused merge (modules/exposure_series.py:317-419).
 
     frames : N tensors (buf_rows, W, C), all uint8 DNs or all float64 values, ascending exposure.
@@ -341,6 +372,12 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
              (hm_merge_std_table), so no std frame exists in device memory. The outputs equal those of `stds=[linearize(f, None,
              std_table)[0] for f in frames]`, bit for bit. Needs icrf_diff; excludes `stds` (ValueError). At most HM_MAX_FRAMES frames
              and no forced chunking: NotImplementedError.
+    bit_depth : 9..16, required for (and only for) torch.uint16 DN frames of 9- to 16-bit cameras (hm_merge_u16): ValueError otherwise. A DN
+             has the value DN / (2**bit_depth - 1) and the table index DN & (2**bit_depth - 1); `icrf` / `icrf_diff` must have
+             2**bit_depth rows, the weight tables are weight_luts(device, bit_depth). float32 stds are widened to float64. Not built for
+             such frames - NotImplementedError: `std_table`, `darks`, a uint8 `flat`, more than HM_MAX_FRAMES frames (or forced chunking).
+             variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
+             memory / split between the two.
     """
     if out_dtype not in (_F64, torch.float32):
         raise TypeError(f"out_dtype must be torch.float64 or torch.float32, got {out_dtype}")
@@ -351,8 +388,22 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         _require_cuda(f, f"frames[{i}]")
     dev = frames[0].device
     dt = frames[0].dtype
-    if dt not in (_U8, _F64):
-        raise TypeError(f"frames must be uint8 or float64, got {dt}")
+    u16 = dt == _U16
+    if u16:
+        bit_depth = _check_bit_depth(bit_depth)
+        if std_table is not None:
+            raise NotImplementedError("uint16 frames: the per-DN std table (std_table) is built for 8-bit frames only")
+        if darks is not None and any(d is not None for d in darks):
+            raise NotImplementedError("uint16 frames: dark maps (the hot-pixel pass) are built for 8-bit frames only")
+        if flat is not None and flat.dtype == _U8:
+            raise NotImplementedError("uint16 frames: a uint8 flat field is built for 8-bit frames only (pass a float64 flat)")
+        if n > nat.HM_MAX_FRAMES or variant <= -2:
+            raise NotImplementedError(f"uint16 frames: at most {nat.HM_MAX_FRAMES} frames in one launch (no chunked path)")
+    elif bit_depth is not None:
+        raise ValueError(f"bit_depth is for torch.uint16 frames, got {dt} frames")
+    if dt not in (_U8, _F64, _U16):
+        raise TypeError(f"frames must be uint8, float64 or (with bit_depth) uint16, got {dt}")
+    n_rows = 2 ** bit_depth if u16 else BITS
     shape = tuple(frames[0].shape)
     if len(shape) != 3:
         raise ValueError(f"frames must be (H, W, C), got shape {shape}")
@@ -388,18 +439,18 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
             if tuple(s.shape) != shape:
                 raise ValueError("Value and std shapes must match.")
         # float32 std frames as they are (hm_merge_std_f32) where one launch takes the stack; everything else widened, as ever
-        sd_f32 = all(s.dtype == torch.float32 for s in stds) and n <= nat.HM_MAX_FRAMES and variant > -2
+        sd_f32 = all(s.dtype == torch.float32 for s in stds) and n <= nat.HM_MAX_FRAMES and variant > -2 and not u16
         sd = [s.contiguous() if sd_f32 else s.to(_F64).contiguous() for s in stds]
         keep.extend(sd)
     icrf_t = _dev_f64(icrf, dev)
-    if tuple(icrf_t.shape) != (BITS, Cc):
-        raise ValueError(f"ICRF must have shape ({BITS}, {Cc}), got {tuple(icrf_t.shape)}")
+    if tuple(icrf_t.shape) != (n_rows, Cc):
+        raise ValueError(f"ICRF must have shape ({n_rows}, {Cc}), got {tuple(icrf_t.shape)}")
     diff_t = None
     if icrf_diff is not None:
         diff_t = _dev_f64(icrf_diff, dev)
-        if tuple(diff_t.shape) != (BITS, Cc):
-            raise ValueError(f"ICRF_diff must have shape ({BITS}, {Cc})")
-    w_lut, dw_lut = weight_luts(dev)
+        if tuple(diff_t.shape) != (n_rows, Cc):
+            raise ValueError(f"ICRF_diff must have shape ({n_rows}, {Cc})")
+    w_lut, dw_lut = weight_luts(dev, bit_depth) if u16 else weight_luts(dev)
     keep += [icrf_t, diff_t, w_lut, dw_lut]
     table_t = None
     if std_table is not None:
@@ -413,7 +464,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     a.out_kind = nat.HM_OUT_F32 if out_dtype == torch.float32 else nat.HM_OUT_F64
     a.height, a.width, a.row0, a.rows, a.buf_row0, a.buf_rows = height, W, int(row0), rows, int(buf_row0), buf_rows
     fptrs, sptrs = _ptr_array(fr), None
-    if dt == _U8:
+    if u16:
+        pass                                               # hm_merge_u16 takes the frame pointers beside the struct
+    elif dt == _U8:
         a.frames_u8 = C.cast(fptrs, C.POINTER(C.c_void_p))
     else:
         a.frames_f64 = C.cast(fptrs, C.POINTER(C.c_void_p))
@@ -496,8 +549,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         ws = torch.empty(fw, dtype=_U8, device=dev)
         a.frames_workspace, a.frames_workspace_bytes = ws.data_ptr(), fw
         keep.append(ws)
-    plan = MergePlan(a, keep, dev, outputs, std_table=table_t, stds_f32=sptrs if sd_f32 else None)
-    if out_dtype == torch.float32 or table_t is not None or sd_f32:
+    plan = MergePlan(a, keep, dev, outputs, std_table=table_t, stds_f32=sptrs if sd_f32 else None,
+                     frames_u16=fptrs if u16 else None, bit_depth=bit_depth)
+    if out_dtype == torch.float32 or table_t is not None or sd_f32 or u16:
         plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs / table calls raises here, not at the first launch
     return plan
 

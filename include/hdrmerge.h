@@ -43,7 +43,9 @@ extern "C" {
  * 2: frames_workspace / frames_workspace_bytes (296 bytes), hm_merge_frames_workspace_bytes(), stacks of more than HM_MAX_FRAMES
  *    frames; hm_merge still accepts the 264- and 280-byte layouts (the missing tail reads as "no workspace").
  *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only), and likewise by
- *    hm_merge_std_table* and hm_merge_std_f32* (new entry points beside hm_merge; hm_merge_args keeps its 296 bytes).     */
+ *    hm_merge_std_table* and hm_merge_std_f32* (new entry points beside hm_merge; hm_merge_args keeps its 296 bytes), and by
+ *    hm_merge_u16*, hm_linearize_u16 and hm_gaussian_weight_lut_bits_host (uint16 DN frames of 9- to 16-bit cameras; HM_BITS below is
+ *    the table size of the 8-bit entry points only).                                                                        */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -258,6 +260,45 @@ int64_t hm_merge_std_table_algorithmic_bytes(const hm_merge_args* args /*[host]*
 int hm_merge_std_f32(const hm_merge_args* args /*[host]*/, const float* const* stds_f32 /*[host] N device pointers*/, void* stream);
 int hm_merge_std_f32_describe(const hm_merge_args* args, const float* const* stds_f32, char* buf, int buf_len);
 int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
+
+/* hm_merge for 9- to 16-bit cameras: N frames of uint16 DNs with an explicit bit depth. With M = 2^bit_depth - 1 a frame element DN has
+ * the value DN / M; the kernels never form it: everything per-DN comes from the caller's tables of 2^bit_depth rows - icrf, icrf_diff:
+ * (2^bit_depth, C); w_lut, dw_lut: (2^bit_depth,) (hm_gaussian_weight_lut_bits_host) - at the index idx = DN & M, the package's wrap
+ * convention. The mask is applied before EVERY table access, so stray high bits never read outside a table. The arithmetic per output
+ * element is hm_merge's operation sequence: a result does not depend on which kernel or tiling produced it, and a stack whose DNs and
+ * tables embed an 8-bit stack (DN16 = DN8 << (bit_depth - 8)) gives hm_merge's bits.
+ * frames_u16: [host] array of N device pointers (host memory on the host build), 2-byte aligned, addressing image row buf_row0.
+ * args->frames_u8 and args->frames_f64 must be NULL. Statuses, an earlier rule wins:
+ *   1. HM_EINVAL: NULL args or a bad struct_size; frames_u8 / frames_f64 set; NULL frames_u16 or a NULL entry; bit_depth outside 9..16;
+ *      no w_lut; with stds: no icrf_diff or no dw_lut.
+ *   2. HM_EALIGN: a frame pointer that is not 2-byte aligned.
+ *   3. Every remaining rule of hm_merge; then HM_EINVAL for a variant above 3.
+ *   4. HM_EUNSUPPORTED, before any launch: darks_u8, flat_u8, more than HM_MAX_FRAMES frames or variant <= -2, variant 1 with tables
+ *      that do not fit in LDS, variant 3 where not even the per-DN tables fit.
+ * Supported: value-only merges and float64 std frames (args->stds), out_sum_w, the sum-of-weights-only call, both out_kind values,
+ * flat_f64 with flat_std, row tiles, C = 1..4, the 264- and 280-byte layouts.
+ * variant: 0 the library's choice; -1 the one-element-per-thread kernel; 1 the streaming kernel with its tables in LDS; 2 the streaming
+ * kernel with its tables read from global memory; 3 the streaming kernel with the largest PART of its tables that fits in LDS.
+ * Tables in LDS - the fit rule, n = 2^bit_depth: value-only calls hold w[n] and (w g)[n C], 8 (1 + C) n bytes; std calls hold {w, dw}[n]
+ * and {g, d}[n C], 16 (1 + C) n bytes; the tables live in LDS when that is at most 160 KiB (a gfx950 workgroup's maximum). Where it is
+ * more, the largest of these parts that fits does ("tab=mixed-..."): std calls {w, dw}[n] and g[n C], 8 (2 + C) n bytes, with icrf_diff
+ * gathered from global memory; else the per-DN tables alone, w[n] (8 n bytes) or {w, dw}[n] (16 n bytes), with the per-(DN, channel)
+ * tables gathered from global memory; else nothing (every gather from global memory: value-only from 15 bits, with std from 14).
+ * The streaming kernels' pair rule (two elements per lane, one 4-byte load per frame): frame pointers 4-byte aligned at the first input
+ * element, float64 outputs / flat field / std frames 16-byte aligned there (float32 outputs: 8-byte). Calls that break it run in the
+ * one-element-per-thread kernel with the same bits.
+ * hm_merge_u16_describe: as hm_merge_describe; the kernel names say where the tables live ("merge_u16_stream<tab=lds,...>", "tab=global",
+ * "tab=mixed-wdwg", "tab=mixed-wdw", "tab=mixed-w").
+ * hm_merge_u16_algorithmic_bytes: 2 N bytes per element for the frames; the rest as hm_merge. */
+int hm_merge_u16(const hm_merge_args* args /*[host]*/, const uint16_t* const* frames_u16 /*[host] N device pointers*/, int bit_depth, void* stream);
+int hm_merge_u16_describe(const hm_merge_args* args, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len);
+int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
+/* hm_linearize_u8 for uint16 DNs: idx = dn & (2^bit_depth - 1), tables of 2^bit_depth rows gathered from global memory; out_idx
+ * (nullable, 2-byte aligned) receives the masked DN. bit_depth outside 9..16: HM_EINVAL; dn / out_idx not 2-byte aligned: HM_EALIGN. */
+int hm_linearize_u16(const uint16_t* dn, const double* std, const double* icrf, const double* icrf_diff,
+                     double* out_val, double* out_std, uint16_t* out_idx, int64_t n, int C, int lut_stride, int bit_depth, void* stream);
+/* [host] hm_gaussian_weight_lut_host's formula on the grid v = k / (2^bit_depth - 1), 2^bit_depth entries each (bit_depth 8..16). */
+int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut /*[host]*/, double* dw_lut /*[host]*/);
 
 /* ------------------------------------------------------------------------------------------
  * Row 8 standalone - AbstractMeasurand.filter_larger_than_by_map (modules/measurand.py:543-557):

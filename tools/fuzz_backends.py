@@ -801,7 +801,99 @@ def case_pairs_hist(rng):
     return desc
 
 
-CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
+def icrf_tables_bits(rng, c, b):
+    n = 2 ** b
+    g = np.linspace(0, 1, n)[:, None] ** rng.uniform(0.6, 2.6, size=c)[None, :]
+    if rng.random() < 0.2:
+        g = g - 0.1
+    d = np.stack([np.gradient(g[:, k], 2 / (n - 1)) for k in range(c)], axis=1)
+    return np.ascontiguousarray(g), np.ascontiguousarray(d)
+
+
+def dn16(rng, shape, b):
+    """uniform DNs of depth b; below 16 bits about 1 % of them with bits above the depth set (they must behave as their masked value)"""
+    x = rng.integers(0, 2 ** b, shape).astype(np.uint16)
+    if b < 16:
+        x[rng.random(shape) < 0.01] |= np.uint16((0xFFFF << b) & 0xFFFF)
+    return x
+
+
+def case_merge_u16(rng):
+    """the merge on uint16 DN frames with a bit depth (engine.plan_merge(bit_depth=...), hm_merge_u16): HIP - the default dispatch or a forced
+    table placement / the generic kernel, whole images or row tiles - against the host build's whole-image result, bit for bit (the rule of
+    the uint8 merge: table gathers and one shared operation sequence)"""
+    c = int(rng.choice([1, 2, 3, 3, 3, 4]))
+    n = int(rng.choice([1, 2, 3, 5, 7, 7, 8, 9, 15, 16, 17, 20, 32]))
+    b = int(rng.choice([9, 10, 10, 11, 12, 12, 13, 14, 15, 16]))
+    h, w = int(rng.integers(1, 48 * args.scale)), int(rng.integers(1, 130 * args.scale))
+    if rng.random() < 0.3:
+        h, w = int(rng.integers(8, 40 * args.scale)), 128 * int(rng.integers(1, 4 * args.scale))
+    with_std, use_flat, sum_w, f32 = rng.random() < 0.5, rng.random() < 0.4, rng.random() < 0.3, rng.random() < 0.25
+    variant = int(rng.choice([0, 0, 0, -1, 1, 2, 3]))
+    desc = f"merge_u16 n={n} h={h} w={w} c={c} bits={b} std={with_std} flat={use_flat} sum_w={sum_w} f32={f32} variant={variant}"
+    frames = [dn16(rng, (h, w, c), b) for _ in range(n)]
+    stds = [np.abs(rng.normal(size=(h, w, c))) * 0.01 for _ in range(n)] if with_std else None
+    t = 1e-3 * rng.uniform(1.2, 2.2) ** np.arange(n)
+    g, d = icrf_tables_bits(rng, c, b)
+    kw = dict(bit_depth=b, want_sum_w=bool(sum_w))
+    if f32:
+        kw["out_dtype"] = torch.float32
+    if use_flat:
+        kw.update(flat=0.5 + 0.5 * rng.random((h, w, c)), ff_mean=list(rng.uniform(0.6, 0.9, size=c)))
+        if with_std:
+            kw.update(flat_std=0.002 * (1 + rng.random((h, w, c))), ff_std_mean=list(rng.uniform(0.001, 0.003, size=c)))
+    tile = None
+    if rng.random() < 0.33 and h >= 2:
+        r0 = int(rng.integers(0, h - 1)); r1 = int(rng.integers(r0 + 1, h + 1))
+        tile = (r0, r1, int(rng.integers(0, r0 + 1)), int(rng.integers(r1, h + 1)))
+    desc += f" tile={tile}"
+
+    def run(eng, conv, tl, v):
+        k2 = dict(kw)
+        rows = slice(None) if tl is None else slice(tl[2], tl[3])
+        out_rows = slice(None) if tl is None else slice(tl[0], tl[1])
+        for name in ("flat", "flat_std"):
+            if name in k2:
+                k2[name] = conv(k2[name][out_rows])
+        if tl is not None:
+            k2.update(height=h, row0=tl[0], rows=tl[1] - tl[0], buf_row0=tl[2])
+        return eng.merge([conv(f[rows]) for f in frames], list(t), g, d if with_std else None,
+                         [conv(s[rows]) for s in stds] if with_std else None, variant=v, **k2)
+
+    try:
+        a = run(engine, D, tile, variant)
+    except NotImplementedError:                                        # a forced placement whose tables do not fit: the library's choice instead
+        desc += " (variant refused: 0)"
+        a = run(engine, D, tile, 0)
+    b_ = run(heng, Hh, None, 0)
+    if tile is not None:
+        b_ = {key: v[tile[0]:tile[1]] for key, v in b_.items()}
+    for key in b_:
+        compare(f"{key}", a[key], b_[key], None)
+    return desc
+
+
+def case_linearize_u16(rng):
+    c = int(rng.choice([1, 2, 3, 4]))
+    b = int(rng.choice([9, 10, 12, 14, 16]))
+    shape = tuple(int(rng.integers(1, 40)) for _ in range(int(rng.integers(1, 3)))) + (c,)
+    g, d = icrf_tables_bits(rng, c, b)
+    one_d = rng.random() < 0.4                                         # the 1-D table mode (lut_stride = 1) for any channel count
+    if one_d:
+        g, d = g[:, 0].copy(), d[:, 0].copy()
+    x = dn16(rng, shape, b)
+    xs = np.abs(rng.normal(size=shape)) * 0.01 if rng.random() < 0.6 else None
+    use_diff = rng.random() < 0.7
+    desc = f"linearize_u16 shape={shape} bits={b} 1d={one_d} std={xs is not None} diff={use_diff}"
+    ra = engine.linearize(D(x), D(xs), g, d if use_diff else None, return_index=True, bit_depth=b)
+    rb = heng.linearize(Hh(x), Hh(xs), g, d if use_diff else None, return_index=True, bit_depth=b)
+    compare("idx", ra[2], rb[2], None)
+    compare("val", ra[0], rb[0], None)
+    compare("std", ra[1], rb[1], None)
+    return desc
+
+
+CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_linearize_u16, 1),(case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
          (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()

@@ -1,4 +1,4 @@
-// merge_rules_check.cpp - the host build's three merge _describe entries (camera_linearity_amd/csrc/hm_merge_rules.h through
+// merge_rules_check.cpp - the host build's four merge _describe entries (camera_linearity_amd/csrc/hm_merge_rules.h through
 // csrc_host/hm_host.cpp) under AddressSanitizer / UBSan: the NULL, short-struct_size and n_frames = 33 cases, in which the rules must
 // answer without reading past what the caller gave them. A development step for whoever changes that header: a stand-alone program, not
 // part of the library, the package or the test suite, and it needs no GPU.
@@ -44,6 +44,23 @@ int main() {
             expect("std_f32", hm_merge_std_f32_describe(g, stds_f32.data(), buf, sizeof buf), size == 100u ? HM_EINVAL : n == 33 ? HM_EUNSUPPORTED : HM_OK);
             expect("std_table, NULL table", hm_merge_std_table_describe(g, nullptr, buf, sizeof buf), HM_EINVAL);
             expect("std_f32, NULL stds", hm_merge_std_f32_describe(g, nullptr, buf, sizeof buf), HM_EINVAL);
+            {   // hm_merge_u16: the frames travel beside the struct (frames_u8 must be NULL); the chunked path does not exist for it
+                std::vector<const uint16_t*> frames_u16(n, reinterpret_cast<const uint16_t*>(0x600000));
+                std::vector<char> block16(block);
+                auto* g16 = reinterpret_cast<hm_merge_args*>(block16.data());
+                g16->frames_u8 = nullptr;
+                if (size != 100u) g16->out_std = nullptr;        // (value-only first; the 100-byte block ends before the field)
+                const int rc16 = size == 100u ? HM_EINVAL : n == 33 ? HM_EUNSUPPORTED : HM_OK;
+                expect("u16", hm_merge_u16_describe(g16, frames_u16.data(), 12, buf, sizeof buf), rc16);
+                expect("u16, 16 bits", hm_merge_u16_describe(g16, frames_u16.data(), 16, buf, sizeof buf), rc16);
+                expect("u16, 8 bits", hm_merge_u16_describe(g16, frames_u16.data(), 8, buf, sizeof buf), HM_EINVAL);
+                expect("u16, NULL frames", hm_merge_u16_describe(g16, nullptr, 12, buf, sizeof buf), HM_EINVAL);
+                expect("u16, frames_u8 set", hm_merge_u16_describe(g, frames_u16.data(), 12, buf, sizeof buf), HM_EINVAL);
+                g16->stds = stds.data();
+                if (size != 100u) g16->out_std = a.out_std;
+                expect("u16 with stds", hm_merge_u16_describe(g16, frames_u16.data(), 10, buf, sizeof buf), rc16);
+                if (size != 100u) hm_merge_u16_algorithmic_bytes(g16);
+            }
             g->stds = stds.data();
             expect("merge", hm_merge_describe(g, buf, sizeof buf), short_rc);
             expect("merge, NULL buf", hm_merge_describe(g, nullptr, 0), HM_EINVAL);
@@ -55,6 +72,8 @@ int main() {
     expect("merge, NULL args", hm_merge_describe(nullptr, buf, sizeof buf), HM_EINVAL);
     expect("std_table, NULL args", hm_merge_std_table_describe(nullptr, nullptr, buf, sizeof buf), HM_EINVAL);
     expect("std_f32, NULL args", hm_merge_std_f32_describe(nullptr, nullptr, buf, sizeof buf), HM_EINVAL);
+    expect("u16, NULL args", hm_merge_u16_describe(nullptr, nullptr, 12, buf, sizeof buf), HM_EINVAL);
+    if (hm_merge_u16_algorithmic_bytes(nullptr)) ++failures;
     if (hm_merge_algorithmic_bytes(nullptr) || hm_merge_std_table_algorithmic_bytes(nullptr) || hm_merge_std_f32_algorithmic_bytes(nullptr)) ++failures;
     std::printf(failures ? "merge_rules_check: %d FAILED\n" : "merge_rules_check: ok\n", failures);
     return failures != 0;
