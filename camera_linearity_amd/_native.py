@@ -88,6 +88,10 @@ _SIGNATURES = {
     "hm_merge_u16": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_int, C.c_void_p]),
     "hm_merge_u16_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "hm_merge_u16_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs)]),
+    # ... with uint16 dark maps (darks: a ctypes array of N pointers, NULL entries allowed, passed as its address after the frames)
+    "hm_merge_u16_darks": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "hm_merge_u16_darks_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "hm_merge_u16_darks_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs), C.c_void_p]),
     "hm_linearize_u16": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]),

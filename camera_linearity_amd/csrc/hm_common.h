@@ -138,6 +138,11 @@ template <> struct MedianKey<uint8_t> {
     static __device__ __forceinline__ uint32_t lo(uint32_t a, uint32_t b) { return a < b ? a : b; }
     static __device__ __forceinline__ uint32_t hi(uint32_t a, uint32_t b) { return a < b ? b : a; }
 };
+template <> struct MedianKey<uint16_t> {           // (masked) uint16 DNs of the 9- to 16-bit merge, one VGPR each
+    using type = uint32_t;
+    static __device__ __forceinline__ uint32_t lo(uint32_t a, uint32_t b) { return a < b ? a : b; }
+    static __device__ __forceinline__ uint32_t hi(uint32_t a, uint32_t b) { return a < b ? b : a; }
+};
 template <> struct MedianKey<double> {
     using type = double;
     static __device__ __forceinline__ double lo(double a, double b) { return a < b ? a : b; }

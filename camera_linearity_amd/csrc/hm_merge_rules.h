@@ -1,4 +1,5 @@
-// hm_merge_rules.h - the argument rules of the fused merge's four C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32, hm_merge_u16), written
+// hm_merge_rules.h - the argument rules of the fused merge's five C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32, hm_merge_u16,
+// hm_merge_u16_darks), written
 // once for both builds of the ABI: the device build's dispatcher (hm_merge.hip) and the host build (csrc_host/hm_host.cpp) include this file
 // and hold no argument test of their own - one ABI, one answer. Plain C++17 on hdrmerge.h and the standard headers: no HIP type, no OpenMP.
 //
@@ -17,10 +18,10 @@
 
 namespace hm_rules {
 
-enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32, ENTRY_U16 };   // the C entry point called
+enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32, ENTRY_U16, ENTRY_U16_DARKS };   // the C entry point called
 
-// hm_merge_u16's own arguments (check_merge_call's `extra` for ENTRY_U16)
-struct U16Extra { const uint16_t* const* frames; int bit_depth; };
+// hm_merge_u16's own arguments (check_merge_call's `extra` for ENTRY_U16), and hm_merge_u16_darks's (ENTRY_U16_DARKS: with the N dark maps)
+struct U16Extra { const uint16_t* const* frames; int bit_depth; const uint16_t* const* darks = nullptr; };
 
 // hm_merge_u16: which of a call's tables a streaming kernel holds in LDS, the bytes that takes, and the fit rule - at most a gfx950
 // workgroup's 160 KiB (hdrmerge.h states all of it for callers). n = 2^bit_depth rows:
@@ -62,6 +63,7 @@ struct MergeCall {
     bool f64in;                        // float64 frames (else uint8, or uint16 in a hm_merge_u16 call)
     const uint16_t* const* frames_u16; // hm_merge_u16: the N frames (a.frames_u8 and a.frames_f64 are NULL), else NULL
     int bit_depth;                     // hm_merge_u16: 9..16, else 0
+    const uint16_t* const* darks_u16;  // hm_merge_u16_darks: the N dark maps (NULL entries: no filter; a.darks_u8 is NULL), else NULL
     bool with_std;                     // std_src != STD_NONE
     bool flat;                         // a flat field of either kind
     bool hot;                          // at least one frame has a dark map
@@ -86,7 +88,7 @@ inline bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
 }
 
 // extra: the entry point's own pointer - NULL for hm_merge, std_table for hm_merge_std_table, stds_f32 for hm_merge_std_f32, a U16Extra
-// for hm_merge_u16.
+// for hm_merge_u16 and hm_merge_u16_darks.
 // Returns the call's status; `call` is complete when that is HM_OK (with call.empty set there is nothing to run).
 inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const void* extra, MergeCall& call) {
     call = MergeCall{};
@@ -112,15 +114,22 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         for (int i = 0; i < N; ++i)
             if (!ptr_aligned(stds_f32[i], 4)) return HM_EALIGN;
         if (g->out_val) { call.std_src = STD_F32; g->stds = reinterpret_cast<const double* const*>(stds_f32); }
-    } else if (entry == ENTRY_U16) {
+    } else if (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) {
         const U16Extra* x = static_cast<const U16Extra*>(extra);
         if (g->frames_u8 || g->frames_f64 || !x || !x->frames) return HM_EINVAL;
         for (int i = 0; i < N; ++i)
             if (!x->frames[i]) return HM_EINVAL;
         if (x->bit_depth < 9 || x->bit_depth > 16 || !g->w_lut) return HM_EINVAL;
         if (g->stds && (!g->icrf_diff || !g->dw_lut)) return HM_EINVAL;
+        // hm_merge_u16_darks: the maps come beside the struct (uint16), never in it (uint8), and always with their thresholds
+        if (entry == ENTRY_U16_DARKS && (!x->darks || g->darks_u8 || !g->dark_min_dn)) return HM_EINVAL;
         for (int i = 0; i < N; ++i)
             if (!ptr_aligned(x->frames[i], 2)) return HM_EALIGN;
+        if (entry == ENTRY_U16_DARKS) {
+            for (int i = 0; i < N; ++i)
+                if (!ptr_aligned(x->darks[i], 2)) return HM_EALIGN;
+            call.darks_u16 = x->darks;
+        }
         call.frames_u16 = x->frames; call.bit_depth = x->bit_depth;
         if (g->stds) call.std_src = STD_F64;
     } else if (g->stds) call.std_src = STD_F64;
@@ -154,6 +163,8 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         if (!g->dark_min_dn) return HM_EINVAL;
         for (int i = 0; i < N; ++i) call.hot = call.hot || (g->darks_u8[i] != nullptr);
     }
+    if (call.darks_u16)
+        for (int i = 0; i < N; ++i) call.hot = call.hot || (call.darks_u16[i] != nullptr);
     if (call.hot) {
         const int k = g->median_k;
         if (k < 3 || k > 7 || (k % 2) == 0) return HM_EINVAL;
@@ -161,6 +172,10 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         const int64_t need_lo = g->row0 - r < 0 ? 0 : g->row0 - r;
         const int64_t need_hi = g->row0 + g->rows + r > g->height ? g->height : g->row0 + g->rows + r;
         if (g->buf_row0 > need_lo || g->buf_row0 + g->buf_rows < need_hi) return HM_ESHAPE;   // halo too small
+        // hm_merge_u16_darks: the threshold of every frame that has a map, 1 .. 2^bit_depth (2^bit_depth: no DN is hot)
+        if (call.darks_u16)
+            for (int i = 0; i < N; ++i)
+                if (call.darks_u16[i] && (g->dark_min_dn[i] < 1 || g->dark_min_dn[i] > (1 << call.bit_depth))) return HM_EINVAL;
     }
     // per-frame pointers and exposures (any N: neither build's hm_merge has a frame limit)
     for (int i = 0; i < N; ++i) {
@@ -183,11 +198,11 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
     const bool chunked = N > HM_MAX_FRAMES || g->variant <= -2;
     if (call.f32out && (chunked || g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     if (call.std_src == STD_F32 && chunked) return HM_EUNSUPPORTED;
-    if (entry == ENTRY_U16) {
+    if (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) {
         // variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
         // memory / split between the two (the largest partial placement)
         if (g->variant > 3) return HM_EINVAL;
-        // what hm_merge_u16 leaves out: dark maps and uint8 flat fields (8-bit data), the chunked path
+        // what the uint16 entries leave out: uint8 dark maps and uint8 flat fields (8-bit data), the chunked path
         if (g->darks_u8 || g->flat_u8 || chunked) return HM_EUNSUPPORTED;
         if (g->variant == 1 && !u16_tables_fit_lds(call.bit_depth, C, with_std && g->out_val)) return HM_EUNSUPPORTED;
         if (g->variant == 3 && u16_mixed_tables(call.bit_depth, C, with_std && g->out_val) == U16_TAB_GLOBAL) return HM_EUNSUPPORTED;
@@ -197,13 +212,14 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
 
 // Algorithmic bytes of a call through `entry` (hdrmerge.h: hm_merge_algorithmic_bytes): STD_TABLE calls read no std stream, STD_F32 calls
 // 4-byte ones (args->stds is NULL in both). Takes the caller's arguments as they are: a refused call has a count too.
-inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry) {
+// darks_u16 (ENTRY_U16_DARKS): the N uint16 dark maps, 2 bytes per element for every distinct (map, threshold).
+inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry, const uint16_t* const* darks_u16 = nullptr) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
     const int N = g->n_frames;
     const bool lut = entry == ENTRY_STD_TABLE, sd32 = entry == ENTRY_STD_F32;
     const bool s = lut || sd32 || g->stds != nullptr;
-    const int64_t in_b = entry == ENTRY_U16 ? 2 : g->frames_f64 ? 8 : 1;
+    const int64_t in_b = (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) ? 2 : g->frames_f64 ? 8 : 1;
     int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
@@ -216,6 +232,14 @@ inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry)
             for (int k = 0; k < i; ++k)
                 seen = seen || (g->darks_u8[k] == g->darks_u8[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
             per += seen ? 0 : 1;
+        }
+    if (entry == ENTRY_U16_DARKS && darks_u16)
+        for (int i = 0; i < N; ++i) {
+            if (!darks_u16[i]) continue;
+            bool seen = false;
+            for (int k = 0; k < i; ++k)
+                seen = seen || (darks_u16[k] == darks_u16[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
+            per += seen ? 0 : 2;
         }
     return per * E;
 }

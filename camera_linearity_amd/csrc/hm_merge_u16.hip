@@ -19,7 +19,9 @@
 // Every table access - LDS or global - is at idx = DN & (2^bit_depth - 1): stray high bits never read outside a table.
 // One operation sequence per output element in every kernel, merge_one_element's (hm_merge_dev.h): S in frame order, 1/S and 1/S**2 once,
 // the numerator and the variance terms accumulated with fma in frame order, the product w g formed once (a table entry or a register).
-#include "hm_merge_host.h"
+// hm_merge_u16_darks adds the hot-pixel pass of hm_merge_u16_hot.hip after these kernels (ENTRY_U16_DARKS): they never read a dark map; the
+// first of them zeroes the hot-pixel queue's counters in passing (MergeK::hot_reset, NULL in every hm_merge_u16 call).
+#include "hm_merge_u16.h"
 #include "hm_merge_rules.h"
 #include <mutex>
 
@@ -28,10 +30,6 @@ namespace hm {
 constexpr int kU16Chunk = 8;          // frames whose loads a wave issues together (merge_u8_loop's kLoopChunk)
 constexpr int kU16LdsBlock = 1024;    // threads of the tab=lds workgroup
 constexpr int kU16GlobalBlock = 256;
-
-__device__ __forceinline__ uint32_t ld_dn16(const MergeK& a, int i, int64_t ei, uint32_t mask) {
-    return static_cast<uint32_t>(static_cast<const uint16_t*>(a.frame[i])[ei]) & mask;
-}
 
 // merge_one_element<false, STD, HOT_NONE, OUT> for uint16 frames, tables in global memory
 template <bool STD, int OUT>
@@ -73,6 +71,7 @@ __device__ __forceinline__ void merge_u16_element(const MergeK& a, uint32_t mask
 
 template <bool STD, int OUT>
 __global__ __launch_bounds__(256) void merge_u16_generic(const MergeK a, const uint32_t mask) {
+    reset_hot_counters(a);
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; q < a.n_elems; q += stride)
         merge_u16_element<STD, OUT>(a, mask, a.elem0 + q);
@@ -95,6 +94,7 @@ __global__ __launch_bounds__(PLACE != hm_rules::U16_TAB_GLOBAL ? kU16LdsBlock : 
     const int N = a.n_frames;
     const uint32_t C = static_cast<uint32_t>(a.C);
     const uint32_t n_dn = mask + 1u;                                      // rows of every table
+    reset_hot_counters(a);
 
     if constexpr (TABLDS) {
         if constexpr (!STD) {
@@ -348,13 +348,14 @@ template <int OUT>
 static int merge_u16_launch(const hm_rules::MergeCall& call, void* stream) {
     const hm_merge_args* g = &call.a;
     const int N = g->n_frames, C = g->channels, bits = call.bit_depth;
-    const bool with_std = call.with_std && g->out_val, flat = call.flat;
+    const bool with_std = call.with_std && g->out_val, flat = call.flat, hot = call.hot;
     MergeK k{};
     for (int i = 0; i < N; ++i) {
         k.frame[i] = call.frames_u16[i];
         if (g->stds) k.sd[i] = g->stds[i];
         k.inv_t[i] = 1.0 / g->exposures[i];
-        k.dark_min[i] = 1 << 16;
+        k.dark[i] = hot ? reinterpret_cast<const uint8_t*>(call.darks_u16[i]) : nullptr;       // read through dark16()
+        k.dark_min[i] = hot && call.darks_u16[i] ? g->dark_min_dn[i] : 1 << 16;
     }
     k.icrf = g->icrf; k.icrf_diff = g->icrf_diff; k.w_lut = g->w_lut; k.dw_lut = g->dw_lut;
     k.flat_f64 = g->flat_f64; k.flat_std = g->flat_std;
@@ -364,9 +365,18 @@ static int merge_u16_launch(const hm_rules::MergeCall& call, void* stream) {
     k.n_elems = E; k.elem0 = 0;
     k.in_off = (g->row0 - g->buf_row0) * g->width * C;
     k.H = g->height; k.W = g->width; k.row0 = g->row0; k.buf_row0 = g->buf_row0; k.buf_rows = g->buf_rows;
-    k.n_frames = N; k.C = C; k.median_k = 3; k.has_flat = flat ? 1 : 0;
+    k.n_frames = N; k.C = C; k.median_k = hot ? g->median_k : 3; k.has_flat = flat ? 1 : 0;
     k.variant = g->variant; k.inv_t_inrange = 1;
     hipStream_t st = as_stream(stream);
+    // the hot-pixel pass's queue: the caller's workspace where it is usable (hm_merge's rule), else the pass tests every element itself
+    const bool hot_queue = hot && g->hot_workspace && g->hot_workspace_bytes >= hm_merge_hot_workspace_min_bytes(E) &&
+                           aligned(g->hot_workspace, 16) && E < (int64_t{1} << 32);
+    k.hot_reset = hot_queue ? static_cast<uint32_t*>(g->hot_workspace) : nullptr;
+    const auto hot_pass = [&]() {
+        if (!hot) return static_cast<int>(HM_OK);
+        return launch_u16_hot(k, bits, with_std, OUT == OUT_F32, hot_queue ? static_cast<uint32_t*>(g->hot_workspace) : nullptr,
+                              hot_queue ? g->hot_workspace_bytes : 0, st);
+    };
 
     // the pair rule (hdrmerge.h): 4-byte frame words, 16-byte float64 pairs (8-byte float32 ones)
     bool fast = g->out_val && E < (int64_t{1} << 32) && g->variant >= 0;
@@ -377,7 +387,10 @@ static int merge_u16_launch(const hm_rules::MergeCall& call, void* stream) {
     constexpr int pair_bytes = OUT == OUT_F32 ? 8 : 16;
     fast = fast && aligned(k.out_val, pair_bytes) && (!k.out_std || aligned(k.out_std, pair_bytes)) && (!k.out_sum_w || aligned(k.out_sum_w, 16));
     if (fast && flat) fast = aligned(k.flat_f64, 16) && (!with_std || aligned(k.flat_std, 16));
-    if (!fast) return launch_u16_generic<OUT>(k, bits, with_std, st);
+    if (!fast) {
+        const int rc = launch_u16_generic<OUT>(k, bits, with_std, st);
+        return rc != HM_OK ? rc : hot_pass();
+    }
 
     // (variants 1 and 3 that do not fit: refused by the rules)
     const int place = g->variant == 1 ? hm_rules::U16_TAB_ALL : g->variant == 2 ? hm_rules::U16_TAB_GLOBAL
@@ -392,15 +405,17 @@ static int merge_u16_launch(const hm_rules::MergeCall& call, void* stream) {
     if (body < E) {                                        // tail: less than one group
         MergeK kt = k;
         kt.elem0 = body; kt.n_elems = E - body;
-        return launch_u16_generic<OUT>(kt, bits, with_std, st);
+        const int rc = launch_u16_generic<OUT>(kt, bits, with_std, st);
+        if (rc != HM_OK) return rc;
     }
-    return HM_OK;
+    return hot_pass();                                     // stream-ordered after the streaming pass: it overwrites the affected elements
 }
 
-static int merge_u16_entry(const hm_merge_args* g_in, const uint16_t* const* frames_u16, int bit_depth, void* stream) {
-    const hm_rules::U16Extra x{frames_u16, bit_depth};
+static int merge_u16_entry(const hm_merge_args* g_in, hm_rules::MergeEntry entry, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16,
+                           int bit_depth, void* stream) {
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
     hm_rules::MergeCall call;
-    const int rc = hm_rules::check_merge_call(g_in, hm_rules::ENTRY_U16, &x, call);
+    const int rc = hm_rules::check_merge_call(g_in, entry, &x, call);
     if (rc != HM_OK || call.empty) return rc;
     if (g_describe) g_describe->f32 = call.f32out;
     return call.f32out ? merge_u16_launch<OUT_F32>(call, stream) : merge_u16_launch<OUT_F64>(call, stream);
@@ -411,7 +426,7 @@ static int merge_u16_entry(const hm_merge_args* g_in, const uint16_t* const* fra
 extern "C" int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16); }
 
 extern "C" int hm_merge_u16(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, void* stream) {
-    return hm::merge_u16_entry(g, frames_u16, bit_depth, stream);
+    return hm::merge_u16_entry(g, hm_rules::ENTRY_U16, frames_u16, nullptr, bit_depth, stream);
 }
 
 // the dispatch above with launching switched off (hm_merge_describe's mechanism). Returns for NULL args before anything else is read - or written.
@@ -419,7 +434,27 @@ extern "C" int hm_merge_u16_describe(const hm_merge_args* g, const uint16_t* con
     if (!buf || buf_len < 1 || !g) return HM_EINVAL;
     hm::DescribeCtx ctx;
     hm::g_describe = &ctx;
-    const int rc = hm::merge_u16_entry(g, frames_u16, bit_depth, nullptr);
+    const int rc = hm::merge_u16_entry(g, hm_rules::ENTRY_U16, frames_u16, nullptr, bit_depth, nullptr);
+    hm::g_describe = nullptr;
+    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
+    return rc;
+}
+
+// hm_merge_u16 with uint16 dark maps: the same launches, then the hot-pixel pass of hm_merge_u16_hot.hip where a frame has a map
+extern "C" int64_t hm_merge_u16_darks_algorithmic_bytes(const hm_merge_args* g, const uint16_t* const* darks_u16) {
+    return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16_DARKS, darks_u16);
+}
+
+extern "C" int hm_merge_u16_darks(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth, void* stream) {
+    return hm::merge_u16_entry(g, hm_rules::ENTRY_U16_DARKS, frames_u16, darks_u16, bit_depth, stream);
+}
+
+extern "C" int hm_merge_u16_darks_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
+                                           char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
+    hm::DescribeCtx ctx;
+    hm::g_describe = &ctx;
+    const int rc = hm::merge_u16_entry(g, hm_rules::ENTRY_U16_DARKS, frames_u16, darks_u16, bit_depth, nullptr);
     hm::g_describe = nullptr;
     snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
     return rc;

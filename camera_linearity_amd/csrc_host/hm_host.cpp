@@ -520,9 +520,14 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
 }
 
 // hm_merge_u16: uint16 DN frames, tables of 2^bit_depth rows read at idx = DN & mask. One pass over the elements with the operation
-// sequence of merge_elements' general loop (no dark maps, no per-DN std table, float64 std frames, the float64 flat field).
-template <bool STD>
-static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* frames, uint32_t mask, const double* inv_t) {
+// sequence of merge_elements' general loop (no per-DN std table, float64 std frames, the float64 flat field).
+// HOT (hm_merge_u16_darks, merge_u16_darks_host): darks[i] is frame i's uint16 dark map or NULL; where (dark & mask) >= dark_min_dn[i] the
+// frame's masked DN is the k x k median of the masked DNs around it and its std the k x k median of the std neighbourhood, filtered inline
+// into the element's idx_of[] / sd_of[] - then the same operations in the same order, so the bits of hm_merge_u16 on pre-filtered frames.
+// Without HOT (hm_merge_u16) nothing is staged: idx_at / sd_at read the frames as that path always did.
+template <bool STD, bool HOT = false>
+static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* frames, uint32_t mask, const double* inv_t,
+                               const uint16_t* const* darks = nullptr) {
     const int N = g->n_frames, C = g->channels;
     const bool flat = g->flat_f64 != nullptr;
     const int64_t wc = g->width * C, E = g->rows * wc;
@@ -535,9 +540,26 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
     for (int64_t e = 0; e < E; ++e) {
         const int64_t ei = in_off + e;
         const int c = static_cast<int>(e % C);
+        [[maybe_unused]] uint32_t idx_of[HOT ? HM_MAX_FRAMES : 1];
+        [[maybe_unused]] double sd_of[HOT && STD ? HM_MAX_FRAMES : 1];
+        if constexpr (HOT) {
+            const int k = g->median_k;
+            const auto masked = [mask](uint16_t x) { return static_cast<double>(x & mask); };      // exact, order-preserving
+            for (int i = 0; i < N; ++i) {
+                idx_of[i] = frames[i][ei] & mask;
+                if constexpr (STD) sd_of[i] = g->stds[i][ei];
+                if (darks[i] && static_cast<int>(darks[i][ei] & mask) >= g->dark_min_dn[i]) {
+                    const int64_t row = g->row0 + e / wc, col = (e % wc) / C;
+                    idx_of[i] = static_cast<uint32_t>(median_mapped_at(frames[i], masked, g->height, g->width, C, g->buf_row0, row, col, c, k));
+                    if constexpr (STD) sd_of[i] = median_at(g->stds[i], g->height, g->width, C, g->buf_row0, row, col, c, k);
+                }
+            }
+        }
+        const auto idx_at = [&](int i) -> uint32_t { if constexpr (HOT) return idx_of[i]; else return frames[i][ei] & mask; };
+        [[maybe_unused]] const auto sd_at = [&](int i) -> double { if constexpr (HOT) return sd_of[i]; else return g->stds[i][ei]; };
         double S = 0.0;
         for (int i = 0; i < N; ++i) {
-            const double w = g->w_lut[frames[i][ei] & mask];
+            const double w = g->w_lut[idx_at(i)];
             S = i == 0 ? w : S + w;                                              // exposure_series.py:340
         }
         if (g->out_sum_w) g->out_sum_w[e] = S;
@@ -545,7 +567,7 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
         const double invS = 1.0 / S, invS2 = 1.0 / (S * S);                     // :343
         double acc = 0.0, var = 0.0;
         for (int i = 0; i < N; ++i) {
-            const uint32_t idx = frames[i][ei] & mask;
+            const uint32_t idx = idx_at(i);
             const double w = g->w_lut[idx];
             const double gg = g->icrf[idx * C + c];
             const double it = inv_t[i];
@@ -553,7 +575,7 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
             acc = i == 0 ? wg * it : std::fma(wg, it, acc);                     // :388 numerator
             if constexpr (STD) {
                 const double dw = g->dw_lut[idx];
-                const double dg = g->icrf_diff[idx * C + c] * g->stds[i][ei];                        // measurand.py:512
+                const double dg = g->icrf_diff[idx * C + c] * sd_at(i);                               // measurand.py:512
                 const double A = (dw * gg + w * dg) * invS - ((dw * w) * gg) * invS2;                // :389
                 const double term = (A * dg) * it;
                 var = i == 0 ? term * term : std::fma(term, term, var);
@@ -595,6 +617,43 @@ int hm_merge_u16(const hm_merge_args* g_in, const uint16_t* const* frames_u16, i
     if (call.with_std && g->out_val) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data());
     else merge_elements_u16<false>(g, call.frames_u16, mask, inv_t.data());
     return HM_OK;
+}
+
+// hm_merge_u16_darks on the host: the same rules (ENTRY_U16_DARKS), the hot-pixel filter inline in merge_elements_u16
+static int merge_u16_darks_host(const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth) {
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g_in, hm_rules::ENTRY_U16_DARKS, &x, call);
+    if (rc != HM_OK || call.empty) return rc;
+    if (!call.hot) return hm_merge_u16(g_in, frames_u16, bit_depth, nullptr);      // every map NULL: hm_merge_u16 as it is
+    const hm_merge_args* g = &call.a;
+    std::vector<double> inv_t(static_cast<size_t>(g->n_frames));
+    for (int i = 0; i < g->n_frames; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
+    const uint32_t mask = (1u << call.bit_depth) - 1u;
+    if (call.with_std && g->out_val) merge_elements_u16<true, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
+    else merge_elements_u16<false, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
+    return HM_OK;
+}
+
+int64_t hm_merge_u16_darks_algorithmic_bytes(const hm_merge_args* g, const uint16_t* const* darks_u16) {
+    return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16_DARKS, darks_u16);
+}
+
+int hm_merge_u16_darks_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
+                                char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
+    MergeCall call;
+    const int rc = hm_rules::check_merge_call(g, hm_rules::ENTRY_U16_DARKS, &x, call);
+    if (rc != HM_OK || call.empty) { buf[0] = 0; return rc; }
+    if (!call.hot) return hm_merge_u16_describe(g, frames_u16, bit_depth, buf, buf_len);
+    std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d,hot=%d%s>(N=%d)", call.bit_depth, call.a.channels,
+                  call.with_std && call.a.out_val, call.a.median_k, call.f32out ? ",out=f32" : "", call.a.n_frames);
+    return rc;
+}
+
+int hm_merge_u16_darks(const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth, void*) {
+    return merge_u16_darks_host(g_in, frames_u16, darks_u16, bit_depth);
 }
 
 static int merge_run(const hm_merge_args* g_in, MergeEntry entry, const void* extra) {

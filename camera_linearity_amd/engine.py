@@ -96,16 +96,22 @@ def weight_luts(device, bit_depth: int = 8) -> tuple:
     return _weight_cache[key]
 
 
-def dark_min_dn(scale: float, threshold: float) -> int:
+def dark_min_dn(scale: float, threshold: float, bit_depth: Optional[int] = None) -> int:
     """Smallest dark DN that counts as hot: the reference tests `dark.val > threshold`
     (modules/measurand.py:545) with dark.val = (DN/255) * scale (modules/image_set.py:223,260);
     evaluated here for all 256 DNs with the same float64 operations, so the DN-domain comparison the
-    kernel performs (`dark_dn >= min_dn`) is exactly equivalent. Returns 256 when no DN is hot."""
-    v = np.arange(BITS, dtype=np.uint8).astype(np.float64) / MAX_DN
+    kernel performs (`dark_dn >= min_dn`) is exactly equivalent. Returns 256 when no DN is hot.
+    bit_depth (9..16, uint16 dark maps of hm_merge_u16_darks): the same evaluation over all 2**bit_depth DNs on DN / (2**bit_depth - 1);
+    returns 2**bit_depth when no DN is hot."""
+    if bit_depth is None:
+        n_dn, v = BITS, np.arange(BITS, dtype=np.uint8).astype(np.float64) / MAX_DN
+    else:
+        n_dn = 2 ** _check_bit_depth(bit_depth)
+        v = np.arange(n_dn, dtype=np.uint32).astype(np.float64) / (n_dn - 1)
     if scale != 1.0:
         v = np.array([scale], dtype=np.float64) * v                       # Measurand(scale) * dark, measurand.py:198
     hot = np.nonzero(v > threshold)[0]
-    return int(hot[0]) if hot.size else BITS
+    return int(hot[0]) if hot.size else n_dn
 
 
 def _stream(device):
@@ -287,7 +293,7 @@ class MergePlan:
     repeatedly (bench, hipGraph capture)."""
 
     def __init__(self, args: nat.MergeArgs, keep: list, device, outputs: dict, std_table: Optional[torch.Tensor] = None, stds_f32=None,
-                 frames_u16=None, bit_depth: Optional[int] = None):
+                 frames_u16=None, bit_depth: Optional[int] = None, darks_u16=None):
         self.args = args
         self._keep = keep
         self.device = torch.device(device)
@@ -298,7 +304,10 @@ class MergePlan:
         # the C entry point the plan goes through and the entry's own argument after the struct: the ctypes array of N pointers to float32
         # std frames (hm_merge_std_f32), the table, or none
         self.bit_depth = bit_depth                         # uint16 DN frames: the plan goes through hm_merge_u16 (ctypes array of N frame pointers, depth)
-        if frames_u16 is not None:
+        self._bytes_extra = ()                             # what the entry's _algorithmic_bytes form takes after the struct
+        if darks_u16 is not None:                          # ... with uint16 dark maps: hm_merge_u16_darks (ctypes array of N map pointers or NULLs)
+            self._entry, self._extra, self._bytes_extra = "hm_merge_u16_darks", (frames_u16, darks_u16, int(bit_depth)), (darks_u16,)
+        elif frames_u16 is not None:
             self._entry, self._extra = "hm_merge_u16", (frames_u16, int(bit_depth))
         elif stds_f32 is not None:
             self._entry, self._extra = "hm_merge_std_f32", (stds_f32,)
@@ -328,7 +337,7 @@ class MergePlan:
 
     @property
     def algorithmic_bytes(self) -> int:
-        return int(self._bytes(self._ref))
+        return int(self._bytes(self._ref, *self._bytes_extra))
 
     @property
     def kernels(self) -> str:
@@ -374,8 +383,11 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
              and no forced chunking: NotImplementedError.
     bit_depth : 9..16, required for (and only for) torch.uint16 DN frames of 9- to 16-bit cameras (hm_merge_u16): ValueError otherwise. A DN
              has the value DN / (2**bit_depth - 1) and the table index DN & (2**bit_depth - 1); `icrf` / `icrf_diff` must have
-             2**bit_depth rows, the weight tables are weight_luts(device, bit_depth). float32 stds are widened to float64. Not built for
-             such frames - NotImplementedError: `std_table`, `darks`, a uint8 `flat`, more than HM_MAX_FRAMES frames (or forced chunking).
+             2**bit_depth rows, the weight tables are weight_luts(device, bit_depth). float32 stds are widened to float64. `darks` are
+             torch.uint16 maps of the frames' shape (hm_merge_u16_darks): frame i is hot where (dark DN & (2**bit_depth - 1)) >=
+             dark_min[i], thresholds 1 .. 2**bit_depth (dark_min_dn(scale, threshold, bit_depth)); `median_k` and `hot_queue` as for 8-bit
+             frames (False: the patch kernel tests every element itself). Not built for such frames - NotImplementedError: `std_table`,
+             dark maps of another dtype, a uint8 `flat`, more than HM_MAX_FRAMES frames (or forced chunking).
              variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
              memory / split between the two.
     """
@@ -393,8 +405,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         bit_depth = _check_bit_depth(bit_depth)
         if std_table is not None:
             raise NotImplementedError("uint16 frames: the per-DN std table (std_table) is built for 8-bit frames only")
-        if darks is not None and any(d is not None for d in darks):
-            raise NotImplementedError("uint16 frames: dark maps (the hot-pixel pass) are built for 8-bit frames only")
+        if darks is not None and any(d is not None and d.dtype != _U16 for d in darks):
+            raise NotImplementedError("uint16 frames: uint16 dark maps are expected (hm_merge_u16_darks); uint8 and other dark map dtypes "
+                                      "are built for 8-bit frames only")
         if flat is not None and flat.dtype == _U8:
             raise NotImplementedError("uint16 frames: a uint8 flat field is built for 8-bit frames only (pass a float64 flat)")
         if n > nat.HM_MAX_FRAMES or variant <= -2:
@@ -481,6 +494,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     keep.append(exp)
     a.icrf, a.icrf_diff = icrf_t.data_ptr(), nat.ptr(diff_t)
     a.w_lut, a.dw_lut = w_lut.data_ptr(), dw_lut.data_ptr()
+    darks_u16 = None
     if darks is not None and any(d is not None for d in darks):
         if len(darks) != n or dark_min is None or len(dark_min) != n:
             raise ValueError("darks and dark_min need one entry per frame")
@@ -490,12 +504,15 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
                 dk.append(None)
                 continue
             _require_cuda(d, f"darks[{i}]")
-            if d.dtype != _U8 or tuple(d.shape) != shape:
-                raise ValueError("dark maps must be uint8 with the frames' shape")
+            if d.dtype != (_U16 if u16 else _U8) or tuple(d.shape) != shape:
+                raise ValueError(f"dark maps must be {'uint16' if u16 else 'uint8'} with the frames' shape")
             dk.append(d.contiguous())
         dptrs = _ptr_array(dk)
         dmin = (C.c_int32 * n)(*[int(x) for x in dark_min])
-        a.darks_u8 = C.cast(dptrs, C.POINTER(C.c_void_p))
+        if u16:
+            darks_u16 = dptrs                              # hm_merge_u16_darks takes the map pointers beside the struct
+        else:
+            a.darks_u8 = C.cast(dptrs, C.POINTER(C.c_void_p))
         a.dark_min_dn = C.cast(dmin, C.POINTER(C.c_int32))
         a.median_k = int(median_k)
         keep += [dk, dptrs, dmin]
@@ -550,7 +567,7 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
         a.frames_workspace, a.frames_workspace_bytes = ws.data_ptr(), fw
         keep.append(ws)
     plan = MergePlan(a, keep, dev, outputs, std_table=table_t, stds_f32=sptrs if sd_f32 else None,
-                     frames_u16=fptrs if u16 else None, bit_depth=bit_depth)
+                     frames_u16=fptrs if u16 else None, bit_depth=bit_depth, darks_u16=darks_u16)
     if out_dtype == torch.float32 or table_t is not None or sd_f32 or u16:
         plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs / table calls raises here, not at the first launch
     return plan
@@ -622,9 +639,10 @@ class PlanGraph:
 
 
 def sum_of_weights(frames, darks=None, dark_min=None, median_k: int = 3, **kw):
-    """modules/exposure_series.py:317-345 -> (S, S**2) as device tensors."""
+    """modules/exposure_series.py:317-345 -> (S, S**2) as device tensors. uint16 frames: with `bit_depth=` (and uint16 `darks`)."""
     Cc = frames[0].shape[-1]
-    ident = np.zeros((BITS, Cc))
+    n_rows = 2 ** _check_bit_depth(kw.get("bit_depth")) if frames[0].dtype == _U16 else BITS
+    ident = np.zeros((n_rows, Cc))
     plan = plan_merge(frames, [1.0] * len(frames), ident, darks=darks, dark_min=dark_min, median_k=median_k,
                       want_sum_w=True, want_val=False, **kw)
     plan.launch()

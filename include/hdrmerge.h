@@ -45,7 +45,7 @@ extern "C" {
  *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only), and likewise by
  *    hm_merge_std_table* and hm_merge_std_f32* (new entry points beside hm_merge; hm_merge_args keeps its 296 bytes), and by
  *    hm_merge_u16*, hm_linearize_u16 and hm_gaussian_weight_lut_bits_host (uint16 DN frames of 9- to 16-bit cameras; HM_BITS below is
- *    the table size of the 8-bit entry points only).                                                                        */
+ *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames).       */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -293,6 +293,35 @@ int64_t hm_merge_std_f32_algorithmic_bytes(const hm_merge_args* args /*[host]*/)
 int hm_merge_u16(const hm_merge_args* args /*[host]*/, const uint16_t* const* frames_u16 /*[host] N device pointers*/, int bit_depth, void* stream);
 int hm_merge_u16_describe(const hm_merge_args* args, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len);
 int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* args /*[host]*/);
+
+/* hm_merge_u16 with the hot-pixel prologue: per frame a uint16 dark DN map with the frames' geometry, or NULL ("no filter for this frame").
+ * With M = 2^bit_depth - 1, frame i is hot at element e iff (darks_u16[i][e] & M) >= args->dark_min_dn[i] - the wrap convention applied to
+ * dark DNs too; thresholds are 1 .. 2^bit_depth, and 2^bit_depth means that no DN is hot (as 256 does for hm_merge). Where a frame is hot
+ * its DN is replaced by the k x k median (k = args->median_k: 3, 5 or 7) of the masked DNs (DN & M) of its spatial neighbourhood - same
+ * channel, scipy 'reflect' at the true image edges - and, with std frames, its std by the k x k median of the std neighbourhood: hm_merge's
+ * pass (modules/measurand.py:543-557). out_val, out_std and out_sum_w (either out_kind, with or without the float64 flat field, the
+ * sum-of-weights-only call included) are bit for bit those of hm_merge_u16 on the frames filtered that way beforehand.
+ * darks_u16: [host] array of N device pointers (host memory on the host build), each NULL or 2-byte aligned, addressing image row
+ * buf_row0. args->darks_u8 must be NULL. args->hot_workspace / hot_workspace_bytes: optional, sized by hm_merge_hot_workspace_bytes /
+ * hm_merge_hot_workspace_min_bytes as for hm_merge; NULL, too small, not 16-byte aligned or a tile of 2^32 elements or more: the patch
+ * kernel tests every element's dark DNs itself (same bits). Row tiles follow hm_merge's halo rule: the buffers cover median_k / 2 rows
+ * beyond the tile except at the image edges. Statuses, an earlier rule wins:
+ *   1. HM_EINVAL: hm_merge_u16's rule 1; then NULL darks_u16, args->darks_u8 set, no dark_min_dn.
+ *   2. HM_EALIGN: a frame pointer, then a dark map pointer, that is not 2-byte aligned.
+ *   3. Every remaining rule of hm_merge, with its hot-pixel checks in their place when at least one map is given: HM_EINVAL for a median_k
+ *      other than 3, 5, 7; HM_ESHAPE for a missing halo; then HM_EINVAL for a threshold outside 1 .. 2^bit_depth of a frame that has a
+ *      map. Then HM_EINVAL for a variant above 3.
+ *   4. HM_EUNSUPPORTED: hm_merge_u16's rule 4 (flat_u8, more than HM_MAX_FRAMES frames or variant <= -2, variants 1 / 3 that do not fit).
+ * With every entry of darks_u16 NULL the call runs exactly as hm_merge_u16 does (same kernels, same describe string); hm_merge_u16 itself
+ * keeps refusing args->darks_u8 with HM_EUNSUPPORTED.
+ * hm_merge_u16_darks_describe: hm_merge_u16's names, then " + merge_u16_scan_hot + merge_u16_patch_hot<bits=b,std=s,k=K>" with a usable
+ * workspace or " + merge_u16_patch_hot<bits=b,std=s,k=K,queue=0>" without one.
+ * hm_merge_u16_darks_algorithmic_bytes: hm_merge_u16's count plus 2 bytes per element for every DISTINCT (map, threshold). */
+int hm_merge_u16_darks(const hm_merge_args* args /*[host]*/, const uint16_t* const* frames_u16 /*[host] N device pointers*/,
+                       const uint16_t* const* darks_u16 /*[host] N device pointers or NULLs*/, int bit_depth, void* stream);
+int hm_merge_u16_darks_describe(const hm_merge_args* args, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
+                                char* buf, int buf_len);
+int64_t hm_merge_u16_darks_algorithmic_bytes(const hm_merge_args* args /*[host]*/, const uint16_t* const* darks_u16 /*[host]*/);
 /* hm_linearize_u8 for uint16 DNs: idx = dn & (2^bit_depth - 1), tables of 2^bit_depth rows gathered from global memory; out_idx
  * (nullable, 2-byte aligned) receives the masked DN. bit_depth outside 9..16: HM_EINVAL; dn / out_idx not 2-byte aligned: HM_EALIGN. */
 int hm_linearize_u16(const uint16_t* dn, const double* std, const double* icrf, const double* icrf_diff,

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
-from camera_linearity_amd import engine, settings  # noqa: E402
+from camera_linearity_amd import _native as nat, engine, settings  # noqa: E402
 from camera_linearity_amd.measurand import _HOST_ENGINE as heng  # noqa: E402
 from camera_linearity_amd.measurand_factory import Measurand  # noqa: E402
 
@@ -29,6 +29,7 @@ ap.add_argument("--log", default=None)
 ap.add_argument("--one", default=None, help="<generator>:<seed> - re-run one reported case and print both sides of the first mismatch in full")
 ap.add_argument("--specials", type=float, default=0.3, help="share of cases whose float operands get NaN / +-inf / +-0 sprinkled in")
 ap.add_argument("--scale", type=int, default=1, help="multiplies the image sizes of the merge / linearity / Welford / statistics generators (streaming kernels over many groups)")
+ap.add_argument("--only", default=None, help="comma-separated generator names (case_merge_u16_darks,...): run these alone")
 ap.add_argument("--self-check", action="store_true", help="host build against itself (no GPU): exercises this script only")
 args = ap.parse_args()
 dev = torch.device("cpu" if args.self_check else "cuda:0")
@@ -873,6 +874,86 @@ def case_merge_u16(rng):
     return desc
 
 
+def case_merge_u16_darks(rng):
+    """the uint16 merge with uint16 dark maps (engine.plan_merge(darks=[uint16 maps], bit_depth=...), hm_merge_u16_darks): HIP - any
+    streaming variant, whole images or row tiles with the median's halo, shared / distinct / missing maps, the recommended workspace, the
+    smallest legal one (one entry: the queue overflows) or none - against the host build's whole-image result, bit for bit"""
+    c = int(rng.choice([1, 2, 3, 3, 3, 4]))
+    n = int(rng.choice([1, 2, 3, 5, 7, 7, 8, 9, 15, 16, 17, 20, 32]))
+    b = int(rng.integers(9, 17))
+    k = int(rng.choice([3, 3, 5, 7]))
+    h, w = int(rng.integers(1, 48 * args.scale)), int(rng.integers(1, 130 * args.scale))
+    if rng.random() < 0.3:
+        h, w = int(rng.integers(8, 40 * args.scale)), 128 * int(rng.integers(1, 4 * args.scale))
+    with_std, use_flat, sum_w, f32, val = rng.random() < 0.5, rng.random() < 0.4, rng.random() < 0.3, rng.random() < 0.25, rng.random() < 0.85
+    variant = int(rng.choice([0, 0, 0, -1, 1, 2, 3]))
+    workspace = str(rng.choice(["rec", "rec", "min", "none"]))
+    top = 2 ** b
+    frames = [dn16(rng, (h, w, c), b) for _ in range(n)]
+    stds = [np.abs(rng.normal(size=(h, w, c))) * 0.01 for _ in range(n)] if with_std else None
+    t = 1e-3 * rng.uniform(1.2, 2.2) ** np.arange(n)
+    g, d = icrf_tables_bits(rng, c, b)
+    pool, darks, mins = [], [], []
+    for i in range(n):
+        r = rng.random()
+        if r < 0.25 and i > 0:
+            darks.append(None); mins.append(top)
+            continue
+        if r < 0.5 and pool:                                           # an earlier frame's map again, with its threshold or another
+            dm = pool[int(rng.integers(len(pool)))]
+        else:
+            dm = rng.integers(0, top // 4, (h, w, c)).astype(np.uint16)
+            dm[rng.random(dm.shape) < rng.choice([0.001, 0.02, 0.3, 0.7])] = top - 3
+            if b < 16:
+                dm[rng.random(dm.shape) < 0.01] |= np.uint16((0xFFFF << b) & 0xFFFF)
+            pool.append(dm)
+        darks.append(dm); mins.append(int(rng.choice([top // 2, top - 3, top - 2, top // 8, top, 1])))
+    desc = (f"merge_u16_darks n={n} h={h} w={w} c={c} bits={b} k={k} std={with_std} flat={use_flat} sum_w={sum_w} f32={f32} val={val} "
+            f"variant={variant} workspace={workspace} maps={len(pool)} mins={mins}")
+    kw = dict(bit_depth=b, want_sum_w=bool(sum_w or not val), want_val=bool(val), dark_min=mins, median_k=k)
+    if f32:
+        kw["out_dtype"] = torch.float32
+    if use_flat:
+        kw.update(flat=0.5 + 0.5 * rng.random((h, w, c)), ff_mean=list(rng.uniform(0.6, 0.9, size=c)))
+        if with_std:
+            kw.update(flat_std=0.002 * (1 + rng.random((h, w, c))), ff_std_mean=list(rng.uniform(0.001, 0.003, size=c)))
+    tile = None
+    if rng.random() < 0.33 and h >= 2:
+        r0 = int(rng.integers(0, h - 1)); r1 = int(rng.integers(r0 + 1, h + 1))
+        tile = (r0, r1, int(rng.integers(0, max(0, r0 - k // 2) + 1)), int(rng.integers(min(h, r1 + k // 2), h + 1)))
+    desc += f" tile={tile}"
+
+    def run(eng, conv, tl, v, ws):
+        k2 = dict(kw)
+        rows = slice(None) if tl is None else slice(tl[2], tl[3])
+        out_rows = slice(None) if tl is None else slice(tl[0], tl[1])
+        for name in ("flat", "flat_std"):
+            if name in k2:
+                k2[name] = conv(k2[name][out_rows])
+        if tl is not None:
+            k2.update(height=h, row0=tl[0], rows=tl[1] - tl[0], buf_row0=tl[2])
+        shared = {}                                                    # frames that share a map share its pointer
+        dk = [None if x is None else shared.setdefault(id(x), conv(x[rows])) for x in darks]
+        plan = eng.plan_merge([conv(f[rows]) for f in frames], list(t), g, d if with_std else None,
+                              [conv(s[rows]) for s in stds] if with_std else None, darks=dk, variant=v, hot_queue=ws != "none", **k2)
+        if ws == "min":
+            plan.args.hot_workspace_bytes = int(nat.hip_lib.hm_merge_hot_workspace_min_bytes(plan.args.rows * w * c))
+        plan.launch()
+        return plan.outputs
+
+    try:
+        a = run(engine, D, tile, variant, workspace)
+    except NotImplementedError:                                        # a forced placement whose tables do not fit: the library's choice instead
+        desc += " (variant refused: 0)"
+        a = run(engine, D, tile, 0, workspace)
+    b_ = run(heng, Hh, None, 0, "none")
+    if tile is not None:
+        b_ = {key: v[tile[0]:tile[1]] for key, v in b_.items()}
+    for key in b_:
+        compare(f"{key}", a[key], b_[key], None)
+    return desc
+
+
 def case_linearize_u16(rng):
     c = int(rng.choice([1, 2, 3, 4]))
     b = int(rng.choice([9, 10, 12, 14, 16]))
@@ -893,8 +974,11 @@ def case_linearize_u16(rng):
     return desc
 
 
-CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_linearize_u16, 1),(case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
+CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
          (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
+if args.only:
+    CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
+    assert CASES, f"--only {args.only}: no such generator"
 weights = np.array([w for _, w in CASES], dtype=np.float64)
 weights /= weights.sum()
 counts = {fn.__name__: 0 for fn, _ in CASES}
