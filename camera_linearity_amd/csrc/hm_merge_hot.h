@@ -7,6 +7,7 @@
 // merge_scan_hot), hm_merge_hot_sd32.hip for float32 std frames (hm_merge_std_f32; template parameter SD = float).
 #pragma once
 #include "hm_merge_host.h"
+#include "hm_merge_hot_scan.h"
 #include <mutex>
 
 namespace hm {
@@ -163,31 +164,7 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
     }
 }
 
-// hot bits of the lane's 16-element chunk: bit b set iff element e0 + b is hot in at least one frame. Every DISTINCT
-// (dark map, threshold) is read once - one 16-byte load when the address allows (the d * N term of the algorithmic bytes).
-__device__ __forceinline__ uint32_t scan_chunk_hotbits(const MergeK& a, int64_t e0, int cnt) {
-    uint32_t hotbits = 0;
-    for (int i = 0; i < a.n_frames; ++i) {
-        const uint8_t* d = a.dark[i];
-        if (!d) continue;
-        bool seen = false;                                          // same map + threshold as an earlier frame
-        for (int k = 0; k < i; ++k) seen = seen || (a.dark[k] == d && a.dark_min[k] == a.dark_min[i]);
-        if (seen) continue;
-        const uint8_t* p = d + a.in_off + e0;
-        const uint32_t thr = static_cast<uint32_t>(a.dark_min[i]);
-        if (cnt == 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-            const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-            const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int b = 0; b < 16; ++b) hotbits |= (((w4[b >> 2] >> (8 * (b & 3))) & 255u) >= thr) ? (1u << b) : 0u;
-        } else {
-            for (int b = 0; b < cnt; ++b) hotbits |= (static_cast<uint32_t>(p[b]) >= thr) ? (1u << b) : 0u;
-        }
-    }
-    return hotbits;
-}
-
-
+// (scan_chunk_hotbits, lane_hotmask and the scan itself: hm_merge_hot_scan.h)
 // (the hot-element queue's layout in the caller's workspace: hm_merge_dev.h)
 
 // merge_fixup_hot: every lane scans 16 consecutive elements of every distinct dark map; elements with at least one hot
@@ -209,7 +186,7 @@ __global__ __launch_bounds__(256) void merge_fixup_hot(const MergeK a) {
         uint32_t hotbits = 0;
         if (chunk < n_chunks) {
             const int64_t left = a.elem0 + a.n_elems - e0;
-            hotbits = scan_chunk_hotbits(a, e0, left < 16 ? static_cast<int>(left) : 16);
+            hotbits = scan_chunk_hotbits<uint8_t>(a, 255u, e0, left < 16 ? static_cast<int>(left) : 16);
         }
         unsigned long long pending = __ballot(hotbits != 0);
         while (pending) {                                                    // rare
@@ -244,23 +221,6 @@ int launch_scan_hot(const MergeK& k, uint32_t* ws, uint32_t capacity, hipStream_
 constexpr int kPatchFB = 4;             // frames whose nine neighbour loads are issued together (float64 values / stds)
 constexpr int kPatchFBU8 = 8;           // the same for uint8 values (one VGPR each)
 constexpr int kPatchF64Frames = 16;     // float64 stacks: frames kept in LDS between the passes (8 B x 256 threads each)
-
-__device__ __forceinline__ uint32_t lane_hotmask(const MergeK& a, int64_t ei) {
-    uint32_t hotmask = 0;
-    const int N = a.n_frames;
-    for (int i0 = 0; i0 < N; i0 += 8) {
-        uint32_t d[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            d[k] = 0;
-            if (i0 + k < N && a.dark[i0 + k]) d[k] = a.dark[i0 + k][ei];                 // wave-uniform condition
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (i0 + k < N && a.dark[i0 + k]) hotmask |= (static_cast<int>(d[k]) >= a.dark_min[i0 + k]) ? (1u << (i0 + k)) : 0u;
-    }
-    return hotmask;
-}
 
 template <bool F64IN, bool STD, int OUT = OUT_F64, bool LUT = false, typename SD = double>
 __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* t_w, const double* t_dw, const double* t_g, const double* t_d,
@@ -488,7 +448,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
     uint32_t hot_first = 0;
     if (overflow == 0u && lane < B && entry_of(0) < count) {
         e_first = static_cast<int64_t>(queue[slot_of(entry_of(0))]);
-        hot_first = lane_hotmask(a, a.in_off + e_first);
+        hot_first = lane_hotmask<uint8_t>(a, a.in_off + e_first, 255u);
     }
     fill_plain_tables<F64IN, STD>(a, t_w, t_dw, t_g, t_d);
     __syncthreads();
@@ -496,7 +456,7 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
         const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; q < a.n_elems; q += stride) {
             const int64_t e = a.elem0 + q;
-            const uint32_t hotmask = lane_hotmask(a, a.in_off + e);
+            const uint32_t hotmask = lane_hotmask<uint8_t>(a, a.in_off + e, 255u);
             if (hotmask) patch_element<F64IN, STD, OUT, LUT, SD>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
         return;
@@ -508,30 +468,45 @@ __global__ __launch_bounds__(256) void merge_patch_hot(const MergeK a, const uin
             uint32_t hotmask = hot_first;
             if (it != 0u) {
                 e = static_cast<int64_t>(queue[slot_of(q)]);
-                hotmask = lane_hotmask(a, a.in_off + e);
+                hotmask = lane_hotmask<uint8_t>(a, a.in_off + e, 255u);
             }
             patch_element<F64IN, STD, OUT, LUT, SD>(a, t_w, t_dw, t_g, t_d, keep_lds, e, hotmask);
         }
     }
 }
 
-// SD = float (hm_merge_std_f32): std calls only, without the per-DN table (the dispatcher sends nothing else)
+// The one place that names the instantiations of this header's three kernel templates. A family wraps one of them (all of its instantiations
+// share a function type); pick_kernel() maps a call to its instantiation, or to nullptr for what no unit holds: SD = float
+// (hm_merge_std_f32) has std calls only, without the per-DN table (the dispatcher sends nothing else; the launchers answer HM_EINVAL).
+#define HM_HOT_FAMILY(K, ...) \
+    struct K##_family { \
+        using fn_t = void (*)(__VA_ARGS__); \
+        template <bool F, bool S, int OUT, bool LUT, typename SD> static fn_t get() { return &K<F, S, OUT, LUT, SD>; } \
+    };
+HM_HOT_FAMILY(merge_generic, const MergeK)
+HM_HOT_FAMILY(merge_fixup_hot, const MergeK)
+HM_HOT_FAMILY(merge_patch_hot, const MergeK, const uint32_t*, uint32_t)
+#undef HM_HOT_FAMILY
+template <typename FAMILY, int OUT, typename SD>
+typename FAMILY::fn_t pick_kernel(const MergeK& k, bool f64in, bool with_std) {
+    const bool lut = with_std && k.std_lut;
+    if constexpr (std::is_same_v<SD, float>) {
+        if (!with_std || lut) return nullptr;
+        return f64in ? FAMILY::template get<true, true, OUT, false, float>() : FAMILY::template get<false, true, OUT, false, float>();
+    } else {
+        if (lut) return f64in ? FAMILY::template get<true, true, OUT, true, double>() : FAMILY::template get<false, true, OUT, true, double>();
+        if (f64in) return with_std ? FAMILY::template get<true, true, OUT, false, double>() : FAMILY::template get<true, false, OUT, false, double>();
+        return with_std ? FAMILY::template get<false, true, OUT, false, double>() : FAMILY::template get<false, false, OUT, false, double>();
+    }
+}
+
 template <int OUT, typename SD>
 int launch_generic(const MergeK& k, bool f64in, bool with_std, hipStream_t st) {
     const unsigned grid = stream_grid(k.n_elems, 256, 8);
     if (describe_only("merge_generic<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
-#define HM_GEN(F, S) hipLaunchKernelGGL((merge_generic<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
-    if constexpr (std::is_same_v<SD, float>) {
-        if (!with_std || k.std_lut) return HM_EINVAL;
-        if (f64in) hipLaunchKernelGGL((merge_generic<true, true, OUT, false, float>), dim3(grid), dim3(256), 0, st, k);
-        else hipLaunchKernelGGL((merge_generic<false, true, OUT, false, float>), dim3(grid), dim3(256), 0, st, k);
-    } else if (with_std && k.std_lut) {
-        if (f64in) hipLaunchKernelGGL((merge_generic<true, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
-        else hipLaunchKernelGGL((merge_generic<false, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
-    }
-    else if (f64in) { if (with_std) HM_GEN(true, true); else HM_GEN(true, false); }
-    else       { if (with_std) HM_GEN(false, true); else HM_GEN(false, false); }
-#undef HM_GEN
+    const auto fn = pick_kernel<merge_generic_family, OUT, SD>(k, f64in, with_std);
+    if (!fn) return HM_EINVAL;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, st, k);
     return launch_status();
 }
 
@@ -540,18 +515,9 @@ int launch_fixup(const MergeK& k, bool f64in, bool with_std, hipStream_t st) {
     const int64_t chunks = (k.n_elems + 15) / 16;
     const unsigned grid = stream_grid(chunks, 256, 8);
     if (describe_only("merge_fixup_hot<f64in=%d,std=%d>", f64in, with_std)) return HM_OK;
-#define HM_FIX(F, S) hipLaunchKernelGGL((merge_fixup_hot<F, S, OUT>), dim3(grid), dim3(256), 0, st, k)
-    if constexpr (std::is_same_v<SD, float>) {
-        if (!with_std || k.std_lut) return HM_EINVAL;
-        if (f64in) hipLaunchKernelGGL((merge_fixup_hot<true, true, OUT, false, float>), dim3(grid), dim3(256), 0, st, k);
-        else hipLaunchKernelGGL((merge_fixup_hot<false, true, OUT, false, float>), dim3(grid), dim3(256), 0, st, k);
-    } else if (with_std && k.std_lut) {
-        if (f64in) hipLaunchKernelGGL((merge_fixup_hot<true, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
-        else hipLaunchKernelGGL((merge_fixup_hot<false, true, OUT, true>), dim3(grid), dim3(256), 0, st, k);
-    }
-    else if (f64in) { if (with_std) HM_FIX(true, true); else HM_FIX(true, false); }
-    else       { if (with_std) HM_FIX(false, true); else HM_FIX(false, false); }
-#undef HM_FIX
+    const auto fn = pick_kernel<merge_fixup_hot_family, OUT, SD>(k, f64in, with_std);
+    if (!fn) return HM_EINVAL;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, st, k);
     return launch_status();
 }
 
@@ -573,14 +539,9 @@ int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t* ws, s
     // resident from the start and a sparse queue costs the latency of one element. A grid of 8 per CU ran its workgroups in three
     // rounds at 3 resident per CU - 57-65 us for 35 000 queued elements, each round the same dependent chain of memory round trips.
     const int keep = patch_keep_bytes(f64in, k.n_frames, k.median_k);
-    const bool lut = with_std && k.std_lut;
-    const void* fn;
-    if constexpr (std::is_same_v<SD, float>) {
-        if (!with_std || lut) return HM_EINVAL;
-        fn = f64in ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT, false, float>) : reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT, false, float>);
-    } else if (lut) fn = f64in ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT, true>) : reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT, true>);
-    else if (f64in) fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<true, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<true, false, OUT>);
-    else       fn = with_std ? reinterpret_cast<const void*>(merge_patch_hot<false, true, OUT>) : reinterpret_cast<const void*>(merge_patch_hot<false, false, OUT>);
+    const auto kernel = pick_kernel<merge_patch_hot_family, OUT, SD>(k, f64in, with_std);
+    if (!kernel) return HM_EINVAL;
+    const void* fn = reinterpret_cast<const void*>(kernel);
     // (the query costs a few microseconds of host time: remembered per kernel, LDS size and device, under a mutex - hm_merge may be called
     // from several host threads)
     static struct { const void* fn; int keep, dev, per_cu; } seen[16];
@@ -607,18 +568,7 @@ int launch_hot_queue(const MergeK& k, bool f64in, bool with_std, uint32_t* ws, s
     const unsigned grid = stream_grid(k.n_elems, 256, per_cu);
     uint32_t bmax = 64;
     if (const int e = tune_env("HM_TUNE_PATCH_BMAX", 1, 64)) bmax = static_cast<uint32_t>(e);
-#define HM_PATCH(K, F, S) hipLaunchKernelGGL((K<F, S, OUT>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax)
-#define HM_PATCH4(K) { if (f64in) { if (with_std) HM_PATCH(K, true, true); else HM_PATCH(K, true, false); } \
-                       else       { if (with_std) HM_PATCH(K, false, true); else HM_PATCH(K, false, false); } }
-    if constexpr (std::is_same_v<SD, float>) {
-        if (f64in) hipLaunchKernelGGL((merge_patch_hot<true, true, OUT, false, float>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
-        else hipLaunchKernelGGL((merge_patch_hot<false, true, OUT, false, float>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
-    } else if (lut) {
-        if (f64in) hipLaunchKernelGGL((merge_patch_hot<true, true, OUT, true>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
-        else hipLaunchKernelGGL((merge_patch_hot<false, true, OUT, true>), dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
-    } else HM_PATCH4(merge_patch_hot)
-#undef HM_PATCH4
-#undef HM_PATCH
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), keep, st, k, static_cast<const uint32_t*>(ws), bmax);
     return launch_status();
 }
 

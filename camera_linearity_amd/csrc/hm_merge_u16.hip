@@ -31,50 +31,12 @@ constexpr int kU16Chunk = 8;          // frames whose loads a wave issues togeth
 constexpr int kU16LdsBlock = 1024;    // threads of the tab=lds workgroup
 constexpr int kU16GlobalBlock = 256;
 
-// merge_one_element<false, STD, HOT_NONE, OUT> for uint16 frames, tables in global memory
-template <bool STD, int OUT>
-__device__ __forceinline__ void merge_u16_element(const MergeK& a, uint32_t mask, int64_t e) {
-    const int C = a.C, N = a.n_frames;
-    const int64_t ei = a.in_off + e;
-    const int c = static_cast<int>(e % C);
-    double S = 0.0;
-    for (int i = 0; i < N; ++i) {
-        const double w = a.w_lut[ld_dn16(a, i, ei, mask)];
-        S = (i == 0) ? w : S + w;                                       // exposure_series.py:340
-    }
-    if (a.out_sum_w) a.out_sum_w[e] = S;
-    if (!a.out_val) return;
-    const double invS = 1.0 / S;
-    const double invS2 = 1.0 / (S * S);                                 // 1 / S**2, exposure_series.py:343
-    double acc = 0.0, var = 0.0;
-    for (int i = 0; i < N; ++i) {
-        const uint32_t idx = ld_dn16(a, i, ei, mask);
-        const double w = a.w_lut[idx];
-        const double dw = STD ? a.dw_lut[idx] : 0.0;
-        const double g = a.icrf[idx * C + c];
-        const double it = a.inv_t[i];
-        const double wg = w * g;
-        acc = (i == 0) ? wg * it : fma(wg, it, acc);                    // :388 numerator
-        if (STD) {
-            const double dg = a.icrf_diff[idx * C + c] * a.sd[i][ei];   // measurand.py:512
-            const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;   // :389
-            const double term = (A * dg) * it;
-            var = (i == 0) ? term * term : fma(term, term, var);
-        }
-    }
-    double val = acc / S;
-    double sd = STD ? sqrt(var) : 0.0;                                  // :394
-    if (a.has_flat) flat_field_apply(a, e, c, STD, val, sd);            // (flat_u8 is NULL in these calls: the float64 flat field)
-    store_out<OUT>(a.out_val, e, val);
-    if (STD) store_out<OUT>(a.out_std, e, sd);
-}
-
 template <bool STD, int OUT>
 __global__ __launch_bounds__(256) void merge_u16_generic(const MergeK a, const uint32_t mask) {
     reset_hot_counters(a);
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; q < a.n_elems; q += stride)
-        merge_u16_element<STD, OUT>(a, mask, a.elem0 + q);
+        merge_u16_element<STD, OUT>(a, a.elem0 + q, U16Frames(a, mask, a.elem0 + q));
 }
 
 // a.n_elems: whole groups of kSub elements, fewer than 2^32; the call keeps the pair rule (hdrmerge.h)
@@ -354,7 +316,7 @@ static int merge_u16_launch(const hm_rules::MergeCall& call, void* stream) {
         k.frame[i] = call.frames_u16[i];
         if (g->stds) k.sd[i] = g->stds[i];
         k.inv_t[i] = 1.0 / g->exposures[i];
-        k.dark[i] = hot ? reinterpret_cast<const uint8_t*>(call.darks_u16[i]) : nullptr;       // read through dark16()
+        k.dark[i] = hot ? reinterpret_cast<const uint8_t*>(call.darks_u16[i]) : nullptr;       // read through dark_as<uint16_t>()
         k.dark_min[i] = hot && call.darks_u16[i] ? g->dark_min_dn[i] : 1 << 16;
     }
     k.icrf = g->icrf; k.icrf_diff = g->icrf_diff; k.w_lut = g->w_lut; k.dw_lut = g->dw_lut;
@@ -421,6 +383,18 @@ static int merge_u16_entry(const hm_merge_args* g_in, hm_rules::MergeEntry entry
     return call.f32out ? merge_u16_launch<OUT_F32>(call, stream) : merge_u16_launch<OUT_F64>(call, stream);
 }
 
+// the dispatch above with launching switched off (hm_merge_describe's mechanism). Returns for NULL args before anything else is read - or written.
+static int merge_u16_describe(const hm_merge_args* g, hm_rules::MergeEntry entry, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16,
+                              int bit_depth, char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
+    DescribeCtx ctx;
+    g_describe = &ctx;
+    const int rc = merge_u16_entry(g, entry, frames_u16, darks_u16, bit_depth, nullptr);
+    g_describe = nullptr;
+    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
+    return rc;
+}
+
 }  // namespace hm
 
 extern "C" int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16); }
@@ -429,15 +403,8 @@ extern "C" int hm_merge_u16(const hm_merge_args* g, const uint16_t* const* frame
     return hm::merge_u16_entry(g, hm_rules::ENTRY_U16, frames_u16, nullptr, bit_depth, stream);
 }
 
-// the dispatch above with launching switched off (hm_merge_describe's mechanism). Returns for NULL args before anything else is read - or written.
 extern "C" int hm_merge_u16_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len) {
-    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
-    hm::DescribeCtx ctx;
-    hm::g_describe = &ctx;
-    const int rc = hm::merge_u16_entry(g, hm_rules::ENTRY_U16, frames_u16, nullptr, bit_depth, nullptr);
-    hm::g_describe = nullptr;
-    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
-    return rc;
+    return hm::merge_u16_describe(g, hm_rules::ENTRY_U16, frames_u16, nullptr, bit_depth, buf, buf_len);
 }
 
 // hm_merge_u16 with uint16 dark maps: the same launches, then the hot-pixel pass of hm_merge_u16_hot.hip where a frame has a map
@@ -451,11 +418,5 @@ extern "C" int hm_merge_u16_darks(const hm_merge_args* g, const uint16_t* const*
 
 extern "C" int hm_merge_u16_darks_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
                                            char* buf, int buf_len) {
-    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
-    hm::DescribeCtx ctx;
-    hm::g_describe = &ctx;
-    const int rc = hm::merge_u16_entry(g, hm_rules::ENTRY_U16_DARKS, frames_u16, darks_u16, bit_depth, nullptr);
-    hm::g_describe = nullptr;
-    snprintf(buf, static_cast<size_t>(buf_len), "%s", ctx.names.c_str());
-    return rc;
+    return hm::merge_u16_describe(g, hm_rules::ENTRY_U16_DARKS, frames_u16, darks_u16, bit_depth, buf, buf_len);
 }

@@ -589,71 +589,60 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
     }
 }
 
-extern "C" {
-
-int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16); }
-
-int hm_merge_u16_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len) {
-    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
-    const hm_rules::U16Extra x{frames_u16, bit_depth};
+// The uint16 entries, shaped like merge_run / merge_describe below: the rules of `entry` (ENTRY_U16 / ENTRY_U16_DARKS), then the one loop.
+// A hm_merge_u16_darks call whose maps are all NULL has call.hot = false: it runs, and answers, as hm_merge_u16.
+static int merge_u16_run(MergeEntry entry, const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth) {
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
     MergeCall call;
-    const int rc = hm_rules::check_merge_call(g, hm_rules::ENTRY_U16, &x, call);
-    if (rc == HM_OK && !call.empty)
-        std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d%s>(N=%d)", call.bit_depth, call.a.channels,
-                      call.with_std && call.a.out_val, call.f32out ? ",out=f32" : "", call.a.n_frames);
-    else buf[0] = 0;
-    return rc;
-}
-
-int hm_merge_u16(const hm_merge_args* g_in, const uint16_t* const* frames_u16, int bit_depth, void*) {
-    const hm_rules::U16Extra x{frames_u16, bit_depth};
-    MergeCall call;
-    const int rc = hm_rules::check_merge_call(g_in, hm_rules::ENTRY_U16, &x, call);
+    const int rc = hm_rules::check_merge_call(g_in, entry, &x, call);
     if (rc != HM_OK || call.empty) return rc;
     const hm_merge_args* g = &call.a;
     std::vector<double> inv_t(static_cast<size_t>(g->n_frames));
     for (int i = 0; i < g->n_frames; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
     const uint32_t mask = (1u << call.bit_depth) - 1u;
-    if (call.with_std && g->out_val) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data());
+    const bool with_std = call.with_std && g->out_val;
+    if (call.hot) {                                                     // the hot-pixel filter inline in merge_elements_u16
+        if (with_std) merge_elements_u16<true, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
+        else merge_elements_u16<false, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
+    } else if (with_std) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data());
     else merge_elements_u16<false>(g, call.frames_u16, mask, inv_t.data());
     return HM_OK;
 }
 
-// hm_merge_u16_darks on the host: the same rules (ENTRY_U16_DARKS), the hot-pixel filter inline in merge_elements_u16
-static int merge_u16_darks_host(const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth) {
+static int merge_u16_describe(MergeEntry entry, const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
+                              char* buf, int buf_len) {
+    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
     const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
     MergeCall call;
-    const int rc = hm_rules::check_merge_call(g_in, hm_rules::ENTRY_U16_DARKS, &x, call);
+    const int rc = hm_rules::check_merge_call(g, entry, &x, call);
+    buf[0] = 0;
     if (rc != HM_OK || call.empty) return rc;
-    if (!call.hot) return hm_merge_u16(g_in, frames_u16, bit_depth, nullptr);      // every map NULL: hm_merge_u16 as it is
-    const hm_merge_args* g = &call.a;
-    std::vector<double> inv_t(static_cast<size_t>(g->n_frames));
-    for (int i = 0; i < g->n_frames; ++i) inv_t[static_cast<size_t>(i)] = 1.0 / g->exposures[i];
-    const uint32_t mask = (1u << call.bit_depth) - 1u;
-    if (call.with_std && g->out_val) merge_elements_u16<true, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
-    else merge_elements_u16<false, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
-    return HM_OK;
+    char hot[24] = "";
+    if (call.hot) std::snprintf(hot, sizeof hot, ",hot=%d", call.a.median_k);
+    std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d%s%s>(N=%d)", call.bit_depth, call.a.channels,
+                  call.with_std && call.a.out_val, hot, call.f32out ? ",out=f32" : "", call.a.n_frames);
+    return rc;
 }
 
+extern "C" {
+
+int64_t hm_merge_u16_algorithmic_bytes(const hm_merge_args* g) { return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16); }
 int64_t hm_merge_u16_darks_algorithmic_bytes(const hm_merge_args* g, const uint16_t* const* darks_u16) {
     return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16_DARKS, darks_u16);
 }
 
+int hm_merge_u16(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, void*) {
+    return merge_u16_run(hm_rules::ENTRY_U16, g, frames_u16, nullptr, bit_depth);
+}
+int hm_merge_u16_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, int bit_depth, char* buf, int buf_len) {
+    return merge_u16_describe(hm_rules::ENTRY_U16, g, frames_u16, nullptr, bit_depth, buf, buf_len);
+}
+int hm_merge_u16_darks(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth, void*) {
+    return merge_u16_run(hm_rules::ENTRY_U16_DARKS, g, frames_u16, darks_u16, bit_depth);
+}
 int hm_merge_u16_darks_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
                                 char* buf, int buf_len) {
-    if (!buf || buf_len < 1 || !g) return HM_EINVAL;
-    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
-    MergeCall call;
-    const int rc = hm_rules::check_merge_call(g, hm_rules::ENTRY_U16_DARKS, &x, call);
-    if (rc != HM_OK || call.empty) { buf[0] = 0; return rc; }
-    if (!call.hot) return hm_merge_u16_describe(g, frames_u16, bit_depth, buf, buf_len);
-    std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d,hot=%d%s>(N=%d)", call.bit_depth, call.a.channels,
-                  call.with_std && call.a.out_val, call.a.median_k, call.f32out ? ",out=f32" : "", call.a.n_frames);
-    return rc;
-}
-
-int hm_merge_u16_darks(const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth, void*) {
-    return merge_u16_darks_host(g_in, frames_u16, darks_u16, bit_depth);
+    return merge_u16_describe(hm_rules::ENTRY_U16_DARKS, g, frames_u16, darks_u16, bit_depth, buf, buf_len);
 }
 
 static int merge_run(const hm_merge_args* g_in, MergeEntry entry, const void* extra) {

@@ -398,6 +398,43 @@ def test_hot_pixel_queue_smallest_workspace(eng):
     assert torch.equal(plan.outputs["val"], old.outputs["val"]) and torch.equal(plan.outputs["std"], old.outputs["std"])
 
 
+@pytest.mark.parametrize("case", ["unaligned-tile", "overflow-between-pieces"])
+def test_hot_pixel_scan_branches(eng, case):
+    """The two branches of the scan that the queue tests above do not pin by kernel name for uint8 maps (the scan's text is shared with
+    the uint16 pass). unaligned-tile: rows 5..10 of a 16 x 11 x 3 image from buffers that start at row 3 - the first input element sits at
+    (5 - 3) * 33 = 66, no multiple of 16, so no map can be read 16 bytes at a time, and 198 elements end in a partial chunk.
+    overflow-between-pieces: 131 328 elements are two whole 65 536-element scan pieces and a bit; about 36 % hot, either piece fits the
+    recommended queue (a quarter of the elements) and both do not, so one piece is queued before the other raises the flag.
+    N = 3: two distinct maps and the first again with another threshold; about 5 % hot in the small case. Bit for bit the workspace-free pass."""
+    from camera_linearity_amd import _native as nat
+    n = 3
+    h, w, tile, density = (16, 11, dict(height=16, row0=5, rows=6, buf_row0=3), 0.05) if case == "unaligned-tile" else (228, 192, {}, 0.2)
+    rng = np.random.default_rng(len(case))
+    frames, stds, t = orc.synthetic_stack(79, n, h, w, with_std=True)
+    icrf, diff = orc.synthetic_icrf()
+    maps = [np.where(rng.random((h, w, 3)) < density, 200, rng.integers(0, 10, (h, w, 3))).astype(np.uint8) for _ in range(2)]
+    if case == "unaligned-tile":
+        maps[0][rng.random((h, w, 3)) < density] = 120                       # hot for the third frame's threshold only
+    rows = slice(3, 12) if tile else slice(None)                            # the tile's rows with one halo row and one spare row above
+    fr, sd = [dev(f[rows]) for f in frames], [dev(s[rows]) for s in stds]
+    d0, d1 = dev(maps[0][rows]), dev(maps[1][rows])
+    kw = dict(darks=[d0, d1, d0], dark_min=[150, 150, 100], median_k=3, want_sum_w=True, **tile)
+    plan = eng.plan_merge(fr, t, icrf, diff, sd, **kw)
+    assert "merge_scan_hot + merge_patch_hot" in plan.kernels
+    if case == "overflow-between-pieces":
+        hot = ((maps[0] >= 100) | (maps[1] >= 150)).reshape(-1)
+        e = hot.size
+        cap = (int(nat.lib.hm_merge_hot_workspace_bytes(e)) - int(nat.lib.hm_merge_hot_workspace_min_bytes(e))) // 4 + 1
+        per_piece = [int(hot[lo:lo + 65536].sum()) for lo in (0, 65536)]
+        assert max(per_piece) < cap < sum(per_piece), (per_piece, cap)
+    plan.launch()
+    old = eng.plan_merge(fr, t, icrf, diff, sd, hot_queue=False, **kw)
+    assert "merge_scan_hot" not in old.kernels and "merge_fixup_hot" in old.kernels
+    old.launch()
+    for key in ("val", "std", "sum_w"):
+        assert torch.equal(plan.outputs[key], old.outputs[key]), key
+
+
 @pytest.mark.parametrize("n", [7, 8, 17, 18, 19, 20, 21, 32])          # (8 + std + flat + sum of weights: the instantiation that spilled 20 B/lane in round 3)
 @pytest.mark.parametrize("with_std", [False, True])
 def test_generic_kernel_bit_identical_to_fast_kernel(eng, with_std, n):
