@@ -119,7 +119,7 @@ __device__ __forceinline__ double rsqrt_third_order(double q) {
 }
 
 // 1 / x for the per-(pixel, frame) reciprocals of the pixel-major kernel: the hardware estimate and ONE second-order step, r0 (1 + e + e^2)
-// with e = 1 - x r0 - 4 instructions and at most 1.00 ulp (hm_stats.hip: rcp_newton, checked on 2 M operands) where the IEEE division
+// with e = 1 - x r0 - 4 instructions and at most 1.00 ulp (hm_moments.h: rcp_newton, checked on 2 M operands) where the IEEE division
 // expansion costs eleven, two of them quarter-rate; x = 0 / inf / NaN keep the estimate (inf / 0 / NaN, the IEEE answers).
 #ifndef HM_ENERGY_RCP
 #define HM_ENERGY_RCP 1

@@ -18,7 +18,7 @@ instead of 8) and materialises DN/255 (modules/image_set.py:223) only when `.val
 
 Rows "next" of SURVEY.md 8f-1: apply_thresholds, compute_difference, interpolate (equal shapes or broadcasting operands),
 compute_dimension_statistics (any axis or axis tuple), extract and compute_channel_histogram run as HIP kernels
-(csrc/hm_stats.hip, hm_ops.hip); what a kernel does not cover raises (more than 32 channels in apply_thresholds, more
+(csrc/hm_pointwise.hip, hm_stats.hip, hm_stats_axis.hip, hm_stats_hist.hip, hm_ops.hip); what a kernel does not cover raises (more than 32 channels in apply_thresholds, more
 than 4 channels in the histogram) - nothing is computed with torch or NumPy arithmetic. Kernel density estimates are
 HostMeasurand.compute_kernel_density_estimate (the reference's NumPy class) and kde.kernel_density_estimate on either backend.
 """

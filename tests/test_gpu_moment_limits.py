@@ -1,5 +1,6 @@
 """The mean / std reductions (csrc/hm_stats.hip: k_stats, k_stats_final, k_pair_stats, k_pair_final, k_pairs_stats, k_pairs_stats_lds,
-k_pairs_final, k_thresholds, k_axis_thread, k_axis_row, k_axis_final, k_axis_final_tree, k_axis_final2, k_axis_final2_tree) on the MI355X at
+k_pairs_final; csrc/hm_pointwise.hip: k_thresholds; csrc/hm_stats_axis.hip: k_axis_thread, k_axis_row, k_axis_final, k_axis_final_tree,
+k_axis_final2, k_axis_final2_tree) on the MI355X at
 the limits of their ABI: the checks of tests/test_moment_limits_host.py - the reference, the derived bounds and every case live there - on
 device tensors, plus the sizes at which a lane folds a 64-element block in mid-stream, a path only the device build has. Every test
 asserts that the device symbol ran and the host one did not."""

@@ -1,4 +1,4 @@
-"""The all-pairs linearity distributions (csrc/hm_stats.hip: k_pairs_hist, k_pairs_minmax, k_pairs_minmax_final) on the MI355X: the
+"""The all-pairs linearity distributions (csrc/hm_stats_hist.hip: k_pairs_hist, k_pairs_minmax, k_pairs_minmax_final) on the MI355X: the
 checks of tests/test_pairs_hist_host.py - the reference, the derived bound and every case live there - on device tensors. Every test
 asserts that the device symbols ran and the host ones did not."""
 import pytest

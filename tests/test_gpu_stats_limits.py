@@ -1,4 +1,4 @@
-"""The histogram and min / max kernels (csrc/hm_stats.hip: k_hist, k_hist_final, k_minmax, k_minmax_final), the ROI mean
+"""The histogram and min / max kernels (csrc/hm_stats_hist.hip: k_hist, k_hist_final, k_minmax, k_minmax_final), the ROI mean
 (csrc/hm_corrections.hip: k_roi_partial, k_roi_final) and the standalone hot-pixel filter (k_hot_filter, k_hot_filter_burst,
 wave_median, lane_median) on the MI355X at the limits of their ABI: the checks of tests/test_stats_limits_host.py - the references, the
 derived bounds and every case live there - on device tensors. Every test asserts that the device symbol ran and the host one did not."""

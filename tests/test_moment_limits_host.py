@@ -1,7 +1,7 @@
 """The mean / std reductions at the limits of their ABI: hm_channel_statistics (csrc/hm_stats.hip: k_stats, k_stats_final),
-hm_pair_statistics (k_pair_stats, k_pair_final), hm_pairs_statistics (k_pairs_stats, k_pairs_stats_lds<STD, NI, THR>, k_pairs_final,
-k_thresholds), hm_axis_statistics (k_axis_thread, k_axis_row, k_axis_final, k_axis_final_tree) and hm_axis_statistics2 (k_axis_final2,
-k_axis_final2_tree), on the HOST build (csrc_host/hm_host.cpp), against a np.longdouble reference written here. The checks are functions
+hm_pair_statistics (k_pair_stats, k_pair_final), hm_pairs_statistics (k_pairs_stats, k_pairs_stats_lds<STD, NI, THR>, k_pairs_final;
+csrc/hm_pointwise.hip: k_thresholds), hm_axis_statistics (csrc/hm_stats_axis.hip: k_axis_thread, k_axis_row, k_axis_final,
+k_axis_final_tree) and hm_axis_statistics2 (k_axis_final2, k_axis_final2_tree), on the HOST build (csrc_host/hm_host.cpp), against a np.longdouble reference written here. The checks are functions
 of a device name: tests/test_gpu_moment_limits.py runs the same ones on the MI355X (and alone runs the sizes whose path - the mid-stream
 block fold - only the device build has).
 
@@ -175,7 +175,7 @@ def ceil_div(a, b):
 
 
 def stat_grid(n, per=256):
-    """stat_grid() of hm_stats.hip (per = 256) and the same arithmetic with 64-lane workgroup rows in hm_pairs_statistics (per = 64)."""
+    """stat_grid() of hm_moments.h: per = 256 in hm_channel_statistics and hm_pair_statistics, 64-lane workgroup rows (per = 64) in hm_pairs_statistics."""
     return min(STAT_BLOCKS, 12 * ceil_div(ceil_div(n, per), 12))
 
 

@@ -1,4 +1,4 @@
-"""The all-pairs linearity distributions - hm_pairs_histogram / hm_pairs_minmax (csrc/hm_stats.hip: k_pairs_hist, k_pairs_minmax,
+"""The all-pairs linearity distributions - hm_pairs_histogram / hm_pairs_minmax (csrc/hm_stats_hist.hip: k_pairs_hist, k_pairs_minmax,
 k_pairs_minmax_final, k_hist_final), engine.pairs_histogram and ExposureSeries.process_linearity_distribution - on the HOST build
 (csrc_host/hm_host.cpp). The checks are functions of a device name: tests/test_gpu_pairs_hist.py runs the same ones on the MI355X.
 
@@ -14,7 +14,7 @@ Asserted
     sides: one rounding per reciprocal, k_b - 1 additions in any order, one for the reference's conversion). The fused result equals
     the unfused path of the same backend (compute_difference + channel_histogram): exactly when unweighted, within twice the bound when
     weighted (each side is within the bound of the reference). hm_pairs_minmax is exact.
-Sizes that come from the kernel's constants (hm_stats.hip)
+Sizes that come from the kernel's constants (hm_stats_hist.hip)
     A launch of np pairs gives every pair wpp = HM_PAIRS_MAX / np waves and runs min(ceil(n / (64 wpp)) rounded up to a multiple of 12,
     kPairsHistBlocks x per_cu) workgroups, each taking wpp 64-element chunks per sweep; kPairsHistBlocks = 252, per_cu = min(160 KiB /
     LDS of the workgroup, 32 / (np wpp), kPairsHistMaxPerCU = 4), LDS of the workgroup = np x 2 x C x bins x 8 bytes. FULL_SWEEP is one

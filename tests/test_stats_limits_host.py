@@ -1,5 +1,5 @@
 """The reductions and selection kernels beside the merge at the limits of their ABI: hm_channel_histogram / hm_channel_minmax
-(csrc/hm_stats.hip: k_hist, k_hist_final, k_minmax, k_minmax_final), hm_roi_mean_u8 / _f64 (csrc/hm_corrections.hip: k_roi_partial,
+(csrc/hm_stats_hist.hip: k_hist, k_hist_final, k_minmax, k_minmax_final), hm_roi_mean_u8 / _f64 (csrc/hm_corrections.hip: k_roi_partial,
 k_roi_final) and the standalone hm_hot_pixel_filter_u8 / _f64 (k_hot_filter, k_hot_filter_burst, wave_median, lane_median), on the
 HOST build (csrc_host/hm_host.cpp), against NumPy references in extended precision written here. The checks are functions of a device
 name: tests/test_gpu_stats_limits.py runs the same ones on the MI355X.
