@@ -19,6 +19,7 @@
 // bodies are the single-problem ones (k_de_trial's a shared function, k_de_select's the same text included a second time,
 // hm_de_select_body.h) applied to problem k's slices of the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
 #include "hm_common.h"
+#include "hm_calibration_rules.h"
 
 namespace hm {
 
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void k_de_select_batch(const DeK a, const DeSe
 
 using namespace hm;
 
-// the kernel arguments of a generation, as given (de_check judges them); a batch passes no seed here: its seeds travel in DeSeeds
+// the kernel arguments of a generation, as given (hm_calibration_rules.h judges them first); a batch passes no seed here: its seeds travel in DeSeeds
 static DeK de_args(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
                    int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits, const double* upper_limits,
                    int pop_size, int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
@@ -173,22 +174,6 @@ static DeK de_args(double* population, double* energies, double* trial, double* 
     k.S = pop_size; k.P = n_params; k.seed = static_cast<uint64_t>(seed); k.max_generations = max_generations;
     k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
     return k;
-}
-
-// the argument checks of hm_de_generation (n_problems = 1) and of hm_de_generation_batch (its n_problems already within 1 ..
-// HM_DE_MAX_PROBLEMS), in the order both document: the first violation decides the code. `stacks` is dn, whichever its type.
-static int de_check(const DeK& k, int n_problems, const void* stacks, const double* exposures, const void* workspace, int64_t n_pixels,
-                    int n_frames, int lower, int upper) {
-    if (k.S < 4 || k.P < 1 || n_pixels < 0 || k.max_generations < 0) return HM_EINVAL;
-    if (k.S > HM_DE_MAX_POP || k.P > HM_DE_MAX_PARAMS) return HM_ESHAPE;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (n_problems * k.S > 65535) return HM_EUNSUPPORTED;                     // the energy grid's candidate dimension (a batch only: S <= HM_DE_MAX_POP)
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (!(k.m_lo >= 0.0 && k.m_lo <= k.m_hi && k.m_hi < 2.0)) return HM_EINVAL;                          // also rejects NaN
-    if (!(k.cr >= 0.0 && k.cr <= 1.0) || !(k.tol >= 0.0) || k.energy_limit != k.energy_limit) return HM_EINVAL;
-    if (!k.pop || !k.energy || !k.trial || !k.trial_energy || !k.icrf || !k.valid || !k.status) return HM_EINVAL;
-    if (!k.mean_icrf || !k.pca || !k.lo || !k.hi || !stacks || !exposures || !workspace) return HM_EINVAL;
-    return HM_OK;
 }
 
 extern "C" size_t hm_de_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size) {
@@ -202,10 +187,13 @@ extern "C" int hm_de_generation(double* population, double* energies, double* tr
                                 const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size,
                                 int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
                                 double recombination, double tol, double energy_limit, void* workspace, void* stream) {
+    int rc = hm_rules::check_de_generation(1, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits,
+                                           upper_limits, dn, exposures, n_pixels, n_frames, lower, upper, pop_size, n_params, max_generations,
+                                           mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    if (rc != HM_OK) return rc;
+    if (!workspace) return HM_EINVAL;                                         // this build's own: the energy stage's partial sums
     const DeK k = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
                           pop_size, n_params, seed, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
-    int rc = de_check(k, 1, dn, exposures, workspace, n_pixels, n_frames, lower, upper);
-    if (rc != HM_OK) return rc;
     hipLaunchKernelGGL(k_de_trial, dim3(pop_size), dim3(256), 0, as_stream(stream), k);
     rc = launch_status();
     if (rc != HM_OK) return rc;
@@ -233,15 +221,14 @@ extern "C" int hm_de_generation_batch(int n_problems, double* population, double
                                       int n_frames, int lower, int upper, int pop_size, int n_params, int64_t max_generations,
                                       double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit,
                                       void* workspace, void* stream) {
-    if (n_problems < 1) return HM_EINVAL;
-    if (n_problems > HM_DE_MAX_PROBLEMS) return HM_ESHAPE;
+    int rc = hm_rules::check_de_generation_batch(n_problems, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca,
+                                                 lower_limits, upper_limits, dn, std, seeds, exposures, n_pixels, n_frames, lower, upper,
+                                                 pop_size, n_params, max_generations, mutation_lo, mutation_hi, recombination, tol,
+                                                 energy_limit);
+    if (rc != HM_OK) return rc;
+    if (!workspace) return HM_EINVAL;                                         // this build's own: the energy stage's partial sums
     const DeK k = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
                           pop_size, n_params, 0, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
-    int rc = de_check(k, n_problems, dn, exposures, workspace, n_pixels, n_frames, lower, upper);
-    if (rc != HM_OK) return rc;
-    if (!seeds) return HM_EINVAL;
-    for (int i = 0; i < n_problems; ++i)                                      // host arrays: read within the validated K only
-        if (!dn[i] || (std && !std[i])) return HM_EINVAL;                     // stds for all problems or for none
     DeSeeds sd{};
     for (int i = 0; i < n_problems; ++i) sd.seed[i] = static_cast<uint64_t>(seeds[i]);
     hipLaunchKernelGGL(k_de_trial_batch, dim3(pop_size, n_problems), dim3(256), 0, as_stream(stream), k, sd);

@@ -30,6 +30,7 @@
 // (energy_pixel_major, energy_chunks), so a candidate's sums are formed in the same order - the same bits - whether its problem is
 // evaluated alone or in a batch.
 #include "hm_common.h"
+#include "hm_calibration_rules.h"
 
 namespace hm {
 
@@ -262,12 +263,10 @@ extern "C" int hm_linearity_energy(const uint8_t* dn, const double* std, const d
                                    const uint8_t* valid, int n_candidates, int lower, int upper, int use_relative,
                                    int64_t n_pixels, int n_frames, double* out_pairs, double* out_energy,
                                    void* workspace, void* stream) {
-    if (n_candidates < 0 || n_pixels < 0) return HM_EINVAL;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (n_candidates == 0) return HM_OK;
-    if (n_candidates > 65535) return HM_EUNSUPPORTED;
-    if (!dn || !exposures || !icrf || !out_energy || !workspace) return HM_EINVAL;
+    bool empty;
+    const int rc0 = hm_rules::check_linearity_energy(dn, exposures, icrf, n_candidates, lower, upper, n_pixels, n_frames, out_energy, empty);
+    if (rc0 != HM_OK || empty) return rc0;
+    if (!workspace) return HM_EINVAL;                                         // this build's own: the partial sums live there
     const int pairs = n_frames * (n_frames - 1) / 2;
     const EnergyK k = energy_args(dn, std, exposures, icrf, valid, lower, upper, use_relative ? 1 : 0, n_pixels, n_frames, workspace);
     if (energy_pixel_major(n_frames, n_candidates, n_pixels)) {

@@ -15,6 +15,7 @@
 //             so a tile whose u range lies further than kKdeCut from every grid point of the workgroup is skipped: exact.
 //             Partials go to workspace[chunk][m]; k_kde_sum adds the chunks in a fixed order and applies the norm.
 #include "hm_common.h"
+#include "hm_producer_rules.h"
 
 namespace hm {
 
@@ -251,17 +252,11 @@ extern "C" size_t hm_kde_workspace_bytes(int64_t n_elems, int C, int m) {
     return e > mo ? e : mo;
 }
 
-static int kde_check(const double* val, int64_t n_elems, int C, int channel, void* workspace, int64_t workspace_bytes) {
-    if (!val || n_elems < 0 || C < 1 || channel < 0 || channel >= C || workspace_bytes < 0 || !workspace) return HM_EINVAL;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    return HM_OK;
-}
-
 extern "C" int hm_kde_moments(const double* val, const double* std, int64_t n_elems, int C, int channel, double* moments,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-    const int rc = kde_check(val, n_elems, C, channel, workspace, workspace_bytes);
+    const int rc = hm_rules::check_kde_moments(val, n_elems, C, channel, moments, workspace, workspace_bytes, true);
     if (rc != HM_OK) return rc;
-    if (!moments || static_cast<size_t>(workspace_bytes) < kde_mom_bytes()) return HM_EINVAL;
+    if (static_cast<size_t>(workspace_bytes) < kde_mom_bytes()) return HM_EINVAL;        // this build's own: the workspace's size
     const int64_t n = n_elems / C;
     double* part = static_cast<double*>(workspace);
     hipStream_t st = as_stream(stream);
@@ -275,13 +270,11 @@ extern "C" int hm_kde_moments(const double* val, const double* std, int64_t n_el
 
 extern "C" int hm_kde_evaluate(const double* val, const double* std, int64_t n_elems, int C, int channel, double h, double scale,
                                const double* grid, int m, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
-    const int rc = kde_check(val, n_elems, C, channel, workspace, workspace_bytes);
-    if (rc != HM_OK) return rc;
-    if (m < 0 || !(h > 0.0) || !std::isfinite(h) || !std::isfinite(scale)) return HM_EINVAL;
-    if (m == 0) return HM_OK;
-    if (!grid || !out) return HM_EINVAL;
+    bool empty;
+    const int rc = hm_rules::check_kde_evaluate(val, n_elems, C, channel, h, scale, grid, m, out, workspace, workspace_bytes, true, empty);
+    if (rc != HM_OK || empty) return rc;
     const int64_t n = n_elems / C;
-    if (static_cast<size_t>(workspace_bytes) < kde_eval_bytes(n, m)) return HM_EINVAL;
+    if (static_cast<size_t>(workspace_bytes) < kde_eval_bytes(n, m)) return HM_EINVAL;   // this build's own: the workspace's size
     const int64_t chunks = kde_chunks(n);
     double* part = static_cast<double*>(workspace);
     hipStream_t st = as_stream(stream);

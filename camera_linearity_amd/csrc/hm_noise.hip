@@ -16,6 +16,7 @@
 //     the output that are contiguous per mean level: LDS layout [m][d][c] = global layout [m][m - half + d][c]).
 // Bound: a workgroup counts at most units_per_lane x 16 x n_frames x 1024 < 2^32 elements per launch (checked on the host).
 #include "hm_common.h"
+#include "hm_producer_rules.h"
 
 namespace hm {
 
@@ -209,12 +210,9 @@ extern "C" int64_t hm_noise_profile_algorithmic_bytes(int n_frames, int64_t n_el
 extern "C" int hm_noise_profile_update(const void* const* frames, int n_frames, const uint8_t* mean, int64_t n_elems, int C,
                                        int64_t* profiles, void* workspace, int64_t workspace_bytes, void* stream) {
     (void)workspace;
-    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || n_elems < 0 || C < 1 || workspace_bytes < 0) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (!frames || !mean || !profiles) return HM_EINVAL;
-    for (int k = 0; k < n_frames; ++k) if (!frames[k]) return HM_EINVAL;
-    if (n_frames == 0 || n_elems == 0) return HM_OK;
+    bool empty;
+    const int rc = hm_rules::check_noise_profile_update(frames, n_frames, mean, n_elems, C, profiles, workspace_bytes, empty);
+    if (rc != HM_OK || empty) return rc;
     NoiseK k{};
     for (int i = 0; i < n_frames; ++i) k.frame[i] = static_cast<const uint8_t*>(frames[i]);
     k.mean = mean; k.prof = reinterpret_cast<unsigned long long*>(profiles); k.n = n_elems; k.n_frames = n_frames;
@@ -226,7 +224,7 @@ extern "C" int hm_noise_profile_update(const void* const* frames, int n_frames, 
     if (need < grid) grid = need;
     if ((units + grid * kNoiseBlock - 1) / (grid * kNoiseBlock) > max_units_per_lane)
         grid = (units + max_units_per_lane * kNoiseBlock - 1) / (max_units_per_lane * kNoiseBlock);
-    if (grid > 0x7fffffff) return HM_EUNSUPPORTED;
+    if (grid > 0x7fffffff) return HM_EUNSUPPORTED;                            // this build's own: the launch grid's limit
     const dim3 g(static_cast<unsigned>(grid)), b(kNoiseBlock);
     switch (C) {
         case 1: hipLaunchKernelGGL(k_noise_profile<1>, g, b, 0, as_stream(stream), k); break;
@@ -238,8 +236,8 @@ extern "C" int hm_noise_profile_update(const void* const* frames, int n_frames, 
 }
 
 extern "C" int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void* stream) {
-    if (!profiles || !edges || !out_std || C < 1) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    const int rc = hm_rules::check_noise_profile_std(profiles, C, edges, out_std);
+    if (rc != HM_OK) return rc;
     const int waves = 256 * C;
     hipLaunchKernelGGL(k_noise_std, dim3((waves + 3) / 4), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const long long*>(profiles), C, edges, out_std);
@@ -247,8 +245,8 @@ extern "C" int hm_noise_profile_std(const int64_t* profiles, int C, const double
 }
 
 extern "C" int hm_noise_profile_clean_edges(int64_t* profiles, int C, void* stream) {
-    if (!profiles || C < 1) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    const int rc = hm_rules::check_noise_profile_clean_edges(profiles, C);
+    if (rc != HM_OK) return rc;
     hipLaunchKernelGGL(k_noise_clean_edges, dim3((256 * C + 63) / 64), dim3(64), 0, as_stream(stream),
                        reinterpret_cast<long long*>(profiles), C);
     return launch_status();

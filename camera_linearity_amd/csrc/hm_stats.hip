@@ -526,7 +526,7 @@ extern "C" int hm_pairs_statistics(const double* const* vals, const double* cons
                                    const int32_t* pair_j, const double* multipliers, int n_pairs, int64_t n, int C,
                                    const double* lower, const double* upper,
                                    double* out /*n_pairs * 6C*/, void* workspace, void* stream) {
-    const int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
     if (rc != HM_OK) return rc;
     const bool thr = lower != nullptr;
     PairsK k{};

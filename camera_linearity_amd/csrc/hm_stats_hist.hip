@@ -323,7 +323,7 @@ extern "C" size_t hm_pairs_histogram_workspace_bytes(int n_pairs, int bins, int 
 extern "C" int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i,
                                const int32_t* pair_j, const double* multipliers, int n_pairs, int64_t n, int C,
                                const double* lower, const double* upper, double* out, void* workspace, void* stream) {
-    const int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
     if (rc != HM_OK) return rc;
     PairsK k{};
     pairs_dist_fill(k, vals, stds, n_frames, n, C, lower, upper);
@@ -347,8 +347,8 @@ extern "C" int hm_pairs_histogram(const double* const* vals, const double* const
                                   const int32_t* pair_j, const double* multipliers, int n_pairs, int64_t n, int C, int channel_mask,
                                   const double* lower, const double* upper, const double* edges, int bins, double* out, void* workspace,
                                   void* stream) {
-    int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
-    if (rc == HM_OK && (bins < 1 || bins > HM_PAIRS_HIST_MAX_BINS || !edges || channel_mask < 0 || (channel_mask >> C) != 0)) rc = HM_EINVAL;
+    const int rc = hm_rules::check_pairs_histogram(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, channel_mask, lower, upper,
+                                                   edges, bins, out, workspace);
     if (rc != HM_OK) return rc;
     PairsK k{};
     pairs_dist_fill(k, vals, stds, n_frames, n, C, lower, upper);

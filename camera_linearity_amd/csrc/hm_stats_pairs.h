@@ -1,7 +1,9 @@
 // hm_stats_pairs.h - what the all-pairs statistics (hm_stats.hip: hm_pairs_statistics) and the all-pairs distributions (hm_stats_hist.hip:
-// hm_pairs_minmax, hm_pairs_histogram) share on the host side: the kernels' argument block, the one argument check and the one fill.
+// hm_pairs_minmax, hm_pairs_histogram) share on the host side: the kernels' argument block and the one fill. Their argument rules are
+// hm_pairs_rules.h, shared with the host build.
 #pragma once
 #include "hm_common.h"
+#include "hm_pairs_rules.h"
 
 namespace hm {
 
@@ -15,19 +17,6 @@ struct PairsK {
     int32_t C, n_pairs, with_std;
     double lo[HM_MAX_CHANNELS], hi[HM_MAX_CHANNELS];        // apply_thresholds limits per channel (THR instantiations of the LDS kernel)
 };
-
-// the argument checks the three entry points share (hdrmerge.h: the statistics block's codes), in the host build's order
-inline int pairs_dist_check(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
-                            const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper,
-                            const void* out, const void* workspace) {
-    if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
-    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!aligned(vals[i], 8) || (stds && !aligned(stds[i], 8))) return HM_EALIGN;
-    for (int p = 0; p < n_pairs; ++p)
-        if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
-    return HM_OK;
-}
 
 inline void pairs_dist_fill(PairsK& k, const double* const* vals, const double* const* stds, int n_frames, int64_t n, int C,
                             const double* lower, const double* upper) {

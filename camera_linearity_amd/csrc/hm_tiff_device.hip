@@ -20,6 +20,7 @@
 // allocation, no host synchronisation.
 #include "hm_common.h"
 #include "hm_tiff_lzw_body.h"
+#include "hm_tiff_rules.h"
 
 static_assert(int(hm_lzw::kEinval) == int(HM_EINVAL) && int(hm_lzw::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_body.h repeats two codes of hdrmerge.h");
 
@@ -27,7 +28,6 @@ namespace {
 
 constexpr int kLzwWaves = 2;                 // waves (= strips) per workgroup of the decoder
 constexpr int kStageBytes = 16 * 1024;       // strips up to this size are decoded in LDS (a 4096-wide RGB row is 12 KiB)
-constexpr int64_t kMaxStripBytes = 1ll << 31;
 
 struct StripGeom {
     const uint8_t* file;
@@ -180,45 +180,24 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(const FinishGeom f) {
     }
 }
 
-// 0 = fine; fills the derived geometry
-int check_geometry(int n_strips, int compression, int predictor, int rows_per_strip, int height, int width, int samples,
-                   int bytes_per_sample, int color_mode, int* rps, int64_t* row_bytes, int64_t* strip_bytes) {
-    if (n_strips < 1 || rows_per_strip < 1 || height < 1 || width < 1) return HM_EINVAL;
-    if (predictor != 1 && predictor != 2) return HM_EINVAL;
-    if (color_mode != 0 && color_mode != 1) return HM_EINVAL;
-    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
-    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
-    if (bytes_per_sample != 1 && bytes_per_sample != 8) return HM_EUNSUPPORTED;
-    if (bytes_per_sample == 8 && (predictor == 2 || color_mode == 1)) return HM_EUNSUPPORTED;
-    *rps = rows_per_strip < height ? rows_per_strip : height;
-    if (n_strips != (height + *rps - 1) / *rps) return HM_ESHAPE;
-    *row_bytes = static_cast<int64_t>(width) * samples * bytes_per_sample;
-    if (*row_bytes > kMaxStripBytes / *rps) return HM_ESHAPE;
-    *strip_bytes = *row_bytes * *rps;
-    return HM_OK;
-}
-
 }  // namespace
 
 extern "C" size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > kMaxStripBytes) return 0;
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
+    return hm_rules::tiff_decode_workspace_bytes(n_strips, strip_bytes, compression);
 }
 
 extern "C" int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts,
                                      int n_strips, int compression, int predictor, int rows_per_strip, int height, int width,
                                      int samples, int bytes_per_sample, int color_mode, void* dst, int64_t* strip_status,
                                      void* workspace, void* stream) {
-    if (!file || !strip_offsets || !strip_counts || !dst || !strip_status || file_len < 0) return HM_EINVAL;
-    int rps = 0;
-    int64_t row_bytes = 0, strip_bytes = 0;
-    const int rc = check_geometry(n_strips, compression, predictor, rows_per_strip, height, width, samples, bytes_per_sample, color_mode,
-                                  &rps, &row_bytes, &strip_bytes);
+    hm_rules::TiffDecodeGeom geom;
+    const int rc = hm_rules::check_tiff_decode(file, file_len, strip_offsets, strip_counts, n_strips, compression, predictor, rows_per_strip,
+                                               height, width, samples, bytes_per_sample, color_mode, dst, strip_status, workspace, geom);
     if (rc != HM_OK) return rc;
-    if (compression == 5 && !workspace) return HM_EINVAL;
+    const int64_t strip_bytes = geom.strip_bytes;
     hipStream_t st = hm::as_stream(stream);
     FinishGeom f;
-    f.g = StripGeom{file, file_len, strip_offsets, strip_counts, n_strips, rps, height, width, row_bytes, strip_bytes, strip_status,
+    f.g = StripGeom{file, file_len, strip_offsets, strip_counts, n_strips, geom.rps, height, width, geom.row_bytes, strip_bytes, strip_status,
                     static_cast<uint8_t*>(workspace)};
     f.compression = compression;
     f.predictor = predictor;

@@ -26,15 +26,15 @@
 // n_strips * pitch = hm_tiff_encode_payload_bytes <= payload_cap. No atomics, no allocation, no host synchronisation.
 #include "hm_common.h"
 #include "hm_tiff_lzw_enc_body.h"
+#include "hm_tiff_rules.h"
 
 static_assert(int(hm_lzw_enc::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_enc_body.h repeats a code of hdrmerge.h");
 
 namespace {
 
-constexpr int64_t kMaxStripBytes = hm_lzw_enc::kMaxInput;      // 2^31 - 1
 constexpr int kMaxStripGrid = 1 << 16;       // workgroups of the per-strip kernels: an image of more strips (up to 2^31 - 1 one-row strips) loops
 
-__host__ __device__ inline int64_t round16(int64_t x) { return (x + 15) & ~int64_t{15}; }
+using hm_rules::round16;
 
 struct EncGeom {
     const uint8_t* src;
@@ -229,66 +229,29 @@ __global__ __launch_bounds__(256) void compact_kernel(const EncGeom g) {
     }
 }
 
-// 0 = fine; fills the derived geometry. Every check of hm_tiff_encode_strips that needs no pointer
-int check_geometry(int src_kind, double divisor, int height, int width, int samples, int rows_per_strip, int compression, int predictor,
-                   EncGeom* g) {
-    if (height < 1 || width < 1 || rows_per_strip < 1) return HM_EINVAL;
-    if (predictor != 1 && predictor != 2) return HM_EINVAL;
-    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
-    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
-    if (src_kind < 0 || src_kind > 2) return HM_EUNSUPPORTED;
-    if (src_kind == 2 && !(divisor > 0.0 && divisor <= 1.7976931348623157e308)) return HM_EINVAL;
-    g->out_bps = src_kind == 1 ? 8 : 1;
-    if (g->out_bps == 8 && predictor == 2) return HM_EUNSUPPORTED;
-    g->rps = rows_per_strip < height ? rows_per_strip : height;
-    g->n_strips = (height + g->rps - 1) / g->rps;
-    g->row_bytes = static_cast<int64_t>(width) * samples * g->out_bps;
-    if (g->row_bytes > kMaxStripBytes / g->rps) return HM_ESHAPE;
-    g->strip_bytes = g->row_bytes * g->rps;
-    g->kind = src_kind;
-    g->divisor = divisor;
-    g->height = height;
-    g->width = width;
-    g->spp = samples;
-    g->compression = compression;
-    g->predictor = predictor;
-    g->bound = hm_lzw_enc::bound(g->strip_bytes);
-    g->in_pitch = round16(g->strip_bytes);
-    g->out_pitch = round16(g->bound);
-    return HM_OK;
-}
-
 }  // namespace
 
-extern "C" int64_t hm_tiff_encode_bound(int64_t strip_bytes) {
-    if (strip_bytes < 1) return HM_EINVAL;
-    if (strip_bytes > kMaxStripBytes) return HM_ESHAPE;
-    return hm_lzw_enc::bound(strip_bytes);
-}
+extern "C" int64_t hm_tiff_encode_bound(int64_t strip_bytes) { return hm_rules::tiff_encode_bound(strip_bytes); }
 
 extern "C" size_t hm_tiff_encode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > kMaxStripBytes) return 0;
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(round16(strip_bytes) + round16(hm_lzw_enc::bound(strip_bytes)));
+    return hm_rules::tiff_encode_workspace_bytes(n_strips, strip_bytes, compression);
 }
 
 extern "C" size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if ((compression != 1 && compression != 5) || n_strips < 1 || strip_bytes < 1 || strip_bytes > kMaxStripBytes) return 0;
-    if (compression == 1) return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(round16(hm_lzw_enc::bound(strip_bytes)));
+    return hm_rules::tiff_encode_payload_bytes(n_strips, strip_bytes, compression);
 }
 
 extern "C" int hm_tiff_encode_strips(const void* src, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
                                      int compression, int predictor, void* payload, int64_t payload_cap, void* strip_offsets,
                                      void* strip_counts, void* workspace, void* stream) {
-    if (!src || !payload || !strip_offsets || !strip_counts) return HM_EINVAL;
-    EncGeom g{};
-    const int rc = check_geometry(src_kind, divisor, height, width, samples, rows_per_strip, compression, predictor, &g);
+    hm_rules::TiffEncodeGeom v;
+    const int rc = hm_rules::check_tiff_encode(src, src_kind, divisor, height, width, samples, rows_per_strip, compression, predictor, payload,
+                                               payload_cap, strip_offsets, strip_counts, workspace, v);
     if (rc != HM_OK) return rc;
-    if (compression == 5 && !workspace) return HM_EINVAL;
-    if (payload_cap < 0 || static_cast<uint64_t>(payload_cap) < hm_tiff_encode_payload_bytes(g.n_strips, g.strip_bytes, compression)) return HM_ESHAPE;
-    if (!hm::aligned(payload, 16) || !hm::aligned(strip_offsets, 8) || !hm::aligned(strip_counts, 8) || !hm::aligned(src, src_kind == 0 ? 1 : 8) ||
-        (compression == 5 && !hm::aligned(workspace, 16)))
-        return HM_EALIGN;
+    EncGeom g{};
+    g.kind = src_kind; g.divisor = divisor; g.height = height; g.width = width; g.spp = samples;
+    g.rps = v.rps; g.n_strips = v.n_strips; g.compression = compression; g.predictor = predictor; g.out_bps = v.out_bps;
+    g.row_bytes = v.row_bytes; g.strip_bytes = v.strip_bytes; g.in_pitch = v.in_pitch; g.out_pitch = v.out_pitch; g.bound = v.bound;
     g.src = static_cast<const uint8_t*>(src);
     g.payload = static_cast<uint8_t*>(payload);
     g.offsets = static_cast<int64_t*>(strip_offsets);

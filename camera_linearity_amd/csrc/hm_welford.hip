@@ -28,6 +28,7 @@
 // a non-zero f/n >= 2^-540 dwarfs it and a run of f = 0 shrinks it by n0/n >= 2^-40 at most - so a non-zero delta = f - m is >= 2^-684.
 // A lane whose state or table is outside those ranges (or not finite) redoes its elements with the full division (welford_exact).
 #include "hm_common.h"
+#include "hm_producer_rules.h"
 
 namespace hm {
 
@@ -185,17 +186,11 @@ using namespace hm;
 
 extern "C" int hm_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* icrf,
                                  double* mean, double* m2, int64_t n_elems, int C, void* stream) {
-    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || count_before < 0 || n_elems < 0) return HM_EINVAL;
-    if (count_before > (int64_t{1} << 40)) return HM_EUNSUPPORTED;       // div_by_count's acceptance test assumes n << 2^53
-    if (C < 1 || C > HM_MAX_CHANNELS) return HM_ESHAPE;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (n_frames == 0 || n_elems == 0) return HM_OK;
-    if (!frames || !mean) return HM_EINVAL;
+    bool empty;
+    const int rc = hm_rules::check_welford_update(frames, n_frames, count_before, mean, n_elems, C, empty);
+    if (rc != HM_OK || empty) return rc;
     WelfordK k{};
-    for (int i = 0; i < n_frames; ++i) {
-        if (!frames[i]) return HM_EINVAL;
-        k.frame[i] = static_cast<const uint8_t*>(frames[i]);
-    }
+    for (int i = 0; i < n_frames; ++i) k.frame[i] = static_cast<const uint8_t*>(frames[i]);
     k.icrf = icrf; k.mean = mean; k.m2 = m2; k.n = n_elems; k.n_frames = n_frames; k.C = C;
     k.count0 = static_cast<double>(count_before);
     for (int i = 0; i < n_frames; ++i) k.rcp[i] = 1.0 / (k.count0 + static_cast<double>(i + 1));
@@ -207,10 +202,9 @@ extern "C" int hm_welford_update(const void* const* frames, int n_frames, int64_
 
 extern "C" int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uint8_t* out_mean,
                                    uint8_t* out_std, int64_t n_elems, void* stream) {
-    if (n_elems < 0 || count < 1) return HM_EINVAL;
-    if (n_elems == 0) return HM_OK;
-    if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
-    if (out_std && count < 2) return HM_EINVAL;            // m2 / (n - 1) needs two frames (:214)
+    bool empty;
+    const int rc = hm_rules::check_welford_finalize(mean, m2, count, out_mean, out_std, n_elems, empty);
+    if (rc != HM_OK || empty) return rc;
     const unsigned grid = stream_grid(n_elems, 256, 8);
     hipLaunchKernelGGL(k_welford_finalize, dim3(grid), dim3(256), 0, as_stream(stream), mean, m2,
                        static_cast<double>(count), out_mean, out_std, n_elems);

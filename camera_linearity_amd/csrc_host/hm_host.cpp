@@ -14,6 +14,10 @@
 // hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
 #include "hdrmerge.h"
 #include "../csrc/hm_merge_rules.h"
+#include "../csrc/hm_calibration_rules.h"
+#include "../csrc/hm_pairs_rules.h"
+#include "../csrc/hm_producer_rules.h"
+#include "../csrc/hm_tiff_rules.h"
 #include "../csrc/hm_tiff_lzw_body.h"
 #include "../csrc/hm_tiff_lzw_enc_body.h"
 
@@ -969,12 +973,8 @@ size_t hm_pairs_statistics_workspace_bytes(int) { return 64; }
 int hm_pairs_statistics(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
                         const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
                         void* workspace, void*) {
-    if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
-    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!aligned8(vals[i]) || (stds && !aligned8(stds[i]))) return HM_EALIGN;
-    for (int p = 0; p < n_pairs; ++p)
-        if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
+    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    if (rc != HM_OK) return rc;
     if (lower)                                                                                           // exposure_series.py:437-441, in place
         for (int i = 0; i < n_frames; ++i)
             hm_apply_thresholds(const_cast<double*>(vals[i]), stds ? const_cast<double*>(stds[i]) : nullptr, lower, upper, n, C, nullptr);
@@ -1024,18 +1024,6 @@ int hm_channel_histogram(const double* val, const double* std_, int64_t n, int C
 // ---- distributions of all exposure pairs (hm_pairs_minmax / hm_pairs_histogram): the difference terms of diff_terms() on the values as
 // read through the thresholds, hm_channel_minmax's / hm_channel_histogram's counting rule, weighted sums added in index order
 namespace {
-int pairs_dist_check(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
-                     const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, const void* out,
-                     const void* workspace) {
-    if (!vals || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
-    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
-    for (int i = 0; i < n_frames; ++i) if (!aligned8(vals[i]) || (stds && !aligned8(stds[i]))) return HM_EALIGN;
-    for (int p = 0; p < n_pairs; ++p)
-        if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
-    return HM_OK;
-}
-
 // element e of pair (x, y): loaded, thresholded as read (a value outside its channel's limits is NaN with its std), differenced
 struct PairElems {
     const double* x; const double* sx; const double* y; const double* sy;
@@ -1057,7 +1045,7 @@ size_t hm_pairs_histogram_workspace_bytes(int, int, int) { return 64; }
 int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
                     const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
                     void* workspace, void*) {
-    const int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
     if (rc != HM_OK) return rc;
 #pragma omp parallel for schedule(dynamic)
     for (int p = 0; p < n_pairs; ++p) {
@@ -1082,8 +1070,8 @@ int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_
 int hm_pairs_histogram(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
                        const double* multipliers, int n_pairs, int64_t n, int C, int channel_mask, const double* lower, const double* upper,
                        const double* edges, int bins, double* out, void* workspace, void*) {
-    int rc = pairs_dist_check(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
-    if (rc == HM_OK && (bins < 1 || bins > HM_PAIRS_HIST_MAX_BINS || !edges || channel_mask < 0 || (channel_mask >> C) != 0)) rc = HM_EINVAL;
+    const int rc = hm_rules::check_pairs_histogram(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, channel_mask, lower, upper,
+                                                   edges, bins, out, workspace);
     if (rc != HM_OK) return rc;
 #pragma omp parallel for schedule(dynamic)
     for (int p = 0; p < n_pairs; ++p) {
@@ -1122,13 +1110,9 @@ int hm_pairs_histogram(const double* const* vals, const double* const* stds, int
 // m2 += delta * (f - mean) (:205-208), f = icrf[dn, c] (:200-201) or dn / 255 (:203)
 int hm_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
                       int64_t n_elems, int C, void*) {
-    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || count_before < 0 || n_elems < 0) return HM_EINVAL;
-    if (count_before > (int64_t{1} << 40)) return HM_EUNSUPPORTED;              // (the device build's limit: one ABI, one answer)
-    if (C < 1 || C > HM_MAX_CHANNELS) return HM_ESHAPE;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (n_frames == 0 || n_elems == 0) return HM_OK;
-    if (!frames || !mean) return HM_EINVAL;
-    for (int k = 0; k < n_frames; ++k) if (!frames[k]) return HM_EINVAL;
+    bool empty;
+    const int rc = hm_rules::check_welford_update(frames, n_frames, count_before, mean, n_elems, C, empty);
+    if (rc != HM_OK || empty) return rc;
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n_elems; ++e) {
         const int c = static_cast<int>(e % C);
@@ -1155,10 +1139,9 @@ static inline uint8_t round_to_u8(double x) {
 }
 
 int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uint8_t* out_mean, uint8_t* out_std, int64_t n_elems, void*) {
-    if (n_elems < 0 || count < 1) return HM_EINVAL;
-    if (n_elems == 0) return HM_OK;
-    if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
-    if (out_std && count < 2) return HM_EINVAL;                                   // m2 / (n - 1) needs two frames (:214)
+    bool empty;
+    const int rc = hm_rules::check_welford_finalize(mean, m2, count, out_mean, out_std, n_elems, empty);
+    if (rc != HM_OK || empty) return rc;
     const double denom = static_cast<double>(count) - 1.0, root_n = std::sqrt(static_cast<double>(count));
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n_elems; ++e) {
@@ -1177,12 +1160,9 @@ int64_t hm_noise_profile_algorithmic_bytes(int n_frames, int64_t n_elems, int C)
 }
 int hm_noise_profile_update(const void* const* frames, int n_frames, const uint8_t* mean, int64_t n_elems, int C, int64_t* profiles,
                             void*, int64_t workspace_bytes, void*) {
-    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || n_elems < 0 || C < 1 || workspace_bytes < 0) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (!frames || !mean || !profiles) return HM_EINVAL;
-    for (int k = 0; k < n_frames; ++k) if (!frames[k]) return HM_EINVAL;
-    if (n_frames == 0 || n_elems == 0) return HM_OK;
+    bool empty;
+    const int rc = hm_rules::check_noise_profile_update(frames, n_frames, mean, n_elems, C, profiles, workspace_bytes, empty);
+    if (rc != HM_OK || empty) return rc;
 #pragma omp parallel
     {
         std::vector<int64_t> loc(static_cast<size_t>(256) * 256 * C, 0);
@@ -1201,8 +1181,8 @@ int hm_noise_profile_update(const void* const* frames, int n_frames, const uint8
 // linspace(0, 1, 256) (the caller's table), mean = sum(h * edges) / sum(h), std = sqrt(sum((edges - mean)^2 h) / sum(h));
 // an empty row gives 0 / 0 = NaN (math.sqrt of NaN: the documented deviation of the Python layer)
 int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void*) {
-    if (!profiles || !edges || !out_std || C < 1) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    const int rc = hm_rules::check_noise_profile_std(profiles, C, edges, out_std);
+    if (rc != HM_OK) return rc;
 #pragma omp parallel for schedule(static)
     for (int t = 0; t < 256 * C; ++t) {
         const int i = t / C, c = t % C;
@@ -1226,8 +1206,8 @@ int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, do
 // clean_data_edges, video_processing.py:12-74: per (row i, channel c) the four integer passes centred at i, in order, in place
 static inline int64_t floordiv2(int64_t x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
 int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
-    if (!profiles || C < 1) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    const int rc = hm_rules::check_noise_profile_clean_edges(profiles, C);
+    if (rc != HM_OK) return rc;
 #pragma omp parallel for schedule(static)
     for (int t = 0; t < 256 * C; ++t) {
         const int i = t / C, c = t % C;
@@ -1271,8 +1251,8 @@ static inline bool kde_load(const double* val, const double* std_, int64_t e, do
     return ok;
 }
 int hm_kde_moments(const double* val, const double* std_, int64_t n_elems, int C, int channel, double* moments, void*, int64_t workspace_bytes, void*) {
-    if (!val || !moments || n_elems < 0 || C < 1 || channel < 0 || channel >= C || workspace_bytes < 0) return HM_EINVAL;
-    if (n_elems % C != 0) return HM_ESHAPE;
+    const int rc = hm_rules::check_kde_moments(val, n_elems, C, channel, moments, nullptr, workspace_bytes, false);
+    if (rc != HM_OK) return rc;
     const int64_t n = n_elems / C;
     std::vector<double> part(static_cast<size_t>(kKdeSlices) * 10);
 #pragma omp parallel for schedule(static)
@@ -1314,11 +1294,9 @@ int hm_kde_moments(const double* val, const double* std_, int64_t n_elems, int C
 }
 int hm_kde_evaluate(const double* val, const double* std_, int64_t n_elems, int C, int channel, double h, double scale, const double* grid,
                     int m, double* out, void*, int64_t workspace_bytes, void*) {
-    if (!val || n_elems < 0 || C < 1 || channel < 0 || channel >= C || workspace_bytes < 0) return HM_EINVAL;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (m < 0 || !(h > 0.0) || !std::isfinite(h) || !std::isfinite(scale)) return HM_EINVAL;
-    if (m == 0) return HM_OK;
-    if (!grid || !out) return HM_EINVAL;
+    bool empty;
+    const int rc = hm_rules::check_kde_evaluate(val, n_elems, C, channel, h, scale, grid, m, out, nullptr, workspace_bytes, false, empty);
+    if (rc != HM_OK || empty) return rc;
     const int64_t n = n_elems / C;
     std::vector<double> u, w;                                        // the counted elements, u = x / h
     for (int64_t i = 0; i < n; ++i) {
@@ -1351,12 +1329,9 @@ size_t hm_linearity_energy_workspace_bytes(int64_t, int, int) { return 0; }
 int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exposures, const double* icrf, const uint8_t* valid,
                         int n_candidates, int lower, int upper, int use_relative, int64_t n_pixels, int n_frames,
                         double* out_pairs, double* out_energy, void*, void*) {
-    if (n_candidates < 0 || n_pixels < 0) return HM_EINVAL;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (n_candidates == 0) return HM_OK;
-    if (n_candidates > 65535) return HM_EUNSUPPORTED;
-    if (!dn || !exposures || !icrf || !out_energy) return HM_EINVAL;
+    bool empty;
+    const int rc = hm_rules::check_linearity_energy(dn, exposures, icrf, n_candidates, lower, upper, n_pixels, n_frames, out_energy, empty);
+    if (rc != HM_OK || empty) return rc;
     const int N = n_frames, pairs = N * (N - 1) / 2;
     std::vector<int> pi(pairs), pj(pairs);
     { int p = 0; for (int i = 0; i < N; ++i) for (int j = i + 1; j < N; ++j, ++p) { pi[p] = i; pj[p] = j; } }
@@ -1435,15 +1410,11 @@ int hm_de_generation(double* population, double* energies, double* trial, double
                      const double* upper_limits, const uint8_t* dn, const double* std_, const double* exposures, int64_t n_pixels,
                      int n_frames, int lower, int upper, int pop_size, int n_params, int64_t seed, int64_t max_generations,
                      double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit, void*, void*) {
-    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
-    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;
-    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
-    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
-    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !exposures) return HM_EINVAL;
-    if (status[HM_DE_STOP] != 0) return HM_OK;                            // after the stop flag a generation is a no-op
+    const int rc0 = hm_rules::check_de_generation(1, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca,
+                                                  lower_limits, upper_limits, dn, exposures, n_pixels, n_frames, lower, upper, pop_size,
+                                                  n_params, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    if (rc0 != HM_OK) return rc0;
+    if (status[HM_DE_STOP] != 0) return HM_OK;                            // this build's own (status is host memory here): after the stop flag a generation is a no-op
     const int S = pop_size, P = n_params;
     const int64_t g = status[HM_DE_GENERATION];
     const uint64_t key = de_mix64(static_cast<uint64_t>(seed) ^ de_mix64(static_cast<uint64_t>(g)));
@@ -1531,19 +1502,11 @@ int hm_de_generation_batch(int n_problems, double* population, double* energies,
                            const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size, int n_params,
                            int64_t max_generations, double mutation_lo, double mutation_hi, double recombination, double tol,
                            double energy_limit, void*, void*) {
-    if (n_problems < 1) return HM_EINVAL;
-    if (n_problems > HM_DE_MAX_PROBLEMS) return HM_ESHAPE;
-    if (pop_size < 4 || n_params < 1 || n_pixels < 0 || max_generations < 0) return HM_EINVAL;
-    if (pop_size > HM_DE_MAX_POP || n_params > HM_DE_MAX_PARAMS) return HM_ESHAPE;
-    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
-    if (n_problems * pop_size > 65535) return HM_EUNSUPPORTED;                // the HIP build's limit, kept so that both builds accept the same calls
-    if (lower < 0 || lower > 255 || upper < 0 || upper > 255) return HM_EINVAL;
-    if (!(mutation_lo >= 0.0 && mutation_lo <= mutation_hi && mutation_hi < 2.0)) return HM_EINVAL;
-    if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
-    if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
-    if (!mean_icrf || !pca || !lower_limits || !upper_limits || !dn || !seeds || !exposures) return HM_EINVAL;
-    for (int k = 0; k < n_problems; ++k)
-        if (!dn[k] || (std_ && !std_[k])) return HM_EINVAL;                   // stds for all problems or for none
+    const int rc0 = hm_rules::check_de_generation_batch(n_problems, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf,
+                                                        pca, lower_limits, upper_limits, dn, std_, seeds, exposures, n_pixels, n_frames, lower,
+                                                        upper, pop_size, n_params, max_generations, mutation_lo, mutation_hi, recombination,
+                                                        tol, energy_limit);
+    if (rc0 != HM_OK) return rc0;
     const int64_t S = pop_size, P = n_params;
     for (int64_t k = 0; k < n_problems; ++k) {
         const int rc = hm_de_generation(population + k * S * P, energies + k * S, trial + k * S * P, trial_energies + k * S,
@@ -1570,28 +1533,19 @@ struct TiffSerialEmit {
 };
 
 size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > (1ll << 31)) return 0;
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
+    return hm_rules::tiff_decode_workspace_bytes(n_strips, strip_bytes, compression);
 }
 
 int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts, int n_strips,
                           int compression, int predictor, int rows_per_strip, int height, int width, int samples, int bytes_per_sample,
                           int color_mode, void* dst_, int64_t* strip_status, void* workspace, void* /*stream*/) {
     static_assert(int(hm_lzw::kEinval) == int(HM_EINVAL) && int(hm_lzw::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_body.h repeats two codes of hdrmerge.h");
-    if (!file || !strip_offsets || !strip_counts || !dst_ || !strip_status || file_len < 0) return HM_EINVAL;
-    if (n_strips < 1 || rows_per_strip < 1 || height < 1 || width < 1) return HM_EINVAL;
-    if (predictor != 1 && predictor != 2) return HM_EINVAL;
-    if (color_mode != 0 && color_mode != 1) return HM_EINVAL;
-    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
-    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
-    if (bytes_per_sample != 1 && bytes_per_sample != 8) return HM_EUNSUPPORTED;
-    if (bytes_per_sample == 8 && (predictor == 2 || color_mode == 1)) return HM_EUNSUPPORTED;
-    const int rps = std::min(rows_per_strip, height);
-    if (n_strips != (height + rps - 1) / rps) return HM_ESHAPE;
-    const int64_t row_bytes = static_cast<int64_t>(width) * samples * bytes_per_sample;
-    if (row_bytes > (1ll << 31) / rps) return HM_ESHAPE;
-    if (compression == 5 && !workspace) return HM_EINVAL;
-    const int64_t strip_bytes = row_bytes * rps;
+    hm_rules::TiffDecodeGeom geom;
+    const int rc = hm_rules::check_tiff_decode(file, file_len, strip_offsets, strip_counts, n_strips, compression, predictor, rows_per_strip,
+                                               height, width, samples, bytes_per_sample, color_mode, dst_, strip_status, workspace, geom);
+    if (rc != HM_OK) return rc;
+    const int rps = geom.rps;
+    const int64_t row_bytes = geom.row_bytes, strip_bytes = geom.strip_bytes;
     const int spp = samples, bps = bytes_per_sample, ospp = color_mode == 1 ? 3 : samples;
     const int64_t out_row_bytes = static_cast<int64_t>(width) * ospp * bps;
     uint8_t* dst = static_cast<uint8_t*>(dst_);
@@ -1640,55 +1594,33 @@ int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* 
  * csrc/hm_tiff_encode.hip, with HOST pointers - the encoder body both builds share (csrc/hm_tiff_lzw_enc_body.h) with its serial ops,
  * one strip per OpenMP iteration. tiff_io.imwrite(compression=5) writes through it, and the GPU tests compare the device call with it.
  * ------------------------------------------------------------------------------------------ */
-static inline int64_t tiff_round16(int64_t x) { return (x + 15) & ~int64_t{15}; }
-
-int64_t hm_tiff_encode_bound(int64_t strip_bytes) {
-    if (strip_bytes < 1) return HM_EINVAL;
-    if (strip_bytes > hm_lzw_enc::kMaxInput) return HM_ESHAPE;
-    return hm_lzw_enc::bound(strip_bytes);
-}
+int64_t hm_tiff_encode_bound(int64_t strip_bytes) { return hm_rules::tiff_encode_bound(strip_bytes); }
 
 size_t hm_tiff_encode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if (compression != 5 || n_strips < 1 || strip_bytes < 1 || strip_bytes > hm_lzw_enc::kMaxInput) return 0;
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(tiff_round16(strip_bytes) + tiff_round16(hm_lzw_enc::bound(strip_bytes)));
+    return hm_rules::tiff_encode_workspace_bytes(n_strips, strip_bytes, compression);
 }
 
 size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes, int compression) {
-    if ((compression != 1 && compression != 5) || n_strips < 1 || strip_bytes < 1 || strip_bytes > hm_lzw_enc::kMaxInput) return 0;
-    if (compression == 1) return static_cast<size_t>(n_strips) * static_cast<size_t>(strip_bytes);
-    return static_cast<size_t>(n_strips) * static_cast<size_t>(tiff_round16(hm_lzw_enc::bound(strip_bytes)));
+    return hm_rules::tiff_encode_payload_bytes(n_strips, strip_bytes, compression);
 }
 
 int hm_tiff_encode_strips(const void* src_, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
                           int compression, int predictor, void* payload_, int64_t payload_cap, void* strip_offsets, void* strip_counts,
                           void* workspace, void* /*stream*/) {
     static_assert(int(hm_lzw_enc::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_enc_body.h repeats a code of hdrmerge.h");
-    if (!src_ || !payload_ || !strip_offsets || !strip_counts) return HM_EINVAL;
-    if (height < 1 || width < 1 || rows_per_strip < 1) return HM_EINVAL;
-    if (predictor != 1 && predictor != 2) return HM_EINVAL;
-    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
-    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
-    if (src_kind < 0 || src_kind > 2) return HM_EUNSUPPORTED;
-    if (src_kind == 2 && !(divisor > 0.0 && divisor <= std::numeric_limits<double>::max())) return HM_EINVAL;
-    const int bps = src_kind == 1 ? 8 : 1;
-    if (bps == 8 && predictor == 2) return HM_EUNSUPPORTED;
-    const int rps = std::min(rows_per_strip, height);
-    const int n_strips = (height + rps - 1) / rps;
-    const int64_t row_bytes = static_cast<int64_t>(width) * samples * bps;
-    if (row_bytes > hm_lzw_enc::kMaxInput / rps) return HM_ESHAPE;
-    const int64_t strip_bytes = row_bytes * rps;
-    if (compression == 5 && !workspace) return HM_EINVAL;
-    if (payload_cap < 0 || static_cast<uint64_t>(payload_cap) < hm_tiff_encode_payload_bytes(n_strips, strip_bytes, compression)) return HM_ESHAPE;
-    auto al = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
-    if (!al(payload_, 16) || !al(strip_offsets, 8) || !al(strip_counts, 8) || !al(src_, src_kind == 0 ? 1 : 8) || (compression == 5 && !al(workspace, 16)))
-        return HM_EALIGN;
+    hm_rules::TiffEncodeGeom geom;
+    const int rc = hm_rules::check_tiff_encode(src_, src_kind, divisor, height, width, samples, rows_per_strip, compression, predictor, payload_,
+                                               payload_cap, strip_offsets, strip_counts, workspace, geom);
+    if (rc != HM_OK) return rc;
+    const int rps = geom.rps, n_strips = geom.n_strips;
+    const int64_t row_bytes = geom.row_bytes, strip_bytes = geom.strip_bytes;
     const uint8_t* src = static_cast<const uint8_t*>(src_);
     uint8_t* payload = static_cast<uint8_t*>(payload_);
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     int64_t* offsets = static_cast<int64_t*>(strip_offsets);
     int64_t* counts = static_cast<int64_t*>(strip_counts);
     const int spp = samples;
-    const int64_t bound = hm_lzw_enc::bound(strip_bytes), in_pitch = tiff_round16(strip_bytes), out_pitch = tiff_round16(bound);
+    const int64_t bound = geom.bound, in_pitch = geom.in_pitch, out_pitch = geom.out_pitch;
 #pragma omp parallel for schedule(dynamic)
     for (int s = 0; s < n_strips; ++s) {
         const int rows = std::min(rps, height - s * rps);
@@ -1727,7 +1659,7 @@ int hm_tiff_encode_strips(const void* src_, int src_kind, double divisor, int he
     int64_t total = 0;
     for (int s = 0; s < n_strips; ++s) {
         offsets[s] = total;
-        total += counts[s] > 0 ? tiff_round16(counts[s]) : 0;
+        total += counts[s] > 0 ? hm_rules::round16(counts[s]) : 0;
     }
     offsets[n_strips] = total;
 #pragma omp parallel for schedule(dynamic)
@@ -1735,7 +1667,7 @@ int hm_tiff_encode_strips(const void* src_, int src_kind, double divisor, int he
         if (counts[s] <= 0) continue;
         uint8_t* out = payload + offsets[s];
         memcpy(out, ws + n_strips * in_pitch + s * out_pitch, static_cast<size_t>(counts[s]));
-        memset(out + counts[s], 0, static_cast<size_t>(tiff_round16(counts[s]) - counts[s]));       // the gap: zeros, never stale memory
+        memset(out + counts[s], 0, static_cast<size_t>(hm_rules::round16(counts[s]) - counts[s]));       // the gap: zeros, never stale memory
     }
     return HM_OK;
 }

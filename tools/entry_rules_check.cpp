@@ -1,0 +1,188 @@
+// entry_rules_check.cpp - the shared argument rules of the TIFF, calibration, producer and all-pairs entries
+// (camera_linearity_amd/csrc/hm_tiff_rules.h, hm_calibration_rules.h, hm_producer_rules.h, hm_pairs_rules.h) under AddressSanitizer /
+// UBSan: every per-frame, per-problem and per-pair array is a heap block of EXACTLY the count passed, at the smallest and the largest
+// counts, and the NULL cases - a rule that reads one entry too many, or looks through a pointer it was to refuse, stops the program.
+// A development step for whoever changes those headers: a stand-alone program, not part of the library, the package or the test suite,
+// and it needs no GPU.
+//
+// Build and run (one command line):
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Icamera_linearity_amd/csrc
+//       tools/entry_rules_check.cpp -o /tmp/entry_rules_check && /tmp/entry_rules_check
+#include <cstdio>
+#include <limits>
+#include <vector>
+#include "hm_calibration_rules.h"
+#include "hm_pairs_rules.h"
+#include "hm_producer_rules.h"
+#include "hm_tiff_rules.h"
+
+namespace {
+
+int failures = 0;
+void expect(const char* what, long long got, long long want) {
+    if (got != want) { std::printf("FAIL %s: %lld, expected %lld\n", what, got, want); ++failures; }
+}
+
+// addresses that are never read: the rules look at pointers, not through them (only the per-frame / per-problem / per-pair arrays are read)
+template <class T> T* fake(uintptr_t a) { return reinterpret_cast<T*>(a); }
+const double kNaN = std::numeric_limits<double>::quiet_NaN();
+
+void producers() {
+    using namespace hm_rules;
+    bool empty;
+    double* mean = fake<double>(0x1000);
+    for (int n : {1, 2, HM_MAX_FRAMES}) {
+        std::vector<const void*> frames(n, fake<void>(0x2000));
+        expect("welford", check_welford_update(frames.data(), n, 0, mean, 12, 3, empty), HM_OK);
+        expect("welford, at the count limit", check_welford_update(frames.data(), n, kWelfordMaxCount, mean, 12, 3, empty), HM_OK);
+        expect("welford, beyond it", check_welford_update(frames.data(), n, kWelfordMaxCount + 1, mean, 12, 3, empty), HM_EUNSUPPORTED);
+        expect("welford, too many frames", check_welford_update(frames.data(), HM_MAX_FRAMES + 1, 0, mean, 12, 3, empty), HM_EINVAL);
+        expect("welford, negative frames", check_welford_update(frames.data(), -1, 0, mean, 12, 3, empty), HM_EINVAL);
+        expect("noise", check_noise_profile_update(frames.data(), n, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_OK);
+        expect("noise, too many frames",
+               check_noise_profile_update(frames.data(), HM_MAX_FRAMES + 1, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_EINVAL);
+        frames[n - 1] = nullptr;
+        expect("welford, last frame NULL", check_welford_update(frames.data(), n, 0, mean, 12, 3, empty), HM_EINVAL);
+        expect("noise, last frame NULL", check_noise_profile_update(frames.data(), n, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_EINVAL);
+    }
+    expect("welford, no frames", check_welford_update(nullptr, 0, 0, nullptr, 12, 3, empty), HM_OK);
+    expect("welford, no frames: empty", empty, 1);
+    expect("welford, frames NULL", check_welford_update(nullptr, 2, 0, mean, 12, 3, empty), HM_EINVAL);
+    expect("welford, C = 0", check_welford_update(nullptr, 2, 0, mean, 12, 0, empty), HM_ESHAPE);
+    expect("noise, C = 0", check_noise_profile_update(nullptr, 2, nullptr, 12, 0, nullptr, 0, empty), HM_EINVAL);
+    expect("noise, frames NULL", check_noise_profile_update(nullptr, 2, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_EINVAL);
+    expect("finalize", check_welford_finalize(mean, mean, 2, fake<uint8_t>(0x5000), fake<uint8_t>(0x6000), 12, empty), HM_OK);
+    expect("finalize, all NULL", check_welford_finalize(nullptr, nullptr, 1, nullptr, nullptr, 12, empty), HM_OK);
+    expect("finalize, one frame", check_welford_finalize(mean, mean, 1, nullptr, fake<uint8_t>(0x6000), 12, empty), HM_EINVAL);
+    expect("noise std, NULL", check_noise_profile_std(nullptr, 3, nullptr, nullptr), HM_EINVAL);
+    expect("noise std, 5 channels", check_noise_profile_std(fake<int64_t>(0x4000), 5, mean, mean), HM_EUNSUPPORTED);
+    expect("clean edges, NULL", check_noise_profile_clean_edges(nullptr, 3), HM_EINVAL);
+    for (bool need_ws : {false, true}) {
+        expect("kde moments", check_kde_moments(mean, 12, 3, 1, mean, mean, 64, need_ws), HM_OK);
+        expect("kde moments, C = 0", check_kde_moments(mean, 12, 0, 0, mean, mean, 64, need_ws), HM_EINVAL);             // no division by C = 0
+        expect("kde moments, NULL workspace", check_kde_moments(mean, 12, 3, 1, mean, nullptr, 64, need_ws), need_ws ? HM_EINVAL : HM_OK);
+        expect("kde moments, NULL moments and a bad shape", check_kde_moments(mean, 11, 3, 1, nullptr, mean, 64, need_ws), need_ws ? HM_ESHAPE : HM_EINVAL);
+        expect("kde evaluate", check_kde_evaluate(mean, 12, 3, 1, 0.5, 1.0, mean, 4, mean, mean, 64, need_ws, empty), HM_OK);
+        expect("kde evaluate, C = 0", check_kde_evaluate(mean, 12, 0, 0, 0.5, 1.0, mean, 4, mean, mean, 64, need_ws, empty), HM_EINVAL);
+        expect("kde evaluate, NaN h", check_kde_evaluate(mean, 12, 3, 1, kNaN, 1.0, mean, 4, mean, mean, 64, need_ws, empty), HM_EINVAL);
+        expect("kde evaluate, no points", check_kde_evaluate(mean, 12, 3, 1, 0.5, 1.0, nullptr, 0, nullptr, mean, 64, need_ws, empty), HM_OK);
+        expect("kde evaluate, no points: empty", empty, 1);
+    }
+}
+
+void calibration() {
+    using namespace hm_rules;
+    bool empty;
+    double* d = fake<double>(0x1000);
+    uint8_t* b = fake<uint8_t>(0x2000);
+    int64_t* s = fake<int64_t>(0x3000);
+    expect("energy", check_linearity_energy(b, d, d, 2, 5, 250, 8, 2, d, empty), HM_OK);
+    expect("energy, 32 frames, 65535 candidates", check_linearity_energy(b, d, d, kEnergyMaxCandidates, 0, 255, 8, HM_MAX_FRAMES, d, empty), HM_OK);
+    expect("energy, 65536 candidates", check_linearity_energy(b, d, d, kEnergyMaxCandidates + 1, 0, 255, 8, 2, d, empty), HM_EUNSUPPORTED);
+    expect("energy, no candidates", check_linearity_energy(nullptr, nullptr, nullptr, 0, 0, 255, 8, 2, nullptr, empty), HM_OK);
+    expect("energy, no candidates: empty", empty, 1);
+    expect("energy, NULL", check_linearity_energy(nullptr, nullptr, nullptr, 2, 0, 255, 8, 2, nullptr, empty), HM_EINVAL);
+    auto de = [&](int pop, int params, int frames) {
+        return check_de_generation(1, d, d, d, d, d, b, s, d, d, d, d, b, d, 8, frames, 5, 250, pop, params, 10, 0.5, 1.0, 0.7, 0.01, 0.0);
+    };
+    expect("de", de(4, 1, 2), HM_OK);
+    expect("de, at the limits", de(HM_DE_MAX_POP, HM_DE_MAX_PARAMS, HM_MAX_FRAMES), HM_OK);
+    expect("de, population beyond", de(HM_DE_MAX_POP + 1, 1, 2), HM_ESHAPE);
+    expect("de, parameters beyond", de(4, HM_DE_MAX_PARAMS + 1, 2), HM_ESHAPE);
+    expect("de, NULL status", check_de_generation(1, d, d, d, d, d, b, nullptr, d, d, d, d, b, d, 8, 2, 5, 250, 4, 1, 10, 0.5, 1.0, 0.7, 0.01, 0.0),
+           HM_EINVAL);
+    expect("de, NaN limit", check_de_generation(1, d, d, d, d, d, b, s, d, d, d, d, b, d, 8, 2, 5, 250, 4, 1, 10, 0.5, 1.0, 0.7, 0.01, kNaN), HM_EINVAL);
+    for (int K : {1, 2, HM_DE_MAX_PROBLEMS}) {
+        std::vector<const uint8_t*> dn(K, b);
+        std::vector<const double*> sd(K, d);
+        std::vector<int64_t> seeds(K, 1);
+        auto batch = [&](int n_problems, int pop, const double* const* stds, const int64_t* sp) {
+            return check_de_generation_batch(n_problems, d, d, d, d, d, b, s, d, d, d, d, dn.data(), stds, sp, d, 8, 2, 5, 250, pop, 1, 10, 0.5, 1.0, 0.7,
+                                             0.01, 0.0);
+        };
+        expect("batch", batch(K, 4, sd.data(), seeds.data()), HM_OK);
+        expect("batch, no stds", batch(K, 4, nullptr, seeds.data()), HM_OK);
+        expect("batch, no seeds", batch(K, 4, sd.data(), nullptr), HM_EINVAL);
+        expect("batch, too many problems", batch(HM_DE_MAX_PROBLEMS + 1, 4, sd.data(), seeds.data()), HM_ESHAPE);
+        expect("batch, no problems", batch(0, 4, sd.data(), seeds.data()), HM_EINVAL);
+        expect("batch, candidates", batch(K, HM_DE_MAX_POP, sd.data(), seeds.data()), K * HM_DE_MAX_POP > kEnergyMaxCandidates ? HM_EUNSUPPORTED : HM_OK);
+        sd[K - 1] = nullptr;
+        expect("batch, last std NULL", batch(K, 4, sd.data(), seeds.data()), HM_EINVAL);
+        dn[K - 1] = nullptr;
+        expect("batch, last stack NULL", batch(K, 4, nullptr, seeds.data()), HM_EINVAL);
+    }
+}
+
+void pairs() {
+    using namespace hm_rules;
+    double* d = fake<double>(0x1000);
+    for (int n : {1, 2, HM_MAX_FRAMES})
+        for (int np : {1, 3, 4 * HM_PAIRS_MAX}) {
+            std::vector<const double*> vals(n, d), stds(n, d);
+            std::vector<int32_t> pi(np, 0), pj(np, n - 1);
+            std::vector<double> mult(np, 1.0);
+            auto stat = [&](int frames, int n_pairs, const double* const* sd) {
+                return check_pairs(vals.data(), sd, frames, pi.data(), pj.data(), mult.data(), n_pairs, 12, 3, nullptr, nullptr, d, d);
+            };
+            expect("pairs", stat(n, np, stds.data()), HM_OK);
+            expect("pairs, no stds", stat(n, np, nullptr), HM_OK);
+            expect("pairs, too many frames", stat(HM_MAX_FRAMES + 1, np, stds.data()), HM_EINVAL);
+            expect("pairs, no pairs", stat(n, 0, stds.data()), HM_EINVAL);
+            expect("pairs histogram", check_pairs_histogram(vals.data(), stds.data(), n, pi.data(), pj.data(), mult.data(), np, 12, 3, 7, nullptr, nullptr, d,
+                                                            HM_PAIRS_HIST_MAX_BINS, d, d), HM_OK);
+            expect("pairs histogram, bins beyond", check_pairs_histogram(vals.data(), stds.data(), n, pi.data(), pj.data(), mult.data(), np, 12, 3, 7, nullptr,
+                                                                         nullptr, d, HM_PAIRS_HIST_MAX_BINS + 1, d, d), HM_EINVAL);
+            pj[np - 1] = n;
+            expect("pairs, last index out of range", stat(n, np, stds.data()), HM_EINVAL);
+            stds[n - 1] = fake<double>(0x1004);
+            expect("pairs, last std misaligned", stat(n, np, stds.data()), HM_EALIGN);
+            vals[n - 1] = nullptr;
+            expect("pairs, last frame NULL", stat(n, np, stds.data()), HM_EINVAL);
+        }
+    expect("pairs, NULL arrays", check_pairs(nullptr, nullptr, 2, nullptr, nullptr, nullptr, 1, 12, 3, nullptr, nullptr, d, d), HM_EINVAL);
+    expect("pairs, C = 0", check_pairs(nullptr, nullptr, 2, nullptr, nullptr, nullptr, 1, 12, 0, nullptr, nullptr, d, d), HM_EINVAL);
+}
+
+void tiff() {
+    using namespace hm_rules;
+    uint8_t* b = fake<uint8_t>(0x1000);
+    int64_t* s = fake<int64_t>(0x2000);
+    TiffDecodeGeom dg;
+    expect("decode", check_tiff_decode(b, 48, s, s, 2, 5, 1, 2, 4, 4, 3, 1, 0, b, s, b, dg), HM_OK);
+    expect("decode: strip bytes", dg.strip_bytes, 24);
+    expect("decode, NULL", check_tiff_decode(nullptr, 48, nullptr, nullptr, 2, 5, 1, 2, 4, 4, 3, 1, 0, nullptr, nullptr, nullptr, dg), HM_EINVAL);
+    expect("decode, no rows per strip", check_tiff_decode(b, 48, s, s, 2, 5, 1, 0, 4, 4, 3, 1, 0, b, s, b, dg), HM_EINVAL);       // no division by rps = 0
+    const int big = std::numeric_limits<int>::max();
+    expect("decode, largest ints", check_tiff_decode(b, 48, s, s, 1, 1, 1, big, big, big, 4, 8, 0, b, s, b, dg), HM_ESHAPE);      // no overflow
+    expect("decode, a 2^31-byte strip", check_tiff_decode(b, 48, s, s, 2, 1, 1, 2, 4, 1 << 30, 1, 1, 0, b, s, nullptr, dg), HM_OK);
+    expect("decode, beyond it", check_tiff_decode(b, 48, s, s, 2, 1, 1, 2, 4, (1 << 30) + 1, 1, 1, 0, b, s, nullptr, dg), HM_ESHAPE);
+    TiffEncodeGeom eg;
+    const int64_t cap = std::numeric_limits<int64_t>::max();
+    expect("encode", check_tiff_encode(b, 0, 1.0, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_OK);
+    expect("encode: strips", eg.n_strips, 2);
+    expect("encode: pitches", eg.in_pitch + eg.out_pitch, round16(24) + round16(hm_lzw_enc::bound(24)));
+    expect("encode, NULL", check_tiff_encode(nullptr, 0, 1.0, 4, 4, 3, 2, 5, 1, nullptr, cap, nullptr, nullptr, nullptr, eg), HM_EINVAL);
+    expect("encode, no rows per strip", check_tiff_encode(b, 0, 1.0, 4, 4, 3, 0, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("encode, largest ints", check_tiff_encode(b, 1, 1.0, big, big, 4, big, 1, 1, b, cap, s, s, b, eg), HM_ESHAPE);
+    expect("encode, a (2^31 - 1)-byte strip", check_tiff_encode(b, 0, 1.0, 4, big, 1, 1, 1, 1, b, cap, s, s, nullptr, eg), HM_OK);
+    expect("encode, a 2^31-byte strip", check_tiff_encode(b, 0, 1.0, 4, 1 << 30, 1, 2, 1, 1, b, cap, s, s, nullptr, eg), HM_ESHAPE);
+    expect("encode, NaN divisor", check_tiff_encode(b, 2, kNaN, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("bound(0)", tiff_encode_bound(0), HM_EINVAL);
+    expect("bound(2^31)", tiff_encode_bound(int64_t{1} << 31), HM_ESHAPE);
+    expect("bound(2^31 - 1)", tiff_encode_bound(kTiffEncodeMaxStripBytes), hm_lzw_enc::bound(kTiffEncodeMaxStripBytes));
+    expect("payload, most strips of the largest size", tiff_encode_payload_bytes(big, kTiffEncodeMaxStripBytes, 5) > 0, 1);     // no overflow
+    expect("workspace, most strips of the largest size", tiff_encode_workspace_bytes(big, kTiffEncodeMaxStripBytes, 5) > 0, 1);
+    expect("decode workspace, at the limit", static_cast<long long>(tiff_decode_workspace_bytes(1, kTiffDecodeMaxStripBytes, 5)), 1ll << 31);
+    expect("decode workspace, beyond", static_cast<long long>(tiff_decode_workspace_bytes(1, kTiffDecodeMaxStripBytes + 1, 5)), 0);
+}
+
+}  // namespace
+
+int main() {
+    producers();
+    calibration();
+    pairs();
+    tiff();
+    std::printf(failures ? "%d FAILED\n" : "entry rules: all checks passed\n", failures);
+    return failures ? 1 : 0;
+}
