@@ -167,6 +167,12 @@ _SIGNATURES = {
     "hm_linearity_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    # the energy on uint16 DN stacks: ... n_frames, bit_depth, variant, out_pairs, out_energy, workspace, stream
+    "hm_linearity_energy_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    # (buf is a HOST array the call writes to: typed, so that nothing but a ctypes string buffer or None is ever passed for it)
+    "hm_linearity_energy_u16_describe": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char), C.c_int]),
     "hm_de_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hm_de_generation": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,

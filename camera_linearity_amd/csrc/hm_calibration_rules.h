@@ -1,11 +1,12 @@
-// hm_calibration_rules.h - the argument rules of the ICRF-calibration entries (hm_linearity_energy, hm_de_generation,
-// hm_de_generation_batch), written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build (hm_energy.hip,
-// hm_de.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it. Plain C++17 on hdrmerge.h: no HIP type.
+// hm_calibration_rules.h - the argument rules of the ICRF-calibration entries (hm_linearity_energy, hm_linearity_energy_u16,
+// hm_de_generation, hm_de_generation_batch), written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build
+// (hm_energy.hip, hm_energy_u16.hip, hm_de.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it.
+// Plain C++17 on hdrmerge.h: no HIP type.
 //
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call.
 //
 // What each build adds after the shared call, and why that changes no call's status:
-//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all three entries it follows rules that are HM_EINVAL too or
+//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all four entries it follows rules that are HM_EINVAL too or
 //           comes last. The energy launch refuses a frame count its pixel-major kernels are not instantiated for (HM_EUNSUPPORTED).
 //   host    hm_de_generation returns HM_OK at once when status[HM_DE_STOP] is set: there `status` is host memory. On the device build
 //           the kernels read the flag, so it cannot be a rule of this file.
@@ -27,6 +28,46 @@ inline int check_linearity_energy(const uint8_t* dn, const double* exposures, co
     if (n_candidates == 0) { empty = true; return HM_OK; }
     if (n_candidates > kEnergyMaxCandidates) return HM_EUNSUPPORTED;
     if (!dn || !exposures || !icrf || !out_energy) return HM_EINVAL;
+    return HM_OK;
+}
+
+// hm_linearity_energy_u16: uint16 DNs of bit_depth 9..16, candidate rows of 2^bit_depth float64.
+// variant 1 keeps the candidate's row in LDS. It fits where the row and the kernels' static reduction scratch - red[4][2 * 28] float64 of
+// the pixel-major kernel at 8 frames, the largest - together are at most the CU's 160 KiB: 4 KiB + scratch at 9 bits, 32 KiB at 12,
+// 128 KiB at 14; not at 15 bits (256 KiB) or 16 bits (512 KiB), where the row is gathered from global memory (variant 2).
+constexpr int64_t kEnergyLdsBytes = 160 * 1024;
+constexpr int64_t kEnergyU16ScratchBytes = 4 * 2 * 28 * 8;
+inline bool energy_u16_row_fits_lds(int bit_depth) {
+    return (int64_t{8} << bit_depth) + kEnergyU16ScratchBytes <= kEnergyLdsBytes;
+}
+
+// The statuses of hm_linearity_energy_u16, in this order:
+//   1. HM_EINVAL       a negative count, bit_depth outside 9..16, variant outside 0..2
+//   2. HM_ESHAPE       n_frames outside 2..HM_MAX_FRAMES
+//   3. HM_EINVAL       lower or upper outside 0 .. 2^bit_depth - 1
+//   4. HM_OK, empty    n_candidates == 0: nothing to do, and no pointer has been looked at
+//   5. HM_EUNSUPPORTED more than kEnergyMaxCandidates candidates; variant 1 at a depth whose row does not fit LDS
+//   6. HM_EINVAL       NULL dn, exposures, icrf or out_energy
+//   7. HM_EALIGN       dn not 2-byte aligned
+// rules 1-5, which look at no pointer: what hm_linearity_energy_u16_describe checks (with limits of 0)
+inline int check_linearity_energy_u16_counts(int n_candidates, int lower, int upper, int64_t n_pixels, int n_frames, int bit_depth, int variant,
+                                             bool& empty) {
+    empty = false;
+    if (n_candidates < 0 || n_pixels < 0 || bit_depth < 9 || bit_depth > 16 || variant < 0 || variant > 2) return HM_EINVAL;
+    if (n_frames < 2 || n_frames > HM_MAX_FRAMES) return HM_ESHAPE;
+    const int max_dn = (1 << bit_depth) - 1;
+    if (lower < 0 || lower > max_dn || upper < 0 || upper > max_dn) return HM_EINVAL;
+    if (n_candidates == 0) { empty = true; return HM_OK; }
+    if (n_candidates > kEnergyMaxCandidates || (variant == 1 && !energy_u16_row_fits_lds(bit_depth))) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+inline int check_linearity_energy_u16(const uint16_t* dn, const double* exposures, const double* icrf, int n_candidates, int lower, int upper,
+                                      int64_t n_pixels, int n_frames, int bit_depth, int variant, const double* out_energy, bool& empty) {
+    const int rc = check_linearity_energy_u16_counts(n_candidates, lower, upper, n_pixels, n_frames, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    if (!dn || !exposures || !icrf || !out_energy) return HM_EINVAL;
+    if (reinterpret_cast<uintptr_t>(dn) & 1) return HM_EALIGN;
     return HM_OK;
 }
 

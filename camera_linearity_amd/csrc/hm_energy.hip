@@ -29,10 +29,19 @@
 // k_energy_final's is a shared function) and the geometry and the chunk count come from the per-problem S and pixel count
 // (energy_pixel_major, energy_chunks), so a candidate's sums are formed in the same order - the same bits - whether its problem is
 // evaluated alone or in a batch.
-#include "hm_common.h"
+//
+// uint16 stacks of 9- to 16-bit cameras: hm_energy_u16.hip, the same bodies with candidate rows of 2^bit_depth entries. What the two units
+// share beside the bodies - geometry, chunk count, reductions, the launcher of k_energy_final - is in hm_energy_dev.h.
+#include "hm_energy_dev.h"
 #include "hm_calibration_rules.h"
 
 namespace hm {
+
+// where the kernel bodies keep the candidate's row (hm_energy_pixel_body.h, hm_energy_partial_body.h): all 256 entries in static LDS, one
+// per thread of the workgroup; a DN is its own index
+#define HM_ENERGY_ROW_DECL __shared__ double lut[256];
+#define HM_ENERGY_ROW_FILL(b) lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x]; __syncthreads();
+#define HM_ENERGY_ROW(dn) lut[dn]
 
 struct EnergyK {
     const uint8_t* dn;        // (P, N)
@@ -43,14 +52,6 @@ struct EnergyK {
     int64_t P;
     int32_t N, lower, upper, relative, chunks;
     double t[HM_MAX_FRAMES];
-};
-
-// pixel-major variant (N <= kEnergyRegFrames): per-pair ratio t_i / t_j and its reciprocal from the host
-constexpr int kEnergyRegFrames = 8;
-constexpr int kEnergyRegPairs = kEnergyRegFrames * (kEnergyRegFrames - 1) / 2;
-struct EnergyPairs {
-    double ratio[kEnergyRegPairs];
-    double inv_ratio[kEnergyRegPairs];
 };
 
 // the problems of a batch: the stacks travel in the kernel arguments (a recorded graph holds them by value)
@@ -70,19 +71,6 @@ __device__ __forceinline__ EnergyK on_stack_of(const EnergyK& a, const EnergyBat
     EnergyK r = a;
     r.dn = q.dn[k]; r.sd = q.sd[k];
     return r;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// pair index p (row-major upper triangle, np.triu_indices(N, 1) order) -> (i, j)
-__device__ __forceinline__ void pair_of(int p, int N, int& i, int& j) {
-    int row = 0, left = p;
-    while (left >= N - 1 - row) { left -= N - 1 - row; ++row; }
-    i = row; j = row + 1 + left;
 }
 
 template <bool STD>
@@ -109,29 +97,6 @@ __global__ __launch_bounds__(256) void k_energy_partial_batch(const EnergyK a, c
 // the four IEEE divisions + square root per pair-pixel: 1 / v_j is formed once per (pixel, frame), 1 / (v_j ratio) is
 // a product, and the weight 1 / sigma is one reciprocal square root. Those products differ from the reference's
 // quotients by an ulp or two per term (tests: 1e-12 relative on the pair results).
-// 1 / sqrt(q) for the weights of the pixel-major kernel: the hardware estimate (about 2^-24) and ONE third-order step,
-// y0 (1 + e/2 + 3 e^2 / 8) with e = 1 - q y0^2 - 8 instructions and at most 1.25 ulp (checked on 2 M operands against long-double
-// references, as for the pair statistics) where the library's rsqrt() costs about twenty; q = 0 / inf keep the estimate (inf / 0).
-__device__ __forceinline__ double rsqrt_third_order(double q) {
-    const double y0 = __builtin_amdgcn_rsq(q);
-    const double e = fma(-(q * y0), y0, 1.0);
-    const double y = fma(y0, fma(0.375, e, 0.5) * e, y0);
-    return __builtin_amdgcn_class(y0, 0x264) ? y0 : y;                  // -inf | -0 | +0 | +inf
-}
-
-// 1 / x for the per-(pixel, frame) reciprocals of the pixel-major kernel: the hardware estimate and ONE second-order step, r0 (1 + e + e^2)
-// with e = 1 - x r0 - 4 instructions and at most 1.00 ulp (hm_moments.h: rcp_newton, checked on 2 M operands) where the IEEE division
-// expansion costs eleven, two of them quarter-rate; x = 0 / inf / NaN keep the estimate (inf / 0 / NaN, the IEEE answers).
-#ifndef HM_ENERGY_RCP
-#define HM_ENERGY_RCP 1
-#endif
-__device__ __forceinline__ double rcp_second_order(double x) {
-    const double r0 = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r0, 1.0);
-    const double r = fma(r0, fma(e, e, e), r0);
-    return __builtin_amdgcn_class(r0, 0x264) ? r0 : r;                   // -inf | -0 | +0 | +inf
-}
-
 template <int N, bool STD>
 __global__ __launch_bounds__(256) void k_energy_pixel(const EnergyK a, const EnergyPairs pr) {
 #include "hm_energy_pixel_body.h"
@@ -186,26 +151,10 @@ __global__ __launch_bounds__(64) void k_energy_final_batch(const double* __restr
     energy_final_body(partial, valid, pairs, chunks, nullptr, out_energy, b);
 }
 
-static int energy_chunks(int64_t P) {
-    int64_t c = (P + 1023) / 1024;                  // >= 4 pixels per thread before splitting further
-    if (c < 1) c = 1;
-    return static_cast<int>(c > 64 ? 64 : c);
-}
-
-// pixel-major kernel when there are enough candidates (or few enough pixels) for chunks x candidates workgroups to
-// fill the chip; a lone candidate on a large stack keeps the pair-major kernel's pairs x chunks workgroups.
-// n_candidates is the count of ONE stack's candidates: a batch decides from its per-problem S, never from K x S.
-static bool energy_pixel_major(int n_frames, int n_candidates, int64_t n_pixels) {
-    return n_frames <= kEnergyRegFrames && (n_candidates >= 8 || n_pixels <= 16384);
-}
-
-static void energy_pair_ratios(EnergyPairs& pr, const double* exposures, int n_frames) {
-    int p = 0;
-    for (int i = 0; i < n_frames; ++i)
-        for (int j = i + 1; j < n_frames; ++j, ++p) {
-            pr.ratio[p] = exposures[i] / exposures[j];                       // :100
-            pr.inv_ratio[p] = 1.0 / pr.ratio[p];
-        }
+int energy_final(const double* partial, const uint8_t* valid, int pairs, int chunks, int n_candidates, double* out_pairs,
+                 double* out_energy, hipStream_t st) {
+    hipLaunchKernelGGL(k_energy_final, dim3(n_candidates), dim3(64), 0, st, partial, valid, pairs, chunks, out_pairs, out_energy);
+    return launch_status();
 }
 
 // the kernel arguments of one launch (validated by the caller); a batch passes no stack here: on_stack_of() gives each problem its own
@@ -284,7 +233,5 @@ extern "C" int hm_linearity_energy(const uint8_t* dn, const double* std, const d
     }
     int rc = launch_status();
     if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(k_energy_final, dim3(n_candidates), dim3(64), 0, as_stream(stream),
-                       static_cast<const double*>(workspace), valid, pairs, k.chunks, out_pairs, out_energy);
-    return launch_status();
+    return energy_final(static_cast<const double*>(workspace), valid, pairs, k.chunks, n_candidates, out_pairs, out_energy, as_stream(stream));
 }

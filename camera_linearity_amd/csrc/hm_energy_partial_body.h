@@ -1,11 +1,13 @@
 // hm_energy_partial_body.h - the body of the pair-major energy kernel: one workgroup reduces one frame pair of one candidate over one
 // pixel chunk. Not a header of declarations: hm_energy.hip includes this text twice, as the body of k_energy_partial<STD> and as the
-// body of energy_partial_body<STD> (which k_energy_partial_batch calls on its problem's stack).
-// In scope at the point of inclusion: `a` (the EnergyK arguments) and the template parameter STD; wave_sum and pair_of from hm_energy.hip.
+// body of energy_partial_body<STD> (which k_energy_partial_batch calls on its problem's stack), and hm_energy_u16.hip once, as the body of
+// k_energy_partial_u16<STD, LUT>.
+// In scope at the point of inclusion: `a` (the unit's kernel arguments) and the template parameter STD; wave_sum and pair_of from
+// hm_energy_dev.h; and the unit's placement of the candidate's row: HM_ENERGY_ROW_DECL, HM_ENERGY_ROW_FILL(b), HM_ENERGY_ROW(dn).
 // Included, not called: routing the single-stack kernel through a shared inlined function moved its register allocation in every form
 // tried, and the single-stack path must not pay for the batch. One text keeps the two forms to the same arithmetic;
 // tools/kernel_asm_diff.py shows that an edit here left the kernels it was not meant to change as they were.
-    __shared__ double lut[256];
+    HM_ENERGY_ROW_DECL
     __shared__ double red[4][2];
     const int b = blockIdx.z;
     double* out = a.partial + ((static_cast<int64_t>(b) * gridDim.y + blockIdx.y) * a.chunks + blockIdx.x) * 2;
@@ -13,19 +15,18 @@
         if (threadIdx.x == 0) { out[0] = 0.0; out[1] = 0.0; }
         return;
     }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
+    HM_ENERGY_ROW_FILL(b)
     int i, j;
     pair_of(blockIdx.y, a.N, i, j);
-    const double lo = lut[a.lower], hi = lut[a.upper];
+    const double lo = HM_ENERGY_ROW(a.lower), hi = HM_ENERGY_ROW(a.upper);
     const double ratio = a.t[i] / a.t[j];
     const int N = a.N;
 
     double num = 0.0, den = 0.0;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < a.P; p += stride) {
-        const uint8_t* px = a.dn + p * N;
-        double vi = lut[px[i]], vj = lut[px[j]];
+        const auto* px = a.dn + p * N;
+        double vi = HM_ENERGY_ROW(px[i]), vj = HM_ENERGY_ROW(px[j]);
         if (vi < lo || vi > hi) vi = __builtin_nan("");
         if (vj < lo || vj > hi) vj = __builtin_nan("");
         const double scaled = vj * ratio;

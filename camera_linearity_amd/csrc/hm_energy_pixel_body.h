@@ -1,14 +1,16 @@
 // hm_energy_pixel_body.h - the body of the pixel-major energy kernel (N <= 8 frames): a thread owns pixels and evaluates all N(N-1)/2
 // pairs of a pixel from registers. Not a header of declarations: hm_energy.hip includes this text twice, as the body of
-// k_energy_pixel<N, STD> and as the body of energy_pixel_body<N, STD> (which k_energy_pixel_batch calls on its problem's stack).
-// In scope at the point of inclusion: `a` (the EnergyK arguments), `pr` (the EnergyPairs ratios) and the template parameters N and STD;
-// wave_sum, rcp_second_order, rsqrt_third_order and HM_ENERGY_RCP from hm_energy.hip.
+// k_energy_pixel<N, STD> and as the body of energy_pixel_body<N, STD> (which k_energy_pixel_batch calls on its problem's stack), and
+// hm_energy_u16.hip once, as the body of k_energy_pixel_u16<N, STD, LUT>.
+// In scope at the point of inclusion: `a` (the unit's kernel arguments), `pr` (the EnergyPairs ratios) and the template parameters N and STD;
+// wave_sum, rcp_second_order, rsqrt_third_order and HM_ENERGY_RCP from hm_energy_dev.h; and the unit's placement of the candidate's row:
+// HM_ENERGY_ROW_DECL (its declarations), HM_ENERGY_ROW_FILL(b) (made readable by the whole workgroup), HM_ENERGY_ROW(dn) (the entry of a DN).
 // Included, not called: routing the single-stack kernel through a shared inlined function moved its register allocation in every form
 // tried - an occupancy step for k_energy_pixel<5, false> - and the single-stack path must not pay for the batch. One
 // text keeps the two forms to the same arithmetic; tools/kernel_asm_diff.py shows that an edit here left the kernels it was not meant
 // to change as they were.
     constexpr int P = N * (N - 1) / 2;
-    __shared__ double lut[256];
+    HM_ENERGY_ROW_DECL
     __shared__ double red[4][2 * P];
     const int b = blockIdx.y;
     const int pairs = P;
@@ -17,9 +19,8 @@
         if (threadIdx.x < P) { double* o = out_of(threadIdx.x); o[0] = 0.0; o[1] = 0.0; }
         return;
     }
-    lut[threadIdx.x] = a.icrf[static_cast<int64_t>(b) * 256 + threadIdx.x];
-    __syncthreads();
-    const double lo = lut[a.lower], hi = lut[a.upper];
+    HM_ENERGY_ROW_FILL(b)
+    const double lo = HM_ENERGY_ROW(a.lower), hi = HM_ENERGY_ROW(a.upper);
     const bool rel = a.relative != 0;
     double num[P], den[P];
 #pragma unroll
@@ -27,11 +28,11 @@
 
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t px = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; px < a.P; px += stride) {
-        const uint8_t* q = a.dn + px * N;
+        const auto* q = a.dn + px * N;
         double v[N], rv[N], s[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            double x = lut[q[i]];
+            double x = HM_ENERGY_ROW(q[i]);
             if (x < lo || x > hi) x = __builtin_nan("");                       // :96-97
             v[i] = x;
             rv[i] = HM_ENERGY_RCP ? rcp_second_order(x) : 1.0 / x;

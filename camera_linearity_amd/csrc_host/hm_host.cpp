@@ -1322,16 +1322,18 @@ int hm_kde_evaluate(const double* val, const double* std_, int64_t n_elems, int 
     return HM_OK;
 }
 
+}  // extern "C" (a template below)
+
 // _energy_function + analyze_linearity, modules/ICRF_calibration_exposure.py:66-145,148-201, for n_candidates ICRFs of one channel:
 // per candidate and exposure pair (i < j, np.triu_indices order) the (weighted) mean of |v_i - v_j t_i/t_j| (/ (v_j t_i/t_j) when
 // relative) over the pixels whose values lie inside [icrf[lower], icrf[upper]]; the energy is the nanmean over the pairs, +inf for NaN
-size_t hm_linearity_energy_workspace_bytes(int64_t, int, int) { return 0; }
-int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exposures, const double* icrf, const uint8_t* valid,
-                        int n_candidates, int lower, int upper, int use_relative, int64_t n_pixels, int n_frames,
-                        double* out_pairs, double* out_energy, void*, void*) {
-    bool empty;
-    const int rc = hm_rules::check_linearity_energy(dn, exposures, icrf, n_candidates, lower, upper, n_pixels, n_frames, out_energy, empty);
-    if (rc != HM_OK || empty) return rc;
+// (validated arguments) DN: uint8_t with n_rows = 256 (hm_linearity_energy), uint16_t with n_rows = 2^bit_depth (hm_linearity_energy_u16);
+// a DN's index is DN & (n_rows - 1) - every uint8 DN is its own
+template <typename DN>
+static int linearity_energy_host(const DN* dn, const double* std_, const double* exposures, const double* icrf, const uint8_t* valid,
+                                 int n_candidates, int lower, int upper, int use_relative, int64_t n_pixels, int n_frames, int n_rows,
+                                 double* out_pairs, double* out_energy) {
+    const unsigned mask = static_cast<unsigned>(n_rows - 1);
     const int N = n_frames, pairs = N * (N - 1) / 2;
     std::vector<int> pi(pairs), pj(pairs);
     { int p = 0; for (int i = 0; i < N; ++i) for (int j = i + 1; j < N; ++j, ++p) { pi[p] = i; pj[p] = j; } }
@@ -1341,14 +1343,14 @@ int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exp
         for (int p = 0; p < pairs; ++p) {
             double& r = res[static_cast<size_t>(b) * pairs + p];
             if (valid && !valid[b]) { r = kNaN; continue; }
-            const double* lut = icrf + static_cast<int64_t>(b) * 256;
+            const double* lut = icrf + static_cast<int64_t>(b) * n_rows;
             const double lo = lut[lower], hi = lut[upper];
             const int i = pi[p], j = pj[p];
             const double ratio = exposures[i] / exposures[j];                            // :100
             double num = 0.0, den = 0.0, bnum = 0.0, bden = 0.0;                       // sums in blocks of 1024 pixels (a million-term running sum
             for (int64_t px = 0; px < n_pixels; ++px) {                                  // loses three more digits than NumPy's pairwise one)
                 if ((px & 1023) == 0) { num += bnum; den += bden; bnum = 0.0; bden = 0.0; }
-                double vi = lut[dn[px * N + i]], vj = lut[dn[px * N + j]];
+                double vi = lut[dn[px * N + i] & mask], vj = lut[dn[px * N + j] & mask];
                 if (vi < lo || vi > hi) vi = kNaN;                                       // :96-97
                 if (vj < lo || vj > hi) vj = kNaN;
                 const double scaled = vj * ratio;                                        // :111
@@ -1383,6 +1385,42 @@ int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exp
         const double e = sum / cnt;                                                      // :196
         out_energy[b] = (ok && e == e) ? e : std::numeric_limits<double>::infinity();    // :197-200
     }
+    return HM_OK;
+}
+
+extern "C" {
+
+size_t hm_linearity_energy_workspace_bytes(int64_t, int, int) { return 0; }
+int hm_linearity_energy(const uint8_t* dn, const double* std_, const double* exposures, const double* icrf, const uint8_t* valid,
+                        int n_candidates, int lower, int upper, int use_relative, int64_t n_pixels, int n_frames,
+                        double* out_pairs, double* out_energy, void*, void*) {
+    bool empty;
+    const int rc = hm_rules::check_linearity_energy(dn, exposures, icrf, n_candidates, lower, upper, n_pixels, n_frames, out_energy, empty);
+    if (rc != HM_OK || empty) return rc;
+    return linearity_energy_host(dn, std_, exposures, icrf, valid, n_candidates, lower, upper, use_relative, n_pixels, n_frames, 256, out_pairs,
+                                 out_energy);
+}
+
+// ... on uint16 DNs of 9 to 16 bits, candidate rows of 2^bit_depth entries. `variant` places the row on the device; here it is only checked.
+int hm_linearity_energy_u16(const uint16_t* dn, const double* std_, const double* exposures, const double* icrf, const uint8_t* valid,
+                            int n_candidates, int lower, int upper, int use_relative, int64_t n_pixels, int n_frames, int bit_depth,
+                            int variant, double* out_pairs, double* out_energy, void*, void*) {
+    bool empty;
+    const int rc = hm_rules::check_linearity_energy_u16(dn, exposures, icrf, n_candidates, lower, upper, n_pixels, n_frames, bit_depth, variant,
+                                                        out_energy, empty);
+    if (rc != HM_OK || empty) return rc;
+    return linearity_energy_host(dn, std_, exposures, icrf, valid, n_candidates, lower, upper, use_relative, n_pixels, n_frames, 1 << bit_depth,
+                                 out_pairs, out_energy);
+}
+
+int hm_linearity_energy_u16_describe(int64_t n_pixels, int n_frames, int n_candidates, int with_std, int bit_depth, int variant, char* buf,
+                                     int buf_len) {
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    buf[0] = '\0';
+    bool empty;
+    const int rc = hm_rules::check_linearity_energy_u16_counts(n_candidates, 0, 0, n_pixels, n_frames, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "host_linearity_energy<dn=u16,std=%d,bits=%d>(N=%d)", with_std != 0, bit_depth, n_frames);
     return HM_OK;
 }
 

@@ -1293,15 +1293,17 @@ def noise_profile_clean_edges(profiles: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 # ICRF-calibration energy function (modules/ICRF_calibration_exposure.py:66-201), batched over candidates
 # ------------------------------------------------------------------------------------------------
-def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures, batch: bool = False):
+def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures, batch: bool = False,
+                  dn_dtype=_U8):
     """The uint8 (X, Y, N) stacks of a calibration - one, or those of a batch: one shape, one device -, their float64 std stacks (None,
     or a sequence whose entries are all None: no stds) and the N exposures, checked in this order
     -> (contiguous stacks, contiguous std stacks | None, exposures as a float64 array). `batch` words the std messages for a batch, whose
-    std stacks must also live on the stacks' device."""
+    std stacks must also live on the stacks' device. `dn_dtype`: torch.uint16 for the energy of a stack with a bit depth (linearity_energy
+    alone: the differential-evolution plans take uint8 stacks only)."""
     first = dn_stacks[0]
     for s in dn_stacks:
         _require_cuda(s, "image_value_stack")
-        if s.dtype != torch.uint8:
+        if s.dtype != dn_dtype:
             raise TypeError("image_value_stack must be uint8 digital numbers")
         if s.dim() != 3:
             raise ValueError("image_stack must be a 3D array with shape (X, Y, N).")             # ICRF_calibration_exposure.py:82-83
@@ -1325,19 +1327,39 @@ def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequen
     return [s.contiguous() for s in dn_stacks], [s.contiguous() for s in std_stacks], t
 
 
+def _energy_bit_depth(dn_stack, bit_depth) -> Optional[int]:
+    """The depth of an energy call's stack: None for uint8 DNs, `bit_depth` in 9..16 for torch.uint16 ones. Any other dtype is left to
+    _check_stacks' TypeError unless it comes with a bit_depth, which only uint16 stacks take."""
+    if isinstance(dn_stack, torch.Tensor) and dn_stack.dtype == _U16:
+        if bit_depth is None:
+            raise ValueError("a torch.uint16 image_value_stack needs bit_depth (9..16): the number of rows of its candidate ICRFs")
+        return _check_bit_depth(bit_depth)
+    if bit_depth is not None:
+        raise ValueError(f"bit_depth is for torch.uint16 DN stacks, got {getattr(dn_stack, 'dtype', type(dn_stack))}")
+    return None
+
+
 def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], icrf_batch,
-                     lower: int, upper: int, valid=None, use_relative: bool = True, return_pairs: bool = False):
+                     lower: int, upper: int, valid=None, use_relative: bool = True, return_pairs: bool = False,
+                     bit_depth: Optional[int] = None, variant: int = 0):
     """Energy of every candidate ICRF row of `icrf_batch` ((B, 256) float64) on one channel's (X, Y, N) uint8 stack.
-    -> energies (B,) float64 device tensor [, pair results (B, N(N-1)/2)]."""
-    (dn_stack,), sd, t = _check_stacks([dn_stack], [std_stack], exposures)
+    -> energies (B,) float64 device tensor [, pair results (B, N(N-1)/2)].
+    torch.uint16 stacks need `bit_depth` in 9..16 (hm_linearity_energy_u16): candidates of 2**bit_depth entries, a DN's index
+    DN & (2**bit_depth - 1), `lower` / `upper` DNs of that depth. `variant` places the candidate's row on the device (0: the library's
+    choice, 1: LDS, up to 14 bits, 2: global memory); the result does not depend on it."""
+    bit_depth = _energy_bit_depth(dn_stack, bit_depth)
+    (dn_stack,), sd, t = _check_stacks([dn_stack], [std_stack], exposures, dn_dtype=_U8 if bit_depth is None else _U16)
     std_stack = None if sd is None else sd[0]
     dev = dn_stack.device
     N = dn_stack.shape[2]
+    n_rows = BITS if bit_depth is None else 2 ** bit_depth
     lut = _dev_f64(icrf_batch, dev)
     if lut.dim() == 1:
         lut = lut[None]
-    if lut.shape[1] != BITS:
-        raise ValueError(f"candidate ICRFs must have {BITS} entries")
+    if lut.shape[1] != n_rows:
+        raise ValueError(f"candidate ICRFs must have {n_rows} entries")
+    if bit_depth is not None and not (0 <= int(lower) < n_rows and 0 <= int(upper) < n_rows):
+        raise ValueError(f"lower and upper must be DNs in 0..{n_rows - 1} at bit_depth {bit_depth}, got {lower}, {upper}")
     lut = lut.contiguous()
     B = lut.shape[0]
     vd = None if valid is None else torch.as_tensor(np.asarray(valid, dtype=np.uint8), device=dev)
@@ -1346,12 +1368,24 @@ def linearity_energy(dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], 
     energy = torch.empty(B, dtype=_F64, device=dev)
     out_pairs = torch.empty((B, pairs), dtype=_F64, device=dev) if return_pairs else None
     ws = torch.empty(max(1, nat.lib.hm_linearity_energy_workspace_bytes(P, N, B) // 8), dtype=_F64, device=dev)
+    head = (dn_stack.data_ptr(), nat.ptr(std_stack), (C.c_double * N)(*t.tolist()), lut.data_ptr(), nat.ptr(vd), B, int(lower), int(upper),
+            int(bool(use_relative)), P, N)
+    tail = (nat.ptr(out_pairs), energy.data_ptr(), ws.data_ptr(), _stream(dev))
     with _on(dev):
-        nat.check(nat.lib.hm_linearity_energy(dn_stack.data_ptr(), nat.ptr(std_stack), (C.c_double * N)(*t.tolist()), lut.data_ptr(),
-                                              nat.ptr(vd), B, int(lower), int(upper), int(bool(use_relative)), P, N,
-                                              nat.ptr(out_pairs), energy.data_ptr(), ws.data_ptr(), _stream(dev)),
-                  "hm_linearity_energy")
+        if bit_depth is None:
+            nat.check(nat.lib.hm_linearity_energy(*head, *tail), "hm_linearity_energy")
+        else:
+            nat.check(nat.lib.hm_linearity_energy_u16(*head, bit_depth, int(variant), *tail), "hm_linearity_energy_u16")
     return (energy, out_pairs) if return_pairs else energy
+
+
+def energy_kernel(n_pixels: int, n_frames: int, n_candidates: int, with_std: bool, bit_depth: int, variant: int = 0) -> str:
+    """The kernel linearity_energy(..., bit_depth=bit_depth, variant=variant) starts on such a problem, as hm_linearity_energy_u16_describe
+    names it (e.g. "k_energy_pixel_u16<N=7,std=1,lut=lds,bits=12>"); nothing is launched. For tests and benchmarks."""
+    buf = C.create_string_buffer(128)
+    nat.check(nat.lib.hm_linearity_energy_u16_describe(int(n_pixels), int(n_frames), int(n_candidates), int(bool(with_std)), int(bit_depth),
+                                                       int(variant), buf, len(buf)), "hm_linearity_energy_u16_describe")
+    return buf.value.decode()
 
 
 # ------------------------------------------------------------------------------------------------

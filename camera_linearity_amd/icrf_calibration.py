@@ -30,13 +30,14 @@ from . import settings as gs
 
 
 def _inverse_camera_response_function(mean_ICRF, PCA_array, PCA_params, use_mean_ICRF):
-    """:22-45. PCA_params may be one vector (n_params,) or a batch (n_candidates, n_params); returns (256,) or
-    (n_candidates, 256)."""
+    """:22-45. PCA_params may be one vector (n_params,) or a batch (n_candidates, n_params); returns (n,) or
+    (n_candidates, n) with n the rows of the PCA basis: 256, or 2**bit_depth for a deeper camera (the power-law base takes its grid from
+    there, not from settings.BITS)."""
     p = np.asarray(PCA_params, dtype=np.float64)
     single = p.ndim == 1
     p = np.atleast_2d(p)
     if not use_mean_ICRF:
-        base = np.linspace(0, 1, gs.BITS)[None, :] ** p[:, :1]
+        base = np.linspace(0, 1, np.shape(PCA_array)[0])[None, :] ** p[:, :1]
         out = np.stack([base[b] + np.matmul(PCA_array, p[b, 1:]) for b in range(p.shape[0])])
     else:
         out = np.stack([mean_ICRF + np.matmul(PCA_array, p[b]) for b in range(p.shape[0])])
@@ -45,7 +46,8 @@ def _inverse_camera_response_function(mean_ICRF, PCA_array, PCA_params, use_mean
 
 def candidate_icrfs(PCA_params, mean_ICRF, PCA_array, use_mean_ICRF=True):
     """Candidate ICRFs as the energy function sees them (:165-179): shifted so that ICRF[-1] = 1 and ICRF[0] = 0, and the
-    per-candidate verdict of the range and strict-monotonicity tests. -> (icrfs (B, 256), valid (B,) bool)."""
+    per-candidate verdict of the range and strict-monotonicity tests. -> (icrfs (B, n), valid (B,) bool), n the rows of the mean ICRF / PCA
+    basis (256, or 2**bit_depth)."""
     icrfs = np.atleast_2d(_inverse_camera_response_function(mean_ICRF, PCA_array, PCA_params, use_mean_ICRF)).copy()
     icrfs += (1 - icrfs[:, -1])[:, None]                                         # :166
     icrfs[:, 0] = 0                                                              # :167
@@ -55,11 +57,13 @@ def candidate_icrfs(PCA_params, mean_ICRF, PCA_array, use_mean_ICRF=True):
 
 
 def analyze_linearity(image_value_stack: torch.Tensor, image_std_stack: Optional[torch.Tensor], ICRF_ch, lower: int, upper: int,
-                      use_relative: bool, exposure_values):
+                      use_relative: bool, exposure_values, bit_depth: Optional[int] = None):
     """:66-145 for a uint8 DN stack seen through one ICRF: the N(N-1)/2 pair results (device tensor) in
-    np.triu_indices(N, 1) order. `lower` / `upper` are DN limits (the energy function maps them through the ICRF, :181-182)."""
+    np.triu_indices(N, 1) order. `lower` / `upper` are DN limits (the energy function maps them through the ICRF, :181-182).
+    bit_depth=b (9..16): a torch.uint16 stack, an ICRF of 2**b entries, limits that are DNs of that depth."""
     _, pairs = _engine_for(image_value_stack).linearity_energy(image_value_stack, image_std_stack, _host(exposure_values),
-                                                               np.asarray(ICRF_ch)[None], lower, upper, None, use_relative, return_pairs=True)
+                                                               np.asarray(ICRF_ch)[None], lower, upper, None, use_relative, return_pairs=True,
+                                                               bit_depth=bit_depth)
     return pairs[0]
 
 
@@ -80,47 +84,60 @@ def _engine_for(stack: torch.Tensor):
 
 
 def energy_function_batch(PCA_params, mean_ICRF, PCA_array, image_value_stack, image_std_stack, lower, upper, use_mean,
-                          exposure_values) -> np.ndarray:
-    """Energies of a batch of candidates. PCA_params: (n_candidates, n_params). One device launch."""
+                          exposure_values, bit_depth: Optional[int] = None) -> np.ndarray:
+    """Energies of a batch of candidates. PCA_params: (n_candidates, n_params). One device launch.
+    bit_depth=b (9..16): a torch.uint16 stack, mean ICRF and PCA basis of 2**b rows."""
     icrfs, valid = candidate_icrfs(PCA_params, mean_ICRF, PCA_array, use_mean)
     if not valid.any():
         return np.full(len(valid), np.inf)
     e = _engine_for(image_value_stack).linearity_energy(image_value_stack, image_std_stack, _host(exposure_values), icrfs, int(lower), int(upper),
-                                valid, True)
+                                valid, True, bit_depth=bit_depth)
     return e.cpu().numpy()
 
 
 def _energy_function(PCA_params, mean_ICRF, PCA_array, image_value_stack, image_std_stack, lower, upper, use_mean,
-                     exposure_values):
+                     exposure_values, bit_depth: Optional[int] = None):
     """:148-201, the reference's signature: one candidate -> float. With a (n_params, S) array (SciPy's
-    `vectorized=True` calling convention) -> (S,) energies from one launch."""
+    `vectorized=True` calling convention) -> (S,) energies from one launch. `bit_depth` trails, so SciPy's `args` tuple carries it."""
     p = np.asarray(PCA_params, dtype=np.float64)
     if p.ndim == 2:
         return energy_function_batch(p.T, mean_ICRF, PCA_array, image_value_stack, image_std_stack, lower, upper, use_mean,
-                                     exposure_values)
+                                     exposure_values, bit_depth)
     return float(energy_function_batch(p[None], mean_ICRF, PCA_array, image_value_stack, image_std_stack, lower, upper, use_mean,
-                                       exposure_values)[0])
+                                       exposure_values, bit_depth)[0])
 
 
-def interpolate_ICRF(ICRF_array, datapoints: Optional[int] = None):
-    """:204-216: resample (DATAPOINTS, C) to (BITS, C) by linear interpolation when the sizes differ."""
+def interpolate_ICRF(ICRF_array, datapoints: Optional[int] = None, bits: Optional[int] = None):
+    """:204-216: resample (DATAPOINTS, C) to (BITS, C) by linear interpolation when the sizes differ. `bits`: the rows to resample to
+    instead of settings.BITS (2**bit_depth for a deeper camera)."""
     ICRF_array = np.asarray(ICRF_array, dtype=np.float64)
     datapoints = ICRF_array.shape[0] if datapoints is None else datapoints
-    if gs.BITS == datapoints:
+    bits = gs.BITS if bits is None else int(bits)
+    if bits == datapoints:
         return ICRF_array
-    x_new = np.linspace(0, 1, num=gs.BITS)
+    x_new = np.linspace(0, 1, num=bits)
     x_old = np.linspace(0, 1, num=datapoints)
-    out = np.zeros((gs.BITS, ICRF_array.shape[1]), dtype=float)
+    out = np.zeros((bits, ICRF_array.shape[1]), dtype=float)
     for c in range(ICRF_array.shape[1]):
         out[:, c] = np.interp(x_new, x_old, ICRF_array[:, c])
     return out
 
 
 def initialize_channel_image_stacks(frames: Sequence, exposures: Sequence[float], stds: Optional[Sequence] = None,
-                                    data_spacing=150, device=None):
+                                    data_spacing=150, device=None, bit_depth: Optional[int] = None):
     """:219-284 for frames already in memory (uint8 (H, W, C) arrays / tensors): sort by exposure, thin the pixels with
     `data_spacing` (int or (x_step, y_step); plain strided selection) and stack every channel to (X, Y, N).
-    -> (channel value stacks [C x uint8 (X, Y, N) device tensors], channel std stacks or [None]*C, exposures ndarray)."""
+    -> (channel value stacks [C x uint8 (X, Y, N) device tensors], channel std stacks or [None]*C, exposures ndarray).
+    bit_depth=b (9..16): uint16 frames of a b-bit camera, kept as torch.uint16 stacks for calibration(..., bit_depth=b). uint16 frames
+    without it raise ValueError (cast to uint8 they would wrap)."""
+    u16 = [(f.dtype == torch.uint16) if isinstance(f, torch.Tensor) else (np.asarray(f).dtype == np.uint16) for f in frames]
+    if bit_depth is not None:
+        engine._check_bit_depth(bit_depth)
+        if not all(u16):
+            raise ValueError("bit_depth is for uint16 frames")
+    elif any(u16):
+        raise ValueError("uint16 frames need bit_depth (9..16): as uint8 stacks their DNs would wrap")
+    dn_dtype = torch.uint8 if bit_depth is None else torch.uint16
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     x_step, y_step = data_spacing if isinstance(data_spacing, tuple) else (data_spacing, data_spacing)
     order = np.argsort(np.asarray(exposures, dtype=np.float64), kind="stable")
@@ -130,8 +147,10 @@ def initialize_channel_image_stacks(frames: Sequence, exposures: Sequence[float]
         a = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
         return a[::x_step, ::y_step].to(device=device, dtype=dtype)
 
-    vals = torch.stack([thin(frames[i], torch.uint8) for i in order], dim=-1)            # (X, Y, C, N)
-    value_stacks = [vals[:, :, c, :].contiguous() for c in range(vals.shape[2])]
+    # (uint16 frames are stacked as their int16 bit patterns: torch implements few operations for unsigned 16-bit tensors)
+    as_stacked = (lambda x: x) if bit_depth is None else (lambda x: x.view(torch.int16))
+    vals = torch.stack([as_stacked(thin(frames[i], dn_dtype)) for i in order], dim=-1)            # (X, Y, C, N)
+    value_stacks = [vals[:, :, c, :].contiguous().view(dn_dtype) for c in range(vals.shape[2])]
     if stds is not None:
         sds = torch.stack([thin(stds[i], torch.float64) for i in order], dim=-1)
         std_stacks = [sds[:, :, c, :].contiguous() for c in range(sds.shape[2])]
@@ -210,11 +229,20 @@ def _device_defaults():
     return {name: par[name].default for name in ("check_every", "graph", "tol")}
 
 
+def _scipy_only(bit_depth, solver, batched, restarts):
+    """A calibration with a bit depth runs on SciPy's solver: the device solver's kernels form candidate rows of 256 entries."""
+    engine._check_bit_depth(bit_depth)
+    if solver == "device" or batched or restarts > 1:
+        raise NotImplementedError('bit_depth needs solver="scipy" without batched=True or restarts > 1: the device solver forms candidate '
+                                  'ICRFs of 256 entries')
+
+
 def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values,
                   lower_PCA_limit: float, upper_PCA_limit: float, use_mean_ICRF: bool = True,
                   data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, seed=7,
                   max_iterations: int = 1000, vectorized: bool = True, popsize: int = 15, channel: int = 0, verbose: bool = False,
-                  solver: str = "scipy", check_every: int = 8, graph: bool = True, tol: float = 0.01, restarts: int = 1):
+                  solver: str = "scipy", check_every: int = 8, graph: bool = True, tol: float = 0.01, restarts: int = 1,
+                  bit_depth: Optional[int] = None):
     """The per-channel solve of calibration() (:329-369): SciPy's DifferentialEvolutionSolver with the reference's
     settings. vectorized=True evaluates each generation's population in ONE launch (SciPy then uses deferred updating);
     vectorized=False keeps the reference's immediate updating and evaluates one candidate per launch.
@@ -225,12 +253,16 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     restarts=R > 1 (solver="device" only): R solves of the same channel from other seeds - restart r uses restart_seed(seed, r) =
     seed + 1 000 003 r, so restart 0 is the restarts=1 solve, and starts from SciPy's Sobol population for that seed - advanced together
     in one engine.DEBatchPlan; the triple of the restart with the lowest final energy is returned (ties: the lowest r).
-    -> (ICRF of the channel (256,), final energy, iterations)."""
+    bit_depth=b (9..16, solver="scipy" only): a torch.uint16 stack of a b-bit camera, mean ICRF and PCA basis of 2**b rows. `data_limits`
+    are DNs of the stack's depth and are not rescaled: the defaults are 8-bit DNs and wrong for any other depth.
+    -> (ICRF of the channel (256,) - (2**b,) with bit_depth -, final energy, iterations)."""
     if solver not in ("scipy", "device"):
         raise ValueError(f"solver must be 'scipy' or 'device', got {solver!r}")
     restarts = int(restarts)
     if restarts < 1:
         raise ValueError(f"restarts must be >= 1, got {restarts}")
+    if bit_depth is not None:
+        _scipy_only(bit_depth, solver, False, restarts)
     if restarts > 1 and solver != "device":
         raise ValueError('restarts > 1 needs solver="device": the restarts run as one batch on the stack\'s backend')
     if solver == "device" and not use_mean_ICRF:
@@ -247,7 +279,7 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
         x0.append(0)
     assert len(limits) == n_params
     args = (mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, data_limits[0], data_limits[1], use_mean_ICRF,
-            exposure_values)
+            exposure_values) + (() if bit_depth is None else (bit_depth,))
     extra = dict(vectorized=True, updating="deferred") if vectorized else {}
     extra.update(_seed_keyword(seed))
     if solver == "device" and restarts > 1:
@@ -294,7 +326,7 @@ def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_
                 lower_PCA_limit: float, upper_PCA_limit: float, initial_function=None,
                 data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, rng_seed: int = 7,
                 vectorized: bool = True, max_iterations: int = 1000, popsize: int = 15, solver: str = "scipy", batched: bool = False,
-                restarts: int = 1):
+                restarts: int = 1, bit_depth: Optional[int] = None):
     """calibration() (:287-405) from arrays: per-channel mean ICRF (or `initial_function`) and PCA basis, the channel stacks
     of initialize_channel_image_stacks. By default the channels are solved one after another on this process's GPU (the reference
     forks one joblib worker per channel, :383; with one process per GPU, give each rank a channel instead).
@@ -303,7 +335,12 @@ def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_
     restart_seed(rng_seed + c, r), the best restart kept per channel. It needs channel stacks of one shape and the same number of PCA
     components for every channel (ValueError otherwise, never a sequential fallback); with restarts=1 the result equals the sequential
     solver="device" one bit for bit. `restarts` > 1 without `batched` runs each channel's restarts as a batch, channel after channel.
-    -> (ICRF (BITS, C) interpolated, final energies (C,))."""
+    bit_depth=b (9..16, solver="scipy" only): torch.uint16 channel stacks of a b-bit camera (initialize_channel_image_stacks(...,
+    bit_depth=b)), mean ICRFs and PCA bases of 2**b rows; the result has 2**b rows and is what engine.merge(..., bit_depth=b) takes.
+    `data_limits` are DNs of the stacks' depth and are not rescaled: the defaults are 8-bit DNs and wrong for any other depth.
+    -> (ICRF (BITS, C) interpolated - (2**b, C) with bit_depth -, final energies (C,))."""
+    if bit_depth is not None:
+        _scipy_only(bit_depth, solver, batched, int(restarts))
     C = len(channel_image_value_stacks)
     use_mean_ICRF = initial_function is None
     results, energies = [], np.zeros(C)
@@ -330,11 +367,11 @@ def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_
             icrf_c, energies[c], _ = solve_channel(base, PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
                                                    exposure_values, lower_PCA_limit, upper_PCA_limit, use_mean_ICRF, data_limits,
                                                    energy_limit, rng_seed + c, max_iterations, vectorized, popsize, c, solver=solver,
-                                                   restarts=restarts)
+                                                   restarts=restarts, bit_depth=bit_depth)
             results.append(icrf_c)
     ICRF = np.stack(results, axis=1)
     ICRF += (1 - ICRF[-1, :])[None, :]                                           # :390
     ICRF[0, :] = 0                                                               # :391
     ICRF[ICRF < 0] = 0                                                           # :395-396
     ICRF[ICRF > 1] = 1
-    return interpolate_ICRF(ICRF), energies
+    return interpolate_ICRF(ICRF, bits=None if bit_depth is None else 2 ** bit_depth), energies

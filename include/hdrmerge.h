@@ -591,6 +591,31 @@ int hm_linearity_energy(const uint8_t* dn, const double* std /*nullable*/, const
                         int lower, int upper, int use_relative, int64_t n_pixels, int n_frames,
                         double* out_pairs /*nullable*/, double* out_energy, void* workspace, void* stream);
 
+/* ... on uint16 DN stacks of 9- to 16-bit cameras: candidate ICRFs of 2^bit_depth rows. Everything not named here is
+ * hm_linearity_energy's: the layouts, the `valid` convention, pair order, +inf and NaN behaviour, no allocation, no host synchronisation;
+ * hm_linearity_energy_workspace_bytes(n_pixels, n_frames, n_candidates) sizes the workspace.
+ *   dn         (n_pixels, n_frames) uint16, 2-byte aligned; a DN's table index is DN & (2^bit_depth - 1), applied before every
+ *              table access (hm_merge_u16's convention)
+ *   icrf       (n_candidates, 2^bit_depth) float64; lower, upper: DNs of that depth, 0 .. 2^bit_depth - 1
+ *   variant    where a workgroup reads the candidate's row from - 0: the library's choice; 1: a copy in LDS (the row of 8 * 2^bit_depth
+ *              bytes and the kernels' reduction scratch must fit the CU's 160 KiB: up to 14 bits); 2: gathered from global memory
+ *              (every depth). The placements give the same bits. The host build checks it and ignores it.
+ *   The sums are formed in hm_linearity_energy's order: an 8-bit problem embedded at depth b (DN << (b - 8), the 256 entries at rows
+ *   k << (b - 8), limits shifted alike) gives hm_linearity_energy's out_energy and out_pairs bit for bit.
+ *   Statuses, an earlier one winning: HM_EINVAL for a negative count, bit_depth outside 9..16 or variant outside 0..2; HM_ESHAPE for
+ *   n_frames outside 2..HM_MAX_FRAMES; HM_EINVAL for a limit outside 0 .. 2^bit_depth - 1; n_candidates == 0 returns HM_OK with no pointer
+ *   looked at; HM_EUNSUPPORTED for more than 65535 candidates and for variant 1 where the row does not fit; HM_EINVAL for NULL dn,
+ *   exposures, icrf or out_energy; HM_EALIGN for a dn that is not 2-byte aligned; (device build) HM_EINVAL for a NULL workspace.
+ *   hm_linearity_energy_u16_describe writes the name of the pixel kernel such a call would launch, e.g.
+ *   "k_energy_pixel_u16<N=7,std=1,lut=lds,bits=12>" or "k_energy_partial_u16<std=0,lut=global,bits=16>(N=9)" (the host build: a host
+ *   name), and launches nothing; the same statuses up to HM_EUNSUPPORTED, HM_EINVAL for a NULL or empty buf. */
+int hm_linearity_energy_u16(const uint16_t* dn, const double* std /*nullable*/, const double* exposures /*[host]*/,
+                            const double* icrf /*(n_candidates, 2^bit_depth)*/, const uint8_t* valid /*nullable*/, int n_candidates,
+                            int lower, int upper, int use_relative, int64_t n_pixels, int n_frames, int bit_depth, int variant,
+                            double* out_pairs /*nullable*/, double* out_energy, void* workspace, void* stream);
+int hm_linearity_energy_u16_describe(int64_t n_pixels, int n_frames, int n_candidates, int with_std, int bit_depth, int variant,
+                                     char* buf, int buf_len);
+
 /* ------------------------------------------------------------------------------------------
  * ICRF-calibration differential evolution, one generation per call: the solver loop of calibration(),
  * modules/ICRF_calibration_exposure.py:288-369 (SciPy's DifferentialEvolutionSolver with strategy 'currenttobest1bin',

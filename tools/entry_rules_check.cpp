@@ -82,6 +82,35 @@ void calibration() {
     expect("energy, no candidates", check_linearity_energy(nullptr, nullptr, nullptr, 0, 0, 255, 8, 2, nullptr, empty), HM_OK);
     expect("energy, no candidates: empty", empty, 1);
     expect("energy, NULL", check_linearity_energy(nullptr, nullptr, nullptr, 2, 0, 255, 8, 2, nullptr, empty), HM_EINVAL);
+    uint16_t* w = fake<uint16_t>(0x4000);
+    auto e16 = [&](const uint16_t* dn, int cands, int lower, int upper, int frames, int bits, int variant) {
+        return check_linearity_energy_u16(dn, d, d, cands, lower, upper, 8, frames, bits, variant, d, empty);
+    };
+    for (int bits = 9; bits <= 16; ++bits) {
+        const int top = (1 << bits) - 1;
+        expect("energy u16, limits at the ends", e16(w, 2, 0, top, 2, bits, 0), HM_OK);
+        expect("energy u16, upper beyond the depth", e16(w, 2, 0, top + 1, 2, bits, 0), HM_EINVAL);
+        expect("energy u16, lower beyond the depth", e16(w, 2, top + 1, top, 2, bits, 2), HM_EINVAL);
+        expect("energy u16, row in LDS", e16(w, 2, 0, top, 2, bits, 1), bits <= 14 ? HM_OK : HM_EUNSUPPORTED);
+        expect("energy u16, row fits LDS", energy_u16_row_fits_lds(bits), bits <= 14);
+    }
+    expect("energy u16, 32 frames, 65535 candidates", e16(w, kEnergyMaxCandidates, 5, 4000, HM_MAX_FRAMES, 12, 0), HM_OK);
+    expect("energy u16, 65536 candidates", e16(w, kEnergyMaxCandidates + 1, 5, 4000, 2, 12, 0), HM_EUNSUPPORTED);
+    expect("energy u16, 8 bits", e16(w, 2, 5, 250, 2, 8, 0), HM_EINVAL);
+    expect("energy u16, 17 bits", e16(w, 2, 5, 250, 2, 17, 0), HM_EINVAL);
+    expect("energy u16, variant 3", e16(w, 2, 5, 250, 2, 12, 3), HM_EINVAL);
+    expect("energy u16, variant -1 before one frame", e16(w, 2, 5, 250, 1, 12, -1), HM_EINVAL);
+    expect("energy u16, one frame before a limit", e16(w, 2, -1, 250, 1, 12, 0), HM_ESHAPE);
+    expect("energy u16, 33 frames", e16(w, 2, 5, 250, HM_MAX_FRAMES + 1, 12, 0), HM_ESHAPE);
+    expect("energy u16, a limit before no candidates", e16(nullptr, 0, 5, 4096, 2, 12, 0), HM_EINVAL);
+    expect("energy u16, no candidates", check_linearity_energy_u16(nullptr, nullptr, nullptr, 0, 0, 4095, 8, 2, 12, 0, nullptr, empty), HM_OK);
+    expect("energy u16, no candidates: empty", empty, 1);
+    expect("energy u16, no candidates before a row that does not fit", e16(nullptr, 0, 0, 4095, 2, 15, 1), HM_OK);
+    expect("energy u16, a row that does not fit before NULL", e16(nullptr, 2, 0, 4095, 2, 15, 1), HM_EUNSUPPORTED);
+    expect("energy u16, NULL", check_linearity_energy_u16(nullptr, nullptr, nullptr, 2, 0, 4095, 8, 2, 12, 0, nullptr, empty), HM_EINVAL);
+    expect("energy u16, NULL icrf before an odd dn", check_linearity_energy_u16(fake<uint16_t>(0x4001), d, nullptr, 2, 0, 4095, 8, 2, 12, 0, d, empty), HM_EINVAL);
+    expect("energy u16, odd dn", e16(fake<uint16_t>(0x4001), 2, 0, 4095, 2, 12, 0), HM_EALIGN);
+    expect("energy u16 describe, counts only", check_linearity_energy_u16_counts(2, 0, 0, 8, 2, 12, 0, empty), HM_OK);
     auto de = [&](int pop, int params, int frames) {
         return check_de_generation(1, d, d, d, d, d, b, s, d, d, d, d, b, d, 8, frames, 5, 250, pop, params, 10, 0.5, 1.0, 0.7, 0.01, 0.0);
     };

@@ -631,6 +631,35 @@ def case_energy(rng):
     return desc
 
 
+def case_energy_u16(rng):
+    """hm_linearity_energy_u16: case_energy on a uint16 stack of 9 to 16 bits with stray bits above the depth, the candidate's row in LDS
+    (variant 1, up to 14 bits) or gathered from global memory (variant 2), in both geometries (a lone candidate on more than 16 384 pixels
+    or more than 8 frames run pair-major); compared as case_energy compares."""
+    depth = int(rng.integers(9, 17))
+    n = 2 ** depth
+    X, Y = (int(rng.integers(1, 30)), int(rng.integers(1, 30))) if rng.random() < 0.8 else (130, int(rng.integers(126, 140)))
+    N = int(rng.choice([2, 3, 5, 7, 8, 9, 12]))
+    B = int(rng.choice([1, 3, 8, 20]))
+    variant = int(rng.choice([1, 2] if depth <= 14 else [2]))
+    dn = np.sort(rng.integers(0, n, (X, Y, N)), axis=2)
+    dn = (dn | (rng.integers(0, 2 ** (16 - depth), dn.shape) << depth)).astype(np.uint16)          # stray high bits: masked by both builds
+    sd = 0.004 * (1 + rng.random((X, Y, N))) if rng.random() < 0.5 else None
+    if sd is not None and rng.random() < 0.3:
+        sd[rng.random(sd.shape) < 0.05] = 0.0
+    t = np.sort(rng.uniform(1e-3, 1.0, size=N)) + np.arange(N) * 1e-4
+    cands = np.linspace(0, 1, n)[None, :] ** rng.uniform(0.5, 2.5, size=B)[:, None]
+    valid = rng.random(B) < 0.8
+    lower, upper = int(rng.integers(0, n // 6)), int(rng.integers(n - n // 5, n))
+    rel = bool(rng.random() < 0.7)
+    kernel = engine.energy_kernel(X * Y, N, B, sd is not None, depth, variant)
+    desc = f"energy_u16 {X}x{Y}x{N} B={B} bits={depth} std={sd is not None} rel={rel} limits=({lower},{upper}) {kernel}"
+    ea, pa = engine.linearity_energy(D(dn), D(sd), t, cands, lower, upper, valid, rel, return_pairs=True, bit_depth=depth, variant=variant)
+    eb, pb = heng.linearity_energy(Hh(dn), Hh(sd), t, cands, lower, upper, valid, rel, return_pairs=True, bit_depth=depth)
+    compare("energy", ea, eb, 1e-11)
+    compare("pairs", pa, pb, 1e-11)
+    return desc
+
+
 def case_series(rng):
     """The drop-in classes end to end on both backends: ImageSet(value=uint8 frame, std) x N -> ExposureSeries.process_HDR_image(ICRF,
     ICRF_diff, dark_list, flat_list) with the reference's dark-frame rule (exact-exposure dark, else the next longer one scaled by t / t_dark,
@@ -975,7 +1004,7 @@ def case_linearize_u16(rng):
 
 
 CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
     assert CASES, f"--only {args.only}: no such generator"
