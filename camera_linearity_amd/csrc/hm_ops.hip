@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void k_binary_burst(const double* __restrict__
 __global__ __launch_bounds__(256) void k_unary(int op, const double* __restrict__ x, const double* __restrict__ s,
                                                double* __restrict__ out, double* __restrict__ out_std, int64_t n) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double ln10 = log(5.0) + log(2.0);                   // measurand.py:277
+    const double ln10 = 0x1.26bb1bbb55515p+1;                  // fl(log 5) + fl(log 2), the constant measurand.py:277 forms (hm_host.cpp holds the same literal)
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
         const double v = x[e];
         double r, rs = 0.0;
@@ -182,7 +182,10 @@ template <int KIND>
 __device__ __forceinline__ void pow_scalar_eval(double x, double s, double p, int ip, bool with_std, double& r, double& rs) {
     double d;                                               // x ** (p - 1)
     if (KIND == POW_SQUARE) { r = x * x; d = x; }
-    else if (KIND == POW_SQRT) { r = sqrt(x); d = 1.0 / r; }
+    else if (KIND == POW_SQRT) {                            // sqrt: the correctly rounded x ** 0.5. NumPy's pow() differs from it at two arguments only:
+        const double ax = (x == 0.0 || x == -__builtin_huge_val()) ? fabs(x) : x;       // -inf -> +inf (d = +0) and -0.0 -> +0.0 (d = +inf)
+        r = sqrt(ax); d = 1.0 / r;
+    }
     else if (KIND == POW_ONE) { r = x; d = 1.0; }
     else if (KIND == POW_INT) {                             // |ip| <= 8: x**(|ip|-1) by multiplication, one more for the value
         const int n = ip < 0 ? -ip : ip;
@@ -331,7 +334,7 @@ extern "C" int hm_binary_op(int op, const double* x1, const double* s1, const do
     int64_t n = 1;
     bool dense = true;
     for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] < 0) return HM_EINVAL;
+        if (shape[d] < 0 || strides1[d] < 0 || strides2[d] < 0) return HM_EINVAL;          // as the _bcast entries (hm_pointwise.hip: fill_bcast)
         b.shape[d] = shape[d]; b.st1[d] = strides1[d]; b.st2[d] = strides2[d];
         if (shape[d] != 1 && (strides1[d] != n || strides2[d] != n)) dense = false;
         n *= shape[d];

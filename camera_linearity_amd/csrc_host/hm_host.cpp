@@ -780,7 +780,7 @@ int hm_unary_op(int op, const double* x, const double* s, double* out_val, doubl
     if (op < HM_UOP_NEG || op > HM_UOP_LOG_10 || n < 0) return HM_EINVAL;
     if (n == 0) return HM_OK;
     if (!x || !out_val || ((out_std != nullptr) != (s != nullptr))) return HM_EINVAL;
-    const double ln10 = std::log(10.0);
+    const double ln10 = 0x1.26bb1bbb55515p+1;                  // fl(log 5) + fl(log 2), the constant measurand.py:277 forms (hm_ops.hip holds the same literal)
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
         const double v = x[e];
@@ -804,7 +804,10 @@ int hm_pow_scalar(const double* x, const double* s, double exponent, double* out
         const double v = x[e];
         double r, d;                                                                                     // d = x ** (p - 1)
         if (p == 2.0) { r = v * v; d = v; }
-        else if (p == 0.5) { r = std::sqrt(v); d = 1.0 / r; }
+        else if (p == 0.5) {                                    // sqrt: the correctly rounded x ** 0.5. NumPy's pow() differs from it at two arguments only:
+            const double av = (v == 0.0 || v == -kInf) ? std::fabs(v) : v;              // -inf -> +inf (d = +0) and -0.0 -> +0.0 (d = +inf)
+            r = std::sqrt(av); d = 1.0 / r;
+        }
         else if (p == 1.0) { r = v; d = 1.0; }
         else { r = std::pow(v, p); d = std::pow(v, p - 1.0); }
         out_val[e] = r;
@@ -840,9 +843,10 @@ int hm_take_axis(const double* x, const double* s, double* out_val, double* out_
 
 // ---- linearity statistics ----------------------------------------------------------------------------
 int hm_apply_thresholds(double* val, double* std_, const double* lower, const double* upper, int64_t n, int C, void*) {
-    if (n < 0 || C < 1 || C > HM_THRESHOLD_MAX_CHANNELS) return HM_EINVAL;
+    if (n < 0 || C < 1 || !lower || !upper) return HM_EINVAL;
+    if (C > HM_THRESHOLD_MAX_CHANNELS) return HM_EUNSUPPORTED;
     if (n == 0) return HM_OK;
-    if (!val || !lower || !upper) return HM_EINVAL;
+    if (!val) return HM_EINVAL;
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
         const int c = static_cast<int>(e % C);

@@ -365,7 +365,10 @@ int hm_normalize_by_map(const double* val, const double* std,
  * Row 10 - Measurand operators with first-order uncertainty propagation
  * (modules/measurand.py:106-279). Operands broadcast NumPy-style: `shape` is the broadcast result
  * shape (ndim <= 6), strides are in ELEMENTS with 0 on broadcast axes. s1 / s2 may be NULL (treated
- * as zeros, :121-124); out_std must be NULL iff both are NULL.
+ * as zeros, :121-124); out_std must be NULL iff both are NULL. Strides are non-negative and need not be dense (an operand may be a
+ * strided slice of a larger allocation); a negative stride or extent, ndim outside 1..HM_MAX_DIMS and an unknown op are HM_EINVAL;
+ * an extent of 0 returns HM_OK and writes nothing.
+ * hm_unary_op LOG_10: std = s / (x * ln10) with ln10 = 0x1.26bb1bbb55515p+1, the float64 sum log(5) + log(2) of :277, as a literal.
  * ------------------------------------------------------------------------------------------ */
 enum { HM_OP_ADD = 0, HM_OP_SUB = 1, HM_OP_MUL = 2, HM_OP_DIV = 3, HM_OP_POW = 4 };
 enum { HM_UOP_NEG = 0, HM_UOP_LOG_E = 1, HM_UOP_LOG_10 = 2 };
@@ -379,7 +382,8 @@ int hm_unary_op(int op, const double* x, const double* s, double* out_val, doubl
 /* Measurand.__pow__ with a plain scalar exponent (modules/measurand.py:217-241; `S ** 2`, `** (1/2)` of the merge loop,
  * modules/exposure_series.py:343,394): out = x ** exponent, out_std = |exponent * x ** (exponent - 1)| * s (the exponent
  * has no uncertainty; its term of :237-238 is evaluated only where it is not +0). Exponents 2, 0.5, 1 and integers in
- * [-8, 8] avoid pow(). s / out_std are NULL together. */
+ * [-8, 8] avoid pow(). Exponent 0.5 is sqrt(x), the correctly rounded value, except where NumPy's pow() answers otherwise:
+ * x = -inf gives +inf (x ** -0.5 of the std: +0) and x = -0.0 gives +0.0 (x ** -0.5: +inf). s / out_std are NULL together. */
 int hm_pow_scalar(const double* x, const double* s /*nullable*/, double exponent, double* out_val, double* out_std /*nullable*/,
                   int64_t n, void* stream);
 
@@ -402,7 +406,7 @@ int hm_take_axis(const double* x, const double* s, double* out_val, double* out_
  *                           weighted by 1/std when std is given, plus error = nanmean(std). out is 3*C
  *                           float64 on the device: [mean | std | error]; error is NaN without std.
  * ------------------------------------------------------------------------------------------ */
-#define HM_THRESHOLD_MAX_CHANNELS 32   /* hm_apply_thresholds: channels on the last axis (a slower one-element-per-thread kernel above HM_MAX_CHANNELS) */
+#define HM_THRESHOLD_MAX_CHANNELS 32   /* hm_apply_thresholds: channels on the last axis (a slower one-element-per-thread kernel above HM_MAX_CHANNELS); more: HM_EUNSUPPORTED */
 int hm_apply_thresholds(double* val, double* std /*nullable*/, const double* lower /*[host] C*/,
                         const double* upper /*[host] C*/, int64_t n, int C, void* stream);
 int hm_compute_difference(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
@@ -493,7 +497,8 @@ int hm_axis_statistics2(const double* val, const double* std /*nullable*/, int64
                         double* out_mean, double* out_std, double* out_err /*nullable*/, void* workspace, void* stream);
 /* compute_difference / interpolate on operands that BROADCAST against each other (the reference applies NumPy broadcasting,
  * modules/measurand.py:621-681): `shape` is the broadcast result shape (ndim <= HM_MAX_DIMS), strides are in ELEMENTS with 0 on
- * broadcast axes (as hm_binary_op); an operand and its std share strides. Outputs are dense arrays of that shape. */
+ * broadcast axes (as hm_binary_op, with the same HM_EINVAL for negative strides or extents and HM_OK for an extent of 0); an operand
+ * and its std share strides. Outputs are dense arrays of that shape. */
 int hm_compute_difference_bcast(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
                                 double* out_abs, double* out_abs_std, double* out_rel, double* out_rel_std,
                                 int ndim, const int64_t* shape /*[host]*/, const int64_t* strides_x /*[host]*/,

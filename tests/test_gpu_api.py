@@ -400,7 +400,7 @@ def test_pow_scalar_exponent(M, p):
     close(r.val, rv, 1e-14)
     np.testing.assert_allclose(r.std.cpu().numpy(), rs, rtol=1e-13)
     assert (M(a) ** p).std is None
-    odd = np.array([0.0, -1.5, 2.0, np.inf, 0.25, 1.0, -0.0])                 # odd length: the scalar tail of the 2-per-lane kernel
+    odd = np.array([0.0, -1.5, 2.0, np.inf, 0.25, 1.0, -0.0, -np.inf, 0.5])   # odd length: the scalar tail of the 2-per-lane kernel
     with np.errstate(all="ignore"):
         ov, os_ = orc.op_pow(odd, 0.1 * np.abs(odd) + 0.01, np.array([float(p)]), None)
     got = M(odd, 0.1 * np.abs(odd) + 0.01) ** p
