@@ -1,7 +1,7 @@
 // hm_api.hip - version / error strings / device query / host-side weight table of libhdrmerge.
 #include "hm_common.h"
 #include "hdrmerge_debug.h"
-#include <cmath>
+#include "hm_frame_rules.h"
 #include <cstring>
 
 extern "C" int hm_version(void) { return HM_ABI_VERSION; }
@@ -32,30 +32,10 @@ extern "C" int hm_device_info(int* n_devices, int* cu_count, int* lds_bytes, cha
     return HM_OK;
 }
 
-// modules/measurand.py:615-616 on the DN grid v = k/255, evaluated with libm
-extern "C" int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) {
-    if (!w_lut && !dw_lut) return HM_EINVAL;
-    for (int k = 0; k < HM_BITS; ++k) {
-        const double v = static_cast<double>(k) / 255.0;
-        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
-        if (w_lut) w_lut[k] = y;
-        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
-    }
-    return HM_OK;
-}
-
-// the same formula on the grid v = k / (2^bit_depth - 1): the tables of hm_merge_u16 (bit_depth = 8: the tables above)
+// modules/measurand.py:615-616 on the DN grid v = k/255 and on the grid v = k / (2^bit_depth - 1) of hm_merge_u16: hm_frame_rules.h
+extern "C" int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) { return hm_rules::gaussian_weight_lut(8, w_lut, dw_lut); }
 extern "C" int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut, double* dw_lut) {
-    if ((!w_lut && !dw_lut) || bit_depth < 8 || bit_depth > 16) return HM_EINVAL;
-    const int n = 1 << bit_depth;
-    const double max_dn = static_cast<double>(n - 1);
-    for (int k = 0; k < n; ++k) {
-        const double v = static_cast<double>(k) / max_dn;
-        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
-        if (w_lut) w_lut[k] = y;
-        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
-    }
-    return HM_OK;
+    return hm_rules::gaussian_weight_lut(bit_depth, w_lut, dw_lut);
 }
 
 // number of CUs of the current device (hm_common.h; every unit sizes its grids with it)

@@ -5,6 +5,7 @@
 // All are streaming kernels: 2 elements per lane for uint8 input (ushort load, one 16-byte store that makes
 // every store instruction a contiguous 1 KB), LUTs staged in LDS, grid-stride loops.
 #include "hm_common.h"
+#include "hm_frame_rules.h"
 
 namespace hm {
 
@@ -289,11 +290,7 @@ using namespace hm;
 
 extern "C" int hm_linearize_u16(const uint16_t* dn, const double* std, const double* icrf, const double* icrf_diff,
                                 double* out_val, double* out_std, uint16_t* out_idx, int64_t n, int C, int lut_stride, int bit_depth, void* stream) {
-    if (n < 0 || C < 1 || !icrf || (n > 0 && (!dn || !out_val))) return HM_EINVAL;
-    if ((lut_stride != 1 && lut_stride != C) || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!aligned(dn, 2) || (out_idx && !aligned(out_idx, 2)) || !aligned(out_val, 8) || (out_std && !aligned(out_std, 8)) || (std && !aligned(std, 8)))
-        return HM_EALIGN;
+    if (const int rc = hm_rules::check_linearize_u16(dn, std, icrf, out_val, out_std, out_idx, n, C, lut_stride, bit_depth); rc != HM_OK || n == 0) return rc;
     const bool with_std = std && icrf_diff && out_std;                       // measurand.py:498-500
     const unsigned grid = stream_grid(n, 256, 8);
     const uint32_t mask = (1u << bit_depth) - 1u;
@@ -342,12 +339,7 @@ extern "C" int hm_gaussian_weight_u8(const uint8_t* dn, const double* w_lut, con
 
 static int linearize_common(bool f64in, const void* in, const double* sd, const double* icrf, const double* icrf_diff,
                             double* out_val, double* out_std, uint8_t* out_idx, int64_t n, int C, int lut_stride, void* stream) {
-    if (n < 0 || C < 1 || !icrf || (n > 0 && (!in || !out_val))) return HM_EINVAL;
-    if (lut_stride != 1 && lut_stride != C) return HM_EINVAL;
-    if (C > HM_MAX_CHANNELS && lut_stride != 1) return HM_EUNSUPPORTED;
-    if (n == 0) return HM_OK;
-    if (!aligned(out_val, 8) || (out_std && !aligned(out_std, 8)) || (sd && !aligned(sd, 8)) || (f64in && !aligned(in, 8)))
-        return HM_EALIGN;
+    if (const int rc = hm_rules::check_linearize(f64in, in, sd, icrf, out_val, out_std, n, C, lut_stride, hm_rules::DEVICE); rc != HM_OK || n == 0) return rc;
     const bool with_std = sd && icrf_diff && out_std;                       // measurand.py:498-500
     hipStream_t st = as_stream(stream);
     // streaming kernel for the body (whole groups of 384 elements) when the shape and the alignment allow it

@@ -2,6 +2,7 @@
 // Formulas and operation order of modules/measurand.py:106-279 (add/sub/neg/div/mul/pow/log_e/log_10);
 // operands broadcast NumPy-style through element strides (0 on broadcast axes).
 #include "hm_common.h"
+#include "hm_ops_rules.h"
 
 namespace hm {
 
@@ -304,19 +305,11 @@ using namespace hm;
 
 extern "C" int hm_take_axis(const double* x, const double* s, double* out_val, double* out_std, int64_t outer, int64_t axis_len,
                             int64_t inner, const int64_t* indices, int n_indices, void* stream) {
-    if (!x || !out_val || !indices || outer < 0 || axis_len < 1 || inner < 1 || n_indices < 1) return HM_EINVAL;
-    if (n_indices > HM_TAKE_MAX) return HM_EUNSUPPORTED;
-    if ((out_std != nullptr) != (s != nullptr)) return HM_EINVAL;
     TakeK t{};
+    if (const int rc = hm_rules::check_take_axis(x, s, out_val, out_std, outer, axis_len, inner, indices, n_indices, hm_rules::DEVICE, [&] { return t.idx; });
+        rc != HM_OK || outer == 0) return rc;
     t.n_idx = n_indices;
-    for (int q = 0; q < n_indices; ++q) {
-        int64_t v = indices[q];
-        if (v < 0) v += axis_len;                          // NumPy's negative indices
-        if (v < 0 || v >= axis_len) return HM_ESHAPE;      // np.take raises IndexError (mode='raise')
-        t.idx[q] = v;
-    }
     const int64_t n = outer * n_indices * inner;
-    if (n == 0) return HM_OK;
     hipLaunchKernelGGL(k_take, dim3(stream_grid(n, 256, 8)), dim3(256), 0, as_stream(stream), x, s, out_val, out_std, outer, axis_len, inner, t);
     return launch_status();
 }
@@ -324,23 +317,19 @@ extern "C" int hm_take_axis(const double* x, const double* s, double* out_val, d
 extern "C" int hm_binary_op(int op, const double* x1, const double* s1, const double* x2, const double* s2,
                             double* out_val, double* out_std, int ndim, const int64_t* shape,
                             const int64_t* strides1, const int64_t* strides2, void* stream) {
-    if (op < HM_OP_ADD || op > HM_OP_POW || ndim < 1 || ndim > HM_MAX_DIMS || !shape || !strides1 || !strides2)
-        return HM_EINVAL;
-    if (!x1 || !x2 || !out_val) return HM_EINVAL;
-    if ((out_std != nullptr) != (s1 != nullptr || s2 != nullptr)) return HM_EINVAL;
-    if (!aligned(x1, 8) || !aligned(x2, 8) || !aligned(out_val, 8)) return HM_EALIGN;
+    int64_t n;
+    if (const int rc = hm_rules::check_binary_op(op, x1, s1, x2, s2, out_val, out_std, ndim, shape, strides1, strides2, hm_rules::DEVICE, n);
+        rc != HM_OK || n == 0) return rc;
     BcastK b{};
     b.ndim = ndim;
-    int64_t n = 1;
+    int64_t below = 1;                                       // the element count of the dimensions after d
     bool dense = true;
     for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] < 0 || strides1[d] < 0 || strides2[d] < 0) return HM_EINVAL;          // as the _bcast entries (hm_pointwise.hip: fill_bcast)
         b.shape[d] = shape[d]; b.st1[d] = strides1[d]; b.st2[d] = strides2[d];
-        if (shape[d] != 1 && (strides1[d] != n || strides2[d] != n)) dense = false;
-        n *= shape[d];
+        if (shape[d] != 1 && (strides1[d] != below || strides2[d] != below)) dense = false;
+        below *= shape[d];
     }
     b.contiguous = dense ? 1 : 0;
-    if (n == 0) return HM_OK;
     hipStream_t st = as_stream(stream);
     const bool al16 = aligned(x1, 16) && aligned(x2, 16) && aligned(out_val, 16) && (!s1 || aligned(s1, 16)) && (!s2 || aligned(s2, 16)) &&
                       (!out_std || aligned(out_std, 16));
@@ -397,19 +386,13 @@ extern "C" int hm_binary_op(int op, const double* x1, const double* s1, const do
 
 extern "C" int hm_unary_op(int op, const double* x, const double* s, double* out_val, double* out_std,
                            int64_t n, void* stream) {
-    if (op < HM_UOP_NEG || op > HM_UOP_LOG_10 || n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !out_val || ((out_std != nullptr) != (s != nullptr))) return HM_EINVAL;
-    if (!aligned(x, 8) || !aligned(out_val, 8)) return HM_EALIGN;
+    if (const int rc = hm_rules::check_unary_op(op, x, s, out_val, out_std, n, hm_rules::DEVICE); rc != HM_OK || n == 0) return rc;
     hipLaunchKernelGGL(k_unary, dim3(stream_grid(n, 256, 8)), dim3(256), 0, as_stream(stream), op, x, s, out_val, out_std, n);
     return launch_status();
 }
 
 extern "C" int hm_pow_scalar(const double* x, const double* s, double exponent, double* out_val, double* out_std, int64_t n, void* stream) {
-    if (n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !out_val || ((out_std != nullptr) != (s != nullptr))) return HM_EINVAL;
-    if (!aligned(x, 8) || !aligned(out_val, 8)) return HM_EALIGN;
+    if (const int rc = hm_rules::check_unary_op(HM_UOP_NEG, x, s, out_val, out_std, n, hm_rules::DEVICE); rc != HM_OK || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     const double p = exponent;
     const bool small = p >= -8.0 && p <= 8.0;                       // range first: double -> int is undefined outside int's range and for NaN

@@ -5,12 +5,9 @@
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call. There is no
 // difference between the builds: both ask for the workspace and for 8-byte-aligned frames.
 #pragma once
-#include "hdrmerge.h"
-#include <cstdint>
+#include "hm_rules_common.h"
 
 namespace hm_rules {
-
-inline bool pairs_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // the three entries' common arguments; vals, stds (n_frames entries) and pair_i, pair_j (n_pairs entries) are host arrays in both builds
 inline int check_pairs(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
@@ -21,7 +18,7 @@ inline int check_pairs(const double* const* vals, const double* const* stds, int
     for (int i = 0; i < n_frames; ++i)
         if (!vals[i] || (stds && !stds[i])) return HM_EINVAL;
     for (int i = 0; i < n_frames; ++i)
-        if (!pairs_aligned8(vals[i]) || (stds && !pairs_aligned8(stds[i]))) return HM_EALIGN;
+        if (!aligned8(vals[i]) || (stds && !aligned8(stds[i]))) return HM_EALIGN;
     for (int p = 0; p < n_pairs; ++p)
         if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
     return HM_OK;

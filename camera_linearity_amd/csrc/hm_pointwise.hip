@@ -5,6 +5,7 @@
 //   hm_compute_difference_bcast, hm_interpolate_bcast    the same two on broadcast operands   modules/measurand.py:621-681
 // Streaming, HBM-bound. The statistics of the row: hm_stats.hip, hm_stats_hist.hip, hm_stats_axis.hip.
 #include "hm_pointwise.h"
+#include "hm_ops_rules.h"
 
 namespace hm {
 
@@ -304,16 +305,12 @@ __global__ __launch_bounds__(256) void k_interpolate_bcast(const double* __restr
     }
 }
 
-static bool fill_bcast(Bcast2K& b, int ndim, const int64_t* shape, const int64_t* st1, const int64_t* st2, int64_t& n) {
-    if (ndim < 1 || ndim > HM_MAX_DIMS || !shape || !st1 || !st2) return false;
-    n = 1;
+// the kernel argument of a checked broadcast (hm_rules::check_bcast)
+static Bcast2K fill_bcast(int ndim, const int64_t* shape, const int64_t* st1, const int64_t* st2) {
+    Bcast2K b;
     b.ndim = ndim;
-    for (int d = 0; d < ndim; ++d) {
-        if (shape[d] < 0 || st1[d] < 0 || st2[d] < 0) return false;
-        b.shape[d] = shape[d]; b.st1[d] = st1[d]; b.st2[d] = st2[d];
-        n *= shape[d];
-    }
-    return true;
+    for (int d = 0; d < ndim; ++d) { b.shape[d] = shape[d]; b.st1[d] = st1[d]; b.st2[d] = st2[d]; }
+    return b;
 }
 
 void launch_thresholds(double* val, double* sd, const ChanLimits& lim, int64_t n, int C, hipStream_t st) {
@@ -326,11 +323,7 @@ using namespace hm;
 
 extern "C" int hm_apply_thresholds(double* val, double* std, const double* lower, const double* upper,
                                    int64_t n, int C, void* stream) {
-    if (n < 0 || C < 1 || !lower || !upper) return HM_EINVAL;
-    if (C > HM_THRESHOLD_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (n == 0) return HM_OK;
-    if (!val) return HM_EINVAL;
-    if (!aligned(val, 8) || (std && !aligned(std, 8))) return HM_EALIGN;
+    if (const int rc = hm_rules::check_apply_thresholds(val, std, lower, upper, n, C, hm_rules::DEVICE); rc != HM_OK || n == 0) return rc;
     if (C > HM_MAX_CHANNELS) {
         ChanLimitsWide w{};
         for (int c = 0; c < C; ++c) { w.lo[c] = lower[c]; w.hi[c] = upper[c]; }
@@ -346,11 +339,10 @@ extern "C" int hm_apply_thresholds(double* val, double* std, const double* lower
 extern "C" int hm_compute_difference(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
                                      double* out_abs, double* out_abs_std, double* out_rel, double* out_rel_std,
                                      int64_t n, void* stream) {
-    if (n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !y || !out_abs || !out_rel) return HM_EINVAL;
+    int64_t one = 1, count;                 // checked as the _bcast form on shape {n}, strides {1}: n < 0 is its negative extent, n == 0 its "no element"
+    if (const int rc = hm_rules::check_compute_difference_bcast(x, sx, y, sy, out_abs, out_abs_std, out_rel, out_rel_std, 1, &n, &one, &one, count);
+        rc != HM_OK || n == 0) return rc;
     const bool with_std = sx || sy;
-    if (with_std != (out_abs_std != nullptr) || with_std != (out_rel_std != nullptr)) return HM_EINVAL;
     const bool al16 = aligned(x, 16) && aligned(y, 16) && aligned(out_abs, 16) && aligned(out_rel, 16) && (!sx || aligned(sx, 16)) &&
                       (!sy || aligned(sy, 16)) && (!with_std || (aligned(out_abs_std, 16) && aligned(out_rel_std, 16)));
     if (al16) {
@@ -382,9 +374,8 @@ extern "C" int hm_compute_difference(const double* x, const double* sx, const do
 
 extern "C" int hm_interpolate(const double* x0, const double* s0, const double* x1, const double* s1,
                               double y0, double y1, double y, double* out, double* out_std, int64_t n, void* stream) {
-    if (n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x0 || !x1 || !out || ((s0 || s1) != (out_std != nullptr))) return HM_EINVAL;
+    int64_t one = 1, count;                 // checked as the _bcast form on shape {n}, strides {1}: n < 0 is its negative extent, n == 0 its "no element"
+    if (const int rc = hm_rules::check_interpolate_bcast(x0, s0, x1, s1, out, out_std, 1, &n, &one, &one, count); rc != HM_OK || n == 0) return rc;
     const bool al16 = aligned(x0, 16) && aligned(x1, 16) && aligned(out, 16) && (!s0 || aligned(s0, 16)) && (!s1 || aligned(s1, 16)) &&
                       (!out_std || aligned(out_std, 16));
     const int64_t n_chunks = n / kDiffChunk;
@@ -409,13 +400,10 @@ extern "C" int hm_interpolate(const double* x0, const double* s0, const double* 
 extern "C" int hm_compute_difference_bcast(const double* x, const double* sx, const double* y, const double* sy, double multiplier,
                                            double* out_abs, double* out_abs_std, double* out_rel, double* out_rel_std,
                                            int ndim, const int64_t* shape, const int64_t* strides_x, const int64_t* strides_y, void* stream) {
-    hm::Bcast2K b;
-    int64_t n = 0;
-    if (!hm::fill_bcast(b, ndim, shape, strides_x, strides_y, n)) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !y || !out_abs || !out_rel) return HM_EINVAL;
-    const bool with_std = sx || sy;
-    if (with_std != (out_abs_std != nullptr) || with_std != (out_rel_std != nullptr)) return HM_EINVAL;
+    int64_t n;
+    if (const int rc = hm_rules::check_compute_difference_bcast(x, sx, y, sy, out_abs, out_abs_std, out_rel, out_rel_std, ndim, shape, strides_x,
+                                                            strides_y, n); rc != HM_OK || n == 0) return rc;
+    const hm::Bcast2K b = hm::fill_bcast(ndim, shape, strides_x, strides_y);
     hipLaunchKernelGGL(hm::k_difference_bcast, dim3(hm::stream_grid(n, 256, 8)), dim3(256), 0, hm::as_stream(stream),
                        x, sx, y, sy, multiplier, out_abs, out_abs_std, out_rel, out_rel_std, n, b);
     return hm::launch_status();
@@ -424,11 +412,9 @@ extern "C" int hm_compute_difference_bcast(const double* x, const double* sx, co
 extern "C" int hm_interpolate_bcast(const double* x0, const double* s0, const double* x1, const double* s1, double y0, double y1, double y,
                                     double* out, double* out_std, int ndim, const int64_t* shape, const int64_t* strides0,
                                     const int64_t* strides1, void* stream) {
-    hm::Bcast2K b;
-    int64_t n = 0;
-    if (!hm::fill_bcast(b, ndim, shape, strides0, strides1, n)) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x0 || !x1 || !out || ((s0 || s1) != (out_std != nullptr))) return HM_EINVAL;
+    int64_t n;
+    if (const int rc = hm_rules::check_interpolate_bcast(x0, s0, x1, s1, out, out_std, ndim, shape, strides0, strides1, n); rc != HM_OK || n == 0) return rc;
+    const hm::Bcast2K b = hm::fill_bcast(ndim, shape, strides0, strides1);
     hipLaunchKernelGGL(hm::k_interpolate_bcast, dim3(hm::stream_grid(n, 256, 8)), dim3(256), 0, hm::as_stream(stream),
                        x0, s0, x1, s1, y0, y1, y, out, out_std, n, b);
     return hm::launch_status();

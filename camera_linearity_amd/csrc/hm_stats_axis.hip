@@ -9,7 +9,7 @@
 //                   thread count that is a multiple of inner (every thread keeps ONE channel), then folds threads of equal channel.
 // Both split A into KS segments (grid dimension) when there are too few outputs to fill the chip; k_axis_final folds the segments.
 #include "hm_moments.h"
-#include <initializer_list>
+#include "hm_rules_common.h"
 
 namespace hm {
 
@@ -216,16 +216,6 @@ __global__ __launch_bounds__(256) void k_axis_final2_tree(const double* __restri
     if (threadIdx.x == 0) axis_finish_store(mom_load(tree[0]), f.weighted != 0, j, out_mean, out_std, out_err);
 }
 
-// the element count of a dense block of the given extents, or -1 when an extent is < 1 or the product does not fit (absurd arguments must
-// come back as HM_EINVAL / 0, not as an integer overflow inside the launch arithmetic)
-static int64_t dense_elems(std::initializer_list<int64_t> dims) {
-    int64_t n = 1;
-    for (int64_t d : dims) {
-        if (d < 1 || __builtin_mul_overflow(n, d, &n) || n > (int64_t{1} << 48)) return -1;
-    }
-    return n;
-}
-
 struct AxisPlan { bool row; int KS; };
 static AxisPlan axis_plan(int64_t outer, int64_t A, int64_t inner) {
     AxisPlan p;
@@ -280,7 +270,7 @@ static Axis2Plan axis2_plan(int64_t outer, int64_t a1, int64_t mid, int64_t a2, 
 }  // namespace hm
 
 extern "C" size_t hm_axis_statistics_workspace_bytes(int64_t outer, int64_t axis_len, int64_t inner) {
-    if (hm::dense_elems({outer, axis_len, inner}) < 0) return 0;
+    if (hm_rules::dense_elems({outer, axis_len, inner}) < 0) return 0;
     const hm::AxisPlan p = hm::axis_plan(outer, axis_len, inner);
     return p.KS > 1 ? static_cast<size_t>(p.KS) * static_cast<size_t>(outer * inner) * hm::kMomVals * sizeof(double) : 0;
 }
@@ -288,7 +278,7 @@ extern "C" size_t hm_axis_statistics_workspace_bytes(int64_t outer, int64_t axis
 extern "C" int hm_axis_statistics(const double* val, const double* std, int64_t outer, int64_t axis_len, int64_t inner,
                                   double* out_mean, double* out_std, double* out_err, void* workspace, void* stream) {
     using namespace hm;
-    if (dense_elems({outer, axis_len, inner}) < 0 || !val || !out_mean || !out_std) return HM_EINVAL;
+    if (hm_rules::dense_elems({outer, axis_len, inner}) < 0 || !val || !out_mean || !out_std) return HM_EINVAL;
     if (!aligned(val, 8) || (std && !aligned(std, 8))) return HM_EALIGN;
     const AxisPlan p = axis_plan(outer, axis_len, inner);
     if (p.KS > 1 && !workspace) return HM_EINVAL;
@@ -306,7 +296,7 @@ extern "C" int hm_axis_statistics(const double* val, const double* std, int64_t 
 }
 
 extern "C" size_t hm_axis_statistics2_workspace_bytes(int64_t outer, int64_t a1, int64_t mid, int64_t a2, int64_t inner) {
-    if (hm::dense_elems({outer, a1, mid, a2, inner}) < 0) return 0;
+    if (hm_rules::dense_elems({outer, a1, mid, a2, inner}) < 0) return 0;
     const hm::Axis2Plan q = hm::axis2_plan(outer, a1, mid, a2, inner);
     return static_cast<size_t>(q.p.KS) * static_cast<size_t>(q.f.n_out1) * hm::kMomVals * sizeof(double);
 }
@@ -314,7 +304,7 @@ extern "C" size_t hm_axis_statistics2_workspace_bytes(int64_t outer, int64_t a1,
 extern "C" int hm_axis_statistics2(const double* val, const double* std, int64_t outer, int64_t a1, int64_t mid, int64_t a2, int64_t inner,
                                    double* out_mean, double* out_std, double* out_err, void* workspace, void* stream) {
     using namespace hm;
-    if (dense_elems({outer, a1, mid, a2, inner}) < 0 || !val || !out_mean || !out_std || !workspace) return HM_EINVAL;
+    if (hm_rules::dense_elems({outer, a1, mid, a2, inner}) < 0 || !val || !out_mean || !out_std || !workspace) return HM_EINVAL;
     if (!aligned(val, 8) || (std && !aligned(std, 8))) return HM_EALIGN;
     Axis2Plan q = axis2_plan(outer, a1, mid, a2, inner);
     q.f.weighted = std ? 1 : 0;

@@ -12,9 +12,14 @@
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
 // hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twin of
 // hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
+//
+// The argument rules of most entries are a check_* of the ../csrc/hm_*_rules.h headers included below, the copies the device build compiles
+// too; where this build differs the check is called with hm_rules::HOST, and the header's top comment lists the difference.
 #include "hdrmerge.h"
 #include "../csrc/hm_merge_rules.h"
 #include "../csrc/hm_calibration_rules.h"
+#include "../csrc/hm_frame_rules.h"
+#include "../csrc/hm_ops_rules.h"
 #include "../csrc/hm_pairs_rules.h"
 #include "../csrc/hm_producer_rules.h"
 #include "../csrc/hm_tiff_rules.h"
@@ -35,16 +40,7 @@ namespace {
 
 constexpr double kNaN = std::numeric_limits<double>::quiet_NaN();
 constexpr double kInf = std::numeric_limits<double>::infinity();
-
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-// the element count of a dense block of the given extents, or -1 when an extent is < 1 or the product is above 2^48 (as the HIP build)
-inline int64_t dense_elems(std::initializer_list<int64_t> dims) {
-    int64_t n = 1;
-    for (int64_t d : dims)
-        if (d < 1 || __builtin_mul_overflow(n, d, &n) || n > (int64_t{1} << 48)) return -1;
-    return n;
-}
+using hm_rules::aligned8, hm_rules::dense_elems;
 
 // measurand.py:615: w = e ** (-30 (v - 0.5)^2)
 inline double gauss_weight(double dv) { return std::exp(-30.0 * (dv * dv)); }
@@ -113,28 +109,14 @@ inline void flat_field_math(double F, double sF, double m, double s, bool with_s
     val = (val / F) * m;
 }
 
-struct Bcast {
-    int ndim;
-    int64_t shape[HM_MAX_DIMS], st1[HM_MAX_DIMS], st2[HM_MAX_DIMS];
-    int64_t n;
-};
-bool fill_bcast(Bcast& b, int ndim, const int64_t* shape, const int64_t* s1, const int64_t* s2) {
-    if (ndim < 1 || ndim > HM_MAX_DIMS || !shape || !s1 || !s2) return false;
-    b.ndim = ndim; b.n = 1;
-    for (int d = 0; d < ndim; ++d) {
-        if (shape[d] < 0 || s1[d] < 0 || s2[d] < 0) return false;
-        b.shape[d] = shape[d]; b.st1[d] = s1[d]; b.st2[d] = s2[d];
-        b.n *= shape[d];
-    }
-    return true;
-}
-inline void bcast_offsets(const Bcast& b, int64_t e, int64_t& o1, int64_t& o2) {
+// the two operands' offsets of element e of a checked broadcast (hm_rules::check_bcast)
+inline void bcast_offsets(int ndim, const int64_t* shape, const int64_t* st1, const int64_t* st2, int64_t e, int64_t& o1, int64_t& o2) {
     o1 = 0; o2 = 0;
-    for (int d = b.ndim - 1; d >= 0; --d) {
-        const int64_t i = e % b.shape[d];
-        e /= b.shape[d];
-        o1 += i * b.st1[d];
-        o2 += i * b.st2[d];
+    for (int d = ndim - 1; d >= 0; --d) {
+        const int64_t i = e % shape[d];
+        e /= shape[d];
+        o1 += i * st1[d];
+        o2 += i * st2[d];
     }
 }
 
@@ -239,29 +221,8 @@ int hm_gaussian_weight_u8(const uint8_t* dn, const double* w_lut, const double* 
     return HM_OK;
 }
 
-int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) {
-    if (!w_lut && !dw_lut) return HM_EINVAL;
-    for (int k = 0; k < HM_BITS; ++k) {
-        const double v = static_cast<double>(k) / 255.0;
-        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
-        if (w_lut) w_lut[k] = y;
-        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
-    }
-    return HM_OK;
-}
-
-int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut, double* dw_lut) {
-    if ((!w_lut && !dw_lut) || bit_depth < 8 || bit_depth > 16) return HM_EINVAL;
-    const int n = 1 << bit_depth;
-    const double max_dn = static_cast<double>(n - 1);
-    for (int k = 0; k < n; ++k) {
-        const double v = static_cast<double>(k) / max_dn;
-        const double y = std::pow(M_E, -30.0 * ((v - 0.5) * (v - 0.5)));
-        if (w_lut) w_lut[k] = y;
-        if (dw_lut) dw_lut[k] = ((-2.0 * 30.0) * (v - 0.5)) * y;
-    }
-    return HM_OK;
-}
+int hm_gaussian_weight_lut_host(double* w_lut, double* dw_lut) { return hm_rules::gaussian_weight_lut(8, w_lut, dw_lut); }
+int hm_gaussian_weight_lut_bits_host(int bit_depth, double* w_lut, double* dw_lut) { return hm_rules::gaussian_weight_lut(bit_depth, w_lut, dw_lut); }
 
 int hm_u8_to_unit_f64(const uint8_t* dn, double* out, int64_t n, void*) {
     if (n < 0 || (n > 0 && (!dn || !out))) return HM_EINVAL;
@@ -272,9 +233,8 @@ int hm_u8_to_unit_f64(const uint8_t* dn, double* out, int64_t n, void*) {
 
 static int linearize_any(const uint8_t* dn, const double* v, const double* std_, const double* icrf, const double* icrf_diff,
                          double* out_val, double* out_std, uint8_t* out_idx, int64_t n, int C, int lut_stride) {
-    if (n < 0 || C < 1 || (lut_stride != 1 && lut_stride != C)) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if ((!dn && !v) || !icrf || !out_val) return HM_EINVAL;
+    if (const int rc = hm_rules::check_linearize(v != nullptr, dn ? static_cast<const void*>(dn) : v, std_, icrf, out_val, out_std, n, C, lut_stride,
+                                                 hm_rules::HOST); rc != HM_OK) return rc;
     const bool use_std = std_ && icrf_diff && out_std;                            // measurand.py:498-500
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
@@ -297,11 +257,7 @@ int hm_linearize_f64(const double* v, const double* std_, const double* icrf, co
 // uint16 DNs: idx = dn & (2^bit_depth - 1), tables of 2^bit_depth rows
 int hm_linearize_u16(const uint16_t* dn, const double* std_, const double* icrf, const double* icrf_diff, double* out_val, double* out_std,
                      uint16_t* out_idx, int64_t n, int C, int lut_stride, int bit_depth, void*) {
-    if (n < 0 || C < 1 || !icrf || (n > 0 && (!dn || !out_val))) return HM_EINVAL;
-    if ((lut_stride != 1 && lut_stride != C) || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if ((reinterpret_cast<uintptr_t>(dn) & 1u) || (reinterpret_cast<uintptr_t>(out_idx) & 1u) || !aligned8(out_val) || (out_std && !aligned8(out_std)) ||
-        (std_ && !aligned8(std_))) return HM_EALIGN;
+    if (const int rc = hm_rules::check_linearize_u16(dn, std_, icrf, out_val, out_std, out_idx, n, C, lut_stride, bit_depth); rc != HM_OK) return rc;
     const bool use_std = std_ && icrf_diff && out_std;                            // measurand.py:498-500
     const uint32_t mask = (1u << bit_depth) - 1u;
 #pragma omp parallel for schedule(static)
@@ -749,15 +705,14 @@ int hm_normalize_by_map(const double* val, const double* std_, const uint8_t* fl
 // ---- row 10: operators (measurand.py:106-279) ----------------------------------------------------------------------
 int hm_binary_op(int op, const double* x1, const double* s1, const double* x2, const double* s2, double* out_val, double* out_std,
                  int ndim, const int64_t* shape, const int64_t* strides1, const int64_t* strides2, void*) {
-    Bcast b;
-    if (op < HM_OP_ADD || op > HM_OP_POW || !fill_bcast(b, ndim, shape, strides1, strides2)) return HM_EINVAL;
-    if (!x1 || !x2 || !out_val) return HM_EINVAL;
-    if ((out_std != nullptr) != (s1 != nullptr || s2 != nullptr)) return HM_EINVAL;
+    int64_t n;
+    if (const int rc = hm_rules::check_binary_op(op, x1, s1, x2, s2, out_val, out_std, ndim, shape, strides1, strides2, hm_rules::HOST, n);
+        rc != HM_OK) return rc;
     const bool with_std = out_std != nullptr;
 #pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < b.n; ++e) {
+    for (int64_t e = 0; e < n; ++e) {
         int64_t o1, o2;
-        bcast_offsets(b, e, o1, o2);
+        bcast_offsets(ndim, shape, strides1, strides2, e, o1, o2);
         const double a = x1[o1], c = x2[o2];
         const double sa = (with_std && s1) ? s1[o1] : 0.0, sc = (with_std && s2) ? s2[o2] : 0.0;       // missing std -> zeros (:121-124)
         double r, rs = 0.0;
@@ -777,9 +732,7 @@ int hm_binary_op(int op, const double* x1, const double* s1, const double* x2, c
 }
 
 int hm_unary_op(int op, const double* x, const double* s, double* out_val, double* out_std, int64_t n, void*) {
-    if (op < HM_UOP_NEG || op > HM_UOP_LOG_10 || n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !out_val || ((out_std != nullptr) != (s != nullptr))) return HM_EINVAL;
+    if (const int rc = hm_rules::check_unary_op(op, x, s, out_val, out_std, n, hm_rules::HOST); rc != HM_OK) return rc;
     const double ln10 = 0x1.26bb1bbb55515p+1;                  // fl(log 5) + fl(log 2), the constant measurand.py:277 forms (hm_ops.hip holds the same literal)
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
@@ -795,9 +748,7 @@ int hm_unary_op(int op, const double* x, const double* s, double* out_val, doubl
 }
 
 int hm_pow_scalar(const double* x, const double* s, double exponent, double* out_val, double* out_std, int64_t n, void*) {
-    if (n < 0) return HM_EINVAL;
-    if (n == 0) return HM_OK;
-    if (!x || !out_val || ((out_std != nullptr) != (s != nullptr))) return HM_EINVAL;
+    if (const int rc = hm_rules::check_unary_op(HM_UOP_NEG, x, s, out_val, out_std, n, hm_rules::HOST); rc != HM_OK) return rc;
     const double p = exponent;
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
@@ -823,15 +774,10 @@ int hm_pow_scalar(const double* x, const double* s, double exponent, double* out
 
 int hm_take_axis(const double* x, const double* s, double* out_val, double* out_std, int64_t outer, int64_t axis_len, int64_t inner,
                  const int64_t* indices, int n_indices, void*) {
-    if (!x || !out_val || !indices || outer < 0 || axis_len < 1 || inner < 1 || n_indices < 1) return HM_EINVAL;
-    if ((out_std != nullptr) != (s != nullptr)) return HM_EINVAL;
-    std::vector<int64_t> idx(static_cast<size_t>(n_indices));
-    for (int q = 0; q < n_indices; ++q) {
-        int64_t v = indices[q];
-        if (v < 0) v += axis_len;
-        if (v < 0 || v >= axis_len) return HM_ESHAPE;
-        idx[static_cast<size_t>(q)] = v;
-    }
+    std::vector<int64_t> idx;
+    if (const int rc = hm_rules::check_take_axis(x, s, out_val, out_std, outer, axis_len, inner, indices, n_indices, hm_rules::HOST,
+                                                 [&] { idx.resize(static_cast<size_t>(n_indices)); return idx.data(); });
+        rc != HM_OK) return rc;
     for (int64_t o = 0; o < outer; ++o)
         for (int q = 0; q < n_indices; ++q) {
             const int64_t src = (o * axis_len + idx[static_cast<size_t>(q)]) * inner, dst = (o * n_indices + q) * inner;
@@ -843,10 +789,7 @@ int hm_take_axis(const double* x, const double* s, double* out_val, double* out_
 
 // ---- linearity statistics ----------------------------------------------------------------------------
 int hm_apply_thresholds(double* val, double* std_, const double* lower, const double* upper, int64_t n, int C, void*) {
-    if (n < 0 || C < 1 || !lower || !upper) return HM_EINVAL;
-    if (C > HM_THRESHOLD_MAX_CHANNELS) return HM_EUNSUPPORTED;
-    if (n == 0) return HM_OK;
-    if (!val) return HM_EINVAL;
+    if (const int rc = hm_rules::check_apply_thresholds(val, std_, lower, upper, n, C, hm_rules::HOST); rc != HM_OK) return rc;
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
         const int c = static_cast<int>(e % C);
@@ -859,16 +802,14 @@ int hm_apply_thresholds(double* val, double* std_, const double* lower, const do
 int hm_compute_difference_bcast(const double* x, const double* sx, const double* y, const double* sy, double multiplier, double* out_abs,
                                 double* out_abs_std, double* out_rel, double* out_rel_std, int ndim, const int64_t* shape,
                                 const int64_t* strides_x, const int64_t* strides_y, void*) {
-    Bcast b;
-    if (!fill_bcast(b, ndim, shape, strides_x, strides_y)) return HM_EINVAL;
-    if (b.n == 0) return HM_OK;
-    if (!x || !y || !out_abs || !out_rel) return HM_EINVAL;
+    int64_t n;
+    if (const int rc = hm_rules::check_compute_difference_bcast(x, sx, y, sy, out_abs, out_abs_std, out_rel, out_rel_std, ndim, shape, strides_x,
+                                                            strides_y, n); rc != HM_OK) return rc;
     const bool with_std = sx || sy;
-    if (with_std != (out_abs_std != nullptr) || with_std != (out_rel_std != nullptr)) return HM_EINVAL;
 #pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < b.n; ++e) {
+    for (int64_t e = 0; e < n; ++e) {
         int64_t ox, oy;
-        bcast_offsets(b, e, ox, oy);
+        bcast_offsets(ndim, shape, strides_x, strides_y, e, ox, oy);
         double a, as, r, rs;
         diff_terms(x[ox], sx ? sx[ox] : 0.0, y[oy], sy ? sy[oy] : 0.0, multiplier, with_std, a, as, r, rs);
         out_abs[e] = a; out_rel[e] = r;
@@ -878,23 +819,20 @@ int hm_compute_difference_bcast(const double* x, const double* sx, const double*
 }
 int hm_compute_difference(const double* x, const double* sx, const double* y, const double* sy, double multiplier, double* out_abs,
                           double* out_abs_std, double* out_rel, double* out_rel_std, int64_t n, void* stream) {
-    if (n < 0) return HM_EINVAL;
-    const int64_t shape[1] = {n}, st[1] = {1};
+    const int64_t shape[1] = {n}, st[1] = {1};                                       // n < 0: the negative extent of the _bcast rules
     return hm_compute_difference_bcast(x, sx, y, sy, multiplier, out_abs, out_abs_std, out_rel, out_rel_std, 1, shape, st, st, stream);
 }
 
 int hm_interpolate_bcast(const double* x0, const double* s0, const double* x1, const double* s1, double y0, double y1, double y,
                          double* out, double* out_std, int ndim, const int64_t* shape, const int64_t* strides0, const int64_t* strides1, void*) {
-    Bcast b;
-    if (!fill_bcast(b, ndim, shape, strides0, strides1)) return HM_EINVAL;
-    if (b.n == 0) return HM_OK;
-    if (!x0 || !x1 || !out || ((s0 || s1) != (out_std != nullptr))) return HM_EINVAL;
+    int64_t n;
+    if (const int rc = hm_rules::check_interpolate_bcast(x0, s0, x1, s1, out, out_std, ndim, shape, strides0, strides1, n); rc != HM_OK) return rc;
     const double a = y1 - y, bb = y - y0, d = y1 - y0;
     const double ca = (a / d) * (a / d), cb = (bb / d) * (bb / d);
 #pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < b.n; ++e) {
+    for (int64_t e = 0; e < n; ++e) {
         int64_t o0, o1;
-        bcast_offsets(b, e, o0, o1);
+        bcast_offsets(ndim, shape, strides0, strides1, e, o0, o1);
         out[e] = (x0[o0] * a + x1[o1] * bb) / d;                                                         // :665
         if (out_std) out_std[e] = std::sqrt((s0 ? s0[o0] : 0.0) * ca + (s1 ? s1[o1] : 0.0) * cb);       // :679 as written
     }
@@ -902,7 +840,6 @@ int hm_interpolate_bcast(const double* x0, const double* s0, const double* x1, c
 }
 int hm_interpolate(const double* x0, const double* s0, const double* x1, const double* s1, double y0, double y1, double y, double* out,
                    double* out_std, int64_t n, void* stream) {
-    if (n < 0) return HM_EINVAL;
     const int64_t shape[1] = {n}, st[1] = {1};
     return hm_interpolate_bcast(x0, s0, x1, s1, y0, y1, y, out, out_std, 1, shape, st, st, stream);
 }

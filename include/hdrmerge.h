@@ -346,7 +346,7 @@ int hm_hot_pixel_filter_f64(const double* x, const uint8_t* map_u8, const double
  * Row 9 standalone - flat-field ROI mean (modules/measurand.py:561-583) and normalize_by_map
  * (modules/measurand.py:585-604).
  * hm_roi_mean: per-channel mean over rows [x0,x1) x cols [y0,y1) of an H x W x C image, two-stage
- * deterministic reduction; `workspace` needs hm_roi_mean_workspace_bytes() bytes; out_mean is C
+ * deterministic reduction; `workspace` needs hm_roi_mean_workspace_bytes() bytes (the host build does not look at it); out_mean is C
  * float64 on the device.
  * ------------------------------------------------------------------------------------------ */
 size_t hm_roi_mean_workspace_bytes(void);
@@ -390,7 +390,8 @@ int hm_pow_scalar(const double* x, const double* s /*nullable*/, double exponent
 /* Measurand.extract (modules/measurand.py:352-373, `lib.take(val, dims, axis)`): out[o, k, i] = in[o, indices[k], i]
  * for the dense (outer, axis_len, inner) view of the array; axis=None in the reference is outer = inner = 1 on the
  * flattened array. std (nullable, with out_std) is taken with the same indices. Negative indices count from the end;
- * an index out of range returns HM_ESHAPE (np.take raises IndexError). At most HM_TAKE_MAX indices per call. */
+ * an index out of range returns HM_ESHAPE (np.take raises IndexError). At most HM_TAKE_MAX indices per call (more: HM_EUNSUPPORTED; the
+ * host build takes any number). */
 #define HM_TAKE_MAX 16
 int hm_take_axis(const double* x, const double* s, double* out_val, double* out_std, int64_t outer, int64_t axis_len,
                  int64_t inner, const int64_t* indices /*[host]*/, int n_indices, void* stream);
@@ -420,7 +421,8 @@ int hm_interpolate(const double* x0, const double* s0, const double* x1, const d
  * out is 6*C float64 on the device: [abs mean | abs std | abs error | rel mean | rel std | rel error]. */
 /* Status codes of the statistics entry points below, the same on both builds: n counts the elements of whole pixels, so n % C != 0 is
  * HM_EINVAL, as are n < 1, C outside 1..HM_MAX_CHANNELS, an extent < 1 or a product of extents above 2^48, a NULL val / out / workspace
- * (hm_axis_statistics: a NULL workspace only where hm_axis_statistics_workspace_bytes() is not 0), n_pairs < 1, n_frames outside
+ * (hm_axis_statistics: a NULL workspace only where hm_axis_statistics_workspace_bytes() is not 0; the host build, which needs none,
+ * refuses a NULL workspace only in hm_channel_statistics, hm_pair_statistics and the all-pairs entries), n_pairs < 1, n_frames outside
  * 1..HM_MAX_FRAMES, a pair index outside the frames and `lower` without `upper`; a value or std buffer that is not 8-byte aligned is
  * HM_EALIGN. Every one of them returns before anything is launched or written.
  * The stds of one reduction line are expected to have one sign: all negative gives the reference's mean and (positive) std with

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Print the argument-rule sweep of tests/test_entry_rules_host.py (the TIFF, calibration, producer and all-pairs entries): the status
+"""Print the argument-rule sweep of tests/test_entry_rules_host.py (every entry family but the merge, which has its own sweep): the status
 each build returned for every case. Per entry point: its faults, numbered; one line for the base call and for each single fault; and for
 the pairs of faults one line per first fault with one character per second fault, in the numbered order, for each build. Run it at two
-commits and diff the outputs to show that a change to the rule headers (csrc/hm_tiff_rules.h, hm_calibration_rules.h, hm_producer_rules.h,
-hm_pairs_rules.h) or to either build's use of them left every answer as it was:
+commits and diff the outputs to show that a change to the rule headers (csrc/hm_*_rules.h) or to either build's use of them left every answer
+as it was:
 
     python tools/entry_rules_sweep.py > this.txt
     HDRMERGE_LIB=<other>/libhdrmerge.so HDRMERGE_HOST_LIB=<other>/libhdrmerge_host.so python tools/entry_rules_sweep.py > other.txt
