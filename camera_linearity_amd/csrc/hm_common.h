@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hdrmerge.h"
+#include "hm_merge_math.h"
 #include <string>
 
 namespace hm {
@@ -45,38 +46,7 @@ inline unsigned balanced_wave_grid(int64_t wave_items, int waves_per_block, int 
     return static_cast<unsigned>((waves + waves_per_block - 1) / waves_per_block);
 }
 
-// Gaussian weight of the merge, measurand.py:615: w = e ** (-30 (v - 0.5)^2) with dv = v - 0.5. One definition for every
-// kernel that evaluates it analytically (float64 frames), so they agree bit for bit.
-#ifdef HM_FAKE_EXP          /* timing experiment only: removes the cost of exp() */
-__device__ __forceinline__ double gauss_weight(double dv) { return 1.0 + -30.0 * (dv * dv); }
-#else
-__device__ __forceinline__ double gauss_weight(double dv) { return exp(-30.0 * (dv * dv)); }
-#endif
-
-// flat-field epilogue on loaded operands, modules/measurand.py:585-602. The value keeps the reference's
-// operations, (val / F) * m (:602). The three variance terms (:586-596) each divide by F**2 or F**4 in the
-// reference; here 1/F**2 is formed once and multiplied (3 float64 divisions fewer per element; the std
-// moves by <= 2 ulp, its test tolerance is 1e-9).
-__device__ __forceinline__ void flat_field_math(double F, double iF2 /* 1 / (F*F) */, double sF, double m, double s,
-                                                bool with_std, double& val, double& sd) {
-    if (with_std) {
-        const double v2 = val * val;
-        const double u_acq = ((sd * sd) * iF2) * (m * m);
-        const double u_ff = ((v2 * (iF2 * iF2)) * (sF * sF)) * (m * m);
-        const double u_ffm = (v2 * iF2) * (s * s);
-        sd = sqrt(u_acq + u_ff + u_ffm);
-    }
-    val = (val / F) * m;
-}
-
-// scipy.ndimage 'reflect' (d c b a | a b c d) index fold, valid for any offset
-__device__ __forceinline__ int64_t reflect_index(int64_t i, int64_t n) {
-    while (i < 0 || i >= n) {
-        if (i < 0) i = -i - 1;
-        if (i >= n) i = 2 * n - i - 1;
-    }
-    return i;
-}
+// gauss_weight(), flat_field_math(), reflect_index(): hm_merge_math.h, the text the host build compiles too
 
 // ------------------------------------------------------------------------------------------------
 // k x k median of one channel around one pixel, 'reflect' at the true image edges, computed by the

@@ -232,23 +232,6 @@ __global__ __launch_bounds__(256) void k_roi_final(const double* __restrict__ pa
 // ---- normalize_by_map ----
 struct FFMeans { double m[HM_MAX_CHANNELS]; double s[HM_MAX_CHANNELS]; };
 
-// one element of normalize_by_map, operation for operation (measurand.py:585-602)
-__device__ __forceinline__ void normalize_one(double v, double s0, double F, double sF, double m, double s, bool with_std,
-                                              double& ov, double& os) {
-    if (with_std) {
-        const double F2 = F * F;
-        double u_acq = (s0 * s0) / F2;        // measurand.py:586-587
-        u_acq *= m * m;
-        double u_ff = (v * v) / (F2 * F2);    // :590-592
-        u_ff *= sF * sF;
-        u_ff *= m * m;
-        double u_ffm = (v * v) / F2;          // :595-596
-        u_ffm *= s * s;
-        os = sqrt(u_acq + u_ff + u_ffm);      // :599
-    }
-    ov = (v / F) * m;                         // :602
-}
-
 __device__ __forceinline__ double pick(const double (&a)[HM_MAX_CHANNELS], uint32_t c) {      // no per-lane kernarg indexing
     double r = a[0];
 #pragma unroll
@@ -302,8 +285,8 @@ __global__ __launch_bounds__(256) void k_normalize(const double* __restrict__ va
             }
         }
         double ov[2], os[2] = {0.0, 0.0};
-        normalize_one(v[0], s0[0], F[0], sF[0], pick(ff.m, c0), pick(ff.s, c0), with_std, ov[0], os[0]);
-        normalize_one(v[1], s0[1], F[1], sF[1], pick(ff.m, c1), pick(ff.s, c1), with_std, ov[1], os[1]);
+        flat_field_exact(v[0], s0[0], F[0], sF[0], pick(ff.m, c0), pick(ff.s, c0), with_std, ov[0], os[0]);
+        flat_field_exact(v[1], s0[1], F[1], sF[1], pick(ff.m, c1), pick(ff.s, c1), with_std, ov[1], os[1]);
         if (vec_ok) {
             f64x2 o; o.x = ov[0]; o.y = ov[1];
             __builtin_nontemporal_store(o, reinterpret_cast<f64x2*>(out_val + e));
@@ -320,7 +303,7 @@ __global__ __launch_bounds__(256) void k_normalize(const double* __restrict__ va
         const uint32_t c = static_cast<uint32_t>(e % C);
         const double F = flat_u8 ? static_cast<double>(flat_u8[e]) / 255.0 : flat_f64[e];
         double ov, os = 0.0;
-        normalize_one(val[e], with_std ? sd[e] : 0.0, F, with_std ? flat_std[e] : 0.0, pick(ff.m, c), pick(ff.s, c), with_std, ov, os);
+        flat_field_exact(val[e], with_std ? sd[e] : 0.0, F, with_std ? flat_std[e] : 0.0, pick(ff.m, c), pick(ff.s, c), with_std, ov, os);
         out_val[e] = ov;
         if (with_std) out_std[e] = os;
     }

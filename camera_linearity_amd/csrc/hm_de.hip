@@ -19,6 +19,7 @@
 // bodies are the single-problem ones (k_de_trial's a shared function, k_de_select's the same text included a second time,
 // hm_de_select_body.h) applied to problem k's slices of the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
 #include "hm_common.h"
+#include "hm_producer_math.h"
 #include "hm_calibration_rules.h"
 
 namespace hm {
@@ -45,18 +46,6 @@ struct DeK {
     int64_t max_generations;
     double m_lo, m_hi, cr, tol, energy_limit;
 };
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {          // the splitmix64 step
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ double de_uniform(uint64_t key, int i, int k) {
-    const uint64_t r = mix64(key + (static_cast<uint64_t>(i + 1) << 20) + static_cast<uint64_t>(k));
-    return static_cast<double>(r >> 11) * 0x1.0p-53;
-}
 
 // the seeds of a batch travel in the kernel arguments, like the stack pointers of its energy stage
 struct DeSeeds {

@@ -15,6 +15,7 @@
 //             so a tile whose u range lies further than kKdeCut from every grid point of the workgroup is skipped: exact.
 //             Partials go to workspace[chunk][m]; k_kde_sum adds the chunks in a fixed order and applies the norm.
 #include "hm_common.h"
+#include "hm_stats_math.h"
 #include "hm_producer_rules.h"
 
 namespace hm {
@@ -40,19 +41,6 @@ __host__ __device__ inline int64_t kde_chunks(int64_t n) {
     const int64_t len = kde_chunk_len(n);
     const int64_t k = n / len + (n % len != 0);
     return k < 1 ? 1 : k;
-}
-
-// counted element i of channel c: finite x, and std != 0 when std is given; w = 1 / std or 1
-__device__ __forceinline__ bool kde_load(const double* __restrict__ val, const double* __restrict__ std, int64_t e, double& x, double& w) {
-    x = val[e];
-    w = 1.0;
-    bool ok = isfinite(x);
-    if (std) {
-        const double s = std[e];
-        ok = ok && s != 0.0;
-        w = 1.0 / s;
-    }
-    return ok;
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void k_weight_f64(const double* __restrict__ v
         const double d = v[e] - 0.5;
         const double y = gauss_weight(d);          // np.e ** (-30 (v - 0.5)^2), measurand.py:615
         if (w) w[e] = y;
-        if (dw) dw[e] = (-60.0 * d) * y;                // -2 * 30 * (v - 0.5) * y, measurand.py:616
+        if (dw) dw[e] = gauss_dweight(d, y);                // -2 * 30 * (v - 0.5) * y, measurand.py:616
     }
 }
 
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_weight_f64_burst(const double* __restri
             const double d0 = x[k].x - 0.5, d1 = x[k].y - 0.5;
             const double y0 = gauss_weight(d0), y1 = gauss_weight(d1);      // measurand.py:615
             y[k] = f64x2{y0, y1};
-            dy[k] = f64x2{(-60.0 * d0) * y0, (-60.0 * d1) * y1};           // measurand.py:616
+            dy[k] = f64x2{gauss_dweight(d0, y0), gauss_dweight(d1, y1)};           // measurand.py:616
         }
         if constexpr (HAS_W) {
 #pragma unroll
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_linearize(const void* __restrict__ in, 
         const uint32_t cstep = per_ch ? static_cast<uint32_t>(stride % C) : 0u;
         for (int64_t e = e_0; e < n; e += stride) {
             // around(val * MAX_DN).astype(uint8): round half to even, then wrap (measurand.py:503)
-            const uint32_t k = static_cast<uint32_t>(static_cast<int64_t>(rint(v[e] * 255.0))) & 255u;
+            const uint32_t k = lut_index(v[e]);
             const Entry gd = t[k * ls + c];
             out_val[e] = lin_g(gd);
             if (STD) out_std[e] = lin_d(gd) * sd[e];
@@ -236,8 +236,8 @@ __global__ __launch_bounds__(256) void k_linearize_stream(const void* __restrict
         for (int s_ = 0; s_ < static_cast<int>(kLinU); ++s_) {
             uint32_t k0, k1;
             if constexpr (F64IN) {                                                   // around(val * MAX_DN).astype(uint8): half to even, wrap (measurand.py:503)
-                k0 = static_cast<uint32_t>(static_cast<int64_t>(rint(x[s_].x * 255.0))) & 255u;
-                k1 = static_cast<uint32_t>(static_cast<int64_t>(rint(x[s_].y * 255.0))) & 255u;
+                k0 = lut_index(x[s_].x);
+                k1 = lut_index(x[s_].y);
             } else { k0 = r[s_] & 255u; k1 = r[s_] >> 8; }
             const char* tb = reinterpret_cast<const char*>(t);
             const uint32_t a0 = PERCH ? __umul24(k0, 3u * ENT) + off[(2 * s_) % 3] : k0 * ENT;

@@ -154,8 +154,8 @@ __global__ __launch_bounds__(256) void merge_chunk(const ChunkK a) {
                 if (F64IN) {
                     const double dv = v[j] - 0.5;
                     w = gauss_weight(dv);                                            // measurand.py:615
-                    if (PH == PH_STD) dw = (-60.0 * dv) * w;                         // :616
-                    idx = static_cast<uint32_t>(static_cast<int64_t>(rint(v[j] * 255.0))) & 255u;   // :503
+                    if (PH == PH_STD) dw = gauss_dweight(dv, w);                         // :616
+                    idx = lut_index(v[j]);   // :503
                 } else {
                     idx = dn[j];
                     w = t_w[idx];
@@ -168,8 +168,7 @@ __global__ __launch_bounds__(256) void merge_chunk(const ChunkK a) {
                     acc[j] = start ? wg * it : fma(wg, it, acc[j]);                  // :388 numerator
                     if (PH == PH_STD) {
                         const double dg = t_d[idx * C + ch[j]] * sdv[j];             // measurand.py:512
-                        const double A = (dw * g + w * dg) * invS[j] - ((dw * w) * g) * invS2[j];   // :389
-                        const double term = (A * dg) * it;
+                        const double term = merge_var_term(w, dw, g, dg, invS[j], invS2[j], it);   // :389
                         var[j] = start ? term * term : fma(term, term, var[j]);
                     }
                 }

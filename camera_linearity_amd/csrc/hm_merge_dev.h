@@ -80,12 +80,9 @@ __device__ __forceinline__ void flat_field_apply(const MergeK& a, int64_t e, int
     flat_field_math(F, with_std ? 1.0 / (F * F) : 1.0, with_std ? a.flat_std[e] : 0.0, a.ff_mean[c], a.ff_std_mean[c], with_std, val, sd);
 }
 
-// index linearize forms from a frame value (measurand.py:503): the DN itself, or the rounded, wrapped float64 value
-__device__ __forceinline__ uint32_t lut_index_f64(double v) {
-    return static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;
-}
+// index linearize forms from a frame value (measurand.py:503): the DN itself, or lut_index() of the float64 value
 __device__ __forceinline__ uint32_t lut_index_of(uint8_t v) { return v; }
-__device__ __forceinline__ uint32_t lut_index_of(double v) { return lut_index_f64(v); }
+__device__ __forceinline__ uint32_t lut_index_of(double v) { return lut_index(v); }
 
 // std of element `i` of frame `f` through the per-DN table (hm_merge_std_table): what linearize(frame, icrf = std_table).val holds there.
 // Handed to the k x k medians as their element accessor: a hot frame's std is the median of the MAPPED neighbourhood (the reference
@@ -180,8 +177,8 @@ __device__ __forceinline__ void merge_one_element(const MergeK& a, const double*
             const double v = value_f64(i, hot);
             const double dv = v - 0.5;
             w = gauss_weight(dv);
-            dw = (-60.0 * dv) * w;                                      // measurand.py:616
-            idx = static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;   // measurand.py:503
+            dw = gauss_dweight(dv, w);                                  // measurand.py:616
+            idx = lut_index(v);                                         // measurand.py:503
         } else {
             idx = value_u8(i, hot);
             w = t_w[idx];
@@ -211,8 +208,7 @@ __device__ __forceinline__ void merge_one_element(const MergeK& a, const double*
                 } else s = at(ei);
             }
             const double dg = t_d[idx * C + c] * s;                     // measurand.py:512
-            const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;   // :389
-            const double term = (A * dg) * it;
+            const double term = merge_var_term(w, dw, g, dg, invS, invS2, it);    // :389
             var = (i == 0) ? term * term : fma(term, term, var);
         }
     }

@@ -103,7 +103,7 @@ __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
                             const double x = j == 0 ? v[k].x : v[k].y;
                             const double dv = x - 0.5;
                             const double w = gauss_weight(dv);                            // measurand.py:615
-                            const double gg = t_gd[lut_index_f64(x) * C + cs[j]].x;
+                            const double gg = t_gd[lut_index(x) * C + cs[j]].x;
                             const double wg = w * gg;
                             if (i0 + k == 0) { S[j] = w; acc[j] = wg * it; }
                             else { S[j] += w; acc[j] = fma(wg, it, acc[j]); }                   // exposure_series.py:340, :388
@@ -125,13 +125,12 @@ __device__ __forceinline__ void merge_f64_body(const MergeK& a) {
             double invS[2], invS2[2];
             // one frame of pass 2 (measurand.py:512,616; exposure_series.py:388-389) given its weight
             auto pass2 = [&](int i, int j, double x, double w, double s, double it) {
-                const double dw = (-60.0 * (x - 0.5)) * w;                                      // measurand.py:616
-                const double2 gd = t_gd[lut_index_f64(x) * C + cs[j]];
+                const double dw = gauss_dweight(x - 0.5, w);                                      // measurand.py:616
+                const double2 gd = t_gd[lut_index(x) * C + cs[j]];
                 const double gg = gd.x;
                 const double wg = w * gg;
                 const double dg = gd.y * s;                                                     // measurand.py:512
-                const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];     // :389
-                const double term = (A * dg) * it;
+                const double term = merge_var_term(w, dw, gg, dg, invS[j], invS2[j], it);   // :389
                 if (i == 0) { acc[j] = wg * it; var[j] = term * term; }
                 else { acc[j] = fma(wg, it, acc[j]); var[j] = fma(term, term, var[j]); }
             };

@@ -68,7 +68,7 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
     const bool hot = owner && dk && static_cast<int>(dk[ei]) >= dmin;
     double v = F64IN ? static_cast<const double*>(fr)[ei] : static_cast<double>(static_cast<const uint8_t*>(fr)[ei]);
     double sdv = 0.0;
-    if constexpr (STD) sdv = LUT ? a.std_lut[(F64IN ? lut_index_f64(v) : static_cast<uint32_t>(v)) * C + c] : static_cast<double>(sp[ei]);
+    if constexpr (STD) sdv = LUT ? a.std_lut[(F64IN ? lut_index(v) : static_cast<uint32_t>(v)) * C + c] : static_cast<double>(sp[ei]);
     // --- medians of the hot frames, floor(64 / k^2) frames per batch
     const unsigned long long hotmask = __ballot(hot);
     const int k = a.median_k, kk = k * k, r = k / 2, m = kk / 2;
@@ -90,7 +90,7 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
         double nv = 0.0, ns = 0.0;
         if (part) {
             nv = F64IN ? static_cast<const double*>(pf)[ni] : static_cast<double>(static_cast<const uint8_t*>(pf)[ni]);
-            if constexpr (STD) ns = LUT ? a.std_lut[(F64IN ? lut_index_f64(nv) : static_cast<uint32_t>(nv)) * C + cc] : static_cast<double>(ps[ni]);
+            if constexpr (STD) ns = LUT ? a.std_lut[(F64IN ? lut_index(nv) : static_cast<uint32_t>(nv)) * C + cc] : static_cast<double>(ps[ni]);
         }
         int lv = 0, qv = 0, ls = 0, qs = 0;
         for (int q = 0; q < kk; ++q) {
@@ -120,8 +120,8 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
         if (F64IN) {
             const double dv = v - 0.5;
             w = gauss_weight(dv);
-            dw = (-60.0 * dv) * w;
-            idx = static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;
+            dw = gauss_dweight(dv, w);
+            idx = lut_index(v);
         } else {
             idx = static_cast<uint32_t>(v);
             w = t_w[idx];
@@ -143,8 +143,7 @@ __device__ __forceinline__ void fixup_element(const MergeK& a, const double* t_w
     double term = 0.0;
     if (STD) {
         const double dg = t_d[idx * C + c] * sdv;
-        const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;
-        term = (A * dg) * it;
+        term = merge_var_term(w, dw, g, dg, invS, invS2, it);
     }
     double acc = 0.0, var = 0.0;
     for (int i = 0; i < N; ++i) {
@@ -319,8 +318,8 @@ __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* 
                     const double v = keep[i * 256];
                     const double dv = v - 0.5;
                     w = gauss_weight(dv);
-                    dw = (-60.0 * dv) * w;                                               // measurand.py:616
-                    idx = static_cast<uint32_t>(static_cast<int64_t>(rint(v * 255.0))) & 255u;   // measurand.py:503
+                    dw = gauss_dweight(dv, w);                                               // measurand.py:616
+                    idx = lut_index(v);   // measurand.py:503
                 } else {
                     idx = keep[i * 256];
                     w = t_w[idx];
@@ -333,8 +332,7 @@ __device__ __forceinline__ void patch_element_k3(const MergeK& a, const double* 
                 if constexpr (STD) {
                     const double sv = median9<double>(sp[f]);
                     const double dg = t_d[idx * C + c] * sv;                             // measurand.py:512
-                    const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;  // :389
-                    const double term = (A * dg) * it;
+                    const double term = merge_var_term(w, dw, g, dg, invS, invS2, it);   // :389
                     var = (i == 0) ? term * term : fma(term, term, var);
                 }
             }

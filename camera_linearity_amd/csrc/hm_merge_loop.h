@@ -159,8 +159,7 @@ __device__ __forceinline__ void merge_u8_loop_body(const MergeK& a) {
                             const double2 gd = *reinterpret_cast<const double2*>(t_gd + dn * (16u * C) + coffs[j]);
                             const double w = wdw.x, dw = wdw.y, gg = gd.x;
                             const double dg = LUT ? gd.y : gd.y * static_cast<double>(j == 0 ? sdv[k].x : sdv[k].y);   // measurand.py:512
-                            const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
-                            const double term = (A * dg) * it;
+                            const double term = merge_var_term(w, dw, gg, dg, invS[j], invS2[j], it);   // :389
                             if (i0 + k == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }
                             else {
                                 acc[j] = fma(w * gg, it, acc[j]);                                          // :388

@@ -281,6 +281,7 @@ __device__ __forceinline__ void merge_u8_fast_body(const MergeK& a) {
 #endif
                         const double w = wdw.x, dw = wdw.y, gg = gd.x;
                         const double dg = LUT ? gd.y : gd.y * static_cast<double>(j == 0 ? sdv.x : sdv.y);   // measurand.py:512
+                        // merge_var_term() of hm_merge_math.h, written out: called here, the N = 1 kernels schedule differently
                         const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
                         const double term = (A * dg) * it;
                         if (i == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }

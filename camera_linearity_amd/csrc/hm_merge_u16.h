@@ -39,8 +39,7 @@ __device__ __forceinline__ void merge_u16_element(const MergeK& a, int64_t e, co
         acc = (i == 0) ? wg * it : fma(wg, it, acc);                    // :388 numerator
         if (STD) {
             const double dg = a.icrf_diff[idx * C + c] * src.sd_at(i);  // measurand.py:512
-            const double A = (dw * g + w * dg) * invS - ((dw * w) * g) * invS2;   // :389
-            const double term = (A * dg) * it;
+            const double term = merge_var_term(w, dw, g, dg, invS, invS2, it);   // :389
             var = (i == 0) ? term * term : fma(term, term, var);
         }
     }

@@ -207,6 +207,7 @@ __global__ __launch_bounds__(PLACE != hm_rules::U16_TAB_GLOBAL ? kU16LdsBlock : 
                             double w, dw, gg, d;
                             get_std(idx, cs[j], w, dw, gg, d);
                             const double dg = d * (j == 0 ? sdv[k].x : sdv[k].y);                          // measurand.py:512
+                            // merge_var_term() of hm_merge_math.h, written out: called here, the std kernels schedule differently
                             const double A = (dw * gg + w * dg) * invS[j] - ((dw * w) * gg) * invS2[j];   // :389
                             const double term = (A * dg) * it;
                             if (i0 + k == 0) { acc[j] = (w * gg) * it; var[j] = term * term; }

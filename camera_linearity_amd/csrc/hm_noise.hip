@@ -16,6 +16,7 @@
 //     the output that are contiguous per mean level: LDS layout [m][d][c] = global layout [m][m - half + d][c]).
 // Bound: a workgroup counts at most units_per_lane x 16 x n_frames x 1024 < 2^32 elements per launch (checked on the host).
 #include "hm_common.h"
+#include "hm_producer_math.h"
 #include "hm_producer_rules.h"
 
 namespace hm {
@@ -164,9 +165,8 @@ __global__ __launch_bounds__(256) void k_noise_std(const long long* __restrict__
     if (lane == 0) out[i * C + c] = sqrt(s2 / cnt);
 }
 
-// clean_data_edges (:12-74): one lane per (row i, channel c), the reference's four integer passes in order, in place
-__device__ __forceinline__ long long floordiv2(long long x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
-
+// clean_data_edges (:12-74): one lane per (row i, channel c), the reference's four integer passes in order, in place. The passes are
+// clean_edges_row() of hm_producer_math.h written out: called here, the kernel's code changes.
 __global__ __launch_bounds__(64) void k_noise_clean_edges(long long* __restrict__ prof, int C) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 256 * C) return;

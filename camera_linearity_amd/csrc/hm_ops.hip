@@ -2,6 +2,7 @@
 // Formulas and operation order of modules/measurand.py:106-279 (add/sub/neg/div/mul/pow/log_e/log_10);
 // operands broadcast NumPy-style through element strides (0 on broadcast axes).
 #include "hm_common.h"
+#include "hm_ops_math.h"
 #include "hm_ops_rules.h"
 
 namespace hm {
@@ -13,32 +14,6 @@ struct BcastK {
     int ndim;
     int contiguous;     // both operands dense and same shape: offsets == linear index
 };
-
-template <int OP>
-__device__ __forceinline__ void binary_eval(double x1, double s1, double x2, double s2, bool with_std,
-                                            double& r, double& rs) {
-    if (OP == HM_OP_ADD) {                                  // measurand.py:114,126
-        r = x1 + x2;
-        if (with_std) rs = sqrt((s1 * s1) + (s2 * s2));
-    } else if (OP == HM_OP_SUB) {                           // :138,149
-        r = x1 - x2;
-        if (with_std) rs = sqrt((s1 * s1) + (s2 * s2));
-    } else if (OP == HM_OP_MUL) {                           // :198,209
-        r = x1 * x2;
-        if (with_std) { const double a = x1 * s2, b = x2 * s1; rs = sqrt(a * a + b * b); }
-    } else if (OP == HM_OP_DIV) {                           // :173,184-186
-        r = x1 / x2;
-        if (with_std) { const double u1 = s1 / x2, u2 = (x1 * s2) / (x2 * x2); rs = sqrt(u1 * u1 + u2 * u2); }
-    } else {                                                // pow :225,236-239
-        r = pow(x1, x2);
-        if (with_std) {
-            const double u1 = x2 * pow(x1, x2 - 1.0);
-            const double u2 = log(x1) * r;
-            const double a = u1 * s1, b = u2 * s2;
-            rs = sqrt(a * a + b * b);
-        }
-    }
-}
 
 template <int OP>
 __global__ __launch_bounds__(256) void k_binary(const double* __restrict__ x1, const double* __restrict__ s1,
@@ -153,57 +128,21 @@ __global__ __launch_bounds__(256) void k_binary_burst(const double* __restrict__
 __global__ __launch_bounds__(256) void k_unary(int op, const double* __restrict__ x, const double* __restrict__ s,
                                                double* __restrict__ out, double* __restrict__ out_std, int64_t n) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double ln10 = 0x1.26bb1bbb55515p+1;                  // fl(log 5) + fl(log 2), the constant measurand.py:277 forms (hm_host.cpp holds the same literal)
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
         const double v = x[e];
         double r, rs = 0.0;
-        if (op == HM_UOP_NEG) { r = -v; if (out_std) rs = s[e]; }                              // :154-157
-        else if (op == HM_UOP_LOG_E) { r = log(v); if (out_std) rs = s[e] / r; }               // :251,258 (as written)
-        else { r = log10(v); if (out_std) rs = s[e] / (v * ln10); }                            // :270,277
+        unary_eval(op, v, out_std != nullptr, [&] { return s[e]; }, r, rs);
         out[e] = r;
         if (out_std) out_std[e] = rs;
     }
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// x ** p for a plain scalar exponent p (no uncertainty of its own) - Measurand.__pow__, modules/measurand.py:217-241, as the
-// merge loop uses it (S ** 2 at exposure_series.py:343, ** (1/2) at :394). The generic kernel above evaluates pow() twice and
-// log() once per element (0.19 of the HBM roofline, profiles/r01e_bench_ops.json); with the exponent known on the host
-//   value:  p == 2 -> x*x,  p == 0.5 -> sqrt(x),  p == 1 -> x,  small integer p -> repeated multiplication, else pow(x, p)
-//   std  :  |dx**p/dx| * s = (p * x**(p-1)) * s, with x**(p-1) = x, 1/sqrt(x)... formed from the value; the exponent's term
-//           (ln x * x**p * 0)**2 of :236-239 is +0 whenever ln x * x**p is finite and is evaluated as written otherwise
-//           (x <= 0 or non-finite: NumPy gives NaN / inf there and so does this kernel).
-// Results agree with NumPy's pow-based evaluation to a few ulp (tests hold 1e-13 against the reference's own outputs).
+// x ** p for a plain scalar exponent p (no uncertainty of its own) - Measurand.__pow__, modules/measurand.py:217-241, as the merge loop
+// uses it (S ** 2 at exposure_series.py:343, ** (1/2) at :394). The generic kernel above evaluates pow() twice and log() once per element
+// (0.19 of the HBM roofline, profiles/r01e_bench_ops.json); with the exponent's kind known on the host it is pow_scalar_eval<KIND> of
+// hm_ops_math.h. Results agree with NumPy's pow-based evaluation to a few ulp (tests hold 1e-13 against the reference's own outputs).
 // Two elements per lane, 16-byte accesses.
-// ------------------------------------------------------------------------------------------------
-enum { POW_SQUARE = 0, POW_SQRT = 1, POW_ONE = 2, POW_INT = 3, POW_GENERAL = 4 };
-
-template <int KIND>
-__device__ __forceinline__ void pow_scalar_eval(double x, double s, double p, int ip, bool with_std, double& r, double& rs) {
-    double d;                                               // x ** (p - 1)
-    if (KIND == POW_SQUARE) { r = x * x; d = x; }
-    else if (KIND == POW_SQRT) {                            // sqrt: the correctly rounded x ** 0.5. NumPy's pow() differs from it at two arguments only:
-        const double ax = (x == 0.0 || x == -__builtin_huge_val()) ? fabs(x) : x;       // -inf -> +inf (d = +0) and -0.0 -> +0.0 (d = +inf)
-        r = sqrt(ax); d = 1.0 / r;
-    }
-    else if (KIND == POW_ONE) { r = x; d = 1.0; }
-    else if (KIND == POW_INT) {                             // |ip| <= 8: x**(|ip|-1) by multiplication, one more for the value
-        const int n = ip < 0 ? -ip : ip;
-        double acc = 1.0;
-        for (int k = 1; k < n; ++k) acc *= x;
-        if (ip > 0) { d = acc; r = acc * x; }
-        else { r = 1.0 / (acc * x); d = r / x; }
-    } else { r = pow(x, p); d = pow(x, p - 1.0); }
-    if (with_std) {
-        const double a = (p * d) * s;                        // measurand.py:236
-        double b = 0.0;                                      // (log(x1) * x1**x2) * 0, :237-238
-        const double lr = r;
-        if (!(x > 0.0) || !(fabs(x) < __builtin_huge_val()) || !(fabs(lr) < __builtin_huge_val())) b = (log(x) * r) * 0.0;
-        rs = sqrt(a * a + b * b);
-    }
-}
-
 template <int KIND>
 __global__ __launch_bounds__(256) void k_pow_scalar(const double* __restrict__ x, const double* __restrict__ s, double* __restrict__ out,
                                                     double* __restrict__ out_s, int64_t n, double p, int ip) {

@@ -5,6 +5,7 @@
 //   hm_compute_difference_bcast, hm_interpolate_bcast    the same two on broadcast operands   modules/measurand.py:621-681
 // Streaming, HBM-bound. The statistics of the row: hm_stats.hip, hm_stats_hist.hip, hm_stats_axis.hip.
 #include "hm_pointwise.h"
+#include "hm_ops_math.h"
 #include "hm_ops_rules.h"
 
 namespace hm {
@@ -53,17 +54,13 @@ __global__ __launch_bounds__(256) void k_difference(const double* __restrict__ x
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
         const double xv = x[e], yv = y[e];
-        const double scale = mult * yv;                     // :634
-        const double a = xv - scale;                        // :635
+        const double a = diff_abs(xv, yv, mult);
         ad[e] = a;
-        rd[e] = a / scale;                                  // :636
+        rd[e] = diff_rel(a, yv, mult);
         if (ads) {
             const double xs = sx ? sx[e] : 0.0, ys = sy ? sy[e] : 0.0;
-            const double m1 = mult * ys;
-            ads[e] = sqrt(xs * xs + m1 * m1);               // :652
-            const double u1 = xs / (mult * yv);
-            const double u2 = (ys * xv) / (mult * (yv * yv));
-            rds[e] = sqrt(u1 * u1 + u2 * u2);               // :653
+            ads[e] = diff_abs_std(xs, ys, mult);
+            rds[e] = diff_rel_std(xv, yv, xs, ys, mult);
         }
     }
 }
@@ -78,18 +75,6 @@ __global__ __launch_bounds__(256) void k_difference_dense(const double* __restri
     constexpr bool STD = SX || SY;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     const int64_t pairs = n / 2;
-    auto one = [&](double xv, double yv, double xs, double ys, double& a, double& r, double& as, double& rs) {
-        const double scale = mult * yv;                     // :634
-        a = xv - scale;                                     // :635
-        r = a / scale;                                      // :636
-        if constexpr (STD) {
-            const double m1 = mult * ys;
-            as = sqrt(xs * xs + m1 * m1);                   // :652
-            const double u1 = xs / (mult * yv);
-            const double u2 = (ys * xv) / (mult * (yv * yv));
-            rs = sqrt(u1 * u1 + u2 * u2);                   // :653
-        }
-    };
     for (int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; q < pairs; q += stride) {
         const f64x2 xv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(x) + q);
         const f64x2 yv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(y) + q);
@@ -97,8 +82,8 @@ __global__ __launch_bounds__(256) void k_difference_dense(const double* __restri
         if constexpr (SX) xs = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(sx) + q);
         if constexpr (SY) ys = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(sy) + q);
         double a0, a1, r0, r1, as0 = 0.0, as1 = 0.0, rs0 = 0.0, rs1 = 0.0;
-        one(xv.x, yv.x, xs.x, ys.x, a0, r0, as0, rs0);
-        one(xv.y, yv.y, xs.y, ys.y, a1, r1, as1, rs1);
+        diff_terms(xv.x, yv.x, xs.x, ys.x, mult, STD, a0, r0, as0, rs0);
+        diff_terms(xv.y, yv.y, xs.y, ys.y, mult, STD, a1, r1, as1, rs1);
         f64x2 o;
         o.x = a0; o.y = a1; __builtin_nontemporal_store(o, reinterpret_cast<f64x2*>(ad) + q);
         o.x = r0; o.y = r1; __builtin_nontemporal_store(o, reinterpret_cast<f64x2*>(rd) + q);
@@ -110,7 +95,7 @@ __global__ __launch_bounds__(256) void k_difference_dense(const double* __restri
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const int64_t e = n - 1;
         double a, r, as = 0.0, rs = 0.0;
-        one(x[e], y[e], SX ? sx[e] : 0.0, SY ? sy[e] : 0.0, a, r, as, rs);
+        diff_terms(x[e], y[e], SX ? sx[e] : 0.0, SY ? sy[e] : 0.0, mult, STD, a, r, as, rs);
         ad[e] = a; rd[e] = r;
         if constexpr (STD) { ads[e] = as; rds[e] = rs; }
     }
@@ -129,18 +114,6 @@ __global__ __launch_bounds__(256) void k_difference_burst(const double* __restri
     constexpr int B = kDiffBurst;
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t cstride = static_cast<int64_t>(gridDim.x) * 4;
-    auto one = [&](double xv, double yv, double xs, double ys, double& a, double& r, double& as, double& rs) {
-        const double scale = mult * yv;                     // :634
-        a = xv - scale;                                     // :635
-        r = a / scale;                                      // :636
-        if constexpr (STD) {
-            const double m1 = mult * ys;
-            as = sqrt(xs * xs + m1 * m1);                   // :652
-            const double u1 = xs / (mult * yv);
-            const double u2 = (ys * xv) / (mult * (yv * yv));
-            rs = sqrt(u1 * u1 + u2 * u2);                   // :653
-        }
-    };
     for (int64_t c = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); c < n_chunks; c += cstride) {
         const int64_t b = c * kDiffChunk;
         f64x2 xv[B], yv[B], xs[B], ys[B];
@@ -162,8 +135,8 @@ __global__ __launch_bounds__(256) void k_difference_burst(const double* __restri
 #pragma unroll
         for (int k = 0; k < B; ++k) {
             double a0, a1, r0, r1, as0 = 0.0, as1 = 0.0, rs0 = 0.0, rs1 = 0.0;
-            one(xv[k].x, yv[k].x, xs[k].x, ys[k].x, a0, r0, as0, rs0);
-            one(xv[k].y, yv[k].y, xs[k].y, ys[k].y, a1, r1, as1, rs1);
+            diff_terms(xv[k].x, yv[k].x, xs[k].x, ys[k].x, mult, STD, a0, r0, as0, rs0);
+            diff_terms(xv[k].y, yv[k].y, xs[k].y, ys[k].y, mult, STD, a1, r1, as1, rs1);
             a[k] = f64x2{a0, a1}; r[k] = f64x2{r0, r1}; as[k] = f64x2{as0, as1}; rs[k] = f64x2{rs0, rs1};
         }
 #pragma unroll
@@ -184,11 +157,10 @@ __global__ __launch_bounds__(256) void k_interpolate(const double* __restrict__ 
                                                      double y0, double y1, double y, double* __restrict__ out,
                                                      double* __restrict__ out_std, int64_t n) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double a = y1 - y, b = y - y0, d = y1 - y0;
-    const double ca = (a / d) * (a / d), cb = (b / d) * (b / d);
+    const InterpCoef k = interp_coef(y0, y1, y);
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
-        out[e] = (x0[e] * a + x1[e] * b) / d;               // :665
-        if (out_std) out_std[e] = sqrt((s0 ? s0[e] : 0.0) * ca + (s1 ? s1[e] : 0.0) * cb);   // :679 as written
+        out[e] = interp_value(k, x0[e], x1[e]);
+        if (out_std) out_std[e] = interp_std(k, s0 ? s0[e] : 0.0, s1 ? s1[e] : 0.0);
     }
 }
 
@@ -202,8 +174,7 @@ __global__ __launch_bounds__(256) void k_interpolate_burst(const double* __restr
     constexpr int B = kDiffBurst;
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t cstride = static_cast<int64_t>(gridDim.x) * 4;
-    const double a = y1 - y, b = y - y0, d = y1 - y0;
-    const double ca = (a / d) * (a / d), cb = (b / d) * (b / d);
+    const InterpCoef ic = interp_coef(y0, y1, y);
     for (int64_t c = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); c < n_chunks; c += cstride) {
         const int64_t e = c * kDiffChunk;
         f64x2 v0[B], v1[B], u0[B], u1[B];
@@ -224,8 +195,8 @@ __global__ __launch_bounds__(256) void k_interpolate_burst(const double* __restr
         f64x2 o[B], os[B];
 #pragma unroll
         for (int k = 0; k < B; ++k) {
-            o[k] = f64x2{(v0[k].x * a + v1[k].x * b) / d, (v0[k].y * a + v1[k].y * b) / d};             // :665
-            os[k] = f64x2{sqrt(u0[k].x * ca + u1[k].x * cb), sqrt(u0[k].y * ca + u1[k].y * cb)};       // :679 as written
+            o[k] = f64x2{interp_value(ic, v0[k].x, v1[k].x), interp_value(ic, v0[k].y, v1[k].y)};
+            os[k] = f64x2{interp_std(ic, u0[k].x, u1[k].x), interp_std(ic, u0[k].y, u1[k].y)};
         }
 #pragma unroll
         for (int k = 0; k < B; ++k) __builtin_nontemporal_store(o[k], reinterpret_cast<f64x2*>(out + e + 128 * k) + lane);
@@ -276,17 +247,13 @@ __global__ __launch_bounds__(256) void k_difference_bcast(const double* __restri
         int64_t ox, oy;
         bcast_offsets(b, e, ox, oy);
         const double xv = x[ox], yv = y[oy];
-        const double scale = mult * yv;                     // :634
-        const double a = xv - scale;                        // :635
+        const double a = diff_abs(xv, yv, mult);
         ad[e] = a;
-        rd[e] = a / scale;                                  // :636
+        rd[e] = diff_rel(a, yv, mult);
         if (ads) {
             const double xs = sx ? sx[ox] : 0.0, ys = sy ? sy[oy] : 0.0;
-            const double m1 = mult * ys;
-            ads[e] = sqrt(xs * xs + m1 * m1);               // :652
-            const double u1 = xs / (mult * yv);
-            const double u2 = (ys * xv) / (mult * (yv * yv));
-            rds[e] = sqrt(u1 * u1 + u2 * u2);               // :653
+            ads[e] = diff_abs_std(xs, ys, mult);
+            rds[e] = diff_rel_std(xv, yv, xs, ys, mult);
         }
     }
 }
@@ -295,13 +262,12 @@ __global__ __launch_bounds__(256) void k_interpolate_bcast(const double* __restr
                                                            double y0, double y1, double y, double* __restrict__ out,
                                                            double* __restrict__ out_std, int64_t n, const Bcast2K b) {
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double a = y1 - y, bb = y - y0, d = y1 - y0;
-    const double ca = (a / d) * (a / d), cb = (bb / d) * (bb / d);
+    const InterpCoef k = interp_coef(y0, y1, y);
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
         int64_t o0, o1;
         bcast_offsets(b, e, o0, o1);
-        out[e] = (x0[o0] * a + x1[o1] * bb) / d;            // :665
-        if (out_std) out_std[e] = sqrt((s0 ? s0[o0] : 0.0) * ca + (s1 ? s1[o1] : 0.0) * cb);   // :679 as written
+        out[e] = interp_value(k, x0[o0], x1[o1]);
+        if (out_std) out_std[e] = interp_std(k, s0 ? s0[o0] : 0.0, s1 ? s1[o1] : 0.0);
     }
 }
 

@@ -1,0 +1,60 @@
+// hm_producer_math.h - the element formulas of the upstream producers, one text for the device units (hm_welford.hip, hm_noise.hip,
+// hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 rounding of the Welford result, the edge cleaning of one noise-profile row, and the
+// counter-based uniform draws of the differential evolution.
+//
+// DEVICE / HOST - the builds perform the same operations here.
+#pragma once
+#include "hm_math_common.h"
+
+namespace hm {
+
+// np.around(x).astype(uint8): round half to even, then the low byte of the 64-bit integer; NaN and |x| beyond 9.2e18 -> 0 (no
+// out-of-range conversion in either build)
+HM_MATH_FN uint8_t round_to_u8(double x) {
+    const double r = rint(x);
+    if (!(r == r)) return 0;
+    if (r >= 9.2e18 || r <= -9.2e18) return 0;
+    return static_cast<uint8_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 255u);
+}
+
+// Python's x // 2 on a 64-bit integer
+HM_MATH_FN int64_t floordiv2(int64_t x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
+
+// clean_data_edges, modules/video_processing.py:12-74, on one (row, channel) of a noise profile: the reference's four integer passes
+// centred at `center`, in order, in place. D(m) is a reference to bin m of the row, m in 0..255.
+template <typename Row>
+HM_MATH_FN void clean_edges_row(const Row& D, int center) {
+    const int min_dn = 0, max_dn = 255;
+    for (int m = center - 1; m > min_dn; --m) {                                    // :31-38
+        if (D(m) == 0 && D(m - 1) == 0) { for (int q = 0; q < m; ++q) D(q) = 0; break; }
+        if (D(m - 1) >= D(m) || D(m + 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
+    }
+    for (int m = center + 1; m < max_dn; ++m) {                                    // :41-48
+        if (D(m) == 0 && D(m + 1) == 0) { for (int q = m; q < 256; ++q) D(q) = 0; break; }
+        if (D(m + 1) >= D(m) || D(m - 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
+    }
+    for (int m = min_dn + 1; m < center;) {                                        // :51-58
+        if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m - 1);
+        else if (D(m) == D(m + 1) && D(m) != 0) { D(m + 1) += 1; m -= 1; }
+        m += 1;
+    }
+    for (int m = max_dn - 1; m > center;) {                                        // :61-68
+        if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m + 1);
+        else if (D(m) == D(m - 1) && D(m) != 0) { D(m - 1) += 1; m += 1; }
+        m -= 1;
+    }
+}
+
+// the splitmix64 step, and draw k of member i of a generation's key as a double in [0, 1) (53 bits)
+HM_MATH_FN uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+HM_MATH_FN double de_uniform(uint64_t key, int i, int k) {
+    const uint64_t r = mix64(key + (static_cast<uint64_t>(i + 1) << 20) + static_cast<uint64_t>(k));
+    return static_cast<double>(r >> 11) * 0x1.0p-53;
+}
+
+}  // namespace hm

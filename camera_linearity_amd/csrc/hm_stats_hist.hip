@@ -3,15 +3,14 @@
 //   hm_pairs_histogram, hm_pairs_minmax        ExposurePair.process_linearity_distribution, every pair  modules/exposure_series.py:56-76
 // and hm_histogram_workspace_bytes, hm_pairs_histogram_workspace_bytes.
 #include "hm_stats_pairs.h"
+#include "hm_ops_math.h"
+#include "hm_stats_math.h"
 #include <algorithm>
 
 namespace hm {
 
 // ---- per-channel histogram (compute_channel_histogram, modules/measurand.py:430-469) ----------------
-// np.histogram with `bins` equal-width bins on [lo, hi]: the bin of x is int((x - lo) * bins / (hi - lo)),
-// corrected against the actual edges (np.linspace(lo, hi, bins + 1), passed in by the caller) exactly as
-// numpy/lib/_histograms_impl.py does, the right edge inclusive. Non-finite values are skipped
-// (measurand.py:453); with weights, elements whose std is 0 are skipped and the weight is 1/std (:457-460).
+// The counting rule of one element: hm_stats_math.h, the text the host build compiles too.
 // Per-workgroup histograms in LDS (ds_add_f64), written as partials and column-summed: counts are exact,
 // weighted sums reproducible up to the order of the LDS atomics inside a workgroup.
 constexpr int kHistBlocks = 256;
@@ -30,19 +29,11 @@ __global__ __launch_bounds__(256) void k_hist(const double* __restrict__ val, co
         const int c = static_cast<int>(e % C);
         if (!((chan_mask >> c) & 1)) continue;
         const double x = val[e];
-        if (!(fabs(x) <= 1.79769313486231570e308)) continue;              // isfinite
+        if (!hist_finite(x)) continue;
         double w = 1.0;
-        if (sd) {
-            const double s = sd[e];
-            if (s == 0.0) continue;                                         // :457
-            w = 1.0 / s;                                                    // :460
-        }
-        if (!(x >= lo && x <= hi)) continue;                                // outside the range: not counted
-        int idx = static_cast<int>((x - lo) * norm);
-        if (idx == bins) idx -= 1;
-        if (x < edges[idx]) idx -= 1;
-        else if (x >= edges[idx + 1] && idx != bins - 1) idx += 1;
-        atomicAdd(&h[c * bins + idx], w);
+        if (sd && !hist_weight(sd[e], w)) continue;
+        if (!hist_in_range(x, lo, hi)) continue;
+        atomicAdd(&h[c * bins + hist_bin(x, lo, norm, edges, bins)], w);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nb; i += blockDim.x) partial[static_cast<int64_t>(blockIdx.x) * nb + i] = h[i];
@@ -67,7 +58,7 @@ __global__ __launch_bounds__(256) void k_minmax(const double* __restrict__ val, 
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
         const int c = static_cast<int>(e % C);
         const double x = val[e];
-        if (!(fabs(x) <= 1.79769313486231570e308)) continue;
+        if (!hist_finite(x)) continue;
         if (sd && sd[e] == 0.0) continue;
 #pragma unroll
         for (int k = 0; k < HM_MAX_CHANNELS; ++k) if (k == c) { mn[k] = fmin(mn[k], x); mx[k] = fmax(mx[k], x); }
@@ -101,27 +92,12 @@ __global__ __launch_bounds__(64) void k_minmax_final(const double* __restrict__ 
 // k_pairs_stats - a workgroup owns a run of elements (64-element chunks sb0, sb0 + stride, ...; the grid is a multiple of 12 workgroups,
 // so a lane keeps one channel), each of its waves works for ONE pair and reads its own operands, the waves of a workgroup walking the same
 // chunks at about the same time: a chunk comes from HBM once and from L1 / L2 for the other waves. No LDS staging here - the LDS is
-// what the histograms live in. The difference terms are k_difference's expressions, operation for operation; the bin
+// what the histograms live in. The difference terms are k_difference's (diff_terms of hm_ops_math.h); the bin
 // rule is k_hist's. Thresholds (apply_thresholds) act on the values AS READ: a value outside its channel's limits is NaN together with
 // its std, the frames are not written. Without thresholds the limits are -inf / +inf, which no value is outside of.
 // LDS: [pair of the launch][kind: absolute, relative][channel][bin] float64 (ds_add_f64: counts are integers below 2^53, exact).
 constexpr int kPairsHistBlocks = 252;          // workgroups per CU-share of the grid: a multiple of 12 just below the 256 CUs
 constexpr int kPairsHistMaxPerCU = 4;          // workgroups per CU when their LDS and wave count allow it (grid <= 4 x 252)
-
-template <bool STD>
-__device__ __forceinline__ void pairs_dist_terms(double xv, double xs, double yv, double ys, double mult, double& a, double& as, double& r,
-                                                 double& rs) {
-    const double scale = mult * yv;                     // measurand.py:634
-    a = xv - scale;                                     // :635
-    r = a / scale;                                      // :636
-    if constexpr (STD) {
-        const double m1 = mult * ys;
-        as = sqrt(xs * xs + m1 * m1);                   // :652
-        const double u1 = xs / (mult * yv);
-        const double u2 = (ys * xv) / (mult * (yv * yv));
-        rs = sqrt(u1 * u1 + u2 * u2);                   // :653
-    }
-}
 
 // one element of one pair as the kernels below see it: loaded, thresholded as read, differenced. Returns false past the end of the frames.
 template <bool STD>
@@ -143,28 +119,23 @@ struct PairsDistWave {
         xv = mx ? nan : xv; yv = my ? nan : yv;
         if constexpr (STD) { xs = mx ? nan : xs; ys = my ? nan : ys; }
         as = 0.0; rs = 0.0;
-        pairs_dist_terms<STD>(xv, xs, yv, ys, mult, av, as, rv, rs);
+        diff_terms(xv, yv, xs, ys, mult, STD, av, rv, as, rs);
     }
 };
 
-// k_hist's counting rule for one value into one (pair, kind, channel) histogram of `bins` LDS counters. The index is k_hist's
-// int((x - lo) * norm) with `idx == bins -> bins - 1`, written so that NO edge array - edges are device data nobody has checked - can
-// take it outside 0..bins-1: x >= lo = eg[0] rules out the step below bin 0, the step up is not taken from the last bin.
+// k_hist's counting rule for one value into one (pair, kind, channel) histogram of `bins` LDS counters, with the index form that NO edge
+// array - edges are device data nobody has checked - can take outside 0..bins-1 (hist_bin_bounded of hm_stats_math.h).
 template <bool STD>
 __device__ __forceinline__ void pairs_hist_count(double* h, const double* __restrict__ eg, int bins, double lo, double hi, double norm,
                                                  double x, double s) {
-    if (!(fabs(x) <= 1.79769313486231570e308)) return;                    // isfinite
+    if (!hist_finite(x)) return;
     double w = 1.0;
-    if constexpr (STD) {
+    if constexpr (STD) {                                                    // hist_weight() written out: called here, the kernel's code changes
         if (s == 0.0) return;                                               // measurand.py:457
         w = 1.0 / s;                                                        // :460
     }
-    if (!(x >= lo && x <= hi)) return;
-    const double t = (x - lo) * norm;
-    int idx = t < static_cast<double>(bins) ? static_cast<int>(t) : bins - 1;
-    if (x < eg[idx]) idx -= 1;
-    else if (x >= eg[idx + 1] && idx != bins - 1) idx += 1;
-    atomicAdd(&h[idx], w);
+    if (!hist_in_range(x, lo, hi)) return;
+    atomicAdd(&h[hist_bin_bounded(x, lo, norm, eg, bins)], w);
 }
 
 template <bool STD>
@@ -222,7 +193,7 @@ __global__ __launch_bounds__(1024) void k_pairs_minmax(const PairsK a, double* _
         w.element(q, v[0], s[0], v[1], s[1]);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const bool use = fabs(v[k]) <= 1.79769313486231570e308 && !(STD && s[k] == 0.0);
+            const bool use = hist_finite(v[k]) && !(STD && s[k] == 0.0);
             mn[k] = use ? fmin(mn[k], v[k]) : mn[k];
             mx[k] = use ? fmax(mx[k], v[k]) : mx[k];
         }

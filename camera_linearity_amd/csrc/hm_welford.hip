@@ -28,6 +28,7 @@
 // a non-zero f/n >= 2^-540 dwarfs it and a run of f = 0 shrinks it by n0/n >= 2^-40 at most - so a non-zero delta = f - m is >= 2^-684.
 // A lane whose state or table is outside those ranges (or not finite) redoes its elements with the full division (welford_exact).
 #include "hm_common.h"
+#include "hm_producer_math.h"
 #include "hm_producer_rules.h"
 
 namespace hm {
@@ -158,15 +159,6 @@ __global__ __launch_bounds__(256) void k_welford(const WelfordK a) {
         a.mean[e] = m[0];
         if (M2) a.m2[e] = q[0];
     }
-}
-
-// around() = round half to even; astype(uint8) of an in-range value. Out-of-range / NaN inputs follow the
-// convention of hm_linearize_f64's index: convert to a 64-bit integer and keep the low byte (NaN -> 0).
-__device__ __forceinline__ uint8_t round_to_u8(double x) {
-    const double r = rint(x);
-    if (!(r == r)) return 0;
-    if (r >= 9.2e18 || r <= -9.2e18) return 0;
-    return static_cast<uint8_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 255u);
 }
 
 __global__ __launch_bounds__(256) void k_welford_finalize(const double* __restrict__ mean, const double* __restrict__ m2,

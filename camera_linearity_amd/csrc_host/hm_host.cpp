@@ -6,8 +6,9 @@
 // synchronous, workspaces may be NULL - written from scratch in plain C++ (g++ -O2 -fopenmp, no HIP, no NumPy, nothing from
 // oracle/). It is selected EXPLICITLY (Measurand(use_cupy=False) / HostMeasurand); the HIP backend never falls back to it.
 //
-// Arithmetic: the operation sequence of the device kernels, element by element (merge_one_element of hm_merge_dev.h, the operator
-// formulas of hm_ops.hip, ...), each citing the reference line it follows. Statistics use the reference's own two-pass form.
+// Arithmetic: the operation sequence of the device kernels, element by element. The element formulas are the ../csrc/hm_*_math.h headers
+// included below, the text the device kernels compile too; where the builds differ on purpose the header's top comment says so.
+// Statistics use the reference's own two-pass form.
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
 // hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twin of
@@ -16,6 +17,10 @@
 // The argument rules of most entries are a check_* of the ../csrc/hm_*_rules.h headers included below, the copies the device build compiles
 // too; where this build differs the check is called with hm_rules::HOST, and the header's top comment lists the difference.
 #include "hdrmerge.h"
+#include "../csrc/hm_merge_math.h"
+#include "../csrc/hm_ops_math.h"
+#include "../csrc/hm_stats_math.h"
+#include "../csrc/hm_producer_math.h"
 #include "../csrc/hm_merge_rules.h"
 #include "../csrc/hm_calibration_rules.h"
 #include "../csrc/hm_frame_rules.h"
@@ -41,25 +46,7 @@ namespace {
 constexpr double kNaN = std::numeric_limits<double>::quiet_NaN();
 constexpr double kInf = std::numeric_limits<double>::infinity();
 using hm_rules::aligned8, hm_rules::dense_elems;
-
-// measurand.py:615: w = e ** (-30 (v - 0.5)^2)
-inline double gauss_weight(double dv) { return std::exp(-30.0 * (dv * dv)); }
-
-// measurand.py:503: around(v * 255) (half to even) then astype(uint8) - wraps modulo 256, negatives included
-inline uint32_t lut_index(double v) {
-    const double r = std::nearbyint(v * 255.0);          // default rounding mode: to nearest even
-    if (!(r == r) || r >= 9.2e18 || r <= -9.2e18) return 0u;
-    return static_cast<uint32_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 255u);
-}
-
-// scipy.ndimage 'reflect' (d c b a | a b c d)
-inline int64_t reflect_index(int64_t i, int64_t n) {
-    while (i < 0 || i >= n) {
-        if (i < 0) i = -i - 1;
-        if (i >= n) i = 2 * n - i - 1;
-    }
-    return i;
-}
+using namespace hm;                                   // the element formulas of the hm_*_math.h headers
 
 // k x k median of one channel around one pixel; buf holds image rows [buf_row0, ...)
 template <typename T>
@@ -96,17 +83,10 @@ inline double median_mapped_at(const T* buf, At at, int64_t H, int64_t W, int C,
     return v[n / 2];
 }
 
-// measurand.py:585-602 (1 / F**2 formed once, as the device kernels do; <= 2 ulp on the std)
-inline void flat_field_math(double F, double sF, double m, double s, bool with_std, double& val, double& sd) {
-    if (with_std) {
-        const double iF2 = 1.0 / (F * F);
-        const double v2 = val * val;
-        const double u_acq = ((sd * sd) * iF2) * (m * m);
-        const double u_ff = ((v2 * (iF2 * iF2)) * (sF * sF)) * (m * m);
-        const double u_ffm = (v2 * iF2) * (s * s);
-        sd = std::sqrt(u_acq + u_ff + u_ffm);
-    }
-    val = (val / F) * m;
+// flat-field epilogue of merge element e of channel c: flat_field_apply of hm_merge_dev.h (the uint16 entries have no uint8 flat)
+inline void flat_apply(const hm_merge_args* g, int64_t e, int c, bool with_std, double& val, double& sd) {
+    const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
+    flat_field_math(F, with_std ? 1.0 / (F * F) : 1.0, with_std ? g->flat_std[e] : 0.0, g->ff_mean[c], g->ff_std_mean[c], with_std, val, sd);
 }
 
 // the two operands' offsets of element e of a checked broadcast (hm_rules::check_bcast)
@@ -155,22 +135,6 @@ inline void line_statistics(int64_t n, bool weighted, Get get, double& mean, dou
     err = cs ? ss / static_cast<double>(cs) : kNaN;                                // nanmean(stds)
 }
 
-// ExposurePair difference terms of one element (measurand.py:634-653)
-inline void diff_terms(double xv, double xs, double yv, double ys, double mult, bool with_std,
-                       double& a, double& as, double& r, double& rs) {
-    const double scale = mult * yv;
-    a = xv - scale;
-    r = a / scale;
-    as = 0.0; rs = 0.0;
-    if (with_std) {
-        const double m1 = mult * ys;
-        as = std::sqrt(xs * xs + m1 * m1);
-        const double u1 = xs / (mult * yv);
-        const double u2 = (ys * xv) / (mult * (yv * yv));
-        rs = std::sqrt(u1 * u1 + u2 * u2);
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -206,7 +170,7 @@ int hm_gaussian_weight_f64(const double* v, double* w, double* dw, int64_t n, vo
         const double dv = v[e] - 0.5;
         const double y = gauss_weight(dv);
         if (w) w[e] = y;
-        if (dw) dw[e] = (-60.0 * dv) * y;                                         // measurand.py:616
+        if (dw) dw[e] = gauss_dweight(dv, y);                                     // measurand.py:616
     }
     return HM_OK;
 }
@@ -372,10 +336,7 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
                         const int64_t e = lo + j;
                         if (g->out_sum_w) g->out_sum_w[e] = S4[j];
                         double val = a4[j] / S4[j], none = 0.0;
-                        if (flat) {
-                            const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
-                            flat_field_math(F, 0.0, g->ff_mean[cb[j]], g->ff_std_mean[cb[j]], false, val, none);
-                        }
+                        if (flat) flat_apply(g, e, cb[j], false, val, none);
                         put(g->out_val, e, val);
                     }
                 }
@@ -427,11 +388,8 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
                 if (g->out_sum_w) g->out_sum_w[e] = S;
                 if (!g->out_val) continue;
                 double val1 = acc1 / S;
-                if (flat) {
-                    double none = 0.0;
-                    const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
-                    flat_field_math(F, 0.0, g->ff_mean[c], g->ff_std_mean[c], false, val1, none);
-                }
+                double none = 0.0;
+                if (flat) flat_apply(g, e, c, false, val1, none);
                 put(g->out_val, e, val1);
                 continue;
             }
@@ -449,7 +407,7 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
                 if constexpr (F64IN) {
                     const double dv = v[i] - 0.5;
                     w = gauss_weight(dv);
-                    dw = (-60.0 * dv) * w;
+                    dw = gauss_dweight(dv, w);
                     idx = lut_index(v[i]);
                 } else {
                     idx = dn[i];
@@ -462,17 +420,13 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
                 acc = i == 0 ? wg * it : std::fma(wg, it, acc);                     // :388 numerator
                 if constexpr (STD) {
                     const double dg = g->icrf_diff[idx * C + c] * sdv[i];                                // measurand.py:512
-                    const double A = (dw * gg + w * dg) * invS - ((dw * w) * gg) * invS2;                // :389
-                    const double term = (A * dg) * it;
+                    const double term = merge_var_term(w, dw, gg, dg, invS, invS2, it);                  // :389
                     var = i == 0 ? term * term : std::fma(term, term, var);
                 }
             }
             double val = acc / S;
             double sd = STD ? std::sqrt(var) : 0.0;                                 // :394
-            if (flat) {
-                const double F = g->flat_u8 ? static_cast<double>(g->flat_u8[e]) / 255.0 : g->flat_f64[e];
-                flat_field_math(F, STD ? g->flat_std[e] : 0.0, g->ff_mean[c], g->ff_std_mean[c], STD, val, sd);
-            }
+            if (flat) flat_apply(g, e, c, STD, val, sd);
             put(g->out_val, e, val);
             if constexpr (STD) put(g->out_std, e, sd);
         }
@@ -536,14 +490,13 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
             if constexpr (STD) {
                 const double dw = g->dw_lut[idx];
                 const double dg = g->icrf_diff[idx * C + c] * sd_at(i);                               // measurand.py:512
-                const double A = (dw * gg + w * dg) * invS - ((dw * w) * gg) * invS2;                // :389
-                const double term = (A * dg) * it;
+                const double term = merge_var_term(w, dw, gg, dg, invS, invS2, it);                  // :389
                 var = i == 0 ? term * term : std::fma(term, term, var);
             }
         }
         double val = acc / S;
         double sd = STD ? std::sqrt(var) : 0.0;                                 // :394
-        if (flat) flat_field_math(g->flat_f64[e], STD ? g->flat_std[e] : 0.0, g->ff_mean[c], g->ff_std_mean[c], STD, val, sd);
+        if (flat) flat_apply(g, e, c, STD, val, sd);
         put(g->out_val, e, val);
         if constexpr (STD) put(g->out_std, e, sd);
     }
@@ -695,7 +648,7 @@ int hm_normalize_by_map(const double* val, const double* std_, const uint8_t* fl
         const int c = static_cast<int>(e % C);
         const double F = flat_u8 ? static_cast<double>(flat_u8[e]) / 255.0 : flat_f64[e];
         double v = val[e], s = out_std ? std_[e] : 0.0;
-        flat_field_math(F, out_std ? flat_std[e] : 0.0, ff_mean[c], out_std ? ff_std_mean[c] : 0.0, out_std != nullptr, v, s);
+        flat_field_math(F, out_std ? 1.0 / (F * F) : 1.0, out_std ? flat_std[e] : 0.0, ff_mean[c], out_std ? ff_std_mean[c] : 0.0, out_std != nullptr, v, s);
         out_val[e] = v;
         if (out_std) out_std[e] = s;
     }
@@ -717,13 +670,11 @@ int hm_binary_op(int op, const double* x1, const double* s1, const double* x2, c
         const double sa = (with_std && s1) ? s1[o1] : 0.0, sc = (with_std && s2) ? s2[o2] : 0.0;       // missing std -> zeros (:121-124)
         double r, rs = 0.0;
         switch (op) {
-            case HM_OP_ADD: r = a + c; if (with_std) rs = std::sqrt((sa * sa) + (sc * sc)); break;       // :114,126
-            case HM_OP_SUB: r = a - c; if (with_std) rs = std::sqrt((sa * sa) + (sc * sc)); break;       // :138,149
-            case HM_OP_MUL: r = a * c; if (with_std) { const double p = a * sc, q = c * sa; rs = std::sqrt(p * p + q * q); } break;   // :198,209
-            case HM_OP_DIV: r = a / c; if (with_std) { const double u1 = sa / c, u2 = (a * sc) / (c * c); rs = std::sqrt(u1 * u1 + u2 * u2); } break;   // :173,184-186
-            default:
-                r = std::pow(a, c);                                                                      // :225,236-239
-                if (with_std) { const double u1 = c * std::pow(a, c - 1.0), u2 = std::log(a) * r; const double p = u1 * sa, q = u2 * sc; rs = std::sqrt(p * p + q * q); }
+            case HM_OP_ADD: binary_eval<HM_OP_ADD>(a, sa, c, sc, with_std, r, rs); break;
+            case HM_OP_SUB: binary_eval<HM_OP_SUB>(a, sa, c, sc, with_std, r, rs); break;
+            case HM_OP_MUL: binary_eval<HM_OP_MUL>(a, sa, c, sc, with_std, r, rs); break;
+            case HM_OP_DIV: binary_eval<HM_OP_DIV>(a, sa, c, sc, with_std, r, rs); break;
+            default: binary_eval<HM_OP_POW>(a, sa, c, sc, with_std, r, rs);
         }
         out_val[e] = r;
         if (with_std) out_std[e] = rs;
@@ -733,14 +684,10 @@ int hm_binary_op(int op, const double* x1, const double* s1, const double* x2, c
 
 int hm_unary_op(int op, const double* x, const double* s, double* out_val, double* out_std, int64_t n, void*) {
     if (const int rc = hm_rules::check_unary_op(op, x, s, out_val, out_std, n, hm_rules::HOST); rc != HM_OK) return rc;
-    const double ln10 = 0x1.26bb1bbb55515p+1;                  // fl(log 5) + fl(log 2), the constant measurand.py:277 forms (hm_ops.hip holds the same literal)
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
-        const double v = x[e];
         double r, rs = 0.0;
-        if (op == HM_UOP_NEG) { r = -v; if (out_std) rs = s[e]; }                                        // :154-157
-        else if (op == HM_UOP_LOG_E) { r = std::log(v); if (out_std) rs = s[e] / r; }                    // :251,258 (as written)
-        else { r = std::log10(v); if (out_std) rs = s[e] / (v * ln10); }                                 // :270,277
+        unary_eval(op, x[e], out_std != nullptr, [&] { return s[e]; }, r, rs);
         out_val[e] = r;
         if (out_std) out_std[e] = rs;
     }
@@ -750,24 +697,19 @@ int hm_unary_op(int op, const double* x, const double* s, double* out_val, doubl
 int hm_pow_scalar(const double* x, const double* s, double exponent, double* out_val, double* out_std, int64_t n, void*) {
     if (const int rc = hm_rules::check_unary_op(HM_UOP_NEG, x, s, out_val, out_std, n, hm_rules::HOST); rc != HM_OK) return rc;
     const double p = exponent;
+    const int kind = p == 2.0 ? POW_SQUARE : p == 0.5 ? POW_SQRT : p == 1.0 ? POW_ONE : POW_GENERAL;     // never POW_INT: hm_ops_math.h
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
-        const double v = x[e];
-        double r, d;                                                                                     // d = x ** (p - 1)
-        if (p == 2.0) { r = v * v; d = v; }
-        else if (p == 0.5) {                                    // sqrt: the correctly rounded x ** 0.5. NumPy's pow() differs from it at two arguments only:
-            const double av = (v == 0.0 || v == -kInf) ? std::fabs(v) : v;              // -inf -> +inf (d = +0) and -0.0 -> +0.0 (d = +inf)
-            r = std::sqrt(av); d = 1.0 / r;
+        const double v = x[e], sv = out_std ? s[e] : 0.0;
+        double r, rs = 0.0;
+        switch (kind) {
+            case POW_SQUARE: pow_scalar_eval<POW_SQUARE>(v, sv, p, 0, out_std != nullptr, r, rs); break;
+            case POW_SQRT: pow_scalar_eval<POW_SQRT>(v, sv, p, 0, out_std != nullptr, r, rs); break;
+            case POW_ONE: pow_scalar_eval<POW_ONE>(v, sv, p, 0, out_std != nullptr, r, rs); break;
+            default: pow_scalar_eval<POW_GENERAL>(v, sv, p, 0, out_std != nullptr, r, rs);
         }
-        else if (p == 1.0) { r = v; d = 1.0; }
-        else { r = std::pow(v, p); d = std::pow(v, p - 1.0); }
         out_val[e] = r;
-        if (out_std) {
-            const double a = (p * d) * s[e];                                                             // :236
-            double bterm = 0.0;                                                                          // (log(x1) * x1**x2) * 0, :237-238
-            if (!(v > 0.0) || !(std::fabs(v) < kInf) || !(std::fabs(r) < kInf)) bterm = (std::log(v) * r) * 0.0;
-            out_std[e] = std::sqrt(a * a + bterm * bterm);
-        }
+        if (out_std) out_std[e] = rs;
     }
     return HM_OK;
 }
@@ -810,8 +752,8 @@ int hm_compute_difference_bcast(const double* x, const double* sx, const double*
     for (int64_t e = 0; e < n; ++e) {
         int64_t ox, oy;
         bcast_offsets(ndim, shape, strides_x, strides_y, e, ox, oy);
-        double a, as, r, rs;
-        diff_terms(x[ox], sx ? sx[ox] : 0.0, y[oy], sy ? sy[oy] : 0.0, multiplier, with_std, a, as, r, rs);
+        double a, as = 0.0, r, rs = 0.0;
+        diff_terms(x[ox], y[oy], sx ? sx[ox] : 0.0, sy ? sy[oy] : 0.0, multiplier, with_std, a, r, as, rs);
         out_abs[e] = a; out_rel[e] = r;
         if (with_std) { out_abs_std[e] = as; out_rel_std[e] = rs; }
     }
@@ -827,14 +769,13 @@ int hm_interpolate_bcast(const double* x0, const double* s0, const double* x1, c
                          double* out, double* out_std, int ndim, const int64_t* shape, const int64_t* strides0, const int64_t* strides1, void*) {
     int64_t n;
     if (const int rc = hm_rules::check_interpolate_bcast(x0, s0, x1, s1, out, out_std, ndim, shape, strides0, strides1, n); rc != HM_OK) return rc;
-    const double a = y1 - y, bb = y - y0, d = y1 - y0;
-    const double ca = (a / d) * (a / d), cb = (bb / d) * (bb / d);
+    const InterpCoef k = interp_coef(y0, y1, y);
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n; ++e) {
         int64_t o0, o1;
         bcast_offsets(ndim, shape, strides0, strides1, e, o0, o1);
-        out[e] = (x0[o0] * a + x1[o1] * bb) / d;                                                         // :665
-        if (out_std) out_std[e] = std::sqrt((s0 ? s0[o0] : 0.0) * ca + (s1 ? s1[o1] : 0.0) * cb);       // :679 as written
+        out[e] = interp_value(k, x0[o0], x1[o1]);
+        if (out_std) out_std[e] = interp_std(k, s0 ? s0[o0] : 0.0, s1 ? s1[o1] : 0.0);
     }
     return HM_OK;
 }
@@ -900,8 +841,8 @@ int hm_pair_statistics(const double* x, const double* sx, const double* y, const
             double mean, sd, err;
             line_statistics(A, with_std, [&](int64_t k, double& v, double& u) {
                 const int64_t e = k * C + c;
-                double a, as, r, rs;
-                diff_terms(x[e], sx ? sx[e] : 0.0, y[e], sy ? sy[e] : 0.0, multiplier, with_std, a, as, r, rs);
+                double a, as = 0.0, r, rs = 0.0;
+                diff_terms(x[e], y[e], sx ? sx[e] : 0.0, sy ? sy[e] : 0.0, multiplier, with_std, a, r, as, rs);
                 v = h == 0 ? a : r; u = h == 0 ? as : rs;
             }, mean, sd, err);
             double* o = out + 3 * C * h;
@@ -932,7 +873,7 @@ int hm_channel_minmax(const double* val, const double* std_, int64_t n, int C, d
     for (int c = 0; c < C; ++c) { out[2 * c] = kInf; out[2 * c + 1] = -kInf; }
     for (int64_t e = 0; e < n; ++e) {
         const double x = val[e];
-        if (!(std::fabs(x) <= std::numeric_limits<double>::max())) continue;
+        if (!hist_finite(x)) continue;
         if (std_ && std_[e] == 0.0) continue;
         const int c = static_cast<int>(e % C);
         out[2 * c] = std::fmin(out[2 * c], x); out[2 * c + 1] = std::fmax(out[2 * c + 1], x);
@@ -949,15 +890,11 @@ int hm_channel_histogram(const double* val, const double* std_, int64_t n, int C
         const int c = static_cast<int>(e % C);
         if (!((channel_mask >> c) & 1)) continue;
         const double x = val[e];
-        if (!(std::fabs(x) <= std::numeric_limits<double>::max())) continue;
+        if (!hist_finite(x)) continue;
         double w = 1.0;
-        if (std_) { const double s = std_[e]; if (s == 0.0) continue; w = 1.0 / s; }                     // :457,460
-        if (!(x >= lo && x <= hi)) continue;
-        int idx = static_cast<int>((x - lo) * norm);
-        if (idx == bins) idx -= 1;
-        if (x < edges[idx]) idx -= 1;
-        else if (x >= edges[idx + 1] && idx != bins - 1) idx += 1;
-        out[c * bins + idx] += w;
+        if (std_ && !hist_weight(std_[e], w)) continue;
+        if (!hist_in_range(x, lo, hi)) continue;
+        out[c * bins + hist_bin(x, lo, norm, edges, bins)] += w;
     }
     return HM_OK;
 }
@@ -977,7 +914,8 @@ struct PairElems {
             if (xv < lower[c] || xv > upper[c]) { xv = kNaN; xs = sx ? kNaN : 0.0; }                      // measurand.py:418
             if (yv < lower[c] || yv > upper[c]) { yv = kNaN; ys = sy ? kNaN : 0.0; }
         }
-        diff_terms(xv, xs, yv, ys, mult, sx != nullptr, a, as, r, rs);
+        as = 0.0; rs = 0.0;
+        diff_terms(xv, yv, xs, ys, mult, sx != nullptr, a, r, as, rs);
     }
 };
 }  // namespace
@@ -999,7 +937,7 @@ int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_
             pe.at(e, v[0], s[0], v[1], s[1]);
             const int c = static_cast<int>(e % C);
             for (int k = 0; k < 2; ++k) {
-                if (!(std::fabs(v[k]) <= std::numeric_limits<double>::max())) continue;
+                if (!hist_finite(v[k])) continue;
                 if (stds && s[k] == 0.0) continue;
                 double* m = o + (k * C + c) * 2;
                 m[0] = std::fmin(m[0], v[k]); m[1] = std::fmax(m[1], v[k]);
@@ -1031,15 +969,11 @@ int hm_pairs_histogram(const double* const* vals, const double* const* stds, int
                 const double* ek = eg + static_cast<int64_t>(k * C + c) * (bins + 1);
                 const double lo = ek[0], hi = ek[bins];
                 if (!(hi > lo)) continue;                                                                 // (hm_channel_histogram: HM_EINVAL)
-                if (!(std::fabs(x) <= std::numeric_limits<double>::max())) continue;
+                if (!hist_finite(x)) continue;
                 double w = 1.0;
-                if (stds) { if (s[k] == 0.0) continue; w = 1.0 / s[k]; }                                  // :457,460
-                if (!(x >= lo && x <= hi)) continue;
-                const double t = (x - lo) * (static_cast<double>(bins) / (hi - lo));
-                int idx = t < static_cast<double>(bins) ? static_cast<int>(t) : bins - 1;                 // (the device build's form: never outside 0..bins-1)
-                if (x < ek[idx]) idx -= 1;
-                else if (x >= ek[idx + 1] && idx != bins - 1) idx += 1;
-                o[static_cast<int64_t>(k * C + c) * bins + idx] += w;
+                if (stds && !hist_weight(s[k], w)) continue;
+                if (!hist_in_range(x, lo, hi)) continue;
+                o[static_cast<int64_t>(k * C + c) * bins + hist_bin_bounded(x, lo, static_cast<double>(bins) / (hi - lo), ek, bins)] += w;
             }
         }
     }
@@ -1070,13 +1004,6 @@ int hm_welford_update(const void* const* frames, int n_frames, int64_t count_bef
         if (m2) m2[e] = q;
     }
     return HM_OK;
-}
-
-// np.around(x).astype(uint8) as the device build defines it: round half even, NaN and |x| >= 2^63 -> 0, else the low byte
-static inline uint8_t round_to_u8(double x) {
-    const double r = std::nearbyint(x);
-    if (!(r == r) || r >= 9.2e18 || r <= -9.2e18) return 0;
-    return static_cast<uint8_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 255u);
 }
 
 int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uint8_t* out_mean, uint8_t* out_std, int64_t n_elems, void*) {
@@ -1145,7 +1072,6 @@ int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, do
 }
 
 // clean_data_edges, video_processing.py:12-74: per (row i, channel c) the four integer passes centred at i, in order, in place
-static inline int64_t floordiv2(int64_t x) { return x >= 0 ? x / 2 : -((-x + 1) / 2); }
 int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
     const int rc = hm_rules::check_noise_profile_clean_edges(profiles, C);
     if (rc != HM_OK) return rc;
@@ -1153,26 +1079,7 @@ int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
     for (int t = 0; t < 256 * C; ++t) {
         const int i = t / C, c = t % C;
         int64_t* row = profiles + static_cast<int64_t>(i) * 256 * C + c;
-        auto D = [&](int m) -> int64_t& { return row[static_cast<int64_t>(m) * C]; };
-        const int center = i, min_dn = 0, max_dn = 255;
-        for (int m = center - 1; m > min_dn; --m) {                                       // :31-38
-            if (D(m) == 0 && D(m - 1) == 0) { for (int q = 0; q < m; ++q) D(q) = 0; break; }
-            if (D(m - 1) >= D(m) || D(m + 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
-        }
-        for (int m = center + 1; m < max_dn; ++m) {                                       // :41-48
-            if (D(m) == 0 && D(m + 1) == 0) { for (int q = m; q < 256; ++q) D(q) = 0; break; }
-            if (D(m + 1) >= D(m) || D(m - 1) <= D(m)) D(m) = floordiv2(D(m - 1) + D(m + 1));
-        }
-        for (int m = min_dn + 1; m < center;) {                                           // :51-58
-            if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m - 1);
-            else if (D(m) == D(m + 1) && D(m) != 0) { D(m + 1) += 1; m -= 1; }
-            m += 1;
-        }
-        for (int m = max_dn - 1; m > center;) {                                           // :61-68
-            if (D(m) == 0 && D(m - 1) != 0 && D(m + 1) != 0) D(m) = D(m + 1);
-            else if (D(m) == D(m - 1) && D(m) != 0) { D(m - 1) += 1; m += 1; }
-            m -= 1;
-        }
+        clean_edges_row([&](int m) -> int64_t& { return row[static_cast<int64_t>(m) * C]; }, i);
     }
     return HM_OK;
 }
@@ -1184,13 +1091,6 @@ int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
 constexpr int kKdeSlices = 256;
 constexpr int64_t kKdeChunk = 4096;
 size_t hm_kde_workspace_bytes(int64_t, int, int) { return 0; }
-static inline bool kde_load(const double* val, const double* std_, int64_t e, double& x, double& w) {
-    x = val[e];
-    w = 1.0;
-    bool ok = std::isfinite(x);
-    if (std_) { const double s = std_[e]; ok = ok && s != 0.0; w = 1.0 / s; }
-    return ok;
-}
 int hm_kde_moments(const double* val, const double* std_, int64_t n_elems, int C, int channel, double* moments, void*, int64_t workspace_bytes, void*) {
     const int rc = hm_rules::check_kde_moments(val, n_elems, C, channel, moments, nullptr, workspace_bytes, false);
     if (rc != HM_OK) return rc;
@@ -1368,15 +1268,6 @@ int hm_linearity_energy_u16_describe(int64_t n_pixels, int n_frames, int n_candi
 // One generation of the ICRF-calibration differential evolution (calibration(), modules/ICRF_calibration_exposure.py:288-369), as
 // specified in hdrmerge.h: trial (mutation, crossover, redraw), candidate ICRF + verdicts, energy (hm_linearity_energy above),
 // deferred selection, statistics and the stop flag - the HIP build's hm_de.hip with host pointers.
-static inline uint64_t de_mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static inline double de_uniform(uint64_t key, int i, int k) {
-    return static_cast<double>(de_mix64(key + (static_cast<uint64_t>(i + 1) << 20) + static_cast<uint64_t>(k)) >> 11) * 0x1.0p-53;
-}
 static inline double de_tree_sum(std::vector<double>& v) {                // the HIP build's fixed-order tree (size: a power of two)
     for (size_t s = v.size() >> 1; s > 0; s >>= 1)
         for (size_t t = 0; t < s; ++t) v[t] += v[t + s];
@@ -1396,7 +1287,7 @@ int hm_de_generation(double* population, double* energies, double* trial, double
     if (status[HM_DE_STOP] != 0) return HM_OK;                            // this build's own (status is host memory here): after the stop flag a generation is a no-op
     const int S = pop_size, P = n_params;
     const int64_t g = status[HM_DE_GENERATION];
-    const uint64_t key = de_mix64(static_cast<uint64_t>(seed) ^ de_mix64(static_cast<uint64_t>(g)));
+    const uint64_t key = mix64(static_cast<uint64_t>(seed) ^ mix64(static_cast<uint64_t>(g)));
     const double F = mutation_lo + (mutation_hi - mutation_lo) * de_uniform(key, S, 0);
     const int b = std::min(std::max(static_cast<int>(status[HM_DE_BEST_INDEX]), 0), S - 1);
     for (int i = 0; i < S; ++i) {
