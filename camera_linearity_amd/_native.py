@@ -144,6 +144,12 @@ _SIGNATURES = {
                                     C.c_int64, C.c_int, C.c_void_p]),
     "hm_welford_finalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hm_welford_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    # the producer on uint16 frames: ... n_elems, C, bit_depth, variant, stream / ... count, bit_depth, out_mean, out_std, n_elems, stream
+    "hm_welford_update_u16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hm_welford_finalize_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hm_welford_u16_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "hm_welford_update_u16_describe": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char), C.c_int]),
     "hm_noise_profile_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "hm_noise_profile_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int]),
     "hm_noise_profile_update": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

@@ -1,5 +1,5 @@
-// hm_producer_math.h - the element formulas of the upstream producers, one text for the device units (hm_welford.hip, hm_noise.hip,
-// hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 rounding of the Welford result, the edge cleaning of one noise-profile row, and the
+// hm_producer_math.h - the element formulas of the upstream producers, one text for the device units (hm_welford.hip, hm_welford_u16.hip,
+// hm_noise.hip, hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 / uint16 rounding of the Welford result, the edge cleaning of one noise-profile row, and the
 // counter-based uniform draws of the differential evolution.
 //
 // DEVICE / HOST - the builds perform the same operations here.
@@ -15,6 +15,14 @@ HM_MATH_FN uint8_t round_to_u8(double x) {
     if (!(r == r)) return 0;
     if (r >= 9.2e18 || r <= -9.2e18) return 0;
     return static_cast<uint8_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 255u);
+}
+
+// np.around(x).astype(uint16) by the same convention: the low 16 bits of the 64-bit integer, so round_to_u16(x) & 255 == round_to_u8(x)
+HM_MATH_FN uint16_t round_to_u16(double x) {
+    const double r = rint(x);
+    if (!(r == r)) return 0;
+    if (r >= 9.2e18 || r <= -9.2e18) return 0;
+    return static_cast<uint16_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 65535u);
 }
 
 // Python's x // 2 on a 64-bit integer

@@ -1,7 +1,8 @@
-// hm_producer_rules.h - the argument rules of the producer entries (hm_welford_update, hm_welford_finalize, hm_noise_profile_update,
-// hm_noise_profile_std, hm_noise_profile_clean_edges, hm_kde_moments, hm_kde_evaluate), written once for both builds of the ABI in the
-// manner of hm_merge_rules.h: the device build (hm_welford.hip, hm_noise.hip, hm_kde.hip) and the host build (csrc_host/hm_host.cpp)
-// include this file and restate none of it. Plain C++17 on hdrmerge.h and <cmath>: no HIP type.
+// hm_producer_rules.h - the argument rules of the producer entries (hm_welford_update, hm_welford_finalize, hm_welford_update_u16,
+// hm_welford_finalize_u16, hm_noise_profile_update, hm_noise_profile_std, hm_noise_profile_clean_edges, hm_kde_moments, hm_kde_evaluate),
+// written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build (hm_welford.hip, hm_welford_u16.hip,
+// hm_noise.hip, hm_kde.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it. Plain C++17 on hdrmerge.h
+// and <cmath>: no HIP type.
 //
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call. `empty` is set
 // with HM_OK when there is nothing to do; which rules have been looked at by then differs per entry and is kept as it always was.
@@ -42,6 +43,81 @@ inline int check_welford_finalize(const double* mean, const double* m2, int64_t 
     if (n_elems == 0) { empty = true; return HM_OK; }
     if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
     if (out_std && count < 2) return HM_EINVAL;                               // m2 / (n - 1) needs two frames
+    return HM_OK;
+}
+
+// ---- hm_welford_update_u16 / hm_welford_finalize_u16: uint16 frames of bit_depth 9..16 ----------------------------------------------
+// Where the device kernel takes a frame value f from (`variant`; the host build checks it and ignores it). 0 is the library's choice.
+//   WELFORD_U16_LDS       a table in LDS: the ICRF as t[ch][dn] (8 * 2^b * C bytes), or without an ICRF the one column dn / M (8 * 2^b)
+//   WELFORD_U16_COMPUTED  no table: f = (DN & M) / M evaluated in the lane. Exists only without an ICRF.
+//   WELFORD_U16_GLOBAL    no copy: the ICRF gathered from global memory. Exists only with an ICRF.
+enum WelfordU16Tab { WELFORD_U16_AUTO = 0, WELFORD_U16_LDS = 1, WELFORD_U16_COMPUTED = 2, WELFORD_U16_GLOBAL = 3 };
+
+// The fit rule: the LDS table may take 128 KiB of the CU's 160 KiB (the rest is the workgroup's flag word and headroom) - with an ICRF
+// C = 1 up to 14 bits, C = 2 up to 13, C = 3 and 4 up to 12 (96 / 128 KiB); without one up to 14 bits.
+constexpr int64_t kWelfordU16LdsTableBytes = 128 * 1024;
+inline int64_t welford_u16_table_bytes(int bit_depth, int C, bool with_icrf) { return (int64_t{8} << bit_depth) * (with_icrf ? C : 1); }
+inline bool welford_u16_table_fits_lds(int bit_depth, int C, bool with_icrf) {
+    return welford_u16_table_bytes(bit_depth, C, with_icrf) <= kWelfordU16LdsTableBytes;
+}
+// whether a forced placement exists for the call and its table fits
+inline bool welford_u16_placement_applies(int place, int bit_depth, int C, bool with_icrf) {
+    if (place == WELFORD_U16_LDS) return welford_u16_table_fits_lds(bit_depth, C, with_icrf);
+    if (place == WELFORD_U16_COMPUTED) return !with_icrf;
+    return place == WELFORD_U16_GLOBAL && with_icrf;
+}
+// variant = 0: the first placement that applies, in the order LDS, computed, global - LDS where the table fits, else the computed
+// quotient (no ICRF) or global memory (ICRF). Measurements: DESIGN.md 4.4.7.
+inline int welford_u16_default_placement(int bit_depth, int C, bool with_icrf) {
+    if (welford_u16_table_fits_lds(bit_depth, C, with_icrf)) return WELFORD_U16_LDS;
+    return with_icrf ? WELFORD_U16_GLOBAL : WELFORD_U16_COMPUTED;
+}
+
+// The statuses of hm_welford_update_u16 - hm_welford_update's in their order, with the u16 rules at the places marked +:
+//   1. HM_EINVAL        n_frames outside 0..HM_MAX_FRAMES, a negative count_before or n_elems, + bit_depth outside 9..16, + variant outside 0..3
+//   2. HM_EUNSUPPORTED  count_before beyond kWelfordMaxCount
+//   3. HM_ESHAPE        C outside 1..HM_MAX_CHANNELS;  4. HM_ESHAPE  n_elems no multiple of C
+//   5. HM_OK, empty     no frames or no elements: nothing to do, no pointer has been looked at
+//   6. HM_EUNSUPPORTED  + a forced variant that does not exist for the call or whose table does not fit (welford_u16_placement_applies)
+//   7. HM_EINVAL        NULL frames, mean or frames[k]
+//   8. HM_EALIGN        + a frame that is not 2-byte aligned
+// rules 1-6, which look at no pointer: what hm_welford_update_u16_describe checks
+inline int check_welford_update_u16_counts(int n_frames, int64_t count_before, int64_t n_elems, int C, bool with_icrf, int bit_depth, int variant,
+                                           bool& empty) {
+    empty = false;
+    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || count_before < 0 || n_elems < 0 || bit_depth < 9 || bit_depth > 16 || variant < 0 ||
+        variant > WELFORD_U16_GLOBAL)
+        return HM_EINVAL;
+    if (count_before > kWelfordMaxCount) return HM_EUNSUPPORTED;
+    if (C < 1 || C > HM_MAX_CHANNELS) return HM_ESHAPE;
+    if (n_elems % C != 0) return HM_ESHAPE;
+    if (n_frames == 0 || n_elems == 0) { empty = true; return HM_OK; }
+    if (variant != WELFORD_U16_AUTO && !welford_u16_placement_applies(variant, bit_depth, C, with_icrf)) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+inline int check_welford_update_u16(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, const double* mean,
+                                    int64_t n_elems, int C, int bit_depth, int variant, bool& empty) {
+    const int rc = check_welford_update_u16_counts(n_frames, count_before, n_elems, C, icrf != nullptr, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    if (!frames || !mean) return HM_EINVAL;
+    for (int k = 0; k < n_frames; ++k)
+        if (!frames[k]) return HM_EINVAL;
+    for (int k = 0; k < n_frames; ++k)
+        if (reinterpret_cast<uintptr_t>(frames[k]) & 1) return HM_EALIGN;
+    return HM_OK;
+}
+
+// hm_welford_finalize_u16: hm_welford_finalize's statuses in their order, + bit_depth outside 9..16 with the first (HM_EINVAL),
+// + an output frame that is not 2-byte aligned last (HM_EALIGN)
+inline int check_welford_finalize_u16(const double* mean, const double* m2, int64_t count, int bit_depth, const uint16_t* out_mean,
+                                      const uint16_t* out_std, int64_t n_elems, bool& empty) {
+    empty = false;
+    if (n_elems < 0 || count < 1 || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
+    if (n_elems == 0) { empty = true; return HM_OK; }
+    if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
+    if (out_std && count < 2) return HM_EINVAL;                               // m2 / (n - 1) needs two frames
+    if ((reinterpret_cast<uintptr_t>(out_mean) | reinterpret_cast<uintptr_t>(out_std)) & 1) return HM_EALIGN;
     return HM_OK;
 }
 

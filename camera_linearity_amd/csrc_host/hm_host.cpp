@@ -1020,6 +1020,62 @@ int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uin
 }
 int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) { return n_elems * (static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16)); }
 
+// ... on uint16 frames of 9 to 16 bits: f = icrf[DN & M, c] or (DN & M) / M, M = 2^bit_depth - 1. `variant` places the table on the
+// device; here it is only checked.
+int hm_welford_update_u16(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
+                          int64_t n_elems, int C, int bit_depth, int variant, void*) {
+    bool empty;
+    const int rc = hm_rules::check_welford_update_u16(frames, n_frames, count_before, icrf, mean, n_elems, C, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    const int mask = (1 << bit_depth) - 1;
+    const double max_dn = static_cast<double>(mask);
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < n_elems; ++e) {
+        const int c = static_cast<int>(e % C);
+        double m = mean[e], q = m2 ? m2[e] : 0.0, cnt = static_cast<double>(count_before);
+        for (int k = 0; k < n_frames; ++k) {
+            cnt += 1.0;
+            const int dn = static_cast<const uint16_t*>(frames[k])[e] & mask;
+            const double f = icrf ? icrf[dn * C + c] : static_cast<double>(dn) / max_dn;
+            const double delta = f - m;
+            m = m + delta / cnt;
+            q = q + delta * (f - m);
+        }
+        mean[e] = m;
+        if (m2) m2[e] = q;
+    }
+    return HM_OK;
+}
+
+int hm_welford_update_u16_describe(int64_t n_elems, int n_frames, int C, int with_icrf, int with_m2, int bit_depth, int variant, char* buf,
+                                   int buf_len) {
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    buf[0] = '\0';
+    bool empty;
+    const int rc = hm_rules::check_welford_update_u16_counts(n_frames, 0, n_elems, C, with_icrf != 0, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "host_welford<dn=u16,m2=%d,icrf=%d,bits=%d>", with_m2 != 0, with_icrf != 0, bit_depth);
+    return HM_OK;
+}
+
+int hm_welford_finalize_u16(const double* mean, const double* m2, int64_t count, int bit_depth, uint16_t* out_mean, uint16_t* out_std,
+                            int64_t n_elems, void*) {
+    bool empty;
+    const int rc = hm_rules::check_welford_finalize_u16(mean, m2, count, bit_depth, out_mean, out_std, n_elems, empty);
+    if (rc != HM_OK || empty) return rc;
+    const double denom = static_cast<double>(count) - 1.0, root_n = std::sqrt(static_cast<double>(count));
+    const double max_dn = static_cast<double>((1 << bit_depth) - 1);
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < n_elems; ++e) {
+        if (out_mean) out_mean[e] = round_to_u16(mean[e] * max_dn);
+        if (out_std) out_std[e] = round_to_u16(std::sqrt(m2[e] / denom) / root_n);    // as written: not rescaled
+    }
+    return HM_OK;
+}
+int64_t hm_welford_u16_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) {
+    return n_elems * (2 * static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16));
+}
+
 // compute_noise_profiles, modules/video_processing.py:77-106: profile[m, f, c] += 1 for every frame and element (np.add.at).
 // Per thread a private (256, 256, C) count over its elements, added into the profile at the end: exact, any thread count.
 size_t hm_noise_profile_workspace_bytes(int64_t, int) { return 0; }

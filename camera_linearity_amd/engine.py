@@ -1189,10 +1189,25 @@ def kernel_density_estimate(val: torch.Tensor, std: Optional[torch.Tensor], data
 # ------------------------------------------------------------------------------------------------
 # upstream producer: Welford mean / M2 over video frames (modules/video_processing.py:161-219)
 # ------------------------------------------------------------------------------------------------
+def _welford_bit_depth(dtype, bit_depth):
+    """None for uint8 frames; the checked depth for torch.uint16 ones (which need one). A depth with any other dtype is refused."""
+    if dtype == _U16:
+        if bit_depth is None:
+            raise ValueError("torch.uint16 frames need bit_depth (9..16): the camera's DN range")
+        return _check_bit_depth(bit_depth)
+    if bit_depth is not None:
+        raise ValueError(f"bit_depth is for torch.uint16 frames, got {dtype}")
+    return None
+
+
 def welford_update(frames: Sequence[torch.Tensor], count_before: int, mean: torch.Tensor, m2: Optional[torch.Tensor],
-                   icrf=None) -> int:
+                   icrf=None, bit_depth: Optional[int] = None, variant: int = 0) -> int:
     """Fold `frames` (uint8 (H, W, C) device tensors, in order) into the running float64 mean / m2 in place
-    (video_processing.py:199-208). Returns the new frame count. Frames are folded HM_MAX_FRAMES per launch."""
+    (video_processing.py:199-208). Returns the new frame count. Frames are folded HM_MAX_FRAMES per launch.
+    torch.uint16 frames need `bit_depth` in 9..16 (hm_welford_update_u16): an ICRF of 2**bit_depth rows, a DN's index
+    DN & (2**bit_depth - 1), DN / (2**bit_depth - 1) without an ICRF. `variant` says where the device kernel takes a frame value from
+    (0: the library's choice, 1: a table in LDS, 2: computed, without an ICRF only, 3: the ICRF in global memory); the result does not
+    depend on it."""
     _require_cuda(mean, "mean")
     if mean.dtype != _F64 or not mean.is_contiguous():
         raise TypeError("mean must be a contiguous float64 tensor")
@@ -1200,33 +1215,56 @@ def welford_update(frames: Sequence[torch.Tensor], count_before: int, mean: torc
         raise TypeError("m2 must be a contiguous float64 tensor shaped like mean")
     dev = mean.device
     Cc = mean.shape[-1]
-    lut = None if icrf is None else _dev_f64(icrf, dev)
-    if lut is not None and tuple(lut.shape) != (BITS, Cc):
-        raise ValueError(f"ICRF must be shaped ({BITS}, {Cc})")
-    count = int(count_before)
     frames = list(frames)
+    first = frames[0].dtype if frames and isinstance(frames[0], torch.Tensor) else _U16 if bit_depth is not None else _U8
+    bit_depth = _welford_bit_depth(first, bit_depth)
+    rows, dn_dtype = (BITS, _U8) if bit_depth is None else (2 ** bit_depth, _U16)
+    lut = None if icrf is None else _dev_f64(icrf, dev)
+    if lut is not None and tuple(lut.shape) != (rows, Cc):
+        raise ValueError(f"ICRF must be shaped ({rows}, {Cc})")
+    count = int(count_before)
     for f in frames:
         _require_cuda(f, "frame")
-        if f.dtype != torch.uint8 or f.shape != mean.shape:
-            raise ValueError("every frame must be a uint8 tensor shaped like mean")
+        if f.dtype != dn_dtype or f.shape != mean.shape:
+            raise ValueError(f"every frame must be a {str(dn_dtype).replace('torch.', '')} tensor shaped like mean")
     with _on(dev):
         for k0 in range(0, len(frames), nat.HM_MAX_FRAMES):
             batch = [f.contiguous() for f in frames[k0:k0 + nat.HM_MAX_FRAMES]]
-            nat.check(nat.lib.hm_welford_update(_ptr_array(batch), len(batch), count, nat.ptr(lut), mean.data_ptr(), nat.ptr(m2),
-                                                mean.numel(), Cc, _stream(dev)), "hm_welford_update")
+            head = (_ptr_array(batch), len(batch), count, nat.ptr(lut), mean.data_ptr(), nat.ptr(m2), mean.numel(), Cc)
+            if bit_depth is None:
+                nat.check(nat.lib.hm_welford_update(*head, _stream(dev)), "hm_welford_update")
+            else:
+                nat.check(nat.lib.hm_welford_update_u16(*head, bit_depth, int(variant), _stream(dev)), "hm_welford_update_u16")
             count += len(batch)
     return count
 
 
-def welford_finalize(mean: torch.Tensor, m2: Optional[torch.Tensor], count: int):
-    """-> (mean frame uint8, std frame uint8 or None), video_processing.py:210-215."""
+def welford_finalize(mean: torch.Tensor, m2: Optional[torch.Tensor], count: int, bit_depth: Optional[int] = None):
+    """-> (mean frame uint8, std frame uint8 or None), video_processing.py:210-215. With `bit_depth` (9..16) the frames are torch.uint16
+    and the mean is scaled by 2**bit_depth - 1 (hm_welford_finalize_u16)."""
     _require_cuda(mean, "mean")
-    out_mean = torch.empty(mean.shape, dtype=torch.uint8, device=mean.device)
-    out_std = None if m2 is None else torch.empty(mean.shape, dtype=torch.uint8, device=mean.device)
+    if bit_depth is not None:
+        bit_depth = _check_bit_depth(bit_depth)
+    dtype = _U8 if bit_depth is None else _U16
+    out_mean = torch.empty(mean.shape, dtype=dtype, device=mean.device)
+    out_std = None if m2 is None else torch.empty(mean.shape, dtype=dtype, device=mean.device)
     with _on(mean.device):
-        nat.check(nat.lib.hm_welford_finalize(mean.data_ptr(), nat.ptr(m2), int(count), out_mean.data_ptr(), nat.ptr(out_std),
-                                              mean.numel(), _stream(mean.device)), "hm_welford_finalize")
+        if bit_depth is None:
+            nat.check(nat.lib.hm_welford_finalize(mean.data_ptr(), nat.ptr(m2), int(count), out_mean.data_ptr(), nat.ptr(out_std),
+                                                  mean.numel(), _stream(mean.device)), "hm_welford_finalize")
+        else:
+            nat.check(nat.lib.hm_welford_finalize_u16(mean.data_ptr(), nat.ptr(m2), int(count), bit_depth, out_mean.data_ptr(), nat.ptr(out_std),
+                                                      mean.numel(), _stream(mean.device)), "hm_welford_finalize_u16")
     return out_mean, out_std
+
+
+def welford_kernel(n_elems: int, n_frames: int, channels: int, with_icrf: bool, with_m2: bool, bit_depth: int, variant: int = 0) -> str:
+    """The kernel welford_update(..., bit_depth=bit_depth, variant=variant) starts on such a call, as hm_welford_update_u16_describe names
+    it (e.g. "k_welford_u16<m2=1,tab=lds,bits=12>"); nothing is launched. For tests and benchmarks."""
+    buf = C.create_string_buffer(128)
+    nat.check(nat.lib.hm_welford_update_u16_describe(int(n_elems), int(n_frames), int(channels), int(bool(with_icrf)), int(bool(with_m2)),
+                                                     int(bit_depth), int(variant), buf, len(buf)), "hm_welford_update_u16_describe")
+    return buf.value.decode()
 
 
 # ------------------------------------------------------------------------------------------------

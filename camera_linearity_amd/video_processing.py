@@ -1,5 +1,6 @@
 """Mean / STD frames of a video - mirror of modules/video_processing.py:161-262 on the HIP backend - and the camera
-noise profiles with the per-DN STD table computed from them (:12-133).
+noise profiles with the per-DN STD table computed from them (:12-133). The mean / STD frames are also available for the uint16 frames
+of 9- to 16-bit cameras (`bit_depth=`); the noise profiles stay 8-bit: their (2^b, 2^b, C) joint histogram does not scale to 16 bits.
 
 The reference streams frames out of `cv.VideoCapture` one at a time and updates three whole-image NumPy
 arrays per frame (video_processing.py:199-208). Here the decoded frames are uploaded in batches and folded
@@ -60,13 +61,18 @@ def frames_from_capture(capture) -> Iterator[np.ndarray]:
         capture.release()
 
 
-def _as_device_frame(frame, device) -> torch.Tensor:
+def _as_device_frame(frame, device, bit_depth=None) -> torch.Tensor:
+    """A decoded frame as a device tensor: uint8, or - with `bit_depth` (9..16) - the uint16 frame of such a camera."""
     if isinstance(frame, torch.Tensor):
         t = frame
     else:
         t = torch.from_numpy(np.ascontiguousarray(frame))
-    if t.dtype != torch.uint8:
-        raise TypeError(f"video frames must be uint8, got {t.dtype}")
+    if bit_depth is None:
+        if t.dtype != torch.uint8:
+            raise TypeError(f"video frames must be uint8, got {t.dtype}" + (
+                " (welford_algorithm takes uint16 frames with bit_depth=9..16)" if t.dtype == torch.uint16 else ""))
+    elif t.dtype != torch.uint16:
+        raise ValueError(f"bit_depth is for uint16 video frames, got {t.dtype}")
     if t.dim() == 2:
         t = t[..., None]
     if torch.device(device).type == "cpu":
@@ -76,7 +82,7 @@ def _as_device_frame(frame, device) -> torch.Tensor:
 
 def welford_algorithm(frame_sources: Union[Iterable, Sequence[Iterable]], ICRF: Optional[np.ndarray] = None,
                       use_std: Optional[bool] = False, device=None, frames_per_launch: int = FRAMES_PER_LAUNCH,
-                      as_numpy: bool = True):
+                      as_numpy: bool = True, bit_depth: Optional[int] = None):
     """Mean frame and standard-deviation-of-the-mean frame over all frames (video_processing.py:161-219).
 
     Args:
@@ -85,6 +91,8 @@ def welford_algorithm(frame_sources: Union[Iterable, Sequence[Iterable]], ICRF: 
         ICRF: (BITS, NUM_OF_CHS) float64 inverse camera response; frames are linearized on load when given.
         use_std: whether to compute the standard deviation frame.
         device: the GPU to compute on (default: the current one), or "cpu" for the host build (libhdrmerge_host.so).
+        bit_depth: 9..16 for the uint16 frames (NumPy or tensors) of such a camera: MAX_DN becomes 2**bit_depth - 1, the ICRF has
+            2**bit_depth rows, and the result frames are uint16 (hm_welford_update_u16 / hm_welford_finalize_u16).
     Returns:
         {'mean': uint8 (H, W, C), 'std': uint8 (H, W, C) or None} - NumPy arrays (or device tensors with as_numpy=False).
     """
@@ -92,6 +100,8 @@ def welford_algorithm(frame_sources: Union[Iterable, Sequence[Iterable]], ICRF: 
     eng = _engine_for(device)
     if frames_per_launch < 1:
         raise ValueError("frames_per_launch must be positive")
+    if bit_depth is not None:
+        bit_depth = engine._check_bit_depth(bit_depth)
     if isinstance(frame_sources, (list, tuple)) and frame_sources and not _looks_like_frame(frame_sources[0]):
         sources = list(frame_sources)
     else:
@@ -104,14 +114,14 @@ def welford_algorithm(frame_sources: Union[Iterable, Sequence[Iterable]], ICRF: 
     def flush():
         nonlocal count
         if pending:
-            count = eng.welford_update(pending, count, mean, m2, ICRF)
+            count = eng.welford_update(pending, count, mean, m2, ICRF, bit_depth=bit_depth)
             pending.clear()
 
     for source in sources:
         for frame in source:
             if frame is None:
                 break
-            t = _as_device_frame(frame, device)
+            t = _as_device_frame(frame, device, bit_depth)
             if mean is None:
                 mean = torch.zeros(t.shape, dtype=torch.float64, device=device)              # :181
                 m2 = torch.zeros(t.shape, dtype=torch.float64, device=device) if use_std else None   # :184
@@ -125,7 +135,7 @@ def welford_algorithm(frame_sources: Union[Iterable, Sequence[Iterable]], ICRF: 
         raise ValueError("no frames to process")
     if use_std and count < 2:
         raise ValueError("the standard deviation frame needs at least two frames")
-    out_mean, out_std = eng.welford_finalize(mean, m2, count)
+    out_mean, out_std = eng.welford_finalize(mean, m2, count, bit_depth=bit_depth)
     if as_numpy:
         return {"mean": out_mean.cpu().numpy(), "std": None if out_std is None else out_std.cpu().numpy()}
     return {"mean": out_mean, "std": out_std}
@@ -147,9 +157,10 @@ def save_result(ret: dict, video_path) -> None:
             tiff_io.imwrite(video_path.parent.joinpath(video_path.name.replace(".avi", f".{key}.tif")), img)
 
 
-def process_video(frame_source, video_path, ICRF: Optional[np.ndarray] = None, use_std: Optional[bool] = True):
-    """video_processing.py:222-236 for an already opened frame source."""
-    ret = welford_algorithm(frame_source, ICRF, use_std)
+def process_video(frame_source, video_path, ICRF: Optional[np.ndarray] = None, use_std: Optional[bool] = True,
+                  bit_depth: Optional[int] = None):
+    """video_processing.py:222-236 for an already opened frame source (`bit_depth`: welford_algorithm's; the TIFFs are then uint16)."""
+    ret = welford_algorithm(frame_source, ICRF, use_std, bit_depth=bit_depth)
     save_result(ret, video_path)
     return ret
 

@@ -530,6 +530,39 @@ int hm_welford_finalize(const double* mean, const double* m2 /*nullable*/, int64
                         uint8_t* out_mean /*nullable*/, uint8_t* out_std /*nullable*/, int64_t n_elems, void* stream);
 int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems);
 
+/* ... on uint16 frames of 9- to 16-bit cameras, M = 2^bit_depth - 1. Everything not named here is hm_welford_update's /
+ * hm_welford_finalize's: the layouts, the running-state convention, the operation sequence, no allocation, no host synchronisation.
+ *   frames     n_frames uint16 HWC frames, 2-byte aligned. A DN's value is f = icrf[DN & M, c] (icrf (2^bit_depth, C) float64) or, with a
+ *              NULL icrf, (DN & M) / M with the IEEE division; the mask is applied before every table access (hm_merge_u16's convention).
+ *              The device build folds two elements per lane when every frame is 4-byte aligned and mean / m2 are 16-byte aligned, and one
+ *              per lane otherwise: the same bits.
+ *   variant    where the device kernel takes f from - 0: the library's choice; 1: a table in LDS (the ICRF, 8 * 2^bit_depth * C bytes, or
+ *              without an ICRF the column DN / M, 8 * 2^bit_depth bytes); 2: computed in the lane, without an ICRF only; 3: gathered from
+ *              the ICRF in global memory, with an ICRF only. Fit rule: the LDS table may take 128 KiB - with an ICRF C = 1 up to 14 bits,
+ *              C = 2 up to 13, C = 3 and 4 up to 12; without one up to 14 bits. The library's choice is LDS where the table fits, else
+ *              2 (no ICRF) or 3 (ICRF). The placements give the same bits. The host build checks variant and ignores it.
+ *   Statuses of hm_welford_update_u16, an earlier one winning: HM_EINVAL for n_frames outside 0..HM_MAX_FRAMES, a negative count_before or
+ *   n_elems, bit_depth outside 9..16 or variant outside 0..3; HM_EUNSUPPORTED for count_before beyond 2^40; HM_ESHAPE for C outside
+ *   1..HM_MAX_CHANNELS, then for n_elems no multiple of C; n_frames == 0 or n_elems == 0 returns HM_OK with no pointer looked at;
+ *   HM_EUNSUPPORTED for a forced variant that does not exist for the call or whose table does not fit; HM_EINVAL for NULL frames, mean or
+ *   frames[k]; HM_EALIGN for a frame that is not 2-byte aligned.
+ *   hm_welford_finalize_u16   out_mean = around(mean * M) as uint16; out_std = around(sqrt(m2 / (count - 1)) / sqrt(count)) as uint16 (as
+ *              written: not rescaled); both nullable. Rounding as np.around(x).astype(uint16) where that is defined; NaN and |x| >= 9.2e18
+ *              give 0, anything else the low 16 bits of the rounded 64-bit integer. hm_welford_finalize's statuses, bit_depth outside
+ *              9..16 with the first (HM_EINVAL), and last HM_EALIGN for an output that is not 2-byte aligned.
+ *   hm_welford_u16_algorithmic_bytes   n_elems * (2 * n_frames + 16 or 32).
+ *   hm_welford_update_u16_describe writes the name of the kernel such a call would launch, e.g. "k_welford_u16<m2=1,tab=lds,bits=12>"
+ *   (tab = lds, computed or global; the host build: a host name), and launches nothing; hm_welford_update_u16's statuses up to the
+ *   second HM_EUNSUPPORTED, an empty name where there is nothing to do, HM_EINVAL for a NULL or empty buf. */
+int hm_welford_update_u16(const void* const* frames /*[host] n_frames device ptrs*/, int n_frames, int64_t count_before,
+                          const double* icrf /*nullable, (2^bit_depth, C)*/, double* mean, double* m2 /*nullable*/,
+                          int64_t n_elems, int C, int bit_depth, int variant, void* stream);
+int hm_welford_finalize_u16(const double* mean, const double* m2 /*nullable*/, int64_t count, int bit_depth,
+                            uint16_t* out_mean /*nullable*/, uint16_t* out_std /*nullable*/, int64_t n_elems, void* stream);
+int64_t hm_welford_u16_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems);
+int hm_welford_update_u16_describe(int64_t n_elems, int n_frames, int C, int with_icrf, int with_m2, int bit_depth, int variant,
+                                   char* buf, int buf_len);
+
 /* ------------------------------------------------------------------------------------------
  * Camera noise profiles and the per-DN STD table: compute_noise_profiles, _calculate_STD and clean_data_edges,
  * modules/video_processing.py:12-133 (the input of ImageSet.calculate_numerical_STD, modules/image_set.py).

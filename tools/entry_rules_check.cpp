@@ -45,7 +45,18 @@ void producers() {
         expect("noise", check_noise_profile_update(frames.data(), n, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_OK);
         expect("noise, too many frames",
                check_noise_profile_update(frames.data(), HM_MAX_FRAMES + 1, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_EINVAL);
+        expect("welford u16", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 12, 0, empty), HM_OK);
+        expect("welford u16, too many frames", check_welford_update_u16(frames.data(), HM_MAX_FRAMES + 1, 0, nullptr, mean, 12, 3, 12, 0, empty), HM_EINVAL);
+        expect("welford u16, 17 bits", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 17, 0, empty), HM_EINVAL);
+        expect("welford u16, global without a table", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 12, WELFORD_U16_GLOBAL, empty), HM_EUNSUPPORTED);
+        expect("welford u16, computed with a table", check_welford_update_u16(frames.data(), n, 0, mean, mean, 12, 3, 12, WELFORD_U16_COMPUTED, empty), HM_EUNSUPPORTED);
+        expect("welford u16, LDS at 16 bits", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 16, WELFORD_U16_LDS, empty), HM_EUNSUPPORTED);
+        expect("welford u16, LDS, C = 3 at 13 bits", check_welford_update_u16(frames.data(), n, 0, mean, mean, 12, 3, 13, WELFORD_U16_LDS, empty), HM_EUNSUPPORTED);
+        expect("welford u16, LDS, C = 3 at 12 bits", check_welford_update_u16(frames.data(), n, 0, mean, mean, 12, 3, 12, WELFORD_U16_LDS, empty), HM_OK);
+        frames[n - 1] = fake<void>(0x2001);
+        expect("welford u16, last frame odd", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 12, 0, empty), HM_EALIGN);
         frames[n - 1] = nullptr;
+        expect("welford u16, last frame NULL", check_welford_update_u16(frames.data(), n, 0, nullptr, mean, 12, 3, 12, 0, empty), HM_EINVAL);
         expect("welford, last frame NULL", check_welford_update(frames.data(), n, 0, mean, 12, 3, empty), HM_EINVAL);
         expect("noise, last frame NULL", check_noise_profile_update(frames.data(), n, fake<uint8_t>(0x3000), 12, 3, fake<int64_t>(0x4000), 0, empty), HM_EINVAL);
     }
@@ -58,6 +69,21 @@ void producers() {
     expect("finalize", check_welford_finalize(mean, mean, 2, fake<uint8_t>(0x5000), fake<uint8_t>(0x6000), 12, empty), HM_OK);
     expect("finalize, all NULL", check_welford_finalize(nullptr, nullptr, 1, nullptr, nullptr, 12, empty), HM_OK);
     expect("finalize, one frame", check_welford_finalize(mean, mean, 1, nullptr, fake<uint8_t>(0x6000), 12, empty), HM_EINVAL);
+    expect("welford u16, no frames", check_welford_update_u16(nullptr, 0, 0, nullptr, nullptr, 12, 3, 12, WELFORD_U16_GLOBAL, empty), HM_OK);
+    expect("welford u16, no frames: empty", empty, 1);
+    expect("welford u16, frames NULL", check_welford_update_u16(nullptr, 2, 0, nullptr, mean, 12, 3, 12, 0, empty), HM_EINVAL);
+    for (int bits = 9; bits <= 16; ++bits)
+        for (int C = 1; C <= HM_MAX_CHANNELS; ++C) {
+            expect("welford u16, fit rule with a table", welford_u16_table_fits_lds(bits, C, true), bits <= (C == 1 ? 14 : C == 2 ? 13 : 12));
+            expect("welford u16, fit rule without one", welford_u16_table_fits_lds(bits, C, false), bits <= 14);
+            for (bool with_icrf : {false, true})
+                expect("welford u16, the default applies", welford_u16_placement_applies(welford_u16_default_placement(bits, C, with_icrf), bits, C, with_icrf), 1);
+        }
+    expect("finalize u16", check_welford_finalize_u16(mean, mean, 2, 12, fake<uint16_t>(0x5000), fake<uint16_t>(0x6000), 12, empty), HM_OK);
+    expect("finalize u16, all NULL", check_welford_finalize_u16(nullptr, nullptr, 1, 12, nullptr, nullptr, 12, empty), HM_OK);
+    expect("finalize u16, 8 bits", check_welford_finalize_u16(mean, mean, 2, 8, fake<uint16_t>(0x5000), fake<uint16_t>(0x6000), 12, empty), HM_EINVAL);
+    expect("finalize u16, one frame", check_welford_finalize_u16(mean, mean, 1, 12, nullptr, fake<uint16_t>(0x6000), 12, empty), HM_EINVAL);
+    expect("finalize u16, odd output", check_welford_finalize_u16(mean, mean, 2, 12, fake<uint16_t>(0x5001), nullptr, 12, empty), HM_EALIGN);
     expect("noise std, NULL", check_noise_profile_std(nullptr, 3, nullptr, nullptr), HM_EINVAL);
     expect("noise std, 5 channels", check_noise_profile_std(fake<int64_t>(0x4000), 5, mean, mean), HM_EUNSUPPORTED);
     expect("clean edges, NULL", check_noise_profile_clean_edges(nullptr, 3), HM_EINVAL);

@@ -608,6 +608,55 @@ def case_welford(rng):
     return desc
 
 
+def case_welford_u16(rng):
+    """hm_welford_update_u16 / hm_welford_finalize_u16: case_welford on uint16 frames of 9 to 16 bits with stray bits above the depth, every
+    placement of the frame value that applies (LDS where the table fits, computed without an ICRF, global memory with one), odd sizes,
+    frames and state at unaligned views (2-byte / 8-byte aligned only: the scalar path), count_before > 0 - bit-exact against the host build."""
+    depth = int(rng.integers(9, 17))
+    n_dn = 2 ** depth
+    c = int(rng.choice([1, 2, 3, 3, 4]))
+    h, w = int(rng.integers(1, 30 * args.scale)), int(rng.integers(1, 40 * args.scale))
+    n = int(rng.integers(1, 80))
+    use_m2 = rng.random() < 0.7
+    use_icrf = rng.random() < 0.5
+    fits = 8 * n_dn * (c if use_icrf else 1) <= 128 * 1024
+    variant = int(rng.choice([0] + ([1] if fits else []) + ([3] if use_icrf else [2])))
+    g = None
+    if use_icrf:
+        g = np.cumsum(rng.random((n_dn, c)) + 1e-3, axis=0)
+        g = (g - g[0]) / (g[-1] - g[0])
+    frames = rng.integers(0, n_dn, (n, h, w, c))
+    frames = (frames | (rng.integers(0, 2 ** (16 - depth), frames.shape) << depth)).astype(np.uint16)   # stray high bits: masked by both builds
+    splits = sorted(set(int(q) for q in rng.integers(1, n + 1, size=int(rng.integers(0, 3))))) + [n]
+    off_frames, off_state = rng.random() < 0.4, rng.random() < 0.4
+    count0 = int(rng.choice([0, 0, 5, 1000]))
+    e = h * w * c
+    mean0, m2_0 = rng.random(e) if count0 else np.zeros(e), rng.random(e) if count0 else np.zeros(e)
+    desc = (f"welford_u16 bits={depth} n={n} {h}x{w}x{c} m2={use_m2} icrf={use_icrf} variant={variant} launches at {splits} "
+            f"count0={count0} unaligned frames={off_frames} state={off_state}")
+    out = []
+    for eng_, dv in ((engine, dev), (heng, torch.device("cpu"))):
+        def state(a):
+            buf = torch.zeros(e + 2, dtype=torch.float64, device=dv)
+            buf[int(off_state):int(off_state) + e] = torch.from_numpy(a).to(dv)
+            return buf[int(off_state):int(off_state) + e].view(h, w, c)
+
+        def frame(f):
+            buf = torch.zeros(e + 2, dtype=torch.int16, device=dv)
+            buf[int(off_frames):int(off_frames) + e] = torch.from_numpy(f.view(np.int16).reshape(-1).copy()).to(dv)
+            return buf.view(torch.uint16)[int(off_frames):int(off_frames) + e].view(h, w, c)
+        mean, m2 = state(mean0), state(m2_0) if use_m2 else None
+        count, k0 = count0, 0
+        for k1 in splits:
+            count = eng_.welford_update([frame(f) for f in frames[k0:k1]], count, mean, m2, g, bit_depth=depth, variant=variant)
+            k0 = k1
+        fm, fs = eng_.welford_finalize(mean, m2 if count >= 2 else None, count, bit_depth=depth)
+        out.append((mean, m2, fm, fs))
+    for nm, a, b in zip(("mean", "m2", "mean_u16", "std_u16"), *out):
+        compare(nm, a, b, None)
+    return desc
+
+
 def case_energy(rng):
     """hm_linearity_energy: a population of candidate ICRFs (some rejected) on one channel's (X, Y, N) stack; energies and per-pair results
     to 1e-11 (the device's register kernel multiplies by reciprocals; sums run in another order), NaN / inf patterns equal."""
@@ -1004,7 +1053,7 @@ def case_linearize_u16(rng):
 
 
 CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
     assert CASES, f"--only {args.only}: no such generator"
