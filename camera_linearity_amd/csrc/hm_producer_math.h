@@ -1,6 +1,7 @@
 // hm_producer_math.h - the element formulas of the upstream producers, one text for the device units (hm_welford.hip, hm_welford_u16.hip,
-// hm_noise.hip, hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 / uint16 rounding of the Welford result, the edge cleaning of one noise-profile row, and the
-// counter-based uniform draws of the differential evolution.
+// hm_noise.hip, hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 / uint16 rounding of the Welford result (round_to_dn picks by output type:
+// the finalize text of both depths calls it), the edge cleaning of one noise-profile row, and the counter-based uniform draws of the
+// differential evolution. Not the Welford fold: as a shared function it moved the device kernels (hm_welford_fold_body.h).
 //
 // DEVICE / HOST - the builds perform the same operations here.
 #pragma once
@@ -23,6 +24,13 @@ HM_MATH_FN uint16_t round_to_u16(double x) {
     if (!(r == r)) return 0;
     if (r >= 9.2e18 || r <= -9.2e18) return 0;
     return static_cast<uint16_t>(static_cast<uint64_t>(static_cast<int64_t>(r)) & 65535u);
+}
+
+// the one of the two for a DN of type Out (uint8_t, uint16_t): the Welford finalize of both depths is one text
+template <typename Out>
+HM_MATH_FN Out round_to_dn(double x) {
+    if constexpr (sizeof(Out) == 1) return round_to_u8(x);
+    else return round_to_u16(x);
 }
 
 // Python's x // 2 on a 64-bit integer

@@ -22,21 +22,41 @@ namespace hm_rules {
 
 constexpr int64_t kWelfordMaxCount = int64_t{1} << 40;       // the device build's division by the count assumes n << 2^53
 
-inline int check_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* mean, int64_t n_elems, int C,
-                                bool& empty) {
+// ---- the Welford entries: the statuses the uint8 and the uint16 entries share, written once ----------------------------------------
+// hm_welford_update and hm_welford_update_u16 in their order, the uint16 entry's own rules at the places marked +:
+//   1. HM_EINVAL        n_frames outside 0..HM_MAX_FRAMES, a negative count_before or n_elems, + bit_depth outside 9..16, + variant outside 0..3
+//   2. HM_EUNSUPPORTED  count_before beyond kWelfordMaxCount
+//   3. HM_ESHAPE        C outside 1..HM_MAX_CHANNELS;  4. HM_ESHAPE  n_elems no multiple of C
+//   5. HM_OK, empty     no frames or no elements: nothing to do, no pointer has been looked at
+//   6. HM_EUNSUPPORTED  + a forced variant that does not exist for the call or whose table does not fit (welford_u16_placement_applies)
+//   7. HM_EINVAL        NULL frames, mean or frames[k]
+//   8. HM_EALIGN        + a frame that is not 2-byte aligned
+// rules 1-5 (the uint16 entry looks at its part of rule 1 before it calls this: the status is the same)
+inline int welford_update_counts(int n_frames, int64_t count_before, int64_t n_elems, int C, bool& empty) {
     empty = false;
     if (n_frames < 0 || n_frames > HM_MAX_FRAMES || count_before < 0 || n_elems < 0) return HM_EINVAL;
     if (count_before > kWelfordMaxCount) return HM_EUNSUPPORTED;
     if (C < 1 || C > HM_MAX_CHANNELS) return HM_ESHAPE;
     if (n_elems % C != 0) return HM_ESHAPE;
-    if (n_frames == 0 || n_elems == 0) { empty = true; return HM_OK; }
+    if (n_frames == 0 || n_elems == 0) empty = true;
+    return HM_OK;
+}
+inline int welford_update_pointers(const void* const* frames, int n_frames, const double* mean) {      // rule 7
     if (!frames || !mean) return HM_EINVAL;
     for (int k = 0; k < n_frames; ++k)
         if (!frames[k]) return HM_EINVAL;
     return HM_OK;
 }
 
-inline int check_welford_finalize(const double* mean, const double* m2, int64_t count, const uint8_t* out_mean, const uint8_t* out_std,
+inline int check_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* mean, int64_t n_elems, int C,
+                                bool& empty) {
+    const int rc = welford_update_counts(n_frames, count_before, n_elems, C, empty);
+    if (rc != HM_OK || empty) return rc;
+    return welford_update_pointers(frames, n_frames, mean);
+}
+
+// hm_welford_finalize, and hm_welford_finalize_u16 between its own two rules (check_welford_finalize_u16)
+inline int check_welford_finalize(const double* mean, const double* m2, int64_t count, const void* out_mean, const void* out_std,
                                   int64_t n_elems, bool& empty) {
     empty = false;
     if (n_elems < 0 || count < 1) return HM_EINVAL;
@@ -44,6 +64,11 @@ inline int check_welford_finalize(const double* mean, const double* m2, int64_t 
     if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
     if (out_std && count < 2) return HM_EINVAL;                               // m2 / (n - 1) needs two frames
     return HM_OK;
+}
+
+// frames of `bytes_per_dn`-byte DNs read once, the float64 state (mean, and m2 if present) read and written once
+inline int64_t welford_algorithmic_bytes(int bytes_per_dn, int n_frames, bool with_m2, int64_t n_elems) {
+    return n_elems * (static_cast<int64_t>(bytes_per_dn) * n_frames + (with_m2 ? 32 : 16));
 }
 
 // ---- hm_welford_update_u16 / hm_welford_finalize_u16: uint16 frames of bit_depth 9..16 ----------------------------------------------
@@ -73,50 +98,36 @@ inline int welford_u16_default_placement(int bit_depth, int C, bool with_icrf) {
     return with_icrf ? WELFORD_U16_GLOBAL : WELFORD_U16_COMPUTED;
 }
 
-// The statuses of hm_welford_update_u16 - hm_welford_update's in their order, with the u16 rules at the places marked +:
-//   1. HM_EINVAL        n_frames outside 0..HM_MAX_FRAMES, a negative count_before or n_elems, + bit_depth outside 9..16, + variant outside 0..3
-//   2. HM_EUNSUPPORTED  count_before beyond kWelfordMaxCount
-//   3. HM_ESHAPE        C outside 1..HM_MAX_CHANNELS;  4. HM_ESHAPE  n_elems no multiple of C
-//   5. HM_OK, empty     no frames or no elements: nothing to do, no pointer has been looked at
-//   6. HM_EUNSUPPORTED  + a forced variant that does not exist for the call or whose table does not fit (welford_u16_placement_applies)
-//   7. HM_EINVAL        NULL frames, mean or frames[k]
-//   8. HM_EALIGN        + a frame that is not 2-byte aligned
-// rules 1-6, which look at no pointer: what hm_welford_update_u16_describe checks
+// rules 1-6 of the list above, which look at no pointer: what hm_welford_update_u16_describe checks
 inline int check_welford_update_u16_counts(int n_frames, int64_t count_before, int64_t n_elems, int C, bool with_icrf, int bit_depth, int variant,
                                            bool& empty) {
     empty = false;
-    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || count_before < 0 || n_elems < 0 || bit_depth < 9 || bit_depth > 16 || variant < 0 ||
-        variant > WELFORD_U16_GLOBAL)
-        return HM_EINVAL;
-    if (count_before > kWelfordMaxCount) return HM_EUNSUPPORTED;
-    if (C < 1 || C > HM_MAX_CHANNELS) return HM_ESHAPE;
-    if (n_elems % C != 0) return HM_ESHAPE;
-    if (n_frames == 0 || n_elems == 0) { empty = true; return HM_OK; }
+    if (bit_depth < 9 || bit_depth > 16 || variant < 0 || variant > WELFORD_U16_GLOBAL) return HM_EINVAL;
+    const int rc = welford_update_counts(n_frames, count_before, n_elems, C, empty);
+    if (rc != HM_OK || empty) return rc;
     if (variant != WELFORD_U16_AUTO && !welford_u16_placement_applies(variant, bit_depth, C, with_icrf)) return HM_EUNSUPPORTED;
     return HM_OK;
 }
 
 inline int check_welford_update_u16(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, const double* mean,
                                     int64_t n_elems, int C, int bit_depth, int variant, bool& empty) {
-    const int rc = check_welford_update_u16_counts(n_frames, count_before, n_elems, C, icrf != nullptr, bit_depth, variant, empty);
+    int rc = check_welford_update_u16_counts(n_frames, count_before, n_elems, C, icrf != nullptr, bit_depth, variant, empty);
     if (rc != HM_OK || empty) return rc;
-    if (!frames || !mean) return HM_EINVAL;
-    for (int k = 0; k < n_frames; ++k)
-        if (!frames[k]) return HM_EINVAL;
+    rc = welford_update_pointers(frames, n_frames, mean);
+    if (rc != HM_OK) return rc;
     for (int k = 0; k < n_frames; ++k)
         if (reinterpret_cast<uintptr_t>(frames[k]) & 1) return HM_EALIGN;
     return HM_OK;
 }
 
-// hm_welford_finalize_u16: hm_welford_finalize's statuses in their order, + bit_depth outside 9..16 with the first (HM_EINVAL),
-// + an output frame that is not 2-byte aligned last (HM_EALIGN)
+// hm_welford_finalize's statuses in their order, + bit_depth outside 9..16 with the first (HM_EINVAL), + an output frame that is not 2-byte
+// aligned last (HM_EALIGN)
 inline int check_welford_finalize_u16(const double* mean, const double* m2, int64_t count, int bit_depth, const uint16_t* out_mean,
                                       const uint16_t* out_std, int64_t n_elems, bool& empty) {
     empty = false;
-    if (n_elems < 0 || count < 1 || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
-    if (n_elems == 0) { empty = true; return HM_OK; }
-    if ((out_mean && !mean) || (out_std && !m2)) return HM_EINVAL;
-    if (out_std && count < 2) return HM_EINVAL;                               // m2 / (n - 1) needs two frames
+    if (bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
+    const int rc = check_welford_finalize(mean, m2, count, out_mean, out_std, n_elems, empty);
+    if (rc != HM_OK || empty) return rc;
     if ((reinterpret_cast<uintptr_t>(out_mean) | reinterpret_cast<uintptr_t>(out_std)) & 1) return HM_EALIGN;
     return HM_OK;
 }

@@ -14,26 +14,13 @@
 // from a 256 x C table in LDS ({dn/255} or the ICRF), two elements per lane (one ushort load per frame, 16-byte
 // state accesses: every wave instruction covers whole 128-byte lines).
 //
-// delta / n must carry the bits of NumPy's IEEE division, but the divisor is the same for every element of a
-// frame, so the correctly rounded reciprocal r = RN(1 / n) comes from the host per frame and the quotient is
-//     q0 = RN(delta * r);   e = delta - q0 * n  (one FMA, exact);   q = RN(q0 + e * r)  (one FMA)
-// which is the correctly rounded delta / n whenever r = RN(1 / n) and nothing underflows (Markstein's final
-// division step; Brisebarre, Muller, Raina, IEEE TC 53(8) 2004, "division when the divisor is known in
-// advance"). 3 dependent ops instead of the ~14-instruction IEEE sequence (FP64 VALU: 4 cycles per wave op).
-// The range condition is checked, not assumed - once per element and launch, not per frame (round 4: the per-frame test was 2 of the 13.8
-// VALU instructions of an element-frame in a kernel that is FP64-VALU bound): the fast path needs every non-zero delta >= 2^-900.
-// With table entries that are 0 or in [2^-500, 2^500] (checked while the table is built), an incoming mean that is 0 or in
-// [2^-540, 2^500] (checked at load) and n <= 2^40 (checked on the host), every later mean is 0 or >= 2^-632 in magnitude:
-// m' = m (1 - 1/n) + f/n can lose 52 bits to ONE cancellation (two doubles >= 2^-541 differ by >= 2^-593 when they differ), after which
-// a non-zero f/n >= 2^-540 dwarfs it and a run of f = 0 shrinks it by n0/n >= 2^-40 at most - so a non-zero delta = f - m is >= 2^-684.
-// A lane whose state or table is outside those ranges (or not finite) redoes its elements with the full division (welford_exact).
-#include "hm_common.h"
-#include "hm_producer_math.h"
+// delta / n carries the bits of NumPy's IEEE division in three dependent FP64 operations inside a range that is checked once per element
+// and launch; a lane outside it redoes its elements with the full division (welford_exact). The argument and its predicates:
+// hm_welford_dev.h. The lane loop, the fast fold and the finalize loop are the *_body.h texts that hm_welford_u16.hip includes as well.
+#include "hm_welford_dev.h"
 #include "hm_producer_rules.h"
 
 namespace hm {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 struct WelfordK {
     const uint8_t* frame[HM_MAX_FRAMES];
@@ -46,8 +33,7 @@ struct WelfordK {
     double rcp[HM_MAX_FRAMES];   // RN(1 / (count0 + k + 1)), formed on the host
 };
 
-constexpr int kWelfordGroup = 8;             // frames whose loads / table gathers are issued together
-
+// The gathers and the exact redo keep their own text beside hm_welford_u16.hip's: every shared form tried moved a kernel.
 // reference arithmetic with the IEEE division for `count` consecutive elements, all frames (rare path and odd tail)
 template <bool M2>
 __device__ __forceinline__ void welford_exact(const WelfordK& a, const double* t, int64_t e0, int count, double* mean, double* m2) {
@@ -66,7 +52,7 @@ __device__ __forceinline__ void welford_exact(const WelfordK& a, const double* t
     }
 }
 
-// G frames starting at k0 for the lane's two elements (fast division: the caller has checked its range, see the file header)
+// G frames starting at k0 for the lane's two elements (fast division: the caller has checked its range, hm_welford_dev.h)
 template <bool M2, int G, bool VEC>
 __device__ __forceinline__ bool welford_group(const WelfordK& a, const double* t, int k0, int64_t e, uint32_t c0, uint32_t c1,
                                               double& cnt, double (&m)[2], double (&q)[2]) {
@@ -83,21 +69,8 @@ __device__ __forceinline__ bool welford_group(const WelfordK& a, const double* t
         f[k][0] = t[(raw[k] & 255u) + c0 * 256u];
         f[k][1] = t[(raw[k] >> 8) + c1 * 256u];
     }
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-        cnt += 1.0;
-        const double r = a.rcp[k0 + k];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const double delta = f[k][j] - m[j];                                  // :205
-            const double q0 = delta * r;
-            const double quot = fma(fma(-q0, cnt, delta), r, q0);                 // == delta / cnt
-            m[j] = m[j] + quot;                                                   // :206
-            if (M2) q[j] = q[j] + delta * (f[k][j] - m[j]);                       // :208
-        }
-    }
-    return ok;
+#define HM_WELFORD_TEST_GATHERED false
+#include "hm_welford_fold_body.h"
 }
 
 template <bool M2>
@@ -108,68 +81,22 @@ __global__ __launch_bounds__(256) void k_welford(const WelfordK a) {
     for (int i = threadIdx.x; i < 256 * C; i += blockDim.x) {           // t[c][dn]: the gather index is dn + 256 c, no multiply
         const double v = a.icrf ? a.icrf[i] : static_cast<double>(i / C) / 255.0;
         t[(i % C) * 256 + i / C] = v;
-        odd_table |= !(fabs(v) <= 0x1p500) || (v != 0.0 && fabs(v) < 0x1p-500);       // non-finite, huge or tiny entries
+        odd_table |= welford_entry_odd(v);
     }
     const bool table_ok = !__syncthreads_or(odd_table);
 
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const int64_t units = a.n / 2;
-    bool vec_ok = aligned_dev(a.mean, 16) && (!M2 || aligned_dev(a.m2, 16));
-    for (int k = 0; k < a.n_frames; ++k) vec_ok = vec_ok && aligned_dev(a.frame[k], 2);
-
-    for (int64_t u = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; u < units; u += stride) {
-        const int64_t e = 2 * u;
-        const uint32_t c0 = static_cast<uint32_t>(e % C), c1 = (c0 + 1u) % static_cast<uint32_t>(C);
-        double m[2], q[2] = {0.0, 0.0};
-        if (vec_ok) {
-            const f64x2 mv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(a.mean + e));
-            m[0] = mv.x; m[1] = mv.y;
-            if (M2) { const f64x2 qv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(a.m2 + e)); q[0] = qv.x; q[1] = qv.y; }
-        } else {
-            m[0] = a.mean[e]; m[1] = a.mean[e + 1];
-            if (M2) { q[0] = a.m2[e]; q[1] = a.m2[e + 1]; }
-        }
-        auto mean_ok = [](double x) { const double ax = fabs(x); return x == 0.0 || (ax >= 0x1p-540 && ax <= 0x1p500); };
-        bool ok = table_ok && mean_ok(m[0]) && mean_ok(m[1]) && fabs(q[0]) <= 0x1p900 && fabs(q[1]) <= 0x1p900;
-        double cnt = a.count0;
-        int k0 = 0;
-        if (vec_ok) {
-            for (; k0 + kWelfordGroup <= a.n_frames; k0 += kWelfordGroup)
-                ok = welford_group<M2, kWelfordGroup, true>(a, t, k0, e, c0, c1, cnt, m, q) && ok;
-            for (; k0 < a.n_frames; ++k0) ok = welford_group<M2, 1, true>(a, t, k0, e, c0, c1, cnt, m, q) && ok;
-        } else {
-            for (; k0 < a.n_frames; ++k0) ok = welford_group<M2, 1, false>(a, t, k0, e, c0, c1, cnt, m, q) && ok;
-        }
-        if (__builtin_expect(!ok, 0)) {                // the state in memory is still the launch's input
-            welford_exact<M2>(a, t, e, 2, m, q);
-        }
-        if (vec_ok) {
-            f64x2 mv; mv.x = m[0]; mv.y = m[1];
-            __builtin_nontemporal_store(mv, reinterpret_cast<f64x2*>(a.mean + e));
-            if (M2) { f64x2 qv; qv.x = q[0]; qv.y = q[1]; __builtin_nontemporal_store(qv, reinterpret_cast<f64x2*>(a.m2 + e)); }
-        } else {
-            a.mean[e] = m[0]; a.mean[e + 1] = m[1];
-            if (M2) { a.m2[e] = q[0]; a.m2[e + 1] = q[1]; }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (a.n & 1)) {
-        const int64_t e = a.n - 1;
-        double m[1], q[1];
-        welford_exact<M2>(a, t, e, 1, m, q);
-        a.mean[e] = m[0];
-        if (M2) a.m2[e] = q[0];
-    }
+#define HM_WELFORD_PAIR_ALIGN 2
+#define HM_WELFORD_OFFSET(c) (c)
+#define HM_WELFORD_GROUP(G, VEC) welford_group<M2, G, VEC>(a, t, k0, e, off0, off1, cnt, m, q)
+#define HM_WELFORD_EXACT(e0, count) welford_exact<M2>(a, t, e0, count, m, q)
+#include "hm_welford_lane_body.h"
 }
 
 __global__ __launch_bounds__(256) void k_welford_finalize(const double* __restrict__ mean, const double* __restrict__ m2,
                                                           double count, uint8_t* __restrict__ out_mean,
                                                           uint8_t* __restrict__ out_std, int64_t n) {
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double denom = count - 1.0, root_n = sqrt(count);
-    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
-        if (out_mean) out_mean[e] = round_to_u8(mean[e] * 255.0);                        // :210-211
-        if (out_std) out_std[e] = round_to_u8(sqrt(m2[e] / denom) / root_n);           // :214-215
-    }
+#define HM_WELFORD_SCALE 255.0
+#include "hm_welford_finalize_body.h"
 }
 
 }  // namespace hm
@@ -204,5 +131,5 @@ extern "C" int hm_welford_finalize(const double* mean, const double* m2, int64_t
 }
 
 extern "C" int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) {
-    return n_elems * (static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16));
+    return hm_rules::welford_algorithmic_bytes(1, n_frames, with_m2 != 0, n_elems);
 }

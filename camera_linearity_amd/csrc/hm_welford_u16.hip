@@ -1,16 +1,16 @@
 // hm_welford_u16.hip - hm_welford.hip's streaming per-pixel mean / M2 for 9- to 16-bit cameras (gfx950): uint16 HWC frames with an explicit
 // bit depth b, M = 2^b - 1 (hdrmerge.h: hm_welford_update_u16, hm_welford_finalize_u16). The arithmetic and its references are described
-// in hm_welford.hip; this unit keeps that kernel's decomposition and changes only where a frame value comes from:
+// in hm_welford.hip; this unit keeps that kernel's decomposition - the lane loop is the same text, hm_welford_lane_body.h - and changes
+// only where a frame value comes from:
 //
 //   per frame k (count n = count_before + k + 1):
 //       f     = ICRF[DN & M, c]     or   (DN & M) / M
 //       delta = f - mean;   mean = mean + delta / n;   m2 = m2 + delta * (f - mean)
 //   finalize:  mean -> around(mean * M) as uint16;   std -> around(sqrt(m2 / (n - 1)) / sqrt(n)) as uint16   (as written: no * M)
 //
-// k_welford_u16<M2, PLACE>: two elements per lane - one 4-byte load per frame (two uint16 DNs), 16-byte nontemporal state accesses - frames
-// in groups of kGroup whose loads and gathers are issued together, a one-thread odd tail, and welford_exact for the lanes outside the
-// fast-division range. The pair rule: frames 4-byte aligned at the first element and state 16-byte aligned; a call that breaks it takes
-// the scalar loads and stores with the same bits. DN & M is applied before every table access, in LDS or global memory.
+// k_welford_u16<M2, PLACE>: k_welford's lane loop with one 4-byte load per frame (two uint16 DNs). The pair rule: frames 4-byte aligned at
+// the first element and state 16-byte aligned; a call that breaks it takes the scalar loads and stores with the same bits. DN & M is
+// applied before every table access, in LDS or global memory.
 //
 // PLACE (hm_rules::WelfordU16Tab; the fit rule and the default are hm_producer_rules.h's) says where f comes from:
 //   tab=lds       dynamic LDS: the ICRF as t[ch][dn] (8 * 2^b * C bytes), or without an ICRF the one column dn / M (8 * 2^b bytes, formed
@@ -24,7 +24,7 @@
 //                 again through the library by tests/test_welford_u16_host.py::check_computed_quotient).
 //   tab=global    the ICRF gathered from global memory at icrf[dn * C + c]; 256-thread workgroups.
 //
-// The fast-division range argument of hm_welford.hip's header (every non-zero delta >= 2^-900 when table entries are 0 or in
+// The fast-division range argument of hm_welford_dev.h (every non-zero delta >= 2^-900 when table entries are 0 or in
 // [2^-500, 2^500], the incoming mean is 0 or in [2^-540, 2^500], |m2| <= 2^900 and n <= 2^40) holds in every placement because each one
 // establishes the table condition before a fast result is kept; the state is checked at load in all of them:
 //   tab=lds       every entry is tested while the table is filled; one odd entry sends the whole workgroup to welford_exact.
@@ -33,14 +33,11 @@
 //                 and redoes its two elements with welford_exact if one of them is outside the range. A fast result is kept only when
 //                 every f that went into it was inside, which is all the argument needs: it never speaks of entries a lane did not read.
 // A redo reads the state again from memory, where it is still the launch's input.
-#include "hm_common.h"
-#include "hm_producer_math.h"
+#include "hm_welford_dev.h"
 #include "hm_producer_rules.h"
 #include <mutex>
 
 namespace hm {
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 struct WelfordU16K {
     const uint16_t* frame[HM_MAX_FRAMES];
@@ -55,7 +52,6 @@ struct WelfordU16K {
     double rcp[HM_MAX_FRAMES];   // RN(1 / (count0 + k + 1)), formed on the host
 };
 
-constexpr int kWelfordU16Group = 8;          // frames whose loads / table gathers are issued together
 constexpr int kWelfordU16LdsBlock = 1024;    // threads of the tab=lds workgroup: one per CU
 constexpr int kWelfordU16Block = 256;
 constexpr int kWelfordU16LdsHead = 16;       // bytes in front of the LDS table (the odd-table word)
@@ -81,10 +77,7 @@ template <> struct WelfordU16Src<hm_rules::WELFORD_U16_GLOBAL> {
     __device__ __forceinline__ double at(uint32_t dn, uint32_t off) const { return icrf[dn * C + off]; }
 };
 
-__device__ __forceinline__ bool welford_entry_odd(double v) {       // non-finite, huge or tiny
-    return !(fabs(v) <= 0x1p500) || (v != 0.0 && fabs(v) < 0x1p-500);
-}
-
+// The gathers and the exact redo keep their own text beside hm_welford.hip's: every shared form tried moved a kernel.
 // reference arithmetic with the IEEE division for `count` consecutive elements, all frames (rare path and odd tail)
 template <bool M2, typename Src>
 __device__ __forceinline__ void welford_u16_exact(const WelfordU16K& a, const Src& src, int64_t e0, int count, double* mean, double* m2) {
@@ -95,16 +88,15 @@ __device__ __forceinline__ void welford_u16_exact(const WelfordU16K& a, const Sr
         for (int k = 0; k < a.n_frames; ++k) {
             cnt += 1.0;
             const double f = src.at(a.frame[k][e] & a.mask, off);
-            const double delta = f - m;
-            m = m + delta / cnt;
-            if (M2) q = q + delta * (f - m);
+            const double delta = f - m;                                   // :205
+            m = m + delta / cnt;                                          // :206
+            if (M2) q = q + delta * (f - m);                              // :208
         }
         mean[j] = m; m2[j] = q;
     }
 }
 
-// G frames starting at k0 for the lane's two elements (fast division: the caller checks its range, see the file header).
-// -> false when a gathered table value is outside the range (tab=global only: the other placements need no per-value test)
+// G frames starting at k0 for the lane's two elements (fast division: the caller checks its range, hm_welford_dev.h).
 template <bool M2, int G, bool VEC, int PLACE>
 __device__ __forceinline__ bool welford_u16_group(const WelfordU16K& a, const WelfordU16Src<PLACE>& src, int k0, int64_t e, uint32_t off0,
                                                   uint32_t off1, double& cnt, double (&m)[2], double (&q)[2]) {
@@ -120,25 +112,8 @@ __device__ __forceinline__ bool welford_u16_group(const WelfordU16K& a, const We
         f[k][0] = src.at(raw[k] & a.mask, off0);
         f[k][1] = src.at((raw[k] >> 16) & a.mask, off1);
     }
-    bool ok = true;
-    if constexpr (PLACE == hm_rules::WELFORD_U16_GLOBAL) {
-#pragma unroll
-        for (int k = 0; k < G; ++k) ok = ok && !welford_entry_odd(f[k][0]) && !welford_entry_odd(f[k][1]);
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-        cnt += 1.0;
-        const double r = a.rcp[k0 + k];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const double delta = f[k][j] - m[j];
-            const double q0 = delta * r;
-            const double quot = fma(fma(-q0, cnt, delta), r, q0);                 // == delta / cnt
-            m[j] = m[j] + quot;
-            if (M2) q[j] = q[j] + delta * (f[k][j] - m[j]);
-        }
-    }
-    return ok;
+#define HM_WELFORD_TEST_GATHERED (PLACE == hm_rules::WELFORD_U16_GLOBAL)
+#include "hm_welford_fold_body.h"
 }
 
 template <bool M2, int PLACE>
@@ -171,65 +146,18 @@ __global__ __launch_bounds__(PLACE == hm_rules::WELFORD_U16_LDS ? kWelfordU16Lds
         src.icrf = a.icrf; src.C = C;
     }
 
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const int64_t units = a.n / 2;
-    bool vec_ok = aligned_dev(a.mean, 16) && (!M2 || aligned_dev(a.m2, 16));
-    for (int k = 0; k < a.n_frames; ++k) vec_ok = vec_ok && aligned_dev(a.frame[k], 4);
-
-    for (int64_t u = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; u < units; u += stride) {
-        const int64_t e = 2 * u;
-        const uint32_t c0 = static_cast<uint32_t>(e % C), c1 = (c0 + 1u) % C;
-        const uint32_t off0 = src.offset(c0), off1 = src.offset(c1);
-        double m[2], q[2] = {0.0, 0.0};
-        if (vec_ok) {
-            const f64x2 mv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(a.mean + e));
-            m[0] = mv.x; m[1] = mv.y;
-            if (M2) { const f64x2 qv = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(a.m2 + e)); q[0] = qv.x; q[1] = qv.y; }
-        } else {
-            m[0] = a.mean[e]; m[1] = a.mean[e + 1];
-            if (M2) { q[0] = a.m2[e]; q[1] = a.m2[e + 1]; }
-        }
-        auto mean_ok = [](double x) { const double ax = fabs(x); return x == 0.0 || (ax >= 0x1p-540 && ax <= 0x1p500); };
-        bool ok = table_ok && mean_ok(m[0]) && mean_ok(m[1]) && fabs(q[0]) <= 0x1p900 && fabs(q[1]) <= 0x1p900;
-        double cnt = a.count0;
-        int k0 = 0;
-        if (vec_ok) {
-            for (; k0 + kWelfordU16Group <= a.n_frames; k0 += kWelfordU16Group)
-                ok = welford_u16_group<M2, kWelfordU16Group, true, PLACE>(a, src, k0, e, off0, off1, cnt, m, q) && ok;
-            for (; k0 < a.n_frames; ++k0) ok = welford_u16_group<M2, 1, true, PLACE>(a, src, k0, e, off0, off1, cnt, m, q) && ok;
-        } else {
-            for (; k0 < a.n_frames; ++k0) ok = welford_u16_group<M2, 1, false, PLACE>(a, src, k0, e, off0, off1, cnt, m, q) && ok;
-        }
-        if (__builtin_expect(!ok, 0)) {                // the state in memory is still the launch's input
-            welford_u16_exact<M2>(a, src, e, 2, m, q);
-        }
-        if (vec_ok) {
-            f64x2 mv; mv.x = m[0]; mv.y = m[1];
-            __builtin_nontemporal_store(mv, reinterpret_cast<f64x2*>(a.mean + e));
-            if (M2) { f64x2 qv; qv.x = q[0]; qv.y = q[1]; __builtin_nontemporal_store(qv, reinterpret_cast<f64x2*>(a.m2 + e)); }
-        } else {
-            a.mean[e] = m[0]; a.mean[e + 1] = m[1];
-            if (M2) { a.m2[e] = q[0]; a.m2[e + 1] = q[1]; }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (a.n & 1)) {
-        const int64_t e = a.n - 1;
-        double m[1], q[1];
-        welford_u16_exact<M2>(a, src, e, 1, m, q);
-        a.mean[e] = m[0];
-        if (M2) a.m2[e] = q[0];
-    }
+#define HM_WELFORD_PAIR_ALIGN 4
+#define HM_WELFORD_OFFSET(c) src.offset(c)
+#define HM_WELFORD_GROUP(G, VEC) welford_u16_group<M2, G, VEC, PLACE>(a, src, k0, e, off0, off1, cnt, m, q)
+#define HM_WELFORD_EXACT(e0, count) welford_u16_exact<M2>(a, src, e0, count, m, q)
+#include "hm_welford_lane_body.h"
 }
 
 __global__ __launch_bounds__(256) void k_welford_finalize_u16(const double* __restrict__ mean, const double* __restrict__ m2, double count,
                                                               double max_dn, uint16_t* __restrict__ out_mean,
                                                               uint16_t* __restrict__ out_std, int64_t n) {
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-    const double denom = count - 1.0, root_n = sqrt(count);
-    for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < n; e += stride) {
-        if (out_mean) out_mean[e] = round_to_u16(mean[e] * max_dn);
-        if (out_std) out_std[e] = round_to_u16(sqrt(m2[e] / denom) / root_n);
-    }
+#define HM_WELFORD_SCALE max_dn
+#include "hm_welford_finalize_body.h"
 }
 
 // More dynamic LDS than a kernel gets by default: both tab=lds instantiations are given the fit rule's table size and the head, once per
@@ -317,5 +245,5 @@ extern "C" int hm_welford_finalize_u16(const double* mean, const double* m2, int
 }
 
 extern "C" int64_t hm_welford_u16_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) {
-    return n_elems * (2 * static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16));
+    return hm_rules::welford_algorithmic_bytes(2, n_frames, with_m2 != 0, n_elems);
 }

@@ -980,62 +980,21 @@ int hm_pairs_histogram(const double* const* vals, const double* const* stds, int
     return HM_OK;
 }
 
+}  // extern "C" (templates below)
 // ---- the producers ---------------------------------------------------------------------------------
 // welford_algorithm, modules/video_processing.py:161-219: per element, frames in order - delta = f - mean; mean += delta / n;
-// m2 += delta * (f - mean) (:205-208), f = icrf[dn, c] (:200-201) or dn / 255 (:203)
-int hm_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
-                      int64_t n_elems, int C, void*) {
-    bool empty;
-    const int rc = hm_rules::check_welford_update(frames, n_frames, count_before, mean, n_elems, C, empty);
-    if (rc != HM_OK || empty) return rc;
+// m2 += delta * (f - mean) (:205-208), f = icrf[dn, c] (:200-201) or dn / 255 (:203). One text for uint8 frames (mask 255, max_dn 255.0)
+// and uint16 frames of 9 to 16 bits (mask = max_dn = 2^bit_depth - 1): f = icrf[DN & mask, c] or (DN & mask) / max_dn.
+template <typename DN>
+static void welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
+                           int64_t n_elems, int C, int mask, double max_dn) {
 #pragma omp parallel for schedule(static)
     for (int64_t e = 0; e < n_elems; ++e) {
         const int c = static_cast<int>(e % C);
         double m = mean[e], q = m2 ? m2[e] : 0.0, cnt = static_cast<double>(count_before);
         for (int k = 0; k < n_frames; ++k) {
             cnt += 1.0;
-            const int dn = static_cast<const uint8_t*>(frames[k])[e];
-            const double f = icrf ? icrf[dn * C + c] : static_cast<double>(dn) / 255.0;
-            const double delta = f - m;
-            m = m + delta / cnt;
-            q = q + delta * (f - m);
-        }
-        mean[e] = m;
-        if (m2) m2[e] = q;
-    }
-    return HM_OK;
-}
-
-int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uint8_t* out_mean, uint8_t* out_std, int64_t n_elems, void*) {
-    bool empty;
-    const int rc = hm_rules::check_welford_finalize(mean, m2, count, out_mean, out_std, n_elems, empty);
-    if (rc != HM_OK || empty) return rc;
-    const double denom = static_cast<double>(count) - 1.0, root_n = std::sqrt(static_cast<double>(count));
-#pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < n_elems; ++e) {
-        if (out_mean) out_mean[e] = round_to_u8(mean[e] * 255.0);                 // :210-211
-        if (out_std) out_std[e] = round_to_u8(std::sqrt(m2[e] / denom) / root_n); // :214-215, as written
-    }
-    return HM_OK;
-}
-int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) { return n_elems * (static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16)); }
-
-// ... on uint16 frames of 9 to 16 bits: f = icrf[DN & M, c] or (DN & M) / M, M = 2^bit_depth - 1. `variant` places the table on the
-// device; here it is only checked.
-int hm_welford_update_u16(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
-                          int64_t n_elems, int C, int bit_depth, int variant, void*) {
-    bool empty;
-    const int rc = hm_rules::check_welford_update_u16(frames, n_frames, count_before, icrf, mean, n_elems, C, bit_depth, variant, empty);
-    if (rc != HM_OK || empty) return rc;
-    const int mask = (1 << bit_depth) - 1;
-    const double max_dn = static_cast<double>(mask);
-#pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < n_elems; ++e) {
-        const int c = static_cast<int>(e % C);
-        double m = mean[e], q = m2 ? m2[e] : 0.0, cnt = static_cast<double>(count_before);
-        for (int k = 0; k < n_frames; ++k) {
-            cnt += 1.0;
-            const int dn = static_cast<const uint16_t*>(frames[k])[e] & mask;
+            const int dn = static_cast<const DN*>(frames[k])[e] & mask;
             const double f = icrf ? icrf[dn * C + c] : static_cast<double>(dn) / max_dn;
             const double delta = f - m;
             m = m + delta / cnt;
@@ -1044,6 +1003,48 @@ int hm_welford_update_u16(const void* const* frames, int n_frames, int64_t count
         mean[e] = m;
         if (m2) m2[e] = q;
     }
+}
+
+// mean -> around(mean * max_dn) (:210-211), std -> around(sqrt(m2 / (n - 1)) / sqrt(n)) (:214-215, as written: not rescaled)
+template <typename DN>
+static void welford_finalize(const double* mean, const double* m2, int64_t count, double max_dn, DN* out_mean, DN* out_std, int64_t n_elems) {
+    const double denom = static_cast<double>(count) - 1.0, root_n = std::sqrt(static_cast<double>(count));
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < n_elems; ++e) {
+        if (out_mean) out_mean[e] = round_to_dn<DN>(mean[e] * max_dn);
+        if (out_std) out_std[e] = round_to_dn<DN>(std::sqrt(m2[e] / denom) / root_n);
+    }
+}
+
+extern "C" {
+int hm_welford_update(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
+                      int64_t n_elems, int C, void*) {
+    bool empty;
+    const int rc = hm_rules::check_welford_update(frames, n_frames, count_before, mean, n_elems, C, empty);
+    if (rc != HM_OK || empty) return rc;
+    welford_update<uint8_t>(frames, n_frames, count_before, icrf, mean, m2, n_elems, C, 255, 255.0);
+    return HM_OK;
+}
+
+int hm_welford_finalize(const double* mean, const double* m2, int64_t count, uint8_t* out_mean, uint8_t* out_std, int64_t n_elems, void*) {
+    bool empty;
+    const int rc = hm_rules::check_welford_finalize(mean, m2, count, out_mean, out_std, n_elems, empty);
+    if (rc != HM_OK || empty) return rc;
+    welford_finalize<uint8_t>(mean, m2, count, 255.0, out_mean, out_std, n_elems);
+    return HM_OK;
+}
+int64_t hm_welford_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) {
+    return hm_rules::welford_algorithmic_bytes(1, n_frames, with_m2 != 0, n_elems);
+}
+
+// ... on uint16 frames of 9 to 16 bits, M = 2^bit_depth - 1. `variant` places the table on the device; here it is only checked.
+int hm_welford_update_u16(const void* const* frames, int n_frames, int64_t count_before, const double* icrf, double* mean, double* m2,
+                          int64_t n_elems, int C, int bit_depth, int variant, void*) {
+    bool empty;
+    const int rc = hm_rules::check_welford_update_u16(frames, n_frames, count_before, icrf, mean, n_elems, C, bit_depth, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    const int mask = (1 << bit_depth) - 1;
+    welford_update<uint16_t>(frames, n_frames, count_before, icrf, mean, m2, n_elems, C, mask, static_cast<double>(mask));
     return HM_OK;
 }
 
@@ -1063,17 +1064,11 @@ int hm_welford_finalize_u16(const double* mean, const double* m2, int64_t count,
     bool empty;
     const int rc = hm_rules::check_welford_finalize_u16(mean, m2, count, bit_depth, out_mean, out_std, n_elems, empty);
     if (rc != HM_OK || empty) return rc;
-    const double denom = static_cast<double>(count) - 1.0, root_n = std::sqrt(static_cast<double>(count));
-    const double max_dn = static_cast<double>((1 << bit_depth) - 1);
-#pragma omp parallel for schedule(static)
-    for (int64_t e = 0; e < n_elems; ++e) {
-        if (out_mean) out_mean[e] = round_to_u16(mean[e] * max_dn);
-        if (out_std) out_std[e] = round_to_u16(std::sqrt(m2[e] / denom) / root_n);    // as written: not rescaled
-    }
+    welford_finalize<uint16_t>(mean, m2, count, static_cast<double>((1 << bit_depth) - 1), out_mean, out_std, n_elems);
     return HM_OK;
 }
 int64_t hm_welford_u16_algorithmic_bytes(int n_frames, int with_m2, int64_t n_elems) {
-    return n_elems * (2 * static_cast<int64_t>(n_frames) + (with_m2 ? 32 : 16));
+    return hm_rules::welford_algorithmic_bytes(2, n_frames, with_m2 != 0, n_elems);
 }
 
 // compute_noise_profiles, modules/video_processing.py:77-106: profile[m, f, c] += 1 for every frame and element (np.add.at).

@@ -84,6 +84,13 @@ void producers() {
     expect("finalize u16, 8 bits", check_welford_finalize_u16(mean, mean, 2, 8, fake<uint16_t>(0x5000), fake<uint16_t>(0x6000), 12, empty), HM_EINVAL);
     expect("finalize u16, one frame", check_welford_finalize_u16(mean, mean, 1, 12, nullptr, fake<uint16_t>(0x6000), 12, empty), HM_EINVAL);
     expect("finalize u16, odd output", check_welford_finalize_u16(mean, mean, 2, 12, fake<uint16_t>(0x5001), nullptr, 12, empty), HM_EALIGN);
+    expect("welford, the shared counts: the count limit before the shape", welford_update_counts(2, kWelfordMaxCount + 1, 12, 0, empty), HM_EUNSUPPORTED);
+    expect("welford, the shared pointers: frames NULL, none read", welford_update_pointers(nullptr, HM_MAX_FRAMES, mean), HM_EINVAL);
+    expect("welford u16, a depth rule broken before the count limit", check_welford_update_u16_counts(2, kWelfordMaxCount + 1, 12, 3, false, 8, 0, empty), HM_EINVAL);
+    expect("finalize u16, a depth rule broken before nothing to do", check_welford_finalize_u16(nullptr, nullptr, 1, 17, nullptr, nullptr, 0, empty), HM_EINVAL);
+    expect("welford bytes, uint8 frames with m2", welford_algorithmic_bytes(1, HM_MAX_FRAMES, true, 10), 10 * (HM_MAX_FRAMES + 32));
+    expect("welford bytes, uint16 frames without", welford_algorithmic_bytes(2, HM_MAX_FRAMES, false, 10), 10 * (2 * HM_MAX_FRAMES + 16));
+    expect("welford bytes, 2^40 elements", welford_algorithmic_bytes(2, HM_MAX_FRAMES, true, int64_t{1} << 40), (int64_t{1} << 40) * 96);   // no int overflow
     expect("noise std, NULL", check_noise_profile_std(nullptr, 3, nullptr, nullptr), HM_EINVAL);
     expect("noise std, 5 channels", check_noise_profile_std(fake<int64_t>(0x4000), 5, mean, mean), HM_EUNSUPPORTED);
     expect("clean edges, NULL", check_noise_profile_clean_edges(nullptr, 3), HM_EINVAL);

@@ -9,7 +9,9 @@ SHA-256 of every output buffer. Run it on two builds and diff the outputs to sho
 The host library is the only one called. Covered: the merge (all eight mode combinations of float64 / uint8 frames, dark maps and std
 frames, plus the std-table, float32-std, uint16 and uint16-darks entries, with and without flat field, float64 and float32 outputs),
 linearize, the Gaussian weight, normalize_by_map, the operators, difference and interpolate (dense and broadcast), the histograms and
-min / max, welford_finalize, noise_profile_clean_edges, the kernel density estimate and differential-evolution generations.
+min / max, welford_update and welford_update_u16 (with and without ICRF and m2, count_before 0 and 3, NaN and inf in the state, depths
+9 / 12 / 16 with stray high bits), welford_finalize and welford_finalize_u16, noise_profile_clean_edges, the kernel density estimate
+and differential-evolution generations.
 Inputs are seeded and small (images of at most 9 x 11 x 3; N = 1, 2, 5); float inputs carry NaN, +-inf, +-0, negatives and values
 outside [0, 1]. The hashes depend on the machine's libm: a before / after record, not a test fixture.
 """
@@ -332,6 +334,38 @@ def producer_sweep():
     for count in (2, 7):
         om, os_ = np.full(n, 9, np.uint8), np.full(n, 9, np.uint8)
         report(f"welford_finalize count={count}", L.hm_welford_finalize(p(mean), p(m2), count, p(om), p(os_), n, None), mean=om, std=os_)
+    rng_w = np.random.default_rng(59)                                   # a generator of its own: the later cases keep their inputs
+    for bits in (9, 12, 16):
+        top = float((1 << bits) - 1)
+        mean16 = mean * 255.0 / top                                      # the same multiples of 1 / 2 once scaled by 2^bits - 1
+        mean16[20:31] = np.array([0.5, 1.5, 2.5, top - 0.5, top + 0.5, -0.5, top + 1.0, -1.0, 1e30, 3.49999, (top + 1.0) / 2.0 - 0.5]) / top
+        for count in (2, 7):
+            om, os_ = np.full(n, 9, np.uint16), np.full(n, 9, np.uint16)
+            rc = L.hm_welford_finalize_u16(p(mean16), p(m2), count, bits, p(om), p(os_), n, None)
+            report(f"welford_finalize_u16 bits={bits} count={count}", rc, mean=om, std=os_)
+    # the update entries: seeded frames, a NaN and an inf in the mean and in m2 when count_before > 0, with and without ICRF and m2
+    nf = 5
+    for count_before in (0, 3):
+        state = rng_w.uniform(0.0, 1.0, size=n) if count_before else np.zeros(n)
+        sq = rng_w.uniform(0.0, 0.5, size=n) if count_before else np.zeros(n)
+        if count_before:
+            state[7], state[8], sq[9], sq[10] = np.nan, np.inf, np.nan, np.inf
+        for with_icrf in (False, True):
+            for with_m2 in (False, True):
+                frames = [rng_w.integers(0, 256, size=n, dtype=np.uint8) for _ in range(nf)]
+                icrf, _ = tables(rng_w, 256, CH)
+                m, q = state.copy(), (sq.copy() if with_m2 else None)
+                rc = L.hm_welford_update(ptrs(frames), nf, count_before, p(icrf) if with_icrf else None, p(m), p(q), n, CH, None)
+                report(f"welford_update count_before={count_before} icrf={int(with_icrf)} m2={int(with_m2)}", rc, mean=m, m2=q)
+                for bits in (9, 12, 16):
+                    frames16 = [rng_w.integers(0, 1 << bits, size=n, dtype=np.uint16) for _ in range(nf)]
+                    if bits < 16:
+                        frames16[1][::5] |= np.uint16(1 << bits)                # stray high bits: masked away
+                        frames16[3][::3] |= np.uint16(0x8000)
+                    icrf16, _ = tables(rng_w, 1 << bits, CH)
+                    m, q = state.copy(), (sq.copy() if with_m2 else None)
+                    rc = L.hm_welford_update_u16(ptrs(frames16), nf, count_before, p(icrf16) if with_icrf else None, p(m), p(q), n, CH, bits, 0, None)
+                    report(f"welford_update_u16 bits={bits} count_before={count_before} icrf={int(with_icrf)} m2={int(with_m2)}", rc, mean=m, m2=q)
     for ch in (1, 3):
         for fill in ("bell", "sparse", "flat"):
             prof = np.zeros((256, 256, ch), np.int64)
