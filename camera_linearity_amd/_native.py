@@ -156,6 +156,12 @@ _SIGNATURES = {
                                           C.c_int64, C.c_void_p]),
     "hm_noise_profile_std": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_noise_profile_clean_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    # the per-level noise moments of uint16 frames: frames, n_frames, mean, n_elems, C, bit_depth, moments, variant, stream
+    "hm_noise_moments_algorithmic_bytes": (C.c_int64, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "hm_noise_moments_update_u16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p]),
+    "hm_noise_moments_update_u16_describe": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char), C.c_int]),
+    "hm_noise_moments_std": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hm_kde_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hm_kde_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hm_kde_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int,

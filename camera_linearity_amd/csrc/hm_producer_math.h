@@ -1,7 +1,7 @@
 // hm_producer_math.h - the element formulas of the upstream producers, one text for the device units (hm_welford.hip, hm_welford_u16.hip,
-// hm_noise.hip, hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 / uint16 rounding of the Welford result (round_to_dn picks by output type:
-// the finalize text of both depths calls it), the edge cleaning of one noise-profile row, and the counter-based uniform draws of the
-// differential evolution. Not the Welford fold: as a shared function it moved the device kernels (hm_welford_fold_body.h).
+// hm_noise.hip, hm_noise_u16.hip, hm_de.hip) and ../csrc_host/hm_host.cpp: the uint8 / uint16 rounding of the Welford result (round_to_dn
+// picks by output type: the finalize text of both depths calls it), the edge cleaning of one noise-profile row, one level of the STD table
+// from its noise moments, and the counter-based uniform draws of the differential evolution. Not the Welford fold: as a shared function it moved the device kernels (hm_welford_fold_body.h).
 //
 // DEVICE / HOST - the builds perform the same operations here.
 #pragma once
@@ -59,6 +59,21 @@ HM_MATH_FN void clean_edges_row(const Row& D, int center) {
         else if (D(m) == D(m - 1) && D(m) != 0) { D(m - 1) += 1; m += 1; }
         m -= 1;
     }
+}
+
+// One level of the per-DN STD table from its noise moments (hm_noise_moments_std): n frame-elements with S1 = sum d and S2 = sum d^2,
+// d = frame DN - mean DN. _calculate_STD's sqrt(sum((x - mean)^2 h) / n) on the DN grid x = f / M is sqrt(n S2 - S1^2) / n / M: the numerator
+// N = n S2 - S1^2 is formed exactly in 128-bit integers (up to 126 bits), converted half by half (no 128-bit conversion exists on the
+// device), and the rest is FP64 - at most five roundings. n = 0 gives 0 / 0 = NaN (deviation L); moments no data set can have (N < 0): NaN.
+HM_MATH_FN double noise_moments_level_std(int64_t n, int64_t s1, int64_t s2, double max_dn) {
+    const uint64_t a1 = s1 < 0 ? uint64_t{0} - static_cast<uint64_t>(s1) : static_cast<uint64_t>(s1);
+    const unsigned __int128 ns2 = static_cast<unsigned __int128>(static_cast<uint64_t>(n)) * static_cast<uint64_t>(s2);
+    const unsigned __int128 sq = static_cast<unsigned __int128>(a1) * a1;
+    if (n < 0 || ns2 < sq) return NAN;
+    const unsigned __int128 num = ns2 - sq;
+    const uint64_t hi = static_cast<uint64_t>(num >> 64), lo = static_cast<uint64_t>(num);
+    const double x = hi ? static_cast<double>(hi) * 0x1.0p64 + static_cast<double>(lo) : static_cast<double>(lo);
+    return sqrt(x) / static_cast<double>(n) / max_dn;
 }
 
 // the splitmix64 step, and draw k of member i of a generation's key as a double in [0, 1) (53 bits)

@@ -1,7 +1,8 @@
 // hm_producer_rules.h - the argument rules of the producer entries (hm_welford_update, hm_welford_finalize, hm_welford_update_u16,
-// hm_welford_finalize_u16, hm_noise_profile_update, hm_noise_profile_std, hm_noise_profile_clean_edges, hm_kde_moments, hm_kde_evaluate),
+// hm_welford_finalize_u16, hm_noise_profile_update, hm_noise_profile_std, hm_noise_profile_clean_edges, hm_noise_moments_update_u16,
+// hm_noise_moments_std, hm_kde_moments, hm_kde_evaluate),
 // written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build (hm_welford.hip, hm_welford_u16.hip,
-// hm_noise.hip, hm_kde.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it. Plain C++17 on hdrmerge.h
+// hm_noise.hip, hm_noise_u16.hip, hm_kde.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it. Plain C++17 on hdrmerge.h
 // and <cmath>: no HIP type.
 //
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call. `empty` is set
@@ -12,7 +13,8 @@
 //           rule (HM_ESHAPE): `need_workspace` keeps that place. The host build, which has nothing to ask of the workspace, asks for
 //           `moments` at that place instead; the device build asks for it after the shape. After the shared call the device build
 //           adds the size rules of its workspace (HM_EINVAL, last).
-//   hm_noise_profile_update           after the shared call the device build refuses a launch grid beyond 2^31 - 1 (HM_EUNSUPPORTED).
+//   hm_noise_profile_update, hm_noise_moments_update_u16 (LDS placement)
+//           after the shared call the device build refuses a launch grid beyond 2^31 - 1 (HM_EUNSUPPORTED).
 #pragma once
 #include "hdrmerge.h"
 #include <cmath>
@@ -155,6 +157,75 @@ inline int check_noise_profile_clean_edges(const int64_t* profiles, int C) {
     if (!profiles || C < 1) return HM_EINVAL;
     if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
     return HM_OK;
+}
+
+// ---- hm_noise_moments_update_u16 / hm_noise_moments_std: the per-level noise moments of uint16 frames of bit_depth 9..16 -------------
+// Where the device kernel keeps the (2^b, C) triples of a launch (`variant`; the host build checks it and ignores it). 0 is the library's
+// choice.
+//   NOISE_MOMENTS_LDS     every workgroup privatises the whole table in LDS - per level and channel a u32 element count, an i64 sum of d and
+//                         a u64 sum of d^2 (kNoiseMomentsLdsEntryBytes) - and flushes its non-zero entries once per launch
+//   NOISE_MOMENTS_GLOBAL  no copy: every lane adds its triples to `moments` with 8-byte global atomics
+//   NOISE_MOMENTS_WINDOW  a hashed window of kNoiseMomentsWindowSlots (level, channel) slots in LDS over the levels a workgroup meets, flushed
+//                         after every pass over 8192 elements; a triple whose slot another level holds goes to the global atomics. Any depth.
+enum NoiseMomentsTab { NOISE_MOMENTS_AUTO = 0, NOISE_MOMENTS_LDS = 1, NOISE_MOMENTS_GLOBAL = 2, NOISE_MOMENTS_WINDOW = 3 };
+constexpr int kNoiseMomentsWindowBits = 12;
+constexpr uint32_t kNoiseMomentsWindowSlots = 1u << kNoiseMomentsWindowBits;
+constexpr int64_t kNoiseMomentsWindowBytes = int64_t{24} * kNoiseMomentsWindowSlots;        // u64 + i64 + u32 count + u32 key per slot: 96 KiB
+
+// The fit rule: the LDS table may take 128 KiB of the CU's 160 KiB - C = 1 up to 12 bits, C = 2 and 3 up to 11, C = 4 up to 10.
+constexpr int64_t kNoiseMomentsLdsTableBytes = 128 * 1024;
+constexpr int64_t kNoiseMomentsLdsEntryBytes = 20;
+inline int64_t noise_moments_table_bytes(int bit_depth, int C) { return (kNoiseMomentsLdsEntryBytes << bit_depth) * C; }
+inline bool noise_moments_table_fits_lds(int bit_depth, int C) { return noise_moments_table_bytes(bit_depth, C) <= kNoiseMomentsLdsTableBytes; }
+// variant = 0: LDS where the table fits, else the window. Measurements: DESIGN.md 4.4.8.
+inline int noise_moments_default_placement(int bit_depth, int C) {
+    return noise_moments_table_fits_lds(bit_depth, C) ? NOISE_MOMENTS_LDS : NOISE_MOMENTS_WINDOW;
+}
+
+// check_noise_profile_update's statuses in their order, the uint16 entry's own rules at the places marked +:
+//   1. HM_EINVAL        n_frames outside 0..HM_MAX_FRAMES, a negative n_elems, C < 1, + bit_depth outside 9..16, + variant outside 0..3
+//   2. HM_EUNSUPPORTED  C > HM_MAX_CHANNELS
+//   3. HM_ESHAPE        n_elems no multiple of C
+//   4. HM_EUNSUPPORTED  + a forced LDS placement whose table does not fit (noise_moments_table_fits_lds)
+//   5. HM_EINVAL        NULL frames, mean, moments or frames[k]
+//   6. HM_EALIGN        + a frame or a mean that is not 2-byte aligned
+//   7. HM_OK, empty     no frames or no elements: nothing to do
+// rules 1-4, which look at no pointer: what hm_noise_moments_update_u16_describe checks (it sets `empty` itself)
+inline int check_noise_moments_update_counts(int n_frames, int64_t n_elems, int C, int bit_depth, int variant) {
+    if (n_frames < 0 || n_frames > HM_MAX_FRAMES || n_elems < 0 || C < 1 || bit_depth < 9 || bit_depth > 16 || variant < 0 ||
+        variant > NOISE_MOMENTS_WINDOW)
+        return HM_EINVAL;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    if (n_elems % C != 0) return HM_ESHAPE;
+    if (variant == NOISE_MOMENTS_LDS && !noise_moments_table_fits_lds(bit_depth, C)) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+inline int check_noise_moments_update(const void* const* frames, int n_frames, const uint16_t* mean, int64_t n_elems, int C, int bit_depth,
+                                      const int64_t* moments, int variant, bool& empty) {
+    empty = false;
+    const int rc = check_noise_moments_update_counts(n_frames, n_elems, C, bit_depth, variant);
+    if (rc != HM_OK) return rc;
+    if (!frames || !mean || !moments) return HM_EINVAL;
+    for (int k = 0; k < n_frames; ++k)
+        if (!frames[k]) return HM_EINVAL;
+    if (reinterpret_cast<uintptr_t>(mean) & 1) return HM_EALIGN;
+    for (int k = 0; k < n_frames; ++k)
+        if (reinterpret_cast<uintptr_t>(frames[k]) & 1) return HM_EALIGN;
+    empty = n_frames == 0 || n_elems == 0;
+    return HM_OK;
+}
+
+// HM_EINVAL for a NULL pointer, C < 1 or bit_depth outside 9..16, then HM_EUNSUPPORTED for C > HM_MAX_CHANNELS (check_noise_profile_std's order)
+inline int check_noise_moments_std(const int64_t* moments, int C, int bit_depth, const double* out_std) {
+    if (!moments || !out_std || C < 1 || bit_depth < 9 || bit_depth > 16) return HM_EINVAL;
+    if (C > HM_MAX_CHANNELS) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+// the frames and the mean read once (2 bytes per DN), the (2^b, C, 3) int64 state read and written once
+inline int64_t noise_moments_algorithmic_bytes(int n_frames, int64_t n_elems, int C, int bit_depth) {
+    return 2 * n_elems * (static_cast<int64_t>(n_frames) + 1) + ((int64_t{2} * 24) << bit_depth) * C;
 }
 
 inline int check_kde_moments(const double* val, int64_t n_elems, int C, int channel, const double* moments, const void* workspace,

@@ -1135,6 +1135,55 @@ int hm_noise_profile_clean_edges(int64_t* profiles, int C, void*) {
     return HM_OK;
 }
 
+// The per-level noise moments of uint16 frames of 9 to 16 bits, M = 2^bit_depth - 1: per element the sums of d = f - m over the frames,
+// then one add per element into moments[m][c][0..2]; unsigned arithmetic, modulo 2^64 as the header states. `variant` places the table on
+// the device; here it is only checked.
+int64_t hm_noise_moments_algorithmic_bytes(int n_frames, int64_t n_elems, int C, int bit_depth) {
+    return hm_rules::noise_moments_algorithmic_bytes(n_frames, n_elems, C, bit_depth);
+}
+int hm_noise_moments_update_u16(const void* const* frames, int n_frames, const uint16_t* mean, int64_t n_elems, int C, int bit_depth,
+                                int64_t* moments, int variant, void*) {
+    bool empty;
+    const int rc = hm_rules::check_noise_moments_update(frames, n_frames, mean, n_elems, C, bit_depth, moments, variant, empty);
+    if (rc != HM_OK || empty) return rc;
+    const uint32_t mask = (1u << bit_depth) - 1u;
+    uint64_t* mom = reinterpret_cast<uint64_t*>(moments);
+    for (int64_t e = 0; e < n_elems; ++e) {
+        const uint32_t m = mean[e] & mask;
+        uint64_t s1 = 0, s2 = 0;
+        for (int k = 0; k < n_frames; ++k) {
+            const int64_t d = static_cast<int64_t>(static_cast<const uint16_t*>(frames[k])[e] & mask) - static_cast<int64_t>(m);
+            s1 += static_cast<uint64_t>(d);
+            s2 += static_cast<uint64_t>(d * d);
+        }
+        uint64_t* t = mom + (static_cast<int64_t>(m) * C + e % C) * 3;
+        t[0] += static_cast<uint64_t>(n_frames);
+        t[1] += s1;
+        t[2] += s2;
+    }
+    return HM_OK;
+}
+int hm_noise_moments_update_u16_describe(int64_t n_elems, int n_frames, int C, int bit_depth, int variant, char* buf, int buf_len) {
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    buf[0] = '\0';
+    const int rc = hm_rules::check_noise_moments_update_counts(n_frames, n_elems, C, bit_depth, variant);
+    if (rc != HM_OK || n_frames == 0 || n_elems == 0) return rc;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "host_noise_moments<dn=u16,C=%d,bits=%d>", C, bit_depth);
+    return HM_OK;
+}
+int hm_noise_moments_std(const int64_t* moments, int C, int bit_depth, double* out_std, void*) {
+    const int rc = hm_rules::check_noise_moments_std(moments, C, bit_depth, out_std);
+    if (rc != HM_OK) return rc;
+    const int n_ent = (1 << bit_depth) * C;
+    const double max_dn = static_cast<double>((1 << bit_depth) - 1);
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n_ent; ++i) {
+        const int64_t* t = moments + static_cast<int64_t>(i) * 3;
+        out_std[i] = noise_moments_level_std(t[0], t[1], t[2], max_dn);
+    }
+    return HM_OK;
+}
+
 // compute_kernel_density_estimate, modules/measurand.py:716-761 (gaussian_kde(values, 'silverman', weights).evaluate), one channel.
 // The operation sequence of hm_kde.hip: counted = finite x (and std != 0), w = 1 / std or 1; moments over kKdeSlices fixed slices
 // added in order (the same bits for any thread count); evaluate sums w exp(-(d * d) * 0.5), d = x / h - y / h, per chunk of

@@ -1328,6 +1328,69 @@ def noise_profile_clean_edges(profiles: torch.Tensor) -> torch.Tensor:
     return profiles
 
 
+def _check_moments(moments: torch.Tensor, bit_depth) -> tuple:
+    """-> (bit_depth, C) of a (2**bit_depth, C, 3) int64 noise-moments tensor"""
+    bit_depth = _check_bit_depth(bit_depth)
+    _require_cuda(moments, "moments")
+    if moments.dtype != _I64 or not moments.is_contiguous():
+        raise TypeError("moments must be a contiguous int64 tensor")
+    if moments.dim() != 3 or moments.shape[0] != 2 ** bit_depth or moments.shape[2] != 3:
+        raise ValueError(f"moments must be shaped ({2 ** bit_depth}, C, 3) at bit_depth {bit_depth}, got {tuple(moments.shape)}")
+    return bit_depth, moments.shape[1]
+
+
+def noise_moments_update(frames: Sequence[torch.Tensor], mean_u16: torch.Tensor, moments: torch.Tensor, bit_depth: int,
+                         variant: Optional[int] = None) -> None:
+    """Add every element of `frames` (torch.uint16 (H, W, C) tensors of a `bit_depth`-bit camera, 9..16) to the noise moments of its mean
+    level in place (hm_noise_moments_update_u16): with m = mean DN & M, f = frame DN & M and d = f - m, moments[m, c] += (1, d, d * d).
+    `moments` ((2**bit_depth, C, 3) int64) is zeroed by the caller before the first update. HM_MAX_FRAMES frames per launch. `variant` says
+    where the device kernel keeps a launch's sums (None or 0: the library's choice, 1: the whole table in LDS, 2: global atomics, 3: a
+    hashed window in LDS); the result does not depend on it."""
+    bit_depth, Cc = _check_moments(moments, bit_depth)
+    _require_cuda(mean_u16, "mean_frame")
+    if mean_u16.dtype != _U16:
+        raise ValueError(f"bit_depth is for a torch.uint16 mean_frame, got {mean_u16.dtype}")
+    if not mean_u16.is_contiguous():
+        raise TypeError("mean_frame must be a contiguous uint16 tensor")
+    if mean_u16.dim() < 1 or mean_u16.shape[-1] != Cc:
+        raise ValueError(f"mean_frame has {mean_u16.shape[-1] if mean_u16.dim() else 0} channels, moments {Cc}")
+    frames = list(frames)
+    for f in frames:
+        _require_cuda(f, "frame")
+        if f.dtype != _U16:
+            raise ValueError(f"bit_depth is for torch.uint16 frames, got {f.dtype}")
+        if f.shape != mean_u16.shape:
+            raise ValueError("every frame must be a uint16 tensor shaped like mean_frame")
+    dev = moments.device
+    n = mean_u16.numel()
+    variant = 0 if variant is None else int(variant)
+    with _on(dev):
+        for k0 in range(0, len(frames), nat.HM_MAX_FRAMES):
+            batch = [f.contiguous() for f in frames[k0:k0 + nat.HM_MAX_FRAMES]]
+            nat.check(nat.lib.hm_noise_moments_update_u16(_ptr_array(batch), len(batch), mean_u16.data_ptr(), n, Cc, bit_depth,
+                                                          moments.data_ptr(), variant, _stream(dev)), "hm_noise_moments_update_u16")
+
+
+def noise_moments_std(moments: torch.Tensor, bit_depth: int) -> torch.Tensor:
+    """-> (2**bit_depth, C) float64 per-DN STD table on the DN grid k / (2**bit_depth - 1): sqrt(n S2 - S1^2) / n / M per level and channel
+    (hm_noise_moments_std), _calculate_STD's quantity; NaN for a level without counts."""
+    bit_depth, Cc = _check_moments(moments, bit_depth)
+    dev = moments.device
+    out = torch.empty((2 ** bit_depth, Cc), dtype=_F64, device=dev)
+    with _on(dev):
+        nat.check(nat.lib.hm_noise_moments_std(moments.data_ptr(), Cc, bit_depth, out.data_ptr(), _stream(dev)), "hm_noise_moments_std")
+    return out
+
+
+def noise_moments_kernel(n_elems: int, n_frames: int, channels: int, bit_depth: int, variant: int = 0) -> str:
+    """The kernel noise_moments_update starts on such a call, as hm_noise_moments_update_u16_describe names it
+    (e.g. "k_noise_moments_u16<C=3,tab=lds,bits=11>"); nothing is launched. For tests and benchmarks."""
+    buf = C.create_string_buffer(128)
+    nat.check(nat.lib.hm_noise_moments_update_u16_describe(int(n_elems), int(n_frames), int(channels), int(bit_depth), int(variant), buf, len(buf)),
+              "hm_noise_moments_update_u16_describe")
+    return buf.value.decode()
+
+
 # ------------------------------------------------------------------------------------------------
 # ICRF-calibration energy function (modules/ICRF_calibration_exposure.py:66-201), batched over candidates
 # ------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 """Mean / STD frames of a video - mirror of modules/video_processing.py:161-262 on the HIP backend - and the camera
 noise profiles with the per-DN STD table computed from them (:12-133). The mean / STD frames are also available for the uint16 frames
 of 9- to 16-bit cameras (`bit_depth=`); the noise profiles stay 8-bit: their (2^b, 2^b, C) joint histogram does not scale to 16 bits.
+The per-DN STD table of such a camera comes from `compute_noise_moments` / `noise_moments_to_STD_data` instead: three integers per
+(mean level, channel) - count, sum of d, sum of d^2 with d = frame DN - mean DN - are all `_calculate_STD` uses of a profile row.
 
 The reference streams frames out of `cv.VideoCapture` one at a time and updates three whole-image NumPy
 arrays per frame (video_processing.py:199-208). Here the decoded frames are uploaded in batches and folded
@@ -231,6 +233,85 @@ def compute_noise_profiles(frame_sources, mean_frame=None, device=None, frames_p
     if as_numpy:
         return profiles.cpu().numpy(), mean.cpu().numpy()
     return profiles, mean
+
+
+def compute_noise_moments(frame_sources, mean_frame=None, device=None, bit_depth: Optional[int] = None,
+                          frames_per_launch: int = FRAMES_PER_LAUNCH, as_numpy: bool = True):
+    """Per-level noise moments of a 9- to 16-bit camera from uint16 frames of a static scene: what `_calculate_STD` needs of the noise
+    profile - a count, the sum of d and the sum of d^2 per (mean level, channel), d = frame DN - mean DN - without the (2^b, 2^b, C)
+    histogram. `noise_moments_to_STD_data` turns them into the per-DN STD table.
+
+    Args:
+        frame_sources: as `compute_noise_profiles`, with uint16 (H, W, C) (or (H, W)) frames. Without `mean_frame` every source is read
+            twice, so a one-shot iterator is rejected.
+        mean_frame: uint16 (H, W, C) mean frame to count against; default: welford_algorithm(..., bit_depth=bit_depth)'s mean.
+        device: the GPU to compute on (default: the current one), or "cpu" for the host build (libhdrmerge_host.so).
+        bit_depth: 9..16, the camera's DN range; DNs are masked to it.
+    Returns:
+        (moments int64 (2**bit_depth, C, 3), mean_frame uint16 (H, W, C)) - NumPy arrays (device tensors with as_numpy=False);
+        moments[m, c] = (count, sum d, sum d^2) over the elements of channel c whose mean DN is m.
+    """
+    bit_depth = engine._check_bit_depth(bit_depth)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    eng = _engine_for(device)
+    if frames_per_launch < 1:
+        raise ValueError("frames_per_launch must be positive")
+    sources = _source_list(frame_sources)
+    if mean_frame is None:
+        for src in sources:
+            if not callable(src) and iter(src) is src:
+                raise ValueError("compute_noise_moments reads every source twice (mean frame, then moments): pass lists, "
+                                 "zero-argument callables returning fresh iterables, or mean_frame=")
+        mean = welford_algorithm([_fresh(s) for s in sources], None, False, device=device, frames_per_launch=frames_per_launch,
+                                 as_numpy=False, bit_depth=bit_depth)["mean"]
+    else:
+        mean = _as_device_frame(mean_frame, device, bit_depth).contiguous()
+    C = mean.shape[-1]
+    moments = torch.zeros((2 ** bit_depth, C, 3), dtype=torch.int64, device=device)
+    pending = []
+
+    def flush():
+        if pending:
+            eng.noise_moments_update(pending, mean, moments, bit_depth)
+            pending.clear()
+
+    for src in sources:
+        for frame in _fresh(src):
+            if frame is None:
+                break
+            t = _as_device_frame(frame, device, bit_depth)
+            if t.shape != mean.shape:
+                raise ValueError(f"frame shape {tuple(t.shape)} differs from the mean frame's {tuple(mean.shape)}")
+            pending.append(t)
+            if len(pending) == frames_per_launch:
+                flush()
+    flush()
+    if as_numpy:
+        return moments.cpu().numpy(), mean.cpu().numpy()
+    return moments, mean
+
+
+def noise_moments_to_STD_data(moments, bit_depth, device=None):
+    """(2**bit_depth, C) float64 STD table of a 9- to 16-bit camera from `compute_noise_moments`' moments: row k is the standard deviation
+    of the frames at mean level k on the DN grid k / (2**bit_depth - 1), NaN for a level without counts. The std table of
+    `engine.linearize(frame_u16, None, table, bit_depth=bit_depth)`. NumPy in, NumPy out; a tensor stays a tensor on its device."""
+    bit_depth = engine._check_bit_depth(bit_depth)
+    is_np = not isinstance(moments, torch.Tensor)
+    if is_np:
+        a = np.asarray(moments)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"moments must be an integer array, got {a.dtype}")
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    else:
+        if moments.dtype.is_floating_point or moments.dtype == torch.bool:
+            raise TypeError(f"moments must be an integer tensor, got {moments.dtype}")
+        t = moments
+        dev = moments.device if device is None else torch.device(device)
+    if t.dim() != 3 or t.shape[0] != 2 ** bit_depth or t.shape[2] != 3:
+        raise ValueError(f"moments must be shaped ({2 ** bit_depth}, C, 3) at bit_depth {bit_depth}, got {tuple(t.shape)}")
+    out = _engine_for(dev).noise_moments_std(t.to(device=dev, dtype=torch.int64).contiguous(), bit_depth)
+    return out.cpu().numpy() if is_np else out
 
 
 def _profiles_tensor(arr, device, what: str):

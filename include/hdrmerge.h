@@ -45,7 +45,9 @@ extern "C" {
  *    Later grown by the hm_noise_profile_* and hm_kde_* entry points without a bump (additions only), and likewise by
  *    hm_merge_std_table* and hm_merge_std_f32* (new entry points beside hm_merge; hm_merge_args keeps its 296 bytes), and by
  *    hm_merge_u16*, hm_linearize_u16 and hm_gaussian_weight_lut_bits_host (uint16 DN frames of 9- to 16-bit cameras; HM_BITS below is
- *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames).       */
+ *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames), and by
+ *    hm_linearity_energy_u16*, hm_welford_*_u16* and hm_noise_moments_* (the calibration energy, the mean / std producer and the per-DN STD
+ *    table for those frames).       */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -587,6 +589,44 @@ int hm_noise_profile_update(const void* const* frames /*[host] n_frames device p
                             int64_t workspace_bytes, void* stream);
 int hm_noise_profile_std(const int64_t* profiles, int C, const double* edges, double* out_std, void* stream);
 int hm_noise_profile_clean_edges(int64_t* profiles, int C, void* stream);
+
+/* ... the per-DN STD table of 9- to 16-bit cameras, M = 2^bit_depth - 1. The (2^b, 2^b, C) joint histogram does not scale to these depths
+ * (96 GiB at 16 bits); _calculate_STD reduces each of its rows to a count, a mean and a centred second moment, and three integers per
+ * (mean level, channel) carry exactly that.
+ *   moments    (2^bit_depth, C, 3) int64, indexed [level][c][k]. With m = mean[e] & M, f = frame[e] & M (the mask first: hm_merge_u16's
+ *              convention), c = e % C and d = f - m, every frame and element e adds 1 to [m][c][0], d to [m][c][1] and d * d to [m][c][2].
+ *              The caller zero-initialises it before the first update and every update adds to it (hm_noise_profile_update's running-state
+ *              convention). The sums are integers modulo 2^64: exact, and independent of the order of the adds, while count * D * D < 2^63
+ *              for every level, |d| <= D (D <= M; D = 65535 allows 2^31 frame-elements on one level, D = 1023 allows 2^43).
+ *   hm_noise_moments_update_u16   adds n_frames uint16 frames (each n_elems = H*W*C, HWC, 2-byte aligned) against the uint16 mean frame
+ *              `mean`. No allocation, no host synchronisation, no workspace; capturable.
+ *   variant    where the device kernel keeps the triples of a launch - 0: the library's choice; 1: every workgroup privatises the whole
+ *              table in LDS (a u32 element count, an i64 sum of d and a u64 sum of d * d: 20 bytes per level and channel) and flushes its
+ *              non-zero entries once per launch; 2: every lane adds its triples to `moments` with 8-byte global atomics; 3: a hashed
+ *              window of 4096 (level, channel) slots in LDS over the levels a workgroup meets, flushed after every pass over 8192 elements,
+ *              a triple whose slot another level holds going to the global atomics - any depth. Fit rule: the LDS table,
+ *              20 * 2^bit_depth * C bytes, may take 128 KiB - C = 1 up to 12 bits, C = 2 and 3 up to 11, C = 4 up to 10. The library's
+ *              choice is 1 where the table fits, else 3. The placements give the same integers. The host build checks variant and
+ *              ignores it.
+ *   Statuses of hm_noise_moments_update_u16, an earlier one winning (hm_noise_profile_update's order): HM_EINVAL for n_frames outside
+ *   0..HM_MAX_FRAMES, a negative n_elems, C < 1, bit_depth outside 9..16 or variant outside 0..3; HM_EUNSUPPORTED for C > HM_MAX_CHANNELS;
+ *   HM_ESHAPE for n_elems no multiple of C; HM_EUNSUPPORTED for a forced variant 1 whose table does not fit; HM_EINVAL for NULL frames,
+ *   mean, moments or frames[k]; HM_EALIGN for a frame or a mean that is not 2-byte aligned; then n_frames == 0 or n_elems == 0 returns HM_OK.
+ *   hm_noise_moments_algorithmic_bytes   2 * n_elems * (n_frames + 1) + 2 * 24 * 2^bit_depth * C: each frame and the mean read once, the
+ *              moments read and written once.
+ *   hm_noise_moments_update_u16_describe writes the name of the kernel such a call would launch, e.g. "k_noise_moments_u16<C=3,tab=lds,bits=11>"
+ *   (tab = lds, global or window; the host build: a host name), and launches nothing; the statuses above up to the second HM_EUNSUPPORTED, an empty
+ *   name where there is nothing to do, HM_EINVAL for a NULL or empty buf.
+ *   hm_noise_moments_std      out_std (2^bit_depth, C) float64 [level][c]: with n, S1, S2 of a level, std = sqrt(n * S2 - S1 * S1) / n / M.
+ *              The numerator is formed exactly in 128-bit integers and converted to FP64 half by half; the value is at most five FP64
+ *              roundings from the exact one. n == 0 gives NaN (hm_noise_profile_std's row without counts); so do moments that no data
+ *              set has (n < 0, n * S2 < S1 * S1). On the DN grid k / M this is hm_noise_profile_std's quantity. HM_EINVAL for a NULL
+ *              pointer, C < 1 or bit_depth outside 9..16, then HM_EUNSUPPORTED for C > HM_MAX_CHANNELS. */
+int64_t hm_noise_moments_algorithmic_bytes(int n_frames, int64_t n_elems, int C, int bit_depth);
+int hm_noise_moments_update_u16(const void* const* frames /*[host] n_frames device ptrs*/, int n_frames, const uint16_t* mean,
+                                int64_t n_elems, int C, int bit_depth, int64_t* moments, int variant, void* stream);
+int hm_noise_moments_update_u16_describe(int64_t n_elems, int n_frames, int C, int bit_depth, int variant, char* buf, int buf_len);
+int hm_noise_moments_std(const int64_t* moments, int C, int bit_depth, double* out_std, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Weighted Gaussian kernel density estimates: NumpyMeasurand.compute_kernel_density_estimate, modules/measurand.py:716-761

@@ -657,6 +657,48 @@ def case_welford_u16(rng):
     return desc
 
 
+def case_noise_moments(rng):
+    """hm_noise_moments_update_u16 / hm_noise_moments_std: uint16 frames of 9 to 16 bits with stray bits above the depth against a noisy, a
+    constant or an unrelated mean frame, every placement that exists for the case (LDS where the table fits, global atomics, the LDS window),
+    odd sizes, views at 2-byte-aligned addresses, several launches into one state: the integer moments equal to the host build's, the table
+    to 16 * 2^-53 (each build is within 8 * 2^-53 of the exact value: tests/test_noise_moments_host.py) with equal NaN levels."""
+    depth = int(rng.integers(9, 17))
+    n_dn = 2 ** depth
+    c = int(rng.choice([1, 2, 3, 3, 4]))
+    h, w = int(rng.integers(1, 30 * args.scale)), int(rng.integers(1, 40 * args.scale))
+    n = int(rng.integers(1, 80))
+    variant = int(rng.choice([0] + ([1] if 20 * n_dn * c <= 128 * 1024 else []) + [2, 3]))
+    kind = str(rng.choice(["noisy", "constant", "unrelated"]))
+    base = rng.integers(0, n_dn, (h, w, c))
+    sigma = float(rng.choice([0.0, 1.5, n_dn / 100]))
+    frames = np.clip(base + np.around(rng.standard_normal((n, h, w, c)) * sigma), 0, n_dn - 1).astype(np.int64)
+    mean = base if kind == "noisy" else np.full_like(base, int(rng.integers(0, n_dn))) if kind == "constant" else rng.integers(0, n_dn, (h, w, c))
+    high = 2 ** (16 - depth)
+    frames = (frames | (rng.integers(0, high, frames.shape) << depth)).astype(np.uint16)       # stray high bits: masked by both builds
+    mean = (mean | (rng.integers(0, high, mean.shape) << depth)).astype(np.uint16)
+    splits = sorted(set(int(q) for q in rng.integers(1, n + 1, size=int(rng.integers(0, 3))))) + [n]
+    off = rng.random() < 0.4
+    e = h * w * c
+    desc = f"noise_moments bits={depth} n={n} {h}x{w}x{c} variant={variant} mean={kind} sigma={sigma:g} launches at {splits} unaligned={off}"
+    out = []
+    for eng_, dv in ((engine, dev), (heng, torch.device("cpu"))):
+        def frame(f):
+            buf = torch.zeros(e + 2, dtype=torch.int16, device=dv)
+            buf[int(off):int(off) + e] = torch.from_numpy(f.view(np.int16).reshape(-1).copy()).to(dv)
+            return buf.view(torch.uint16)[int(off):int(off) + e].view(h, w, c)
+        mom = torch.zeros((n_dn, c, 3), dtype=torch.int64, device=dv)
+        md, k0 = frame(mean), 0
+        for k1 in splits:
+            eng_.noise_moments_update([frame(f) for f in frames[k0:k1]], md, mom, depth, variant)
+            k0 = k1
+        out.append((mom, eng_.noise_moments_std(mom, depth)))
+    compare("moments", out[0][0], out[1][0], None)
+    if int(as_np(out[1][0])[:, :, 0].sum()) != n * e:
+        raise Mismatch("moments: the counts do not sum to frames * elements")
+    compare("std table", out[0][1], out[1][1], 16 * 2.0 ** -53)
+    return desc
+
+
 def case_energy(rng):
     """hm_linearity_energy: a population of candidate ICRFs (some rejected) on one channel's (X, Y, N) stack; energies and per-pair results
     to 1e-11 (the device's register kernel multiplies by reciprocals; sums run in another order), NaN / inf patterns equal."""
@@ -1053,7 +1095,7 @@ def case_linearize_u16(rng):
 
 
 CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
     assert CASES, f"--only {args.only}: no such generator"
