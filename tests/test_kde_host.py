@@ -66,11 +66,7 @@ def test_host_matches_scipy(n, m, with_std, seed):
 
 
 def test_host_all_negative_weights_work_like_scipy():
-    rng = np.random.default_rng(9)
-    x = rng.standard_normal((300, 1))
-    s = -rng.uniform(0.1, 1.0, (300, 1))
-    res = HostMeasurand(x, s).compute_kernel_density_estimate(40, channels=[0], use_std=True)
-    assert_kde_close(res[0][0], scipy_kde(x[:, 0], 1 / s[:, 0], res[0][1]), rtol=1e-10)
+    check_all_negative_weights(host_run)
 
 
 def test_host_included_range_does_not_filter():
@@ -83,56 +79,78 @@ def test_host_included_range_does_not_filter():
     assert_kde_close(res[1][0], scipy_kde(x[:, 1], None, pts))
 
 
-def test_host_errors_match_reference():
+def host_run(x, s=None, *a, **k):
+    """The measurand factory of the host tests; tests/test_gpu_kde_limits.py passes one that builds a HipMeasurand."""
+    return HostMeasurand(x, s).compute_kernel_density_estimate(*a, **k)
+
+
+def check_errors_match_reference(run):
+    """run(values, stds or None, data_points, **kw) -> the estimate dict: every error the reference raises."""
     rng = np.random.default_rng(2)
     x = rng.standard_normal((6, 7, 3))
     s = rng.uniform(0.1, 1.0, x.shape)
     with pytest.raises(TypeError):                                        # use_std without std: self.std[..., c]
-        HostMeasurand(x).compute_kernel_density_estimate(10, use_std=True)
+        run(x, None, 10, use_std=True)
     one = x.copy()
     one[..., 1] = np.nan
     one[0, 0, 1] = 0.5
     with pytest.raises(ValueError):                                       # a single counted value
-        HostMeasurand(one).compute_kernel_density_estimate(10)
+        run(one, None, 10)
     none = x.copy()
     none[..., 0] = np.inf
     with pytest.raises(ValueError):                                       # nothing counted: np.min of an empty array
-        HostMeasurand(none).compute_kernel_density_estimate(10)
+        run(none, None, 10)
     zero = s.copy()
     zero[..., 2] = 0.0
     zero[0, 0, 2] = zero[0, 1, 2] = 1.0
-    HostMeasurand(x, zero).compute_kernel_density_estimate(10, channels=[2], use_std=True)    # two counted values work
+    run(x, zero, 10, channels=[2], use_std=True)                          # two counted values work
     zero[0, 1, 2] = 0.0
     with pytest.raises(ValueError):                                       # std == 0 removes all but one
-        HostMeasurand(x, zero).compute_kernel_density_estimate(10, channels=[2], use_std=True)
+        run(x, zero, 10, channels=[2], use_std=True)
     nan_std = s.copy()
     nan_std[3, 3, 0] = np.nan
     with pytest.raises(ValueError):                                       # check_finite in scipy
-        HostMeasurand(x, nan_std).compute_kernel_density_estimate(10, use_std=True)
+        run(x, nan_std, 10, use_std=True)
     mixed = s.copy()
     mixed[1, 1, 0] = -0.5
     with pytest.raises(ValueError):
-        HostMeasurand(x, mixed).compute_kernel_density_estimate(10, use_std=True)
+        run(x, mixed, 10, use_std=True)
     const = x.copy()
     const[..., 0] = 0.3
     for std in (None, s):
         with pytest.raises(np.linalg.LinAlgError):                        # deviation M: always, with or without weights
-            HostMeasurand(const, std).compute_kernel_density_estimate(10, use_std=std is not None)
+            run(const, std, 10, use_std=std is not None)
     inf_std = s.copy()
     inf_std[..., 0] = np.inf                                              # every weight 0
     with pytest.raises(ValueError):
-        HostMeasurand(x, inf_std).compute_kernel_density_estimate(10, channels=[0], use_std=True)
+        run(x, inf_std, 10, channels=[0], use_std=True)
 
 
-def test_host_inf_std_counts_with_weight_zero():
+def check_inf_std_counts_with_weight_zero(run):
     """An infinite std keeps its value counted (weight 0): it moves the default range but not the estimate's shape."""
     rng = np.random.default_rng(6)
     x = rng.standard_normal((400, 1))
     s = rng.uniform(0.1, 1.0, x.shape)
     x[7, 0], s[7, 0] = 25.0, np.inf
-    res = HostMeasurand(x, s).compute_kernel_density_estimate(50, channels=[0], use_std=True)
+    res = run(x, s, 50, channels=[0], use_std=True)
     assert res[0][1][-1] == 25.0
     assert_kde_close(res[0][0], scipy_kde(x[:, 0], 1 / s[:, 0], res[0][1]), rtol=1e-10)
+
+
+def check_all_negative_weights(run):
+    rng = np.random.default_rng(9)
+    x = rng.standard_normal((300, 1))
+    s = -rng.uniform(0.1, 1.0, (300, 1))
+    res = run(x, s, 40, channels=[0], use_std=True)
+    assert_kde_close(res[0][0], scipy_kde(x[:, 0], 1 / s[:, 0], res[0][1]), rtol=1e-10)
+
+
+def test_host_errors_match_reference():
+    check_errors_match_reference(host_run)
+
+
+def test_host_inf_std_counts_with_weight_zero():
+    check_inf_std_counts_with_weight_zero(host_run)
 
 
 def test_host_dn_backed_matches_float():
