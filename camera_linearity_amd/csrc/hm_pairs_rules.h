@@ -1,11 +1,14 @@
-// hm_pairs_rules.h - the argument rules of the all-pairs entries (hm_pairs_statistics, hm_pairs_minmax, hm_pairs_histogram), written once
-// for both builds of the ABI in the manner of hm_merge_rules.h: the device build (hm_stats.hip, hm_stats_hist.hip through hm_stats_pairs.h)
-// and the host build (csrc_host/hm_host.cpp) include this file and restate none of it. Plain C++17 on hdrmerge.h: no HIP type.
+// hm_pairs_rules.h - the argument rules of the all-pairs entries (hm_pairs_statistics, hm_pairs_minmax, hm_pairs_histogram,
+// hm_pairs_statistics_dn), written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build (hm_stats.hip,
+// hm_stats_hist.hip, hm_stats_dn.hip through hm_stats_pairs.h) and the host build (csrc_host/hm_host.cpp) include this file and restate none
+// of it. For the DN entry also what both its entry and its _describe decide: the table's fit rule, the kernel of a launch, the names.
+// Plain C++17 on hdrmerge.h: no HIP type.
 //
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call. There is no
-// difference between the builds: both ask for the workspace and for 8-byte-aligned frames.
+// difference between the builds: both ask for the workspace and for 8-byte-aligned float64 frames (DN frames: check_pairs_dn's own rule).
 #pragma once
 #include "hm_rules_common.h"
+#include <cstdio>
 
 namespace hm_rules {
 
@@ -33,6 +36,89 @@ inline int check_pairs_histogram(const double* const* vals, const double* const*
     if (rc != HM_OK) return rc;
     if (bins < 1 || bins > HM_PAIRS_HIST_MAX_BINS || !edges || channel_mask < 0 || (channel_mask >> C) != 0) return HM_EINVAL;
     return HM_OK;
+}
+
+// ---- hm_pairs_statistics_dn: the all-pairs statistics straight from uint8 / uint16 DN frames ----
+// Everything a frame contributes is a function of (DN & (2^bit_depth - 1), channel): a thresholded {value, std} table entry.
+// `variant`: where the staged kernel keeps that table, or the per-wave kernel for every launch.
+enum PairsDnVariant { PAIRS_DN_WAVE = -1, PAIRS_DN_AUTO = 0, PAIRS_DN_LDS = 1, PAIRS_DN_GLOBAL = 2 };
+
+constexpr int64_t kPairsDnLdsBytes = 160 * 1024;          // the LDS of a gfx950 CU
+constexpr int64_t kPairsDnStagesMax = 3 * 21 * 1024;      // three stages of at most 21 streams, 1 KiB each
+
+// 8 bytes (value) or 16 bytes ({value, std}) per (DN, channel)
+inline int64_t pairs_dn_table_bytes(int bit_depth, int C, bool with_std) { return (int64_t{with_std ? 16 : 8} << bit_depth) * C; }
+// the fit rule: the table beside the largest stages the staged kernel ever has (a function of the depth, C and the stds alone)
+inline bool pairs_dn_table_fits_lds(int bit_depth, int C, bool with_std) {
+    return pairs_dn_table_bytes(bit_depth, C, with_std) + kPairsDnStagesMax <= kPairsDnLdsBytes;
+}
+// frames the staged loader can read an item (two DNs) of with one load: uint8 frames 2-byte, uint16 frames 4-byte aligned
+inline bool pairs_dn_frames_item_aligned(const void* const* frames, int n_frames, int bit_depth) {
+    const uintptr_t m = bit_depth == 8 ? 1u : 3u;
+    for (int i = 0; i < n_frames; ++i)
+        if (reinterpret_cast<uintptr_t>(frames[i]) & m) return false;
+    return true;
+}
+// one launch of n_pairs_launch <= HM_PAIRS_MAX pairs: the staged kernel takes it when the frames are item-aligned, a workgroup's threads
+// can copy an iteration's 64 * n_frames items with at most two each and the streams fit three stages (hm_pairs_statistics' own rule)
+struct PairsDnLaunch { bool staged; int ni; bool tab_lds; };
+inline PairsDnLaunch pairs_dn_launch(int n_frames, int n_pairs_launch, bool with_std, int bit_depth, int C, int variant, bool item_aligned) {
+    PairsDnLaunch l{};
+    const int n_streams = n_frames * (with_std ? 2 : 1);
+    l.staged = variant != PAIRS_DN_WAVE && item_aligned && n_frames * 64 <= 2 * 64 * n_pairs_launch && n_streams <= 21;
+    l.ni = n_frames * 64 <= 64 * n_pairs_launch ? 1 : 2;
+    l.tab_lds = variant == PAIRS_DN_LDS || (variant == PAIRS_DN_AUTO && pairs_dn_table_fits_lds(bit_depth, C, with_std));
+    return l;
+}
+
+// the rules that look at no pointer: what hm_pairs_statistics_dn_describe checks
+inline int check_pairs_dn_counts(int n_frames, int n_pairs, int64_t n, int C, bool with_std, int bit_depth, int variant) {
+    if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || n % C != 0) return HM_EINVAL;
+    if (bit_depth < 8 || bit_depth > 16 || variant < PAIRS_DN_WAVE || variant > PAIRS_DN_GLOBAL) return HM_EINVAL;
+    if (variant == PAIRS_DN_LDS && !pairs_dn_table_fits_lds(bit_depth, C, with_std)) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+// hm_pairs_statistics_dn. In hdrmerge.h's order: HM_EINVAL (check_pairs' own rules on the frames, bit_depth, variant, std_table without
+// icrf_diff), HM_EALIGN (a table that is not 8-byte aligned, a uint16 frame that is not 2-byte aligned), HM_EINVAL for a pair index outside
+// the frames (as check_pairs places it), then HM_EUNSUPPORTED for variant 1 with a table that does not fit.
+inline int check_pairs_dn(const void* const* frames, int n_frames, int bit_depth, const double* icrf, const double* icrf_diff,
+                          const double* std_table, const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                          int64_t n, int C, const double* lower, const double* upper, int variant, const void* out, const void* workspace) {
+    if (!frames || !icrf || !pair_i || !pair_j || !multipliers || !out || !workspace || n < 1 || C < 1 || C > HM_MAX_CHANNELS) return HM_EINVAL;
+    if (n_frames < 1 || n_frames > HM_MAX_FRAMES || n_pairs < 1 || ((lower != nullptr) != (upper != nullptr)) || n % C != 0) return HM_EINVAL;
+    if (bit_depth < 8 || bit_depth > 16 || variant < PAIRS_DN_WAVE || variant > PAIRS_DN_GLOBAL || (std_table && !icrf_diff)) return HM_EINVAL;
+    for (int i = 0; i < n_frames; ++i)
+        if (!frames[i]) return HM_EINVAL;
+    if (!aligned8(icrf) || !aligned8(icrf_diff) || !aligned8(std_table)) return HM_EALIGN;
+    if (bit_depth > 8)
+        for (int i = 0; i < n_frames; ++i)
+            if (reinterpret_cast<uintptr_t>(frames[i]) & 1u) return HM_EALIGN;
+    for (int p = 0; p < n_pairs; ++p)
+        if (pair_i[p] < 0 || pair_i[p] >= n_frames || pair_j[p] < 0 || pair_j[p] >= n_frames) return HM_EINVAL;
+    if (variant == PAIRS_DN_LDS && !pairs_dn_table_fits_lds(bit_depth, C, std_table != nullptr)) return HM_EUNSUPPORTED;
+    return HM_OK;
+}
+
+// the kernels of a call, launch by launch (HM_PAIRS_MAX pairs each), joined by " + ": the device build's names
+inline void pairs_dn_describe(int n_frames, int n_pairs, int C, bool with_std, int bit_depth, int variant, bool item_aligned, char* buf,
+                              int buf_len) {
+    int used = 0;
+    buf[0] = '\0';
+    for (int p0 = 0; p0 < n_pairs && used < buf_len - 1; p0 += HM_PAIRS_MAX) {
+        const int np = n_pairs - p0 < HM_PAIRS_MAX ? n_pairs - p0 : HM_PAIRS_MAX;
+        const PairsDnLaunch l = pairs_dn_launch(n_frames, np, with_std, bit_depth, C, variant, item_aligned);
+        const char* dn = bit_depth == 8 ? "u8" : "u16";
+        int w;
+        if (l.staged)
+            w = snprintf(buf + used, static_cast<size_t>(buf_len - used), "%spairs_stats_dn_lds<dn=%s,bits=%d,tab=%s,std=%d,ni=%d>", p0 ? " + " : "",
+                         dn, bit_depth, l.tab_lds ? "lds" : "global", with_std ? 1 : 0, l.ni);
+        else
+            w = snprintf(buf + used, static_cast<size_t>(buf_len - used), "%spairs_stats_dn_wave<dn=%s,bits=%d,std=%d>", p0 ? " + " : "", dn,
+                         bit_depth, with_std ? 1 : 0);
+        if (w < 0 || w >= buf_len - used) break;                                  // (cut short: snprintf has terminated what fitted)
+        used += w;
+    }
 }
 
 }  // namespace hm_rules

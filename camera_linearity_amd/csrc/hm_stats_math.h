@@ -1,4 +1,4 @@
-// hm_stats_math.h - the element rules of the histograms and of the kernel density estimate, one text for the device units
+// hm_stats_math.h - the element rules of the histograms, of the kernel density estimate and of the per-DN table of hm_pairs_statistics_dn, one text for the device units
 // (hm_stats_hist.hip, hm_kde.hip) and ../csrc_host/hm_host.cpp. np.histogram with `bins` equal-width bins on [lo, hi] (compute_channel_histogram, modules/measurand.py:430-469): the bin of x is
 // int((x - lo) * bins / (hi - lo)), corrected against the actual edges (np.linspace(lo, hi, bins + 1), passed in by the caller) exactly as
 // numpy/lib/_histograms_impl.py does, the right edge inclusive. Non-finite values are skipped (:453); with weights, elements whose std is 0
@@ -44,6 +44,18 @@ HM_MATH_FN bool kde_load(const double* __restrict__ val, const double* __restric
     bool ok = isfinite(x);
     if (std_) { const double s = std_[e]; ok = ok && s != 0.0; w = 1.0 / s; }
     return ok;
+}
+
+// hm_pairs_statistics_dn: the thresholded table entry at = idx * C + c of a DN frame. apply_thresholds (modules/measurand.py:375-428) decides
+// on the value for the value and its std (a NaN compares false and stays); the std is measurand.py:512 on calculate_numerical_STD's std
+HM_MATH_FN void pairs_dn_entry(const double* icrf, const double* icrf_diff, const double* std_table, int64_t at, double lo, double hi,
+                               double& v, double& s) {
+    v = icrf[at];
+    s = std_table ? icrf_diff[at] * std_table[at] : 0.0;
+    if (v < lo || v > hi) {
+        v = __builtin_nan("");
+        if (std_table) s = __builtin_nan("");
+    }
 }
 
 }  // namespace hm

@@ -31,4 +31,7 @@ inline void pairs_dist_fill(PairsK& k, const double* const* vals, const double* 
     }
 }
 
+// one workgroup per (pair, difference kind, channel) folds partial[block][pair][channel][kind] of `nblocks` blocks into out (hm_stats.hip)
+void launch_pairs_final(const double* partial, int nblocks, int n_pairs, int C, int weighted, double* out, hipStream_t st);
+
 }  // namespace hm

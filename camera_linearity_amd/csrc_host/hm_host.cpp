@@ -867,6 +867,62 @@ int hm_pairs_statistics(const double* const* vals, const double* const* stds, in
     return HM_OK;
 }
 
+// The same statistics straight from uint8 / uint16 DN frames: the thresholded per-(DN, channel) table first (pairs_dn_entry, the device
+// build's formula), then hm_pair_statistics' loops on the mapped values. The frames are never written. `variant` places the table on the
+// device; here it is only checked.
+size_t hm_pairs_statistics_dn_workspace_bytes(int, int, int) { return 64; }
+int hm_pairs_statistics_dn(const void* const* frames, int n_frames, int bit_depth, const double* icrf, const double* icrf_diff,
+                           const double* std_table, const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                           int64_t n, int C, const double* lower, const double* upper, int variant, double* out, void* workspace, void*) {
+    const int rc = hm_rules::check_pairs_dn(frames, n_frames, bit_depth, icrf, icrf_diff, std_table, pair_i, pair_j, multipliers, n_pairs, n, C,
+                                            lower, upper, variant, out, workspace);
+    if (rc != HM_OK) return rc;
+    const bool with_std = std_table != nullptr;
+    const int64_t entries = (int64_t{1} << bit_depth) * C;
+    std::vector<double> tv(static_cast<size_t>(entries)), ts(static_cast<size_t>(with_std ? entries : 0));
+    for (int64_t at = 0; at < entries; ++at) {
+        const int c = static_cast<int>(at % C);
+        double v, s;
+        hm::pairs_dn_entry(icrf, icrf_diff, std_table, at, lower ? lower[c] : -kInf, upper ? upper[c] : kInf, v, s);
+        tv[static_cast<size_t>(at)] = v;
+        if (with_std) ts[static_cast<size_t>(at)] = s;
+    }
+    const uint32_t mask = (1u << bit_depth) - 1u;
+    auto index = [&](const void* f, int64_t e) -> size_t {
+        const uint32_t dn = bit_depth == 8 ? static_cast<const uint8_t*>(f)[e] : (static_cast<const uint16_t*>(f)[e] & mask);
+        return static_cast<size_t>(dn) * C + static_cast<size_t>(e % C);
+    };
+    const int64_t A = n / C;
+#pragma omp parallel for schedule(dynamic) collapse(2)
+    for (int p = 0; p < n_pairs; ++p)
+        for (int hc = 0; hc < 2 * C; ++hc) {
+            const int h = hc / C, c = hc % C;
+            const void* fx = frames[pair_i[p]];
+            const void* fy = frames[pair_j[p]];
+            double mean, sd, err;
+            line_statistics(A, with_std, [&](int64_t k, double& v, double& u) {
+                const int64_t e = k * C + c;
+                const size_t ax = index(fx, e), ay = index(fy, e);
+                double a, as = 0.0, r, rs = 0.0;
+                diff_terms(tv[ax], tv[ay], with_std ? ts[ax] : 0.0, with_std ? ts[ay] : 0.0, multipliers[p], with_std, a, r, as, rs);
+                v = h == 0 ? a : r; u = h == 0 ? as : rs;
+            }, mean, sd, err);
+            double* o = out + static_cast<int64_t>(p) * 6 * C + 3 * C * h;
+            o[c] = mean; o[C + c] = sd; o[2 * C + c] = err;
+        }
+    return HM_OK;
+}
+
+int hm_pairs_statistics_dn_describe(int64_t n, int n_frames, int n_pairs, int C, int with_std, int bit_depth, int variant, int, char* buf,
+                                    int buf_len) {
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    buf[0] = '\0';
+    const int rc = hm_rules::check_pairs_dn_counts(n_frames, n_pairs, n, C, with_std != 0, bit_depth, variant);
+    if (rc != HM_OK) return rc;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "host_pairs_stats_dn<dn=%s,bits=%d,std=%d>", bit_depth == 8 ? "u8" : "u16", bit_depth, with_std != 0);
+    return HM_OK;
+}
+
 size_t hm_histogram_workspace_bytes(int, int) { return 64; }
 int hm_channel_minmax(const double* val, const double* std_, int64_t n, int C, double* out, void*, void*) {
     if (n < 1 || C < 1 || C > HM_MAX_CHANNELS || !val || !out) return HM_EINVAL;

@@ -994,6 +994,104 @@ def pairs_statistics(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch
     return res
 
 
+class PairsDnPlan:
+    """One hm_pairs_statistics_dn call with everything it reads and writes: the DN frames, the tables, the pair arrays, the output and the
+    workspace. launch() only enqueues (the table kernel, the statistics kernels, the final fold), so a PlanGraph can record it; the
+    statistics are in `outputs["stats"]` (n_pairs * 6C float64) after the stream has run."""
+
+    def __init__(self, frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, thresholds=None,
+                 bit_depth: Optional[int] = None, variant: int = 0):
+        frames = list(frames)
+        if not frames:
+            raise ValueError("pairs_statistics_dn needs at least one frame")
+        for i, f in enumerate(frames):
+            _require_cuda(f, f"frames[{i}]")
+        first = frames[0]
+        if first.dtype not in (_U8, _U16):
+            raise ValueError(f"pairs_statistics_dn takes torch.uint8 or torch.uint16 DN frames, got {first.dtype}")
+        if any(f.dtype != first.dtype or f.shape != first.shape or f.device != first.device for f in frames):
+            raise ValueError("pairs_statistics_dn needs DN frames of one dtype and one shape on one device")
+        self.bit_depth = 8 if _welford_bit_depth(first.dtype, bit_depth) is None else int(bit_depth)
+        if std_table is not None and icrf_diff is None:
+            raise ValueError("std_table needs icrf_diff: the std of a DN is ICRF_diff * STD_table")
+        dev = first.device
+        Cc = first.shape[-1] if first.dim() > 0 else 1
+        rows = 2 ** self.bit_depth
+        self.tables = []
+        for name, t in (("ICRF", icrf), ("ICRF_diff", icrf_diff), ("std_table", std_table)):
+            t = None if t is None else _dev_f64(t, dev)
+            if t is not None and tuple(t.shape) != (rows, Cc):
+                raise ValueError(f"{name} must be shaped ({rows}, {Cc}), got {tuple(t.shape)}")
+            self.tables.append(t)
+        self.lo = self.hi = None
+        if thresholds is not None:
+            if len(thresholds[0]) != Cc or len(thresholds[1]) != Cc:
+                raise ValueError("The length of 'lower' and 'upper' must match the size of the independent axis.")
+            self.lo = (C.c_double * Cc)(*[float(x) for x in thresholds[0]])
+            self.hi = (C.c_double * Cc)(*[float(x) for x in thresholds[1]])
+        self.frames = [f.contiguous() for f in frames]
+        self.n_pairs = P = len(pairs)
+        self.channels = Cc
+        self.weighted = std_table is not None
+        self.variant = int(variant)
+        self.device = dev
+        self.host = dev.type != "cuda"
+        self._fp = _ptr_array(self.frames)
+        self._pi = (C.c_int32 * P)(*[int(p[0]) for p in pairs])
+        self._pj = (C.c_int32 * P)(*[int(p[1]) for p in pairs])
+        self._pm = (C.c_double * P)(*[float(p[2]) for p in pairs])
+        self.outputs = {"stats": torch.empty(P * 6 * Cc, dtype=_F64, device=dev)}
+        self._ws = torch.empty(max(1, (nat.lib.hm_pairs_statistics_dn_workspace_bytes(P, Cc, self.bit_depth) + 7) // 8), dtype=_F64, device=dev)
+
+    def launch(self, stream: Optional[int] = None) -> None:
+        icrf, diff, table = self.tables
+        with _on(self.device):
+            nat.check(nat.lib.hm_pairs_statistics_dn(C.cast(self._fp, C.POINTER(C.c_void_p)), len(self.frames), self.bit_depth, icrf.data_ptr(),
+                                                     nat.ptr(diff), nat.ptr(table), self._pi, self._pj, self._pm, self.n_pairs,
+                                                     self.frames[0].numel(), self.channels, self.lo, self.hi, self.variant,
+                                                     self.outputs["stats"].data_ptr(), self._ws.data_ptr(),
+                                                     _stream(self.device) if stream is None else stream), "hm_pairs_statistics_dn")
+
+    def kernels(self) -> str:
+        aligned = all(f.data_ptr() % (2 if self.bit_depth == 8 else 4) == 0 for f in self.frames)
+        return pairs_statistics_dn_kernel(self.frames[0].numel(), len(self.frames), self.n_pairs, self.channels, self.weighted, self.bit_depth,
+                                          self.variant, aligned)
+
+
+def pairs_statistics_dn(frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, thresholds=None,
+                        bit_depth: Optional[int] = None, to_host: bool = False, variant: int = 0):
+    """pairs_statistics() straight from DN frames (hm_pairs_statistics_dn): torch.uint8 frames, or torch.uint16 frames with `bit_depth` in
+    9..16. Element e of a frame, channel c, idx = DN & (2**bit_depth - 1) stands for the value icrf[idx, c] and - with `std_table`, the
+    weighted statistics - the std icrf_diff[idx, c] * std_table[idx, c]; thresholds = (lower, upper) exclude a value outside its channel's
+    limits together with its std (apply_thresholds). The tables are (2**bit_depth, C). The frames are not modified and no float64 frame
+    is written. `variant`: 0 the library's choice, 1 the table in LDS, 2 gathered from global memory, -1 the per-wave kernel; the result
+    does not depend on it. Returns what pairs_statistics returns."""
+    plan = PairsDnPlan(frames, pairs, icrf, icrf_diff, std_table, thresholds, bit_depth, variant)
+    plan.launch()
+    out = plan.outputs["stats"]
+    Cc, w = plan.channels, plan.weighted
+    if to_host:
+        out = out.cpu()                                   # one device-to-host copy for all pairs (P * 6C numbers)
+    res = []
+    for p in range(plan.n_pairs):
+        b = p * 6 * Cc
+        mk = lambda o: {"mean": out[o:o + Cc], "std": out[o + Cc:o + 2 * Cc], "error": out[o + 2 * Cc:o + 3 * Cc] if w else None}   # noqa: E731
+        res.append((mk(b), mk(b + 3 * Cc)))
+    return res
+
+
+def pairs_statistics_dn_kernel(n_elems: int, n_frames: int, n_pairs: int, channels: int, with_std: bool, bit_depth: int, variant: int = 0,
+                               frames_aligned: bool = True) -> str:
+    """The statistics kernel of each launch of such a pairs_statistics_dn call, as hm_pairs_statistics_dn_describe names them (e.g.
+    "pairs_stats_dn_lds<dn=u16,bits=12,tab=global,std=1,ni=1>"); nothing is launched. frames_aligned: every frame 2-byte (uint8) or
+    4-byte (uint16) aligned. For tests and benchmarks."""
+    buf = C.create_string_buffer(512)
+    nat.check(nat.lib.hm_pairs_statistics_dn_describe(int(n_elems), int(n_frames), int(n_pairs), int(channels), int(bool(with_std)),
+                                                      int(bit_depth), int(variant), int(bool(frames_aligned)), buf, len(buf)),
+              "hm_pairs_statistics_dn_describe")
+    return buf.value.decode()
+
+
 def channel_minmax(val: torch.Tensor) -> np.ndarray:
     """(C, 2) host array: min and max of the finite values of each channel of a (..., C) float64 tensor (hm_channel_minmax; a channel
     without finite values gives (+inf, -inf)). One read-back of 2C doubles."""

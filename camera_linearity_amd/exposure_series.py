@@ -343,7 +343,15 @@ class ExposureSeries(object):
                                                             use_std=use_std, out_dtype=out_dtype, STD_data=STD_data)
 
     # ---- linearity statistics (exposure_series.py:421-476; "next" row f-1)
-    def process_linearity(self, ICRF, linearity_limit: Optional[int] = None, use_std: Optional[bool] = False):
+    def process_linearity(self, ICRF, linearity_limit: Optional[int] = None, use_std: Optional[bool] = False, *,
+                          from_dn: bool = False, ICRF_diff=None, STD_data=None):
+        """exposure_series.py:421-446 on a linearized series. from_dn=True (an addition) takes a series that still holds its 8-bit frames
+        as DNs (from_dn measurands) and gives its pairs the statistics that self.linearize(ICRF, ICRF_diff) followed by
+        process_linearity(ICRF, linearity_limit, use_std) would give them - with use_std the stds ICRF_diff * calculate_numerical_STD(
+        STD_data) - in one hm_pairs_statistics_dn call: no float64 frame is written and the image sets stay DN frames. See
+        _process_linearity_from_dn for what it asks of the series."""
+        if from_dn:
+            return self._process_linearity_from_dn(ICRF, linearity_limit, use_std, ICRF_diff, STD_data)
         lower, upper = map_linearity_limits(linearity_limit, linearity_limit, ICRF)
         for image_set in self.input_image_sets:
             if image_set.measurand.shape is None:
@@ -369,6 +377,19 @@ class ExposureSeries(object):
         """(vals, stds or None, [(i, j, exposure ratio), ...]) when one all-pairs launch can serve this series: the pairs are pairs of the
         series' own images, all images share one (H, W, C <= 4) shape on one device and one backend and either all or none of them carry a
         std. None otherwise."""
+        pairs = self._own_pairs()
+        if pairs is None:
+            return None
+        sets = self.input_image_sets
+        vals = [s.measurand._f64() for s in sets]
+        if not all(v.device == vals[0].device for v in vals):
+            return None
+        stds = [s.measurand._std for s in sets] if sets[0].measurand._std is not None else None
+        return vals, stds, pairs
+
+    def _own_pairs(self):
+        """[(i, j, exposure ratio), ...] under _own_pairs_stack's conditions on the pairs, shapes, stds and backends - no pixel is touched
+        (the devices are the caller's to compare on the tensors it takes). None otherwise."""
         sets = self.input_image_sets
         if not self.exposure_pairs or not sets or len(sets) > nat.HM_MAX_FRAMES:      # (hm_pairs_statistics takes no more on either build)
             return None
@@ -379,14 +400,50 @@ class ExposureSeries(object):
         if len(shapes) != 1 or None in shapes or len(next(iter(shapes))) != 3 or next(iter(shapes))[-1] > 4:
             return None
         have_std = [s.measurand._std is not None for s in sets]
-        if any(have_std) != all(have_std):
+        if any(have_std) != all(have_std) or len({s.measurand.backend for s in sets}) != 1:
             return None
-        vals = [s.measurand._f64() for s in sets]
-        if not all(v.device == vals[0].device for v in vals) or len({s.measurand.backend for s in sets}) != 1:
-            return None
-        stds = [s.measurand._std for s in sets] if all(have_std) else None
-        pairs = [(index[id(p.short_exposure)], index[id(p.long_exposure)], p.exposure_ratio) for p in self.exposure_pairs]
-        return vals, stds, pairs
+        return [(index[id(p.short_exposure)], index[id(p.long_exposure)], p.exposure_ratio) for p in self.exposure_pairs]
+
+    def _process_linearity_from_dn(self, ICRF, linearity_limit, use_std, ICRF_diff, STD_data):
+        """process_linearity(from_dn=True): every image set holds a from_dn measurand (uint8 DNs) without a std frame, and the conditions
+        of _own_pairs_stack hold (the pairs are pairs of the series' own images, one (H, W, C <= 4) shape, one device, one backend);
+        ValueError otherwise. use_std needs ICRF_diff and a per-DN STD table (STD_data, or settings.STD_FILE_NAME). (BITS,) tables serve
+        every channel, as they do in linearize and calculate_numerical_STD."""
+        lower, upper = map_linearity_limits(linearity_limit, linearity_limit, ICRF)
+        sets = self.input_image_sets
+        for image_set in sets:
+            if image_set.measurand.shape is None:
+                image_set.load_value_image()
+        if not sets or any(s.measurand._dn is None for s in sets):
+            raise ValueError("from_dn=True needs every image set to hold a from_dn measurand (8-bit DNs); linearize the series and call "
+                             "process_linearity(ICRF, linearity_limit, use_std) instead")
+        if any(s.measurand._std is not None for s in sets):
+            raise ValueError("from_dn=True takes its stds from the per-DN STD table; a series whose images carry std frames goes the default "
+                             "route: series.linearize(ICRF, ICRF_diff).process_linearity(ICRF, linearity_limit, use_std)")
+        pairs = self._own_pairs()
+        dns = [s.measurand._dn for s in sets]
+        if pairs is None or not all(d.device == dns[0].device for d in dns):
+            raise ValueError("from_dn=True needs the pairs to be pairs of the series' own images, all of one (H, W, C <= 4) shape on one "
+                             "device and one backend")
+        n_ch = dns[0].shape[-1]
+        if len(lower) != n_ch or len(upper) != n_ch:
+            raise ValueError("The length of 'lower' and 'upper' must match the size of the independent axis.")
+
+        def table(t):                                          # (BITS, C), a (BITS,) column repeated for every channel
+            t = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+            return np.repeat(t[:, None], n_ch, axis=1) if t.ndim == 1 else t
+        diff = std_table = None
+        if use_std:
+            if STD_data is None:
+                STD_data = read_STD_file()
+            if ICRF_diff is None or STD_data is None:
+                raise ValueError("use_std=True with from_dn=True needs ICRF_diff and STD_data (or settings.STD_FILE_NAME)")
+            diff, std_table = table(ICRF_diff), table(STD_data)
+        exp = sets[0].measurand._export
+        stats = self._eng().pairs_statistics_dn(dns, pairs, table(ICRF), diff, std_table, thresholds=(lower, upper), to_host=True)
+        for p, (ab, rel) in zip(self.exposure_pairs, stats):
+            p.absolute_stats, p.relative_stats = {k: exp(v) for k, v in ab.items()}, {k: exp(v) for k, v in rel.items()}
+            p.absolute_difference = p.relative_difference = None
 
     def _all_pairs_fused(self, lower=None, upper=None) -> bool:
         """Every pair of the series in ONE launch (hm_pairs_statistics): each frame is read from HBM once instead of once per

@@ -448,6 +448,38 @@ int hm_pairs_statistics(const double* const* vals, const double* const* stds /*n
                         const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
                         int64_t n, int C, const double* lower /*nullable*/, const double* upper /*nullable*/,
                         double* out /*n_pairs * 6C*/, void* workspace, void* stream);
+/* hm_pairs_statistics_dn: the same statistics straight from DN frames, without float64 value and std frames in memory. frames: [host] array
+ * of n_frames device pointers to uint8 frames (bit_depth 8) or uint16 frames (bit_depth 9..16). For element e of a frame, channel
+ * c = e % C and idx = DN & (2^bit_depth - 1):
+ *     v = icrf[idx * C + c]
+ *     s = icrf_diff[idx * C + c] * std_table[idx * C + c]         (only with a std_table: the weighted statistics)
+ *     with lower / upper: v < lower[c] or v > upper[c] makes v (and s) NaN       (apply_thresholds, modules/measurand.py:375-428)
+ * and the six statistics per pair and channel are hm_pairs_statistics' on these values: out as there, error NaN without a std_table, the
+ * same bits as hm_pairs_statistics gives on frames hm_linearize_u8 / hm_linearize_u16 wrote. icrf, icrf_diff (nullable), std_table
+ * (nullable; needs icrf_diff): device, (2^bit_depth, C) float64. The frames are NOT modified.
+ * A small kernel writes the thresholded table into the workspace first; nothing is allocated and nothing synchronises (capturable).
+ * variant: 0 the library's choice; 1 the staged kernel keeps the table in LDS beside its three stages; 2 it gathers from the workspace
+ * table in global memory; -1 the per-wave kernel without staging for every launch. The staged kernel takes a launch (HM_PAIRS_MAX pairs)
+ * when every frame is item-aligned (uint8: 2 bytes, uint16: 4 bytes), n_frames * 64 <= 2 * 64 * pairs and there are at most 21 streams
+ * (n_frames, doubled with a std_table); the per-wave kernel takes every other launch, whatever the variant. Variant 0 puts the table in
+ * LDS where table bytes (8 or 16 * 2^bit_depth * C) + 63 KiB <= 160 KiB.
+ * Statuses, an earlier one winning: HM_EINVAL for hm_pairs_statistics' own rules (NULLs, n < 1, n % C, C, n_frames outside
+ * 1..HM_MAX_FRAMES, n_pairs < 1, lower without upper), bit_depth outside 8..16, variant outside -1..2, std_table without icrf_diff, a NULL
+ * frame; HM_EALIGN for a table that is not 8-byte aligned, then for a uint16 frame that is not 2-byte aligned; HM_EINVAL for a pair index
+ * outside the frames; HM_EUNSUPPORTED for variant 1 with a table that does not fit. Every one returns before anything is launched or written.
+ * hm_pairs_statistics_dn_describe writes the statistics kernel of each launch, joined by " + ", e.g.
+ * "pairs_stats_dn_lds<dn=u16,bits=12,tab=global,std=1,ni=1>" or "pairs_stats_dn_wave<dn=u8,bits=8,std=0>" (the host build: a host name),
+ * and launches nothing; frames_aligned: whether every frame is item-aligned. The statuses above that look at no pointer; HM_EINVAL for a
+ * NULL or empty buf. */
+size_t hm_pairs_statistics_dn_workspace_bytes(int n_pairs, int C, int bit_depth);
+int hm_pairs_statistics_dn(const void* const* frames /*[host] n_frames device ptrs: uint8 (bit_depth 8) or uint16 (9..16)*/,
+                           int n_frames, int bit_depth, const double* icrf, const double* icrf_diff /*nullable*/,
+                           const double* std_table /*nullable; needs icrf_diff*/,
+                           const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                           int64_t n, int C, const double* lower /*nullable*/, const double* upper /*nullable*/, int variant,
+                           double* out /*n_pairs * 6C*/, void* workspace, void* stream);
+int hm_pairs_statistics_dn_describe(int64_t n, int n_frames, int n_pairs, int C, int with_std, int bit_depth, int variant,
+                                    int frames_aligned, char* buf, int buf_len);
 /* hm_channel_histogram: compute_channel_histogram (modules/measurand.py:430-469) = np.histogram per channel on
  * [lo, hi] with `bins` equal-width bins (edges = np.linspace(lo, hi, bins + 1) on the device), non-finite values
  * skipped, optional weights 1/std with zero stds skipped. out is (C, bins) float64; channels not in
