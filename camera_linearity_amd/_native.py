@@ -138,6 +138,18 @@ _SIGNATURES = {
     "hm_pairs_histogram": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same from DN frames: frames, n_frames, bit_depth, icrf, icrf_diff, std_table, pair_i, pair_j, multipliers, n_pairs, n, C,
+    # [channel_mask,] lower, upper (HOST arrays: typed), [edges, bins,] variant, out, workspace, stream
+    "hm_pairs_histogram_dn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hm_pairs_minmax_dn": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hm_pairs_histogram_dn": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, C.c_int,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "hm_pairs_histogram_dn_describe": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_char), C.c_int]),
     "hm_channel_statistics_workspace_bytes": (C.c_size_t, []),
     "hm_channel_statistics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_axis_statistics_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),

@@ -20,18 +20,6 @@
 
 namespace hm {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-struct PairsDnK {
-    const void* frame[HM_MAX_FRAMES];
-    int32_t pi[HM_PAIRS_MAX], pj[HM_PAIRS_MAX];
-    double mult[HM_PAIRS_MAX];
-    const void* table;                  // entry idx * C + c: {v, s} with stds, v without; thresholds folded in
-    int64_t n;
-    int32_t C, n_pairs, n_frames;
-    uint32_t mask, table_bytes;
-};
-
 struct DnLimits { double lo[HM_MAX_CHANNELS], hi[HM_MAX_CHANNELS]; };
 
 template <bool STD>
@@ -47,18 +35,6 @@ __global__ __launch_bounds__(256) void k_pairs_dn_table(const double* __restrict
     pairs_dn_entry(icrf, icrf_diff, STD ? std_table : nullptr, i, lo, hi, v, s);
     if constexpr (STD) static_cast<f64x2*>(table)[i] = f64x2{v, s};
     else static_cast<double*>(table)[i] = v;
-}
-
-// entry `at` of a table at `tab` (global memory, or the LDS copy: the caller's pointer carries the address space)
-template <bool STD, class P>
-__device__ __forceinline__ void dn_entry(P tab, uint32_t at, double& v, double& s) {
-    if constexpr (STD) {
-        const f64x2 e = *reinterpret_cast<const f64x2*>(tab + at * 16u);
-        v = e.x; s = e.y;
-    } else {
-        v = *reinterpret_cast<const double*>(tab + at * 8u);
-        s = 0.0;
-    }
 }
 
 // element q of a frame through the workspace table: what the per-wave loop and the tail read
@@ -271,6 +247,18 @@ static int pairs_dn_lds_limit() {
     return status;
 }
 
+void launch_pairs_dn_table(const double* icrf, const double* icrf_diff, const double* std_table, const double* lower, const double* upper,
+                           int bit_depth, int C, void* table, hipStream_t st) {
+    DnLimits lim{};
+    for (int c = 0; c < HM_MAX_CHANNELS; ++c) {
+        lim.lo[c] = (lower && c < C) ? lower[c] : -__builtin_huge_val();
+        lim.hi[c] = (upper && c < C) ? upper[c] : __builtin_huge_val();
+    }
+    const int entries = (1 << bit_depth) * C;
+    if (std_table) hipLaunchKernelGGL(k_pairs_dn_table<true>, dim3((entries + 255) / 256), dim3(256), 0, st, icrf, icrf_diff, std_table, lim, entries, C, table);
+    else hipLaunchKernelGGL(k_pairs_dn_table<false>, dim3((entries + 255) / 256), dim3(256), 0, st, icrf, icrf_diff, std_table, lim, entries, C, table);
+}
+
 }  // namespace hm
 
 using namespace hm;
@@ -301,21 +289,10 @@ extern "C" int hm_pairs_statistics_dn(const void* const* frames, int n_frames, i
         if (const int lrc = pairs_dn_lds_limit(); lrc != HM_OK) return lrc;
     hipStream_t st = as_stream(stream);
     double* partial = static_cast<double*>(workspace);
-    char* table = static_cast<char*>(workspace) + hm_pairs_statistics_workspace_bytes(n_pairs);
-    table += (16 - (reinterpret_cast<uintptr_t>(table) & 15u)) & 15u;
-    DnLimits lim{};
-    for (int c = 0; c < HM_MAX_CHANNELS; ++c) {
-        lim.lo[c] = (lower && c < C) ? lower[c] : -__builtin_huge_val();
-        lim.hi[c] = (upper && c < C) ? upper[c] : __builtin_huge_val();
-    }
-    const int entries = (1 << bit_depth) * C;
-    if (with_std) hipLaunchKernelGGL(k_pairs_dn_table<true>, dim3((entries + 255) / 256), dim3(256), 0, st, icrf, icrf_diff, std_table, lim, entries, C, table);
-    else hipLaunchKernelGGL(k_pairs_dn_table<false>, dim3((entries + 255) / 256), dim3(256), 0, st, icrf, icrf_diff, std_table, lim, entries, C, table);
+    char* table = pairs_dn_table_at(workspace, hm_pairs_statistics_workspace_bytes(n_pairs));
+    launch_pairs_dn_table(icrf, icrf_diff, std_table, lower, upper, bit_depth, C, table, st);
     PairsDnK k{};
-    for (int i = 0; i < n_frames; ++i) k.frame[i] = frames[i];
-    k.table = table; k.n = n; k.C = C; k.n_frames = n_frames;
-    k.mask = (1u << bit_depth) - 1u;
-    k.table_bytes = static_cast<uint32_t>(pairs_dn_table_bytes(bit_depth, C, with_std));
+    pairs_dn_fill(k, frames, n_frames, bit_depth, with_std, n, C, table);
     const int grid = stat_grid(n, 64);
     for (int p0 = 0; p0 < n_pairs; p0 += HM_PAIRS_MAX) {                 // HM_PAIRS_MAX pairs (waves of a workgroup) per launch
         const int np = n_pairs - p0 < HM_PAIRS_MAX ? n_pairs - p0 : HM_PAIRS_MAX;

@@ -2,7 +2,8 @@
 // k_pair_stats, k_pairs_stats, k_pairs_stats_lds) and on DN frames (hm_stats_dn.hip) share: the difference terms of one element, a wave's
 // iteration over its chunks (whole: pair_process_any; partial: pair_tail_with). Where an operand comes from -
 // a float64 frame, an LDS stage, a per-DN table - is the caller's business: the arithmetic, the fold points and the element order are
-// here, once, so that every kernel built on them gives the same bits for the same operand values.
+// here, once, so that every kernel built on them gives the same bits for the same operand values. At the end: the read of one entry of
+// the per-DN table, shared by the units that read DN frames (hm_stats_dn.hip, hm_stats_hist_dn.hip).
 #pragma once
 #include "hm_moments.h"
 
@@ -114,6 +115,21 @@ __device__ __forceinline__ void pair_tail_with(MomAcc (&st)[2], int it, int64_t 
     }
     mine[0] = acc_finish<true>(st[0], STD);
     mine[1] = acc_finish<true>(st[1], STD);
+}
+
+// ---- the per-DN table of the entries that read DN frames (hm_stats_dn.hip, hm_stats_hist_dn.hip) ----
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// entry `at` of a table at `tab` (global memory, or the LDS copy: the caller's pointer carries the address space)
+template <bool STD, class P>
+__device__ __forceinline__ void dn_entry(P tab, uint32_t at, double& v, double& s) {
+    if constexpr (STD) {
+        const f64x2 e = *reinterpret_cast<const f64x2*>(tab + at * 16u);
+        v = e.x; s = e.y;
+    } else {
+        v = *reinterpret_cast<const double*>(tab + at * 8u);
+        s = 0.0;
+    }
 }
 
 }  // namespace hm

@@ -956,7 +956,9 @@ int hm_channel_histogram(const double* val, const double* std_, int64_t n, int C
 }
 
 // ---- distributions of all exposure pairs (hm_pairs_minmax / hm_pairs_histogram): the difference terms of diff_terms() on the values as
-// read through the thresholds, hm_channel_minmax's / hm_channel_histogram's counting rule, weighted sums added in index order
+// read through the thresholds, hm_channel_minmax's / hm_channel_histogram's counting rule, weighted sums added in index order. The same
+// loops serve hm_pairs_minmax_dn / hm_pairs_histogram_dn on the values a thresholded per-(DN, channel) table maps the DN frames to.
+}  // extern "C" (the loops are templates over the element source)
 namespace {
 // element e of pair (x, y): loaded, thresholded as read (a value outside its channel's limits is NaN with its std), differenced
 struct PairElems {
@@ -974,18 +976,43 @@ struct PairElems {
         diff_terms(xv, yv, xs, ys, mult, sx != nullptr, a, r, as, rs);
     }
 };
-}  // namespace
 
-size_t hm_pairs_histogram_workspace_bytes(int, int, int) { return 64; }
-int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
-                    const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
-                    void* workspace, void*) {
-    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
-    if (rc != HM_OK) return rc;
+// The thresholded table of the DN entries (pairs_dn_entry, the device build's formula) and element e of a pair of DN frames through it.
+struct PairsDnTable {
+    std::vector<double> tv, ts;
+    int bit_depth, C; bool with_std; uint32_t mask;
+    PairsDnTable(const double* icrf, const double* icrf_diff, const double* std_table, const double* lower, const double* upper, int bit_depth_,
+                 int C_) : bit_depth(bit_depth_), C(C_), with_std(std_table != nullptr), mask((1u << bit_depth_) - 1u) {
+        const int64_t entries = (int64_t{1} << bit_depth) * C;
+        tv.resize(static_cast<size_t>(entries)); ts.resize(static_cast<size_t>(with_std ? entries : 0));
+        for (int64_t at = 0; at < entries; ++at) {
+            const int c = static_cast<int>(at % C);
+            double v, s;
+            hm::pairs_dn_entry(icrf, icrf_diff, std_table, at, lower ? lower[c] : -kInf, upper ? upper[c] : kInf, v, s);
+            tv[static_cast<size_t>(at)] = v;
+            if (with_std) ts[static_cast<size_t>(at)] = s;
+        }
+    }
+    size_t index(const void* f, int64_t e) const {
+        const uint32_t dn = bit_depth == 8 ? static_cast<const uint8_t*>(f)[e] : (static_cast<const uint16_t*>(f)[e] & mask);
+        return static_cast<size_t>(dn) * C + static_cast<size_t>(e % C);
+    }
+};
+struct PairDnElems {
+    const PairsDnTable* t; const void* fx; const void* fy; double mult;
+    void at(int64_t e, double& a, double& as, double& r, double& rs) const {
+        const size_t ax = t->index(fx, e), ay = t->index(fy, e);
+        as = 0.0; rs = 0.0;
+        diff_terms(t->tv[ax], t->tv[ay], t->with_std ? t->ts[ax] : 0.0, t->with_std ? t->ts[ay] : 0.0, mult, t->with_std, a, r, as, rs);
+    }
+};
+
+// pair(p) -> the element source of pair p (PairElems, PairDnElems)
+template <class Pair>
+void pairs_minmax_loop(Pair pair, int n_pairs, int64_t n, int C, bool weighted, double* out) {
 #pragma omp parallel for schedule(dynamic)
     for (int p = 0; p < n_pairs; ++p) {
-        const PairElems pe{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
-                           multipliers[p], C};
+        const auto pe = pair(p);
         double* o = out + static_cast<int64_t>(p) * 2 * C * 2;
         for (int i = 0; i < 2 * C; ++i) { o[2 * i] = kInf; o[2 * i + 1] = -kInf; }
         for (int64_t e = 0; e < n; ++e) {
@@ -994,24 +1021,18 @@ int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_
             const int c = static_cast<int>(e % C);
             for (int k = 0; k < 2; ++k) {
                 if (!hist_finite(v[k])) continue;
-                if (stds && s[k] == 0.0) continue;
+                if (weighted && s[k] == 0.0) continue;
                 double* m = o + (k * C + c) * 2;
                 m[0] = std::fmin(m[0], v[k]); m[1] = std::fmax(m[1], v[k]);
             }
         }
     }
-    return HM_OK;
 }
-int hm_pairs_histogram(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
-                       const double* multipliers, int n_pairs, int64_t n, int C, int channel_mask, const double* lower, const double* upper,
-                       const double* edges, int bins, double* out, void* workspace, void*) {
-    const int rc = hm_rules::check_pairs_histogram(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, channel_mask, lower, upper,
-                                                   edges, bins, out, workspace);
-    if (rc != HM_OK) return rc;
+template <class Pair>
+void pairs_histogram_loop(Pair pair, int n_pairs, int64_t n, int C, int channel_mask, bool weighted, const double* edges, int bins, double* out) {
 #pragma omp parallel for schedule(dynamic)
     for (int p = 0; p < n_pairs; ++p) {
-        const PairElems pe{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
-                           multipliers[p], C};
+        const auto pe = pair(p);
         double* o = out + static_cast<int64_t>(p) * 2 * C * bins;
         const double* eg = edges + static_cast<int64_t>(p) * 2 * C * (bins + 1);
         for (int64_t i = 0; i < int64_t{2} * C * bins; ++i) o[i] = 0.0;
@@ -1027,12 +1048,73 @@ int hm_pairs_histogram(const double* const* vals, const double* const* stds, int
                 if (!(hi > lo)) continue;                                                                 // (hm_channel_histogram: HM_EINVAL)
                 if (!hist_finite(x)) continue;
                 double w = 1.0;
-                if (stds && !hist_weight(s[k], w)) continue;
+                if (weighted && !hist_weight(s[k], w)) continue;
                 if (!hist_in_range(x, lo, hi)) continue;
                 o[static_cast<int64_t>(k * C + c) * bins + hist_bin_bounded(x, lo, static_cast<double>(bins) / (hi - lo), ek, bins)] += w;
             }
         }
     }
+}
+}  // namespace
+extern "C" {
+
+size_t hm_pairs_histogram_workspace_bytes(int, int, int) { return 64; }
+int hm_pairs_minmax(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
+                    const double* multipliers, int n_pairs, int64_t n, int C, const double* lower, const double* upper, double* out,
+                    void* workspace, void*) {
+    const int rc = hm_rules::check_pairs(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, lower, upper, out, workspace);
+    if (rc != HM_OK) return rc;
+    pairs_minmax_loop([&](int p) {
+        return PairElems{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
+                         multipliers[p], C};
+    }, n_pairs, n, C, stds != nullptr, out);
+    return HM_OK;
+}
+int hm_pairs_histogram(const double* const* vals, const double* const* stds, int n_frames, const int32_t* pair_i, const int32_t* pair_j,
+                       const double* multipliers, int n_pairs, int64_t n, int C, int channel_mask, const double* lower, const double* upper,
+                       const double* edges, int bins, double* out, void* workspace, void*) {
+    const int rc = hm_rules::check_pairs_histogram(vals, stds, n_frames, pair_i, pair_j, multipliers, n_pairs, n, C, channel_mask, lower, upper,
+                                                   edges, bins, out, workspace);
+    if (rc != HM_OK) return rc;
+    pairs_histogram_loop([&](int p) {
+        return PairElems{vals[pair_i[p]], stds ? stds[pair_i[p]] : nullptr, vals[pair_j[p]], stds ? stds[pair_j[p]] : nullptr, lower, upper,
+                         multipliers[p], C};
+    }, n_pairs, n, C, channel_mask, stds != nullptr, edges, bins, out);
+    return HM_OK;
+}
+
+// The same distributions straight from uint8 / uint16 DN frames: the table first, then the loops above on the mapped values. The frames
+// are never written. `variant` places the table on the device; here it is only checked (the fit rule: hm_pairs_rules.h).
+size_t hm_pairs_histogram_dn_workspace_bytes(int, int, int, int) { return 64; }
+int hm_pairs_minmax_dn(const void* const* frames, int n_frames, int bit_depth, const double* icrf, const double* icrf_diff,
+                       const double* std_table, const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs, int64_t n,
+                       int C, const double* lower, const double* upper, int variant, double* out, void* workspace, void*) {
+    const int rc = hm_rules::check_pairs_minmax_dn(frames, n_frames, bit_depth, icrf, icrf_diff, std_table, pair_i, pair_j, multipliers, n_pairs,
+                                                   n, C, lower, upper, variant, out, workspace);
+    if (rc != HM_OK) return rc;
+    const PairsDnTable t(icrf, icrf_diff, std_table, lower, upper, bit_depth, C);
+    pairs_minmax_loop([&](int p) { return PairDnElems{&t, frames[pair_i[p]], frames[pair_j[p]], multipliers[p]}; }, n_pairs, n, C, t.with_std, out);
+    return HM_OK;
+}
+int hm_pairs_histogram_dn(const void* const* frames, int n_frames, int bit_depth, const double* icrf, const double* icrf_diff,
+                          const double* std_table, const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                          int64_t n, int C, int channel_mask, const double* lower, const double* upper, const double* edges, int bins,
+                          int variant, double* out, void* workspace, void*) {
+    const int rc = hm_rules::check_pairs_histogram_dn(frames, n_frames, bit_depth, icrf, icrf_diff, std_table, pair_i, pair_j, multipliers,
+                                                      n_pairs, n, C, channel_mask, lower, upper, edges, bins, variant, out, workspace);
+    if (rc != HM_OK) return rc;
+    const PairsDnTable t(icrf, icrf_diff, std_table, lower, upper, bit_depth, C);
+    pairs_histogram_loop([&](int p) { return PairDnElems{&t, frames[pair_i[p]], frames[pair_j[p]], multipliers[p]}; }, n_pairs, n, C,
+                         channel_mask, t.with_std, edges, bins, out);
+    return HM_OK;
+}
+int hm_pairs_histogram_dn_describe(int64_t n, int n_frames, int n_pairs, int C, int with_std, int bit_depth, int bins, int variant, char* buf,
+                                   int buf_len) {
+    if (!buf || buf_len < 1) return HM_EINVAL;
+    buf[0] = '\0';
+    const int rc = hm_rules::check_pairs_hist_dn_counts(n_frames, n_pairs, n, C, with_std != 0, bit_depth, bins, variant);
+    if (rc != HM_OK) return rc;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "host_pairs_hist_dn<dn=%s,bits=%d,std=%d>", bit_depth == 8 ? "u8" : "u16", bit_depth, with_std != 0);
     return HM_OK;
 }
 

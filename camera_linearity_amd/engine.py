@@ -994,23 +994,22 @@ def pairs_statistics(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch
     return res
 
 
-class PairsDnPlan:
-    """One hm_pairs_statistics_dn call with everything it reads and writes: the DN frames, the tables, the pair arrays, the output and the
-    workspace. launch() only enqueues (the table kernel, the statistics kernels, the final fold), so a PlanGraph can record it; the
-    statistics are in `outputs["stats"]` (n_pairs * 6C float64) after the stream has run."""
+class _PairsDnArgs:
+    """What the entries that read DN frames (pairs_statistics_dn, pairs_histogram_dn) take, checked and kept alive: the DN frames, the
+    (2**bit_depth, C) tables on the frames' device, the thresholds and the pair arrays. `what` names the caller in the errors."""
 
-    def __init__(self, frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, thresholds=None,
+    def __init__(self, what: str, frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, thresholds=None,
                  bit_depth: Optional[int] = None, variant: int = 0):
         frames = list(frames)
         if not frames:
-            raise ValueError("pairs_statistics_dn needs at least one frame")
+            raise ValueError(f"{what} needs at least one frame")
         for i, f in enumerate(frames):
             _require_cuda(f, f"frames[{i}]")
         first = frames[0]
         if first.dtype not in (_U8, _U16):
-            raise ValueError(f"pairs_statistics_dn takes torch.uint8 or torch.uint16 DN frames, got {first.dtype}")
+            raise ValueError(f"{what} takes torch.uint8 or torch.uint16 DN frames, got {first.dtype}")
         if any(f.dtype != first.dtype or f.shape != first.shape or f.device != first.device for f in frames):
-            raise ValueError("pairs_statistics_dn needs DN frames of one dtype and one shape on one device")
+            raise ValueError(f"{what} needs DN frames of one dtype and one shape on one device")
         self.bit_depth = 8 if _welford_bit_depth(first.dtype, bit_depth) is None else int(bit_depth)
         if std_table is not None and icrf_diff is None:
             raise ValueError("std_table needs icrf_diff: the std of a DN is ICRF_diff * STD_table")
@@ -1040,6 +1039,17 @@ class PairsDnPlan:
         self._pi = (C.c_int32 * P)(*[int(p[0]) for p in pairs])
         self._pj = (C.c_int32 * P)(*[int(p[1]) for p in pairs])
         self._pm = (C.c_double * P)(*[float(p[2]) for p in pairs])
+
+
+class PairsDnPlan(_PairsDnArgs):
+    """One hm_pairs_statistics_dn call with everything it reads and writes: the DN frames, the tables, the pair arrays, the output and the
+    workspace. launch() only enqueues (the table kernel, the statistics kernels, the final fold), so a PlanGraph can record it; the
+    statistics are in `outputs["stats"]` (n_pairs * 6C float64) after the stream has run."""
+
+    def __init__(self, frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, thresholds=None,
+                 bit_depth: Optional[int] = None, variant: int = 0):
+        super().__init__("pairs_statistics_dn", frames, pairs, icrf, icrf_diff, std_table, thresholds, bit_depth, variant)
+        P, Cc, dev = self.n_pairs, self.channels, self.device
         self.outputs = {"stats": torch.empty(P * 6 * Cc, dtype=_F64, device=dev)}
         self._ws = torch.empty(max(1, (nat.lib.hm_pairs_statistics_dn_workspace_bytes(P, Cc, self.bit_depth) + 7) // 8), dtype=_F64, device=dev)
 
@@ -1142,6 +1152,28 @@ def channel_histogram(val: torch.Tensor, std: Optional[torch.Tensor], bins: int,
     return out
 
 
+def _pairs_histogram_edges(minmax, included_range, P: int, Cc: int, bins: int, channels: Sequence[int], what: str) -> np.ndarray:
+    """The (P, 2, C, bins + 1) bin edges of an all-pairs histogram call: np.linspace over `included_range`, or over np.histogram's default
+    range per (pair, kind, channel) from minmax() - a device tensor of P * 2 * C * 2 min / max values, fetched with one host copy - with
+    channel_histogram's two NumPy rules. Channels outside `channels` keep zero edges (they count nothing)."""
+    if included_range is None:
+        ranges = minmax().cpu().numpy().reshape(P, 2, Cc, 2).copy()        # one device-to-host copy for all pairs
+        empty = ranges[..., 0] > ranges[..., 1]                            # (+inf, -inf): nothing counted - np.histogram of an empty selection uses (0, 1)
+        ranges[empty] = (0.0, 1.0)
+    else:
+        ranges = np.empty((P, 2, Cc, 2))
+        ranges[..., 0], ranges[..., 1] = float(included_range[0]), float(included_range[1])
+    same = ranges[..., 0] == ranges[..., 1]                                # np.histogram widens an empty range by +-0.5
+    ranges[same] += (-0.5, 0.5)
+    if not np.all(ranges[:, :, channels, 1] > ranges[:, :, channels, 0]):
+        raise ValueError(f"{what}: the upper end of the range must be above the lower end")
+    edges = np.zeros((P, 2, Cc, bins + 1))
+    for idx in np.ndindex(P, 2, Cc):
+        if idx[2] in channels:
+            edges[idx] = np.linspace(ranges[idx][0], ranges[idx][1], bins + 1)
+    return edges
+
+
 def pairs_histogram(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch.Tensor]], pairs: Sequence[tuple], bins: int, included_range,
                     channels: Sequence[int], thresholds: Optional[tuple] = None):
     """ExposurePair.compute_difference + process_linearity_distribution of EVERY exposure pair of a stack without the difference images
@@ -1180,24 +1212,12 @@ def pairs_histogram(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch.
     pm = (C.c_double * P)(*[float(p[2]) for p in pairs])
     ws = torch.empty(max(1, nat.lib.hm_pairs_histogram_workspace_bytes(P, bins, Cc) // 8), dtype=_F64, device=dev)
     with _on(dev):
-        if included_range is None:
+        def minmax():
             mm = torch.empty(P * 2 * Cc * 2, dtype=_F64, device=dev)
             nat.check(nat.lib.hm_pairs_minmax(vp, sp, n, pi, pj, pm, P, vals[0].numel(), Cc, lo, hi, mm.data_ptr(), ws.data_ptr(), _stream(dev)),
                       "hm_pairs_minmax")
-            ranges = mm.cpu().numpy().reshape(P, 2, Cc, 2).copy()          # one device-to-host copy for all pairs
-            empty = ranges[..., 0] > ranges[..., 1]                        # (+inf, -inf): nothing counted - np.histogram of an empty selection uses (0, 1)
-            ranges[empty] = (0.0, 1.0)
-        else:
-            ranges = np.empty((P, 2, Cc, 2))
-            ranges[..., 0], ranges[..., 1] = float(included_range[0]), float(included_range[1])
-        same = ranges[..., 0] == ranges[..., 1]                            # np.histogram widens an empty range by +-0.5
-        ranges[same] += (-0.5, 0.5)
-        if not np.all(ranges[:, :, channels, 1] > ranges[:, :, channels, 0]):
-            raise ValueError("pairs_histogram: the upper end of the range must be above the lower end")
-        edges = np.zeros((P, 2, Cc, bins + 1))
-        for idx in np.ndindex(P, 2, Cc):
-            if idx[2] in channels:
-                edges[idx] = np.linspace(ranges[idx][0], ranges[idx][1], bins + 1)
+            return mm
+        edges = _pairs_histogram_edges(minmax, included_range, P, Cc, bins, channels, "pairs_histogram")
         edges_d = torch.as_tensor(edges, device=dev)
         res = torch.empty(P * 2 * Cc * bins, dtype=_F64, device=dev)
         nat.check(nat.lib.hm_pairs_histogram(vp, sp, n, pi, pj, pm, P, vals[0].numel(), Cc, sum(1 << c for c in set(channels)), lo, hi,
@@ -1206,6 +1226,59 @@ def pairs_histogram(vals: Sequence[torch.Tensor], stds: Optional[Sequence[torch.
     if stds is None:
         r = r.astype(np.int64)
     return [tuple({c: (r[p, k, c], edges[p, k, c]) for c in channels} for k in range(2)) for p in range(P)]
+
+
+def pairs_histogram_dn(frames: Sequence[torch.Tensor], pairs: Sequence[tuple], icrf, icrf_diff=None, std_table=None, bins: int = 128,
+                       included_range=None, channels: Optional[Sequence[int]] = None, thresholds: Optional[tuple] = None,
+                       bit_depth: Optional[int] = None, variant: int = 0):
+    """pairs_histogram() straight from DN frames (hm_pairs_minmax_dn, hm_pairs_histogram_dn): torch.uint8 frames, or torch.uint16 frames with
+    `bit_depth` in 9..16, and (2**bit_depth, C) tables - the dtype and depth rules and the per-element semantics of pairs_statistics_dn
+    (value icrf[idx, c], with `std_table` the std icrf_diff[idx, c] * std_table[idx, c] and weighted histograms, thresholds on the values
+    as read). The frames are not modified and no float64 frame is written. channels None: every channel. Edges and result as
+    pairs_histogram: included_range None takes every (pair, kind, channel)'s default range from one hm_pairs_minmax_dn pass first.
+    `variant`: 0 the library's choice, 1 the table in LDS beside the histograms, 2 gathered from global memory; the counts do not depend
+    on it."""
+    plan = _PairsDnArgs("pairs_histogram_dn", frames, pairs, icrf, icrf_diff, std_table, thresholds, bit_depth, variant)
+    bins = int(bins)
+    if not 1 <= bins <= nat.HM_PAIRS_HIST_MAX_BINS:
+        raise ValueError(f"pairs_histogram_dn takes 1..{nat.HM_PAIRS_HIST_MAX_BINS} bins")
+    Cc, P, dev = plan.channels, plan.n_pairs, plan.device
+    channels = list(range(Cc)) if channels is None else [int(c) for c in channels]
+    if any(c < 0 or c >= Cc for c in channels):
+        raise ValueError("channel outside the frames' channels")
+    icrf_t, diff_t, table_t = plan.tables
+    fp = C.cast(plan._fp, C.POINTER(C.c_void_p))
+    n_frames, n = len(plan.frames), plan.frames[0].numel()
+    ws = torch.empty(max(1, (nat.lib.hm_pairs_histogram_dn_workspace_bytes(P, bins, Cc, plan.bit_depth) + 7) // 8), dtype=_F64, device=dev)
+    with _on(dev):
+        def minmax():
+            mm = torch.empty(P * 2 * Cc * 2, dtype=_F64, device=dev)
+            nat.check(nat.lib.hm_pairs_minmax_dn(fp, n_frames, plan.bit_depth, icrf_t.data_ptr(), nat.ptr(diff_t), nat.ptr(table_t), plan._pi,
+                                                 plan._pj, plan._pm, P, n, Cc, plan.lo, plan.hi, plan.variant, mm.data_ptr(), ws.data_ptr(),
+                                                 _stream(dev)), "hm_pairs_minmax_dn")
+            return mm
+        edges = _pairs_histogram_edges(minmax, included_range, P, Cc, bins, channels, "pairs_histogram_dn")
+        edges_d = torch.as_tensor(edges, device=dev)
+        res = torch.empty(P * 2 * Cc * bins, dtype=_F64, device=dev)
+        nat.check(nat.lib.hm_pairs_histogram_dn(fp, n_frames, plan.bit_depth, icrf_t.data_ptr(), nat.ptr(diff_t), nat.ptr(table_t), plan._pi,
+                                                plan._pj, plan._pm, P, n, Cc, sum(1 << c for c in set(channels)), plan.lo, plan.hi,
+                                                edges_d.data_ptr(), bins, plan.variant, res.data_ptr(), ws.data_ptr(), _stream(dev)),
+                  "hm_pairs_histogram_dn")
+        r = res.cpu().numpy().reshape(P, 2, Cc, bins)
+    if not plan.weighted:
+        r = r.astype(np.int64)
+    return [tuple({c: (r[p, k, c], edges[p, k, c]) for c in channels} for k in range(2)) for p in range(P)]
+
+
+def pairs_histogram_dn_kernel(n_elems: int, n_frames: int, n_pairs: int, channels: int, with_std: bool, bit_depth: int, bins: int,
+                              variant: int = 0) -> str:
+    """The histogram kernel of each launch of such a pairs_histogram_dn call, as hm_pairs_histogram_dn_describe names them (e.g.
+    "pairs_hist_dn<dn=u16,bits=12,tab=global,std=1,np=8,wpp=2>"); nothing is launched. For tests and benchmarks."""
+    buf = C.create_string_buffer(1024)
+    nat.check(nat.lib.hm_pairs_histogram_dn_describe(int(n_elems), int(n_frames), int(n_pairs), int(channels), int(bool(with_std)),
+                                                     int(bit_depth), int(bins), int(variant), buf, len(buf)),
+              "hm_pairs_histogram_dn_describe")
+    return buf.value.decode()
 
 
 # ------------------------------------------------------------------------------------------------

@@ -405,11 +405,22 @@ class ExposureSeries(object):
         return [(index[id(p.short_exposure)], index[id(p.long_exposure)], p.exposure_ratio) for p in self.exposure_pairs]
 
     def _process_linearity_from_dn(self, ICRF, linearity_limit, use_std, ICRF_diff, STD_data):
-        """process_linearity(from_dn=True): every image set holds a from_dn measurand (uint8 DNs) without a std frame, and the conditions
-        of _own_pairs_stack hold (the pairs are pairs of the series' own images, one (H, W, C <= 4) shape, one device, one backend);
-        ValueError otherwise. use_std needs ICRF_diff and a per-DN STD table (STD_data, or settings.STD_FILE_NAME). (BITS,) tables serve
-        every channel, as they do in linearize and calculate_numerical_STD."""
+        """process_linearity(from_dn=True): _from_dn_inputs says what it asks of the series."""
         lower, upper = map_linearity_limits(linearity_limit, linearity_limit, ICRF)
+        dns, pairs, icrf, diff, std_table = self._from_dn_inputs(ICRF, lower, upper, use_std, ICRF_diff, STD_data)
+        exp = self.input_image_sets[0].measurand._export
+        stats = self._eng().pairs_statistics_dn(dns, pairs, icrf, diff, std_table, thresholds=(lower, upper), to_host=True)
+        for p, (ab, rel) in zip(self.exposure_pairs, stats):
+            p.absolute_stats, p.relative_stats = {k: exp(v) for k, v in ab.items()}, {k: exp(v) for k, v in rel.items()}
+            p.absolute_difference = p.relative_difference = None
+
+    def _from_dn_inputs(self, ICRF, lower, upper, use_std, ICRF_diff, STD_data):
+        """What from_dn=True asks of the series, for process_linearity and process_linearity_distribution alike: every image set holds a
+        from_dn measurand (uint8 DNs) without a std frame, and the conditions of _own_pairs_stack hold (the pairs are pairs of the series'
+        own images, one (H, W, C <= 4) shape, one device, one backend); ValueError otherwise. use_std needs ICRF_diff and a per-DN STD
+        table (STD_data, or settings.STD_FILE_NAME). (BITS,) tables serve every channel, as they do in linearize and
+        calculate_numerical_STD. lower / upper: one limit per channel. -> (DN frames, pairs, ICRF, ICRF_diff or None, STD table or None),
+        the tables (BITS, C)."""
         sets = self.input_image_sets
         for image_set in sets:
             if image_set.measurand.shape is None:
@@ -439,11 +450,7 @@ class ExposureSeries(object):
             if ICRF_diff is None or STD_data is None:
                 raise ValueError("use_std=True with from_dn=True needs ICRF_diff and STD_data (or settings.STD_FILE_NAME)")
             diff, std_table = table(ICRF_diff), table(STD_data)
-        exp = sets[0].measurand._export
-        stats = self._eng().pairs_statistics_dn(dns, pairs, table(ICRF), diff, std_table, thresholds=(lower, upper), to_host=True)
-        for p, (ab, rel) in zip(self.exposure_pairs, stats):
-            p.absolute_stats, p.relative_stats = {k: exp(v) for k, v in ab.items()}, {k: exp(v) for k, v in rel.items()}
-            p.absolute_difference = p.relative_difference = None
+        return dns, pairs, table(ICRF), diff, std_table
 
     def _all_pairs_fused(self, lower=None, upper=None) -> bool:
         """Every pair of the series in ONE launch (hm_pairs_statistics): each frame is read from HBM once instead of once per
@@ -478,16 +485,36 @@ class ExposureSeries(object):
         return True
 
     def process_linearity_distribution(self, bins: int, included_range=None, channels=None, use_std: Optional[bool] = False,
-                                       lower: Optional[List] = None, upper: Optional[List] = None):
+                                       lower: Optional[List] = None, upper: Optional[List] = None, from_dn: bool = False, ICRF=None,
+                                       ICRF_diff=None, STD_data=None):
         """The distributions of every exposure pair: a list in self.exposure_pairs order of what pair.compute_difference() followed by
         pair.process_linearity_distribution(bins, included_range, channels, use_std) returns - (absolute, relative), each
         {channel: (hist, bin_edges)}. lower / upper: per-channel limits as apply_thresholds takes them, applied to the values as they are
         read: no image set is changed (process_linearity stays the call that thresholds in place).
         Under the conditions of _all_pairs_fused (and use_std only with a std on every image, bins <= HM_PAIRS_HIST_MAX_BINS) all pairs
         go through hm_pairs_histogram - no difference image is written, a frame is read once per launch; otherwise pair by pair through
-        the difference images, each pair's dropped after its histograms."""
+        the difference images, each pair's dropped after its histograms.
+        from_dn=True (an addition) takes a series that still holds its 8-bit frames as DNs (from_dn measurands; _from_dn_inputs says what
+        it asks) and returns what the same call returns on a deep copy of the series that self.linearize(ICRF, ICRF_diff) made float64
+        first - with use_std the stds ICRF_diff * calculate_numerical_STD(STD_data) - through hm_pairs_minmax_dn / hm_pairs_histogram_dn:
+        no float64 frame is written and the image sets stay DN frames. Counts and edges are equal; weighted bins differ by the order of
+        their sums only."""
         if channels is None:
             channels = list(range(gs.NUM_OF_CHS))
+        if from_dn:
+            if ICRF is None:
+                raise ValueError("from_dn=True needs ICRF: the per-DN value table")
+            sets = self.input_image_sets
+            for image_set in sets:
+                if image_set.measurand.shape is None:
+                    image_set.load_value_image()
+            n_ch = sets[0].measurand.shape[-1] if sets and sets[0].measurand.shape else 0
+            lower = [None] * n_ch if lower is None else lower
+            upper = [None] * n_ch if upper is None else upper
+            lower, upper = [-math.inf if l is None else l for l in lower], [math.inf if u is None else u for u in upper]
+            dns, pairs, icrf, diff, std_table = self._from_dn_inputs(ICRF, lower, upper, use_std, ICRF_diff, STD_data)
+            return self._eng().pairs_histogram_dn(dns, pairs, icrf, diff, std_table, bins=bins, included_range=included_range, channels=channels,
+                                                  thresholds=(lower, upper))
         for image_set in self.input_image_sets:
             if image_set.measurand.shape is None:
                 image_set.load_value_image()

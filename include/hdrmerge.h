@@ -515,6 +515,45 @@ int hm_pairs_histogram(const double* const* vals, const double* const* stds /*nu
                        int64_t n, int C, int channel_mask, const double* lower /*nullable*/, const double* upper /*nullable*/,
                        const double* edges /* device: (n_pairs, 2, C, bins + 1) */, int bins,
                        double* out /* device: (n_pairs, 2, C, bins) */, void* workspace, void* stream);
+/* hm_pairs_minmax_dn / hm_pairs_histogram_dn: the same distributions straight from DN frames, without float64 value and std frames in
+ * memory. frames, bit_depth, icrf, icrf_diff, std_table, lower / upper and the per-element semantics are hm_pairs_statistics_dn's:
+ * idx = DN & (2^bit_depth - 1), v = icrf[idx * C + c], s = icrf_diff[idx * C + c] * std_table[idx * C + c], a value outside
+ * lower[c]..upper[c] NaN together with its std; the frames are NOT modified. Per pair, kind and channel the histogram and the min / max
+ * are those hm_pairs_histogram / hm_pairs_minmax give on frames hm_linearize_u8 / hm_linearize_u16 wrote from the same tables, with the
+ * same thresholds: the same difference expressions, the same counting rule, the same bounded bin index; a (pair, kind, channel) whose
+ * last edge is not above its first counts nothing. A std_table means weighted histograms (weights of the same float64 bits), none means
+ * unweighted ones. edges, out, channel_mask: as hm_pairs_histogram.
+ * One small kernel writes the thresholded table into the workspace behind the partials; nothing is allocated and nothing synchronises
+ * (capturable). The workspace (hm_pairs_histogram_dn_workspace_bytes) covers both calls. The DN loads are per element: any frame
+ * alignment hm_pairs_statistics_dn accepts is served by the one kernel form.
+ * variant: 0 the library's choice; 1 the table in LDS beside the histograms; 2 gathered from the workspace table in global memory.
+ * With per_pair = 2 * C * bins * 8 bytes and T = (8, with a std_table 16) * 2^bit_depth * C bytes a launch takes
+ * min(HM_PAIRS_MAX, (160 KiB - (table in LDS ? T : 0)) / per_pair) pairs, the launches of a call of equal size. Variant 0 takes the LDS
+ * table only where it costs the histograms nothing: the call's pairs need no more launches with it, and a CU holds as many workgroups of
+ * the launch with it as without (min(160 KiB / LDS of the workgroup, 32 / waves of the workgroup, 4)). hm_pairs_minmax_dn holds
+ * nothing else in LDS: its table goes there whenever T <= 160 KiB, unless variant 2.
+ * Statuses, an earlier one winning: hm_pairs_statistics_dn's up to and including the pair indices, with a variant outside 0..2
+ * HM_EINVAL; then (histogram) bins < 1, bins > HM_PAIRS_HIST_MAX_BINS, channel_mask with bits at or above C (or negative), NULL edges:
+ * HM_EINVAL; then HM_EUNSUPPORTED for variant 1 where not one pair's histograms fit beside the table (min / max: T > 160 KiB). Every
+ * one returns before anything is launched, written or dereferenced.
+ * hm_pairs_histogram_dn_describe writes the histogram kernel of each launch, joined by " + ", e.g.
+ * "pairs_hist_dn<dn=u16,bits=12,tab=global,std=1,np=8,wpp=2>" (np pairs, wpp waves per pair; the host build: a host name) and launches
+ * nothing. The statuses above that look at no pointer; HM_EINVAL for a NULL or empty buf. */
+size_t hm_pairs_histogram_dn_workspace_bytes(int n_pairs, int bins, int C, int bit_depth);
+int hm_pairs_minmax_dn(const void* const* frames /*[host] n_frames device ptrs: uint8 (bit_depth 8) or uint16 (9..16)*/,
+                       int n_frames, int bit_depth, const double* icrf, const double* icrf_diff /*nullable*/,
+                       const double* std_table /*nullable; needs icrf_diff*/,
+                       const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                       int64_t n, int C, const double* lower /*nullable*/, const double* upper /*nullable*/, int variant,
+                       double* out /* device: (n_pairs, 2 kinds, C, 2) = min, max */, void* workspace, void* stream);
+int hm_pairs_histogram_dn(const void* const* frames, int n_frames, int bit_depth, const double* icrf, const double* icrf_diff /*nullable*/,
+                          const double* std_table /*nullable; needs icrf_diff*/,
+                          const int32_t* pair_i, const int32_t* pair_j, const double* multipliers, int n_pairs,
+                          int64_t n, int C, int channel_mask, const double* lower /*nullable*/, const double* upper /*nullable*/,
+                          const double* edges /* device: (n_pairs, 2, C, bins + 1) */, int bins, int variant,
+                          double* out /* device: (n_pairs, 2, C, bins) */, void* workspace, void* stream);
+int hm_pairs_histogram_dn_describe(int64_t n, int n_frames, int n_pairs, int C, int with_std, int bit_depth, int bins, int variant,
+                                   char* buf, int buf_len);
 size_t hm_channel_statistics_workspace_bytes(void);
 int hm_channel_statistics(const double* val, const double* std /*nullable*/, int64_t n, int C,
                           double* out, void* workspace, void* stream);

@@ -903,6 +903,70 @@ def case_pairs_hist(rng):
     rb = heng.pairs_histogram(vb, sb, pairs, bins, rngs, chans, thresholds=thr)
     for i in range(n):                                                 # thresholds act on the values as read: the frames are untouched
         compare(f"frame[{i}]", va[i], vals[i], None)
+    compare_pairs_hist(ra, rb, with_std, h * w)                        # k_b <= the pixels of the image
+    return desc
+
+
+def case_pairs_hist_dn(rng):
+    """engine.pairs_histogram_dn (hm_pairs_histogram_dn / hm_pairs_minmax_dn) on both builds: uint8 frames and uint16 frames of 9 to 16 bits
+    (stray bits above the depth), every table placement, frames that are not item-aligned on the device, thresholds, channel subsets, given
+    and default ranges, bin counts on both sides of the pairs-per-launch splits. The expectations are case_pairs_hist's (the std table is
+    positive); a variant 1 whose table does not fit must be refused by both builds."""
+    c = int(rng.choice([1, 2, 3, 3, 4]))
+    b = int(rng.choice([8, 8, 9, 10, 12, 12, 14, 16]))
+    n = int(rng.integers(2, 8))
+    h, w = int(rng.integers(1, 40 * args.scale)), int(rng.integers(1, 60 * args.scale))
+    g, d = icrf_tables_bits(rng, c, b)
+    st = 0.002 + 0.01 * rng.random((2 ** b, c))
+    if rng.random() < args.specials:
+        sprinkle(rng, g, p=0.01)
+        sprinkle(rng, st, values=(0.0, np.inf), p=0.01)
+    t = np.sort(rng.uniform(0.05, 1.0, size=n))
+    scene = rng.random((h, w, c))
+    frames = [np.clip(scene * ti * (2 ** b - 1) + rng.normal(size=scene.shape) * 0.01 * 2 ** b, 0, 2 ** b - 1).astype(np.uint8 if b == 8 else np.uint16)
+              for ti in t]
+    if 8 < b < 16:
+        frames = [f | (dn16(rng, f.shape, b) & np.uint16((0xFFFF << b) & 0xFFFF)) for f in frames]
+    pairs = [(i, j, float(t[i] / t[j])) for i in range(n) for j in range(i + 1, n)]
+    if rng.random() < 0.5:
+        pairs = [pairs[int(q)] for q in rng.choice(len(pairs), size=int(rng.integers(1, len(pairs) + 1)), replace=False)]
+    bins = int(rng.choice([1, 7, 64, 256, 700, 1138, 2048]))
+    rngs = None if rng.random() < 0.4 else (float(rng.uniform(-0.2, -0.01)), float(rng.uniform(0.01, 0.2)))
+    chans = sorted(int(a) for a in rng.choice(c, size=int(rng.integers(1, c + 1)), replace=False))
+    thr = None if rng.random() < 0.5 else ([float(rng.uniform(0.0, 0.1)) for _ in range(c)], [float(rng.uniform(0.5, 1.0)) for _ in range(c)])
+    with_std = bool(rng.random() < 0.5)
+    variant = int(rng.integers(0, 3))
+    odd = bool(rng.random() < 0.4)
+    desc = (f"pairs_hist_dn n={n} {h}x{w}x{c} bits={b} pairs={len(pairs)} bins={bins} range={rngs} channels={chans} std={with_std} "
+            f"thresholds={thr is not None} variant={variant} misaligned={odd}")
+
+    def place(f):                                                      # one item off a 16-byte boundary: odd (uint8), 2 bytes off 4 (uint16)
+        if not odd:
+            return D(f)
+        big = torch.zeros(f.size + 8, dtype=torch.uint8 if b == 8 else torch.uint16, device=dev)
+        view = big[1:1 + f.size].view(f.shape)
+        view.copy_(torch.from_numpy(f.copy()))
+        return view
+    fa, fb = [place(f) for f in frames], [Hh(f) for f in frames]
+    kw = dict(bins=bins, included_range=rngs, channels=chans, thresholds=thr, bit_depth=None if b == 8 else b, variant=variant)
+    tabs = (g, d if with_std else None, st if with_std else None)
+    try:
+        ra = engine.pairs_histogram_dn(fa, pairs, *tabs, **kw)
+    except NotImplementedError:
+        try:
+            heng.pairs_histogram_dn(fb, pairs, *tabs, **kw)
+        except NotImplementedError:
+            return desc + " (refused by both)"
+        raise Mismatch("variant 1 refused by the device build only")
+    rb = heng.pairs_histogram_dn(fb, pairs, *tabs, **kw)
+    for i in range(n):
+        compare(f"frame[{i}]", fa[i], frames[i], None)
+    compare_pairs_hist(ra, rb, with_std, h * w)
+    return desc
+
+
+def compare_pairs_hist(ra, rb, with_std, k_max):
+    """pairs_histogram results of the two builds: edges and unweighted counts equal, a weighted bin within 2 (k_max + 2) u of its value"""
     for q, (pa, pb) in enumerate(zip(ra, rb)):
         for kind, (da, db) in enumerate(zip(pa, pb)):
             assert da.keys() == db.keys()
@@ -915,11 +979,9 @@ def case_pairs_hist(rng):
                 if not (np.array_equal(np.isnan(a_), np.isnan(b_)) and np.array_equal(np.isinf(a_), np.isinf(b_))):
                     raise Mismatch(f"pair{q}.kind{kind}.hist[{ch}]: NaN / inf patterns differ")
                 fin = np.isfinite(b_)
-                k_max = h * w                                          # k_b <= the pixels of the image
                 if np.any(np.abs(a_[fin] - b_[fin]) > 2 * (k_max + 2) * 2.0 ** -53 * np.abs(b_[fin])):
                     i_ = int(np.argmax(np.abs(a_[fin] - b_[fin])))
                     raise Mismatch(f"pair{q}.kind{kind}.hist[{ch}]: {a_[fin][i_]!r} vs {b_[fin][i_]!r} beyond 2 (k + 2) u sum|w|")
-    return desc
 
 
 def icrf_tables_bits(rng, c, b):
@@ -1095,7 +1157,7 @@ def case_linearize_u16(rng):
 
 
 CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2), (case_pairs_hist_dn, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
     assert CASES, f"--only {args.only}: no such generator"
