@@ -92,6 +92,10 @@ _SIGNATURES = {
     "hm_merge_u16_darks": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "hm_merge_u16_darks_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "hm_merge_u16_darks_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs), C.c_void_p]),
+    # ... with the stds from the (2**bit_depth, C) per-DN std table: frames, darks (or NULL: no hot-pixel pass), std_table, bit_depth
+    "hm_merge_u16_std_table": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "hm_merge_u16_std_table_describe": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "hm_merge_u16_std_table_algorithmic_bytes": (C.c_int64, [C.POINTER(MergeArgs), C.c_void_p]),
     "hm_linearize_u16": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hm_hot_pixel_filter_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_int64, C.c_int, C.c_void_p]),

@@ -1,5 +1,5 @@
-// hm_merge_rules.h - the argument rules of the fused merge's five C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32, hm_merge_u16,
-// hm_merge_u16_darks), written
+// hm_merge_rules.h - the argument rules of the fused merge's six C entry points (hm_merge, hm_merge_std_table, hm_merge_std_f32, hm_merge_u16,
+// hm_merge_u16_darks, hm_merge_u16_std_table), written
 // once for both builds of the ABI: the device build's dispatcher (hm_merge.hip) and the host build (csrc_host/hm_host.cpp) include this file
 // and hold no argument test of their own - one ABI, one answer. Plain C++17 on hdrmerge.h and the standard headers: no HIP type, no OpenMP.
 //
@@ -18,15 +18,18 @@
 
 namespace hm_rules {
 
-enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32, ENTRY_U16, ENTRY_U16_DARKS };   // the C entry point called
+enum MergeEntry { ENTRY_MERGE, ENTRY_STD_TABLE, ENTRY_STD_F32, ENTRY_U16, ENTRY_U16_DARKS, ENTRY_U16_STD_TABLE };   // the C entry point called
+constexpr bool entry_is_u16(MergeEntry e) { return e == ENTRY_U16 || e == ENTRY_U16_DARKS || e == ENTRY_U16_STD_TABLE; }
 
-// hm_merge_u16's own arguments (check_merge_call's `extra` for ENTRY_U16), and hm_merge_u16_darks's (ENTRY_U16_DARKS: with the N dark maps)
-struct U16Extra { const uint16_t* const* frames; int bit_depth; const uint16_t* const* darks = nullptr; };
+// hm_merge_u16's own arguments (check_merge_call's `extra` for ENTRY_U16), hm_merge_u16_darks's (ENTRY_U16_DARKS: with the N dark maps) and
+// hm_merge_u16_std_table's (ENTRY_U16_STD_TABLE: with the (2^bit_depth, C) per-DN std table, and the N dark maps or NULL for no hot-pixel pass)
+struct U16Extra { const uint16_t* const* frames; int bit_depth; const uint16_t* const* darks = nullptr; const double* std_table = nullptr; };
 
 // hm_merge_u16: which of a call's tables a streaming kernel holds in LDS, the bytes that takes, and the fit rule - at most a gfx950
 // workgroup's 160 KiB (hdrmerge.h states all of it for callers). n = 2^bit_depth rows:
 //   U16_TAB_ALL     value-only w[n] | (w g)[n C]: 8 (1 + C) n bytes; with std {w, dw}[n] | {g, d}[n C]: 16 (1 + C) n bytes
-//   U16_TAB_WDW_G   (std calls) {w, dw}[n] | g[n C]: 8 (2 + C) n bytes; icrf_diff is gathered from global memory
+//   U16_TAB_WDW_G   (std calls) {w, dw}[n] | g[n C]: 8 (2 + C) n bytes; icrf_diff is gathered from global memory. In a table call
+//                   (hm_merge_u16_std_table) the same bytes hold {w, dw}[n] | dg[n C], dg = icrf_diff * std_table, and icrf is gathered
 //   U16_TAB_PER_DN  the per-DN tables only - w[n]: 8 n bytes, with std {w, dw}[n]: 16 n bytes; the per-(DN, channel) ones from global memory
 //   U16_TAB_GLOBAL  nothing in LDS
 enum U16Tables { U16_TAB_GLOBAL = 0, U16_TAB_PER_DN = 1, U16_TAB_WDW_G = 2, U16_TAB_ALL = 3 };
@@ -51,7 +54,7 @@ inline int u16_mixed_tables(int bit_depth, int C, bool with_std) {
 enum StdSource {
     STD_NONE,     // no std is formed (a std-entry call without out_val too: it is hm_merge's sum-of-weights call)
     STD_F64,      // args->stds: N float64 frames
-    STD_TABLE,    // hm_merge_std_table: the (256, C) per-DN table; args->stds is NULL
+    STD_TABLE,    // hm_merge_std_table: the (256, C) per-DN table, hm_merge_u16_std_table: the (2^bit_depth, C) one; args->stds is NULL
     STD_F32       // hm_merge_std_f32: N float32 frames, 4-byte aligned; MergeCall::a.stds addresses them
 };
 
@@ -63,7 +66,7 @@ struct MergeCall {
     bool f64in;                        // float64 frames (else uint8, or uint16 in a hm_merge_u16 call)
     const uint16_t* const* frames_u16; // hm_merge_u16: the N frames (a.frames_u8 and a.frames_f64 are NULL), else NULL
     int bit_depth;                     // hm_merge_u16: 9..16, else 0
-    const uint16_t* const* darks_u16;  // hm_merge_u16_darks: the N dark maps (NULL entries: no filter; a.darks_u8 is NULL), else NULL
+    const uint16_t* const* darks_u16;  // hm_merge_u16_darks, hm_merge_u16_std_table with maps: the N dark maps (NULL entries: no filter; a.darks_u8 is NULL), else NULL
     bool with_std;                     // std_src != STD_NONE
     bool flat;                         // a flat field of either kind
     bool hot;                          // at least one frame has a dark map
@@ -88,7 +91,7 @@ inline bool widen_args(const hm_merge_args* g, hm_merge_args& full) {
 }
 
 // extra: the entry point's own pointer - NULL for hm_merge, std_table for hm_merge_std_table, stds_f32 for hm_merge_std_f32, a U16Extra
-// for hm_merge_u16 and hm_merge_u16_darks.
+// for hm_merge_u16, hm_merge_u16_darks and hm_merge_u16_std_table.
 // Returns the call's status; `call` is complete when that is HM_OK (with call.empty set there is nothing to run).
 inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const void* extra, MergeCall& call) {
     call = MergeCall{};
@@ -114,24 +117,32 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
         for (int i = 0; i < N; ++i)
             if (!ptr_aligned(stds_f32[i], 4)) return HM_EALIGN;
         if (g->out_val) { call.std_src = STD_F32; g->stds = reinterpret_cast<const double* const*>(stds_f32); }
-    } else if (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) {
+    } else if (entry_is_u16(entry)) {
         const U16Extra* x = static_cast<const U16Extra*>(extra);
+        const bool table = entry == ENTRY_U16_STD_TABLE;
+        // the maps of a call: hm_merge_u16_darks always has them, hm_merge_u16_std_table may
+        const bool darks = entry == ENTRY_U16_DARKS || (table && x && x->darks);
         if (g->frames_u8 || g->frames_f64 || !x || !x->frames) return HM_EINVAL;
         for (int i = 0; i < N; ++i)
             if (!x->frames[i]) return HM_EINVAL;
         if (x->bit_depth < 9 || x->bit_depth > 16 || !g->w_lut) return HM_EINVAL;
         if (g->stds && (!g->icrf_diff || !g->dw_lut)) return HM_EINVAL;
-        // hm_merge_u16_darks: the maps come beside the struct (uint16), never in it (uint8), and always with their thresholds
-        if (entry == ENTRY_U16_DARKS && (!x->darks || g->darks_u8 || !g->dark_min_dn)) return HM_EINVAL;
+        // hm_merge_u16_std_table: the table takes the place of the std frames (hm_merge_std_table's rules)
+        if (table && (g->stds || !x->std_table || !g->icrf_diff || !g->dw_lut)) return HM_EINVAL;
+        if (table && g->out_val && !g->out_std) return HM_EINVAL;
+        // the maps come beside the struct (uint16), never in it (uint8), and always with their thresholds
+        if (darks && (!x->darks || g->darks_u8 || !g->dark_min_dn)) return HM_EINVAL;
         for (int i = 0; i < N; ++i)
             if (!ptr_aligned(x->frames[i], 2)) return HM_EALIGN;
-        if (entry == ENTRY_U16_DARKS) {
+        if (darks) {
             for (int i = 0; i < N; ++i)
                 if (!ptr_aligned(x->darks[i], 2)) return HM_EALIGN;
             call.darks_u16 = x->darks;
         }
+        if (table && !ptr_aligned(x->std_table, 8)) return HM_EALIGN;
         call.frames_u16 = x->frames; call.bit_depth = x->bit_depth;
         if (g->stds) call.std_src = STD_F64;
+        if (table && g->out_val) { call.std_src = STD_TABLE; call.std_table = x->std_table; }   // (without out_val: hm_merge_u16's sum-of-weights call)
     } else if (g->stds) call.std_src = STD_F64;
     // hm_merge's rules
     if (N < 1 || C < 1 || g->height < 1 || g->width < 1 || g->rows < 0) return HM_EINVAL;
@@ -198,7 +209,7 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
     const bool chunked = N > HM_MAX_FRAMES || g->variant <= -2;
     if (call.f32out && (chunked || g->rows * g->width * static_cast<int64_t>(C) >= (int64_t{1} << 32))) return HM_EUNSUPPORTED;
     if (call.std_src == STD_F32 && chunked) return HM_EUNSUPPORTED;
-    if (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) {
+    if (entry_is_u16(entry)) {
         // variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
         // memory / split between the two (the largest partial placement)
         if (g->variant > 3) return HM_EINVAL;
@@ -212,14 +223,14 @@ inline int check_merge_call(const hm_merge_args* g_in, MergeEntry entry, const v
 
 // Algorithmic bytes of a call through `entry` (hdrmerge.h: hm_merge_algorithmic_bytes): STD_TABLE calls read no std stream, STD_F32 calls
 // 4-byte ones (args->stds is NULL in both). Takes the caller's arguments as they are: a refused call has a count too.
-// darks_u16 (ENTRY_U16_DARKS): the N uint16 dark maps, 2 bytes per element for every distinct (map, threshold).
+// darks_u16 (ENTRY_U16_DARKS, ENTRY_U16_STD_TABLE): the N uint16 dark maps, 2 bytes per element for every distinct (map, threshold).
 inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry, const uint16_t* const* darks_u16 = nullptr) {
     if (!g || g->n_frames <= 0 || g->rows <= 0 || g->width <= 0 || g->channels <= 0) return 0;
     const int64_t E = g->rows * g->width * g->channels;
     const int N = g->n_frames;
-    const bool lut = entry == ENTRY_STD_TABLE, sd32 = entry == ENTRY_STD_F32;
+    const bool lut = entry == ENTRY_STD_TABLE || entry == ENTRY_U16_STD_TABLE, sd32 = entry == ENTRY_STD_F32;
     const bool s = lut || sd32 || g->stds != nullptr;
-    const int64_t in_b = (entry == ENTRY_U16 || entry == ENTRY_U16_DARKS) ? 2 : g->frames_f64 ? 8 : 1;
+    const int64_t in_b = entry_is_u16(entry) ? 2 : g->frames_f64 ? 8 : 1;
     int64_t per = N * (in_b + ((s && !lut) ? (sd32 ? 4 : 8) : 0));
     const bool f32out = g->struct_size == sizeof(hm_merge_args) && g->out_kind == HM_OUT_F32;   // (the older layouts have no out_kind)
     if (g->out_val) per += (f32out ? 4 : 8) * (1 + (s ? 1 : 0));
@@ -233,7 +244,7 @@ inline int64_t merge_algorithmic_bytes(const hm_merge_args* g, MergeEntry entry,
                 seen = seen || (g->darks_u8[k] == g->darks_u8[i] && (!g->dark_min_dn || g->dark_min_dn[k] == g->dark_min_dn[i]));
             per += seen ? 0 : 1;
         }
-    if (entry == ENTRY_U16_DARKS && darks_u16)
+    if ((entry == ENTRY_U16_DARKS || entry == ENTRY_U16_STD_TABLE) && darks_u16)
         for (int i = 0; i < N; ++i) {
             if (!darks_u16[i]) continue;
             bool seen = false;

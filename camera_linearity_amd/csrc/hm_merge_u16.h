@@ -58,9 +58,16 @@ struct U16Frames {
     __device__ __forceinline__ double sd_at(int i) const { return a.sd[i][ei]; }
 };
 
+// hm_merge_u16_std_table: frame i's std is the per-DN table's entry at the frame's own masked DN (MergeK::std_lut, (2^bit_depth, C))
+struct U16FramesLut : U16Frames {
+    using U16Frames::U16Frames;
+    __device__ __forceinline__ double sd_at(int i) const { return a.std_lut[ld_dn16(a, i, ei, mask) * static_cast<uint32_t>(a.C) + static_cast<uint32_t>(c)]; }
+};
+
 // hm_merge_u16_hot.hip: the stream-ordered pass after hm_merge_u16's kernels (hm_merge_u16_darks). ws != NULL: merge_u16_scan_hot queues
 // the hot elements in the workspace (counters zeroed by the call's first kernel through MergeK::hot_reset) and merge_u16_patch_hot
 // recomputes one queued element per lane; ws == NULL: merge_u16_patch_hot tests every element's dark DNs itself (queue=0).
-int launch_u16_hot(const MergeK& k, int bits, bool with_std, bool f32out, uint32_t* ws, size_t ws_bytes, hipStream_t st);
+// lut (with_std only): the stds come from k.std_lut, a hot frame's as the median of the mapped neighbourhood.
+int launch_u16_hot(const MergeK& k, int bits, bool with_std, bool lut, bool f32out, uint32_t* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace hm

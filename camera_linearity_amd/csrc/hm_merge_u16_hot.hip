@@ -9,6 +9,9 @@
 //                         between the two passes). The queue is dealt as it lies, in blocks of B = ceil(count / waves) <= 64 consecutive
 //                         entries per wave (no image-ordered walk through the piece table). With the scan's overflow flag raised, or without
 //                         a workspace (queue=0), every lane tests its own elements' dark DNs and patches the hot ones.
+//                         LUT (hm_merge_u16_std_table): the stds come from MergeK::std_lut at the filtered DN; a hot frame's is the k x k
+//                         median of the mapped neighbourhood, median_j(std_lut[idx_j C + c]) (StdLutDnAt), while icrf_diff is read at the
+//                         median DN - the two differ wherever the table is not monotone.
 #include "hm_merge_u16.h"
 
 namespace hm {
@@ -26,9 +29,16 @@ struct DnAt {
     __device__ __forceinline__ uint32_t operator()(int64_t i) const { return static_cast<uint32_t>(f[i]) & mask; }
 };
 
+// ... and of the per-DN std table mapped over the same neighbourhood: the std frame the table stands for, never materialised
+struct StdLutDnAt {
+    const uint16_t* f; uint32_t mask; const double* lut; uint32_t C, c;
+    __device__ __forceinline__ double operator()(int64_t i) const { return lut[(static_cast<uint32_t>(f[i]) & mask) * C + c]; }
+};
+
 // merge_u16_element's source with the medians of the hot frames substituted: the masked DN of a hot frame is the k x k median of the masked
 // DNs around it, its std the k x k median of the std neighbourhood. The neighbourhood is read only where the frame is hot.
 // keep: this thread's LDS column (stride kU16PatchBlock) for the filtered DNs between the two passes.
+template <bool LUT>
 struct U16Filtered {
     const MergeK& a; uint32_t mask; uint16_t* keep; uint32_t hotmask;
     int64_t ei, row, col; int c;
@@ -43,13 +53,20 @@ struct U16Filtered {
     }
     __device__ __forceinline__ uint32_t idx_again(int i) const { return keep[i * kU16PatchBlock]; }
     __device__ __forceinline__ double sd_at(int i) const {
+        if constexpr (LUT) {
+            const uint32_t C = static_cast<uint32_t>(a.C), cc = static_cast<uint32_t>(c);
+            if ((hotmask >> i) & 1u)
+                return lane_median_of<double>(StdLutDnAt{static_cast<const uint16_t*>(a.frame[i]), mask, a.std_lut, C, cc}, a.H, a.W, a.C, a.buf_row0,
+                                              row, col, c, a.median_k);
+            return a.std_lut[keep[i * kU16PatchBlock] * C + cc];           // not hot: the frame's own masked DN
+        }
         if ((hotmask >> i) & 1u) return lane_median_of<double>(StdAt<double>{a.sd[i]}, a.H, a.W, a.C, a.buf_row0, row, col, c, a.median_k);
         return a.sd[i][ei];
     }
 };
 
 // ws == NULL: no queue (queue=0)
-template <bool STD, int OUT>
+template <bool STD, int OUT, bool LUT = false>
 __global__ __launch_bounds__(kU16PatchBlock) void merge_u16_patch_hot(const MergeK a, const uint32_t mask, const uint32_t* ws) {
     __shared__ uint16_t s_keep[HM_MAX_FRAMES * kU16PatchBlock];
     uint16_t* const keep = s_keep + threadIdx.x;
@@ -63,7 +80,7 @@ __global__ __launch_bounds__(kU16PatchBlock) void merge_u16_patch_hot(const Merg
         for (int64_t q = static_cast<int64_t>(blockIdx.x) * kU16PatchBlock + threadIdx.x; q < a.n_elems; q += stride) {
             const int64_t e = a.elem0 + q;
             const uint32_t hotmask = lane_hotmask<uint16_t>(a, a.in_off + e, mask);
-            if (hotmask) merge_u16_element<STD, OUT>(a, e, U16Filtered(a, mask, keep, e, hotmask));
+            if (hotmask) merge_u16_element<STD, OUT>(a, e, U16Filtered<LUT>(a, mask, keep, e, hotmask));
         }
         return;
     }
@@ -79,12 +96,13 @@ __global__ __launch_bounds__(kU16PatchBlock) void merge_u16_patch_hot(const Merg
         const uint64_t q = base + lane;
         if (lane < B && q < count) {                                    // count <= the queue's capacity (no overflow)
             const int64_t e = static_cast<int64_t>(queue[q]);          // < n_elems: the scan queues elements of the tile only
-            merge_u16_element<STD, OUT>(a, e, U16Filtered(a, mask, keep, e, lane_hotmask<uint16_t>(a, a.in_off + e, mask)));
+            merge_u16_element<STD, OUT>(a, e, U16Filtered<LUT>(a, mask, keep, e, lane_hotmask<uint16_t>(a, a.in_off + e, mask)));
         }
     }
 }
 
-int launch_u16_hot(const MergeK& k, int bits, bool with_std, bool f32out, uint32_t* ws, size_t ws_bytes, hipStream_t st) {
+int launch_u16_hot(const MergeK& k, int bits, bool with_std, bool lut, bool f32out, uint32_t* ws, size_t ws_bytes, hipStream_t st) {
+    if (lut && !with_std) return HM_EINVAL;
     const uint32_t mask = (1u << bits) - 1u;
     if (ws) {
         if (!describe_only("merge_u16_scan_hot")) {
@@ -98,11 +116,13 @@ int launch_u16_hot(const MergeK& k, int bits, bool with_std, bool f32out, uint32
             if (rc != HM_OK) return rc;
         }
     }
-    if (describe_only(ws ? "merge_u16_patch_hot<bits=%d,std=%d,k=%d>" : "merge_u16_patch_hot<bits=%d,std=%d,k=%d,queue=0>", bits, with_std, k.median_k))
+    if (lut ? describe_only(ws ? "merge_u16_patch_hot<bits=%d,std=lut,k=%d>" : "merge_u16_patch_hot<bits=%d,std=lut,k=%d,queue=0>", bits, k.median_k)
+            : describe_only(ws ? "merge_u16_patch_hot<bits=%d,std=%d,k=%d>" : "merge_u16_patch_hot<bits=%d,std=%d,k=%d,queue=0>", bits, with_std, k.median_k))
         return HM_OK;
     const unsigned grid = stream_grid(k.n_elems, kU16PatchBlock, ws ? 4 : 8);
-    const auto kernel = f32out ? (with_std ? &merge_u16_patch_hot<true, OUT_F32> : &merge_u16_patch_hot<false, OUT_F32>)
-                               : (with_std ? &merge_u16_patch_hot<true, OUT_F64> : &merge_u16_patch_hot<false, OUT_F64>);
+    const auto kernel = lut      ? (f32out ? &merge_u16_patch_hot<true, OUT_F32, true> : &merge_u16_patch_hot<true, OUT_F64, true>)
+                        : f32out ? (with_std ? &merge_u16_patch_hot<true, OUT_F32> : &merge_u16_patch_hot<false, OUT_F32>)
+                                 : (with_std ? &merge_u16_patch_hot<true, OUT_F64> : &merge_u16_patch_hot<false, OUT_F64>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kU16PatchBlock), 0, st, k, mask, static_cast<const uint32_t*>(ws));
     return launch_status();
 }

@@ -439,9 +439,11 @@ static void merge_elements(const hm_merge_args* g, const double* inv_t, int k, c
 // frame's masked DN is the k x k median of the masked DNs around it and its std the k x k median of the std neighbourhood, filtered inline
 // into the element's idx_of[] / sd_of[] - then the same operations in the same order, so the bits of hm_merge_u16 on pre-filtered frames.
 // Without HOT (hm_merge_u16) nothing is staged: idx_at / sd_at read the frames as that path always did.
+// std_table (hm_merge_u16_std_table): frame i's std is std_table[idx_i C + c] instead of g->stds[i] (NULL there); a hot frame's is the k x k
+// median of the mapped neighbourhood, median_j(std_table[idx_j C + c]) - what the median of a materialised std frame is.
 template <bool STD, bool HOT = false>
 static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* frames, uint32_t mask, const double* inv_t,
-                               const uint16_t* const* darks = nullptr) {
+                               const uint16_t* const* darks = nullptr, const double* std_table = nullptr) {
     const int N = g->n_frames, C = g->channels;
     const bool flat = g->flat_f64 != nullptr;
     const int64_t wc = g->width * C, E = g->rows * wc;
@@ -461,16 +463,23 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
             const auto masked = [mask](uint16_t x) { return static_cast<double>(x & mask); };      // exact, order-preserving
             for (int i = 0; i < N; ++i) {
                 idx_of[i] = frames[i][ei] & mask;
-                if constexpr (STD) sd_of[i] = g->stds[i][ei];
+                if constexpr (STD) sd_of[i] = std_table ? std_table[idx_of[i] * C + c] : g->stds[i][ei];
                 if (darks[i] && static_cast<int>(darks[i][ei] & mask) >= g->dark_min_dn[i]) {
                     const int64_t row = g->row0 + e / wc, col = (e % wc) / C;
                     idx_of[i] = static_cast<uint32_t>(median_mapped_at(frames[i], masked, g->height, g->width, C, g->buf_row0, row, col, c, k));
-                    if constexpr (STD) sd_of[i] = median_at(g->stds[i], g->height, g->width, C, g->buf_row0, row, col, c, k);
+                    if constexpr (STD) {
+                        const auto tabled = [=](uint16_t x) { return std_table[(x & mask) * C + c]; };
+                        sd_of[i] = std_table ? median_mapped_at(frames[i], tabled, g->height, g->width, C, g->buf_row0, row, col, c, k)
+                                             : median_at(g->stds[i], g->height, g->width, C, g->buf_row0, row, col, c, k);
+                    }
                 }
             }
         }
         const auto idx_at = [&](int i) -> uint32_t { if constexpr (HOT) return idx_of[i]; else return frames[i][ei] & mask; };
-        [[maybe_unused]] const auto sd_at = [&](int i) -> double { if constexpr (HOT) return sd_of[i]; else return g->stds[i][ei]; };
+        [[maybe_unused]] const auto sd_at = [&](int i) -> double {
+            if constexpr (HOT) return sd_of[i];
+            else return std_table ? std_table[(frames[i][ei] & mask) * C + c] : g->stds[i][ei];
+        };
         double S = 0.0;
         for (int i = 0; i < N; ++i) {
             const double w = g->w_lut[idx_at(i)];
@@ -502,10 +511,11 @@ static void merge_elements_u16(const hm_merge_args* g, const uint16_t* const* fr
     }
 }
 
-// The uint16 entries, shaped like merge_run / merge_describe below: the rules of `entry` (ENTRY_U16 / ENTRY_U16_DARKS), then the one loop.
-// A hm_merge_u16_darks call whose maps are all NULL has call.hot = false: it runs, and answers, as hm_merge_u16.
-static int merge_u16_run(MergeEntry entry, const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth) {
-    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
+// The uint16 entries, shaped like merge_run / merge_describe below: the rules of `entry` (ENTRY_U16 / ENTRY_U16_DARKS / ENTRY_U16_STD_TABLE),
+// then the one loop. A hm_merge_u16_darks call whose maps are all NULL has call.hot = false: it runs, and answers, as hm_merge_u16.
+static int merge_u16_run(MergeEntry entry, const hm_merge_args* g_in, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
+                         const double* std_table = nullptr) {
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16, std_table};
     MergeCall call;
     const int rc = hm_rules::check_merge_call(g_in, entry, &x, call);
     if (rc != HM_OK || call.empty) return rc;
@@ -515,25 +525,26 @@ static int merge_u16_run(MergeEntry entry, const hm_merge_args* g_in, const uint
     const uint32_t mask = (1u << call.bit_depth) - 1u;
     const bool with_std = call.with_std && g->out_val;
     if (call.hot) {                                                     // the hot-pixel filter inline in merge_elements_u16
-        if (with_std) merge_elements_u16<true, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
+        if (with_std) merge_elements_u16<true, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16, call.std_table);
         else merge_elements_u16<false, true>(g, call.frames_u16, mask, inv_t.data(), call.darks_u16);
-    } else if (with_std) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data());
+    } else if (with_std) merge_elements_u16<true>(g, call.frames_u16, mask, inv_t.data(), nullptr, call.std_table);
     else merge_elements_u16<false>(g, call.frames_u16, mask, inv_t.data());
     return HM_OK;
 }
 
 static int merge_u16_describe(MergeEntry entry, const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
-                              char* buf, int buf_len) {
+                              char* buf, int buf_len, const double* std_table = nullptr) {
     if (!buf || buf_len < 1 || !g) return HM_EINVAL;
-    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16};
+    const hm_rules::U16Extra x{frames_u16, bit_depth, darks_u16, std_table};
     MergeCall call;
     const int rc = hm_rules::check_merge_call(g, entry, &x, call);
     buf[0] = 0;
     if (rc != HM_OK || call.empty) return rc;
     char hot[24] = "";
     if (call.hot) std::snprintf(hot, sizeof hot, ",hot=%d", call.a.median_k);
-    std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%d%s%s>(N=%d)", call.bit_depth, call.a.channels,
-                  call.with_std && call.a.out_val, hot, call.f32out ? ",out=f32" : "", call.a.n_frames);
+    const bool with_std = call.with_std && call.a.out_val;
+    std::snprintf(buf, static_cast<size_t>(buf_len), "merge_u16_host<tab=host,bits=%d,C=%d,std=%s%s%s>(N=%d)", call.bit_depth, call.a.channels,
+                  with_std ? (call.std_table ? "lut" : "1") : "0", hot, call.f32out ? ",out=f32" : "", call.a.n_frames);
     return rc;
 }
 
@@ -556,6 +567,18 @@ int hm_merge_u16_darks(const hm_merge_args* g, const uint16_t* const* frames_u16
 int hm_merge_u16_darks_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
                                 char* buf, int buf_len) {
     return merge_u16_describe(hm_rules::ENTRY_U16_DARKS, g, frames_u16, darks_u16, bit_depth, buf, buf_len);
+}
+
+int64_t hm_merge_u16_std_table_algorithmic_bytes(const hm_merge_args* g, const uint16_t* const* darks_u16) {
+    return hm_rules::merge_algorithmic_bytes(g, hm_rules::ENTRY_U16_STD_TABLE, darks_u16);
+}
+int hm_merge_u16_std_table(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, const double* std_table,
+                           int bit_depth, void*) {
+    return merge_u16_run(hm_rules::ENTRY_U16_STD_TABLE, g, frames_u16, darks_u16, bit_depth, std_table);
+}
+int hm_merge_u16_std_table_describe(const hm_merge_args* g, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16,
+                                    const double* std_table, int bit_depth, char* buf, int buf_len) {
+    return merge_u16_describe(hm_rules::ENTRY_U16_STD_TABLE, g, frames_u16, darks_u16, bit_depth, buf, buf_len, std_table);
 }
 
 static int merge_run(const hm_merge_args* g_in, MergeEntry entry, const void* extra) {

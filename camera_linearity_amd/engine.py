@@ -300,12 +300,16 @@ class MergePlan:
         self.outputs = outputs
         self._ref = C.byref(args)
         self.host = self.device.type != "cuda"             # a plan of the host backend (built inside nat.host_mode())
-        self.std_table = std_table                         # (256, C) float64 per-DN std table: the plan goes through hm_merge_std_table
+        self.std_table = std_table                         # float64 per-DN std table: the plan goes through hm_merge_std_table ((256, C)), with
+                                                           # uint16 frames through hm_merge_u16_std_table ((2**bit_depth, C))
         # the C entry point the plan goes through and the entry's own argument after the struct: the ctypes array of N pointers to float32
         # std frames (hm_merge_std_f32), the table, or none
         self.bit_depth = bit_depth                         # uint16 DN frames: the plan goes through hm_merge_u16 (ctypes array of N frame pointers, depth)
         self._bytes_extra = ()                             # what the entry's _algorithmic_bytes form takes after the struct
-        if darks_u16 is not None:                          # ... with uint16 dark maps: hm_merge_u16_darks (ctypes array of N map pointers or NULLs)
+        if frames_u16 is not None and std_table is not None:         # ... with the per-DN std table, with or without uint16 dark maps
+            self._entry, self._bytes_extra = "hm_merge_u16_std_table", (darks_u16,)
+            self._extra = (frames_u16, darks_u16, std_table.data_ptr(), int(bit_depth))
+        elif darks_u16 is not None:                        # ... with uint16 dark maps: hm_merge_u16_darks (ctypes array of N map pointers or NULLs)
             self._entry, self._extra, self._bytes_extra = "hm_merge_u16_darks", (frames_u16, darks_u16, int(bit_depth)), (darks_u16,)
         elif frames_u16 is not None:
             self._entry, self._extra = "hm_merge_u16", (frames_u16, int(bit_depth))
@@ -386,11 +390,19 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
              2**bit_depth rows, the weight tables are weight_luts(device, bit_depth). float32 stds are widened to float64. `darks` are
              torch.uint16 maps of the frames' shape (hm_merge_u16_darks): frame i is hot where (dark DN & (2**bit_depth - 1)) >=
              dark_min[i], thresholds 1 .. 2**bit_depth (dark_min_dn(scale, threshold, bit_depth)); `median_k` and `hot_queue` as for 8-bit
-             frames (False: the patch kernel tests every element itself). Not built for such frames - NotImplementedError: `std_table`,
-             dark maps of another dtype, a uint8 `flat`, more than HM_MAX_FRAMES frames (or forced chunking).
+             frames (False: the patch kernel tests every element itself). Not built for such frames - NotImplementedError: `std_table`
+             (their (2**bit_depth, C) table goes through plan_merge_u16_std_table), dark maps of another dtype, a uint8 `flat`, more than
+             HM_MAX_FRAMES frames (or forced chunking).
              variant: 0 the library's choice, -1 one element per thread, 1 / 2 / 3 the streaming kernel with its tables in LDS / in global
              memory / split between the two.
     """
+    return _plan_merge(frames, exposures, icrf, icrf_diff, stds, darks, dark_min, median_k, flat, flat_std, ff_mean, ff_std_mean, want_sum_w,
+                       want_val, height, row0, rows, buf_row0, variant, hot_queue, out_dtype, std_table, bit_depth, u16_table=False)
+
+
+def _plan_merge(frames, exposures, icrf, icrf_diff, stds, darks, dark_min, median_k, flat, flat_std, ff_mean, ff_std_mean, want_sum_w,
+                want_val, height, row0, rows, buf_row0, variant, hot_queue, out_dtype, std_table, bit_depth, u16_table) -> MergePlan:
+    """plan_merge's body. u16_table: the call is plan_merge_u16_std_table's - uint16 frames with the (2**bit_depth, C) per-DN std table."""
     if out_dtype not in (_F64, torch.float32):
         raise TypeError(f"out_dtype must be torch.float64 or torch.float32, got {out_dtype}")
     n = len(frames)
@@ -403,8 +415,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     u16 = dt == _U16
     if u16:
         bit_depth = _check_bit_depth(bit_depth)
-        if std_table is not None:
-            raise NotImplementedError("uint16 frames: the per-DN std table (std_table) is built for 8-bit frames only")
+        if std_table is not None and not u16_table:
+            raise NotImplementedError("uint16 frames: plan_merge(std_table=...) takes the (256, C) table of 8-bit frames; the per-DN std table "
+                                      "of a 9- to 16-bit camera goes through plan_merge_u16_std_table / merge_u16_std_table")
         if darks is not None and any(d is not None and d.dtype != _U16 for d in darks):
             raise NotImplementedError("uint16 frames: uint16 dark maps are expected (hm_merge_u16_darks); uint8 and other dark map dtypes "
                                       "are built for 8-bit frames only")
@@ -412,6 +425,8 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
             raise NotImplementedError("uint16 frames: a uint8 flat field is built for 8-bit frames only (pass a float64 flat)")
         if n > nat.HM_MAX_FRAMES or variant <= -2:
             raise NotImplementedError(f"uint16 frames: at most {nat.HM_MAX_FRAMES} frames in one launch (no chunked path)")
+    elif u16_table:
+        raise TypeError(f"plan_merge_u16_std_table takes torch.uint16 frames, got {dt}")
     elif bit_depth is not None:
         raise ValueError(f"bit_depth is for torch.uint16 frames, got {dt} frames")
     if dt not in (_U8, _F64, _U16):
@@ -468,8 +483,9 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     table_t = None
     if std_table is not None:
         table_t = _dev_f64(std_table, dev)
-        if tuple(table_t.shape) != (BITS, Cc):
-            raise ValueError(f"std_table must have shape ({BITS}, {Cc}), got {tuple(table_t.shape)}")
+        if tuple(table_t.shape) != (n_rows, Cc):
+            raise ValueError(f"std_table must have shape ({n_rows}, {Cc}), got {tuple(table_t.shape)}")
+        keep.append(table_t)
 
     a = nat.MergeArgs()
     a.struct_size = C.sizeof(nat.MergeArgs)
@@ -571,6 +587,35 @@ def plan_merge(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf,
     if out_dtype == torch.float32 or table_t is not None or sd_f32 or u16:
         plan.kernels                       # the library's own dispatch, dry: what it refuses for float32 outputs / table calls raises here, not at the first launch
     return plan
+
+
+def plan_merge_u16_std_table(frames: Sequence[torch.Tensor], exposures: Sequence[float], icrf, icrf_diff, std_table, *, bit_depth: int,
+                             darks: Optional[Sequence[Optional[torch.Tensor]]] = None, dark_min: Optional[Sequence[int]] = None,
+                             median_k: int = 3, hot_queue: bool = True, flat: Optional[torch.Tensor] = None,
+                             flat_std: Optional[torch.Tensor] = None, ff_mean=None, ff_std_mean=None, want_sum_w: bool = False,
+                             want_val: bool = True, height: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                             buf_row0: int = 0, variant: int = 0, out_dtype: torch.dtype = torch.float64) -> MergePlan:
+    """plan_merge for torch.uint16 DN frames of a 9- to 16-bit camera with the per-frame stds taken from the camera's per-DN STD table
+    (hm_merge_u16_std_table): std_table is (2**bit_depth, C) - what noise_moments_to_STD_data makes - and frame i's std at an element of
+    channel c is std_table[DN_i & (2**bit_depth - 1), c], formed inside the kernels, so no std frame exists in device memory. The outputs
+    equal those of plan_merge(..., stds=[linearize(f, None, std_table, bit_depth=bit_depth)[0] for f in frames], bit_depth=bit_depth), bit
+    for bit; with `darks` (torch.uint16 maps, as plan_merge takes them for such frames) a hot frame's std is the k x k median of the table
+    mapped over its neighbourhood. Everything else - flat field, row tiles, out_dtype, variant - is plan_merge's for uint16 frames, and so
+    is what it refuses (NotImplementedError: more than HM_MAX_FRAMES frames, variant <= -2, uint8 dark maps, a uint8 flat). ValueError: no
+    icrf_diff, a table that is not (2**bit_depth, C). There is no `stds` argument: the table takes the place of the std frames."""
+    if icrf_diff is None:
+        raise ValueError("ICRF_diff is required to propagate uncertainty")
+    if std_table is None:
+        raise ValueError("std_table is required: the (2**bit_depth, C) per-DN STD table")
+    return _plan_merge(frames, exposures, icrf, icrf_diff, None, darks, dark_min, median_k, flat, flat_std, ff_mean, ff_std_mean, want_sum_w,
+                       want_val, height, row0, rows, buf_row0, variant, hot_queue, out_dtype, std_table, bit_depth, u16_table=True)
+
+
+def merge_u16_std_table(frames, exposures, icrf, icrf_diff, std_table, **kw) -> dict:
+    """plan_merge_u16_std_table(...).launch(); returns {'val', 'std', 'sum_w'?} device tensors."""
+    plan = plan_merge_u16_std_table(frames, exposures, icrf, icrf_diff, std_table, **kw)
+    plan.launch()
+    return plan.outputs
 
 
 def merge(frames, exposures, icrf, icrf_diff=None, stds=None, **kw) -> dict:

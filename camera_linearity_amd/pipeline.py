@@ -30,14 +30,18 @@ class _Slot:
 class MergePipeline:
     def __init__(self, n_frames: int, height: int, width: int, exposures: Sequence[float], icrf, icrf_diff=None,
                  channels: int = 3, with_std: bool = False, device=None, depth: int = 2, out_dtype: torch.dtype = torch.float64,
-                 std_table=None, std_dtype: torch.dtype = torch.float64):
+                 std_table=None, std_dtype: torch.dtype = torch.float64, bit_depth: Optional[int] = None):
         """out_dtype: torch.float64 or torch.float32 - the plans' output type (engine.plan_merge) and that of the pinned result staging:
         float32 halves the device-to-host copy, which is what bounds a stream of val-only merges.
         std_table: (256, C) per-DN STD table (engine.plan_merge) - a std output without std inputs: the slots hold no std staging buffers
         and no std frame is copied to the device (8 bytes per element and frame with `with_std`). Excludes with_std.
         std_dtype: torch.float64 (default) or torch.float32, with `with_std` - the element type of the std inputs on both sides of the bus:
         float32 pinned and device staging, read by the merge as they are (engine.plan_merge / hm_merge_std_f32), half the std bytes to
-        copy and to hold, the same output bits as the widened stds. ValueError for other dtypes, or with std_table."""
+        copy and to hold, the same output bits as the widened stds. ValueError for other dtypes, or with std_table.
+        bit_depth: 9..16 - stacks of a 9- to 16-bit camera: pinned and device frame staging are torch.uint16 and the plans go through the
+        uint16 entries (engine.plan_merge(bit_depth=...)); icrf / icrf_diff have 2**bit_depth rows. Value-only, `with_std` (float64 stds:
+        ValueError for std_dtype = float32) and `std_table` of (2**bit_depth, C) (engine.plan_merge_u16_std_table: a std output, no std
+        staging, no std copies). None (default): 8-bit stacks, as ever."""
         if depth < 2:
             raise ValueError("depth must be at least 2 (one slot in flight while the next is filled)")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -49,6 +53,10 @@ class MergePipeline:
             raise ValueError("std_table takes the place of the std inputs: std_dtype does not apply")
         self.n, self.shape, self.with_std, self.depth = n_frames, (height, width, channels), with_std, depth
         self.std_dtype = std_dtype
+        self.bit_depth = bit_depth
+        if bit_depth is not None and std_dtype != torch.float64:
+            raise ValueError("bit_depth: the uint16 merge reads float64 std frames (std_dtype must be torch.float64)")
+        frame_dtype = torch.uint8 if bit_depth is None else torch.uint16
         self.std_out = with_std or std_table is not None             # the plans produce a std image
         if self.std_out and icrf_diff is None:
             raise ValueError("uncertainty propagation needs ICRF_diff")
@@ -58,12 +66,16 @@ class MergePipeline:
         self.slots = []
         for _ in range(depth):
             s = _Slot()
-            s.h_frames = [torch.empty(self.shape, dtype=torch.uint8, pin_memory=True) for _ in range(n_frames)]
+            s.h_frames = [torch.empty(self.shape, dtype=frame_dtype, pin_memory=True) for _ in range(n_frames)]
             s.h_stds = [torch.empty(self.shape, dtype=std_dtype, pin_memory=True) for _ in range(n_frames)] if with_std else None
-            s.d_frames = [torch.empty(self.shape, dtype=torch.uint8, device=self.device) for _ in range(n_frames)]
+            s.d_frames = [torch.empty(self.shape, dtype=frame_dtype, device=self.device) for _ in range(n_frames)]
             s.d_stds = [torch.empty(self.shape, dtype=std_dtype, device=self.device) for _ in range(n_frames)] if with_std else None
-            s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if self.std_out else None, s.d_stds, out_dtype=out_dtype,
-                                       std_table=std_table)
+            if bit_depth is not None and std_table is not None:
+                s.plan = engine.plan_merge_u16_std_table(s.d_frames, exposures, icrf, icrf_diff, std_table, bit_depth=bit_depth,
+                                                         out_dtype=out_dtype)
+            else:
+                s.plan = engine.plan_merge(s.d_frames, exposures, icrf, icrf_diff if self.std_out else None, s.d_stds, out_dtype=out_dtype,
+                                           std_table=std_table, bit_depth=bit_depth)
             s.h_val = torch.empty(self.shape, dtype=out_dtype, pin_memory=True)
             s.h_std = torch.empty(self.shape, dtype=out_dtype, pin_memory=True) if self.std_out else None
             s.ev_h2d = torch.cuda.Event()
@@ -74,7 +86,7 @@ class MergePipeline:
 
     # ---- producer side
     def input_views(self, slot: int):
-        """NumPy views of slot `slot`'s pinned staging: (frames [N x (H, W, C) uint8], stds [N x std_dtype] or None)."""
+        """NumPy views of slot `slot`'s pinned staging: (frames [N x (H, W, C) uint8, uint16 with bit_depth], stds [N x std_dtype] or None)."""
         s = self.slots[slot]
         return [t.numpy() for t in s.h_frames], (None if s.h_stds is None else [t.numpy() for t in s.h_stds])
 
@@ -130,7 +142,7 @@ class MergePipeline:
                 yield kk, val, std
 
     def merge_many(self, stacks: Sequence[Sequence[np.ndarray]], stds: Optional[Sequence[Sequence[np.ndarray]]] = None):
-        """Convenience: merge a list of in-memory stacks (each N uint8 (H, W, C) arrays); returns copies of the results."""
+        """Convenience: merge a list of in-memory stacks (each N uint8 - with bit_depth: uint16 - (H, W, C) arrays); returns copies of the results."""
         def fill(k, fv, sv):
             if k >= len(stacks):
                 return False

@@ -47,7 +47,7 @@ extern "C" {
  *    hm_merge_u16*, hm_linearize_u16 and hm_gaussian_weight_lut_bits_host (uint16 DN frames of 9- to 16-bit cameras; HM_BITS below is
  *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames), and by
  *    hm_linearity_energy_u16*, hm_welford_*_u16* and hm_noise_moments_* (the calibration energy, the mean / std producer and the per-DN STD
- *    table for those frames).       */
+ *    table for those frames), and by hm_merge_u16_std_table* (that table inside the merge of those frames).       */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -324,6 +324,30 @@ int hm_merge_u16_darks(const hm_merge_args* args /*[host]*/, const uint16_t* con
 int hm_merge_u16_darks_describe(const hm_merge_args* args, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16, int bit_depth,
                                 char* buf, int buf_len);
 int64_t hm_merge_u16_darks_algorithmic_bytes(const hm_merge_args* args /*[host]*/, const uint16_t* const* darks_u16 /*[host]*/);
+
+/* hm_merge_u16 / hm_merge_u16_darks with the per-frame stds taken from the per-DN STD table of the camera (hm_noise_moments_*): frame i's
+ * std at element e, channel c is std_table[(DN_i & M) * C + c], M = 2^bit_depth - 1, formed inside the kernels - no std frame exists.
+ * std_table: device pointer (host memory on the host build), (2^bit_depth, C) float64, 8-byte aligned. args->stds must be NULL.
+ * darks_u16: NULL for no hot-pixel pass, else as for hm_merge_u16_darks; a hot frame's std is the k x k median of the mapped neighbourhood,
+ * median_j(std_table[(DN_j & M) * C + c]) - the median of the std frame the table stands for - and its DN the median of the masked DNs.
+ * out_val, out_std and out_sum_w are bit for bit those of hm_merge_u16 / hm_merge_u16_darks given stds[i] = hm_linearize_u16(frame_i,
+ * icrf = std_table).val: both out_kind values, out_sum_w, flat_f64 with flat_std, row tiles, C = 1..4, N = 1..HM_MAX_FRAMES, every variant.
+ * Without out_val the call is hm_merge_u16's sum-of-weights call. Statuses, an earlier rule wins:
+ *   1. HM_EINVAL: hm_merge_u16's rule 1; then args->stds set, NULL std_table, no icrf_diff, no dw_lut; out_val without out_std; with
+ *      darks_u16: args->darks_u8 set or no dark_min_dn.
+ *   2. HM_EALIGN: a frame pointer, then a dark map pointer, that is not 2-byte aligned; then a std_table that is not 8-byte aligned.
+ *   3. / 4. hm_merge_u16_darks's rules 3 and 4; the fit rule of variants 1 and 3 is that of a std call (with out_val).
+ * Tables in LDS, n = 2^bit_depth: "tab=lds" holds {w, dw}[n] and {g, d * std_table}[n C]; "tab=mixed-wdwdg" - the std calls' 8 (2 + C) n
+ * bytes - holds {w, dw}[n] and (d * std_table)[n C] with icrf gathered from global memory; "tab=mixed-wdw" and "tab=global" gather icrf,
+ * icrf_diff and std_table from global memory at the masked index. The pair rule is hm_merge_u16's without the std frames.
+ * hm_merge_u16_std_table_describe: hm_merge_u16_darks_describe's names with "std=lut" in place of "std=1".
+ * hm_merge_u16_std_table_algorithmic_bytes: hm_merge_u16_darks's count of a std call without the 8 N bytes per element of std frames. */
+int hm_merge_u16_std_table(const hm_merge_args* args /*[host]*/, const uint16_t* const* frames_u16 /*[host] N device pointers*/,
+                           const uint16_t* const* darks_u16 /*[host] N device pointers or NULLs, or NULL*/, const double* std_table,
+                           int bit_depth, void* stream);
+int hm_merge_u16_std_table_describe(const hm_merge_args* args, const uint16_t* const* frames_u16, const uint16_t* const* darks_u16,
+                                    const double* std_table, int bit_depth, char* buf, int buf_len);
+int64_t hm_merge_u16_std_table_algorithmic_bytes(const hm_merge_args* args /*[host]*/, const uint16_t* const* darks_u16 /*[host] or NULL*/);
 /* hm_linearize_u8 for uint16 DNs: idx = dn & (2^bit_depth - 1), tables of 2^bit_depth rows gathered from global memory; out_idx
  * (nullable, 2-byte aligned) receives the masked DN. bit_depth outside 9..16: HM_EINVAL; dn / out_idx not 2-byte aligned: HM_EALIGN. */
 int hm_linearize_u16(const uint16_t* dn, const double* std, const double* icrf, const double* icrf_diff,

@@ -1136,6 +1136,85 @@ def case_merge_u16_darks(rng):
     return desc
 
 
+def case_merge_u16_std_table(rng):
+    """the uint16 merge with its stds from the (2**b, C) per-DN std table (engine.plan_merge_u16_std_table, hm_merge_u16_std_table), with or
+    without uint16 dark maps: HIP - any streaming variant, whole images or row tiles with the median's halo, any workspace - against the host
+    build's whole-image result and against the HIP std-frame merge of the materialised stds (no maps), bit for bit. The table is random:
+    not monotone"""
+    c = int(rng.choice([1, 2, 3, 3, 3, 4]))
+    n = int(rng.choice([1, 2, 3, 5, 7, 7, 8, 9, 15, 16, 17, 20, 32]))
+    b = int(rng.integers(9, 17))
+    k = int(rng.choice([3, 3, 5, 7]))
+    h, w = int(rng.integers(1, 48 * args.scale)), int(rng.integers(1, 130 * args.scale))
+    if rng.random() < 0.3:
+        h, w = int(rng.integers(8, 40 * args.scale)), 128 * int(rng.integers(1, 4 * args.scale))
+    use_maps, use_flat, sum_w, f32, val = rng.random() < 0.5, rng.random() < 0.4, rng.random() < 0.3, rng.random() < 0.25, rng.random() < 0.9
+    variant = int(rng.choice([0, 0, 0, -1, 1, 2, 3]))
+    workspace = str(rng.choice(["rec", "rec", "min", "none"]))
+    top = 2 ** b
+    frames = [dn16(rng, (h, w, c), b) for _ in range(n)]
+    table = 0.001 + 0.01 * rng.random((top, c))
+    t = 1e-3 * rng.uniform(1.2, 2.2) ** np.arange(n)
+    g, d = icrf_tables_bits(rng, c, b)
+    darks, mins = None, None
+    if use_maps:
+        dm = rng.integers(0, top // 4, (h, w, c)).astype(np.uint16)
+        dm[rng.random(dm.shape) < rng.choice([0.001, 0.02, 0.3, 0.7])] = top - 3
+        darks = [dm if (i == 0 or rng.random() < 0.6) else None for i in range(n)]
+        mins = [int(rng.choice([top // 2, top - 3, top // 8, top])) for _ in range(n)]
+    desc = (f"merge_u16_std_table n={n} h={h} w={w} c={c} bits={b} k={k} maps={use_maps} flat={use_flat} sum_w={sum_w} f32={f32} val={val} "
+            f"variant={variant} workspace={workspace} mins={mins}")
+    kw = dict(bit_depth=b, want_sum_w=bool(sum_w or not val), want_val=bool(val))
+    if use_maps:
+        kw.update(dark_min=mins, median_k=k)
+    if f32:
+        kw["out_dtype"] = torch.float32
+    if use_flat:
+        kw.update(flat=0.5 + 0.5 * rng.random((h, w, c)), ff_mean=list(rng.uniform(0.6, 0.9, size=c)),
+                  flat_std=0.002 * (1 + rng.random((h, w, c))), ff_std_mean=list(rng.uniform(0.001, 0.003, size=c)))
+    tile = None
+    if rng.random() < 0.33 and h >= 2:
+        r0 = int(rng.integers(0, h - 1)); r1 = int(rng.integers(r0 + 1, h + 1))
+        tile = (r0, r1, int(rng.integers(0, max(0, r0 - k // 2) + 1)), int(rng.integers(min(h, r1 + k // 2), h + 1)))
+    desc += f" tile={tile}"
+
+    def run(eng, conv, tl, v, ws, materialise=False):
+        k2 = dict(kw)
+        rows = slice(None) if tl is None else slice(tl[2], tl[3])
+        out_rows = slice(None) if tl is None else slice(tl[0], tl[1])
+        for name in ("flat", "flat_std"):
+            if name in k2:
+                k2[name] = conv(k2[name][out_rows])
+        if tl is not None:
+            k2.update(height=h, row0=tl[0], rows=tl[1] - tl[0], buf_row0=tl[2])
+        fr = [conv(f[rows]) for f in frames]
+        if materialise:                                                # the route the entry replaces
+            return eng.merge(fr, list(t), g, d, [eng.linearize(f, None, table, bit_depth=b)[0] for f in fr], variant=v, **k2)
+        shared = {}
+        dk = None if darks is None else [None if x is None else shared.setdefault(id(x), conv(x[rows])) for x in darks]
+        plan = eng.plan_merge_u16_std_table(fr, list(t), g, d, table, darks=dk, variant=v, hot_queue=ws != "none", **k2)
+        if ws == "min" and use_maps:
+            plan.args.hot_workspace_bytes = int(nat.hip_lib.hm_merge_hot_workspace_min_bytes(plan.args.rows * w * c))
+        plan.launch()
+        return plan.outputs
+
+    try:
+        a = run(engine, D, tile, variant, workspace)
+    except NotImplementedError:                                        # a forced placement whose tables do not fit: the library's choice instead
+        desc += " (variant refused: 0)"
+        a = run(engine, D, tile, 0, workspace)
+    b_ = run(heng, Hh, None, 0, "none")
+    if tile is not None:
+        b_ = {key: v[tile[0]:tile[1]] for key, v in b_.items()}
+    for key in b_:
+        compare(f"{key}", a[key], b_[key], None)
+    if not use_maps and val:
+        m = run(engine, D, tile, 0, "none", materialise=True)
+        for key in m:
+            compare(f"{key} (materialised stds)", a[key], m[key], None)
+    return desc
+
+
 def case_linearize_u16(rng):
     c = int(rng.choice([1, 2, 3, 4]))
     b = int(rng.choice([9, 10, 12, 14, 16]))
@@ -1156,7 +1235,7 @@ def case_linearize_u16(rng):
     return desc
 
 
-CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
+CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_merge_u16_std_table, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
          (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2), (case_pairs_hist_dn, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]

@@ -1,4 +1,4 @@
-// merge_rules_check.cpp - the host build's four merge _describe entries (camera_linearity_amd/csrc/hm_merge_rules.h through
+// merge_rules_check.cpp - the host build's merge _describe entries (camera_linearity_amd/csrc/hm_merge_rules.h through
 // csrc_host/hm_host.cpp) under AddressSanitizer / UBSan: the NULL, short-struct_size and n_frames = 33 cases, in which the rules must
 // answer without reading past what the caller gave them. A development step for whoever changes that header: a stand-alone program, not
 // part of the library, the package or the test suite, and it needs no GPU.
@@ -60,6 +60,17 @@ int main() {
                 if (size != 100u) g16->out_std = a.out_std;
                 expect("u16 with stds", hm_merge_u16_describe(g16, frames_u16.data(), 10, buf, sizeof buf), rc16);
                 if (size != 100u) hm_merge_u16_algorithmic_bytes(g16);
+                // hm_merge_u16_std_table: the table beside the struct, args->stds NULL, the maps optional
+                const double* table = reinterpret_cast<const double*>(0x700000);
+                std::vector<const uint16_t*> darks_u16(n, nullptr);
+                expect("u16 table, stds set", hm_merge_u16_std_table_describe(g16, frames_u16.data(), nullptr, table, 12, buf, sizeof buf), HM_EINVAL);
+                g16->stds = nullptr;
+                expect("u16 table", hm_merge_u16_std_table_describe(g16, frames_u16.data(), nullptr, table, 12, buf, sizeof buf), rc16);
+                expect("u16 table, NULL table", hm_merge_u16_std_table_describe(g16, frames_u16.data(), nullptr, nullptr, 12, buf, sizeof buf), HM_EINVAL);
+                expect("u16 table, NULL frames", hm_merge_u16_std_table_describe(g16, nullptr, nullptr, table, 12, buf, sizeof buf), HM_EINVAL);
+                expect("u16 table, maps without thresholds", hm_merge_u16_std_table_describe(g16, frames_u16.data(), darks_u16.data(), table, 12, buf, sizeof buf),
+                       HM_EINVAL);
+                if (size != 100u) { hm_merge_u16_std_table_algorithmic_bytes(g16, nullptr); hm_merge_u16_std_table_algorithmic_bytes(g16, darks_u16.data()); }
             }
             g->stds = stds.data();
             expect("merge", hm_merge_describe(g, buf, sizeof buf), short_rc);
@@ -73,7 +84,8 @@ int main() {
     expect("std_table, NULL args", hm_merge_std_table_describe(nullptr, nullptr, buf, sizeof buf), HM_EINVAL);
     expect("std_f32, NULL args", hm_merge_std_f32_describe(nullptr, nullptr, buf, sizeof buf), HM_EINVAL);
     expect("u16, NULL args", hm_merge_u16_describe(nullptr, nullptr, 12, buf, sizeof buf), HM_EINVAL);
-    if (hm_merge_u16_algorithmic_bytes(nullptr)) ++failures;
+    expect("u16 table, NULL args", hm_merge_u16_std_table_describe(nullptr, nullptr, nullptr, nullptr, 12, buf, sizeof buf), HM_EINVAL);
+    if (hm_merge_u16_algorithmic_bytes(nullptr) || hm_merge_u16_std_table_algorithmic_bytes(nullptr, nullptr)) ++failures;
     if (hm_merge_algorithmic_bytes(nullptr) || hm_merge_std_table_algorithmic_bytes(nullptr) || hm_merge_std_f32_algorithmic_bytes(nullptr)) ++failures;
     std::printf(failures ? "merge_rules_check: %d FAILED\n" : "merge_rules_check: ok\n", failures);
     return failures != 0;
