@@ -213,6 +213,10 @@ _SIGNATURES = {
     "hm_de_generation": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_void_p, C.c_void_p]),
+    # the generation on a uint16 DN stack: ... energy_limit, bit_depth, variant, workspace, stream
+    "hm_de_generation_u16": (C.c_int, [C.c_void_p] * 13 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "hm_de_batch_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "hm_de_generation_batch": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,

@@ -1,14 +1,15 @@
 // hm_calibration_rules.h - the argument rules of the ICRF-calibration entries (hm_linearity_energy, hm_linearity_energy_u16,
-// hm_de_generation, hm_de_generation_batch), written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build
-// (hm_energy.hip, hm_energy_u16.hip, hm_de.hip) and the host build (csrc_host/hm_host.cpp) include this file and restate none of it.
+// hm_de_generation, hm_de_generation_u16, hm_de_generation_batch), written once for both builds of the ABI in the manner of
+// hm_merge_rules.h: the device build (hm_energy.hip, hm_energy_u16.hip, hm_de.hip, hm_de_u16.hip) and the host build
+// (csrc_host/hm_host.cpp) include this file and restate none of it.
 // Plain C++17 on hdrmerge.h: no HIP type.
 //
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call.
 //
 // What each build adds after the shared call, and why that changes no call's status:
-//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all four entries it follows rules that are HM_EINVAL too or
+//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all five entries it follows rules that are HM_EINVAL too or
 //           comes last. The energy launch refuses a frame count its pixel-major kernels are not instantiated for (HM_EUNSUPPORTED).
-//   host    hm_de_generation returns HM_OK at once when status[HM_DE_STOP] is set: there `status` is host memory. On the device build
+//   host    hm_de_generation and hm_de_generation_u16 return HM_OK at once when status[HM_DE_STOP] is set: there `status` is host memory. On the device build
 //           the kernels read the flag, so it cannot be a rule of this file.
 #pragma once
 #include "hdrmerge.h"
@@ -87,6 +88,30 @@ inline int check_de_generation(int n_problems, const double* population, const d
     if (!(recombination >= 0.0 && recombination <= 1.0) || !(tol >= 0.0) || energy_limit != energy_limit) return HM_EINVAL;
     if (!population || !energies || !trial || !trial_energies || !icrf || !valid || !status) return HM_EINVAL;
     if (!mean_icrf || !pca || !lower_limits || !upper_limits || !stacks || !exposures) return HM_EINVAL;
+    return HM_OK;
+}
+
+// hm_de_generation_u16: hm_de_generation on a uint16 stack of bit_depth 9..16, rows of 2^bit_depth entries. The statuses, in this order:
+//   1. hm_de_generation's, in its order, but for its limit rule (lower / upper are DNs of the depth here: rule 3 below) - a count, the
+//      shape, the mutation / recombination / tol / energy_limit ranges, a NULL pointer
+//   2. HM_EINVAL       bit_depth outside 9..16, variant outside 0..2                      } check_linearity_energy_u16_counts on
+//   3. HM_EINVAL       lower or upper outside 0 .. 2^bit_depth - 1                         } pop_size candidates: what the energy
+//   4. HM_EUNSUPPORTED variant 1 at a depth whose row does not fit LDS                     } stage would answer, before any launch
+//   5. HM_EALIGN       dn not 2-byte aligned
+inline int check_de_generation_u16(const double* population, const double* energies, const double* trial, const double* trial_energies,
+                                   const double* icrf, const uint8_t* valid, const int64_t* status, const double* mean_icrf,
+                                   const double* pca, const double* lower_limits, const double* upper_limits, const uint16_t* dn,
+                                   const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size,
+                                   int n_params, int64_t max_generations, double mutation_lo, double mutation_hi, double recombination,
+                                   double tol, double energy_limit, int bit_depth, int variant) {
+    int rc = check_de_generation(1, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits,
+                                 upper_limits, dn, exposures, n_pixels, n_frames, 0, 0, pop_size, n_params, max_generations, mutation_lo,
+                                 mutation_hi, recombination, tol, energy_limit);
+    if (rc != HM_OK) return rc;
+    bool empty;                                                               // (never: pop_size >= 4)
+    rc = check_linearity_energy_u16_counts(pop_size, lower, upper, n_pixels, n_frames, bit_depth, variant, empty);
+    if (rc != HM_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(dn) & 1) return HM_EALIGN;
     return HM_OK;
 }
 

@@ -18,9 +18,14 @@
 // energy_batch() (hm_energy.hip), candidates K x S, geometry from the per-problem S; k_de_select_batch, grid = K. The kernel
 // bodies are the single-problem ones (k_de_trial's a shared function, k_de_select's the same text included a second time,
 // hm_de_select_body.h) applied to problem k's slices of the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
+//
+// hm_de_u16.hip (hm_de_generation_u16: rows of 2^bit_depth entries) shares three things with this unit: DeK and de_args (hm_de_args.h), the
+// trial component text (hm_de_trial_component_body.h, included below: its `trial` is this unit's bit for bit) and k_de_select, which it
+// launches through de_select_launch.
 #include "hm_common.h"
 #include "hm_producer_math.h"
 #include "hm_calibration_rules.h"
+#include "hm_de_args.h"
 
 namespace hm {
 
@@ -28,24 +33,6 @@ namespace hm {
 int energy_batch(const uint8_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
                  const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels,
                  int n_frames, double* out_energy, void* workspace, hipStream_t st);
-
-struct DeK {
-    double* pop;              // (S, P) scaled to [0, 1]
-    double* energy;           // (S)
-    double* trial;            // (S, P)
-    double* trial_energy;     // (S)
-    double* icrf;             // (S, 256)
-    uint8_t* valid;           // (S)
-    int64_t* status;          // HM_DE_STATUS_WORDS
-    const double* mean_icrf;  // (256)
-    const double* pca;        // (256, P)
-    const double* lo;         // (P)
-    const double* hi;         // (P)
-    int32_t S, P;
-    uint64_t seed;
-    int64_t max_generations;
-    double m_lo, m_hi, cr, tol, energy_limit;
-};
 
 // the seeds of a batch travel in the kernel arguments, like the stack pointers of its energy stage
 struct DeSeeds {
@@ -72,34 +59,7 @@ __device__ __forceinline__ void de_trial_body(const DeK& a, const int i) {
     const int lane = threadIdx.x, P = a.P, S = a.S;
     const int64_t g = a.status[HM_DE_GENERATION];
 
-    if (lane < P) {
-        const int j = lane;
-        const double ui = a.pop[static_cast<int64_t>(i) * P + j];
-        double tr = ui;                                                   // generation 0 evaluates the initial population: no draws
-        if (g > 0) {
-            const uint64_t key = mix64(a.seed ^ mix64(static_cast<uint64_t>(g)));
-            const double F = a.m_lo + (a.m_hi - a.m_lo) * de_uniform(key, S, 0);
-            // (the clamps never bind for U < 1 and a status block this library wrote: they keep a corrupted one inside the buffers)
-            const int b = min(max(static_cast<int>(a.status[HM_DE_BEST_INDEX]), 0), S - 1);
-            const int pick = min(static_cast<int>(floor(de_uniform(key, i, 0) * (S - 1))), S - 2);
-            const int r0 = pick + (pick >= i);
-            int c = min(static_cast<int>(floor(de_uniform(key, i, 1) * (S - 2))), S - 3);
-            const int lo2 = i < r0 ? i : r0, hi2 = i < r0 ? r0 : i;
-            c += (c >= lo2);
-            c += (c >= hi2);
-            const int r1 = c;
-            const int fill = static_cast<int>(floor(de_uniform(key, i, 2) * P));
-            if (de_uniform(key, i, 3 + j) < a.cr || j == fill) {
-                const double ub = a.pop[static_cast<int64_t>(b) * P + j];
-                const double u0 = a.pop[static_cast<int64_t>(r0) * P + j];
-                const double u1 = a.pop[static_cast<int64_t>(r1) * P + j];
-                tr = ui + F * (((ub - ui) + u0) - u1);
-                if (!(tr >= 0.0 && tr <= 1.0)) tr = de_uniform(key, i, 3 + P + j);   // SciPy's _ensure_constraint
-            }
-        }
-        a.trial[static_cast<int64_t>(i) * P + j] = tr;
-        x[j] = a.lo[j] + tr * (a.hi[j] - a.lo[j]);
-    }
+#include "hm_de_trial_component_body.h"
     __syncthreads();
 
     double row = 0.0;
@@ -148,22 +108,15 @@ __device__ __forceinline__ void de_select_body(const DeK& a) {
 
 __global__ __launch_bounds__(256) void k_de_select_batch(const DeK a, const DeSeeds sd) { de_select_body(problem_of(a, sd, blockIdx.x)); }
 
+// (hm_de_args.h) the select stage of one problem, for this unit's hm_de_generation and for hm_de_u16.hip
+int de_select_launch(const DeK& k, hipStream_t st) {
+    hipLaunchKernelGGL(k_de_select, dim3(1), dim3(256), 0, st, k);
+    return launch_status();
+}
+
 }  // namespace hm
 
 using namespace hm;
-
-// the kernel arguments of a generation, as given (hm_calibration_rules.h judges them first); a batch passes no seed here: its seeds travel in DeSeeds
-static DeK de_args(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
-                   int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits, const double* upper_limits,
-                   int pop_size, int n_params, int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
-                   double recombination, double tol, double energy_limit) {
-    DeK k{};
-    k.pop = population; k.energy = energies; k.trial = trial; k.trial_energy = trial_energies; k.icrf = icrf; k.valid = valid;
-    k.status = status; k.mean_icrf = mean_icrf; k.pca = pca; k.lo = lower_limits; k.hi = upper_limits;
-    k.S = pop_size; k.P = n_params; k.seed = static_cast<uint64_t>(seed); k.max_generations = max_generations;
-    k.m_lo = mutation_lo; k.m_hi = mutation_hi; k.cr = recombination; k.tol = tol; k.energy_limit = energy_limit;
-    return k;
-}
 
 extern "C" size_t hm_de_workspace_bytes(int64_t n_pixels, int n_frames, int pop_size) {
     if (pop_size < 4 || pop_size > HM_DE_MAX_POP) return 0;
@@ -189,8 +142,7 @@ extern "C" int hm_de_generation(double* population, double* energies, double* tr
     rc = hm_linearity_energy(dn, std, exposures, icrf, valid, pop_size, lower, upper, 1, n_pixels, n_frames, nullptr,
                              trial_energies, workspace, stream);
     if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(k_de_select, dim3(1), dim3(256), 0, as_stream(stream), k);
-    return launch_status();
+    return de_select_launch(k, as_stream(stream));
 }
 
 static bool de_batch_shape_ok(int pop_size, int n_problems) {

@@ -23,6 +23,7 @@
 #include "../csrc/hm_producer_math.h"
 #include "../csrc/hm_merge_rules.h"
 #include "../csrc/hm_calibration_rules.h"
+#include "../csrc/hm_de_args.h"
 #include "../csrc/hm_frame_rules.h"
 #include "../csrc/hm_ops_rules.h"
 #include "../csrc/hm_pairs_rules.h"
@@ -1535,6 +1536,41 @@ static inline double de_tree_sum(std::vector<double>& v) {                // the
     return v[0];
 }
 
+// the select stage of a generation g (k_de_select): deferred selection, best index / mean / std, the stop flag, the generation counter
+static void de_select_host(double* population, double* energies, const double* trial, const double* trial_energies, int64_t* status,
+                           int S, int P, int64_t g, int64_t max_generations, double tol, double energy_limit) {
+    size_t n = 1;
+    while (n < static_cast<size_t>(S)) n <<= 1;
+    std::vector<double> v(n, 0.0);
+    for (int i = 0; i < S; ++i) {
+        if (g == 0 || trial_energies[i] <= energies[i]) {
+            energies[i] = trial_energies[i];
+            std::memcpy(population + static_cast<int64_t>(i) * P, trial + static_cast<int64_t>(i) * P, sizeof(double) * P);
+        }
+        v[i] = energies[i];
+    }
+    const double mean = de_tree_sum(v) / S;
+    std::fill(v.begin(), v.end(), 0.0);
+    for (int i = 0; i < S; ++i) { const double d = energies[i] - mean; v[i] = d * d; }
+    const double sd = std::sqrt(de_tree_sum(v) / S);
+    int best = 0;
+    for (int i = 1; i < S; ++i) if (energies[i] < energies[best]) best = i;              // ties: the lowest index
+    int64_t stop = 0;
+    if (g > 0 && (g & 1) == 0) {
+        if (std::isfinite(mean) && sd == sd && sd <= tol * std::fabs(mean)) stop |= HM_DE_STOP_CONVERGED;
+        if (energies[best] < energy_limit) stop |= HM_DE_STOP_ENERGY;
+    }
+    if (g >= max_generations) stop |= HM_DE_STOP_MAX;
+    auto bits = [](double d) { int64_t q; std::memcpy(&q, &d, 8); return q; };
+    status[HM_DE_BEST_INDEX] = best;
+    status[HM_DE_BEST_ENERGY] = bits(energies[best]);
+    status[HM_DE_MEAN] = bits(mean);
+    status[HM_DE_STD] = bits(sd);
+    status[HM_DE_EVALUATIONS] += S;
+    status[HM_DE_STOP] = stop;
+    status[HM_DE_GENERATION] = g + 1;
+}
+
 size_t hm_de_workspace_bytes(int64_t, int, int) { return 0; }
 int hm_de_generation(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
                      int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits,
@@ -1591,36 +1627,54 @@ int hm_de_generation(double* population, double* energies, double* trial, double
     const int rc = hm_linearity_energy(dn, std_, exposures, icrf, valid, S, lower, upper, 1, n_pixels, n_frames, nullptr,
                                        trial_energies, nullptr, nullptr);
     if (rc != HM_OK) return rc;
-    size_t n = 1;
-    while (n < static_cast<size_t>(S)) n <<= 1;
-    std::vector<double> v(n, 0.0);
+    de_select_host(population, energies, trial, trial_energies, status, S, P, g, max_generations, tol, energy_limit);
+    return HM_OK;
+}
+
+// ... on a uint16 stack of 9 to 16 bits, rows of R = 2^bit_depth entries (csrc/hm_de_u16.hip with host pointers): the trial component
+// text the device kernels include, the row walk serially, hm_linearity_energy_u16 above, the selection of hm_de_generation
+int hm_de_generation_u16(double* population, double* energies, double* trial, double* trial_energies, double* icrf, uint8_t* valid,
+                         int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits,
+                         const double* upper_limits, const uint16_t* dn, const double* std_, const double* exposures, int64_t n_pixels,
+                         int n_frames, int lower, int upper, int pop_size, int n_params, int64_t seed, int64_t max_generations,
+                         double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit, int bit_depth,
+                         int variant, void*, void*) {
+    const int rc0 = hm_rules::check_de_generation_u16(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca,
+                                                      lower_limits, upper_limits, dn, exposures, n_pixels, n_frames, lower, upper, pop_size,
+                                                      n_params, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit,
+                                                      bit_depth, variant);
+    if (rc0 != HM_OK) return rc0;
+    if (status[HM_DE_STOP] != 0) return HM_OK;                            // this build's own, as in hm_de_generation
+    using std::floor;
+    using std::max;
+    using std::min;
+    const DeK a = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
+                          pop_size, n_params, seed, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    const int S = pop_size, P = n_params, R = 1 << bit_depth;
+    const int64_t g = status[HM_DE_GENERATION];
     for (int i = 0; i < S; ++i) {
-        if (g == 0 || trial_energies[i] <= energies[i]) {
-            energies[i] = trial_energies[i];
-            std::memcpy(population + static_cast<int64_t>(i) * P, trial + static_cast<int64_t>(i) * P, sizeof(double) * P);
+        double x[HM_DE_MAX_PARAMS];
+        for (int lane = 0; lane < P; ++lane) {
+#include "../csrc/hm_de_trial_component_body.h"
         }
-        v[i] = energies[i];
+        double* row = icrf + static_cast<int64_t>(i) * R;
+        for (int d = 0; d < R; ++d) {
+            double acc = 0.0;
+            for (int j = 0; j < P; ++j) acc += pca[d * P + j] * x[j];
+            row[d] = mean_icrf[d] + acc;
+        }
+        const double shift = 1.0 - row[R - 1];
+        for (int d = 0; d < R; ++d) row[d] += shift;                                     // :166
+        row[0] = 0.0;                                                                    // :167
+        bool ok = true;
+        for (int d = 0; d < R; ++d)
+            if (row[d] > 1.0 || row[d] < 0.0 || (d > 0 && !(row[d] > row[d - 1]))) ok = false;   // :173-179
+        valid[i] = ok;
     }
-    const double mean = de_tree_sum(v) / S;
-    std::fill(v.begin(), v.end(), 0.0);
-    for (int i = 0; i < S; ++i) { const double d = energies[i] - mean; v[i] = d * d; }
-    const double sd = std::sqrt(de_tree_sum(v) / S);
-    int best = 0;
-    for (int i = 1; i < S; ++i) if (energies[i] < energies[best]) best = i;              // ties: the lowest index
-    int64_t stop = 0;
-    if (g > 0 && (g & 1) == 0) {
-        if (std::isfinite(mean) && sd == sd && sd <= tol * std::fabs(mean)) stop |= HM_DE_STOP_CONVERGED;
-        if (energies[best] < energy_limit) stop |= HM_DE_STOP_ENERGY;
-    }
-    if (g >= max_generations) stop |= HM_DE_STOP_MAX;
-    auto bits = [](double d) { int64_t q; std::memcpy(&q, &d, 8); return q; };
-    status[HM_DE_BEST_INDEX] = best;
-    status[HM_DE_BEST_ENERGY] = bits(energies[best]);
-    status[HM_DE_MEAN] = bits(mean);
-    status[HM_DE_STD] = bits(sd);
-    status[HM_DE_EVALUATIONS] += S;
-    status[HM_DE_STOP] = stop;
-    status[HM_DE_GENERATION] = g + 1;
+    const int rc = hm_linearity_energy_u16(dn, std_, exposures, icrf, valid, S, lower, upper, 1, n_pixels, n_frames, bit_depth, variant, nullptr,
+                                           trial_energies, nullptr, nullptr);
+    if (rc != HM_OK) return rc;
+    de_select_host(population, energies, trial, trial_energies, status, S, P, g, max_generations, tol, energy_limit);
     return HM_OK;
 }
 

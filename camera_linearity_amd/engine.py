@@ -1615,8 +1615,8 @@ def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequen
     """The uint8 (X, Y, N) stacks of a calibration - one, or those of a batch: one shape, one device -, their float64 std stacks (None,
     or a sequence whose entries are all None: no stds) and the N exposures, checked in this order
     -> (contiguous stacks, contiguous std stacks | None, exposures as a float64 array). `batch` words the std messages for a batch, whose
-    std stacks must also live on the stacks' device. `dn_dtype`: torch.uint16 for the energy of a stack with a bit depth (linearity_energy
-    alone: the differential-evolution plans take uint8 stacks only)."""
+    std stacks must also live on the stacks' device. `dn_dtype`: torch.uint16 for a stack with a bit depth (linearity_energy(..., bit_depth=)
+    and DEPlanU16; DEPlan and DEBatchPlan take uint8 stacks only)."""
     first = dn_stacks[0]
     for s in dn_stacks:
         _require_cuda(s, "image_value_stack")
@@ -1771,6 +1771,43 @@ class _DEPlanBase:
             if self._stopped(st):
                 return st
 
+    def _init_one(self, dn_stack, std_stack, exposures, mean_icrf, pca, lower_limits, upper_limits, population, lower, upper, seed,
+                  max_generations, mutation, recombination, tol, energy_limit, n_rows, dn_dtype):
+        """The state of ONE problem on a stack of `dn_dtype` DNs with candidate rows of `n_rows` entries (DEPlan: uint8, 256; DEPlanU16:
+        uint16, 2**bit_depth)."""
+        (self.dn,), sd, t = _check_stacks([dn_stack], [std_stack], exposures, dn_dtype=dn_dtype)
+        self.std = None if sd is None else sd[0]
+        dev = dn_stack.device
+        self.device = dev
+        self.host = dev.type != "cuda"
+        N = dn_stack.shape[2]
+        pop = np.ascontiguousarray(np.asarray(population, dtype=np.float64))
+        if pop.ndim != 2:
+            raise ValueError("population must be (S, P) in scaled coordinates [0, 1]")
+        S, P = pop.shape
+        self.S, self.P, self.N = S, P, N
+        self.n_pixels = dn_stack.shape[0] * dn_stack.shape[1]
+        self.mean_icrf = _dev_f64(np.asarray(mean_icrf, dtype=np.float64).reshape(-1), dev)
+        self.pca = _dev_f64(np.asarray(pca, dtype=np.float64), dev)
+        if self.mean_icrf.numel() != n_rows or tuple(self.pca.shape) != (n_rows, P):
+            raise ValueError(f"mean ICRF must have {n_rows} entries and the PCA basis must be ({n_rows}, {P})")
+        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.population = torch.as_tensor(pop, device=dev).clone()
+        self.energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
+        self.trial = torch.zeros((S, P), dtype=_F64, device=dev)
+        self.trial_energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
+        self.icrf = torch.zeros((S, n_rows), dtype=_F64, device=dev)
+        self.valid = torch.zeros(S, dtype=_U8, device=dev)
+        self.status = torch.zeros(nat.HM_DE_STATUS_WORDS, dtype=torch.int64, device=dev)
+        self._t = (C.c_double * N)(*t.tolist())
+        self._scalars = (int(lower), int(upper), int(S), int(P), C.c_int64(int(seed) & 0xFFFFFFFFFFFFFFFF).value,
+                         int(max_generations), float(mutation[0]), float(mutation[1]), float(recombination), float(tol),
+                         float(energy_limit))
+        with nat.host_mode() if self.host else _NoDevice():
+            ws_bytes = nat.lib.hm_de_workspace_bytes(self.n_pixels, N, S)
+        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+
 
 class DEPlan(_DEPlanBase):
     """The state of one channel's differential-evolution solve (population, energies, trial rows, candidate ICRFs, verdicts, status block,
@@ -1785,38 +1822,8 @@ class DEPlan(_DEPlanBase):
     def __init__(self, dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], mean_icrf, pca,
                  lower_limits, upper_limits, population, lower: int, upper: int, seed: int, max_generations: int,
                  mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0):
-        (self.dn,), sd, t = _check_stacks([dn_stack], [std_stack], exposures)
-        self.std = None if sd is None else sd[0]
-        dev = dn_stack.device
-        self.device = dev
-        self.host = dev.type != "cuda"
-        N = dn_stack.shape[2]
-        pop = np.ascontiguousarray(np.asarray(population, dtype=np.float64))
-        if pop.ndim != 2:
-            raise ValueError("population must be (S, P) in scaled coordinates [0, 1]")
-        S, P = pop.shape
-        self.S, self.P, self.N = S, P, N
-        self.n_pixels = dn_stack.shape[0] * dn_stack.shape[1]
-        self.mean_icrf = _dev_f64(np.asarray(mean_icrf, dtype=np.float64).reshape(-1), dev)
-        self.pca = _dev_f64(np.asarray(pca, dtype=np.float64), dev)
-        if self.mean_icrf.numel() != BITS or tuple(self.pca.shape) != (BITS, P):
-            raise ValueError(f"mean ICRF must have {BITS} entries and the PCA basis must be ({BITS}, {P})")
-        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
-        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
-        self.population = torch.as_tensor(pop, device=dev).clone()
-        self.energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
-        self.trial = torch.zeros((S, P), dtype=_F64, device=dev)
-        self.trial_energies = torch.full((S,), float("inf"), dtype=_F64, device=dev)
-        self.icrf = torch.zeros((S, BITS), dtype=_F64, device=dev)
-        self.valid = torch.zeros(S, dtype=_U8, device=dev)
-        self.status = torch.zeros(nat.HM_DE_STATUS_WORDS, dtype=torch.int64, device=dev)
-        self._t = (C.c_double * N)(*t.tolist())
-        self._scalars = (int(lower), int(upper), int(S), int(P), C.c_int64(int(seed) & 0xFFFFFFFFFFFFFFFF).value,
-                         int(max_generations), float(mutation[0]), float(mutation[1]), float(recombination), float(tol),
-                         float(energy_limit))
-        with nat.host_mode() if self.host else _NoDevice():
-            ws_bytes = nat.lib.hm_de_workspace_bytes(self.n_pixels, N, S)
-        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+        self._init_one(dn_stack, std_stack, exposures, mean_icrf, pca, lower_limits, upper_limits, population, lower, upper, seed,
+                       max_generations, mutation, recombination, tol, energy_limit, BITS, _U8)
 
     def _call(self, stream):
         lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
@@ -1833,6 +1840,47 @@ class DEPlan(_DEPlanBase):
 
     def _stopped(self, status: dict) -> bool:
         return bool(status["stop"])
+
+
+class DEPlanU16(_DEPlanBase):
+    """DEPlan for one channel of a 9- to 16-bit camera: a torch.uint16 (X, Y, N) stack with its `bit_depth`, a mean ICRF of 2**bit_depth
+    entries and a PCA basis of (2**bit_depth, P); `lower` / `upper` are DNs of that depth. The state tensors are DEPlan's, `icrf` of shape
+    (S, 2**bit_depth). `launch()` enqueues ONE generation (hm_de_generation_u16: the trial kernel on rows of 2**bit_depth entries,
+    hm_linearity_energy_u16 with `variant` - the placement of a candidate's row, see linearity_energy; the result does not depend on
+    it -, the select kernel); `run()` records and replays a linear chain as DEPlan does. The warm-up launch that precedes the recording
+    is also where the energy entry raises its kernels' dynamic-LDS limit, which is host-side work that stays outside the capture.
+    One problem per plan: uint16 stacks have no batch entry."""
+    _entry = "hm_de_generation_u16"
+
+    def __init__(self, dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], mean_icrf, pca,
+                 lower_limits, upper_limits, population, lower: int, upper: int, seed: int, max_generations: int,
+                 mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0,
+                 bit_depth: Optional[int] = None, variant: int = 0):
+        if isinstance(dn_stack, torch.Tensor) and dn_stack.dtype != _U16:
+            raise TypeError(f"DEPlanU16 takes torch.uint16 digital numbers, got {dn_stack.dtype}: uint8 stacks go to DEPlan")
+        self.bit_depth = _energy_bit_depth(dn_stack, bit_depth)
+        if self.bit_depth is None:                                                   # (not a tensor: _check_stacks raises the TypeError)
+            raise ValueError("DEPlanU16 needs bit_depth (9..16): the number of rows of its candidate ICRFs")
+        n_rows = 2 ** self.bit_depth
+        if not (0 <= int(lower) < n_rows and 0 <= int(upper) < n_rows):
+            raise ValueError(f"lower and upper must be DNs in 0..{n_rows - 1} at bit_depth {self.bit_depth}, got {lower}, {upper}")
+        if int(variant) not in (0, 1, 2):
+            raise ValueError(f"variant must be 0 (the library's choice), 1 (LDS) or 2 (global memory), got {variant}")
+        self.variant = int(variant)
+        self._init_one(dn_stack, std_stack, exposures, mean_icrf, pca, lower_limits, upper_limits, population, lower, upper, seed,
+                       max_generations, mutation, recombination, tol, energy_limit, n_rows, _U16)
+
+    def _call(self, stream):
+        lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
+        return nat.lib.hm_de_generation_u16(self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
+                                            self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
+                                            self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(), self.lo.data_ptr(),
+                                            self.hi.data_ptr(), self.dn.data_ptr(), nat.ptr(self.std), self._t, self.n_pixels, self.N,
+                                            lower, upper, S, P, seed, max_gen, m_lo, m_hi, cr, tol, e_lim, self.bit_depth, self.variant,
+                                            self.workspace.data_ptr(), stream)
+
+    read_status = DEPlan.read_status
+    _stopped = DEPlan._stopped
 
 
 class DEBatchPlan(_DEPlanBase):

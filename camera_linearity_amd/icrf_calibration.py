@@ -15,6 +15,10 @@ with counter-based random numbers (include/hdrmerge.h), started from SciPy's own
 the channels of a calibration (`calibration(..., batched=True)`), restarts of a channel with other seeds (`restarts=R`), or both - run
 in ONE plan (hm_de_generation_batch, engine.DEBatchPlan): one set of launches per generation for all of them, each problem evolving bit
 for bit as it would alone.
+
+A 9- to 16-bit camera's torch.uint16 stacks have the device solver under names of their own, `solve_channel_u16` and `calibration_u16`
+(hm_de_generation_u16, engine.DEPlanU16: rows of 2**bit_depth entries, one problem per plan); `solve_channel` / `calibration` with a
+`bit_depth` stay on SciPy's solver.
 """
 from __future__ import annotations
 
@@ -230,11 +234,13 @@ def _device_defaults():
 
 
 def _scipy_only(bit_depth, solver, batched, restarts):
-    """A calibration with a bit depth runs on SciPy's solver: the device solver's kernels form candidate rows of 256 entries."""
+    """solve_channel / calibration with a bit depth run on SciPy's solver: their device solver forms candidate rows of 256 entries. The
+    device solver for uint16 stacks has entries of its own, solve_channel_u16 and calibration_u16."""
     engine._check_bit_depth(bit_depth)
     if solver == "device" or batched or restarts > 1:
-        raise NotImplementedError('bit_depth needs solver="scipy" without batched=True or restarts > 1: the device solver forms candidate '
-                                  'ICRFs of 256 entries')
+        raise NotImplementedError('bit_depth needs solver="scipy" without batched=True or restarts > 1 here: this device solver forms '
+                                  'candidate ICRFs of 256 entries. The device solver for uint16 stacks is solve_channel_u16 / '
+                                  'calibration_u16 (one problem per plan)')
 
 
 def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values,
@@ -253,7 +259,8 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     restarts=R > 1 (solver="device" only): R solves of the same channel from other seeds - restart r uses restart_seed(seed, r) =
     seed + 1 000 003 r, so restart 0 is the restarts=1 solve, and starts from SciPy's Sobol population for that seed - advanced together
     in one engine.DEBatchPlan; the triple of the restart with the lowest final energy is returned (ties: the lowest r).
-    bit_depth=b (9..16, solver="scipy" only): a torch.uint16 stack of a b-bit camera, mean ICRF and PCA basis of 2**b rows. `data_limits`
+    bit_depth=b (9..16, solver="scipy" only; the device solver for such a stack is solve_channel_u16): a torch.uint16 stack of a b-bit
+    camera, mean ICRF and PCA basis of 2**b rows. `data_limits`
     are DNs of the stack's depth and are not rescaled: the defaults are 8-bit DNs and wrong for any other depth.
     -> (ICRF of the channel (256,) - (2**b,) with bit_depth -, final energy, iterations)."""
     if solver not in ("scipy", "device"):
@@ -322,6 +329,74 @@ def solve_channel(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack
     return icrf, float(func_value), number_of_iterations
 
 
+def _data_limits_u16(data_limits, bit_depth: int):
+    """The DN limits of a uint16 solve: as given (DNs of the stack's depth), or the 8-bit defaults shifted to that depth."""
+    if data_limits is None:
+        return gs.LOWER_LIN_LIM << (bit_depth - 8), gs.UPPER_LIN_LIM << (bit_depth - 8)
+    return int(data_limits[0]), int(data_limits[1])
+
+
+def solve_channel_u16(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values, lower_PCA_limit: float,
+                      upper_PCA_limit: float, bit_depth: int, data_limits=None, energy_limit: float = 0.0, seed: int = 7,
+                      max_iterations: int = 1000, popsize: int = 15, check_every: int = 8, graph: bool = True, tol: float = 0.01,
+                      restarts: int = 1, variant: int = 0):
+    """solve_channel(solver="device") for one channel of a 9- to 16-bit camera: a torch.uint16 stack, a mean ICRF of 2**bit_depth entries
+    and a PCA basis of (2**bit_depth, P). The generations run on the stack's backend (engine.DEPlanU16, hm_de_generation_u16) from SciPy's
+    Sobol population for `seed`, with the 8-bit device solver's strategy, settings and random numbers. `data_limits` are DNs of the stack's
+    depth (default: the 8-bit limits shifted to it); `variant` places a candidate's row for the energy stage (engine.linearity_energy) and
+    does not change the result. restarts=R > 1: R plans one after another, restart r seeded restart_seed(seed, r) - restart 0 is the
+    restarts=1 solve -, the one with the lowest final energy returned (ties: the lowest r); there is no batch entry for uint16 stacks.
+    -> (ICRF of the channel (2**bit_depth,), final energy, iterations)."""
+    bit_depth = engine._check_bit_depth(bit_depth)
+    restarts = int(restarts)
+    if restarts < 1:
+        raise ValueError(f"restarts must be >= 1, got {restarts}")
+    if not isinstance(seed, (int, np.integer)):
+        raise TypeError("solve_channel_u16 needs an integer seed")
+    PCA_array = np.asarray(PCA_array, dtype=np.float64)
+    data_limits = _data_limits_u16(data_limits, bit_depth)
+    limits, x0 = _pca_limits(PCA_array.shape[1], lower_PCA_limit, upper_PCA_limit)
+    lo, hi = np.asarray(limits, dtype=np.float64).T
+    args = (mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, data_limits[0], data_limits[1], True, exposure_values, bit_depth)
+    results = []
+    for r in range(restarts):
+        sd = restart_seed(seed, r)
+        population = _initial_population(limits, x0, args, tol, popsize, dict(vectorized=True, updating="deferred", **_seed_keyword(sd)))
+        plan = _engine_for(image_value_stack).DEPlanU16(image_value_stack, image_std_stack, _host(exposure_values), mean_ICRF_array, PCA_array,
+                                                        lo, hi, population, data_limits[0], data_limits[1], sd, 2 * int(max_iterations),
+                                                        (0.0, 1.95), 0.4, tol, energy_limit, bit_depth, variant)
+        st = plan.run(check_every, graph)
+        u = plan.population[st["best_index"]].cpu().numpy()
+        results.append((_inverse_camera_response_function(mean_ICRF_array, PCA_array, lo + u * (hi - lo), True), st["best_energy"],
+                        st["generation"] // 2))
+    return _best_restart(results)
+
+
+def calibration_u16(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_stacks, channel_image_std_stacks, exposure_values,
+                    lower_PCA_limit: float, upper_PCA_limit: float, bit_depth: int, data_limits=None, energy_limit: float = 0.0,
+                    rng_seed: int = 7, max_iterations: int = 1000, popsize: int = 15, restarts: int = 1, variant: int = 0):
+    """calibration(..., bit_depth=b) with the device solver: torch.uint16 channel stacks of a b-bit camera (initialize_channel_image_stacks(
+    ..., bit_depth=b)), every channel solved by solve_channel_u16 (seed rng_seed + c), one after another. The mean ICRFs are required: the
+    power-law base needs calibration(..., bit_depth=b) on SciPy's solver.
+    -> (ICRF (2**b, C): what engine.merge(..., bit_depth=b) takes, final energies (C,))."""
+    bit_depth = engine._check_bit_depth(bit_depth)
+    C = len(channel_image_value_stacks)
+    if mean_ICRFs is None or len(mean_ICRFs) != C or any(m is None for m in mean_ICRFs):
+        raise ValueError("calibration_u16 needs the mean ICRF of every channel: the device solver forms candidates from a mean ICRF only")
+    results, energies = [], np.zeros(C)
+    for c in range(C):
+        icrf_c, energies[c], _ = solve_channel_u16(mean_ICRFs[c], PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
+                                                   exposure_values, lower_PCA_limit, upper_PCA_limit, bit_depth, data_limits, energy_limit,
+                                                   rng_seed + c, max_iterations, popsize, restarts=restarts, variant=variant)
+        results.append(icrf_c)
+    ICRF = np.stack(results, axis=1)
+    ICRF += (1 - ICRF[-1, :])[None, :]                                           # :390
+    ICRF[0, :] = 0                                                               # :391
+    ICRF[ICRF < 0] = 0                                                           # :395-396
+    ICRF[ICRF > 1] = 1
+    return ICRF, energies
+
+
 def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_stacks, channel_image_std_stacks, exposure_values,
                 lower_PCA_limit: float, upper_PCA_limit: float, initial_function=None,
                 data_limits=(gs.LOWER_LIN_LIM, gs.UPPER_LIN_LIM), energy_limit: float = 0.0, rng_seed: int = 7,
@@ -335,7 +410,7 @@ def calibration(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_
     restart_seed(rng_seed + c, r), the best restart kept per channel. It needs channel stacks of one shape and the same number of PCA
     components for every channel (ValueError otherwise, never a sequential fallback); with restarts=1 the result equals the sequential
     solver="device" one bit for bit. `restarts` > 1 without `batched` runs each channel's restarts as a batch, channel after channel.
-    bit_depth=b (9..16, solver="scipy" only): torch.uint16 channel stacks of a b-bit camera (initialize_channel_image_stacks(...,
+    bit_depth=b (9..16, solver="scipy" only; the device solver is calibration_u16): torch.uint16 channel stacks of a b-bit camera (initialize_channel_image_stacks(...,
     bit_depth=b)), mean ICRFs and PCA bases of 2**b rows; the result has 2**b rows and is what engine.merge(..., bit_depth=b) takes.
     `data_limits` are DNs of the stacks' depth and are not rescaled: the defaults are 8-bit DNs and wrong for any other depth.
     -> (ICRF (BITS, C) interpolated - (2**b, C) with bit_depth -, final energies (C,))."""

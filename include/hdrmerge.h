@@ -47,7 +47,8 @@ extern "C" {
  *    hm_merge_u16*, hm_linearize_u16 and hm_gaussian_weight_lut_bits_host (uint16 DN frames of 9- to 16-bit cameras; HM_BITS below is
  *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames), and by
  *    hm_linearity_energy_u16*, hm_welford_*_u16* and hm_noise_moments_* (the calibration energy, the mean / std producer and the per-DN STD
- *    table for those frames), and by hm_merge_u16_std_table* (that table inside the merge of those frames).       */
+ *    table for those frames), and by hm_merge_u16_std_table* (that table inside the merge of those frames), and by
+ *    hm_de_generation_u16 (the differential-evolution generation on those stacks).       */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -855,6 +856,29 @@ int hm_de_generation(double* population, double* energies, double* trial, double
                      int lower, int upper, int pop_size, int n_params, int64_t seed, int64_t max_generations,
                      double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit,
                      void* workspace, void* stream);
+
+/* ... on a uint16 DN stack of a 9- to 16-bit camera: hm_de_generation's specification - the status block, the stop rule, the random
+ * numbers U(g, i, k), deferred selection, evaluation at generation 0, the contract - with three differences:
+ *   rows       R = 2^bit_depth entries: mean_icrf (R), pca (R, P) row-major, icrf (S, R); candidate: row = mean_icrf + pca @ x,
+ *              row += 1 - row[R - 1], row[0] = 0; valid unless an entry is > 1 or < 0 or the row is not strictly increasing
+ *   limits     lower, upper are DNs of that depth, 0 .. R - 1; dn is (n_pixels, n_frames) uint16, 2-byte aligned, indexed DN & (R - 1)
+ *   energy     hm_linearity_energy_u16 on the S trial rows (use_relative = 1), `variant` handed to it unchanged (0: the library's choice,
+ *              1: the row in LDS, 2: gathered from global memory; the result does not depend on it)
+ * The `trial` array a call writes is bit for bit what hm_de_generation writes from the same population, status block, seed and
+ * settings: the mutation stage does not look at a row. workspace: hm_de_workspace_bytes(n_pixels, n_frames, pop_size) bytes.
+ * Statuses, an earlier one winning, all before any launch: hm_de_generation's in its order (but for its limit rule); HM_EINVAL for
+ * bit_depth outside 9..16 or variant outside 0..2; HM_EINVAL for a limit outside 0 .. R - 1; HM_EUNSUPPORTED for variant 1 where the row
+ * does not fit LDS (15 and 16 bits); HM_EALIGN for a dn that is not 2-byte aligned; (device build) HM_EINVAL for a NULL workspace.
+ * One problem per call: there is no batch entry for uint16 stacks. */
+int hm_de_generation_u16(double* population, double* energies, double* trial, double* trial_energies,
+                         double* icrf /*(S, 2^bit_depth)*/, uint8_t* valid, int64_t* status,
+                         const double* mean_icrf /*(2^b)*/, const double* pca /*(2^b, P) row-major*/,
+                         const double* lower_limits, const double* upper_limits,
+                         const uint16_t* dn, const double* std /*nullable*/, const double* exposures /*[host]*/,
+                         int64_t n_pixels, int n_frames, int lower, int upper, int pop_size, int n_params,
+                         int64_t seed, int64_t max_generations, double mutation_lo, double mutation_hi,
+                         double recombination, double tol, double energy_limit,
+                         int bit_depth, int variant, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The same generation for n_problems independent problems of identical shape - the channels of a calibration, or
