@@ -195,6 +195,9 @@ _SIGNATURES = {
     "hm_tiff_decode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_tiff_decode_strips": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 8
                               + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # 2-, 4- and 8-byte samples: ... samples, bytes_per_sample, big_endian, color_mode, dst, strip_status, workspace, stream
+    "hm_tiff_decode_strips_wide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 9
+                                   + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hm_tiff_encode_bound": (C.c_int64, [C.c_int64]),
     "hm_tiff_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_tiff_encode_payload_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),

@@ -1,4 +1,4 @@
-// hm_tiff_device.hip - TIFF strips decoded on the device: hm_tiff_decode_strips (include/hdrmerge.h). The neighbour of hm_tiff.hip
+// hm_tiff_device.hip - TIFF strips decoded on the device: hm_tiff_decode_strips, hm_tiff_decode_strips_wide (include/hdrmerge.h). The neighbour of hm_tiff.hip
 // (the host decoders, unchanged and still the default path of tiff_io.imread): the file's bytes are uploaded as they are, and two
 // kernels turn them into the frame cv.imread would return.
 //
@@ -14,6 +14,11 @@
 //                       carry between steps), swaps R and B at sample granularity, applies cv.imread's flag (IMREAD_COLOR: grey
 //                       replicated, alpha dropped) and writes the final frame. Compression 1 reads the strips straight from the file
 //                       bytes, so it is the only kernel of that path.
+//   wide_rows_kernel    finish_rows_kernel's geometry for 2-, 4- and 8-byte samples of either byte order (hm_tiff_decode_strips_wide):
+//                       the row itself is hm_tiff_wide_body.h, the text the host build runs serially, with the wave as its lanes -
+//                       sample-wide loads and stores (byte loads only for a strip at an odd offset), the byte reversal, the scan
+//                       modulo 65536 on the reversed values, the R/B swap and imread's >> 8. LZW is byte-oriented: lzw_strips_kernel
+//                       serves both entries as it is.
 //
 // Safety: a strip's [offset, offset + count) is checked against file_len before anything of it is read; the decoder's bounds are those
 // stated in hm_tiff_lzw_body.h; a strip that fails gets a negative status and its rows of dst are left untouched. No atomics, no
@@ -21,6 +26,7 @@
 #include "hm_common.h"
 #include "hm_tiff_lzw_body.h"
 #include "hm_tiff_rules.h"
+#include "hm_tiff_wide_body.h"
 
 static_assert(int(hm_lzw::kEinval) == int(HM_EINVAL) && int(hm_lzw::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_body.h repeats two codes of hdrmerge.h");
 
@@ -180,6 +186,59 @@ __global__ __launch_bounds__(256) void finish_rows_kernel(const FinishGeom f) {
     }
 }
 
+struct WideGeom {
+    StripGeom g;
+    int compression, predictor, spp, big_endian, color_mode;
+    uint8_t* dst;
+};
+
+// the wave as the lanes of hm_tiff_wide_body.h: 64 pixels per step
+struct WaveLanes {
+    int ln;
+    __device__ __forceinline__ int width() const { return hm::kWave; }
+    __device__ __forceinline__ int lane() const { return ln; }
+    __device__ __forceinline__ uint32_t scan_add(uint32_t x) const {
+#pragma unroll
+        for (int d = 1; d < hm::kWave; d <<= 1) {
+            const uint32_t up = __shfl_up(x, d);
+            if (ln >= d) x += up;
+        }
+        return x;
+    }
+    __device__ __forceinline__ uint32_t last(uint32_t x) const { return __shfl(x, hm::kWave - 1); }
+};
+
+template <int B>
+__global__ __launch_bounds__(256) void wide_rows_kernel(const WideGeom f) {
+    const StripGeom& g = f.g;
+    WaveLanes lanes{static_cast<int>(threadIdx.x & 63)};
+    const int out_px_bytes = f.color_mode == 1 ? 3 : f.spp * B;
+    const int64_t out_row_bytes = static_cast<int64_t>(g.width) * out_px_bytes;
+    for (int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); row < g.height; row += static_cast<int64_t>(gridDim.x) * 4) {
+        const int s = static_cast<int>(row / g.rps);
+        const int r = static_cast<int>(row - static_cast<int64_t>(s) * g.rps);
+        const int rows_left = g.height - s * g.rps;
+        const int64_t want = static_cast<int64_t>(rows_left < g.rps ? rows_left : g.rps) * g.row_bytes;
+        const uint8_t* in;
+        int64_t st;
+        if (f.compression == 1) {
+            const int64_t o = g.offsets[s], c = g.counts[s];
+            st = strip_range_ok(o, c, g.file_len) ? (c < want ? c : want) : static_cast<int64_t>(HM_EINVAL);
+            if (r == 0 && lanes.ln == 0) g.status[s] = st;
+            in = g.file + o;
+        } else {
+            st = g.status[s];
+            in = g.workspace + static_cast<int64_t>(s) * g.strip_bytes;
+        }
+        // failed and short strips: as in finish_rows_kernel. A stream that ends inside a sample or a pixel does not give that pixel
+        const int64_t avail = (st < want ? st : want) - static_cast<int64_t>(r) * g.row_bytes;
+        if (avail <= 0) continue;
+        const int npx = avail >= g.row_bytes ? g.width : static_cast<int>(avail / (f.spp * B));
+        hm_tiff_wide::finish_row<B>(in + static_cast<int64_t>(r) * g.row_bytes, npx, f.spp, f.big_endian != 0, f.predictor, f.color_mode,
+                                    f.dst + row * out_row_bytes, lanes);
+    }
+}
+
 }  // namespace
 
 extern "C" size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
@@ -213,5 +272,38 @@ extern "C" int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, cons
         if (e != HM_OK) return e;
     }
     hipLaunchKernelGGL(finish_rows_kernel, dim3(hm::stream_grid(static_cast<int64_t>(height) * hm::kWave, 256, 8)), dim3(256), 0, st, f);
+    return hm::launch_status();
+}
+
+extern "C" int hm_tiff_decode_strips_wide(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts,
+                                          int n_strips, int compression, int predictor, int rows_per_strip, int height, int width,
+                                          int samples, int bytes_per_sample, int big_endian, int color_mode, void* dst,
+                                          int64_t* strip_status, void* workspace, void* stream) {
+    hm_rules::TiffDecodeGeom geom;
+    const int rc = hm_rules::check_tiff_decode_wide(file, file_len, strip_offsets, strip_counts, n_strips, compression, predictor,
+                                                    rows_per_strip, height, width, samples, bytes_per_sample, big_endian, color_mode, dst,
+                                                    strip_status, workspace, geom);
+    if (rc != HM_OK) return rc;
+    hipStream_t st = hm::as_stream(stream);
+    WideGeom f;
+    f.g = StripGeom{file, file_len, strip_offsets, strip_counts, n_strips, geom.rps, height, width, geom.row_bytes, geom.strip_bytes,
+                    strip_status, static_cast<uint8_t*>(workspace)};
+    f.compression = compression;
+    f.predictor = predictor;
+    f.spp = samples;
+    f.big_endian = big_endian;
+    f.color_mode = color_mode;
+    f.dst = static_cast<uint8_t*>(dst);
+    if (compression == 5) {
+        const unsigned grid = static_cast<unsigned>((n_strips + kLzwWaves - 1) / kLzwWaves);
+        if (geom.strip_bytes <= kStageBytes) hipLaunchKernelGGL(lzw_strips_kernel<true>, dim3(grid), dim3(kLzwWaves * hm::kWave), 0, st, f.g);
+        else hipLaunchKernelGGL(lzw_strips_kernel<false>, dim3(grid), dim3(kLzwWaves * hm::kWave), 0, st, f.g);
+        const int e = hm::launch_status();
+        if (e != HM_OK) return e;
+    }
+    const dim3 grid(hm::stream_grid(static_cast<int64_t>(height) * hm::kWave, 256, 8));
+    if (bytes_per_sample == 2) hipLaunchKernelGGL(wide_rows_kernel<2>, grid, dim3(256), 0, st, f);
+    else if (bytes_per_sample == 4) hipLaunchKernelGGL(wide_rows_kernel<4>, grid, dim3(256), 0, st, f);
+    else hipLaunchKernelGGL(wide_rows_kernel<8>, grid, dim3(256), 0, st, f);
     return hm::launch_status();
 }

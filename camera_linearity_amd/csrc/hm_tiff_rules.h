@@ -1,4 +1,4 @@
-// hm_tiff_rules.h - the argument rules and size functions of the TIFF strip entries (hm_tiff_decode_strips, hm_tiff_encode_strips and their
+// hm_tiff_rules.h - the argument rules and size functions of the TIFF strip entries (hm_tiff_decode_strips, hm_tiff_decode_strips_wide, hm_tiff_encode_strips and their
 // _workspace_bytes / _bound / _payload_bytes), written once for both builds of the ABI in the manner of hm_merge_rules.h: the device build
 // (hm_tiff_device.hip, hm_tiff_encode.hip) and the host build (csrc_host/hm_host.cpp) include this file and hold no argument test of
 // their own for these entries. Plain C++17 on hdrmerge.h, the encoder body's size bound and the standard headers: no HIP type.
@@ -59,6 +59,33 @@ inline int check_tiff_decode(const uint8_t* file, int64_t file_len, const int64_
     if (g.row_bytes > kTiffDecodeMaxStripBytes / g.rps) return HM_ESHAPE;
     g.strip_bytes = g.row_bytes * g.rps;
     if (compression == 5 && !workspace) return HM_EINVAL;
+    return HM_OK;
+}
+
+// hm_tiff_decode_strips_wide: the same geometry for 2-, 4- and 8-byte samples of either byte order. 1-byte samples belong to the entry
+// above; Predictor 2 and the 8-bit conversion (color_mode 1) exist for 2-byte samples only. In color_mode 0 dst holds samples and must
+// be aligned to them; in color_mode 1 it holds bytes.
+inline int check_tiff_decode_wide(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts,
+                                  int n_strips, int compression, int predictor, int rows_per_strip, int height, int width, int samples,
+                                  int bytes_per_sample, int big_endian, int color_mode, const void* dst, const int64_t* strip_status,
+                                  const void* workspace, TiffDecodeGeom& g) {
+    g = TiffDecodeGeom{};
+    if (!file || !strip_offsets || !strip_counts || !dst || !strip_status || file_len < 0) return HM_EINVAL;
+    if (n_strips < 1 || rows_per_strip < 1 || height < 1 || width < 1) return HM_EINVAL;
+    if (predictor != 1 && predictor != 2) return HM_EINVAL;
+    if (color_mode != 0 && color_mode != 1) return HM_EINVAL;
+    if (big_endian != 0 && big_endian != 1) return HM_EINVAL;
+    if (compression == 5 && !workspace) return HM_EINVAL;
+    if (compression != 1 && compression != 5) return HM_EUNSUPPORTED;
+    if (samples != 1 && samples != 3 && samples != 4) return HM_EUNSUPPORTED;
+    if (bytes_per_sample != 2 && bytes_per_sample != 4 && bytes_per_sample != 8) return HM_EUNSUPPORTED;
+    if (bytes_per_sample != 2 && (predictor == 2 || color_mode == 1)) return HM_EUNSUPPORTED;
+    g.rps = rows_per_strip < height ? rows_per_strip : height;
+    if (n_strips != (height - 1) / g.rps + 1) return HM_ESHAPE;                    // as above
+    g.row_bytes = static_cast<int64_t>(width) * samples * bytes_per_sample;
+    if (g.row_bytes > kTiffDecodeMaxStripBytes / g.rps) return HM_ESHAPE;
+    g.strip_bytes = g.row_bytes * g.rps;
+    if (color_mode == 0 && !tiff_aligned(dst, static_cast<uintptr_t>(bytes_per_sample))) return HM_EALIGN;
     return HM_OK;
 }
 

@@ -11,8 +11,8 @@
 // Statistics use the reference's own two-pass form.
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
-// hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twin of
-// hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
+// hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twins of
+// hm_tiff_decode_strips_wide (2-, 4- and 8-byte samples) and of hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
 //
 // The argument rules of most entries are a check_* of the ../csrc/hm_*_rules.h headers included below, the copies the device build compiles
 // too; where this build differs the check is called with hm_rules::HOST, and the header's top comment lists the difference.
@@ -31,6 +31,7 @@
 #include "../csrc/hm_tiff_rules.h"
 #include "../csrc/hm_tiff_lzw_body.h"
 #include "../csrc/hm_tiff_lzw_enc_body.h"
+#include "../csrc/hm_tiff_wide_body.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -1769,6 +1770,64 @@ int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* 
                     }
                     out[static_cast<int64_t>(px) * ospp + ch] = v;
                 }
+        }
+    }
+    return HM_OK;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * hm_tiff_decode_strips_wide on the host: 2-, 4- and 8-byte samples of either byte order. The same rule function, status words and
+ * frame as the device entry point; the row is the text both builds share (csrc/hm_tiff_wide_body.h) with one pixel per step, its
+ * loads of samples at odd offsets go through memcpy. One strip per OpenMP iteration, as above.
+ * ------------------------------------------------------------------------------------------ */
+struct TiffSerialLanes {
+    int width() const { return 1; }
+    int lane() const { return 0; }
+    uint32_t scan_add(uint32_t x) const { return x; }
+    uint32_t last(uint32_t x) const { return x; }
+};
+
+int hm_tiff_decode_strips_wide(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts,
+                               int n_strips, int compression, int predictor, int rows_per_strip, int height, int width, int samples,
+                               int bytes_per_sample, int big_endian, int color_mode, void* dst_, int64_t* strip_status,
+                               void* workspace, void* /*stream*/) {
+    hm_rules::TiffDecodeGeom geom;
+    const int rc = hm_rules::check_tiff_decode_wide(file, file_len, strip_offsets, strip_counts, n_strips, compression, predictor,
+                                                    rows_per_strip, height, width, samples, bytes_per_sample, big_endian, color_mode, dst_,
+                                                    strip_status, workspace, geom);
+    if (rc != HM_OK) return rc;
+    const int rps = geom.rps;
+    const int64_t row_bytes = geom.row_bytes, strip_bytes = geom.strip_bytes;
+    const int spp = samples, bps = bytes_per_sample;
+    const int64_t out_row_bytes = static_cast<int64_t>(width) * (color_mode == 1 ? 3 : spp * bps);
+    uint8_t* dst = static_cast<uint8_t*>(dst_);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+#pragma omp parallel for schedule(dynamic)
+    for (int s = 0; s < n_strips; ++s) {
+        const int64_t o = strip_offsets[s], c = strip_counts[s];
+        const int rows = std::min(rps, height - s * rps);
+        const int64_t want = rows * row_bytes;
+        if (!(o >= 0 && c >= 0 && o <= file_len && c <= file_len - o)) { strip_status[s] = HM_EINVAL; continue; }
+        const uint8_t* in = file + o;
+        int64_t st = std::min(c, want);
+        if (compression == 5) {
+            std::vector<hm_lzw::Table> table(1);
+            TiffSerialEmit emit{ws + s * strip_bytes};
+            st = hm_lzw::decode(file + o, c, want, table[0], emit);
+            in = emit.out;
+        }
+        strip_status[s] = st;
+        if (st <= 0) continue;
+        TiffSerialLanes lanes;
+        for (int r = 0; r < rows; ++r) {
+            const int64_t avail = std::min(st, want) - r * row_bytes;
+            if (avail <= 0) break;
+            const int npx = avail >= row_bytes ? width : static_cast<int>(avail / (spp * bps));
+            const uint8_t* row_in = in + r * row_bytes;
+            uint8_t* out = dst + (static_cast<int64_t>(s) * rps + r) * out_row_bytes;
+            if (bps == 2) hm_tiff_wide::finish_row<2>(row_in, npx, spp, big_endian != 0, predictor, color_mode, out, lanes);
+            else if (bps == 4) hm_tiff_wide::finish_row<4>(row_in, npx, spp, big_endian != 0, predictor, color_mode, out, lanes);
+            else hm_tiff_wide::finish_row<8>(row_in, npx, spp, big_endian != 0, predictor, color_mode, out, lanes);
         }
     }
     return HM_OK;

@@ -147,7 +147,8 @@ class ExposureSeries(object):
         return out
 
     def load_value_images(self, bit_64: Optional[bool] = False, device_decode: Optional[bool] = False):
-        """`device_decode=True` (an addition): the TIFFs are decoded on the GPU, ImageSet.load_value_image."""
+        """`device_decode=True` (an addition): the TIFFs are decoded on the GPU, ImageSet.load_value_image - 16-bit and big-endian
+        files and, in load_std_images, float32 ' STD.tif' files included (tiff_io.imread_device(wide_samples=True))."""
         for image_set in self.input_image_sets:
             image_set.load_value_image(bit64=bit_64, device_decode=device_decode)
 

@@ -39,11 +39,13 @@ def _read_image(path: Path, unchanged: bool = False) -> Optional[np.ndarray]:
 
 
 def _read_image_device(path: Path, unchanged: bool, device) -> Optional[torch.Tensor]:
-    """_read_image with the TIFF decoded on the GPU (tiff_io.imread_device): a device tensor, None for a missing file."""
+    """_read_image with the TIFF decoded on the GPU (tiff_io.imread_device): a device tensor, None for a missing file. uint16 and
+    float32 files and big-endian ones are read too (wide_samples=True), as _read_image reads them."""
     path = Path(path)
     if path.suffix == ".npy":
         raise NotImplementedError("device_decode reads TIFF files; .npy arrays load through the default path (device_decode=False)")
-    return tiff_io.imread_device(path, tiff_io.IMREAD_UNCHANGED if unchanged else tiff_io.IMREAD_COLOR, device=device)
+    return tiff_io.imread_device(path, tiff_io.IMREAD_UNCHANGED if unchanged else tiff_io.IMREAD_COLOR, device=device,
+                                 wide_samples=True)
 
 
 def _std_path(path: Path) -> Path:

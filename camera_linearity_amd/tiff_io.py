@@ -30,6 +30,9 @@ Predictor 2, swaps R and B and applies the imread flag on the GPU, so the frame 
 little-endian samples of uint8 (1 / 3 / 4 samples, Predictor 1 / 2) and float64 (1 / 3 samples), Compression 1 and 5,
 strips, chunky; everything else it refuses with NotImplementedError - there is no fallback, `imread` is the host path.
 A `DeviceTiffReader` owns the staging and device buffers and is reused across the files of a series.
+`imread_device(..., wide_samples=True)` widens that family through hm_tiff_decode_strips_wide: uint16 (1 / 3 / 4 samples,
+Predictor 1 / 2, both flags - the DN frames of 9- to 16-bit cameras), float32 and float64 (1 / 3 samples, IMREAD_UNCHANGED), in
+either byte order. Without the keyword every refusal stays as it was.
 
 `imwrite_device` is its writing twin: a uint8 or float64 tensor in device memory goes through hm_tiff_encode_strips
 (csrc/hm_tiff_encode.hip) - optional quantisation to uint8, R/B swap, Predictor 2, LZW, compaction - and comes down as one payload
@@ -396,15 +399,44 @@ def imwrite(path, img, compression: int = 1, predictor: int = 1) -> bool:
 _HOST_PATH = "tiff_io.imread is the host path for such files"
 
 
-def _device_layout_check(lay: TiffLayout, flags: int) -> None:
-    """NotImplementedError for every kind of file the device decoder does not read (it never falls back)."""
-    spp = lay.shape[2]
+def _device_compression_check(lay: TiffLayout) -> None:
     if lay.compression in (8, 32946):
         raise NotImplementedError(f"imread_device: Deflate-compressed strips are not decoded on the device; {_HOST_PATH}")
     if lay.compression == 32773:
         raise NotImplementedError(f"imread_device: PackBits-compressed strips are not decoded on the device; {_HOST_PATH}")
     if lay.compression not in (1, 5):
         raise NotImplementedError(f"imread_device: TIFF compression {lay.compression} is not supported; {_HOST_PATH}")
+
+
+def _device_layout_check_wide(lay: TiffLayout, flags: int) -> None:
+    """_device_layout_check for imread_device(wide_samples=True): uint8 / uint16 (1 / 3 / 4 samples, Predictor 1 / 2, both flags) and
+    float32 / float64 (1 / 3 samples, IMREAD_UNCHANGED) in either byte order."""
+    spp = lay.shape[2]
+    _device_compression_check(lay)
+    kind = lay.dtype.kind + str(lay.dtype.itemsize)
+    if kind not in ("u1", "u2", "f4", "f8"):
+        raise NotImplementedError(f"imread_device: {lay.dtype.name} samples are not decoded on the device (uint8, uint16, float32 and "
+                                  f"float64 are); {_HOST_PATH}")
+    if spp not in ((1, 3, 4) if lay.dtype.kind == "u" else (1, 3)):
+        raise NotImplementedError(f"imread_device: {spp} {lay.dtype.name} samples per pixel are not decoded on the device; {_HOST_PATH}")
+    if lay.predictor not in (1, 2):
+        raise NotImplementedError(f"TIFF predictor {lay.predictor}")
+    if lay.predictor == 2 and lay.dtype.kind != "u":
+        raise NotImplementedError(f"imread_device: the horizontal predictor on floating-point samples is not supported; {_HOST_PATH}")
+    if lay.photometric == 0 and spp == 1 and lay.dtype.kind == "u":
+        raise NotImplementedError(f"imread_device: WhiteIsZero images are not inverted on the device; {_HOST_PATH}")
+    if lay.dtype.kind == "f" and flags != IMREAD_UNCHANGED:
+        raise NotImplementedError(f"imread_device: {lay.dtype.name} samples are read with IMREAD_UNCHANGED only (no 8-bit conversion on "
+                                  f"the device); {_HOST_PATH}")
+
+
+def _device_layout_check(lay: TiffLayout, flags: int, wide_samples: bool = False) -> None:
+    """NotImplementedError for every kind of file the device decoder does not read (it never falls back). `wide_samples` admits what
+    hm_tiff_decode_strips_wide reads: uint16 and float32 samples and big-endian multi-byte ones."""
+    if wide_samples:
+        return _device_layout_check_wide(lay, flags)
+    spp = lay.shape[2]
+    _device_compression_check(lay)
     kind = lay.dtype.kind + str(lay.dtype.itemsize)
     if kind not in ("u1", "f8"):
         raise NotImplementedError(f"imread_device: {lay.dtype.name} samples are not decoded on the device (uint8 and float64 are); "
@@ -452,8 +484,10 @@ class DeviceTiffReader:
             setattr(self, name, t)
         return t
 
-    def read(self, path, flags: int = IMREAD_COLOR):
-        """The frame `imread(path, flags)` returns, as a tensor on the reader's device; None when the file does not exist."""
+    def read(self, path, flags: int = IMREAD_COLOR, wide_samples: bool = False):
+        """The frame `imread(path, flags)` returns, as a tensor on the reader's device; None when the file does not exist.
+        `wide_samples=True` also reads uint16 and float32 samples and big-endian multi-byte ones (hm_tiff_decode_strips_wide): a
+        torch.uint16 / float32 / float64 tensor, uint8 for uint16 samples under IMREAD_COLOR."""
         path = Path(path)
         if not path.exists():
             return None
@@ -475,7 +509,7 @@ class DeviceTiffReader:
                     raise NotImplementedError(f"imread_device: {e}; tiff_io.imread, the host path, refuses this layout too") from e
                 finally:
                     view.release()
-            _device_layout_check(lay, flags)
+            _device_layout_check(lay, flags, wide_samples)
             H, W, spp = lay.shape
             n = lay.n_strips
             if len(lay.counts) < n:
@@ -505,12 +539,22 @@ class DeviceTiffReader:
         out_shape = (H, W) if out_spp == 1 else (H, W, out_spp)
         with torch.cuda.device(device):
             dev[:used].copy_(self._pinned[:used], non_blocking=True)
-            dst = torch.empty(out_shape, dtype=torch.uint8 if bps == 1 else torch.float64, device=device)
             base = dev.data_ptr()
-            nat.check(nat.hip_lib.hm_tiff_decode_strips(base, size, base + cap, base + cap + 8 * n, n, lay.compression, lay.predictor,
-                                                        lay.rows_per_strip, H, W, spp, bps, 1 if color else 0, dst.data_ptr(),
-                                                        status.data_ptr(), nat.ptr(ws), nat.current_stream_ptr(device)),
-                      "hm_tiff_decode_strips")
+            big_endian = bps > 1 and lay.dtype.byteorder == ">"
+            if bps in (2, 4) or big_endian:            # only reached with wide_samples: the layout check refuses them without it
+                kind = lay.dtype.kind + str(bps)
+                dst = torch.empty(out_shape, dtype=torch.uint8 if color else getattr(torch, _WIDE_TORCH_DTYPES[kind]), device=device)
+                nat.check(nat.hip_lib.hm_tiff_decode_strips_wide(base, size, base + cap, base + cap + 8 * n, n, lay.compression,
+                                                                 lay.predictor, lay.rows_per_strip, H, W, spp, bps, int(big_endian),
+                                                                 1 if color else 0, dst.data_ptr(), status.data_ptr(), nat.ptr(ws),
+                                                                 nat.current_stream_ptr(device)),
+                          "hm_tiff_decode_strips_wide")
+            else:
+                dst = torch.empty(out_shape, dtype=torch.uint8 if bps == 1 else torch.float64, device=device)
+                nat.check(nat.hip_lib.hm_tiff_decode_strips(base, size, base + cap, base + cap + 8 * n, n, lay.compression, lay.predictor,
+                                                            lay.rows_per_strip, H, W, spp, bps, 1 if color else 0, dst.data_ptr(),
+                                                            status.data_ptr(), nat.ptr(ws), nat.current_stream_ptr(device)),
+                          "hm_tiff_decode_strips")
             st = status[:n].cpu().numpy()              # waits for the upload and the kernels: the pinned buffer is free again after it
         want = np.minimum(lay.rows_per_strip, H - np.arange(n, dtype=np.int64) * lay.rows_per_strip) * lay.row_bytes
         bad = np.flatnonzero(st < want)
@@ -524,19 +568,21 @@ class DeviceTiffReader:
         return dst
 
 
+_WIDE_TORCH_DTYPES = {"u2": "uint16", "f4": "float32", "f8": "float64"}       # names: torch is imported by the first read
 _readers = {}
 
 
-def imread_device(path, flags: int = IMREAD_COLOR, device=None, reader: Optional[DeviceTiffReader] = None):
+def imread_device(path, flags: int = IMREAD_COLOR, device=None, reader: Optional[DeviceTiffReader] = None, wide_samples: bool = False):
     """`imread` with the decode on the GPU: the same array (values, dtype, shape, BGR order) as a torch tensor in device memory, None
     when the file does not exist. Opt-in; files outside the device decoder's family raise NotImplementedError (no fallback: call
     `imread`), damaged strips raise TiffError naming the strip. `reader` (a DeviceTiffReader) carries the buffers from file to file;
-    without one, a reader per device is kept by the module."""
+    without one, a reader per device is kept by the module. `wide_samples=True` (opt-in) widens the family to uint16 (both flags; a
+    torch.uint16 tensor, or uint8 `>> 8` under IMREAD_COLOR), float32 and big-endian multi-byte samples: DeviceTiffReader.read."""
     if reader is None:
         reader = _readers.get(str(device))
         if reader is None:
             reader = _readers[str(device)] = DeviceTiffReader(device)
-    return reader.read(path, flags)
+    return reader.read(path, flags, wide_samples)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@
  * (csrc_host/hm_host.cpp, plain C++) is the HOST build behind Measurand(use_cupy=False) - the slot of the reference's NumpyMeasurand
  * (modules/measurand_factory.py:10-14): every pointer is then a HOST pointer, `stream` is ignored, calls are synchronous and workspaces
  * may be NULL; the hm_tiff_* decoders are not exported (the two strip decoders are host code of libhdrmerge.so already;
- * hm_tiff_decode_strips, the device path of the same files, and hm_tiff_encode_strips, its writing twin, are in both builds).
+ * hm_tiff_decode_strips / hm_tiff_decode_strips_wide, the device path of the same files, and hm_tiff_encode_strips, its writing twin, are in both builds).
  * The device build never calls or falls back to the host build.
  */
 #ifndef HDRMERGE_H
@@ -964,6 +964,36 @@ size_t hm_tiff_decode_workspace_bytes(int n_strips, int64_t strip_bytes, int com
 int hm_tiff_decode_strips(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts, int n_strips,
                           int compression, int predictor, int rows_per_strip, int height, int width, int samples, int bytes_per_sample,
                           int color_mode, void* dst, int64_t* strip_status, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same call for the wider sample types, in either byte order (csrc/hm_tiff_device.hip; the host build carries it with host
+ * pointers, and both run one text for the row, csrc/hm_tiff_wide_body.h): uint16 frames of 9- to 16-bit cameras, the float32
+ * " STD.tif" companions ImageSet.save_32bit writes, and big-endian float64. Opt-in (tiff_io.imread_device(wide_samples=True)).
+ * Everything not named here is as in hm_tiff_decode_strips: the strips and their range check against file_len, the LZW decode,
+ * strip_status, the workspace (hm_tiff_decode_workspace_bytes with this call's bytes_per_sample in strip_bytes), failed strips that
+ * leave their rows alone. A short strip fills the whole pixels it holds: a stream that ends inside a sample or a pixel does not write
+ * that pixel.
+ *   bytes_per_sample    2 (uint16), 4 (float32) or 8 (float64); 4- and 8-byte samples are moved as bit patterns
+ *   big_endian          0 or 1; 1: every sample is byte-reversed as it is read (an MM file), so dst is in native order either way
+ *   predictor           1, or 2 with 2-byte samples: the differences are undone on sample values modulo 65536 - for a big-endian file
+ *                       after the reversal, like tiff_io.imread
+ *   samples             1, 3 or 4 per pixel
+ *   color_mode          0 = cv.IMREAD_UNCHANGED: dst is (height, width, samples) of the sample type in B,G,R(,A) order (samples == 1:
+ *                       (height, width)); 1 = cv.IMREAD_COLOR, 2-byte samples only: dst is (height, width, 3) uint8 B,G,R with
+ *                       each sample >> 8 - grey replicated, alpha dropped (cv.imread's conversion)
+ *   dst                 aligned to bytes_per_sample in color_mode 0. Strips may sit at any file offset, odd ones included: rows that
+ *                       start on a sample boundary are loaded sample-wide, the others byte by byte
+ * Returns, before any HIP call: HM_EINVAL for a NULL file / strip_offsets / strip_counts / dst / strip_status (or workspace with
+ * compression 5), file_len < 0, n_strips / rows_per_strip / height / width < 1, a predictor other than 1 or 2, a color_mode or a
+ * big_endian other than 0 or 1; HM_EUNSUPPORTED for a compression other than 1 or 5, samples other than 1, 3 or 4, bytes_per_sample
+ * other than 2, 4 or 8 (1 is hm_tiff_decode_strips), and 4- or 8-byte samples with predictor 2 or color_mode 1; HM_ESHAPE for an
+ * n_strips that does not match the geometry and for strips of more than 2^31 bytes; HM_EALIGN for a misaligned dst. An earlier code
+ * wins over a later one.
+ * ------------------------------------------------------------------------------------------ */
+int hm_tiff_decode_strips_wide(const uint8_t* file, int64_t file_len, const int64_t* strip_offsets, const int64_t* strip_counts,
+                               int n_strips, int compression, int predictor, int rows_per_strip, int height, int width, int samples,
+                               int bytes_per_sample, int big_endian, int color_mode, void* dst, int64_t* strip_status,
+                               void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The writing twin (csrc/hm_tiff_encode.hip; the host build carries the same entry points with host pointers, one strip per OpenMP

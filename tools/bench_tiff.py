@@ -5,7 +5,10 @@ installed) for a smooth, a photo-like (gradient + sensor noise) and a noise imag
 Without arguments: the host path (tiff_io.imread) only, no GPU needed. `--device`: the device path (tiff_io.imread_device) next to it, on
 the same files in the same run - timed from the open() of the file to the synchronised status read-back, so the upload of the file's
 bytes is inside - and the wall time of `ExposureSeries.from_dir_path -> load_value_images -> process_HDR_image` for a stack of
-7 x 4096 x 4096 x 3 LZW frames both ways (warm: the second run of each).
+7 x 4096 x 4096 x 3 LZW frames both ways (warm: the second run of each). Then the wide samples (`imread_device(wide_samples=True)`,
+hm_tiff_decode_strips_wide) on 4096 x 4096 x 3 files, host `imread` against the device in the same run: uint16 with 12-bit content,
+photo-like and noise, LZW + Predictor 2 and uncompressed; float32 uncompressed; a big-endian uint16 uncompressed file; and loading a
+7-frame 12-bit LZW stack plus `engine.merge(bit_depth=12)` through both decoders. `--wide-only` (with `--device`) runs only these.
 
 `--write` (needs a GPU; nothing else runs): the way out of HBM. For a smooth, a photo-like and a noise image of 4096 x 4096 x 3 and
 2048 x 2048 x 3 held by a device-backend ImageSet as a float64 value image (values up to 4) with a std image, the wall time from the
@@ -27,6 +30,7 @@ from camera_linearity_amd import tiff_io as T  # noqa: E402
 ap = argparse.ArgumentParser(description=__doc__)
 ap.add_argument("--device", action="store_true", help="also time tiff_io.imread_device and the 7-frame load-and-merge both ways (needs a GPU)")
 ap.add_argument("--write", action="store_true", help="time ImageSet.save_8bit / save_64bit, host path against device_encode=True (needs a GPU)")
+ap.add_argument("--wide-only", action="store_true", help="with --device: only the rows of the wide samples (uint16, float32, big-endian)")
 args = ap.parse_args()
 
 
@@ -130,9 +134,10 @@ if args.write:
 d = pathlib.Path(tempfile.mkdtemp())
 rng = np.random.default_rng(0)
 ramp = np.add.outer(np.arange(4096), np.arange(4096))[:, :, None]
-images = {"smooth": (ramp // 37 % 256 * np.ones(3)).astype(np.uint8),
-          "photo-like": np.clip(ramp / 40 + rng.normal(size=(4096, 4096, 3)) * 2, 0, 255).astype(np.uint8),
-          "noise": (rng.random((4096, 4096, 3)) * 255).astype(np.uint8)}
+images = {} if args.wide_only else {
+    "smooth": (ramp // 37 % 256 * np.ones(3)).astype(np.uint8),
+    "photo-like": np.clip(ramp / 40 + rng.normal(size=(4096, 4096, 3)) * 2, 0, 255).astype(np.uint8),
+    "noise": (rng.random((4096, 4096, 3)) * 255).astype(np.uint8)}
 
 
 def timed_read(path, flag=None):
@@ -142,22 +147,22 @@ def timed_read(path, flag=None):
     return a, time.perf_counter() - t0
 
 
-def timed_read_device(path, flag=T.IMREAD_COLOR):
+def timed_read_device(path, flag=T.IMREAD_COLOR, wide=False):
     import torch
-    T.imread_device(path, flag)                     # warm: buffers grown, kernels loaded, file in the page cache
+    T.imread_device(path, flag, wide_samples=wide)  # warm: buffers grown, kernels loaded, file in the page cache
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    a = T.imread_device(path, flag)                 # returns after the status read-back, which waits for upload and kernels
+    a = T.imread_device(path, flag, wide_samples=wide)     # returns after the status read-back, which waits for upload and kernels
     torch.cuda.synchronize()
     return a.cpu().numpy(), time.perf_counter() - t0
 
 
-def both(path, nbytes, flag=None, expect=None):
+def both(path, nbytes, flag=None, expect=None, wide=False):
     a, dt = timed_read(path, flag)
     assert expect is None or np.array_equal(a, expect)
     text = f"{nbytes / dt / 1e6:.0f} MB/s"
     if args.device:
-        b, dt = timed_read_device(path, T.IMREAD_COLOR if flag is None else flag)
+        b, dt = timed_read_device(path, T.IMREAD_COLOR if flag is None else flag, wide)
         assert np.array_equal(a, b)
         text += f" host, {nbytes / dt / 1e6:.0f} MB/s device"
     return text
@@ -173,11 +178,12 @@ for name, img in images.items():
     except ImportError:
         pass
     print(line, flush=True)
-f64 = rng.random((2048, 2048, 3))
-T.imwrite(d / "f64.tif", f64)
-print(f"float64 2048 x 2048 x 3 uncompressed: {both(d / 'f64.tif', f64.nbytes, T.IMREAD_UNCHANGED, expect=f64)}", flush=True)
+if not args.wide_only:
+    f64 = rng.random((2048, 2048, 3))
+    T.imwrite(d / "f64.tif", f64)
+    print(f"float64 2048 x 2048 x 3 uncompressed: {both(d / 'f64.tif', f64.nbytes, T.IMREAD_UNCHANGED, expect=f64)}", flush=True)
 
-if args.device:
+if args.device and not args.wide_only:
     import torch
     from PIL import Image
     from camera_linearity_amd.exposure_series import ExposureSeries
@@ -208,6 +214,112 @@ if args.device:
         val, t_load, t_all = results[device_decode]
         print(f"7 x 4096 x 4096 x 3 LZW stack, {'device' if device_decode else 'host'} decode: load {t_load * 1e3:.0f} ms, "
               f"load + merge {t_all * 1e3:.0f} ms", flush=True)
+    assert np.array_equal(results[False][0].view(np.uint64), results[True][0].view(np.uint64))       # the same bits either way
+
+
+def write_u16_lzw(path, a):
+    """(H, W, 3) uint16 BGR as an LZW + Predictor 2 file with imwrite's strips. LZW is byte-oriented, so the host build's encoder takes
+    the differenced samples as rows of W * 6 one-byte pixels; the IFD says what they are."""
+    from camera_linearity_amd import _native as nat
+    lib = nat.host_lib()
+    rgb = np.ascontiguousarray(a[:, :, ::-1])
+    stored = rgb.copy()
+    stored[:, 1:] -= rgb[:, :-1]                                        # modulo 65536, per sample
+    H, W, S = a.shape
+    row = W * S * 2
+    rps = T._strip_rows(H, row)
+    n = -(-H // rps)
+    cap = int(lib.hm_tiff_encode_payload_bytes(n, rps * row, 5))
+    buf = np.empty(cap, dtype=np.uint8)
+    ws = np.empty(int(lib.hm_tiff_encode_workspace_bytes(n, rps * row, 5)), dtype=np.uint8)
+    tables = np.empty(2 * n + 1, dtype=np.int64)
+    nat.check(lib.hm_tiff_encode_strips(stored.ctypes.data, 0, 1.0, H, row, 1, rps, 5, 1, buf.ctypes.data, cap, tables.ctypes.data,
+                                        tables.ctypes.data + 8 * (n + 1), ws.ctypes.data, None), "hm_tiff_encode_strips")
+    offsets, counts = tables[:n + 1], tables[n + 1:]
+    assert (counts > 0).all()
+    total = int(offsets[n])
+    head, tail = T._file_frame(H, W, S, np.dtype(np.uint16), rps, offsets, counts, total, 5, 2)
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(memoryview(buf)[:total])
+        f.write(tail)
+
+
+def write_u16_big_endian(path, a):
+    """(H, W, 3) uint16 BGR as an uncompressed big-endian (MM) classic TIFF, one row per strip."""
+    import struct
+    H, W, S = a.shape
+    data = a[:, :, ::-1].astype(">u2").tobytes()
+    row = W * S * 2
+    offsets = [8 + r * row for r in range(H)]
+    entries = [(256, 4, [W]), (257, 4, [H]), (258, 3, [16] * S), (259, 3, [1]), (262, 3, [2]), (273, 4, offsets), (277, 3, [S]),
+               (278, 4, [1]), (279, 4, [row] * H), (284, 3, [1]), (339, 3, [1] * S)]
+    ifd_off = 8 + len(data)
+    extra_off = ifd_off + 2 + 12 * len(entries) + 4
+    ifd, extra = bytearray(struct.pack(">H", len(entries))), bytearray()
+    for tag, typ, vals in entries:
+        payload = struct.pack(">" + {3: "H", 4: "I"}[typ] * len(vals), *vals)
+        ifd += struct.pack(">HHI", tag, typ, len(vals))
+        if len(payload) <= 4:
+            ifd += payload.ljust(4, b"\0")
+        else:
+            ifd += struct.pack(">I", extra_off + len(extra))
+            extra += payload + (b"\0" if len(payload) & 1 else b"")
+    ifd += struct.pack(">I", 0)
+    with open(path, "wb") as f:
+        f.write(struct.pack(">2sHI", b"MM", 42, ifd_off) + data + bytes(ifd) + bytes(extra))
+
+
+if args.device:
+    import torch
+    from camera_linearity_amd import engine
+    U = T.IMREAD_UNCHANGED
+    images16 = {"photo-like": np.clip(ramp * (4095 / 8190) + rng.normal(size=(4096, 4096, 3)) * 8, 0, 4095).astype(np.uint16),
+                "noise": rng.integers(0, 4096, (4096, 4096, 3), dtype=np.uint16)}
+    for name, img in images16.items():
+        T.imwrite(d / "raw16.tif", img)
+        write_u16_lzw(d / "lzw16.tif", img)
+        print(f"uint16 (12-bit content) {name}: uncompressed {both(d / 'raw16.tif', img.nbytes, U, expect=img, wide=True)}, "
+              f"LZW + Predictor 2 ({(d / 'lzw16.tif').stat().st_size / 1e6:.1f} MB file) "
+              f"{both(d / 'lzw16.tif', img.nbytes, U, expect=img, wide=True)}", flush=True)
+    img = images16["photo-like"]
+    write_u16_big_endian(d / "mm16.tif", img)
+    print(f"uint16 big-endian uncompressed: {both(d / 'mm16.tif', img.nbytes, U, expect=img, wide=True)}", flush=True)
+    f32 = rng.random((4096, 4096, 3), dtype=np.float32)
+    T.imwrite(d / "f32.tif", f32)
+    print(f"float32 4096 x 4096 x 3 uncompressed: {both(d / 'f32.tif', f32.nbytes, U, expect=f32, wide=True)}", flush=True)
+    del f32
+    stack16 = d / "stack16"
+    stack16.mkdir()
+    scene = images16["photo-like"].astype(np.float32)
+    paths = []
+    for k in range(7):
+        paths.append(stack16 / f"{2 ** k}ms.tif")
+        write_u16_lzw(paths[-1], np.clip(scene * 2.0 ** (k - 4), 0, 4095).astype(np.uint16))
+    exposures = [2.0 ** k * 1e-3 for k in range(7)]
+    icrf12 = np.stack([np.linspace(0.0, 1.0, 4096) ** 2.2] * 3, axis=1)
+    dev = torch.device("cuda", 0)
+
+    def load_and_merge_u16(device_decode):
+        t0 = time.perf_counter()
+        if device_decode:
+            frames = [T.imread_device(p, U, device=dev, wide_samples=True) for p in paths]
+        else:
+            frames = [torch.as_tensor(T.imread(p, U), device=dev) for p in paths]
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        val = engine.merge(frames, exposures, icrf12, bit_depth=12)["val"]
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        return val.cpu().numpy(), t1 - t0, t2 - t0
+
+    results = {}
+    for device_decode in (False, True):
+        load_and_merge_u16(device_decode)
+        results[device_decode] = load_and_merge_u16(device_decode)
+        val, t_load, t_all = results[device_decode]
+        print(f"7 x 4096 x 4096 x 3 12-bit LZW + Predictor 2 stack, {'device' if device_decode else 'host'} decode: load {t_load * 1e3:.0f} ms, "
+              f"load + engine.merge(bit_depth=12) {t_all * 1e3:.0f} ms", flush=True)
     assert np.array_equal(results[False][0].view(np.uint64), results[True][0].view(np.uint64))       # the same bits either way
 import shutil  # noqa: E402
 shutil.rmtree(d)
