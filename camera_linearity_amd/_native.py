@@ -33,6 +33,7 @@ HM_OK, HM_EINVAL, HM_EUNSUPPORTED, HM_EALIGN, HM_ELAUNCH, HM_ENODEVICE, HM_ESHAP
 HM_OP_ADD, HM_OP_SUB, HM_OP_MUL, HM_OP_DIV, HM_OP_POW = range(5)
 HM_UOP_NEG, HM_UOP_LOG_E, HM_UOP_LOG_10 = range(3)
 HM_OUT_F64, HM_OUT_F32 = 0, 1          # hm_merge_args.out_kind: element type of out_val / out_std
+HM_TIFF_SRC_U16, HM_TIFF_SRC_F32, HM_TIFF_SRC_F64_AS_F32, HM_TIFF_SRC_F64_AS_U16 = range(4)     # hm_tiff_encode_strips_wide: src_kind
 
 
 class HdrMergeError(RuntimeError):
@@ -202,6 +203,8 @@ _SIGNATURES = {
     "hm_tiff_encode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_tiff_encode_payload_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "hm_tiff_encode_strips": (C.c_int, [C.c_void_p, C.c_int, C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    # 2- and 4-byte stored samples: src, src_kind (HM_TIFF_SRC_*), divisor, max_dn, height, width, samples, rows_per_strip, compression, ...
+    "hm_tiff_encode_strips_wide": (C.c_int, [C.c_void_p, C.c_int, C.c_double] + [C.c_int] * 7 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "hm_linearity_energy_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "hm_linearity_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

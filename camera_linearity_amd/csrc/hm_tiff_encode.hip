@@ -6,6 +6,11 @@
 //                       Predictor 2 (a difference to the pixel on the left, which is read again from the source: no scan) and writes
 //                       file order. Compression 1 writes straight into the payload at s * strip_bytes and is the only kernel of that
 //                       path; compression 5 writes the strip's slot of the workspace.
+//   wide_pack_rows_kernel  pack_rows_kernel for hm_tiff_encode_strips_wide: 2- and 4-byte stored samples (uint16 as it is, float32 bit for
+//                       bit, float64 narrowed to float32 or quantised to uint16), the same geometry - one row per wave, 64 pixels per
+//                       spp steps, a grid-stride loop over rows - and the same two destinations. The row is hm_tiff_wide_enc_body.h,
+//                       the text the host build runs too: the lanes of a step store 64 CONSECUTIVE samples (one run of 128 or 256
+//                       bytes per wave store, whatever the pixel size) and gather their source samples from the same run.
 //   lzw_encode_kernel   One strip per WAVE, one wave per workgroup. The encoder state (prefix, next, code width, bit accumulator) is
 //                       wave-uniform and every lane runs the same loop of hm_tiff_lzw_enc_body.h. The lanes do what is parallel: the
 //                       input is fetched 256 bytes at a time (one dword per lane, the next chunk in flight while this one is consumed,
@@ -27,6 +32,7 @@
 #include "hm_common.h"
 #include "hm_tiff_lzw_enc_body.h"
 #include "hm_tiff_rules.h"
+#include "hm_tiff_wide_enc_body.h"
 
 static_assert(int(hm_lzw_enc::kEshape) == int(HM_ESHAPE), "hm_tiff_lzw_enc_body.h repeats a code of hdrmerge.h");
 
@@ -38,13 +44,13 @@ using hm_rules::round16;
 
 struct EncGeom {
     const uint8_t* src;
-    int kind;                                // 0 uint8, 1 float64, 2 float64 -> uint8
+    int kind;                                // 0 uint8, 1 float64, 2 float64 -> uint8; the wide entry: HM_TIFF_SRC_* (0 .. 3)
     double divisor;
     int height, width, spp;
     int rps;                                 // rows per strip, already clamped to the height
     int n_strips;
     int compression, predictor;
-    int out_bps;                             // bytes per stored sample: 1 or 8
+    int out_bps;                             // bytes per stored sample: 1 or 8; the wide entry: 2 or 4
     int64_t row_bytes;                       // of the stored layout
     int64_t strip_bytes;                     // rps * row_bytes
     int64_t in_pitch;                        // compression 5: round16(strip_bytes), the pitch of the packed strips in the workspace
@@ -108,6 +114,32 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const EncGeom g) {
                 q[c] = static_cast<uint8_t>(v - left);
             }
         }
+    }
+}
+
+struct WaveLanes {                           // the lanes of hm_tiff_wide_enc_body.h: one stored sample per lane and step
+    int ln;
+    __device__ __forceinline__ int width() const { return hm::kWave; }
+    __device__ __forceinline__ int lane() const { return ln; }
+};
+
+// max_dn is an argument of its own: EncGeom, and with it the kernels above and below, stay as they were
+__global__ __launch_bounds__(256) void wide_pack_rows_kernel(const EncGeom g, const int max_dn) {
+    WaveLanes lanes{static_cast<int>(threadIdx.x & 63)};
+    const int in_bps = g.kind == HM_TIFF_SRC_U16 ? 2 : (g.kind == HM_TIFF_SRC_F32 ? 4 : 8);
+    for (int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6); row < g.height; row += static_cast<int64_t>(gridDim.x) * 4) {
+        const int s = static_cast<int>(row / g.rps);
+        const int r = static_cast<int>(row - static_cast<int64_t>(s) * g.rps);
+        uint8_t* out = (g.compression == 1 ? g.payload + static_cast<int64_t>(s) * g.strip_bytes
+                                           : g.workspace + static_cast<int64_t>(s) * g.in_pitch) + static_cast<int64_t>(r) * g.row_bytes;
+        if (g.compression == 1 && r == 0 && lanes.ln == 0) {       // the tables of an uncompressed file: known from the geometry
+            g.offsets[s] = static_cast<int64_t>(s) * g.strip_bytes;
+            g.counts[s] = strip_len(g, s);
+            if (s == g.n_strips - 1) g.offsets[g.n_strips] = static_cast<int64_t>(g.height) * g.row_bytes;
+        }
+        const uint8_t* in = g.src + row * g.width * g.spp * in_bps;
+        if (g.out_bps == 2) hm_tiff_wide_enc::pack_row<2>(in, g.kind, g.divisor, max_dn, g.width, g.spp, g.predictor, out, lanes);
+        else hm_tiff_wide_enc::pack_row<4>(in, g.kind, g.divisor, max_dn, g.width, g.spp, g.predictor, out, lanes);
     }
 }
 
@@ -241,13 +273,10 @@ extern "C" size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes
     return hm_rules::tiff_encode_payload_bytes(n_strips, strip_bytes, compression);
 }
 
-extern "C" int hm_tiff_encode_strips(const void* src, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
-                                     int compression, int predictor, void* payload, int64_t payload_cap, void* strip_offsets,
-                                     void* strip_counts, void* workspace, void* stream) {
-    hm_rules::TiffEncodeGeom v;
-    const int rc = hm_rules::check_tiff_encode(src, src_kind, divisor, height, width, samples, rows_per_strip, compression, predictor, payload,
-                                               payload_cap, strip_offsets, strip_counts, workspace, v);
-    if (rc != HM_OK) return rc;
+namespace {
+
+EncGeom make_geom(const hm_rules::TiffEncodeGeom& v, const void* src, int src_kind, double divisor, int height, int width, int samples,
+                  int compression, int predictor, void* payload, void* strip_offsets, void* strip_counts, void* workspace) {
     EncGeom g{};
     g.kind = src_kind; g.divisor = divisor; g.height = height; g.width = width; g.spp = samples;
     g.rps = v.rps; g.n_strips = v.n_strips; g.compression = compression; g.predictor = predictor; g.out_bps = v.out_bps;
@@ -257,10 +286,12 @@ extern "C" int hm_tiff_encode_strips(const void* src, int src_kind, double divis
     g.offsets = static_cast<int64_t*>(strip_offsets);
     g.counts = static_cast<int64_t*>(strip_counts);
     g.workspace = static_cast<uint8_t*>(workspace);
-    hipStream_t st = hm::as_stream(stream);
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(hm::stream_grid(static_cast<int64_t>(height) * hm::kWave, 256, 8)), dim3(256), 0, st, g);
-    int e = hm::launch_status();
-    if (e != HM_OK || compression == 1) return e;
+    return g;
+}
+
+// what follows the pack kernel with Compression 5, the same for both entries: the strips' slots of the workspace -> payload and tables
+int launch_lzw_stage(const EncGeom& g, hipStream_t st) {
+    int e;
     const unsigned strip_grid = static_cast<unsigned>(g.n_strips < kMaxStripGrid ? g.n_strips : kMaxStripGrid);
     hipLaunchKernelGGL(lzw_encode_kernel, dim3(strip_grid), dim3(hm::kWave), 0, st, g);
     if ((e = hm::launch_status()) != HM_OK) return e;
@@ -268,4 +299,39 @@ extern "C" int hm_tiff_encode_strips(const void* src, int src_kind, double divis
     if ((e = hm::launch_status()) != HM_OK) return e;
     hipLaunchKernelGGL(compact_kernel, dim3(strip_grid), dim3(256), 0, st, g);
     return hm::launch_status();
+}
+
+}  // namespace
+
+extern "C" int hm_tiff_encode_strips(const void* src, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
+                                     int compression, int predictor, void* payload, int64_t payload_cap, void* strip_offsets,
+                                     void* strip_counts, void* workspace, void* stream) {
+    hm_rules::TiffEncodeGeom v;
+    const int rc = hm_rules::check_tiff_encode(src, src_kind, divisor, height, width, samples, rows_per_strip, compression, predictor, payload,
+                                               payload_cap, strip_offsets, strip_counts, workspace, v);
+    if (rc != HM_OK) return rc;
+    const EncGeom g = make_geom(v, src, src_kind, divisor, height, width, samples, compression, predictor, payload, strip_offsets, strip_counts,
+                                workspace);
+    hipStream_t st = hm::as_stream(stream);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(hm::stream_grid(static_cast<int64_t>(height) * hm::kWave, 256, 8)), dim3(256), 0, st, g);
+    const int e = hm::launch_status();
+    if (e != HM_OK || compression == 1) return e;
+    return launch_lzw_stage(g, st);
+}
+
+// The pack launch: at most cu_count() * 8 workgroups of 4 waves, one row per wave - taller images run the grid-stride row loop.
+extern "C" int hm_tiff_encode_strips_wide(const void* src, int src_kind, double divisor, int max_dn, int height, int width, int samples,
+                                          int rows_per_strip, int compression, int predictor, void* payload, int64_t payload_cap,
+                                          void* strip_offsets, void* strip_counts, void* workspace, void* stream) {
+    hm_rules::TiffEncodeGeom v;
+    const int rc = hm_rules::check_tiff_encode_wide(src, src_kind, divisor, max_dn, height, width, samples, rows_per_strip, compression, predictor,
+                                                    payload, payload_cap, strip_offsets, strip_counts, workspace, v);
+    if (rc != HM_OK) return rc;
+    const EncGeom g = make_geom(v, src, src_kind, divisor, height, width, samples, compression, predictor, payload, strip_offsets, strip_counts,
+                                workspace);
+    hipStream_t st = hm::as_stream(stream);
+    hipLaunchKernelGGL(wide_pack_rows_kernel, dim3(hm::stream_grid(static_cast<int64_t>(height) * hm::kWave, 256, 8)), dim3(256), 0, st, g, max_dn);
+    const int e = hm::launch_status();
+    if (e != HM_OK || compression == 1) return e;
+    return launch_lzw_stage(g, st);
 }

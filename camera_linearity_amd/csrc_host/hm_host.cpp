@@ -12,7 +12,7 @@
 // Since round 4 also the upstream producers (hm_welford_*, hm_linearity_energy: SURVEY.md 8f-2/3). Not here:
 // the two TIFF strip decoders hm_tiff_lzw_decode / hm_tiff_packbits_decode (host code already, in libhdrmerge.so) and the hm_debug_* probes.
 // hm_tiff_decode_strips, the device path of those files, has its host-pointer twin at the end of this file, followed by the twins of
-// hm_tiff_decode_strips_wide (2-, 4- and 8-byte samples) and of hm_tiff_encode_strips, through which tiff_io.imwrite writes LZW strips.
+// hm_tiff_decode_strips_wide (2-, 4- and 8-byte samples) and of hm_tiff_encode_strips / hm_tiff_encode_strips_wide, through which tiff_io.imwrite writes LZW strips.
 //
 // The argument rules of most entries are a check_* of the ../csrc/hm_*_rules.h headers included below, the copies the device build compiles
 // too; where this build differs the check is called with hm_rules::HOST, and the header's top comment lists the difference.
@@ -32,6 +32,7 @@
 #include "../csrc/hm_tiff_lzw_body.h"
 #include "../csrc/hm_tiff_lzw_enc_body.h"
 #include "../csrc/hm_tiff_wide_body.h"
+#include "../csrc/hm_tiff_wide_enc_body.h"
 
 #ifdef _OPENMP
 #include <omp.h>
@@ -1838,6 +1839,24 @@ int hm_tiff_decode_strips_wide(const uint8_t* file, int64_t file_len, const int6
  * csrc/hm_tiff_encode.hip, with HOST pointers - the encoder body both builds share (csrc/hm_tiff_lzw_enc_body.h) with its serial ops,
  * one strip per OpenMP iteration. tiff_io.imwrite(compression=5) writes through it, and the GPU tests compare the device call with it.
  * ------------------------------------------------------------------------------------------ */
+// the offsets from the counts (each rounded up to 16) and the streams moved from their slots behind the packed strips into the payload
+static void tiff_compact_strips(uint8_t* payload, const uint8_t* streams, int64_t out_pitch, int n_strips, int64_t* offsets,
+                                const int64_t* counts) {
+    int64_t total = 0;
+    for (int s = 0; s < n_strips; ++s) {
+        offsets[s] = total;
+        total += counts[s] > 0 ? hm_rules::round16(counts[s]) : 0;
+    }
+    offsets[n_strips] = total;
+#pragma omp parallel for schedule(dynamic)
+    for (int s = 0; s < n_strips; ++s) {
+        if (counts[s] <= 0) continue;
+        uint8_t* out = payload + offsets[s];
+        memcpy(out, streams + s * out_pitch, static_cast<size_t>(counts[s]));
+        memset(out + counts[s], 0, static_cast<size_t>(hm_rules::round16(counts[s]) - counts[s]));       // the gap: zeros, never stale memory
+    }
+}
+
 int64_t hm_tiff_encode_bound(int64_t strip_bytes) { return hm_rules::tiff_encode_bound(strip_bytes); }
 
 size_t hm_tiff_encode_workspace_bytes(int n_strips, int64_t strip_bytes, int compression) {
@@ -1900,19 +1919,64 @@ int hm_tiff_encode_strips(const void* src_, int src_kind, double divisor, int he
         offsets[n_strips] = static_cast<int64_t>(height) * row_bytes;
         return HM_OK;
     }
-    int64_t total = 0;
-    for (int s = 0; s < n_strips; ++s) {
-        offsets[s] = total;
-        total += counts[s] > 0 ? hm_rules::round16(counts[s]) : 0;
-    }
-    offsets[n_strips] = total;
+    tiff_compact_strips(payload, ws + n_strips * in_pitch, out_pitch, n_strips, offsets, counts);
+    return HM_OK;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * hm_tiff_encode_strips_wide on the host: 2- and 4-byte stored samples. The same rule function, payload layout and bytes as the device
+ * entry point; the row is the text both builds share (csrc/hm_tiff_wide_enc_body.h) with one sample per step, the LZW stage and the
+ * compaction are those of hm_tiff_encode_strips above. One strip per OpenMP iteration. tiff_io.imwrite(wide_samples=True) writes
+ * through it.
+ * ------------------------------------------------------------------------------------------ */
+struct TiffEncSerialLanes {
+    int width() const { return 1; }
+    int lane() const { return 0; }
+};
+
+int hm_tiff_encode_strips_wide(const void* src_, int src_kind, double divisor, int max_dn, int height, int width, int samples,
+                               int rows_per_strip, int compression, int predictor, void* payload_, int64_t payload_cap,
+                               void* strip_offsets, void* strip_counts, void* workspace, void* /*stream*/) {
+    hm_rules::TiffEncodeGeom geom;
+    const int rc = hm_rules::check_tiff_encode_wide(src_, src_kind, divisor, max_dn, height, width, samples, rows_per_strip, compression,
+                                                    predictor, payload_, payload_cap, strip_offsets, strip_counts, workspace, geom);
+    if (rc != HM_OK) return rc;
+    const int rps = geom.rps, n_strips = geom.n_strips;
+    const int64_t row_bytes = geom.row_bytes, strip_bytes = geom.strip_bytes;
+    const uint8_t* src = static_cast<const uint8_t*>(src_);
+    uint8_t* payload = static_cast<uint8_t*>(payload_);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    int64_t* offsets = static_cast<int64_t*>(strip_offsets);
+    int64_t* counts = static_cast<int64_t*>(strip_counts);
+    const int in_bps = src_kind == HM_TIFF_SRC_U16 ? 2 : (src_kind == HM_TIFF_SRC_F32 ? 4 : 8);
+    const int64_t in_row_bytes = static_cast<int64_t>(width) * samples * in_bps;
+    const int64_t bound = geom.bound, in_pitch = geom.in_pitch, out_pitch = geom.out_pitch;
 #pragma omp parallel for schedule(dynamic)
     for (int s = 0; s < n_strips; ++s) {
-        if (counts[s] <= 0) continue;
-        uint8_t* out = payload + offsets[s];
-        memcpy(out, ws + n_strips * in_pitch + s * out_pitch, static_cast<size_t>(counts[s]));
-        memset(out + counts[s], 0, static_cast<size_t>(hm_rules::round16(counts[s]) - counts[s]));       // the gap: zeros, never stale memory
+        const int rows = std::min(rps, height - s * rps);
+        const int64_t len = rows * row_bytes;
+        uint8_t* packed = compression == 1 ? payload + s * strip_bytes : ws + s * in_pitch;
+        TiffEncSerialLanes lanes;
+        for (int r = 0; r < rows; ++r) {
+            const uint8_t* in = src + (static_cast<int64_t>(s) * rps + r) * in_row_bytes;
+            uint8_t* out = packed + r * row_bytes;
+            if (geom.out_bps == 2) hm_tiff_wide_enc::pack_row<2>(in, src_kind, divisor, max_dn, width, samples, predictor, out, lanes);
+            else hm_tiff_wide_enc::pack_row<4>(in, src_kind, divisor, max_dn, width, samples, predictor, out, lanes);
+        }
+        if (compression == 1) {
+            offsets[s] = s * strip_bytes;
+            counts[s] = len;
+        } else {
+            std::vector<hm_lzw_enc::Dict> dict(1);
+            hm_lzw_enc::SerialOps ops;
+            counts[s] = hm_lzw_enc::encode(packed, len, ws + n_strips * in_pitch + s * out_pitch, bound, dict[0], ops);
+        }
     }
+    if (compression == 1) {
+        offsets[n_strips] = static_cast<int64_t>(height) * row_bytes;
+        return HM_OK;
+    }
+    tiff_compact_strips(payload, ws + n_strips * in_pitch, out_pitch, n_strips, offsets, counts);
     return HM_OK;
 }
 

@@ -6,7 +6,7 @@ kernels behind HipMeasurand. File naming grammar (image_set.py:1-9, 542-568): de
 by spaces - '<exposure>ms', 'bf'/'df', '<magnification>x', subject; ' STD' marks an uncertainty image.
 
 IO: the reference reads/writes TIFF through OpenCV. Here `load_value_image` /
-`load_std_image` / `save_64bit` / `save_8bit` go through `tiff_io` (cv.imread / cv.imwrite conventions
+`load_std_image` / `save_64bit` / `save_32bit` / `save_16bit` / `save_8bit` go through `tiff_io` (cv.imread / cv.imwrite conventions
 without cv2: BGR arrays, RGB files, 8-bit and float64 samples) and also accept `.npy` arrays; images can
 always be supplied in memory (`value=`, `std=`, `measurand=`). 8-bit images are kept as uint8 DNs in HBM.
 `load_value_image(device_decode=True)` / `load_std_image(device_decode=True)` (device backend only, opt-in) decode the TIFF on the GPU
@@ -345,16 +345,40 @@ class ImageSet(object):
                 if std is not None:
                     tiff_io.imwrite(base + std_suffix.replace(".tif", f" {name}.tif"), std[:, :, c].astype(np.float64, copy=False))
 
-    def save_32bit(self, save_path: Optional[Path] = None, is_HDR: Optional[bool] = False, separate_channels: Optional[bool] = False):
+    def save_32bit(self, save_path: Optional[Path] = None, is_HDR: Optional[bool] = False, separate_channels: Optional[bool] = False,
+                   device_encode: Optional[bool] = False):
         """float32 TIFFs (an addition: what a merge with out_dtype=torch.float32 produces, and what HDR tools exchange): save_64bit's
         naming and suffixes under '32bit/', written uncompressed by the host tiff_io.imwrite (a float32 image is stored bit for bit;
-        a float64 one is rounded to float32 here). There is no device-encode form: tiff_io.imwrite_device does not take float32.
+        a float64 one is rounded to float32 here).
+        `device_encode=True` (device backend only) writes the same files from the device tensors through
+        tiff_io.imwrite_device: float32 images as they are (wide_samples=True), float64 images narrowed on the device
+        (narrow_to_float32=True) - they never become host arrays. The files are byte-identical to the default's.
         A float32 '<name> STD.tif' written here comes back from load_std_image as float32, and ExposureSeries.process_HDR_image merges
         such std images as they are (hm_merge_std_f32), without widening them to float64 first."""
+        if device_encode:
+            self._require_device_encode()
         file_path = self.path.parent.joinpath("32bit", self.path.name) if save_path is None else Path(save_path)
         file_path.parent.mkdir(parents=True, exist_ok=True)
         base = str(file_path).removesuffix(".tif")
         acq_suffix, std_suffix = (" HDR.tif", " HDR STD.tif") if is_HDR else (".tif", " STD.tif")
+        if device_encode:
+            def write(path, t):
+                if t.dtype == torch.float32:
+                    tiff_io.imwrite_device(path, t.contiguous(), wide_samples=True)
+                else:
+                    tiff_io.imwrite_device(path, t.to(torch.float64).contiguous(), narrow_to_float32=True)
+            if not separate_channels:
+                write(base + acq_suffix, self.measurand.val)
+                if self.measurand.std is not None:
+                    write(base + std_suffix, self.measurand.std)
+            else:
+                for c in range(self.measurand.shape[-1]):
+                    name = gs.CH_STR.get(c, str(c))
+                    one = self.extract([c]).measurand
+                    write(base + acq_suffix.replace(".tif", f" {name}.tif"), one.val)
+                    if one.std is not None:
+                        write(base + std_suffix.replace(".tif", f" {name}.tif"), one.std)
+            return
         val, std = self.host_arrays()
         if not separate_channels:
             tiff_io.imwrite(base + acq_suffix, val.astype(np.float32, copy=False))
@@ -405,6 +429,65 @@ class ImageSet(object):
                     std /= max_float
                 std = np.around(std * gs.MAX_DN).astype(np.uint8)
             tiff_io.imwrite(std_path, std, compression=compression if force_8_bit else 1)
+
+    @staticmethod
+    def _write_16bit_device(path, t: torch.Tensor, max_dn: int, compression: int, predictor: int):
+        """One uint16 file of save_16bit from device memory: the image is scaled by its finite maximum if that exceeds 1 and quantised
+        by the wide encoder's pack kernel (around((v / max) * max_dn))."""
+        t = t.to(torch.float64).contiguous()
+        C = t.shape[-1] if t.dim() == 3 else 1
+        from . import engine
+        max_float = float(engine.channel_minmax(t.reshape(-1, C))[:, 1].max())      # one read-back of 2C doubles
+        tiff_io.imwrite_device(path, t, compression=compression, predictor=predictor,
+                               quantize_divisor=max_float if max_float > 1 else 1.0, quantize_max_dn=max_dn)
+
+    def save_16bit(self, save_path: Optional[Path] = None, bit_depth: int = 16, device_encode: Optional[bool] = False,
+                   compression: int = 1, predictor: int = 1, force_16_bit: Optional[bool] = False):
+        """save_8bit for 9- to 16-bit cameras (an addition): '<name>.tif' under '16bit/' holds uint16 samples
+        around(value * (2**bit_depth - 1)) - value = DN / (2**bit_depth - 1), the convention of engine.weight_luts_host and
+        VideoProcessing(bit_depth=) - with the value image scaled by its finite maximum if that exceeds 1; the std image is written as
+        float64 unless force_16_bit. `compression=5` writes the uint16 files with LZW strips and `predictor=2` with horizontal
+        differencing (the layout camera software gives such frames); a float64 std file stays uncompressed.
+        The default path is NumPy and tiff_io.imwrite(wide_samples=True). `device_encode=True` (device backend only) takes the
+        maximum on the device and quantises, swaps, differences, compresses and compacts there (tiff_io.imwrite_device with
+        quantize_max_dn): the float64 image never reaches the host.
+        For images whose samples are all finite and whose scaled values lie in [0, 2**bit_depth - 1] the files decode to exactly the
+        arrays the default's files decode to. Outside that, the device path is defined - non-finite samples are ignored by the maximum
+        and stored as 0, scaled values outside [0, 65535] wrap modulo 65536 - where the default depends on NumPy's float-to-uint16
+        cast."""
+        if isinstance(bit_depth, bool) or int(bit_depth) != bit_depth or not 1 <= int(bit_depth) <= 16:
+            raise ValueError(f"save_16bit: bit_depth must be an integer in 1..16, got {bit_depth}")
+        max_dn = (1 << int(bit_depth)) - 1
+        if device_encode:
+            self._require_device_encode()
+        file_path = self.path.parent.joinpath("16bit", self.path.name) if save_path is None else Path(save_path)
+        file_path.parent.mkdir(parents=True, exist_ok=True)
+        std_path = str(file_path).removesuffix(".tif") + " STD.tif"
+        if device_encode:
+            m = self.measurand
+            self._write_16bit_device(file_path, m.val, max_dn, compression, predictor)
+            if m.std is not None:
+                if force_16_bit:
+                    self._write_16bit_device(std_path, m.std, max_dn, compression, predictor)
+                else:
+                    tiff_io.imwrite_device(std_path, m.std.to(torch.float64).contiguous())
+            return
+
+        def quantised(a):
+            a = a.astype(np.float64, copy=True)
+            finite = a[np.isfinite(a)]
+            max_float = finite.max() if finite.size else 0.0
+            if max_float > 1:
+                a /= max_float
+            with np.errstate(invalid="ignore"):
+                return np.around(a * max_dn).astype(np.uint16)
+        val, std = self.host_arrays()
+        tiff_io.imwrite(file_path, quantised(val), compression=compression, predictor=predictor, wide_samples=True)
+        if std is not None:
+            if force_16_bit:
+                tiff_io.imwrite(std_path, quantised(std), compression=compression, predictor=predictor, wide_samples=True)
+            else:
+                tiff_io.imwrite(std_path, std.astype(np.float64))
 
     def save_npy(self, save_path: Path, is_HDR: bool = False):
         """Host-side dump of val (and std) as .npy next to each other ('<name> HDR.npy', '<name> HDR STD.npy' -

@@ -10,7 +10,9 @@ that family of files:
          change), Deflate (8 / 32946), PackBits (32773), Predictor 1 / 2 (horizontal differencing)
   write  classic TIFF (BigTIFF when the file would pass 4 GiB), one strip per ~8 KiB of rows like OpenCV,
          uint8 / uint16 / float32 / float64 uncompressed (the default); on request LZW (5, what cv.imwrite's TIFF writer
-         uses) for uint8 / float64 and Predictor 2 for uint8, encoded by the host build's hm_tiff_encode_strips
+         uses) for uint8 / float64 and Predictor 2 for uint8, encoded by the host build's hm_tiff_encode_strips; with
+         `wide_samples=True` also LZW for uint16 / float32 and Predictor 2 for uint16 (hm_tiff_encode_strips_wide) - the layout
+         camera software and cv.imwrite give 9- to 16-bit frames
 
 `imread` / `imwrite` follow OpenCV's channel convention: files hold RGB(A), arrays are BGR(A). OpenCV applies
 the swap on both sides for every depth, so a file written here and read by the reference (or the reverse) shows
@@ -37,7 +39,11 @@ either byte order. Without the keyword every refusal stays as it was.
 `imwrite_device` is its writing twin: a uint8 or float64 tensor in device memory goes through hm_tiff_encode_strips
 (csrc/hm_tiff_encode.hip) - optional quantisation to uint8, R/B swap, Predictor 2, LZW, compaction - and comes down as one payload
 that is written between the header and the IFD. Compression 1 gives the very bytes `imwrite` writes. A `DeviceTiffWriter` owns
-the buffers. Not written on the device: uint16 / float32, tiles, Deflate, PackBits; there is no fallback, `imwrite` is the host path.
+the buffers. `imwrite_device(..., wide_samples=True)` widens that family through hm_tiff_encode_strips_wide: torch.uint16 tensors
+(Predictor 1 / 2) and torch.float32 tensors (bit for bit), Compression 1 and 5; a float64 tensor is stored as float32 with
+`narrow_to_float32=True` (the rounding of ndarray.astype(np.float32)) and as uint16 with `quantize_divisor=d, quantize_max_dn=m`
+(around((v / d) * m), save_16bit's arithmetic). Without these keywords every refusal stays as it was. Not written on the device:
+tiles, Deflate, PackBits, big-endian files, Predictor 2 or 3 on float samples; there is no fallback, `imwrite` is the host path.
 """
 from __future__ import annotations
 
@@ -329,22 +335,30 @@ def _file_frame(H: int, W: int, S: int, dtype: np.dtype, rps: int, offsets, coun
     return head, pad + bytes(ifd) + bytes(extra)
 
 
-def _check_write_options(dtype, compression: int, predictor: int, who: str) -> None:
+def _check_write_options(dtype, compression: int, predictor: int, who: str, wide_samples: bool = False) -> None:
+    """What is not written raises here, before a file or a launch. `wide_samples` admits what hm_tiff_encode_strips_wide encodes: LZW
+    strips of uint16 and float32 samples and the horizontal predictor on uint16."""
     if compression not in (1, 5):
         raise NotImplementedError(f"{who}: TIFF compression {compression} is not written (1 = none and 5 = LZW are)")
     if predictor not in (1, 2):
         raise ValueError(f"{who}: TIFF predictor {predictor} (1 = none and 2 = horizontal differencing exist)")
+    if wide_samples:
+        if predictor == 2 and np.dtype(dtype) not in (np.uint8, np.uint16):
+            raise NotImplementedError(f"{who}: the horizontal predictor is written for uint8 and uint16 samples, not {np.dtype(dtype).name}")
+        return
     if predictor == 2 and np.dtype(dtype) != np.uint8:
         raise NotImplementedError(f"{who}: the horizontal predictor is written for uint8 samples only, not {np.dtype(dtype).name}")
     if (compression, predictor) != (1, 1) and np.dtype(dtype) not in (np.uint8, np.float64):
         raise NotImplementedError(f"{who}: LZW strips and the predictor are written for uint8 and float64 samples, not {np.dtype(dtype).name}")
 
 
-def imwrite(path, img, compression: int = 1, predictor: int = 1) -> bool:
+def imwrite(path, img, compression: int = 1, predictor: int = 1, wide_samples: bool = False) -> bool:
     """cv.imwrite for TIFF files: (H, W) or (H, W, 3|4) arrays in BGR(A) order; uint8 / uint16 / float32 / float64.
     RGB(A) order in the file. Default: uncompressed strips. `compression=5` writes LZW strips (uint8 and float64; what cv.imwrite's TIFF
-    writer does), `predictor=2` horizontal differencing (uint8 only); both go through the host build's hm_tiff_encode_strips. What is
-    not written raises ValueError / NotImplementedError before the file is created."""
+    writer does), `predictor=2` horizontal differencing (uint8 only); both go through the host build's hm_tiff_encode_strips.
+    `wide_samples=True` (opt-in) also takes `compression=5` for uint16 and float32 and `predictor=2` for uint16 (differences modulo
+    65536), through the host build's hm_tiff_encode_strips_wide; without it every refusal is as it was. What is not written raises
+    ValueError / NotImplementedError before the file is created."""
     a = np.asarray(img)
     if a.dtype == np.bool_:
         a = a.astype(np.uint8)
@@ -357,7 +371,7 @@ def imwrite(path, img, compression: int = 1, predictor: int = 1) -> bool:
     H, W, S = a.shape
     if H == 0 or W == 0:
         raise ValueError("imwrite: empty image")
-    _check_write_options(a.dtype, compression, predictor, "imwrite")
+    _check_write_options(a.dtype, compression, predictor, "imwrite", wide_samples)
     row_bytes = W * S * a.dtype.itemsize
     rps = _strip_rows(H, row_bytes)
     n_strips = (H + rps - 1) // rps
@@ -377,9 +391,15 @@ def imwrite(path, img, compression: int = 1, predictor: int = 1) -> bool:
         buf = np.empty(cap, dtype=np.uint8)
         ws = np.empty(max(1, int(lib.hm_tiff_encode_workspace_bytes(n_strips, strip_bytes, compression))), dtype=np.uint8)
         tables = np.empty(2 * n_strips + 1, dtype=np.int64)
-        nat.check(lib.hm_tiff_encode_strips(a.ctypes.data, 0 if a.dtype == np.uint8 else 1, 1.0, H, W, S, rps, compression, predictor,
-                                            buf.ctypes.data, cap, tables.ctypes.data, tables.ctypes.data + 8 * (n_strips + 1),
-                                            ws.ctypes.data, None), "hm_tiff_encode_strips")
+        if a.dtype in (np.uint16, np.float32):         # only reached with wide_samples: the option check refuses them without it
+            nat.check(lib.hm_tiff_encode_strips_wide(a.ctypes.data, nat.HM_TIFF_SRC_U16 if a.dtype == np.uint16 else nat.HM_TIFF_SRC_F32,
+                                                     1.0, 0, H, W, S, rps, compression, predictor, buf.ctypes.data, cap, tables.ctypes.data,
+                                                     tables.ctypes.data + 8 * (n_strips + 1), ws.ctypes.data, None),
+                      "hm_tiff_encode_strips_wide")
+        else:
+            nat.check(lib.hm_tiff_encode_strips(a.ctypes.data, 0 if a.dtype == np.uint8 else 1, 1.0, H, W, S, rps, compression, predictor,
+                                                buf.ctypes.data, cap, tables.ctypes.data, tables.ctypes.data + 8 * (n_strips + 1),
+                                                ws.ctypes.data, None), "hm_tiff_encode_strips")
         offsets, counts = tables[:n_strips + 1], tables[n_strips + 1:]
         if (counts < 0).any():
             raise TiffError(f"strip {int(np.flatnonzero(counts < 0)[0])} could not be encoded ({nat.strerror(int(counts[counts < 0][0]))})")
@@ -586,7 +606,7 @@ def imread_device(path, flags: int = IMREAD_COLOR, device=None, reader: Optional
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The device path of writing (opt-in): hm_tiff_encode_strips
+# The device path of writing (opt-in): hm_tiff_encode_strips, hm_tiff_encode_strips_wide
 # ---------------------------------------------------------------------------------------------------------------------
 class DeviceTiffWriter:
     """The buffers of the device writer, kept and grown across files like DeviceTiffReader's: the device payload, the encoder's
@@ -601,18 +621,25 @@ class DeviceTiffWriter:
 
     _grow = DeviceTiffReader._grow
 
-    def write(self, path, tensor, compression: int = 1, predictor: int = 1, quantize_divisor: Optional[float] = None) -> bool:
+    def write(self, path, tensor, compression: int = 1, predictor: int = 1, quantize_divisor: Optional[float] = None,
+              wide_samples: bool = False, narrow_to_float32: bool = False, quantize_max_dn: Optional[int] = None) -> bool:
         """`imwrite(path, array)` for a tensor in device memory: (H, W) or (H, W, 1|3|4), contiguous, uint8 or float64, BGR(A) order.
         `quantize_divisor=d` (float64 tensors) stores uint8 samples around((v / d) * 255) - save_8bit's arithmetic; non-finite samples
-        give 0, results outside 0..255 wrap modulo 256. Nothing falls back: what the device does not write raises."""
+        give 0, results outside 0..255 wrap modulo 256. Nothing falls back: what the device does not write raises.
+        Through hm_tiff_encode_strips_wide (all opt-in): `wide_samples=True` also takes torch.uint16 (stored as it is, Predictor 1 / 2)
+        and torch.float32 (stored bit for bit) tensors; `narrow_to_float32=True` stores a float64 tensor as float32, rounded like
+        ndarray.astype(np.float32); `quantize_max_dn=m` (1 .. 65535, with `quantize_divisor=d`, 1.0 if not given) stores a float64
+        tensor as uint16 samples around((v / d) * m) - save_16bit's arithmetic; non-finite samples give 0, results outside 0..65535
+        wrap modulo 65536 - with Predictor 1 / 2."""
         import torch
         if not isinstance(tensor, torch.Tensor):
             raise TypeError(f"imwrite_device: a torch tensor in device memory is required, got {type(tensor).__name__}; "
                             "tiff_io.imwrite is the host path")
         if tensor.device.type != "cuda":
             raise ValueError("imwrite_device: the tensor is in host memory; tiff_io.imwrite is the host path")
-        if tensor.dtype not in (torch.uint8, torch.float64):
-            raise TypeError(f"imwrite_device: uint8 and float64 tensors are written, not {tensor.dtype}; tiff_io.imwrite is the host path")
+        if tensor.dtype not in ((torch.uint8, torch.float64, torch.uint16, torch.float32) if wide_samples else (torch.uint8, torch.float64)):
+            raise TypeError(f"imwrite_device: uint8 and float64 tensors are written (uint16 and float32 with wide_samples=True), not "
+                            f"{tensor.dtype}; tiff_io.imwrite is the host path")
         if tensor.dim() not in (2, 3) or (tensor.dim() == 3 and tensor.shape[2] not in (1, 3, 4)) or tensor.numel() == 0:
             raise ValueError(f"imwrite_device: unsupported tensor shape {tuple(tensor.shape)}")
         if not tensor.is_contiguous():
@@ -623,9 +650,32 @@ class DeviceTiffWriter:
             quantize_divisor = float(quantize_divisor)
             if not (0.0 < quantize_divisor < float("inf")):
                 raise ValueError(f"imwrite_device: quantize_divisor must be finite and positive, got {quantize_divisor}")
-        kind = 0 if tensor.dtype == torch.uint8 else (1 if quantize_divisor is None else 2)
-        out_dtype = np.dtype(np.float64 if kind == 1 else np.uint8)
-        _check_write_options(out_dtype, compression, predictor, "imwrite_device")
+        if quantize_max_dn is not None:
+            if tensor.dtype != torch.float64:
+                raise ValueError("imwrite_device: quantize_max_dn applies to float64 tensors")
+            if isinstance(quantize_max_dn, bool) or int(quantize_max_dn) != quantize_max_dn or not 1 <= int(quantize_max_dn) <= 65535:
+                raise ValueError(f"imwrite_device: quantize_max_dn must be an integer in 1..65535 (2**bit_depth - 1), got {quantize_max_dn}")
+            quantize_max_dn = int(quantize_max_dn)
+        if narrow_to_float32:
+            if tensor.dtype != torch.float64:
+                raise ValueError("imwrite_device: narrow_to_float32 applies to float64 tensors")
+            if quantize_divisor is not None or quantize_max_dn is not None:
+                raise ValueError("imwrite_device: narrow_to_float32 and quantisation exclude each other")
+        nat = _native()
+        wide = True                                 # hm_tiff_encode_strips_wide; `kind` is the entry's own src_kind
+        if tensor.dtype == torch.uint16:
+            kind, out_dtype = nat.HM_TIFF_SRC_U16, np.dtype(np.uint16)
+        elif tensor.dtype == torch.float32:
+            kind, out_dtype = nat.HM_TIFF_SRC_F32, np.dtype(np.float32)
+        elif narrow_to_float32:
+            kind, out_dtype = nat.HM_TIFF_SRC_F64_AS_F32, np.dtype(np.float32)
+        elif quantize_max_dn is not None:
+            kind, out_dtype = nat.HM_TIFF_SRC_F64_AS_U16, np.dtype(np.uint16)
+        else:
+            wide = False
+            kind = 0 if tensor.dtype == torch.uint8 else (1 if quantize_divisor is None else 2)
+            out_dtype = np.dtype(np.float64 if kind == 1 else np.uint8)
+        _check_write_options(out_dtype, compression, predictor, "imwrite_device", wide)
         if self._device_arg is not None and torch.device(self._device_arg).index not in (None, tensor.device.index):
             raise ValueError(f"imwrite_device: the writer belongs to {self._device_arg}, the tensor is on {tensor.device}")
         device = self.device = tensor.device
@@ -635,7 +685,6 @@ class DeviceTiffWriter:
         rps = _strip_rows(H, row_bytes)
         n = (H + rps - 1) // rps
         strip_bytes = rps * row_bytes
-        nat = _native()
         lib = nat.hip_lib
         cap = int(lib.hm_tiff_encode_payload_bytes(n, strip_bytes, compression))
         if cap == 0:
@@ -645,10 +694,17 @@ class DeviceTiffWriter:
         ws = self._grow("_ws", ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
         tables = self._grow("_tables", 2 * n + 1, dtype=torch.int64, device=device)
         with torch.cuda.device(device):
-            nat.check(lib.hm_tiff_encode_strips(tensor.data_ptr(), kind, 1.0 if quantize_divisor is None else quantize_divisor, H, W, S,
-                                                rps, compression, predictor, payload.data_ptr(), cap, tables.data_ptr(),
-                                                tables.data_ptr() + 8 * (n + 1), nat.ptr(ws), nat.current_stream_ptr(device)),
-                      "hm_tiff_encode_strips")
+            divisor = 1.0 if quantize_divisor is None else quantize_divisor
+            if wide:
+                nat.check(lib.hm_tiff_encode_strips_wide(tensor.data_ptr(), kind, divisor, quantize_max_dn or 0, H, W, S, rps, compression,
+                                                         predictor, payload.data_ptr(), cap, tables.data_ptr(),
+                                                         tables.data_ptr() + 8 * (n + 1), nat.ptr(ws), nat.current_stream_ptr(device)),
+                          "hm_tiff_encode_strips_wide")
+            else:
+                nat.check(lib.hm_tiff_encode_strips(tensor.data_ptr(), kind, divisor, H, W, S, rps, compression, predictor,
+                                                    payload.data_ptr(), cap, tables.data_ptr(), tables.data_ptr() + 8 * (n + 1),
+                                                    nat.ptr(ws), nat.current_stream_ptr(device)),
+                          "hm_tiff_encode_strips")
             if compression == 1:
                 counts = [row_bytes * min(rps, H - s * rps) for s in range(n)]
                 offsets = [s * strip_bytes for s in range(n)]
@@ -675,15 +731,17 @@ _writers = {}
 
 
 def imwrite_device(path, tensor, compression: int = 1, predictor: int = 1, quantize_divisor: Optional[float] = None,
-                   writer: Optional[DeviceTiffWriter] = None) -> bool:
+                   writer: Optional[DeviceTiffWriter] = None, wide_samples: bool = False, narrow_to_float32: bool = False,
+                   quantize_max_dn: Optional[int] = None) -> bool:
     """`imwrite` with the encode on the GPU (hm_tiff_encode_strips): the tensor - contiguous, in device memory, uint8 or float64,
     (H, W) or (H, W, 1|3|4) in BGR(A) order - becomes the strips of the file on the device and comes down as one payload. With
     compression 1 the file is byte-identical to imwrite's. Opt-in; a host tensor, another dtype or a non-contiguous tensor raises (no
     fallback: call `imwrite`). `writer` (a DeviceTiffWriter) carries the buffers from file to file; without one, a writer per device is
-    kept by the module."""
+    kept by the module. `wide_samples=True` (opt-in) also takes torch.uint16 and torch.float32 tensors, `narrow_to_float32=True` stores a
+    float64 tensor as float32 and `quantize_max_dn=m` stores it as uint16 (hm_tiff_encode_strips_wide): DeviceTiffWriter.write."""
     if writer is None:
         key = str(getattr(tensor, "device", None))
         writer = _writers.get(key)
         if writer is None:
             writer = _writers[key] = DeviceTiffWriter()
-    return writer.write(path, tensor, compression, predictor, quantize_divisor)
+    return writer.write(path, tensor, compression, predictor, quantize_divisor, wide_samples, narrow_to_float32, quantize_max_dn)

@@ -26,7 +26,7 @@
  * (csrc_host/hm_host.cpp, plain C++) is the HOST build behind Measurand(use_cupy=False) - the slot of the reference's NumpyMeasurand
  * (modules/measurand_factory.py:10-14): every pointer is then a HOST pointer, `stream` is ignored, calls are synchronous and workspaces
  * may be NULL; the hm_tiff_* decoders are not exported (the two strip decoders are host code of libhdrmerge.so already;
- * hm_tiff_decode_strips / hm_tiff_decode_strips_wide, the device path of the same files, and hm_tiff_encode_strips, its writing twin, are in both builds).
+ * hm_tiff_decode_strips / hm_tiff_decode_strips_wide, the device path of the same files, and hm_tiff_encode_strips / hm_tiff_encode_strips_wide, their writing twins, are in both builds).
  * The device build never calls or falls back to the host build.
  */
 #ifndef HDRMERGE_H
@@ -1033,6 +1033,41 @@ size_t hm_tiff_encode_payload_bytes(int n_strips, int64_t strip_bytes, int compr
 int hm_tiff_encode_strips(const void* src, int src_kind, double divisor, int height, int width, int samples, int rows_per_strip,
                           int compression, int predictor, void* payload, int64_t payload_cap, void* strip_offsets /* n_strips + 1 int64 */,
                           void* strip_counts /* n_strips int64 */, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same call for the wider stored samples (csrc/hm_tiff_encode.hip; the host build carries it with host pointers, and both run one
+ * text for the row, csrc/hm_tiff_wide_enc_body.h): the uint16 DN frames of 9- to 16-bit cameras, the float32 images ImageSet.save_32bit
+ * writes, and float64 images stored as float32 or quantised to uint16 (ImageSet.save_16bit). The writing twin of
+ * hm_tiff_decode_strips_wide; opt-in (tiff_io.imwrite_device(wide_samples=True), tiff_io.imwrite(wide_samples=True) through the host
+ * build). Everything not named here is as in hm_tiff_encode_strips: little-endian samples in R,G,B(,A) order with the R/B swap at sample
+ * granularity, the strips, the LZW stage, payload, strip_offsets, strip_counts, the 16-byte rounding with zeroed gaps and the workspace
+ * (hm_tiff_encode_bound / _workspace_bytes / _payload_bytes with this call's strip bytes).
+ *   src_kind            HM_TIFF_SRC_U16        (0) uint16, stored as it is
+ *                       HM_TIFF_SRC_F32        (1) float32, stored bit for bit
+ *                       HM_TIFF_SRC_F64_AS_F32 (2) float64 stored as float32: IEEE round-to-nearest-even narrowing, what
+ *                                                  ndarray.astype(np.float32) gives - subnormal results kept, overflow to +-inf, a NaN
+ *                                                  stays a NaN (its payload bits are not pinned)
+ *                       HM_TIFF_SRC_F64_AS_U16 (3) float64 stored as uint16: q = rint((v / divisor) * max_dn) in exactly that order,
+ *                                                  round half to even, wrapped modulo 65536; non-finite samples and |q| >= 2^63 give 0
+ *   divisor, max_dn     read with src_kind 3 only: divisor finite and positive, max_dn in 1 .. 65535 (2^bit_depth - 1)
+ *   predictor           1, or 2 with uint16 output (kinds 0 and 3): the difference, modulo 65536, of the STORED values (for kind 3 the
+ *                       quantised ones) to the same channel of the pixel on the left; the first pixel of every row is stored as it is
+ *   src                 aligned to its own sample size: 2 (kind 0), 4 (kind 1) or 8 (kinds 2 and 3)
+ * Returns, before any HIP call and in this order (an earlier code wins over a later one): HM_EINVAL for a NULL src / payload /
+ * strip_offsets / strip_counts, height / width / rows_per_strip < 1 and a predictor other than 1 or 2; HM_EINVAL for, with src_kind 3, a
+ * divisor that is not finite and positive or a max_dn outside 1 .. 65535, and for a NULL workspace with compression 5; HM_EUNSUPPORTED
+ * for a compression other than 1 or 5, samples other than 1, 3 or 4, a src_kind outside 0 .. 3 and predictor 2 with float32 output;
+ * HM_ESHAPE for strips of 2^31 bytes or more and a payload_cap below hm_tiff_encode_payload_bytes; HM_EALIGN for a payload or workspace
+ * that is not 16-byte aligned, tables that are not 8-byte aligned and a src that is not aligned to its sample size.
+ * ------------------------------------------------------------------------------------------ */
+#define HM_TIFF_SRC_U16 0
+#define HM_TIFF_SRC_F32 1
+#define HM_TIFF_SRC_F64_AS_F32 2
+#define HM_TIFF_SRC_F64_AS_U16 3
+int hm_tiff_encode_strips_wide(const void* src, int src_kind, double divisor, int max_dn, int height, int width, int samples,
+                               int rows_per_strip, int compression, int predictor, void* payload, int64_t payload_cap,
+                               void* strip_offsets /* n_strips + 1 int64 */, void* strip_counts /* n_strips int64 */, void* workspace,
+                               void* stream);
 
 #ifdef __cplusplus
 }

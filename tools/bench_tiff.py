@@ -15,7 +15,15 @@ photo-like and noise, LZW + Predictor 2 and uncompressed; float32 uncompressed; 
 device-resident image to the closed files of `save_8bit` (compression 1 and 5) and `save_64bit` (val and std), host path against
 `device_encode=True`, warm (the median of three runs after a first, with the fastest and slowest in brackets), the size of the value file, and the device time of hm_tiff_encode_strips alone
 (HIP events around the call) with compression 1 - the pack kernel only - and 5, whose difference is the LZW kernel with its scan and
-compaction. The host path is the code of the commit before the device writer, unchanged, so one run gives both sides."""
+compaction. The host path is the code of the commit before the device writer, unchanged, so one run gives both sides.
+
+`--device --wide-write` (needs a GPU; nothing else runs): the wide samples on the way out, 4096 x 4096 x 3 images resident in device
+memory, host path against `imwrite_device` in one run, pixel MB/s of the stored image (median of five warm runs after a first, fastest
+and slowest in brackets): uint16 with 12-bit content, photo-like and noise, LZW + Predictor 2; uint16 uncompressed; float32 uncompressed;
+float64 stored as float32; float64 quantised to 12 bits, LZW + Predictor 2. The host column is the copy to the host, the NumPy
+conversion where there is one and `imwrite(wide_samples=True)` - for uncompressed float32 the only path there was - with `imwrite` alone
+(array already on the host) beside it; the device column is `imwrite_device` with `wide_samples`, `narrow_to_float32` or
+`quantize_max_dn`. The two files are compared byte for byte. Last, the device time of hm_tiff_encode_strips_wide alone (HIP events)."""
 import argparse
 import pathlib
 import sys
@@ -31,6 +39,8 @@ ap = argparse.ArgumentParser(description=__doc__)
 ap.add_argument("--device", action="store_true", help="also time tiff_io.imread_device and the 7-frame load-and-merge both ways (needs a GPU)")
 ap.add_argument("--write", action="store_true", help="time ImageSet.save_8bit / save_64bit, host path against device_encode=True (needs a GPU)")
 ap.add_argument("--wide-only", action="store_true", help="with --device: only the rows of the wide samples (uint16, float32, big-endian)")
+ap.add_argument("--wide-write", action="store_true", help="with --device: only the writing rows of the wide samples, imwrite(wide_samples=True) "
+                                                          "against imwrite_device (uint16, float32, float64 narrowed / quantised)")
 args = ap.parse_args()
 
 
@@ -127,8 +137,101 @@ def bench_write():
     shutil.rmtree(d)
 
 
+def bench_wide_write():
+    import shutil
+    import torch
+    from camera_linearity_amd import _native as nat
+    d = pathlib.Path(tempfile.mkdtemp())
+    rng = np.random.default_rng(0)
+    dev = torch.device("cuda", 0)
+    size = 4096
+    ramp = np.add.outer(np.arange(size), np.arange(size))[:, :, None]
+
+    def timed(fn, reps=5):
+        """(median, fastest, slowest) seconds of `reps` warm runs after a first."""
+        fn()
+        torch.cuda.synchronize()
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            runs.append(time.perf_counter() - t0)
+        runs.sort()
+        return runs[len(runs) // 2], runs[0], runs[-1]
+
+    def rate(nbytes, t):
+        return f"{nbytes / t[0] / 1e6:.0f} ({nbytes / t[2] / 1e6:.0f}-{nbytes / t[1] / 1e6:.0f}) MB/s"
+
+    def encode_ms(t, kind, out_bytes, divisor, max_dn, compression, predictor):
+        """Device time of one hm_tiff_encode_strips_wide (HIP events), warm: the median of five."""
+        H, W, S = t.shape
+        row = W * S * out_bytes
+        rps = T._strip_rows(H, row)
+        n = -(-H // rps)
+        lib = nat.hip_lib
+        cap = lib.hm_tiff_encode_payload_bytes(n, rps * row, compression)
+        payload = torch.empty(cap, dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(16, lib.hm_tiff_encode_workspace_bytes(n, rps * row, compression)), dtype=torch.uint8, device=dev)
+        tables = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)
+        times = []
+        for _ in range(6):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            nat.check(lib.hm_tiff_encode_strips_wide(t.data_ptr(), kind, divisor, max_dn, H, W, S, rps, compression, predictor,
+                                                     payload.data_ptr(), cap, tables.data_ptr(), tables.data_ptr() + 8 * (n + 1),
+                                                     ws.data_ptr(), nat.current_stream_ptr(dev)), "hm_tiff_encode_strips_wide")
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1))
+        return sorted(times[1:])[2]
+
+    def row(name, tensor, to_host, stored_bytes, host_kw, dev_kw, abi):
+        """One line: the host path from the device tensor (copy down, `to_host` conversion, imwrite), imwrite alone, imwrite_device."""
+        host_img = to_host(tensor.cpu().numpy())
+        th = timed(lambda: T.imwrite(d / "h.tif", to_host(tensor.cpu().numpy()), wide_samples=True, **host_kw))
+        ta = timed(lambda: T.imwrite(d / "h.tif", host_img, wide_samples=True, **host_kw))
+        td = timed(lambda: T.imwrite_device(d / "d.tif", tensor, **dev_kw, **host_kw))
+        assert (d / "h.tif").read_bytes() == (d / "d.tif").read_bytes(), name
+        ms = encode_ms(tensor, *abi, host_kw.get("compression", 1), host_kw.get("predictor", 1))
+        moved = tensor.numel() * tensor.element_size() + stored_bytes
+        print(f"{name}: host {rate(stored_bytes, th)} (imwrite alone {rate(stored_bytes, ta)}), device {rate(stored_bytes, td)} "
+              f"({th[0] / td[0]:.1f} x); file {(d / 'd.tif').stat().st_size / 1e6:.1f} MB; hm_tiff_encode_strips_wide alone {ms:.2f} ms"
+              + (f" = {moved / ms / 1e6:.0f} GB/s read + written" if host_kw.get("compression", 1) == 1 else ""), flush=True)
+
+    def same(a):
+        return a
+    lzw2 = dict(compression=5, predictor=2)
+    photo = np.clip(ramp * (4095 / 8190) + rng.normal(size=(size, size, 3)) * 8, 0, 4095).astype(np.uint16)
+    noise = rng.integers(0, 4096, (size, size, 3), dtype=np.uint16)
+    wide = dict(wide_samples=True)
+    print(f"--- {size} x {size} x 3, pixel MB/s of the stored image, median (slowest-fastest) of 5 warm runs", flush=True)
+    t = torch.from_numpy(photo).to(dev)
+    row("uint16 12-bit photo-like, LZW + Predictor 2", t, same, photo.nbytes, lzw2, wide, (nat.HM_TIFF_SRC_U16, 2, 1.0, 0))
+    row("uint16 uncompressed", t, same, photo.nbytes, {}, wide, (nat.HM_TIFF_SRC_U16, 2, 1.0, 0))
+    t = torch.from_numpy(noise).to(dev)
+    row("uint16 12-bit noise, LZW + Predictor 2", t, same, noise.nbytes, lzw2, wide, (nat.HM_TIFF_SRC_U16, 2, 1.0, 0))
+    del noise
+    f64 = photo / 4095.0 * 3.7
+    del photo
+    t = torch.from_numpy(f64.astype(np.float32)).to(dev)
+    row("float32 uncompressed", t, same, f64.size * 4, {}, wide, (nat.HM_TIFF_SRC_F32, 4, 1.0, 0))
+    t = torch.from_numpy(f64).to(dev)
+    del f64
+    row("float64 -> float32 uncompressed", t, lambda a: a.astype(np.float32), t.numel() * 4, {}, dict(narrow_to_float32=True),
+        (nat.HM_TIFF_SRC_F64_AS_F32, 4, 1.0, 0))
+    row("float64 -> 12-bit uint16, LZW + Predictor 2", t, lambda a: np.around((a / 3.7) * 4095).astype(np.uint16), t.numel() * 2, lzw2,
+        dict(quantize_divisor=3.7, quantize_max_dn=4095), (nat.HM_TIFF_SRC_F64_AS_U16, 2, 3.7, 4095))
+    shutil.rmtree(d)
+
+
 if args.write:
     bench_write()
+    sys.exit(0)
+if args.wide_write:
+    if not args.device:
+        ap.error("--wide-write needs --device")
+    bench_wide_write()
     sys.exit(0)
 
 d = pathlib.Path(tempfile.mkdtemp())

@@ -233,6 +233,16 @@ void tiff() {
     expect("encode, a (2^31 - 1)-byte strip", check_tiff_encode(b, 0, 1.0, 4, big, 1, 1, 1, 1, b, cap, s, s, nullptr, eg), HM_OK);
     expect("encode, a 2^31-byte strip", check_tiff_encode(b, 0, 1.0, 4, 1 << 30, 1, 2, 1, 1, b, cap, s, s, nullptr, eg), HM_ESHAPE);
     expect("encode, NaN divisor", check_tiff_encode(b, 2, kNaN, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("encode wide", check_tiff_encode_wide(b, HM_TIFF_SRC_U16, 1.0, 0, 4, 4, 3, 2, 5, 2, b, cap, s, s, b, eg), HM_OK);
+    expect("encode wide: pitches", eg.in_pitch + eg.out_pitch, round16(48) + round16(hm_lzw_enc::bound(48)));
+    expect("encode wide, NULL", check_tiff_encode_wide(nullptr, 0, 1.0, 0, 4, 4, 3, 2, 5, 1, nullptr, cap, nullptr, nullptr, nullptr, eg), HM_EINVAL);
+    expect("encode wide, no rows per strip", check_tiff_encode_wide(b, 0, 1.0, 0, 4, 4, 3, 0, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("encode wide, largest ints", check_tiff_encode_wide(b, HM_TIFF_SRC_F32, 1.0, 0, big, big, 4, big, 1, 1, b, cap, s, s, b, eg), HM_ESHAPE);
+    expect("encode wide, a (2^31 - 2)-byte strip", check_tiff_encode_wide(b, 0, 1.0, 0, 4, (1 << 30) - 1, 1, 1, 1, 1, b, cap, s, s, nullptr, eg), HM_OK);
+    expect("encode wide, a 2^31-byte strip", check_tiff_encode_wide(b, 0, 1.0, 0, 4, 1 << 30, 1, 1, 1, 1, b, cap, s, s, nullptr, eg), HM_ESHAPE);
+    expect("encode wide, NaN divisor", check_tiff_encode_wide(b, HM_TIFF_SRC_F64_AS_U16, kNaN, 4095, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("encode wide, max_dn 65536", check_tiff_encode_wide(b, HM_TIFF_SRC_F64_AS_U16, 1.0, 65536, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_EINVAL);
+    expect("encode wide, NaN divisor not read", check_tiff_encode_wide(b, HM_TIFF_SRC_F64_AS_F32, kNaN, -1, 4, 4, 3, 2, 5, 1, b, cap, s, s, b, eg), HM_OK);
     expect("bound(0)", tiff_encode_bound(0), HM_EINVAL);
     expect("bound(2^31)", tiff_encode_bound(int64_t{1} << 31), HM_ESHAPE);
     expect("bound(2^31 - 1)", tiff_encode_bound(kTiffEncodeMaxStripBytes), hm_lzw_enc::bound(kTiffEncodeMaxStripBytes));
