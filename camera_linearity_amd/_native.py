@@ -227,6 +227,11 @@ _SIGNATURES = {
     "hm_de_generation_batch": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    # the batch on uint16 DN stacks: ... energy_limit, bit_depth, variant, workspace (hm_de_batch_workspace_bytes), stream
+    "hm_de_generation_u16_batch": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
 }
 
 # Entry points that fill HOST arrays whose length follows from a scalar argument (2**bit_depth doubles each): bound like the others, kept

@@ -1,5 +1,5 @@
 // hm_calibration_rules.h - the argument rules of the ICRF-calibration entries (hm_linearity_energy, hm_linearity_energy_u16,
-// hm_de_generation, hm_de_generation_u16, hm_de_generation_batch), written once for both builds of the ABI in the manner of
+// hm_de_generation, hm_de_generation_u16, hm_de_generation_batch, hm_de_generation_u16_batch), written once for both builds of the ABI in the manner of
 // hm_merge_rules.h: the device build (hm_energy.hip, hm_energy_u16.hip, hm_de.hip, hm_de_u16.hip) and the host build
 // (csrc_host/hm_host.cpp) include this file and restate none of it.
 // Plain C++17 on hdrmerge.h: no HIP type.
@@ -7,10 +7,10 @@
 // Every status is here in the order hdrmerge.h gives them: an earlier rule wins over a later one broken in the same call.
 //
 // What each build adds after the shared call, and why that changes no call's status:
-//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all five entries it follows rules that are HM_EINVAL too or
+//   device  a NULL workspace is HM_EINVAL (the host build needs none). In all six entries it follows rules that are HM_EINVAL too or
 //           comes last. The energy launch refuses a frame count its pixel-major kernels are not instantiated for (HM_EUNSUPPORTED).
 //   host    hm_de_generation and hm_de_generation_u16 return HM_OK at once when status[HM_DE_STOP] is set: there `status` is host memory. On the device build
-//           the kernels read the flag, so it cannot be a rule of this file.
+//           the kernels read the flag, so it cannot be a rule of this file. (The two batch entries call them per problem.)
 #pragma once
 #include "hdrmerge.h"
 #include <cstdint>
@@ -132,6 +132,34 @@ inline int check_de_generation_batch(int n_problems, const double* population, c
     if (!seeds) return HM_EINVAL;
     for (int k = 0; k < n_problems; ++k)
         if (!dn[k] || (std_ && !std_[k])) return HM_EINVAL;                   // stds for all problems or for none
+    return HM_OK;
+}
+
+// hm_de_generation_u16_batch: n_problems problems on uint16 stacks of one shape and one bit_depth. The statuses, in this order:
+//   1. hm_de_generation_batch's, in its order, but for its limit rule (lower / upper are DNs of the depth here): n_problems, the counts,
+//      the shape, n_problems * pop_size, the mutation / recombination / tol / energy_limit ranges, a NULL pointer, a NULL seeds array, a
+//      NULL entry of dn or std
+//   2. hm_de_generation_u16's rules 2-4 (check_linearity_energy_u16_counts on pop_size candidates): HM_EINVAL for bit_depth outside
+//      9..16, variant outside 0..2 or a limit outside 0 .. 2^bit_depth - 1; HM_EUNSUPPORTED for variant 1 where the row does not fit LDS
+//   3. HM_EALIGN       a dn[k] that is not 2-byte aligned
+// (the stack pointers are only compared with NULL and looked at for alignment: the batch rule takes them as the 8-bit entry's type)
+inline int check_de_generation_u16_batch(int n_problems, const double* population, const double* energies, const double* trial,
+                                         const double* trial_energies, const double* icrf, const uint8_t* valid, const int64_t* status,
+                                         const double* mean_icrf, const double* pca, const double* lower_limits, const double* upper_limits,
+                                         const uint16_t* const* dn, const double* const* std_, const int64_t* seeds, const double* exposures,
+                                         int64_t n_pixels, int n_frames, int lower, int upper, int pop_size, int n_params,
+                                         int64_t max_generations, double mutation_lo, double mutation_hi, double recombination, double tol,
+                                         double energy_limit, int bit_depth, int variant) {
+    int rc = check_de_generation_batch(n_problems, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca,
+                                       lower_limits, upper_limits, reinterpret_cast<const uint8_t* const*>(dn), std_, seeds, exposures, n_pixels,
+                                       n_frames, 0, 0, pop_size, n_params, max_generations, mutation_lo, mutation_hi, recombination, tol,
+                                       energy_limit);
+    if (rc != HM_OK) return rc;
+    bool empty;                                                               // (never: pop_size >= 4)
+    rc = check_linearity_energy_u16_counts(pop_size, lower, upper, n_pixels, n_frames, bit_depth, variant, empty);
+    if (rc != HM_OK) return rc;
+    for (int k = 0; k < n_problems; ++k)
+        if (reinterpret_cast<uintptr_t>(dn[k]) & 1) return HM_EALIGN;
     return HM_OK;
 }
 

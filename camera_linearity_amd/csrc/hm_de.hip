@@ -19,9 +19,9 @@
 // bodies are the single-problem ones (k_de_trial's a shared function, k_de_select's the same text included a second time,
 // hm_de_select_body.h) applied to problem k's slices of the (K, ...) state and to its seed, so a problem evolves to the same bits alone or in a batch; every stage, the energy kernels included, returns for a problem whose stop flag is set.
 //
-// hm_de_u16.hip (hm_de_generation_u16: rows of 2^bit_depth entries) shares three things with this unit: DeK and de_args (hm_de_args.h), the
-// trial component text (hm_de_trial_component_body.h, included below: its `trial` is this unit's bit for bit) and k_de_select, which it
-// launches through de_select_launch.
+// hm_de_u16.hip (hm_de_generation_u16 and hm_de_generation_u16_batch: rows of 2^bit_depth entries) shares three things with this unit: DeK,
+// DeSeeds and de_args (hm_de_args.h), the trial component text (hm_de_trial_component_body.h, included below: its `trial` is this unit's
+// bit for bit) and k_de_select / k_de_select_batch, which it launches through de_select_launch / de_select_batch_launch.
 #include "hm_common.h"
 #include "hm_producer_math.h"
 #include "hm_calibration_rules.h"
@@ -33,11 +33,6 @@ namespace hm {
 int energy_batch(const uint8_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
                  const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels,
                  int n_frames, double* out_energy, void* workspace, hipStream_t st);
-
-// the seeds of a batch travel in the kernel arguments, like the stack pointers of its energy stage
-struct DeSeeds {
-    uint64_t seed[HM_DE_MAX_PROBLEMS];
-};
 
 // problem k of a batch: its slices of the (K, ...) state arrays and its seed; everything else is shared
 __device__ __forceinline__ DeK problem_of(const DeK& a, const DeSeeds& sd, const int k) {
@@ -114,6 +109,12 @@ int de_select_launch(const DeK& k, hipStream_t st) {
     return launch_status();
 }
 
+// (hm_de_args.h) the select stage of a batch, for this unit's hm_de_generation_batch and for hm_de_u16.hip
+int de_select_batch_launch(const DeK& k, const DeSeeds& sd, int n_problems, hipStream_t st) {
+    hipLaunchKernelGGL(k_de_select_batch, dim3(n_problems), dim3(256), 0, st, k, sd);
+    return launch_status();
+}
+
 }  // namespace hm
 
 using namespace hm;
@@ -178,6 +179,5 @@ extern "C" int hm_de_generation_batch(int n_problems, double* population, double
     rc = energy_batch(dn, std, status, n_problems, pop_size, exposures, icrf, valid, lower, upper, n_pixels, n_frames, trial_energies,
                       workspace, as_stream(stream));
     if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(k_de_select_batch, dim3(n_problems), dim3(256), 0, as_stream(stream), k, sd);
-    return launch_status();
+    return de_select_batch_launch(k, sd, n_problems, as_stream(stream));
 }

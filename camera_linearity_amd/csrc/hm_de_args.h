@@ -1,7 +1,8 @@
-// hm_de_args.h - the arguments of one differential-evolution generation as the kernels of hm_de.hip and hm_de_u16.hip take them (DeK),
-// and what those two units share on the host side. Plain C++ on <cstdint>: ../csrc_host/hm_host.cpp fills a DeK too, for the trial
+// hm_de_args.h - the arguments of one differential-evolution generation as the kernels of hm_de.hip and hm_de_u16.hip take them (DeK,
+// and DeSeeds for a batch), and what those two units share on the host side. Plain C++ on <cstdint>: ../csrc_host/hm_host.cpp fills a DeK too, for the trial
 // component text it shares with the device kernels (hm_de_trial_component_body.h).
 #pragma once
+#include "hdrmerge.h"
 #include <cstdint>
 
 namespace hm {
@@ -37,9 +38,17 @@ inline DeK de_args(double* population, double* energies, double* trial, double* 
     return k;
 }
 
+// the seeds of a batch travel in the kernel arguments, like the stack pointers of its energy stage
+struct DeSeeds {
+    uint64_t seed[HM_DE_MAX_PROBLEMS];
+};
+
 #ifdef __HIPCC__
 // hm_de.hip: k_de_select on one problem's state (the last stage of hm_de_generation, and of hm_de_generation_u16 in hm_de_u16.hip) -> status
 int de_select_launch(const DeK& k, hipStream_t st);
+// hm_de.hip: k_de_select_batch on the (K, ...) state of n_problems problems (the last stage of hm_de_generation_batch, and of
+// hm_de_generation_u16_batch in hm_de_u16.hip: the selection never touches a row, so the rows' length does not matter to it) -> status
+int de_select_batch_launch(const DeK& k, const DeSeeds& sd, int n_problems, hipStream_t st);
 #endif
 
 }  // namespace hm

@@ -22,6 +22,13 @@
 // The contract is hm_de.hip's: all state is the caller's, nothing is allocated, nothing synchronises the host, no atomics; after the stop
 // flag is set k_de_trial_u16, k_de_verdict_u16 and k_de_select return before their first store.
 //
+// hm_de_generation_u16_batch advances K problems of one shape and one depth by the same stages with the problem as one more grid
+// dimension: k_de_trial_u16_batch, grid = (S, 1, K) or (S, slabs, K) - the walk's text, hm_de_trial_u16_body.h, included a second time
+// on problem k's slices of the (K, ...) state and its seed -, k_de_verdict_u16_batch, grid = ((S + 255) / 256, K), on verdict bytes
+// indexed (k, i, y); energy_u16_batch (hm_energy_u16.hip), candidates K x S, geometry and placement from the per-problem S and pixel
+// count; k_de_select_batch (hm_de.hip) through de_select_batch_launch. A problem evolves to the same bits alone or in a batch, and every
+// stage returns before its first store for a problem whose stop flag is set.
+//
 // Why two forms: with S = 128 members one workgroup per member leaves half the CUs idle, each of the others with one wave per SIMD. At 16
 // bits (128 rows of 512 KiB) that walk took 179 us of a 204 us generation on a 28 x 28 x 7 stack; over (S, 16) workgroups the generation
 // takes 74 us, at 14 bits 42 us instead of 65. At 12 bits the walk is 13 us and the two forms are within 1 us of each other: the one
@@ -38,80 +45,7 @@ namespace hm {
 // combines them); else grid = S, one workgroup walks the whole row and writes valid[i] itself (slab_bad is not looked at).
 template <int U, bool SLAB>
 __global__ __launch_bounds__(256) void k_de_trial_u16(const DeK a, const int bits, uint8_t* const slab_bad) {
-    __shared__ double x[HM_DE_MAX_PARAMS];
-    __shared__ double last;
-    __shared__ double edge[2][U][4];                                      // [trip parity][segment of the trip][wave]: lane 63's row
-    __shared__ int bad[4];
-    if (a.status[HM_DE_STOP] != 0) return;                                // uniform: the whole generation is a no-op
-    const int i = blockIdx.x;
-    const int lane = threadIdx.x, P = a.P, S = a.S;
-    const int64_t g = a.status[HM_DE_GENERATION];
-
-#include "hm_de_trial_component_body.h"
-    __syncthreads();
-
-    const int R = 1 << bits;
-    if (lane == 255) {
-        const int d = R - 1;
-        double row = 0.0;
-        for (int j = 0; j < P; ++j) row += a.pca[d * P + j] * x[j];       // PCA @ x, DN R - 1: the expression of the walk below
-        row = a.mean_icrf[d] + row;
-        last = row;
-    }
-    __syncthreads();
-    const double shift = 1.0 - last;                                      // :166
-    double* const out = a.icrf + static_cast<int64_t>(i) * R;             // S * R * 8 bytes reach 512 MiB
-    const int w = lane >> 6;
-    bool wrong = false;
-    const int s_count = SLAB ? (R >> 8) / static_cast<int>(gridDim.y) : R >> 8;   // segments of this workgroup
-    const int s_begin = SLAB ? static_cast<int>(blockIdx.y) * s_count : 0;
-    double carry = 0.0;                                                   // the previous trip's last row (lane 255): DN d - 1 of lane 0
-    if (SLAB && s_begin > 0) {                                            // a later slab's left neighbour: the same expression (d > 0: not row 0)
-        const int d = (s_begin << 8) - 1;
-        double row = 0.0;
-        for (int j = 0; j < P; ++j) row += a.pca[d * P + j] * x[j];
-        row = a.mean_icrf[d] + row;
-        carry = row + shift;
-    }
-    for (int s = s_begin, trip = 0; s < s_begin + s_count; s += U, ++trip) {
-        const int d0 = (s << 8) + lane;
-        double row[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) row[u] = 0.0;
-#pragma unroll 4
-        for (int j = 0; j < P; ++j) {
-            const double xj = x[j];
-#pragma unroll
-            for (int u = 0; u < U; ++u) row[u] += a.pca[(d0 + (u << 8)) * P + j] * xj;
-        }
-        double (*e)[4] = edge[trip & 1];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int d = d0 + (u << 8);
-            row[u] = a.mean_icrf[d] + row[u];
-            row[u] += shift;
-            if (d == 0) row[u] = 0.0;                                     // :167
-            out[d] = row[u];
-            if ((lane & 63) == 63) e[u][w] = row[u];
-        }
-        __syncthreads();
-        // range (:173-175) and strict monotonicity (:177-179)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int d = d0 + (u << 8);
-            double prev = __shfl_up(row[u], 1, 64);
-            if ((lane & 63) == 0) prev = lane > 0 ? e[u][w - 1] : (u > 0 ? e[u - 1][3] : carry);
-            wrong |= row[u] > 1.0 || row[u] < 0.0 || (d > 0 && !(row[u] > prev));
-        }
-        carry = e[U - 1][3];                                              // (this buffer is next written two trips on, behind the next barrier)
-    }
-    const unsigned long long any = __ballot(wrong);
-    if ((lane & 63) == 0) bad[w] = any != 0ull;
-    __syncthreads();
-    if (lane == 0) {
-        if (SLAB) slab_bad[static_cast<int64_t>(i) * gridDim.y + blockIdx.y] = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
-        else a.valid[i] = !(bad[0] | bad[1] | bad[2] | bad[3]);
-    }
+#include "hm_de_trial_u16_body.h"
 }
 
 // the slab form's verdict: one byte valid[i] from the member's slab bytes, before the energy stage reads it
@@ -124,10 +58,45 @@ __global__ __launch_bounds__(256) void k_de_verdict_u16(const DeK a, const uint8
     a.valid[i] = !any;
 }
 
+// problem k of a batch: its slices of the (K, ...) state arrays, with rows of R entries, and its seed; everything else is shared.
+// Every offset is 64-bit: K * S * R * 8 bytes reach 32 GiB at the limits.
+__device__ __forceinline__ DeK problem_of_rows(const DeK& a, const DeSeeds& sd, const int k, const int64_t R) {
+    DeK r = a;
+    const int64_t S = a.S, P = a.P, K = k;
+    r.pop += K * S * P; r.energy += K * S; r.trial += K * S * P; r.trial_energy += K * S; r.icrf += K * S * R;
+    r.valid += K * S; r.status += K * HM_DE_STATUS_WORDS; r.mean_icrf += K * R;
+    r.pca += K * R * P;
+    r.seed = sd.seed[k];
+    return r;
+}
+
+// k_de_trial_u16 on problem blockIdx.z of a batch: grid = (S, 1, K), or (S, slabs, K) with the verdict bytes indexed (k, i, y)
+template <int U, bool SLAB>
+__global__ __launch_bounds__(256) void k_de_trial_u16_batch(const DeK a0, const DeSeeds sd, const int bits, uint8_t* const slab_bad0) {
+    const DeK a = problem_of_rows(a0, sd, blockIdx.z, int64_t{1} << bits);
+    uint8_t* const slab_bad = slab_bad0 + static_cast<int64_t>(blockIdx.z) * a0.S * gridDim.y;
+#include "hm_de_trial_u16_body.h"
+}
+
+// k_de_verdict_u16 for a batch: grid = ((S + 255) / 256, K), one lane per member of problem blockIdx.y; nothing for a stopped problem
+__global__ __launch_bounds__(256) void k_de_verdict_u16_batch(const DeK a, const uint8_t* const slab_bad, const int slabs) {
+    const int64_t k = blockIdx.y;
+    if (a.status[k * HM_DE_STATUS_WORDS + HM_DE_STOP] != 0) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.S) return;
+    const int64_t m = k * a.S + i;
+    int any = 0;
+    for (int y = 0; y < slabs; ++y) any |= slab_bad[m * slabs + y];
+    a.valid[m] = !any;
+}
+
 // The slab grid from this depth on (DESIGN.md 4.4.3 has the measurement: builds with 12 and 17 here against this one)
 constexpr int kDeU16SlabMinBits = 14;
 static_assert(kDeU16SlabMinBits >= 12, "a slab is at least one trip of 2048 DNs and a member gets at least two");
-constexpr int kDeU16MaxSlabs = 16;      // S * slabs verdict bytes fit every workspace: hm_de_workspace_bytes is at least 16 S bytes (one pair, one chunk)
+// S * slabs verdict bytes fit every workspace: hm_de_workspace_bytes is at least 16 S bytes (one pair, one chunk, two float64 per member).
+// A batch's K * S * slabs bytes fit its workspace for the same reason: hm_de_batch_workspace_bytes is K times the single size.
+constexpr int kDeU16MaxSlabs = 16;
+static_assert(kDeU16MaxSlabs <= 2 * sizeof(double), "the verdict bytes of a member fit the 16 bytes that a workspace holds per member at least");
 
 // 2 segments at 9 bits, 4 at 10: the whole row in one trip; 8 per trip from 11 bits on. From kDeU16SlabMinBits on the trips are
 // dealt to up to kDeU16MaxSlabs workgroups per member (14 bits: 8 slabs of one trip, 15: 16 of one, 16: 16 of two), whose verdict bytes
@@ -149,6 +118,30 @@ static int de_trial_u16_launch(const DeK& k, int bit_depth, void* workspace, hip
     else hipLaunchKernelGGL((k_de_trial_u16<8, false>), grid, block, 0, st, k, bit_depth, slab_bad);
     return launch_status();
 }
+
+// the same for the K problems of a batch: the same U per depth and the same slab counts, the problem in the grid's z (y for the verdict)
+static int de_trial_u16_batch_launch(const DeK& k, const DeSeeds& sd, int n_problems, int bit_depth, void* workspace, hipStream_t st) {
+    const dim3 block(256);
+    uint8_t* const slab_bad = static_cast<uint8_t*>(workspace);
+    if (bit_depth >= kDeU16SlabMinBits) {
+        const int trips = (1 << bit_depth) >> 11, slabs = trips < kDeU16MaxSlabs ? trips : kDeU16MaxSlabs;
+        hipLaunchKernelGGL((k_de_trial_u16_batch<8, true>), dim3(k.S, slabs, n_problems), block, 0, st, k, sd, bit_depth, slab_bad);
+        const int rc = launch_status();
+        if (rc != HM_OK) return rc;
+        hipLaunchKernelGGL(k_de_verdict_u16_batch, dim3((k.S + 255) / 256, n_problems), block, 0, st, k, slab_bad, slabs);
+        return launch_status();
+    }
+    const dim3 grid(k.S, 1, n_problems);
+    if (bit_depth == 9) hipLaunchKernelGGL((k_de_trial_u16_batch<2, false>), grid, block, 0, st, k, sd, bit_depth, slab_bad);
+    else if (bit_depth == 10) hipLaunchKernelGGL((k_de_trial_u16_batch<4, false>), grid, block, 0, st, k, sd, bit_depth, slab_bad);
+    else hipLaunchKernelGGL((k_de_trial_u16_batch<8, false>), grid, block, 0, st, k, sd, bit_depth, slab_bad);
+    return launch_status();
+}
+
+// hm_energy_u16.hip: the energy stage of hm_de_generation_u16_batch (K problems x S candidates per launch; see there)
+int energy_u16_batch(const uint16_t* const* dn, const double* const* std, const int64_t* status, int n_problems, int pop_size,
+                     const double* exposures, const double* icrf, const uint8_t* valid, int lower, int upper, int64_t n_pixels, int n_frames,
+                     int bit_depth, int variant, double* out_energy, void* workspace, hipStream_t st);
 
 }  // namespace hm
 
@@ -174,4 +167,32 @@ extern "C" int hm_de_generation_u16(double* population, double* energies, double
                                  trial_energies, workspace, stream);
     if (rc != HM_OK) return rc;
     return de_select_launch(k, as_stream(stream));
+}
+
+// K problems of one shape and one depth per call (include/hdrmerge.h): the three stages of hm_de_generation_u16 with the problem as one
+// more grid dimension - k_de_trial_u16_batch (and k_de_verdict_u16_batch from 14 bits), energy_u16_batch (hm_energy_u16.hip),
+// k_de_select_batch (hm_de.hip) - one linear chain on one stream. The workspace is hm_de_batch_workspace_bytes' (K times the single size).
+extern "C" int hm_de_generation_u16_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies,
+                                          double* icrf, uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca,
+                                          const double* lower_limits, const double* upper_limits, const uint16_t* const* dn,
+                                          const double* const* std, const int64_t* seeds, const double* exposures, int64_t n_pixels,
+                                          int n_frames, int lower, int upper, int pop_size, int n_params, int64_t max_generations,
+                                          double mutation_lo, double mutation_hi, double recombination, double tol, double energy_limit,
+                                          int bit_depth, int variant, void* workspace, void* stream) {
+    int rc = hm_rules::check_de_generation_u16_batch(n_problems, population, energies, trial, trial_energies, icrf, valid, status, mean_icrf,
+                                                     pca, lower_limits, upper_limits, dn, std, seeds, exposures, n_pixels, n_frames, lower,
+                                                     upper, pop_size, n_params, max_generations, mutation_lo, mutation_hi, recombination, tol,
+                                                     energy_limit, bit_depth, variant);
+    if (rc != HM_OK) return rc;
+    if (!workspace) return HM_EINVAL;                                         // this build's own: the verdict bytes and the energy stage's partial sums
+    const DeK k = de_args(population, energies, trial, trial_energies, icrf, valid, status, mean_icrf, pca, lower_limits, upper_limits,
+                          pop_size, n_params, 0, max_generations, mutation_lo, mutation_hi, recombination, tol, energy_limit);
+    DeSeeds sd{};
+    for (int i = 0; i < n_problems; ++i) sd.seed[i] = static_cast<uint64_t>(seeds[i]);
+    rc = de_trial_u16_batch_launch(k, sd, n_problems, bit_depth, workspace, as_stream(stream));
+    if (rc != HM_OK) return rc;
+    rc = energy_u16_batch(dn, std, status, n_problems, pop_size, exposures, icrf, valid, lower, upper, n_pixels, n_frames, bit_depth, variant,
+                          trial_energies, workspace, as_stream(stream));
+    if (rc != HM_OK) return rc;
+    return de_select_batch_launch(k, sd, n_problems, as_stream(stream));
 }

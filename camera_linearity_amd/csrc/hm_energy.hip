@@ -157,6 +157,13 @@ int energy_final(const double* partial, const uint8_t* valid, int pairs, int chu
     return launch_status();
 }
 
+// (hm_energy_dev.h) k_energy_final_batch on the partial sums of `total` = K x S candidates, for energy_batch below and for hm_energy_u16.hip
+int energy_final_batch(const double* partial, const uint8_t* valid, int pairs, int chunks, int total, double* out_energy,
+                       const int64_t* status, int pop_size, hipStream_t st) {
+    hipLaunchKernelGGL(k_energy_final_batch, dim3(total), dim3(64), 0, st, partial, valid, pairs, chunks, out_energy, status, pop_size);
+    return launch_status();
+}
+
 // the kernel arguments of one launch (validated by the caller); a batch passes no stack here: on_stack_of() gives each problem its own
 static EnergyK energy_args(const uint8_t* dn, const double* std, const double* exposures, const double* icrf, const uint8_t* valid,
                            int lower, int upper, int relative, int64_t n_pixels, int n_frames, void* workspace) {
@@ -193,9 +200,7 @@ int energy_batch(const uint8_t* const* dn, const double* const* std, const int64
     }
     int rc = launch_status();
     if (rc != HM_OK) return rc;
-    hipLaunchKernelGGL(k_energy_final_batch, dim3(total), dim3(64), 0, st, static_cast<const double*>(workspace), valid, pairs,
-                       k.chunks, out_energy, status, pop_size);
-    return launch_status();
+    return energy_final_batch(static_cast<const double*>(workspace), valid, pairs, k.chunks, total, out_energy, status, pop_size, st);
 }
 
 }  // namespace hm

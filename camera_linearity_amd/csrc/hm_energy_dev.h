@@ -77,4 +77,9 @@ static void energy_pair_ratios(EnergyPairs& pr, const double* exposures, int n_f
 int energy_final(const double* partial, const uint8_t* valid, int pairs, int chunks, int n_candidates, double* out_pairs,
                  double* out_energy, hipStream_t st);
 
+// hm_energy.hip: k_energy_final_batch on the partial sums of `total` = K x pop_size candidates (one wave each; none for a problem whose
+// stop flag in `status` (K, HM_DE_STATUS_WORDS) is set) -> out_energy
+int energy_final_batch(const double* partial, const uint8_t* valid, int pairs, int chunks, int total, double* out_energy,
+                       const int64_t* status, int pop_size, hipStream_t st);
+
 }  // namespace hm

@@ -1,7 +1,7 @@
 // hm_energy_pixel_body.h - the body of the pixel-major energy kernel (N <= 8 frames): a thread owns pixels and evaluates all N(N-1)/2
 // pairs of a pixel from registers. Not a header of declarations: hm_energy.hip includes this text twice, as the body of
 // k_energy_pixel<N, STD> and as the body of energy_pixel_body<N, STD> (which k_energy_pixel_batch calls on its problem's stack), and
-// hm_energy_u16.hip once, as the body of k_energy_pixel_u16<N, STD, LUT>.
+// hm_energy_u16.hip twice, as the body of k_energy_pixel_u16<N, STD, LUT> and of k_energy_pixel_u16_batch<N, STD, LUT>.
 // In scope at the point of inclusion: `a` (the unit's kernel arguments), `pr` (the EnergyPairs ratios) and the template parameters N and STD;
 // wave_sum, rcp_second_order, rsqrt_third_order and HM_ENERGY_RCP from hm_energy_dev.h; and the unit's placement of the candidate's row:
 // HM_ENERGY_ROW_DECL (its declarations), HM_ENERGY_ROW_FILL(b) (made readable by the whole workgroup), HM_ENERGY_ROW(dn) (the entry of a DN).
@@ -9,6 +9,12 @@
 // tried - an occupancy step for k_energy_pixel<5, false> - and the single-stack path must not pay for the batch. One
 // text keeps the two forms to the same arithmetic; tools/kernel_asm_diff.py shows that an edit here left the kernels it was not meant
 // to change as they were.
+// The stack a kernel reads is HM_ENERGY_DN / HM_ENERGY_SD: the arguments' own unless the including unit names another before the
+// inclusion (hm_energy_u16.hip's batched kernels: their problem's; see hm_energy_partial_body.h).
+#ifndef HM_ENERGY_DN
+#define HM_ENERGY_DN a.dn
+#define HM_ENERGY_SD a.sd
+#endif
     constexpr int P = N * (N - 1) / 2;
     HM_ENERGY_ROW_DECL
     __shared__ double red[4][2 * P];
@@ -28,7 +34,7 @@
 
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     for (int64_t px = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; px < a.P; px += stride) {
-        const auto* q = a.dn + px * N;
+        const auto* q = HM_ENERGY_DN + px * N;
         double v[N], rv[N], s[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -36,7 +42,7 @@
             if (x < lo || x > hi) x = __builtin_nan("");                       // :96-97
             v[i] = x;
             rv[i] = HM_ENERGY_RCP ? rcp_second_order(x) : 1.0 / x;
-            s[i] = STD ? a.sd[px * N + i] : 0.0;
+            s[i] = STD ? HM_ENERGY_SD[px * N + i] : 0.0;
         }
         int p = 0;
 #pragma unroll

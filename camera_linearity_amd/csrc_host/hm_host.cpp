@@ -1706,6 +1706,31 @@ int hm_de_generation_batch(int n_problems, double* population, double* energies,
     return HM_OK;
 }
 
+// ... and of uint16 stacks of one depth: each problem through hm_de_generation_u16 on its slices, rows of R = 2^bit_depth entries (a
+// stopped problem is skipped there: it returns at once)
+int hm_de_generation_u16_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies, double* icrf,
+                               uint8_t* valid, int64_t* status, const double* mean_icrf, const double* pca, const double* lower_limits,
+                               const double* upper_limits, const uint16_t* const* dn, const double* const* std_, const int64_t* seeds,
+                               const double* exposures, int64_t n_pixels, int n_frames, int lower, int upper, int pop_size, int n_params,
+                               int64_t max_generations, double mutation_lo, double mutation_hi, double recombination, double tol,
+                               double energy_limit, int bit_depth, int variant, void*, void*) {
+    const int rc0 = hm_rules::check_de_generation_u16_batch(n_problems, population, energies, trial, trial_energies, icrf, valid, status,
+                                                            mean_icrf, pca, lower_limits, upper_limits, dn, std_, seeds, exposures, n_pixels,
+                                                            n_frames, lower, upper, pop_size, n_params, max_generations, mutation_lo,
+                                                            mutation_hi, recombination, tol, energy_limit, bit_depth, variant);
+    if (rc0 != HM_OK) return rc0;
+    const int64_t S = pop_size, P = n_params, R = int64_t{1} << bit_depth;
+    for (int64_t k = 0; k < n_problems; ++k) {
+        const int rc = hm_de_generation_u16(population + k * S * P, energies + k * S, trial + k * S * P, trial_energies + k * S,
+                                            icrf + k * S * R, valid + k * S, status + k * HM_DE_STATUS_WORDS, mean_icrf + k * R,
+                                            pca + k * R * P, lower_limits, upper_limits, dn[k], std_ ? std_[k] : nullptr, exposures,
+                                            n_pixels, n_frames, lower, upper, pop_size, n_params, seeds[k], max_generations, mutation_lo,
+                                            mutation_hi, recombination, tol, energy_limit, bit_depth, variant, nullptr, nullptr);
+        if (rc != HM_OK) return rc;
+    }
+    return HM_OK;
+}
+
 /* ------------------------------------------------------------------------------------------
  * hm_tiff_decode_strips on the host: the same argument checks, status words and frame as the device entry point of
  * csrc/hm_tiff_device.hip, with HOST pointers - the decoder body both builds share (csrc/hm_tiff_lzw_body.h) with a serial emitter,

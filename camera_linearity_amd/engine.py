@@ -1616,7 +1616,7 @@ def _check_stacks(dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequen
     or a sequence whose entries are all None: no stds) and the N exposures, checked in this order
     -> (contiguous stacks, contiguous std stacks | None, exposures as a float64 array). `batch` words the std messages for a batch, whose
     std stacks must also live on the stacks' device. `dn_dtype`: torch.uint16 for a stack with a bit depth (linearity_energy(..., bit_depth=)
-    and DEPlanU16; DEPlan and DEBatchPlan take uint8 stacks only)."""
+    DEPlanU16 and DEBatchPlanU16; DEPlan and DEBatchPlan take uint8 stacks only)."""
     first = dn_stacks[0]
     for s in dn_stacks:
         _require_cuda(s, "image_value_stack")
@@ -1716,9 +1716,10 @@ def _status_dict(w: np.ndarray) -> dict:
 
 
 class _DEPlanBase:
-    """What DEPlan and DEBatchPlan share: one native call per generation, `check_every` of them recorded as one linear chain and
-    replayed until the plan has stopped. A subclass sets `device` and `host`, names its entry point (`_entry`) and supplies
-    `_call(stream)` (the native call -> status code), `read_status()` and `_stopped(status)`."""
+    """What DEPlan, DEPlanU16, DEBatchPlan and DEBatchPlanU16 share: one native call per generation, `check_every` of them recorded as one
+    linear chain and replayed until the plan has stopped. A subclass sets `device` and `host` (through `_init_one` or `_init_batch`),
+    names its entry point (`_entry`) and supplies `_call(stream)` (the native call -> status code), `read_status()` and
+    `_stopped(status)`."""
     _entry = ""
     _graph = None
     _graph_len = 0
@@ -1808,6 +1809,70 @@ class _DEPlanBase:
             ws_bytes = nat.lib.hm_de_workspace_bytes(self.n_pixels, N, S)
         self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
 
+    def _init_batch(self, dn_stacks, std_stacks, exposures, mean_icrfs, pcas, lower_limits, upper_limits, populations, lower, upper, seeds,
+                    max_generations, mutation, recombination, tol, energy_limit, stack_of, n_rows, dn_dtype):
+        """The state of K problems of one shape on stacks of `dn_dtype` DNs with candidate rows of `n_rows` entries (DEBatchPlan: uint8,
+        256; DEBatchPlanU16: uint16, 2**bit_depth), the problem outermost in every state tensor."""
+        dn_stacks = list(dn_stacks)
+        if not dn_stacks:
+            raise ValueError("dn_stacks must hold at least one stack")
+        self.dn, self.std, t = _check_stacks(dn_stacks, std_stacks, exposures, batch=True, dn_dtype=dn_dtype)
+        dev = dn_stacks[0].device
+        self.device = dev
+        self.host = dev.type != "cuda"
+        N = dn_stacks[0].shape[2]
+        pop = np.ascontiguousarray(np.asarray(populations, dtype=np.float64))
+        if pop.ndim != 3:
+            raise ValueError("populations must be (K, S, P) in scaled coordinates [0, 1]")
+        K, S, P = pop.shape
+        if K < 1 or K > nat.HM_DE_MAX_PROBLEMS:
+            raise ValueError(f"a batch holds 1 to {nat.HM_DE_MAX_PROBLEMS} problems, got {K}")
+        if stack_of is None:
+            if len(dn_stacks) != K:
+                raise ValueError(f"{len(dn_stacks)} stacks for {K} problems: give stack_of, the stack index of every problem")
+            stack_of = range(K)
+        stack_of = [int(i) for i in stack_of]
+        if len(stack_of) != K or any(i < 0 or i >= len(dn_stacks) for i in stack_of):
+            raise ValueError(f"stack_of must hold {K} indices into the {len(dn_stacks)} stacks, got {stack_of}")
+        seeds = [int(s) for s in seeds]
+        if len(seeds) != K or len(mean_icrfs) != K or len(pcas) != K:
+            raise ValueError(f"seeds, mean_icrfs and pcas must hold one entry per problem ({K})")
+        self.K, self.S, self.P, self.N = K, S, P, N
+        self.stack_of = stack_of
+        self.n_pixels = dn_stacks[0].shape[0] * dn_stacks[0].shape[1]
+        means = [np.asarray(m, dtype=np.float64).reshape(-1) for m in mean_icrfs]
+        bases = [np.asarray(b, dtype=np.float64) for b in pcas]
+        if any(m.size != n_rows for m in means) or any(b.shape != (n_rows, P) for b in bases):
+            raise ValueError(f"every mean ICRF must have {n_rows} entries and every PCA basis must be ({n_rows}, {P})")
+        self.mean_icrf = _dev_f64(np.stack(means), dev)
+        self.pca = _dev_f64(np.stack(bases), dev)
+        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
+        self.population = torch.as_tensor(pop, device=dev).clone()
+        self.energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
+        self.trial = torch.zeros((K, S, P), dtype=_F64, device=dev)
+        self.trial_energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
+        self.icrf = torch.zeros((K, S, n_rows), dtype=_F64, device=dev)
+        self.valid = torch.zeros((K, S), dtype=_U8, device=dev)
+        self.status = torch.zeros((K, nat.HM_DE_STATUS_WORDS), dtype=torch.int64, device=dev)
+        self._t = (C.c_double * N)(*t.tolist())
+        self._dn = _ptr_array([self.dn[i] for i in stack_of])
+        self._sd = None if self.std is None else _ptr_array([self.std[i] for i in stack_of])
+        self._seeds = (C.c_int64 * K)(*[C.c_int64(s & 0xFFFFFFFFFFFFFFFF).value for s in seeds])
+        self._scalars = (int(lower), int(upper), int(S), int(P), int(max_generations), float(mutation[0]), float(mutation[1]),
+                         float(recombination), float(tol), float(energy_limit))
+        with nat.host_mode() if self.host else _NoDevice():
+            ws_bytes = nat.lib.hm_de_batch_workspace_bytes(self.n_pixels, N, S, K)
+        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+
+    def _batch_head(self):
+        """The leading arguments that hm_de_generation_batch and hm_de_generation_u16_batch share, up to energy_limit."""
+        lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
+        return (self.K, self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(), self.trial_energies.data_ptr(),
+                self.icrf.data_ptr(), self.valid.data_ptr(), self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(),
+                self.lo.data_ptr(), self.hi.data_ptr(), self._dn, self._sd, self._seeds, self._t, self.n_pixels, self.N, lower, upper, S, P,
+                max_gen, m_lo, m_hi, cr, tol, e_lim)
+
 
 class DEPlan(_DEPlanBase):
     """The state of one channel's differential-evolution solve (population, energies, trial rows, candidate ICRFs, verdicts, status block,
@@ -1849,7 +1914,7 @@ class DEPlanU16(_DEPlanBase):
     hm_linearity_energy_u16 with `variant` - the placement of a candidate's row, see linearity_energy; the result does not depend on
     it -, the select kernel); `run()` records and replays a linear chain as DEPlan does. The warm-up launch that precedes the recording
     is also where the energy entry raises its kernels' dynamic-LDS limit, which is host-side work that stays outside the capture.
-    One problem per plan: uint16 stacks have no batch entry."""
+    One problem per plan; DEBatchPlanU16 advances several such problems per launch."""
     _entry = "hm_de_generation_u16"
 
     def __init__(self, dn_stack: torch.Tensor, std_stack: Optional[torch.Tensor], exposures: Sequence[float], mean_icrf, pca,
@@ -1898,66 +1963,11 @@ class DEBatchPlan(_DEPlanBase):
                  mean_icrfs, pcas, lower_limits, upper_limits, populations, lower: int, upper: int, seeds: Sequence[int],
                  max_generations: int, mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0,
                  stack_of: Optional[Sequence[int]] = None):
-        dn_stacks = list(dn_stacks)
-        if not dn_stacks:
-            raise ValueError("dn_stacks must hold at least one stack")
-        self.dn, self.std, t = _check_stacks(dn_stacks, std_stacks, exposures, batch=True)
-        dev = dn_stacks[0].device
-        self.device = dev
-        self.host = dev.type != "cuda"
-        N = dn_stacks[0].shape[2]
-        pop = np.ascontiguousarray(np.asarray(populations, dtype=np.float64))
-        if pop.ndim != 3:
-            raise ValueError("populations must be (K, S, P) in scaled coordinates [0, 1]")
-        K, S, P = pop.shape
-        if K < 1 or K > nat.HM_DE_MAX_PROBLEMS:
-            raise ValueError(f"a batch holds 1 to {nat.HM_DE_MAX_PROBLEMS} problems, got {K}")
-        if stack_of is None:
-            if len(dn_stacks) != K:
-                raise ValueError(f"{len(dn_stacks)} stacks for {K} problems: give stack_of, the stack index of every problem")
-            stack_of = range(K)
-        stack_of = [int(i) for i in stack_of]
-        if len(stack_of) != K or any(i < 0 or i >= len(dn_stacks) for i in stack_of):
-            raise ValueError(f"stack_of must hold {K} indices into the {len(dn_stacks)} stacks, got {stack_of}")
-        seeds = [int(s) for s in seeds]
-        if len(seeds) != K or len(mean_icrfs) != K or len(pcas) != K:
-            raise ValueError(f"seeds, mean_icrfs and pcas must hold one entry per problem ({K})")
-        self.K, self.S, self.P, self.N = K, S, P, N
-        self.stack_of = stack_of
-        self.n_pixels = dn_stacks[0].shape[0] * dn_stacks[0].shape[1]
-        means = [np.asarray(m, dtype=np.float64).reshape(-1) for m in mean_icrfs]
-        bases = [np.asarray(b, dtype=np.float64) for b in pcas]
-        if any(m.size != BITS for m in means) or any(b.shape != (BITS, P) for b in bases):
-            raise ValueError(f"every mean ICRF must have {BITS} entries and every PCA basis must be ({BITS}, {P})")
-        self.mean_icrf = _dev_f64(np.stack(means), dev)
-        self.pca = _dev_f64(np.stack(bases), dev)
-        self.lo = _dev_f64(np.broadcast_to(np.asarray(lower_limits, dtype=np.float64), (P,)).copy(), dev)
-        self.hi = _dev_f64(np.broadcast_to(np.asarray(upper_limits, dtype=np.float64), (P,)).copy(), dev)
-        self.population = torch.as_tensor(pop, device=dev).clone()
-        self.energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
-        self.trial = torch.zeros((K, S, P), dtype=_F64, device=dev)
-        self.trial_energies = torch.full((K, S), float("inf"), dtype=_F64, device=dev)
-        self.icrf = torch.zeros((K, S, BITS), dtype=_F64, device=dev)
-        self.valid = torch.zeros((K, S), dtype=_U8, device=dev)
-        self.status = torch.zeros((K, nat.HM_DE_STATUS_WORDS), dtype=torch.int64, device=dev)
-        self._t = (C.c_double * N)(*t.tolist())
-        self._dn = _ptr_array([self.dn[i] for i in stack_of])
-        self._sd = None if self.std is None else _ptr_array([self.std[i] for i in stack_of])
-        self._seeds = (C.c_int64 * K)(*[C.c_int64(s & 0xFFFFFFFFFFFFFFFF).value for s in seeds])
-        self._scalars = (int(lower), int(upper), int(S), int(P), int(max_generations), float(mutation[0]), float(mutation[1]),
-                         float(recombination), float(tol), float(energy_limit))
-        with nat.host_mode() if self.host else _NoDevice():
-            ws_bytes = nat.lib.hm_de_batch_workspace_bytes(self.n_pixels, N, S, K)
-        self.workspace = torch.empty(max(1, ws_bytes // 8), dtype=_F64, device=dev)
+        self._init_batch(dn_stacks, std_stacks, exposures, mean_icrfs, pcas, lower_limits, upper_limits, populations, lower, upper, seeds,
+                         max_generations, mutation, recombination, tol, energy_limit, stack_of, BITS, _U8)
 
     def _call(self, stream):
-        lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim = self._scalars
-        return nat.lib.hm_de_generation_batch(self.K, self.population.data_ptr(), self.energies.data_ptr(), self.trial.data_ptr(),
-                                              self.trial_energies.data_ptr(), self.icrf.data_ptr(), self.valid.data_ptr(),
-                                              self.status.data_ptr(), self.mean_icrf.data_ptr(), self.pca.data_ptr(),
-                                              self.lo.data_ptr(), self.hi.data_ptr(), self._dn, self._sd, self._seeds, self._t,
-                                              self.n_pixels, self.N, lower, upper, S, P, max_gen, m_lo, m_hi, cr, tol, e_lim,
-                                              self.workspace.data_ptr(), stream)
+        return nat.lib.hm_de_generation_batch(*self._batch_head(), self.workspace.data_ptr(), stream)
 
     def read_status(self) -> list:
         """The K status blocks from ONE copy to the host (this synchronises): a list of DEPlan.read_status() dicts."""
@@ -1966,3 +1976,46 @@ class DEBatchPlan(_DEPlanBase):
 
     def _stopped(self, status: list) -> bool:
         return all(s["stop"] for s in status)
+
+
+class DEBatchPlanU16(_DEPlanBase):
+    """DEBatchPlan for a 9- to 16-bit camera: K problems on torch.uint16 (X, Y, N) stacks of one shape and ONE `bit_depth` (an int, or one
+    per stack - all equal), mean ICRFs of 2**bit_depth entries, PCA bases of (2**bit_depth, P), `lower` / `upper` DNs of that depth. The
+    state tensors are DEBatchPlan's with `icrf` of shape (K, S, 2**bit_depth). `launch()` enqueues ONE generation of every problem
+    (hm_de_generation_u16_batch: the row walk on (S, 1 | slabs, K) workgroups, the energy kernels on K x S candidates with `variant` -
+    the placement of a candidate's row, see linearity_energy; the result does not depend on it -, the select kernel on K workgroups).
+    Every problem evolves bit for bit as a DEPlanU16 with the same inputs would; a problem whose stop flag is set costs no further
+    work. `run()`, the graph recorded after the warm-up launch (which is also where the dynamic-LDS limit of the `variant` 1 kernels is
+    raised, outside the capture), `read_status()` (one copy) and the stop test (all flags) are DEBatchPlan's."""
+    _entry = "hm_de_generation_u16_batch"
+
+    def __init__(self, dn_stacks: Sequence[torch.Tensor], std_stacks: Optional[Sequence[Optional[torch.Tensor]]], exposures: Sequence[float],
+                 mean_icrfs, pcas, lower_limits, upper_limits, populations, lower: int, upper: int, seeds: Sequence[int],
+                 max_generations: int, mutation=(0.0, 1.95), recombination: float = 0.4, tol: float = 0.01, energy_limit: float = 0.0,
+                 stack_of: Optional[Sequence[int]] = None, bit_depth=None, variant: int = 0):
+        dn_stacks = list(dn_stacks)
+        if not dn_stacks:
+            raise ValueError("dn_stacks must hold at least one stack")
+        for s in dn_stacks:
+            if isinstance(s, torch.Tensor) and s.dtype != _U16:
+                raise TypeError(f"DEBatchPlanU16 takes torch.uint16 digital numbers, got {s.dtype}: uint8 stacks go to DEBatchPlan")
+        depths = list(bit_depth) if isinstance(bit_depth, (list, tuple)) else [bit_depth]
+        if len(depths) not in (1, len(dn_stacks)) or any(d != depths[0] for d in depths):
+            raise ValueError(f"the stacks of a batch must have one bit depth, got {depths} for {len(dn_stacks)} stacks")
+        self.bit_depth = _energy_bit_depth(dn_stacks[0], depths[0])
+        if self.bit_depth is None:                                                   # (not a tensor: _check_stacks raises the TypeError)
+            raise ValueError("DEBatchPlanU16 needs bit_depth (9..16): the number of rows of its candidate ICRFs")
+        n_rows = 2 ** self.bit_depth
+        if not (0 <= int(lower) < n_rows and 0 <= int(upper) < n_rows):
+            raise ValueError(f"lower and upper must be DNs in 0..{n_rows - 1} at bit_depth {self.bit_depth}, got {lower}, {upper}")
+        if int(variant) not in (0, 1, 2):
+            raise ValueError(f"variant must be 0 (the library's choice), 1 (LDS) or 2 (global memory), got {variant}")
+        self.variant = int(variant)
+        self._init_batch(dn_stacks, std_stacks, exposures, mean_icrfs, pcas, lower_limits, upper_limits, populations, lower, upper, seeds,
+                         max_generations, mutation, recombination, tol, energy_limit, stack_of, n_rows, _U16)
+
+    def _call(self, stream):
+        return nat.lib.hm_de_generation_u16_batch(*self._batch_head(), self.bit_depth, self.variant, self.workspace.data_ptr(), stream)
+
+    read_status = DEBatchPlan.read_status
+    _stopped = DEBatchPlan._stopped

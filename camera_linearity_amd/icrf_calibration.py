@@ -17,7 +17,8 @@ in ONE plan (hm_de_generation_batch, engine.DEBatchPlan): one set of launches pe
 for bit as it would alone.
 
 A 9- to 16-bit camera's torch.uint16 stacks have the device solver under names of their own, `solve_channel_u16` and `calibration_u16`
-(hm_de_generation_u16, engine.DEPlanU16: rows of 2**bit_depth entries, one problem per plan); `solve_channel` / `calibration` with a
+(hm_de_generation_u16, engine.DEPlanU16: rows of 2**bit_depth entries), and with `batched=True` the restarts of a channel or all channels
+and restarts of a calibration in ONE plan (hm_de_generation_u16_batch, engine.DEBatchPlanU16); `solve_channel` / `calibration` with a
 `bit_depth` stay on SciPy's solver.
 """
 from __future__ import annotations
@@ -29,6 +30,7 @@ import numpy as np
 import torch
 from scipy.optimize._differentialevolution import DifferentialEvolutionSolver   # same access as the reference (:7)
 
+from . import _native as nat
 from . import engine
 from . import settings as gs
 
@@ -190,9 +192,11 @@ def _initial_population(limits, x0, args, tol, popsize, extra) -> np.ndarray:
 
 
 def _solve_batch(means, pcas, stacks, std_stacks, stack_of, seeds, exposure_values, lower_PCA_limit, upper_PCA_limit, data_limits,
-                 energy_limit, max_iterations, popsize, check_every, graph, tol):
+                 energy_limit, max_iterations, popsize, check_every, graph, tol, bit_depth=None, variant=0):
     """K device solves of one shape in one engine.DEBatchPlan: problem k on stacks[stack_of[k]] with means[k], pcas[k], seeds[k] and
-    SciPy's Sobol population for seeds[k]. -> [(icrf, energy, iterations)] * K, each what solve_channel(solver="device") returns for it."""
+    SciPy's Sobol population for seeds[k]. -> [(icrf, energy, iterations)] * K, each what solve_channel(solver="device") returns for it.
+    bit_depth=b: torch.uint16 stacks of a b-bit camera in one engine.DEBatchPlanU16 (`variant`: the placement of a candidate's row), each
+    triple what solve_channel_u16 returns for it."""
     K = len(seeds)
     pcas = [np.asarray(b, dtype=np.float64) for b in pcas]
     n_params = {b.shape[1] for b in pcas}
@@ -208,12 +212,17 @@ def _solve_batch(means, pcas, stacks, std_stacks, stack_of, seeds, exposure_valu
     pops = []
     for k in range(K):
         c = stack_of[k]
-        args = (means[k], pcas[k], stacks[c], std_stacks[c], data_limits[0], data_limits[1], True, exposure_values)
+        args = (means[k], pcas[k], stacks[c], std_stacks[c], data_limits[0], data_limits[1], True, exposure_values) + \
+            (() if bit_depth is None else (bit_depth,))
         pops.append(_initial_population(limits, x0, args, tol, popsize, dict(vectorized=True, updating="deferred", **_seed_keyword(seeds[k]))))
     lo, hi = np.asarray(limits, dtype=np.float64).T
-    plan = _engine_for(stacks[0]).DEBatchPlan(stacks, std_stacks, _host(exposure_values), means, pcas, lo, hi, np.stack(pops), data_limits[0],
-                                              data_limits[1], [int(sd) for sd in seeds], 2 * int(max_iterations), (0.0, 1.95), 0.4, tol,
-                                              energy_limit, stack_of=stack_of)
+    eng = _engine_for(stacks[0])
+    plan_args = (stacks, std_stacks, _host(exposure_values), means, pcas, lo, hi, np.stack(pops), data_limits[0], data_limits[1],
+                 [int(sd) for sd in seeds], 2 * int(max_iterations), (0.0, 1.95), 0.4, tol, energy_limit)
+    if bit_depth is None:
+        plan = eng.DEBatchPlan(*plan_args, stack_of=stack_of)
+    else:
+        plan = eng.DEBatchPlanU16(*plan_args, stack_of=stack_of, bit_depth=bit_depth, variant=variant)
     sts = plan.run(check_every, graph)
     best = plan.population[torch.arange(K), torch.as_tensor([st["best_index"] for st in sts])].cpu().numpy()      # one copy for the K members
     return [(_inverse_camera_response_function(means[k], pcas[k], lo + best[k] * (hi - lo), True), sts[k]["best_energy"],
@@ -225,11 +234,12 @@ def _best_restart(results):
     return min(enumerate(results), key=lambda ir: (ir[1][1], ir[0]))[1]
 
 
-def _device_defaults():
+def _device_defaults(solve=None):
     """solve_channel's own defaults of check_every, graph and tol: what calibration()'s sequential path inherits by not passing them,
-    handed to the batched path from the same place, so the two stay array-equal if a default moves."""
+    handed to the batched path from the same place, so the two stay array-equal if a default moves. `solve`: another solve function to
+    read them from (calibration_u16: solve_channel_u16)."""
     import inspect
-    par = inspect.signature(solve_channel).parameters
+    par = inspect.signature(solve_channel if solve is None else solve).parameters
     return {name: par[name].default for name in ("check_every", "graph", "tol")}
 
 
@@ -339,13 +349,15 @@ def _data_limits_u16(data_limits, bit_depth: int):
 def solve_channel_u16(mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, exposure_values, lower_PCA_limit: float,
                       upper_PCA_limit: float, bit_depth: int, data_limits=None, energy_limit: float = 0.0, seed: int = 7,
                       max_iterations: int = 1000, popsize: int = 15, check_every: int = 8, graph: bool = True, tol: float = 0.01,
-                      restarts: int = 1, variant: int = 0):
+                      restarts: int = 1, variant: int = 0, batched: bool = False):
     """solve_channel(solver="device") for one channel of a 9- to 16-bit camera: a torch.uint16 stack, a mean ICRF of 2**bit_depth entries
     and a PCA basis of (2**bit_depth, P). The generations run on the stack's backend (engine.DEPlanU16, hm_de_generation_u16) from SciPy's
     Sobol population for `seed`, with the 8-bit device solver's strategy, settings and random numbers. `data_limits` are DNs of the stack's
     depth (default: the 8-bit limits shifted to it); `variant` places a candidate's row for the energy stage (engine.linearity_energy) and
     does not change the result. restarts=R > 1: R plans one after another, restart r seeded restart_seed(seed, r) - restart 0 is the
-    restarts=1 solve -, the one with the lowest final energy returned (ties: the lowest r); there is no batch entry for uint16 stacks.
+    restarts=1 solve -, the one with the lowest final energy returned (ties: the lowest r). batched=True runs the R restarts as ONE
+    engine.DEBatchPlanU16 on the shared stack (hm_de_generation_u16_batch: one set of launches per generation for all of them, each
+    evolving bit for bit as it would alone): the same return value, as arrays and floats.
     -> (ICRF of the channel (2**bit_depth,), final energy, iterations)."""
     bit_depth = engine._check_bit_depth(bit_depth)
     restarts = int(restarts)
@@ -355,6 +367,11 @@ def solve_channel_u16(mean_ICRF_array, PCA_array, image_value_stack, image_std_s
         raise TypeError("solve_channel_u16 needs an integer seed")
     PCA_array = np.asarray(PCA_array, dtype=np.float64)
     data_limits = _data_limits_u16(data_limits, bit_depth)
+    if batched:
+        return _best_restart(_solve_batch([mean_ICRF_array] * restarts, [PCA_array] * restarts, [image_value_stack], [image_std_stack],
+                                          [0] * restarts, [restart_seed(seed, r) for r in range(restarts)], exposure_values,
+                                          lower_PCA_limit, upper_PCA_limit, data_limits, energy_limit, max_iterations, popsize,
+                                          check_every, graph, tol, bit_depth=bit_depth, variant=variant))
     limits, x0 = _pca_limits(PCA_array.shape[1], lower_PCA_limit, upper_PCA_limit)
     lo, hi = np.asarray(limits, dtype=np.float64).T
     args = (mean_ICRF_array, PCA_array, image_value_stack, image_std_stack, data_limits[0], data_limits[1], True, exposure_values, bit_depth)
@@ -374,21 +391,45 @@ def solve_channel_u16(mean_ICRF_array, PCA_array, image_value_stack, image_std_s
 
 def calibration_u16(mean_ICRFs: Sequence, PCA_arrays: Sequence, channel_image_value_stacks, channel_image_std_stacks, exposure_values,
                     lower_PCA_limit: float, upper_PCA_limit: float, bit_depth: int, data_limits=None, energy_limit: float = 0.0,
-                    rng_seed: int = 7, max_iterations: int = 1000, popsize: int = 15, restarts: int = 1, variant: int = 0):
+                    rng_seed: int = 7, max_iterations: int = 1000, popsize: int = 15, restarts: int = 1, variant: int = 0,
+                    batched: bool = False):
     """calibration(..., bit_depth=b) with the device solver: torch.uint16 channel stacks of a b-bit camera (initialize_channel_image_stacks(
     ..., bit_depth=b)), every channel solved by solve_channel_u16 (seed rng_seed + c), one after another. The mean ICRFs are required: the
     power-law base needs calibration(..., bit_depth=b) on SciPy's solver.
+    batched=True solves all C x `restarts` problems as one engine.DEBatchPlanU16 - channel c's restart r seeded restart_seed(rng_seed + c, r),
+    the best restart kept per channel; more than 64 problems go in consecutive batches of at most 64. It needs channel stacks of one shape
+    and the same number of PCA components for every channel (ValueError otherwise, never a sequential fallback); the result is array-equal
+    to the sequential one.
     -> (ICRF (2**b, C): what engine.merge(..., bit_depth=b) takes, final energies (C,))."""
     bit_depth = engine._check_bit_depth(bit_depth)
     C = len(channel_image_value_stacks)
     if mean_ICRFs is None or len(mean_ICRFs) != C or any(m is None for m in mean_ICRFs):
         raise ValueError("calibration_u16 needs the mean ICRF of every channel: the device solver forms candidates from a mean ICRF only")
     results, energies = [], np.zeros(C)
-    for c in range(C):
-        icrf_c, energies[c], _ = solve_channel_u16(mean_ICRFs[c], PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
-                                                   exposure_values, lower_PCA_limit, upper_PCA_limit, bit_depth, data_limits, energy_limit,
-                                                   rng_seed + c, max_iterations, popsize, restarts=restarts, variant=variant)
-        results.append(icrf_c)
+    if batched:
+        restarts = int(restarts)
+        if restarts < 1:
+            raise ValueError(f"restarts must be >= 1, got {restarts}")
+        n_params =[np.shape(b)[1] for b in PCA_arrays]
+        if len(set(n_params)) != 1:                                              # (before the batches are cut: one of them might hold one channel only)
+            raise ValueError(f"a batched solve needs the same number of PCA components for every problem, got {n_params}")
+        idx = [(c, r) for c in range(C) for r in range(restarts)]
+        solved = []
+        for first in range(0, len(idx), nat.HM_DE_MAX_PROBLEMS):
+            part = idx[first:first + nat.HM_DE_MAX_PROBLEMS]
+            solved += _solve_batch([mean_ICRFs[c] for c, _ in part], [PCA_arrays[c] for c, _ in part], list(channel_image_value_stacks),
+                                   list(channel_image_std_stacks), [c for c, _ in part], [restart_seed(rng_seed + c, r) for c, r in part],
+                                   exposure_values, lower_PCA_limit, upper_PCA_limit, _data_limits_u16(data_limits, bit_depth), energy_limit,
+                                   max_iterations, popsize, **_device_defaults(solve_channel_u16), bit_depth=bit_depth, variant=variant)
+        for c in range(C):
+            icrf_c, energies[c], _ = _best_restart(solved[c * restarts:(c + 1) * restarts])
+            results.append(icrf_c)
+    else:
+        for c in range(C):
+            icrf_c, energies[c], _ = solve_channel_u16(mean_ICRFs[c], PCA_arrays[c], channel_image_value_stacks[c], channel_image_std_stacks[c],
+                                                       exposure_values, lower_PCA_limit, upper_PCA_limit, bit_depth, data_limits, energy_limit,
+                                                       rng_seed + c, max_iterations, popsize, restarts=restarts, variant=variant)
+            results.append(icrf_c)
     ICRF = np.stack(results, axis=1)
     ICRF += (1 - ICRF[-1, :])[None, :]                                           # :390
     ICRF[0, :] = 0                                                               # :391

@@ -48,7 +48,8 @@ extern "C" {
  *    the table size of the 8-bit entry points only), and by hm_merge_u16_darks* (uint16 dark maps for those frames), and by
  *    hm_linearity_energy_u16*, hm_welford_*_u16* and hm_noise_moments_* (the calibration energy, the mean / std producer and the per-DN STD
  *    table for those frames), and by hm_merge_u16_std_table* (that table inside the merge of those frames), and by
- *    hm_de_generation_u16 (the differential-evolution generation on those stacks).       */
+ *    hm_de_generation_u16 (the differential-evolution generation on those stacks), and by hm_de_generation_u16_batch (several such
+ *    problems per call).                                                                  */
 #define HM_ABI_VERSION 2
 #define HM_BITS 256
 #define HM_MAX_FRAMES 32     /* frames per merge LAUNCH; hm_merge takes any number of frames (32 per launch, see frames_workspace) */
@@ -869,7 +870,7 @@ int hm_de_generation(double* population, double* energies, double* trial, double
  * Statuses, an earlier one winning, all before any launch: hm_de_generation's in its order (but for its limit rule); HM_EINVAL for
  * bit_depth outside 9..16 or variant outside 0..2; HM_EINVAL for a limit outside 0 .. R - 1; HM_EUNSUPPORTED for variant 1 where the row
  * does not fit LDS (15 and 16 bits); HM_EALIGN for a dn that is not 2-byte aligned; (device build) HM_EINVAL for a NULL workspace.
- * One problem per call: there is no batch entry for uint16 stacks. */
+ * One problem per call; hm_de_generation_u16_batch below advances several such problems per call. */
 int hm_de_generation_u16(double* population, double* energies, double* trial, double* trial_energies,
                          double* icrf /*(S, 2^bit_depth)*/, uint8_t* valid, int64_t* status,
                          const double* mean_icrf /*(2^b)*/, const double* pca /*(2^b, P) row-major*/,
@@ -920,6 +921,37 @@ int hm_de_generation_batch(int n_problems, double* population, double* energies,
                            const double* exposures /*[host]*/, int64_t n_pixels, int n_frames, int lower, int upper,
                            int pop_size, int n_params, int64_t max_generations, double mutation_lo, double mutation_hi,
                            double recombination, double tol, double energy_limit, void* workspace, void* stream);
+
+/* ... for n_problems problems on uint16 DN stacks of ONE shape and ONE bit depth (9..16): hm_de_generation_batch's text with rows of
+ * R = 2^bit_depth entries in place of 256. Specification: problem k evolves exactly as hm_de_generation_u16 would evolve it alone with
+ * the same inputs, seeds[k], bit_depth and variant - BIT FOR BIT, in every state array and every status word, after every call.
+ *   state      contiguous with the problem outermost: population (K, S, P), energies (K, S), trial (K, S, P), trial_energies (K, S),
+ *              icrf (K, S, R), valid (K, S), status (K, HM_DE_STATUS_WORDS) zeroed before generation 0; mean_icrf (K, R), pca (K, R, P)
+ *   dn, std, seeds   HOST arrays of n_problems entries that travel in the kernel arguments (a recorded graph holds them by value): device
+ *              pointers to the uint16 (n_pixels, n_frames) stacks, 2-byte aligned (problems may name the same stack); std NULL or
+ *              given for ALL problems; random numbers depend on (seeds[k], generation, member, draw) only
+ *   stop       each problem has its own stop flag. Once it is set no kernel of a later call stores anything for that problem - the row
+ *              walk, the verdict kernel, the energy kernels (its workgroups return before the row fill) and the selection included
+ *   energy     the launch geometry (pixel- or pair-major, the chunk count) and, with variant 0, the row's placement are chosen as
+ *              hm_linearity_energy_u16 chooses them for pop_size candidates on n_pixels pixels - per problem, never from K x S
+ *   workspace  hm_de_batch_workspace_bytes(n_pixels, n_frames, pop_size, n_problems) bytes: the 8-bit batch's function (K times
+ *              hm_de_workspace_bytes, which does not depend on the depth; 0 for arguments the call would reject)
+ * One linear chain of launches on one stream; no allocation, no host synchronisation, no atomics of any kind.
+ * Statuses, an earlier one winning, all before any launch and before any device pointer is read: hm_de_generation_batch's in its order
+ * (but for its 8-bit limit rule) - HM_EINVAL for n_problems < 1, HM_ESHAPE for n_problems > HM_DE_MAX_PROBLEMS, the counts and shapes,
+ * HM_EUNSUPPORTED for n_problems * pop_size > 65535, the ranges, HM_EINVAL for a NULL array or a NULL entry of dn / std; then
+ * hm_de_generation_u16's additions - HM_EINVAL for bit_depth outside 9..16, variant outside 0..2 or a limit outside 0 .. R - 1,
+ * HM_EUNSUPPORTED for variant 1 where the row does not fit LDS; HM_EALIGN for a dn[k] that is not 2-byte aligned; (device build)
+ * HM_EINVAL for a NULL workspace. */
+int hm_de_generation_u16_batch(int n_problems, double* population, double* energies, double* trial, double* trial_energies,
+                               double* icrf /*(K, S, 2^bit_depth)*/, uint8_t* valid, int64_t* status,
+                               const double* mean_icrf /*(K, 2^b)*/, const double* pca /*(K, 2^b, P)*/,
+                               const double* lower_limits, const double* upper_limits, const uint16_t* const* dn /*[host]*/,
+                               const double* const* std /*[host], nullable*/, const int64_t* seeds /*[host]*/,
+                               const double* exposures /*[host]*/, int64_t n_pixels, int n_frames, int lower, int upper,
+                               int pop_size, int n_params, int64_t max_generations, double mutation_lo, double mutation_hi,
+                               double recombination, double tol, double energy_limit, int bit_depth, int variant,
+                               void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * On-disk formats: host-side strip decoders for the TIFF files the reference exchanges with

@@ -16,7 +16,16 @@ k_de_trial_u16's average duration next to the energy and select kernels' (one JS
 missing or fails - the timings above do not depend on it). The driver ends with a summary line of the ratios.
 --step solve --modes device-graph[,...] --sizes N --depths B runs one child's work for those modes alone (how two builds of the library
 were compared: HDRMERGE_LIB names the other one).
-Options: --generations G (400), --repeats R (5), --check-every K (8), --sizes 28,256, --depths 10,12,16, --scipy-budget S (60), --trace DIR."""
+Options: --generations G (400), --repeats R (5), --check-every K (8), --sizes 28,256, --depths 10,12,16, --scipy-budget S (60), --trace DIR.
+
+--problems K[,K...] measures the batched plan instead, by tools/bench_de.py --problems' protocol: for every (stack, depth) ONE child process
+times, for every K, an engine.DEBatchPlanU16 of K problems (3 channel stacks, problem k on stack k mod 3 with seed 7 + k) next to K
+engine.DEPlanU16 plans of the same problems replayed one after another - HIP events around the graph replays of --generations generations,
+the two sides alternating region by region, median of --repeats regions after one dropped warm-up region each, never stopping (tol = 0, no
+generation limit). Afterwards every state array and status block of the two sides is compared as bytes. One JSON line per (stack, depth, K):
+batch_us_per_generation (one batched generation of all K problems), sequential_us_per_generation (one generation of each of the K single
+plans in turn), their spreads over the regions, sequential_over_batch, and batch_within_margin (batch <= sequential (1 + margin), margin
+the larger of 4 % and the sequential regions' min-max spread)."""
 import csv
 import json
 import pathlib
@@ -109,6 +118,62 @@ def solve_step(side, depth, generations, repeats, check_every, scipy_budget):
         print(json.dumps(res), flush=True)
 
 
+def batch_step(side, depth, counts, generations, repeats, check_every):
+    """--problems: an engine.DEBatchPlanU16 of K problems next to K engine.DEPlanU16 plans replayed one after another, in this process,
+    the two sides alternating region by region (tools/bench_de.py --problems' protocol at depth `depth`)."""
+    import numpy as np
+    import torch
+    from scipy.stats import qmc
+    from camera_linearity_amd import engine
+    replays = max(1, generations // check_every)
+    gens = replays * check_every
+
+    def region(graphs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for g in graphs:                                          # one plan after another, as K sequential solves run
+            for _ in range(replays):
+                g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / gens
+    channels = [problem(side, depth, seed=21 + c) for c in range(3)]
+    mean_icrf, pca, _, t, limits = channels[0]
+    stacks = [c[2] for c in channels]
+    for K in counts:
+        pops = np.stack([qmc.Sobol(P, seed=7 + k).random(S) for k in range(K)])
+        stack_of = [k % 3 for k in range(K)]
+        seeds = [7 + k for k in range(K)]
+        batch = engine.DEBatchPlanU16(stacks, None, t, [mean_icrf] * K, [pca] * K, -1.0, 1.0, pops, limits[0], limits[1], seeds, 1 << 40, tol=0.0,
+                                      stack_of=stack_of, bit_depth=depth)
+        singles = [engine.DEPlanU16(stacks[stack_of[k]], None, t, mean_icrf, pca, -1.0, 1.0, pops[k], limits[0], limits[1], seeds[k], 1 << 40,
+                                    tol=0.0, bit_depth=depth) for k in range(K)]
+        for pl in [batch] + singles:
+            pl._record(check_every)
+        seq, bat = [], []
+        for _ in range(repeats + 1):                              # alternating; the first region of either side warms up and is dropped
+            seq.append(region([pl._graph for pl in singles]))
+            bat.append(region([batch._graph]))
+        seq, bat = seq[1:], bat[1:]
+        torch.cuda.synchronize()
+        # the same generations ran on both sides: the states must be the same bytes (reported in the line, and the run ends if they are not)
+        differ = [(k, name) for k in range(K) for name in ("population", "energies", "trial", "trial_energies", "icrf", "valid", "status")
+                  if not torch.equal(getattr(batch, name)[k].view(torch.uint8), getattr(singles[k], name).view(torch.uint8))]
+        b, q = statistics.median(bat), statistics.median(seq)
+        margin = max(0.04, (max(seq) - min(seq)) / q)
+        print(json.dumps({"step": "batch", "stack": [side, side, 7], "bit_depth": depth, "problems": K, "population": S, "params": P,
+                          "generations": gens, "check_every": check_every, "repeats": repeats,
+                          "batch_us_per_generation": round(b, 2), "batch_us_spread": [round(min(bat), 2), round(max(bat), 2)],
+                          "sequential_us_per_generation": round(q, 2), "sequential_us_spread": [round(min(seq), 2), round(max(seq), 2)],
+                          "sequential_over_batch": round(q / b, 3), "margin": round(margin, 4),
+                          "batch_within_margin": bool(b <= q * (1 + margin)), "states_equal": not differ,
+                          "device": torch.cuda.get_device_name(0)}), flush=True)
+        if differ:
+            sys.exit(f"batch and single plans differ: {differ}")
+        del batch, singles
+        torch.cuda.empty_cache()
+
+
 def kernels_step(side, depth, generations):
     """the launches a kernel trace is taken of: `generations` eager generations of one plan"""
     import torch
@@ -146,8 +211,22 @@ def main():
         sys.path.insert(0, str(ROOT))
         if opt("--step", "") == "kernels":
             kernels_step(sizes[0], depths[0], generations)
+        elif opt("--step", "") == "batch":
+            batch_step(sizes[0], depths[0], [int(k) for k in opt("--problems", "1").split(",")], generations, repeats, check_every)
         else:
             solve_step(sizes[0], depths[0], generations, repeats, check_every, budget)
+        return
+    if "--problems" in sys.argv:                                  # one child per (stack, depth) for all problem counts, under its own time limit
+        for side in sizes:
+            for depth in depths:
+                cmd = ["timeout", "-k", "10", "300", sys.executable, str(pathlib.Path(__file__).resolve()), "--step", "batch", "--problems",
+                       opt("--problems", "1"), "--sizes", str(side), "--depths", str(depth), "--generations", str(generations),
+                       "--repeats", str(repeats), "--check-every", str(check_every)]
+                p = subprocess.run(cmd)
+                if p.returncode != 0:                             # stop at the first failure: start nothing more on the GPU
+                    print(json.dumps({"tool": "bench_de_u16", "failed_step": "batch", "stack_side": side, "bit_depth": depth,
+                                      "exit_status": p.returncode}))
+                    sys.exit(p.returncode)
         return
     results = []
     for side in sizes:

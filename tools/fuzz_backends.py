@@ -871,6 +871,48 @@ def case_de_batch(rng):
     return desc
 
 
+def case_de_u16_batch(rng):
+    """hm_de_generation_u16_batch against hm_de_generation_u16: case_de_batch on uint16 stacks of 9 to 16 bits (every depth: each U of the
+    row walk, the slab grids from 14 bits) with a random placement of the candidate's row, on BOTH builds - within a build every state
+    array and status word of problem k must equal its single plan's bit for bit after a few generations."""
+    depth = int(rng.integers(9, 17))
+    n = 2 ** depth
+    K, S, P = int(rng.integers(1, 5)), int(rng.choice([4, 5, 8, 13, 32])), int(rng.integers(1, 6))
+    X, Y = (int(rng.integers(1, 40)), int(rng.integers(1, 40))) if rng.random() < 0.8 else (130, int(rng.integers(126, 140)))   # around 16 384 pixels
+    N = int(rng.choice([2, 3, 5, 7, 8, 9, 12]))
+    variant = int(rng.choice([0, 1, 2] if depth <= 14 else [0, 2]))
+    n_stacks = int(rng.integers(1, K + 1))
+    stack_of = [int(c) for c in rng.permutation(np.concatenate([np.arange(n_stacks), rng.integers(0, n_stacks, K - n_stacks)]))]
+    dns = [np.sort(rng.integers(0, n, (X, Y, N)), axis=2).astype(np.uint16) for _ in range(n_stacks)]
+    sds = [0.004 * (1 + rng.random((X, Y, N))) for _ in range(n_stacks)] if rng.random() < 0.4 else None
+    t = np.sort(rng.uniform(1e-3, 1.0, size=N)) + np.arange(N) * 1e-4
+    xs = np.linspace(0, 1, n)
+    means = [0.5 * xs + 0.5 * xs ** rng.uniform(1.2, 2.5) for _ in range(K)]            # (a first step well above the rows' rounding at 16 bits)
+    pcas = [np.stack([np.sin(np.pi * (m + 1) * xs) / (m + 1) for m in range(P)], axis=1) * rng.uniform(0.02, 0.15) for _ in range(K)]
+    pop = rng.random((K, S, P))
+    pop[:, ::2] = 0.5 + 0.3 * (pop[:, ::2] - 0.5)                                     # half of the members near the mean ICRF: valid rows
+    seeds = [int(x) for x in rng.integers(-2 ** 62, 2 ** 62, K)]
+    gens, max_gen = int(rng.integers(1, 7)), int(rng.choice([2, 3, 100]))
+    tol = float(rng.choice([0.0, 0.01, 10.0]))
+    lower, upper = int(rng.integers(0, n // 6)), int(rng.integers(n - n // 5, n))
+    desc = (f"de_u16_batch bits={depth} K={K} S={S} P={P} {X}x{Y}x{N} stacks={stack_of} std={sds is not None} variant={variant} gens={gens} "
+            f"max={max_gen} tol={tol}")
+    for name, eng, up in (("device", engine, D), ("host", heng, Hh)):
+        st, sd = [up(a) for a in dns], None if sds is None else [up(a) for a in sds]
+        batch = eng.DEBatchPlanU16(st, sd, t, means, pcas, -1.0, 1.0, pop, lower, upper, seeds, max_gen, tol=tol, stack_of=stack_of,
+                                   bit_depth=depth, variant=variant)
+        singles = [eng.DEPlanU16(st[c], None if sd is None else sd[c], t, means[k], pcas[k], -1.0, 1.0, pop[k], lower, upper, seeds[k], max_gen,
+                                 tol=tol, bit_depth=depth, variant=variant) for k, c in enumerate(stack_of)]
+        for _ in range(gens + 1):
+            batch.launch()
+            for pl in singles:
+                pl.launch()
+        for k, pl in enumerate(singles):
+            for what in ("population", "energies", "trial", "trial_energies", "icrf", "valid", "status"):
+                compare(f"{name} problem {k} {what}", getattr(batch, what)[k], getattr(pl, what), None)
+    return desc
+
+
 def case_pairs_hist(rng):
     """engine.pairs_histogram (hm_pairs_histogram / hm_pairs_minmax) on both builds: thresholds as read, channel subsets, given and default
     ranges, bin counts on both sides of the pairs-per-launch splits. Unweighted counts and all edges must be equal; a weighted bin of k_b
@@ -1236,7 +1278,7 @@ def case_linearize_u16(rng):
 
 
 CASES = [(case_merge, 5), (case_merge_std_table, 3), (case_merge_std_f32, 3), (case_merge_u16, 3), (case_merge_u16_darks, 3), (case_merge_u16_std_table, 3), (case_linearize_u16, 1), (case_binary, 3), (case_unary, 1), (case_stats, 3), (case_pair, 2), (case_linearize, 2), (case_corrections, 2),
-         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_pairs_hist, 2), (case_pairs_hist_dn, 2)]
+         (case_hist_extract, 2), (case_linearity, 2), (case_welford, 2), (case_welford_u16, 2), (case_noise_moments, 2), (case_energy, 2), (case_energy_u16, 2), (case_series, 2), (case_kde, 2), (case_de_batch, 2), (case_de_u16_batch, 2), (case_pairs_hist, 2), (case_pairs_hist_dn, 2)]
 if args.only:
     CASES = [(f, w) for f, w in CASES if f.__name__ in args.only.split(",")]
     assert CASES, f"--only {args.only}: no such generator"
